@@ -12,6 +12,7 @@ Contract (one JSON line on rank 0):
              same workload, one host core, rank 0, N = 1 only.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3] [--no-cpu] [--mode sharded|replicas]
+  [--dump-outputs DIR]
 N > 1: one rank per GPU.  Under torch.distributed.run (RANK / WORLD_SIZE in the environment) this process IS a rank;
 without a launcher `python bench.py --gpus N` starts the N ranks itself -- fresh child processes, spawned before this
 process has imported torch or touched the GPU; the parent only relays rank 0's JSON line.  MISSLAP_DIST_BACKEND=gloo lets
@@ -238,8 +239,7 @@ def run_concurrent(B, steps, make_solver, edges_per_solve, want_sha, digest):
     n = B * steps
     return {"B": B, "solves": n, "wall_ms": round(1e3 * wall, 3), "ms_per_solve": round(1e3 * wall / n, 3),
             "aggregate_medges_s": round(edges_per_solve * n / wall / 1e6, 2),
-            "all_sha256_equal_reference_run": all(d == want_sha for d in shas) and len(shas) == n,
-            "hw_queues_env": os.environ.get("GPU_MAX_HW_QUEUES")}
+            "all_sha256_equal_reference_run": all(d == want_sha for d in shas) and len(shas) == n}
 
 
 def run_batch(B, group, steps, make_solver, edges_per_solve, want_sha, digest):
@@ -267,6 +267,18 @@ def run_batch(B, group, steps, make_solver, edges_per_solve, want_sha, digest):
             "calls_recorded": infos[-1]["calls_recorded"], "launches_issued": infos[-1]["launches_issued"],
             "host_ms_summed_over_groups": infos[-1]["host_ms"],
             "all_sha256_equal_reference_run": all(d == want_sha for d in shas) and len(shas) == n}
+
+
+def dump_outputs(out_dir, sol, meta, gpu):
+    """--dump-outputs: the assignment (person -> object; C5, the largest config: 1M rows, 8 MB) and every numeric field of
+    the solver's `meta` (what auction_solve returns), plus the f64 objective, each as <out_dir>/<name>.npy in float64.
+    The inputs come from a fixed seed, so two builds run with the same arguments can be compared file by file."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    out = {"sol": sol, "obj_f64": gpu["obj_f64"]}
+    out.update((k, v) for k, v in meta.items() if isinstance(v, (int, float)))
+    for k, v in out.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.asarray(v, dtype=np.float64))
 
 
 def source_digest():
@@ -324,20 +336,16 @@ def main():
                     help="N > 1: 'sharded' = ONE problem, persons of the big rounds sharded over the ranks, RCCL "
                          "exchange (strong scaling; the default); 'replicas' = N independent problems, one per GPU, "
                          "no collective (weak scaling: how independent LAPs -- the reference's typical use -- scale)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller (the assignment "
+                         "and the solver's result fields) as DIR/<name>.npy, float64; rank 0 only")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     backend = os.environ.get("MISSLAP_DIST_BACKEND", "nccl")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and backend != "threads":
         launch_ranks(args.gpus, sys.argv[1:])  # does not return
-    if args.batch > 1:
-        os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")  # (a queue per group of the batched solve)
-    if args.concurrent > 1:
-        # hardware queues for the concurrent streams (the runtime's default is 4 per process: streams beyond that
-        # share a queue and their kernels serialise -- C3, 16 at a time: 2.8x the single-solve throughput with 4 queues,
-        # 4.8x with 16, 6.4x with 32); must be in the environment before the HIP runtime starts
-        os.environ.setdefault("GPU_MAX_HW_QUEUES", str(min(max(2 * args.concurrent, 4), 32)))
-    if backend == "threads" and args.gpus > 1:
-        os.environ.setdefault("GPU_MAX_HW_QUEUES", str(min(max(2 * args.gpus, 4), 32)))  # a queue per rank thread
 
     import numpy as np
     import torch
@@ -476,6 +484,8 @@ def run_rank(args, rank, world, local_rank, ranks, comm, shared, backend):
         runs.append((dict(s.meta), dict(s.gpu)))
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, sol, *runs[-1])
     if replicas:
         dt = ranks.max_f(dt)
         edges_all = ranks.sum_i(sum(g["edges_scanned"] for _, g in runs))  # N independent solves: every rank's edges are unique work

@@ -105,7 +105,10 @@ def _worker(rank, world, port, spec, prob, max_iter, shard_min_K, out):
     comm = host_gloo_comm(rank, world, exchanges)
     sol, calls = drive_with_c_loop(b, comm)
     out.put((rank, sol.tolist(), b.its, b.nreductions, b.p.tobytes(), len(exchanges), calls.count("round_bid")))
-    dist.barrier()
+    # the barrier before teardown, as a host all-reduce: dist.barrier() looks for an accelerator, which initialises the
+    # HIP runtime -- on a GPU box every rank of this CPU test would open the GPU
+    import torch
+    dist.all_reduce(torch.zeros(1))
     dist.destroy_process_group()
 
 
