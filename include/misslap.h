@@ -318,6 +318,41 @@ int misslap_drive_sharded(const misslap_round_ops *ops, misslap_comm *comm);
 int misslap_get_state(misslap_solver *h, double *prices, int32_t *unassigned, int32_t *person_to_object,
                       int32_t *object_to_person);
 
+/* ---- warm-started re-solve (no counterpart in the reference, whose AuctionSolver starts every solve from zero prices,
+ * auction_.pyx:220).  The auction may start from any prices with every person unassigned: a problem whose costs drifted a
+ * little is re-solved from the prices of the last solve with a small eps, on the handle that already holds its graph
+ * (no second create, no second feasibility guard).  Prices are those of the MAXIMISED problem, i.e. for 'min' the prices
+ * of the negated costs, in and out alike.  Single-GPU handles only (world == 1; sharded handles: MISSLAP_ERR_STATE).
+ *
+ * The current prices, n_cols doubles, into host memory or (out_on_device != 0) device memory. */
+int misslap_get_prices(misslap_solver *h, double *out, int32_t out_on_device);
+/* New values for the handle's entries, in the order of the create-time `loc` and in the caller's sign (the library
+ * negates for 'min' on the device; the caller's buffer is never written).  Sparsity and stored order do not change.
+ * on_device: `val` is a device pointer, produced on `input_stream` (NULL: the library waits for the whole device first).
+ * *max_abs_change (may be NULL) receives max |new - old|: the natural eps_start of the next misslap_resolve (prices that
+ * satisfied eps-CS for the old values satisfy (eps + 2 delta)-CS for the old assignment under the new ones).
+ * All or nothing: NaN / infinity, a wrong nnz, or -- on a handle that keeps 8 B/edge fp32 values because its values at
+ * create were all fp32-exact -- a value that is not exact in fp32 is MISSLAP_ERR_INVALID and leaves the handle's values
+ * unchanged (create with options.force_f64_values = 1 to update with arbitrary doubles).  Every layout that carries a
+ * value is rewritten (row-major edges, the tile-major copy), the candidate lines are invalidated, and what create derived
+ * from max|val| is derived again.  On a handle on which no round has run since create or the last resolve, the next
+ * misslap_solve starts from the eps0 of the new values. */
+int misslap_update_values(misslap_solver *h, const double *val, int64_t nnz, int32_t on_device, void *input_stream,
+                          double *max_abs_change);
+/* The same for a handle made by misslap_create_dense: mat is double[n_rows][n_cols] with the shape given at create.  Its
+ * v >= 0 pattern must be the handle's: as many valid entries in every row, and every stored entry still valid (otherwise
+ * MISSLAP_ERR_INVALID, the handle unchanged). */
+int misslap_update_dense(misslap_solver *h, const double *mat, int32_t on_device, void *input_stream,
+                         double *max_abs_change);
+/* Solve again, on a created or a solved handle, starting from `prices` (n_cols doubles, host or device memory; NULL: the
+ * handle's current prices) with every person unassigned, its = nreductions = 0, eps0 = eps_start if eps_start > 0, else
+ * C / 2 with C = max |val| of the current values (auction_.pyx:241-249), and the same theta and target eps = 1 / N.  The
+ * result is what the reference's solve() returns when its prices start at `prices` instead of zeros, bit for bit.  Prices
+ * must be finite and >= 0 with the sign bit clear (bids are ordered by their bit patterns, the numeric order of non-negative
+ * doubles only): checked on the device before anything is reset, MISSLAP_ERR_INVALID otherwise.  Outputs as misslap_solve. */
+int misslap_resolve(misslap_solver *h, const double *prices, int32_t prices_on_device, float eps_start,
+                    int32_t *person_to_object_out, misslap_meta *meta);
+
 /* Device properties of the GPU the handle runs on (name buffer >= 128 bytes). */
 int misslap_device_info(int32_t device, char *name, int32_t name_len, int32_t *compute_units,
                         int64_t *hbm_bytes);

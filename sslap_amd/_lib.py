@@ -135,6 +135,10 @@ SYMBOLS = {
     "misslap_matching_gpu": (C.c_int, [_VP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _I32P, _VP, _VP, _I32P]),
     "misslap_trim_caches": (C.c_int, [C.POINTER(C.c_int64)]),
     "misslap_set_cache_limits": (C.c_int, [C.c_int64, C.c_int64, C.c_int32]),
+    "misslap_get_prices": (C.c_int, [_VP, _VP, C.c_int32]),
+    "misslap_update_values": (C.c_int, [_VP, _VP, C.c_int64, C.c_int32, _VP, C.POINTER(C.c_double)]),
+    "misslap_update_dense": (C.c_int, [_VP, _VP, C.c_int32, _VP, C.POINTER(C.c_double)]),
+    "misslap_resolve": (C.c_int, [_VP, _VP, C.c_int32, C.c_float, _VP, C.POINTER(Meta)]),
     "misslap_last_error": (C.c_char_p, []),
     "misslap_abi_version": (C.c_int, []),
 }

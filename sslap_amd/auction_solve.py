@@ -202,7 +202,8 @@ class AuctionSolver:
         return sol
 
     def _fill_meta(self, m):
-        # auction_.pyx:297-304
+        # auction_.pyx:297-304 (and :264: the eps0 of this solve -- after update_values or resolve not that of create)
+        self.meta["start_eps"] = round(float(m.start_eps), 3)
         self.meta["eCE"] = int(m.eCE)
         self.meta["its"] = int(m.its)
         self.meta["nreductions"] = int(m.nreductions)
@@ -241,6 +242,98 @@ class AuctionSolver:
                      fullscan_edges_read=int(m.fullscan_edges_read))
         self.gpu = g
         self.meta["gpu"] = g
+
+    # -- warm-started re-solve (no counterpart in the reference; include/misslap.h: misslap_resolve) -------------------
+    # Prices are those of the maximised problem (for problem='min' the prices of the negated costs), out and in alike.
+    @property
+    def prices(self):
+        """The current prices, float64[num_cols]."""
+        p = np.empty(self.num_cols, dtype=np.float64)
+        _lib.check(_lib.load().misslap_get_prices(self._h, p.ctypes.data, 0))
+        return p
+
+    def update_values(self, val):
+        """Replace the values of the handle's entries in place: a 1-D float64 array of `nnz` values in the order of the
+        constructor's `loc`, or for a solver made by `from_matrix` an (N, M) float64 matrix with the same `v >= 0`
+        pattern.  Values are in the caller's sign and the caller's array is not written (unlike the constructor, there is
+        no reference quirk to mirror).  All or nothing: a rejected update leaves the handle unchanged.  Returns
+        max |new - old| in cost units, the natural `eps_start` of the next `resolve`."""
+        if not isinstance(val, np.ndarray):
+            raise TypeError("val must be a numpy array")
+        if val.dtype != np.float64:
+            raise ValueError(f"Buffer dtype mismatch, expected 'double' but got '{_cname(val.dtype)}'")
+        delta = C.c_double(0.0)
+        if val.ndim == 2:
+            shape = getattr(self, "_dense_shape", None)
+            if shape is None:
+                raise ValueError("an (N, M) matrix updates a solver made by from_matrix only; pass the nnz values instead")
+            if val.shape != shape:
+                raise ValueError(f"matrix of shape {val.shape}, the solver was made from one of shape {shape}")
+            v = np.ascontiguousarray(val)
+            if np.isposinf(v).any():  # (NaN and negative entries are invalid ones, as in from_matrix)
+                raise ValueError("the matrix holds +inf")
+            _lib.check(_lib.load().misslap_update_dense(self._h, v.ctypes.data, 0, None, C.byref(delta)))
+            return float(delta.value)
+        if val.ndim != 1:
+            raise ValueError(f"Buffer has wrong number of dimensions (expected 1, got {val.ndim})")
+        if val.shape[0] != self.nnz:
+            raise ValueError(f"{val.shape[0]} values given, the solver holds {self.nnz} entries")
+        v = np.ascontiguousarray(val)
+        if not np.isfinite(v).all():
+            raise ValueError("val holds a NaN or an infinity")
+        _lib.check(_lib.load().misslap_update_values(self._h, v.ctypes.data, self.nnz, 0, None, C.byref(delta)))
+        return float(delta.value)
+
+    def update_values_device(self, ptr, input_stream=None, dense=False):
+        """update_values on values already in HBM: `ptr` is a device pointer to nnz float64 values (or, dense=True, to the
+        (N, M) matrix of a from_matrix solver), produced on the hipStream_t `input_stream` (None: the library waits for
+        the whole device).  Checked on the device only."""
+        delta = C.c_double(0.0)
+        stream = None if input_stream is None else C.c_void_p(int(input_stream))
+        lib = _lib.load()
+        if dense:
+            _lib.check(lib.misslap_update_dense(self._h, C.c_void_p(int(ptr)), 1, stream, C.byref(delta)))
+        else:
+            _lib.check(lib.misslap_update_values(self._h, C.c_void_p(int(ptr)), self.nnz, 1, stream, C.byref(delta)))
+        return float(delta.value)
+
+    def resolve(self, prices=None, eps_start=0):
+        """Solve again from `prices` (float64[num_cols], a numpy array or a tensor on the device; None: the current
+        prices) with every person unassigned and eps0 = eps_start if > 0, else C / 2 of the current values.  Returns
+        person_to_object and refreshes self.meta like solve()."""
+        e = float(eps_start)
+        if e != e:
+            raise ValueError("eps_start is NaN")
+        ptr, on_device = None, 0
+        if prices is not None:
+            if isinstance(prices, np.ndarray):
+                if prices.dtype != np.float64:
+                    raise ValueError(f"Buffer dtype mismatch, expected 'double' but got '{_cname(prices.dtype)}'")
+                p = np.ascontiguousarray(prices)
+                bad_nan, bad_sign = not np.isfinite(p).all(), bool(np.signbit(p).any())
+                ptr = p.ctypes.data
+            elif hasattr(prices, "data_ptr") and getattr(prices, "is_cuda", False):  # a torch tensor in HBM
+                import torch
+                if prices.dtype != torch.float64:
+                    raise ValueError(f"prices must be float64, got {prices.dtype}")
+                p = prices.contiguous()
+                bad_nan, bad_sign = not bool(torch.isfinite(p).all()), bool(torch.signbit(p).any())
+                ptr, on_device = p.data_ptr(), 1
+            else:
+                raise TypeError("prices must be a numpy array or a tensor on the device")
+            if p.ndim != 1 or p.shape[0] != self.num_cols:
+                raise ValueError(f"prices must have shape ({self.num_cols},), got {tuple(p.shape)}")
+            if bad_nan:
+                raise ValueError("prices hold a NaN or an infinity")
+            if bad_sign:
+                raise ValueError("prices must be >= 0 (with the sign bit clear: -0.0 is rejected)")
+        lib = _lib.load()
+        sol = np.empty(self.num_rows, dtype=np.int32)
+        meta = _lib.new_meta()
+        _lib.check(lib.misslap_resolve(self._h, None if ptr is None else C.c_void_p(ptr), on_device, float(np.float32(e)),
+                                       sol.ctypes.data, C.byref(meta)))
+        self._fill_meta(meta)
+        return sol
 
     # -- stepwise API (tests, multi-GPU driver) ----------------------------------------------------
     def status(self):
@@ -338,6 +431,7 @@ def from_matrix(mat, problem="min", eps_start=0, max_iter=1000000, fast=False, c
         raise ValueError(f"Matrix is infeasible - Fewer than {N} valid values provided for {N} rows.")
     _lib.check(rc)
     solver = AuctionSolver._from_handle(h, opts, problem)
+    solver._dense_shape = (N, M)  # (update_values takes an (N, M) matrix)
     if cardinality_check:  # :562-566, on the CSR the handle already holds in device memory
         cardinality = solver.matching_cardinality()
         if cardinality < N:

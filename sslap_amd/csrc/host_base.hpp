@@ -167,8 +167,16 @@ struct misslap_solver {
     // huge |cost| in the LAST eps-phases (eps falls to 0.15 / N).  The lines are used while the phase's eps is at or above
     // lines_safe_eps = max|cost| x 2^-44 (2^9 ulps of the largest cost) and dropped for good from the first phase below it
     // (begin_phase; the full scans never depend on the invariant; kErrPriceFell is the run-time backstop).
+    // A warm start (misslap_resolve) can begin far from zero prices, and the operands of a price update are then of the
+    // size of the prices as well: the bound is (max|cost| + max starting price) x 2^-44 (warm starts).
     double lines_safe_eps = 0.0;
     bool lines_dropped = false;     // ... that phase has been reached: the lines are no longer read or maintained
+    double max_abs = 0.0;           // max |value| of the current values (C of eps0 = C / 2, auction_.pyx:242-246)
+    double pmax0 = 0.0;             // largest starting price of the current solve (0 after create)
+    float eps_start_opt = 0.f;      // options.eps_start of create (> 0: overrides eps0)
+    bool untouched = true;          // no round has run since create or the last reset_state (launch_bid / launch_tail)
+    bool dense = false;             // made by misslap_create_dense: dense_cols columns of the caller's matrix
+    int64_t dense_cols = 0;
     int device = 0;
     hipStream_t stream = nullptr;
     bool own_stream = false;
@@ -185,6 +193,7 @@ struct misslap_solver {
     float *price32 = nullptr;  // fp32 mirror of the prices for the filter scans of the wave-per-row kernel (wave_bid_filter);
     int *pmax_bits = nullptr;  // nullptr: no filter.  pmax_bits: the largest price at the last rebuild of the mirror
     float cmax32 = 0.f;        // (float) max |cost|
+    float *price32_buf = nullptr;  // the mirror's memory: price32 points at it while the filter's error bound holds (set_filter)
     PriceRec *rec = nullptr;
     int2 *cand = nullptr;  // candidate lines, 256 B per person
     double *cand64 = nullptr;  // ... and 256 B of fp64 costs per person in the 12 B/edge layout
@@ -219,6 +228,8 @@ struct misslap_solver {
     unsigned long long *take_edges_out = nullptr;  // add up: its grid and where the count goes
     int *split_cnt = nullptr;    // ... and the arrival counter of every slice 
     int n_tiled = 0;  // entries of `tiled` including the padding entries
+    int tile_cols = 0;      // columns per tile of the tile-major copy, and entries of its segment table (value updates walk it)
+    long long tile_L = 0;
     int T = 0;
     bool tiled_ok = false;
     int tiled_min_K = 0;
@@ -265,6 +276,7 @@ struct misslap_solver {
     long long tail_nits0 = -1;       // (the control block's own counter reaches the host with a full read only)
                                      // round count in front of the tail launches whose rounds are not yet counted; -1: none
     bool long_rows = false;  // some row is longer than kCandRowMax: k_refresh_long has work
+    bool long_rows0 = false, long_rows_later0 = false;  // ... both as create decided them (a reset returns to them)
     bool line_maintenance = true;  // k_refresh_lines ahead of the tail kernels (options.reserved[4] = 2: off)
     int cand_refresh_min = kDefaultCandRefresh;
     bool round_ordered = false;  // the current round's bidders were taken in person order (k_order_*, partial tiled rounds)

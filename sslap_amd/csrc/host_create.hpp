@@ -27,6 +27,64 @@ void free_all(misslap_solver *h) {
     delete h;
 }
 
+// The fp32 filter of the wave-per-row kernel (price32_buf, allocated at create) is used while its relative error bound
+// holds: costs and prices of ordinary magnitude (no subnormal fp32 cost maximum, no overflow of fl32(price)).
+void set_filter(misslap_solver *h) {
+    const bool range_ok = h->max_abs > 0x1p-100 && h->max_abs < 0x1p60 && h->pmax0 < 0x1p60;
+    h->price32 = h->price32_buf && range_ok ? h->price32_buf : nullptr;
+    h->cmax32 = (float)h->max_abs;
+}
+
+// The state a solve starts from (auction_.pyx:220-264): the last step of create, and of misslap_resolve.  d_p0: starting
+// prices in device memory (h->price itself: keep the current ones; nullptr: zeros, :220), pmax0 their maximum, checked by
+// the caller; eps_start > 0 overrides eps0 = C / 2 (:251-252).  Every person unassigned, its = nreductions = 0, candidate
+// lines invalidated (they hold costs, and they are exact only while prices never fall -- a warm start may begin below the
+// prices the lines were built at), and the host-side state of a solve as create leaves it.
+int reset_state(misslap_solver *h, const double *d_p0, double pmax0, float eps_start) {
+    const size_t N = (size_t)h->n_rows, M = (size_t)h->n_cols;
+    if (h->profile) {
+        HIP_TRY(hipMemsetAsync(h->launch_edges, 0, sizeof(unsigned long long) * 2 * (size_t)h->launch_edges_cap, h->stream));
+        h->launch_idx = 0;
+        h->prof_used = 0;
+    }
+    hipLaunchKernelGGL(k_init_state, dim3(blocks_for((long long)(N > M ? N : M), 256)), dim3(256), 0, h->stream,
+                       h->ctl, h->price, h->rec, h->p2o, h->o2p, h->U, h->best_key, h->best_pos, h->cand, h->n_rows, h->n_cols,
+                       (long long)h->max_iter, d_p0);
+    HIP_TRY(hipGetLastError());
+    h->ece_flag_clear = true;
+    h->live_valid = false;  // (K was set by a launch without a ticket)
+    h->ctl_fresh = 0;
+    h->nreductions = 0;
+    h->finished = false;
+    h->phases_run = h->phases_with_lines = 0;
+    h->sharded_rounds = 0;
+    h->solve_ms = 0;
+    h->lines_dropped = false;
+    h->long_rows = h->long_rows0;
+    h->long_rows_later = h->long_rows_later0;
+    h->tail_rounds_host = 0;
+    h->tail_nits0 = -1;
+    h->walk_rev_next = false;
+    h->round_small = h->round_done = h->round_ordered = false;
+    h->take_edges_n = 0;
+    h->pmax0 = pmax0;
+    h->lines_safe_eps = (h->max_abs + pmax0) * 0x1p-44;  // < 2^9 ulps of the largest operand of a price update
+    set_filter(h);
+    // eps schedule, fp32 exactly as the generated C of the reference (SURVEY.md section 5 quirk 8)
+    const float C = (float)h->max_abs;            // auction_.pyx:242-243
+    h->eps = (float)((double)C / 2.0);            // :246
+    h->target_eps = (float)(1.0 / (double)h->n_rows);  // :247
+    h->theta = (float)0.15;                       // :248
+    if (eps_start > 0) h->eps = eps_start;        // :251-252
+    h->start_eps = h->eps;
+    begin_phase(h);
+    h->K_ub = h->n_rows;
+    h->K_exact = true;
+    h->phase_fresh = true;
+    h->untouched = true;
+    return MISSLAP_OK;
+}
+
 // Shared tail of the two constructors: d_loc / d_val are device-resident COO arrays.
 int build_from_device_coo(misslap_solver *h, const int *d_loc, const double *d_val, int last_row,
                           const misslap_options *opt) {
@@ -72,10 +130,8 @@ int build_from_device_coo(misslap_solver *h, const int *d_loc, const double *d_v
     // (candidate lines and eps: see misslap_solver::lines_safe_eps; the decision is taken per eps-phase, begin_phase)
     int cand_mode = opt->cand_mode;
     {
-        double max_abs_d;
         const long long b = (long long)st.max_abs_bits;
-        std::memcpy(&max_abs_d, &b, sizeof(double));
-        h->lines_safe_eps = max_abs_d * 0x1p-44;  // < 2^9 ulps of the largest cost
+        std::memcpy(&h->max_abs, &b, sizeof(double));  // (lines_safe_eps: reset_state)
     }
     // Lines for long rows (k_refresh_long) pay where a row scan is long: dense 8000^2 1.79 -> 0.60 s.  At a few
     // hundred edges per row the pass costs more than the scans it saves (C4, 300 edges per row, 176 rounds: 13.4 ->
@@ -92,6 +148,8 @@ int build_from_device_coo(misslap_solver *h, const int *d_loc, const double *d_v
     const bool many_long = (long long)st.long_rows * 100 >= (long long)kLongRowsMixedPercent * h->n_rows;
     h->long_rows_later = !h->long_rows && (avg_row > kCandRowMax || (st.max_row_len > kCandRowMax && many_long)) &&
                          avg_row <= kCandLongMax && cand_mode != 1;
+    h->long_rows0 = h->long_rows;
+    h->long_rows_later0 = h->long_rows_later;
     if (h->thr < 0) {  // library default: by whether the persons will have candidate lines (rows of <= 256 edges)
         const bool lines = cand_mode != 1 && (avg_row <= kCandRowMax || h->long_rows);
         h->thr = lines ? kDefaultTailThreshold : kDefaultTailThresholdNoLines;
@@ -274,6 +332,8 @@ int build_from_device_coo(misslap_solver *h, const int *d_loc, const double *d_v
                 HIP_TRY(hipStreamSynchronize(h->stream));
                 trace.stage("tile-major copy");
                 h->tiled_ok = true;
+                h->tile_cols = tcols;
+                h->tile_L = L;
                 // break-even against k_bid (cost ~ K) measured at C3: the full-scan engines have a fixed cost
                 // (price fills, barriers / the merge pass) of about a fifth of a full k_bid scan: 0.3 N.  Where the rows
                 // keep candidate lines (<= 256 edges) the engine takes the rounds from 0.7 N on only (round 6): a partial
@@ -336,16 +396,13 @@ int build_from_device_coo(misslap_solver *h, const int *d_loc, const double *d_v
             // copy) and the fp64 price table exceeds an XCD's L2 share (>= 3 MB); costs of ordinary magnitude only (the
             // error bound of the filter is relative: no subnormal fp32 values, no overflow of fl32(price)).
             // MISSLAP_F32_FILTER=0 / 1: never / whatever the table's size (A/B timing, tests)
+            // (set_filter, in reset_state, points price32 at the buffer and sets the cost bound)
             const char *fe = std::getenv("MISSLAP_F32_FILTER");  // (read per create: the tests switch it)
             const int env = fe ? std::atoi(fe) : -1;
-            double max_abs_d;
-            const long long b = (long long)st.max_abs_bits;
-            std::memcpy(&max_abs_d, &b, sizeof(double));
-            const bool range_ok = max_abs_d > 0x1p-100 && max_abs_d < 0x1p60;
+            const bool range_ok = h->max_abs > 0x1p-100 && h->max_abs < 0x1p60;
             if (!h->tiled_ok && range_ok && env != 0 && (env == 1 || M * sizeof(double) >= ((size_t)3 << 20))) {
-                blk.want(&h->price32, M);
+                blk.want(&h->price32_buf, M);
                 blk.want(&h->pmax_bits, 1);
-                h->cmax32 = (float)max_abs_d;
             }
         }
         h->line_maintenance = cand_mode != 2;
@@ -391,8 +448,6 @@ int build_from_device_coo(misslap_solver *h, const int *d_loc, const double *d_v
     HIP_TRY(hipMemsetAsync(h->bid_rec, 0, sizeof(int4) * kRoundSmallMax, h->stream));
     HIP_TRY(hipMemsetAsync(h->wg_stats, 0, sizeof(unsigned long long) * kStatWords * (size_t)h->wg_stats_slots, h->stream));
     if (h->split_cnt) HIP_TRY(hipMemsetAsync(h->split_cnt, 0, sizeof(int) * ((size_t)N / 256 + 1024), h->stream));
-    if (h->profile)
-        HIP_TRY(hipMemsetAsync(h->launch_edges, 0, sizeof(unsigned long long) * 2 * (size_t)h->launch_edges_cap, h->stream));
     // the mirror, the two trailing status copies and the live status words (kept together: one pooled allocation)
     // (coherent + mapped EXPLICITLY: with HIP_HOST_COHERENT=0 in the environment a default allocation is not coherent,
     // and the kernels' system-scope stores to the live words would become visible at sync points only)
@@ -424,27 +479,8 @@ int build_from_device_coo(misslap_solver *h, const int *d_loc, const double *d_v
     if (h->cand_build_max_K == 0x7fffffff)
         h->cand_build_max_K = (int)std::max<size_t>((N * 3) / 10, 8192) - 1;
     h->max_iter = opt->max_iter < 1 ? 1 : opt->max_iter;  // the loop body runs before the first test (:271-275)
-    hipLaunchKernelGGL(k_init_state, dim3(blocks_for((long long)(N > M ? N : M), 256)), dim3(256), 0, h->stream,
-                       h->ctl, h->price, h->rec, h->p2o, h->o2p, h->U, h->best_key, h->best_pos, h->cand, h->n_rows, h->n_cols,
-                       (long long)h->max_iter);
-    HIP_TRY(hipGetLastError());
-    h->ece_flag_clear = true;
-    // eps schedule, fp32 exactly as the generated C of the reference (SURVEY.md section 5 quirk 8)
-    double max_abs;
-    {
-        const long long b = (long long)st.max_abs_bits;
-        std::memcpy(&max_abs, &b, sizeof(double));
-    }
-    const float C = (float)max_abs;               // auction_.pyx:242-243
-    h->eps = (float)((double)C / 2.0);            // :246
-    h->target_eps = (float)(1.0 / (double)h->n_rows);  // :247
-    h->theta = (float)0.15;                       // :248
-    if (opt->eps_start > 0) h->eps = opt->eps_start;  // :251-252
-    h->start_eps = h->eps;
-    begin_phase(h);
-    h->K_ub = h->n_rows;
-    h->K_exact = true;
-    h->phase_fresh = true;
+    h->eps_start_opt = opt->eps_start;
+    if ((rc = reset_state(h, nullptr, 0.0, opt->eps_start))) return rc;
     HIP_TRY(hipStreamSynchronize(h->stream));
     tmp.drained = true;
     trace.stage("state blocks + init");

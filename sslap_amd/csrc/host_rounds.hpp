@@ -320,6 +320,7 @@ bool use_round_small(const misslap_solver *h) {
 
 int launch_bid(misslap_solver *h) {
     h->ctl_fresh = false;
+    h->untouched = false;
     // (not behind a full-scan engine launch: the engines always feed best_key, which k_round_small ignores)
     h->round_small = use_round_small(h) && !(h->tiled_ok && h->K_ub >= h->tiled_min_K);
     if (h->tiled_ok && h->K_ub >= h->tiled_min_K) {
@@ -452,6 +453,7 @@ int launch_apply(misslap_solver *h) {
 int launch_tail(misslap_solver *h) {
     if (h->thr <= 0) return MISSLAP_OK;
     h->ctl_fresh = false;
+    h->untouched = false;
     // Rows of a few hundred edges keep no lines until the solve has shown that its tail is long: that many tail rounds
     // (a tail round without a line is a row scan by one wavefront, 1.5-4 us at 300-1000 edges; the pass that builds the
     // lines of every row costs milliseconds at C4's 100 000 rows and pays for itself within a phase at a dense

@@ -95,25 +95,32 @@ __global__ __launch_bounds__(256) void k_build_edges_f64(const int *loc, const d
     }
 }
 
+// Candidate lines invalidated: tau = +inf (no line yet), every slot empty.
+__device__ __forceinline__ void clear_lines_body(int2 *cand, int n_rows) {
+    const int stride = gridDim.x * blockDim.x;
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    const double inf = __builtin_huge_val();
+    for (long long k = t; k < (long long)n_rows * kCandLanes; k += stride)
+        cand[k] = (k & (kCandLanes - 1)) == 0 ? make_int2(__double2loint(inf), __double2hiint(inf)) : make_int2(-1, 0);
+}
+
+// The state a solve starts from (auction_.pyx:220-260).  p0: the starting prices (a warm start, misslap_resolve; may be
+// `price` itself), nullptr = zeros (:220).  They go to both price tables, `price` and PriceRec::price.
 __global__ __launch_bounds__(256) void k_init_state(Ctl *ctl, double *price, PriceRec *rec, int *p2o, int *o2p, int *U,
                                                     unsigned long long *best_key, int *best_pos, int2 *cand,
-                                                    int n_rows, int n_cols, long long max_iter) {
+                                                    int n_rows, int n_cols, long long max_iter, const double *p0) {
     const int stride = gridDim.x * blockDim.x;
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     for (int i = t; i < n_rows; i += stride) {
         p2o[i] = -1;  // :231
         U[i] = i;     // :260
     }
-    if (cand) {  // candidate lines: tau = +inf (no line yet), every slot empty
-        const double inf = __builtin_huge_val();
-        for (long long k = t; k < (long long)n_rows * kCandLanes; k += stride)
-            cand[k] = (k & (kCandLanes - 1)) == 0 ? make_int2(__double2loint(inf), __double2hiint(inf))
-                                                  : make_int2(-1, 0);
-    }
+    if (cand) clear_lines_body(cand, n_rows);  // candidate lines: none yet
     for (int j = t; j < n_cols; j += stride) {
-        price[j] = 0.0;        // :220
+        const double pj = p0 ? p0[j] : 0.0;
+        price[j] = pj;        // :220
         PriceRec r;
-        r.price = 0.0;
+        r.price = pj;
         r.owner = -1;
         r.ostart = 0;
         rec[j] = r;

@@ -37,6 +37,7 @@
 #include "host_comm.hpp"
 #include "kernels_matching.hpp"
 #include "kernels_tiled.hpp"
+#include "kernels_warm.hpp"
 
 using namespace misslap;
 
@@ -171,6 +172,8 @@ MISSLAP_API int misslap_create_dense(misslap_solver **out, int64_t n_rows, int64
                        d_loc, d_val);
     rc = build_from_device_coo(h, d_loc, d_val, (int)n_rows - 1, opt);
     if (rc) return cleanup(rc);
+    h->dense = true;  // (misslap_update_dense: the caller's matrix has this many columns)
+    h->dense_cols = n_cols;
     cleanup(0);
     h->setup_ms = now_ms() - t0;
     *out = h;
@@ -498,3 +501,4 @@ MISSLAP_API int misslap_get_state(misslap_solver *h, double *prices, int32_t *un
     return MISSLAP_OK;
 }
 #include "abi_diag.hpp"
+#include "abi_warm.hpp"
