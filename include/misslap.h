@@ -30,7 +30,8 @@ extern "C" {
  *      misslap_finish / misslap_solve_sharded on that handle (INTEGRATION.md section 5 lists both layouts).
  *   2  the knobs are named fields, misslap_meta starts with `struct_size` (the library writes min(struct_size,
  *      sizeof) bytes: a caller built against a shorter version-2 header keeps working when fields are appended),
- *      validity flags of the assignment, misslap_trim_caches. */
+ *      validity flags of the assignment, misslap_trim_caches.  Additions since: the warm-start entry points,
+ *      misslap_solve_dense_batch. */
 
 #define MISSLAP_OK 0
 #define MISSLAP_ERR_INVALID 1    /* malformed arguments / input contract violated */
@@ -420,6 +421,61 @@ typedef struct misslap_batch_info {
 } misslap_batch_info;
 int misslap_solve_batch(misslap_solver *const *handles, int32_t n, int32_t *const *person_to_object_out,
                         misslap_meta *const *meta_out, int32_t group_size, misslap_batch_info *info);
+
+/* ---- many small DENSE problems in one call (no counterpart in the reference, whose own benchmark solves small dense
+ * matrices one at a time: benchmarking.py:146).  mat is double[B][N][M] (row-major, problem b at offset b * N * M,
+ * counted in 64 bits); problem b is mat[b][:n_b][:m_b] with (n_b, m_b) = shapes[2b], shapes[2b + 1] (shapes NULL: every
+ * problem is N x M; entries outside the slice are never read).  Entries are read with _from_matrix's rule (v >= 0 is an
+ * entry; negatives and NaN are not, auction_.pyx:546-557).  Each problem is solved by ONE workgroup of ONE launch, its
+ * whole state in LDS (csrc/kernels_dense_batch.hpp), and its result is exactly what _from_matrix(mat[b][:n_b][:m_b],
+ * ...).solve() returns: same assignment, its, nreductions, eCE, objective and price bits.
+ *   opt            device, maximize, eps_start, max_iter, input_on_device (mat and prices_in are device pointers) and
+ *                  input_stream (as for misslap_create_dense); every other field must be 0.
+ *   eps_start      float[B] host array or NULL: problem b's eps_start (> 0 overrides C / 2, auction_.pyx:251-252); NULL =
+ *                  opt->eps_start for every problem.  (The front-end's `fast` passes 1 / n_b here, :568-569.)
+ *   prices_in      double[B][M] or NULL: problem b starts from prices_in[b][:m_b] as misslap_resolve does (every person
+ *                  unassigned, its = nreductions = 0); finite and >= 0 with the sign bit clear.
+ *   cardinality_check  != 0: the Hopcroft-Karp guard of _from_matrix (auction_.pyx:562-566), per problem, on the host.
+ *   sol            int32[B][N]: sol[b][:n_b] the assignment (-1 = unassigned), -1 beyond n_b.
+ *   prices_out     double[B][M] or NULL: final prices of the maximised problem; 0 beyond m_b.
+ *   out_on_device  != 0: sol and prices_out are device pointers (meta is always host memory).
+ *   meta           host array of B misslap_dense_batch_meta, meta[0].struct_size set (the stride of the array), or NULL.
+ *   info           may be NULL.
+ * All or nothing: every problem is validated before any is solved.  A failing problem gives MISSLAP_ERR_INVALID and the
+ * text "problem <b>: <what _from_matrix raises for that slice>" for the first failing b, in _from_matrix's order: fewer
+ * valid values than rows, an empty row, +inf, the matching guard, then bad starting prices.  N and M are at most
+ * MISSLAP_DENSE_BATCH_MAX_DIM (larger problems: misslap_create_dense / misslap_solve_batch).  Every solve ends after at
+ * most max_iter rounds. */
+#define MISSLAP_DENSE_BATCH_MAX_DIM 1024
+typedef struct misslap_dense_batch_meta {
+    int32_t struct_size;  /* IN (element 0 only): sizeof(misslap_dense_batch_meta); the stride of the array */
+    int32_t n_rows;       /* n_b */
+    int32_t n_cols;       /* the reference's M: max valid column + 1 (auction_.pyx:209-212) */
+    int32_t eCE;          /* :297 */
+    int64_t nnz;          /* valid entries of the slice */
+    int64_t its;          /* :298 */
+    int64_t n_assigned;   /* :301 */
+    int32_t nreductions;  /* :299 */
+    int32_t soln_found;   /* :300 */
+    float start_eps;      /* :264 (unrounded fp32) */
+    float final_eps;      /* :303 */
+    float target_eps;     /* :247 */
+    float obj_f32;        /* get_obj() returns a C float, :489 */
+    double obj_f64;       /* the same sum before the cast */
+    uint64_t bids_made;
+} misslap_dense_batch_meta;
+typedef struct misslap_dense_batch_info {
+    int32_t threads;      /* workgroup size of the solve launch */
+    int32_t lds_bytes;    /* dynamic LDS per workgroup */
+    double check_ms;      /* validation launch + read-back (wall) */
+    double matching_ms;   /* host matching guard (wall) */
+    double solve_ms;      /* the solve launch (HIP events) */
+    double wall_ms;       /* the whole call */
+} misslap_dense_batch_info;
+int misslap_solve_dense_batch(int64_t B, int64_t N, int64_t M, const double *mat, const int32_t *shapes,
+                              const float *eps_start, const double *prices_in, int32_t cardinality_check,
+                              const misslap_options *opt, int32_t *sol, double *prices_out, int32_t out_on_device,
+                              misslap_dense_batch_meta *meta, misslap_dense_batch_info *info);
 
 const char *misslap_last_error(void);
 int misslap_abi_version(void);

@@ -57,6 +57,25 @@ class BatchInfo(C.Structure):
                 ("host_ms_flush", C.c_double), ("host_ms_wait", C.c_double)]
 
 
+class DenseBatchMeta(C.Structure):
+    """misslap_dense_batch_meta: one per problem of misslap_solve_dense_batch (struct_size set in element 0)."""
+    _fields_ = [
+        ("struct_size", C.c_int32), ("n_rows", C.c_int32), ("n_cols", C.c_int32), ("eCE", C.c_int32),
+        ("nnz", C.c_int64), ("its", C.c_int64), ("n_assigned", C.c_int64),
+        ("nreductions", C.c_int32), ("soln_found", C.c_int32),
+        ("start_eps", C.c_float), ("final_eps", C.c_float), ("target_eps", C.c_float), ("obj_f32", C.c_float),
+        ("obj_f64", C.c_double), ("bids_made", C.c_uint64),
+    ]
+
+
+class DenseBatchInfo(C.Structure):
+    _fields_ = [("threads", C.c_int32), ("lds_bytes", C.c_int32), ("check_ms", C.c_double), ("matching_ms", C.c_double),
+                ("solve_ms", C.c_double), ("wall_ms", C.c_double)]
+
+
+DENSE_BATCH_MAX_DIM = 1024  # MISSLAP_DENSE_BATCH_MAX_DIM
+
+
 def new_meta():
     m = Meta()
     m.struct_size = C.sizeof(Meta)
@@ -139,6 +158,9 @@ SYMBOLS = {
     "misslap_update_values": (C.c_int, [_VP, _VP, C.c_int64, C.c_int32, _VP, C.POINTER(C.c_double)]),
     "misslap_update_dense": (C.c_int, [_VP, _VP, C.c_int32, _VP, C.POINTER(C.c_double)]),
     "misslap_resolve": (C.c_int, [_VP, _VP, C.c_int32, C.c_float, _VP, C.POINTER(Meta)]),
+    "misslap_solve_dense_batch": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, _VP, _VP, _VP, _VP, C.c_int32,
+                                            C.POINTER(Options), _VP, _VP, C.c_int32, C.POINTER(DenseBatchMeta),
+                                            C.POINTER(DenseBatchInfo)]),
     "misslap_last_error": (C.c_char_p, []),
     "misslap_abi_version": (C.c_int, []),
 }

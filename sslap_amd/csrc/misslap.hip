@@ -10,6 +10,7 @@
 #include <hip/hip_ext.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cstdarg>
@@ -38,6 +39,7 @@
 #include "kernels_matching.hpp"
 #include "kernels_tiled.hpp"
 #include "kernels_warm.hpp"
+#include "kernels_dense_batch.hpp"
 
 using namespace misslap;
 
@@ -502,3 +504,4 @@ MISSLAP_API int misslap_get_state(misslap_solver *h, double *prices, int32_t *un
 }
 #include "abi_diag.hpp"
 #include "abi_warm.hpp"
+#include "abi_dense_batch.hpp"
