@@ -31,7 +31,7 @@ extern "C" {
  *   2  the knobs are named fields, misslap_meta starts with `struct_size` (the library writes min(struct_size,
  *      sizeof) bytes: a caller built against a shorter version-2 header keeps working when fields are appended),
  *      validity flags of the assignment, misslap_trim_caches.  Additions since: the warm-start entry points,
- *      misslap_solve_dense_batch. */
+ *      misslap_solve_dense_batch, misslap_solve_sparse_batch. */
 
 #define MISSLAP_OK 0
 #define MISSLAP_ERR_INVALID 1    /* malformed arguments / input contract violated */
@@ -476,6 +476,41 @@ int misslap_solve_dense_batch(int64_t B, int64_t N, int64_t M, const double *mat
                               const float *eps_start, const double *prices_in, int32_t cardinality_check,
                               const misslap_options *opt, int32_t *sol, double *prices_out, int32_t out_on_device,
                               misslap_dense_batch_meta *meta, misslap_dense_batch_info *info);
+
+/* ---- many small SPARSE problems in one call: the batch form of _from_sparse(loc, val, size=...) (auction_.pyx:575-617).
+ * loc is int32[nnz][2] and val double[nnz]; problem b is the entries offsets[b] .. offsets[b + 1] (offsets: host
+ * int64[B + 1], offsets[0] = 0, non-decreasing, offsets[B] = nnz), its row and column indices its own and 0-based, read
+ * in their stored order as the reference reads them.  Each problem is solved by ONE workgroup of ONE launch, its whole
+ * state in LDS (csrc/kernels_sparse_batch.hpp), and its result is exactly what _from_sparse(loc_b, val_b, size=sizes[b],
+ * ...).solve() returns: same assignment, its, nreductions, eCE, objective and price bits.  The per-problem records and
+ * the call info are the dense batch's structs, misslap_dense_batch_meta / misslap_dense_batch_info: nothing in them is
+ * dense-specific (meta.n_rows = max row + 1, meta.n_cols = max column + 1, meta.nnz = the problem's entries).
+ *   sizes          int64[B][2] host array or NULL: problem b's `size` of _from_sparse, read as it reads it (M, N =
+ *                  size, :592); NULL = N is the maximum row index (:594).  N only enters the "fewer than N entries"
+ *                  check; the solve uses the problem's own max row + 1.
+ *   eps_start      float[B] host array or NULL: as for misslap_solve_dense_batch (the front-end's `fast` passes 1 / N_b).
+ *   prices_in      double[B][prices_ld] or NULL: problem b starts from prices_in[b][:n_cols_b] as misslap_resolve does;
+ *                  prices_ld >= every n_cols_b.
+ *   cardinality_check  != 0: _from_sparse's Hopcroft-Karp guard on the true graph (:608-612), per problem, on the host.
+ *   sol            int32[B][sol_ld]: sol[b][:n_b] the assignment, -1 beyond.
+ *   prices_out     double[B][prices_out_ld] or NULL: final prices of the maximised problem, 0 beyond n_cols_b.
+ *   sol_ld, prices_out_ld   the caller's leading dimensions: at least the largest n_b / n_cols_b of the batch.  A caller
+ *                  sizes them from loc alone: max(loc[:, 0]) + 1 and max(loc[:, 1]) + 1, capped at
+ *                  MISSLAP_SPARSE_BATCH_MAX_DIM.  Checked per problem as its last check: a call that does not fit fails
+ *                  like any other check, before anything is solved.
+ *   opt, out_on_device, meta, info   as for misslap_solve_dense_batch (input_on_device: loc, val and prices_in are
+ *                  device pointers; offsets and sizes are always host memory).
+ * All or nothing: the first failing problem gives MISSLAP_ERR_INVALID and the text "problem <b>: <what _from_sparse
+ * raises for that problem alone>", checked in its order: no entries, fewer entries than N, the matching guard (with
+ * misslap_hopcroft_karp's index and order checks), the constructor's checks (negative index, rows not ascending, a row
+ * gap, NaN / infinity, a column too large), n_b or n_cols_b above MISSLAP_SPARSE_BATCH_MAX_DIM, bad starting prices,
+ * then the leading dimensions.  Every solve ends after at most max_iter rounds. */
+#define MISSLAP_SPARSE_BATCH_MAX_DIM 2048
+int misslap_solve_sparse_batch(int64_t B, const int32_t *loc, const double *val, const int64_t *offsets,
+                               const int64_t *sizes, const float *eps_start, const double *prices_in, int64_t prices_ld,
+                               int32_t cardinality_check, const misslap_options *opt, int32_t *sol, int64_t sol_ld,
+                               double *prices_out, int64_t prices_out_ld, int32_t out_on_device,
+                               misslap_dense_batch_meta *meta, misslap_dense_batch_info *info);
 
 const char *misslap_last_error(void);
 int misslap_abi_version(void);

@@ -74,6 +74,7 @@ class DenseBatchInfo(C.Structure):
 
 
 DENSE_BATCH_MAX_DIM = 1024  # MISSLAP_DENSE_BATCH_MAX_DIM
+SPARSE_BATCH_MAX_DIM = 2048  # MISSLAP_SPARSE_BATCH_MAX_DIM
 
 
 def new_meta():
@@ -161,6 +162,9 @@ SYMBOLS = {
     "misslap_solve_dense_batch": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, _VP, _VP, _VP, _VP, C.c_int32,
                                             C.POINTER(Options), _VP, _VP, C.c_int32, C.POINTER(DenseBatchMeta),
                                             C.POINTER(DenseBatchInfo)]),
+    "misslap_solve_sparse_batch": (C.c_int, [C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int64, C.c_int32,
+                                             C.POINTER(Options), _VP, C.c_int64, _VP, C.c_int64, C.c_int32,
+                                             C.POINTER(DenseBatchMeta), C.POINTER(DenseBatchInfo)]),
     "misslap_last_error": (C.c_char_p, []),
     "misslap_abi_version": (C.c_int, []),
 }

@@ -1,0 +1,305 @@
+// abi_sparse_batch.hpp -- C ABI: many small sparse (loc / val) problems in one call, one workgroup per problem
+// (misslap_solve_sparse_batch; the kernels are in kernels_sparse_batch.hpp).
+// (part of the single translation unit misslap.hip; included in the order given there, after abi_dense_batch.hpp)
+#pragma once
+
+namespace {
+// The feasibility guard of from_sparse for one problem (auction_.pyx:608-612 on the true graph n_true x m_true):
+// misslap_hopcroft_karp's argument checks in its order, then the matching.  Returns false and the text of the first
+// failure; the matcher never sees an index outside the graph.
+bool sparse_problem_guard(const int32_t *loc, int64_t nnz, int n_true, int m_true, char *buf, size_t len) {
+    if (n_true < 0 || m_true < 0) {
+        snprintf(buf, len, "bad argument");
+        return false;
+    }
+    for (int64_t k = 0; k < nnz; ++k) {
+        const int32_t i = loc[2 * k], j = loc[2 * k + 1];
+        if (i < 0 || i >= n_true || j < 0 || j >= m_true) {
+            snprintf(buf, len, "loc entry %lld = (%d, %d) outside %d x %d", (long long)k, i, j, n_true, m_true);
+            return false;
+        }
+        if (k && i < loc[2 * (k - 1)]) {
+            snprintf(buf, len, "loc rows must be sorted in ascending order");
+            return false;
+        }
+    }
+    // Indices far beyond the entry count (a malformed problem: it has empty rows) are ranked first, so that the matcher's
+    // arrays stay O(nnz).  Rows and columns without an entry take no part in a matching: the cardinality is the same.
+    std::vector<int32_t> ranked;
+    int nr = n_true, mr = m_true;
+    if (n_true > nnz || m_true > nnz) {
+        std::vector<int32_t> rows((size_t)nnz), cols((size_t)nnz);
+        for (int64_t k = 0; k < nnz; ++k) {
+            rows[(size_t)k] = loc[2 * k];
+            cols[(size_t)k] = loc[2 * k + 1];
+        }
+        std::sort(rows.begin(), rows.end());
+        rows.erase(std::unique(rows.begin(), rows.end()), rows.end());
+        std::sort(cols.begin(), cols.end());
+        cols.erase(std::unique(cols.begin(), cols.end()), cols.end());
+        ranked.resize(2 * (size_t)nnz);
+        for (int64_t k = 0; k < nnz; ++k) {
+            ranked[2 * (size_t)k] = (int32_t)(std::lower_bound(rows.begin(), rows.end(), loc[2 * k]) - rows.begin());
+            ranked[2 * (size_t)k + 1] = (int32_t)(std::lower_bound(cols.begin(), cols.end(), loc[2 * k + 1]) - cols.begin());
+        }
+        nr = (int)rows.size();
+        mr = (int)cols.size();
+        loc = ranked.data();
+    }
+    HopcroftKarp hk(loc, nnz, nr, mr);
+    const int card = hk.solve();
+    if (card < n_true) {
+        snprintf(buf, len, "Matrix is infeasible (Maximum matching possible only involves %d out of %d rows.)", card, n_true);
+        return false;
+    }
+    return true;
+}
+}  // namespace
+
+MISSLAP_API int misslap_solve_sparse_batch(int64_t B, const int32_t *loc, const double *val, const int64_t *offsets,
+                                           const int64_t *sizes, const float *eps_start, const double *prices_in,
+                                           int64_t prices_ld, int32_t cardinality_check, const misslap_options *opt_in,
+                                           int32_t *sol, int64_t sol_ld, double *prices_out, int64_t prices_out_ld,
+                                           int32_t out_on_device, misslap_dense_batch_meta *meta,
+                                           misslap_dense_batch_info *info) {
+    const double t_start = now_ms();
+    misslap_options opt;
+    int abi = 0;
+    int rc = normalise_options(opt_in, &opt, &abi);
+    if (rc) return rc;
+    if (opt.tail_threshold > 0 || opt.force_f64_values || opt.profile || opt.shard_world > 1 || opt.rounds_per_sync ||
+        opt.tiled_min_K || opt.tiled_shape || opt.tiled_force || opt.shard_min_K || opt.cand_mode || opt.nnz_limit ||
+        opt.cand_build_max_K || opt.cand_refresh_min)
+        return fail(MISSLAP_ERR_INVALID, "misslap_solve_sparse_batch takes device, maximize, eps_start, max_iter, "
+                                         "input_on_device and input_stream only: every other option must be 0");
+    if (!loc || !val || !offsets || !sol) return fail(MISSLAP_ERR_INVALID, "null loc / val / offsets / sol");
+    if (B < 1 || B > 0x7fffffff) return fail(MISSLAP_ERR_INVALID, "B = %lld: 1 .. 2^31 - 1 problems", (long long)B);
+    if (offsets[0] != 0) return fail(MISSLAP_ERR_INVALID, "offsets[0] = %lld: must be 0", (long long)offsets[0]);
+    for (int64_t b = 0; b < B; ++b) {
+        const int64_t z = offsets[b + 1] - offsets[b];
+        if (z < 0) return fail(MISSLAP_ERR_INVALID, "offsets must be non-decreasing (offsets[%lld] > offsets[%lld])",
+                               (long long)b, (long long)b + 1);
+        if (z >= 0x7fffffff)
+            return fail(MISSLAP_ERR_INVALID, "problem %lld: %lld entries; a problem takes fewer than 2^31 - 1", (long long)b,
+                        (long long)z);
+    }
+    if (sol_ld < 1 || (prices_out && prices_out_ld < 1) || (prices_in && prices_ld < 1))
+        return fail(MISSLAP_ERR_INVALID, "sol_ld / prices_out_ld / prices_ld must be >= 1");
+    int32_t stride = 0;
+    if (meta) {
+        stride = meta[0].struct_size;
+        if (stride < (int32_t)offsetof(misslap_dense_batch_meta, its) || stride > 4096)
+            return fail(MISSLAP_ERR_INVALID, "misslap_dense_batch_meta.struct_size = %d: set it to sizeof (%d) in meta[0]",
+                        stride, (int)sizeof(misslap_dense_batch_meta));
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail(MISSLAP_ERR_NO_DEVICE, "no HIP device available: libmisslap has no CPU fallback");
+    if (opt.device < 0 || opt.device >= ndev) return fail(MISSLAP_ERR_INVALID, "device %d out of range", opt.device);
+    HIP_TRY(hipSetDevice(opt.device));
+    hipStream_t st = nullptr;
+    if ((rc = dense_batch_stream(opt.device, &st))) return rc;
+    if ((rc = sync_device_inputs(&opt, st))) return rc;
+
+    const size_t nnz = (size_t)offsets[B];
+    DevScratch tmp;
+    const int32_t *d_loc = loc;
+    const double *d_val = val, *d_p0 = prices_in;
+    if (!opt.input_on_device) {
+        int32_t *p = nullptr;
+        double *q = nullptr;
+        if ((rc = tmp.alloc(&p, 2 * nnz)) || (rc = tmp.alloc(&q, nnz))) return rc;
+        HIP_TRY(hipMemcpyAsync(p, loc, sizeof(int32_t) * 2 * nnz, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(q, val, sizeof(double) * nnz, hipMemcpyHostToDevice, st));
+        d_loc = p;
+        d_val = q;
+        if (prices_in) {
+            double *r = nullptr;
+            const size_t pcells = (size_t)B * (size_t)prices_ld;
+            if ((rc = tmp.alloc(&r, pcells))) return rc;
+            HIP_TRY(hipMemcpyAsync(r, prices_in, sizeof(double) * pcells, hipMemcpyHostToDevice, st));
+            d_p0 = r;
+        }
+    }
+    long long *d_off = nullptr;
+    int *d_rs = nullptr;
+    float *d_eps = nullptr;
+    SparseBatchCheck *d_chk = nullptr;
+    misslap_dense_batch_meta *d_meta = nullptr;
+    if ((rc = tmp.alloc(&d_off, (size_t)B + 1)) || (rc = tmp.alloc(&d_rs, nnz + (size_t)B)) ||
+        (rc = tmp.alloc(&d_chk, (size_t)B)) || (rc = tmp.alloc(&d_meta, (size_t)B)))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(d_off, offsets, sizeof(int64_t) * ((size_t)B + 1), hipMemcpyHostToDevice, st));
+    if (eps_start) {
+        if ((rc = tmp.alloc(&d_eps, (size_t)B))) return rc;
+        HIP_TRY(hipMemcpyAsync(d_eps, eps_start, sizeof(float) * (size_t)B, hipMemcpyHostToDevice, st));
+    }
+
+    // ---- check pass: every problem before any is solved
+    hipLaunchKernelGGL(k_sparse_batch_check, dim3((unsigned)B), dim3(256), 0, st, d_loc, d_val, d_off, d_p0,
+                       (long long)prices_ld, d_rs, d_chk);
+    HIP_TRY(hipGetLastError());
+    std::vector<SparseBatchCheck> chk((size_t)B);
+    HIP_TRY(hipMemcpyAsync(chk.data(), d_chk, sizeof(SparseBatchCheck) * (size_t)B, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const double t_checked = now_ms();
+
+    // the checks of from_sparse ahead of its guard (:604-605)
+    auto pre_guard_error = [&](int64_t b, char *buf, size_t len) -> bool {
+        const int64_t z = offsets[b + 1] - offsets[b];
+        const int64_t N = sizes ? sizes[2 * b + 1] : (int64_t)chk[(size_t)b].max_row;  // sic, :592 / :594
+        if (z == 0)
+            snprintf(buf, len, "no entries");
+        else if (z < N)
+            snprintf(buf, len, "Matrix is infeasible - Fewer than %lld valid values provided for %lld rows.", (long long)N,
+                     (long long)N);
+        else
+            return false;
+        return true;
+    };
+    // the guard on the true graph, per problem on up to 16 host threads (device input: loc copied back once)
+    std::vector<std::string> guard_err;
+    if (cardinality_check) {
+        std::vector<int32_t> host_copy;
+        const int32_t *H = loc;
+        if (opt.input_on_device) {
+            host_copy.resize(2 * nnz);
+            HIP_TRY(hipMemcpy(host_copy.data(), loc, sizeof(int32_t) * 2 * nnz, hipMemcpyDeviceToHost));
+            H = host_copy.data();
+        }
+        guard_err.assign((size_t)B, std::string());
+        std::atomic<int64_t> next{0};
+        std::atomic<int> oom{0};
+        auto work = [&]() {
+            char buf[256];
+            for (int64_t b; (b = next.fetch_add(1)) < B;) {
+                if (pre_guard_error(b, buf, sizeof(buf))) continue;
+                const SparseBatchCheck &c = chk[(size_t)b];
+                try {
+                    // n_true = max row + 1, m_true = max column + 1 (int arithmetic of the front-end's int())
+                    if (!sparse_problem_guard(H + 2 * offsets[b], offsets[b + 1] - offsets[b], (int)((int64_t)c.max_row + 1),
+                                              (int)((int64_t)c.max_col + 1), buf, sizeof(buf)))
+                        guard_err[(size_t)b] = buf;
+                } catch (const std::bad_alloc &) {
+                    oom = 1;
+                }
+            }
+        };
+        const int nthr = (int)std::min<int64_t>(B, std::max(1u, std::min(16u, std::thread::hardware_concurrency())));
+        std::vector<std::thread> pool;
+        for (int t = 1; t < nthr; ++t) pool.emplace_back(work);
+        work();
+        for (auto &t : pool) t.join();
+        if (oom) return fail(MISSLAP_ERR_HIP, "out of host memory in the matching guard");
+    }
+    const double t_matched = now_ms();
+    int Ns = 1, Ms = 1;
+    for (int64_t b = 0; b < B; ++b) {
+        char buf[256];
+        const SparseBatchCheck &c = chk[(size_t)b];
+        if (pre_guard_error(b, buf, sizeof(buf))) return fail(MISSLAP_ERR_INVALID, "problem %lld: %s", (long long)b, buf);
+        if (cardinality_check && !guard_err[(size_t)b].empty())
+            return fail(MISSLAP_ERR_INVALID, "problem %lld: %s", (long long)b, guard_err[(size_t)b].c_str());
+        // AuctionSolver.__init__ (build_from_device_coo's checks and texts, in its order)
+        const char *bad = nullptr;
+        if (c.last_row < 0) bad = "negative row index";
+        else if (c.err & kErrColNegative) bad = "loc holds a negative row or column index";
+        else if (c.err & kErrRowsUnsorted) bad = "loc rows must be sorted in ascending order (auction_.pyx:33-48 contract)";
+        else if (c.err & kErrRowGap) bad = "every row 0..N-1 must have at least one entry (auction_.pyx:33-48 contract)";
+        else if (c.err & kErrNonFinite) bad = "val holds a NaN or an infinity";
+        else if (c.max_col >= 0x7ffffffe) bad = "column index too large (max + 1 must fit an int32)";
+        if (bad) return fail(MISSLAP_ERR_INVALID, "problem %lld: %s", (long long)b, bad);
+        const int n = c.last_row + 1, m = c.max_col + 1;
+        if (n > kSparseBatchMaxDim || m > kSparseBatchMaxDim)
+            return fail(MISSLAP_ERR_INVALID, "problem %lld: %d x %d exceeds MISSLAP_SPARSE_BATCH_MAX_DIM (%d); solve it with "
+                        "from_sparse / solve_batch", (long long)b, n, m, kSparseBatchMaxDim);
+        if (prices_in) {  // (the checks of AuctionSolver.resolve)
+            if (m > prices_ld)
+                return fail(MISSLAP_ERR_INVALID, "problem %lld: prices hold %lld columns, the problem has %d", (long long)b,
+                            (long long)prices_ld, m);
+            if (c.bad_price & 1) return fail(MISSLAP_ERR_INVALID, "problem %lld: prices hold a NaN or an infinity", (long long)b);
+            if (c.bad_price & 2)
+                return fail(MISSLAP_ERR_INVALID, "problem %lld: prices must be >= 0 (with the sign bit clear: -0.0 is "
+                            "rejected)", (long long)b);
+        }
+        if (n > sol_ld || (prices_out && m > prices_out_ld))
+            return fail(MISSLAP_ERR_INVALID, "problem %lld: %d x %d does not fit sol_ld = %lld / prices_out_ld = %lld",
+                        (long long)b, n, m, (long long)sol_ld, (long long)prices_out_ld);
+        Ns = std::max(Ns, n);
+        Ms = std::max(Ms, m);
+    }
+
+    // ---- the solve: one launch, one workgroup per problem
+    int32_t *d_sol = sol;
+    double *d_prices = prices_out;
+    if (!out_on_device) {
+        if ((rc = tmp.alloc(&d_sol, (size_t)B * (size_t)sol_ld))) return rc;
+        if (prices_out && (rc = tmp.alloc(&d_prices, (size_t)B * (size_t)prices_out_ld))) return rc;
+    }
+    SparseBatchArgs a;
+    a.loc = d_loc;
+    a.val = d_val;
+    a.offsets = d_off;
+    a.row_start = d_rs;
+    a.eps_b = d_eps;
+    a.eps_opt = opt.eps_start;
+    a.p0 = d_p0;
+    a.p0_ld = prices_ld;
+    a.chk = d_chk;
+    a.maximize = opt.maximize ? 1 : 0;
+    a.max_iter = opt.max_iter;
+    a.Ns = Ns;
+    a.Ms = Ms;
+    a.sol = d_sol;
+    a.sol_ld = sol_ld;
+    a.prices = d_prices;
+    a.prices_ld = prices_out_ld;
+    a.meta = d_meta;
+    // a wavefront bids for one list position at a time: enough wavefronts for the first round's bidders, at most 16
+    const int threads = Ns <= 256 ? 256 : (Ns <= 512 ? 512 : 1024);
+    const size_t lds = sparse_batch_lds_bytes(Ns, Ms);
+    if (lds > 65536)  // (per call: the > 64 KB dynamic-LDS opt-in is a property of the function on the current device)
+        HIP_TRY(hipFuncSetAttribute((const void *)k_sparse_batch_solve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    HIP_TRY(hipEventCreate(&ev[0]));
+    HIP_TRY(hipEventCreate(&ev[1]));
+    struct EvGuard {
+        hipEvent_t *e;
+        ~EvGuard() {
+            (void)hipEventDestroy(e[0]);
+            (void)hipEventDestroy(e[1]);
+        }
+    } ev_guard{ev};
+    HIP_TRY(hipEventRecord(ev[0], st));
+    hipLaunchKernelGGL(k_sparse_batch_solve, dim3((unsigned)B), dim3(threads), lds, st, a);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ev[1], st));
+    if (!out_on_device) {
+        HIP_TRY(hipMemcpyAsync(sol, d_sol, sizeof(int32_t) * (size_t)B * (size_t)sol_ld, hipMemcpyDeviceToHost, st));
+        if (prices_out)
+            HIP_TRY(hipMemcpyAsync(prices_out, d_prices, sizeof(double) * (size_t)B * (size_t)prices_out_ld,
+                                   hipMemcpyDeviceToHost, st));
+    }
+    if (meta) {
+        const size_t w = std::min((size_t)stride, sizeof(misslap_dense_batch_meta));
+        HIP_TRY(hipMemcpy2DAsync(meta, (size_t)stride, d_meta, sizeof(misslap_dense_batch_meta), w, (size_t)B,
+                                 hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    tmp.drained = true;
+    if (meta)  // (struct_size is an input field: the caller's value stays)
+        for (int64_t b = 0; b < B; ++b)
+            reinterpret_cast<misslap_dense_batch_meta *>(reinterpret_cast<char *>(meta) + (size_t)b * (size_t)stride)
+                ->struct_size = stride;
+    if (info) {
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
+        info->threads = threads;
+        info->lds_bytes = (int32_t)lds;
+        info->check_ms = t_checked - t_start;
+        info->matching_ms = t_matched - t_checked;
+        info->solve_ms = ms;
+        info->wall_ms = now_ms() - t_start;
+    }
+    return MISSLAP_OK;
+}

@@ -40,6 +40,7 @@
 #include "kernels_tiled.hpp"
 #include "kernels_warm.hpp"
 #include "kernels_dense_batch.hpp"
+#include "kernels_sparse_batch.hpp"
 
 using namespace misslap;
 
@@ -505,3 +506,4 @@ MISSLAP_API int misslap_get_state(misslap_solver *h, double *prices, int32_t *un
 #include "abi_diag.hpp"
 #include "abi_warm.hpp"
 #include "abi_dense_batch.hpp"
+#include "abi_sparse_batch.hpp"
