@@ -435,7 +435,9 @@ int misslap_solve_batch(misslap_solver *const *handles, int32_t n, int32_t *cons
  *                  opt->eps_start for every problem.  (The front-end's `fast` passes 1 / n_b here, :568-569.)
  *   prices_in      double[B][M] or NULL: problem b starts from prices_in[b][:m_b] as misslap_resolve does (every person
  *                  unassigned, its = nreductions = 0); finite and >= 0 with the sign bit clear.
- *   cardinality_check  != 0: the Hopcroft-Karp guard of _from_matrix (auction_.pyx:562-566), per problem, on the host.
+ *   cardinality_check  != 0: the Hopcroft-Karp guard of _from_matrix (auction_.pyx:562-566), per problem: for B >= 64 on
+ *                  the device (the kernel of misslap_matching_dense_batch, enqueued behind the validation pass), for
+ *                  smaller batches on the host.
  *   sol            int32[B][N]: sol[b][:n_b] the assignment (-1 = unassigned), -1 beyond n_b.
  *   prices_out     double[B][M] or NULL: final prices of the maximised problem; 0 beyond m_b.
  *   out_on_device  != 0: sol and prices_out are device pointers (meta is always host memory).
@@ -468,7 +470,7 @@ typedef struct misslap_dense_batch_info {
     int32_t threads;      /* workgroup size of the solve launch */
     int32_t lds_bytes;    /* dynamic LDS per workgroup */
     double check_ms;      /* validation launch + read-back (wall) */
-    double matching_ms;   /* host matching guard (wall) */
+    double matching_ms;   /* guard time: device kernel (HIP events) plus any host-guarded problems (wall) */
     double solve_ms;      /* the solve launch (HIP events) */
     double wall_ms;       /* the whole call */
 } misslap_dense_batch_info;
@@ -491,7 +493,10 @@ int misslap_solve_dense_batch(int64_t B, int64_t N, int64_t M, const double *mat
  *   eps_start      float[B] host array or NULL: as for misslap_solve_dense_batch (the front-end's `fast` passes 1 / N_b).
  *   prices_in      double[B][prices_ld] or NULL: problem b starts from prices_in[b][:n_cols_b] as misslap_resolve does;
  *                  prices_ld >= every n_cols_b.
- *   cardinality_check  != 0: _from_sparse's Hopcroft-Karp guard on the true graph (:608-612), per problem, on the host.
+ *   cardinality_check  != 0: _from_sparse's Hopcroft-Karp guard on the true graph (:608-612), per problem: for B >= 256
+ *                  on the device (the kernel of misslap_matching_batch) for problems whose graph the check pass found
+ *                  clean (rows ascending from 0 without a gap, no negative index) and within the cap, on the host for
+ *                  the rest and for smaller batches.
  *   sol            int32[B][sol_ld]: sol[b][:n_b] the assignment, -1 beyond.
  *   prices_out     double[B][prices_out_ld] or NULL: final prices of the maximised problem, 0 beyond n_cols_b.
  *   sol_ld, prices_out_ld   the caller's leading dimensions: at least the largest n_b / n_cols_b of the batch.  A caller
@@ -511,6 +516,49 @@ int misslap_solve_sparse_batch(int64_t B, const int32_t *loc, const double *val,
                                int32_t cardinality_check, const misslap_options *opt, int32_t *sol, int64_t sol_ld,
                                double *prices_out, int64_t prices_out_ld, int32_t out_on_device,
                                misslap_dense_batch_meta *meta, misslap_dense_batch_info *info);
+
+/* ---- the matching of many small graphs in one call: the batch form of misslap_hopcroft_karp / sslap.hopcroft_solve
+ * (feasibility_.pyx:227-283).  Each graph is matched by ONE workgroup of ONE launch, its state in LDS
+ * (csrc/kernels_matching_batch.hpp), and its result is exactly the reference's HopcroftKarpSolverCython.solve() on that
+ * graph (:95-225): the same size, Pair_U and Pair_V, not merely a maximum matching.  Graphs have at most
+ * MISSLAP_MATCHING_BATCH_MAX_DIM rows and columns (larger ones: misslap_hopcroft_karp / misslap_matching_gpu).
+ *   misslap_matching_batch        loc is int32[nnz][2]; graph b is the entries offsets[b] .. offsets[b + 1] (offsets:
+ *                                 host int64[B + 1], offsets[0] = 0, non-decreasing), rows ascending, read in stored
+ *                                 order; n_b = max row + 1, m_b = max column + 1 of the graph (:245-246), and a row
+ *                                 without entries is an isolated vertex.  A graph holds at most 2^31 - 129 entries.
+ *   misslap_matching_dense_batch  mat is double[B][N][M] (problem stride N * M, counted in 64 bits); graph b is
+ *                                 mat[b][:n_b][:m_b] with (n_b, m_b) = shapes[2b], shapes[2b + 1] (shapes NULL: N x M),
+ *                                 entry (i, j) iff mat[b][i][j] >= 0 (:256-262; NaN is not an entry, -0.0 and +inf are).
+ *   opt            device, input_on_device (loc / mat are device pointers) and input_stream, as for the batch solves;
+ *                  maximize, eps_start and max_iter are ignored, every other field must be 0.
+ *   size, n_rows, n_cols   host int32[B]: the cardinality and the graph's dimensions.
+ *   left_pairings  int32[B][left_ld] or NULL: Pair_U of graph b in [:n_b], -1 beyond (and for a free row).
+ *   right_pairings int32[B][right_ld] or NULL: Pair_V of graph b in [:m_b], -1 beyond.
+ *   out_on_device  != 0: the pairings are device pointers.
+ *   info           may be NULL; info->struct_size set to sizeof(misslap_matching_batch_info).
+ * All or nothing: every graph is checked before any is matched.  The first failing graph gives MISSLAP_ERR_INVALID and
+ * the text "graph <b>: <what>", <what> one of "no entries", misslap_hopcroft_karp's own texts ("loc entry k = (i, j)
+ * outside n x m" with k counted in the graph, "loc rows must be sorted in ascending order"), "n x m exceeds
+ * MISSLAP_MATCHING_BATCH_MAX_DIM (2048)", a shape outside the stack, or dimensions that do not fit the leading
+ * dimensions. */
+#define MISSLAP_MATCHING_BATCH_MAX_DIM 2048
+typedef struct misslap_matching_batch_info {
+    int32_t struct_size;  /* IN: sizeof(misslap_matching_batch_info) */
+    int32_t threads;      /* workgroup size of the matching launch */
+    int32_t lds_bytes;    /* dynamic LDS per workgroup */
+    int32_t reserved;
+    double check_ms;      /* upload + argument checks (wall) */
+    double kernel_ms;     /* the matching launch (HIP events) */
+    double wall_ms;       /* the whole call */
+} misslap_matching_batch_info;
+int misslap_matching_batch(int64_t B, const int32_t *loc, const int64_t *offsets, const misslap_options *opt,
+                           int32_t *size, int32_t *n_rows, int32_t *n_cols, int32_t *left_pairings, int64_t left_ld,
+                           int32_t *right_pairings, int64_t right_ld, int32_t out_on_device,
+                           misslap_matching_batch_info *info);
+int misslap_matching_dense_batch(int64_t B, int64_t N, int64_t M, const double *mat, const int32_t *shapes,
+                                 const misslap_options *opt, int32_t *size, int32_t *n_rows, int32_t *n_cols,
+                                 int32_t *left_pairings, int64_t left_ld, int32_t *right_pairings, int64_t right_ld,
+                                 int32_t out_on_device, misslap_matching_batch_info *info);
 
 const char *misslap_last_error(void);
 int misslap_abi_version(void);

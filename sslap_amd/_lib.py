@@ -73,8 +73,15 @@ class DenseBatchInfo(C.Structure):
                 ("solve_ms", C.c_double), ("wall_ms", C.c_double)]
 
 
+class MatchingBatchInfo(C.Structure):
+    """misslap_matching_batch_info (struct_size set by the caller)."""
+    _fields_ = [("struct_size", C.c_int32), ("threads", C.c_int32), ("lds_bytes", C.c_int32), ("reserved", C.c_int32),
+                ("check_ms", C.c_double), ("kernel_ms", C.c_double), ("wall_ms", C.c_double)]
+
+
 DENSE_BATCH_MAX_DIM = 1024  # MISSLAP_DENSE_BATCH_MAX_DIM
 SPARSE_BATCH_MAX_DIM = 2048  # MISSLAP_SPARSE_BATCH_MAX_DIM
+MATCHING_BATCH_MAX_DIM = 2048  # MISSLAP_MATCHING_BATCH_MAX_DIM
 
 
 def new_meta():
@@ -165,6 +172,11 @@ SYMBOLS = {
     "misslap_solve_sparse_batch": (C.c_int, [C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int64, C.c_int32,
                                              C.POINTER(Options), _VP, C.c_int64, _VP, C.c_int64, C.c_int32,
                                              C.POINTER(DenseBatchMeta), C.POINTER(DenseBatchInfo)]),
+    "misslap_matching_batch": (C.c_int, [C.c_int64, _VP, _VP, C.POINTER(Options), _VP, _VP, _VP, _VP, C.c_int64, _VP,
+                                         C.c_int64, C.c_int32, C.POINTER(MatchingBatchInfo)]),
+    "misslap_matching_dense_batch": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, _VP, _VP, C.POINTER(Options), _VP, _VP,
+                                               _VP, _VP, C.c_int64, _VP, C.c_int64, C.c_int32,
+                                               C.POINTER(MatchingBatchInfo)]),
     "misslap_last_error": (C.c_char_p, []),
     "misslap_abi_version": (C.c_int, []),
 }

@@ -139,9 +139,38 @@ MISSLAP_API int misslap_solve_sparse_batch(int64_t B, const int32_t *loc, const 
     hipLaunchKernelGGL(k_sparse_batch_check, dim3((unsigned)B), dim3(256), 0, st, d_loc, d_val, d_off, d_p0,
                        (long long)prices_ld, d_rs, d_chk);
     HIP_TRY(hipGetLastError());
+    // The matching guard on the device, behind the check pass and read back with it, for every problem whose graph the
+    // check pass finds clean (rows ascending from 0 without a gap, no negative index) and within the cap: card[b] >= 0.
+    // The carve is sized before the maxima are known: a clean graph has at most as many rows as entries.  Small batches
+    // keep the host guard for every problem (card[b] = -1; sparse_guard_on_device).
+    const bool device_guard = cardinality_check && sparse_guard_on_device(B);
+    std::vector<int> card((size_t)B, -1);
+    GuardEvents gev;
+    if (device_guard) {
+        int64_t zmax = 1;
+        for (int64_t b = 0; b < B; ++b) zmax = std::max<int64_t>(zmax, offsets[b + 1] - offsets[b]);
+        int *d_card = nullptr;
+        if ((rc = tmp.alloc(&d_card, (size_t)B))) return rc;
+        MatchBatchArgs g{};
+        g.loc = d_loc;
+        g.offsets = d_off;
+        g.schk = d_chk;
+        g.Ns = (int)std::min<int64_t>(zmax, kSparseBatchMaxDim);
+        g.Ms = kSparseBatchMaxDim;
+        g.size = d_card;
+        if ((rc = gev.create())) return rc;
+        HIP_TRY(hipEventRecord(gev.e[0], st));
+        hipLaunchKernelGGL(k_matching_batch<false>, dim3((unsigned)B), dim3(kMatchBatchThreads),
+                           matching_batch_lds_bytes(g.Ns, g.Ms, false), st, g);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(gev.e[1], st));
+        HIP_TRY(hipMemcpyAsync(card.data(), d_card, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost, st));
+    }
     std::vector<SparseBatchCheck> chk((size_t)B);
     HIP_TRY(hipMemcpyAsync(chk.data(), d_chk, sizeof(SparseBatchCheck) * (size_t)B, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
+    double guard_ms = 0;
+    if (device_guard && (rc = gev.elapsed(&guard_ms))) return rc;
     const double t_checked = now_ms();
 
     // the checks of from_sparse ahead of its guard (:604-605)
@@ -157,27 +186,67 @@ MISSLAP_API int misslap_solve_sparse_batch(int64_t B, const int32_t *loc, const 
             return false;
         return true;
     };
-    // the guard on the true graph, per problem on up to 16 host threads (device input: loc copied back once)
+    // the guard on the true graph: the device's cardinality where it has one, else per problem on up to 16 host threads
+    // (device input: only those problems' loc slices are copied back)
     std::vector<std::string> guard_err;
     if (cardinality_check) {
-        std::vector<int32_t> host_copy;
-        const int32_t *H = loc;
-        if (opt.input_on_device) {
-            host_copy.resize(2 * nnz);
-            HIP_TRY(hipMemcpy(host_copy.data(), loc, sizeof(int32_t) * 2 * nnz, hipMemcpyDeviceToHost));
-            H = host_copy.data();
-        }
         guard_err.assign((size_t)B, std::string());
+        std::vector<int64_t> on_host;
+        for (int64_t b = 0; b < B; ++b) {
+            char buf[256];
+            if (pre_guard_error(b, buf, sizeof(buf))) continue;
+            const int card_b = card[(size_t)b];
+            if (card_b < 0) {
+                on_host.push_back(b);
+                continue;
+            }
+            const int n_true = chk[(size_t)b].max_row + 1;
+            if (card_b < n_true) {
+                snprintf(buf, sizeof(buf), "Matrix is infeasible (Maximum matching possible only involves %d out of %d rows.)",
+                         card_b, n_true);
+                guard_err[(size_t)b] = buf;
+            }
+        }
+        // Device input: the host copy the host guard reads.  Without the device guard that is the whole of loc in one
+        // copy, as before; with it, only the host-guarded problems' entries, one copy per run of problems whose entries
+        // are adjacent in loc.  host_at[t]: where problem on_host[t] starts in host_copy.
+        std::vector<int32_t> host_copy;
+        std::vector<int64_t> host_at;
+        if (opt.input_on_device && !on_host.empty()) {
+            if (!device_guard) {
+                host_copy.resize(2 * nnz);
+                HIP_TRY(hipMemcpy(host_copy.data(), loc, sizeof(int32_t) * 2 * nnz, hipMemcpyDeviceToHost));
+                for (int64_t b : on_host) host_at.push_back(offsets[b]);
+            } else {
+                int64_t total = 0;
+                for (int64_t b : on_host) {
+                    host_at.push_back(total);
+                    total += offsets[b + 1] - offsets[b];
+                }
+                host_copy.resize(2 * (size_t)total);
+                for (size_t t = 0; t < on_host.size();) {
+                    size_t u = t + 1;  // the run on_host[t .. u)
+                    while (u < on_host.size() && offsets[on_host[u]] == offsets[on_host[u - 1] + 1]) ++u;
+                    const int64_t first = offsets[on_host[t]], last = offsets[on_host[u - 1] + 1];
+                    HIP_TRY(hipMemcpyAsync(host_copy.data() + 2 * host_at[t], loc + 2 * first,
+                                           sizeof(int32_t) * 2 * (size_t)(last - first), hipMemcpyDeviceToHost, st));
+                    t = u;
+                }
+                HIP_TRY(hipStreamSynchronize(st));
+            }
+        }
         std::atomic<int64_t> next{0};
         std::atomic<int> oom{0};
+        const int64_t nh = (int64_t)on_host.size();
         auto work = [&]() {
             char buf[256];
-            for (int64_t b; (b = next.fetch_add(1)) < B;) {
-                if (pre_guard_error(b, buf, sizeof(buf))) continue;
+            for (int64_t t; (t = next.fetch_add(1)) < nh;) {
+                const int64_t b = on_host[(size_t)t];
                 const SparseBatchCheck &c = chk[(size_t)b];
+                const int32_t *H = opt.input_on_device ? host_copy.data() + 2 * host_at[(size_t)t] : loc + 2 * offsets[b];
                 try {
                     // n_true = max row + 1, m_true = max column + 1 (int arithmetic of the front-end's int())
-                    if (!sparse_problem_guard(H + 2 * offsets[b], offsets[b + 1] - offsets[b], (int)((int64_t)c.max_row + 1),
+                    if (!sparse_problem_guard(H, offsets[b + 1] - offsets[b], (int)((int64_t)c.max_row + 1),
                                               (int)((int64_t)c.max_col + 1), buf, sizeof(buf)))
                         guard_err[(size_t)b] = buf;
                 } catch (const std::bad_alloc &) {
@@ -185,7 +254,7 @@ MISSLAP_API int misslap_solve_sparse_batch(int64_t B, const int32_t *loc, const 
                 }
             }
         };
-        const int nthr = (int)std::min<int64_t>(B, std::max(1u, std::min(16u, std::thread::hardware_concurrency())));
+        const int nthr = (int)std::min<int64_t>(nh, std::max(1u, std::min(16u, std::thread::hardware_concurrency())));
         std::vector<std::thread> pool;
         for (int t = 1; t < nthr; ++t) pool.emplace_back(work);
         work();
@@ -296,8 +365,8 @@ MISSLAP_API int misslap_solve_sparse_batch(int64_t B, const int32_t *loc, const 
         HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
         info->threads = threads;
         info->lds_bytes = (int32_t)lds;
-        info->check_ms = t_checked - t_start;
-        info->matching_ms = t_matched - t_checked;
+        info->check_ms = t_checked - t_start - guard_ms;
+        info->matching_ms = guard_ms + (t_matched - t_checked);
         info->solve_ms = ms;
         info->wall_ms = now_ms() - t_start;
     }

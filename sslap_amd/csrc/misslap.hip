@@ -41,6 +41,7 @@
 #include "kernels_warm.hpp"
 #include "kernels_dense_batch.hpp"
 #include "kernels_sparse_batch.hpp"
+#include "kernels_matching_batch.hpp"
 
 using namespace misslap;
 
@@ -507,3 +508,4 @@ MISSLAP_API int misslap_get_state(misslap_solver *h, double *prices, int32_t *un
 #include "abi_warm.hpp"
 #include "abi_dense_batch.hpp"
 #include "abi_sparse_batch.hpp"
+#include "abi_matching_batch.hpp"

@@ -1,0 +1,193 @@
+"""Maximum matching of many small bipartite graphs in one call (misslap_matching_batch / misslap_matching_dense_batch,
+include/misslap.h).
+
+The batch form of `hopcroft_solve(loc=)` / `hopcroft_solve(mat=)`: graph b is matched by one workgroup of one launch,
+and its result is exactly the reference's HopcroftKarpSolverCython.solve() on that graph -- the same size and the same
+pairing arrays (csrc/kernels_matching_batch.hpp).  The reference has no counterpart; it matches one graph per call.
+"""
+import ctypes as C
+import os
+
+import numpy as np
+
+from . import _lib
+from .auction_solve import _ENV_DEVICE, _cname
+from .dense_batch import _is_device_tensor
+from .sparse_batch import _maxima
+
+MAX_DIM = _lib.MATCHING_BATCH_MAX_DIM
+
+
+def _pack(locs):
+    """A list of per-graph loc arrays -> (loc int32, offsets) on the host (cast to int32 as hopcroft_solve does)."""
+    out = []
+    for b, lb in enumerate(locs):
+        if not isinstance(lb, np.ndarray):
+            raise TypeError(f"graph {b}: loc must be a numpy array")
+        if lb.ndim != 2 or lb.shape[1] != 2 or not np.issubdtype(lb.dtype, np.integer):
+            raise ValueError(f"graph {b}: loc must be an integer array of shape (nnz, 2), got {lb.dtype} {lb.shape}")
+        out.append(lb.astype(np.int32))
+    if not out:
+        raise ValueError("no graphs given")
+    counts = np.array([x.shape[0] for x in out], dtype=np.int64)
+    offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    return np.ascontiguousarray(np.concatenate(out, axis=0).reshape(-1, 2), dtype=np.int32), offsets
+
+
+def _check_loc(loc, offsets):
+    """loc (numpy integer or device int32, (nnz, 2)) and host offsets; returns (loc, B, offsets int64, on_device)."""
+    if isinstance(loc, np.ndarray):
+        on_device = False
+        if loc.ndim != 2 or loc.shape[1] != 2:
+            raise ValueError(f"loc must have shape (nnz, 2), got {loc.shape}")
+        if not np.issubdtype(loc.dtype, np.integer):
+            raise ValueError(f"loc must be an integer array, got {loc.dtype}")
+        loc = np.ascontiguousarray(loc, dtype=np.int32)
+    elif _is_device_tensor(loc):
+        import torch
+        on_device = True
+        if loc.dim() != 2 or loc.shape[1] != 2:
+            raise ValueError(f"loc must have shape (nnz, 2), got {tuple(loc.shape)}")
+        if loc.dtype != torch.int32:
+            raise ValueError(f"loc must be int32, got {loc.dtype}")
+        if not loc.is_contiguous():
+            raise ValueError("a device tensor must be contiguous (it is read in place)")
+    else:
+        raise TypeError("loc must be a numpy array, a contiguous int32 tensor on the device or a list of numpy arrays")
+    nnz = int(loc.shape[0])
+    if offsets is None:
+        raise ValueError("offsets is required with a packed loc (a list of per-graph loc arrays needs none)")
+    if _is_device_tensor(offsets):
+        raise TypeError("offsets must be a host array")
+    off = np.asarray(offsets)
+    if off.ndim != 1 or off.shape[0] < 2 or not np.issubdtype(off.dtype, np.integer):
+        raise ValueError(f"offsets must be a 1-d integer array of length B + 1 >= 2, got {off.dtype} {off.shape}")
+    off = off.astype(np.int64)
+    if off[0] != 0 or off[-1] != nnz:
+        raise ValueError(f"offsets must start at 0 and end at nnz = {nnz}, got {int(off[0])} .. {int(off[-1])}")
+    if (np.diff(off) < 0).any():
+        b = int(np.flatnonzero(np.diff(off) < 0)[0])
+        raise ValueError(f"offsets must be non-decreasing (offsets[{b}] > offsets[{b + 1}])")
+    return loc, off.shape[0] - 1, np.ascontiguousarray(off), on_device
+
+
+def _check_mats(mats, shapes):
+    """mats (numpy or device float64, (B, N, M)) and optional shapes; returns (B, N, M, shapes int32 or None, on_device)."""
+    if isinstance(mats, np.ndarray):
+        on_device = False
+        if mats.ndim != 3:
+            raise ValueError(f"mats must have 3 dimensions (B, N, M), got {mats.ndim}")
+        if mats.dtype != np.float64:
+            raise ValueError(f"Buffer dtype mismatch, expected 'double' but got '{_cname(mats.dtype)}'")
+    elif _is_device_tensor(mats):
+        import torch
+        on_device = True
+        if mats.dim() != 3:
+            raise ValueError(f"mats must have 3 dimensions (B, N, M), got {mats.dim()}")
+        if mats.dtype != torch.float64:
+            raise ValueError(f"mats must be float64, got {mats.dtype}")
+        if not mats.is_contiguous():
+            raise ValueError("a device tensor must be contiguous (it is read in place)")
+    else:
+        raise TypeError("mats must be a numpy array or a contiguous tensor on the device")
+    B, N, M = (int(d) for d in mats.shape)
+    if B < 1 or N < 1 or M < 1:
+        raise ValueError(f"empty stack of shape {(B, N, M)}")
+    if shapes is None:
+        if N > MAX_DIM or M > MAX_DIM:
+            raise ValueError(f"graph 0: {N} x {M} exceeds MISSLAP_MATCHING_BATCH_MAX_DIM ({MAX_DIM})")
+        return B, N, M, None, on_device
+    s = np.asarray(shapes)
+    if s.shape != (B, 2) or not np.issubdtype(s.dtype, np.integer):
+        raise ValueError(f"shapes must be an integer array of shape ({B}, 2), got {s.dtype} {s.shape}")
+    bad = (s[:, 0] < 1) | (s[:, 0] > N) | (s[:, 1] < 1) | (s[:, 1] > M)
+    if bad.any():
+        b = int(np.flatnonzero(bad)[0])
+        raise ValueError(f"graph {b}: shape ({int(s[b, 0])}, {int(s[b, 1])}) outside 1 .. {N} x 1 .. {M}")
+    big = (s[:, 0] > MAX_DIM) | (s[:, 1] > MAX_DIM)
+    if big.any():
+        b = int(np.flatnonzero(big)[0])
+        raise ValueError(f"graph {b}: {int(s[b, 0])} x {int(s[b, 1])} exceeds MISSLAP_MATCHING_BATCH_MAX_DIM ({MAX_DIM})")
+    return B, N, M, np.ascontiguousarray(s, dtype=np.int32), on_device
+
+
+def _options(on_device, dev_tensor):
+    opts = _lib.Options()
+    opts.struct_size = C.sizeof(_lib.Options)
+    opts.device = int(os.environ.get(_ENV_DEVICE, 0))
+    stream = None
+    if on_device:
+        import torch
+        if dev_tensor.device.index is not None:
+            opts.device = dev_tensor.device.index
+        stream = torch.cuda.current_stream(dev_tensor.device).cuda_stream
+    opts.input_on_device = 1 if on_device else 0
+    opts.input_stream = None if stream is None else C.c_void_p(int(stream))
+    return opts
+
+
+def hopcroft_solve_batch(loc=None, offsets=None, mats=None, shapes=None):
+    """Maximum matching of B small bipartite graphs in one call, one workgroup per graph.
+
+    Exactly ONE of
+    loc:  a packed integer (nnz, 2) array of edges (i, j), numpy or a contiguous int32 tensor on the device (read in
+          place, ordered behind torch.cuda.current_stream()); graph b is the entries offsets[b]:offsets[b + 1] (a host
+          integer array of length B + 1), rows ascending, n_b = max row + 1 and m_b = max column + 1 of the graph.  Or a
+          list of per-graph loc numpy arrays, with offsets None.
+    mats: a float64 (B, N, M) stack, numpy or a contiguous device tensor; graph b is mats[b, :n_b, :m_b] with
+          (n_b, m_b) = shapes[b] (optional integer (B, 2); default N x M), edge (i, j) iff the entry is >= 0.
+    A graph has at most MISSLAP_MATCHING_BATCH_MAX_DIM rows and columns.
+
+    Returns dict(size=int32 (B,), left_pairings=int32 (B, Nmax), right_pairings=int32 (B, Mmax), n_rows, n_cols);
+    row b equals hopcroft_solve(loc=loc_b) / hopcroft_solve(mat=mats[b, :n_b, :m_b]) on [:n_b] / [:m_b], -1 beyond.
+    Device input gives device tensors for the pairings.  All or nothing: a failing graph raises
+    ValueError("graph <b>: ...") and nothing is matched.  The caller's arrays are never written.
+    """
+    if (loc is None) == (mats is None):
+        raise ValueError("exactly one of loc and mats must be given")
+    if mats is not None:
+        if offsets is not None:
+            raise TypeError("offsets goes with loc, not with mats")
+        B, N, M, shp, on_device = _check_mats(mats, shapes)
+        Nmax = int(shp[:, 0].max()) if shp is not None else N
+        Mmax = int(shp[:, 1].max()) if shp is not None else M
+        src = mats
+    else:
+        if shapes is not None:
+            raise TypeError("shapes goes with mats, not with loc")
+        if isinstance(loc, (list, tuple)):
+            if offsets is not None:
+                raise TypeError("a list of per-graph loc arrays takes no offsets")
+            loc, offsets = _pack(loc)
+        loc, B, off, on_device = _check_loc(loc, offsets)
+        max_row, max_col, _ = _maxima(loc, off, on_device, per_problem=False)
+        Nmax = min(max(max_row + 1, 1), MAX_DIM)  # (a graph beyond the cap is rejected by the library, in its order)
+        Mmax = min(max(max_col + 1, 1), MAX_DIM)
+        src = loc
+    opts = _options(on_device, src)
+    size = np.empty(B, dtype=np.int32)
+    n_rows = np.empty(B, dtype=np.int32)
+    n_cols = np.empty(B, dtype=np.int32)
+    if on_device:
+        import torch
+        left = torch.empty((B, Nmax), dtype=torch.int32, device=src.device)
+        right = torch.empty((B, Mmax), dtype=torch.int32, device=src.device)
+        left_ptr, right_ptr, src_ptr = left.data_ptr(), right.data_ptr(), src.data_ptr()
+    else:
+        left = np.empty((B, Nmax), dtype=np.int32)
+        right = np.empty((B, Mmax), dtype=np.int32)
+        src = np.ascontiguousarray(src)
+        left_ptr, right_ptr, src_ptr = left.ctypes.data, right.ctypes.data, src.ctypes.data
+    info = _lib.MatchingBatchInfo()
+    info.struct_size = C.sizeof(_lib.MatchingBatchInfo)
+    outs = (size.ctypes.data, n_rows.ctypes.data, n_cols.ctypes.data, C.c_void_p(left_ptr), Nmax, C.c_void_p(right_ptr),
+            Mmax, 1 if on_device else 0, C.byref(info))
+    lib = _lib.load()
+    if mats is not None:
+        _lib.check(lib.misslap_matching_dense_batch(B, N, M, C.c_void_p(src_ptr),
+                                                    None if shp is None else shp.ctypes.data, C.byref(opts), *outs))
+    else:
+        _lib.check(lib.misslap_matching_batch(B, C.c_void_p(src_ptr), off.ctypes.data, C.byref(opts), *outs))
+    return dict(size=size, left_pairings=left, right_pairings=right, n_rows=n_rows, n_cols=n_cols,
+                gpu=dict(threads=int(info.threads), lds_bytes=int(info.lds_bytes), check_ms=float(info.check_ms),
+                         kernel_ms=float(info.kernel_ms), wall_ms=float(info.wall_ms)))
