@@ -1,0 +1,189 @@
+"""Plumbing shared by the one-workgroup-per-problem wrappers: dense_batch, sparse_batch and matching_batch.
+
+Argument checks that raise before the library is called, the options of the call and the decoding of its per-problem
+records.  The library is reached through `_lib.load()` at call time, never through a name bound here.
+"""
+import ctypes as C
+import os
+
+import numpy as np
+
+from . import _lib
+from .auction_solve import _ENV_DEVICE, _cname
+
+
+def _is_device_tensor(x):
+    return hasattr(x, "data_ptr") and getattr(x, "is_cuda", False)
+
+
+def _check_stack(mats):
+    """dtype / rank / layout of a float64 (B, N, M) stack (numpy array or device tensor); returns (B, N, M, on_device).
+    The cap is the caller's check."""
+    if isinstance(mats, np.ndarray):
+        on_device = False
+        if mats.ndim != 3:
+            raise ValueError(f"mats must have 3 dimensions (B, N, M), got {mats.ndim}")
+        if mats.dtype != np.float64:
+            raise ValueError(f"Buffer dtype mismatch, expected 'double' but got '{_cname(mats.dtype)}'")
+    elif _is_device_tensor(mats):
+        import torch
+        on_device = True
+        if mats.dim() != 3:
+            raise ValueError(f"mats must have 3 dimensions (B, N, M), got {mats.dim()}")
+        if mats.dtype != torch.float64:
+            raise ValueError(f"mats must be float64, got {mats.dtype}")
+        if not mats.is_contiguous():
+            raise ValueError("a device tensor must be contiguous (it is read in place)")
+    else:
+        raise TypeError("mats must be a numpy array or a contiguous tensor on the device")
+    B, N, M = (int(d) for d in mats.shape)
+    if B < 1 or N < 1 or M < 1:
+        raise ValueError(f"empty stack of shape {(B, N, M)}")
+    return B, N, M, on_device
+
+
+def _check_shapes(shapes, B, N, M, what):
+    """Optional integer (B, 2) shapes within the stack; returns them as int32 or None.  what: "problem" / "graph"."""
+    if shapes is None:
+        return None
+    s = np.asarray(shapes)
+    if s.shape != (B, 2) or not np.issubdtype(s.dtype, np.integer):
+        raise ValueError(f"shapes must be an integer array of shape ({B}, 2), got {s.dtype} {s.shape}")
+    bad = (s[:, 0] < 1) | (s[:, 0] > N) | (s[:, 1] < 1) | (s[:, 1] > M)
+    if bad.any():
+        b = int(np.flatnonzero(bad)[0])
+        raise ValueError(f"{what} {b}: shape ({int(s[b, 0])}, {int(s[b, 1])}) outside 1 .. {N} x 1 .. {M}")
+    return np.ascontiguousarray(s, dtype=np.int32)
+
+
+def _check_offsets(offsets, nnz, missing):
+    """Host offsets of B problems over nnz packed entries; returns (B, offsets int64).  missing: the text without them."""
+    if offsets is None:
+        raise ValueError(missing)
+    if _is_device_tensor(offsets):
+        raise TypeError("offsets must be a host array")
+    off = np.asarray(offsets)
+    if off.ndim != 1 or off.shape[0] < 2 or not np.issubdtype(off.dtype, np.integer):
+        raise ValueError(f"offsets must be a 1-d integer array of length B + 1 >= 2, got {off.dtype} {off.shape}")
+    off = off.astype(np.int64)
+    if off[0] != 0 or off[-1] != nnz:
+        raise ValueError(f"offsets must start at 0 and end at nnz = {nnz}, got {int(off[0])} .. {int(off[-1])}")
+    if (np.diff(off) < 0).any():
+        b = int(np.flatnonzero(np.diff(off) < 0)[0])
+        raise ValueError(f"offsets must be non-decreasing (offsets[{b}] > offsets[{b + 1}])")
+    return off.shape[0] - 1, np.ascontiguousarray(off)
+
+
+def _maxima(loc, offsets, on_device, per_problem):
+    """(max row, max column) over all of loc, and per problem the max row (per_problem; empty problems: 0)."""
+    B = offsets.shape[0] - 1
+    nnz = int(offsets[-1])
+    if nnz == 0:
+        return -1, -1, np.zeros(B, dtype=np.int64)
+    starts = offsets[:-1]
+    nonempty = offsets[1:] > starts
+    rows = np.zeros(B, dtype=np.int64)
+    if on_device:
+        import torch
+        mx = loc.amax(dim=0).cpu().numpy()  # (ordered behind the current stream, like every read of loc)
+        if per_problem:
+            counts = torch.from_numpy(np.diff(offsets)).to(loc.device)
+            seg = torch.repeat_interleave(torch.arange(B, device=loc.device), counts)
+            r = torch.full((B,), np.iinfo(np.int32).min, dtype=torch.int32, device=loc.device)
+            r = r.scatter_reduce(0, seg, loc[:, 0], reduce="amax", include_self=True)
+            rows = r.cpu().numpy().astype(np.int64)
+    else:
+        mx = (loc[:, 0].max(), loc[:, 1].max())  # (a column at a time: 25x faster than an axis-0 reduction of (nnz, 2))
+        if per_problem:
+            rows[nonempty] = np.maximum.reduceat(loc[:, 0], starts[nonempty])
+    rows[~nonempty] = 0
+    return int(mx[0]), int(mx[1]), rows
+
+
+def _starting_prices(prices, B, cols, exact, on_device, src, need):
+    """Optional float64 starting prices of shape (B, cols) (exact) or (B, P) with P >= cols, on the host or, with device
+    input, on the device (src: the device input, need: what it is called in the error text).  Returns (buffer to keep
+    alive, pointer, leading dimension); (None, None, 0) without prices."""
+    if prices is None:
+        return None, None, 0
+    want = f"({B}, {cols})" if exact else f"({B}, P) with P >= {cols}"
+
+    def bad_shape(shape):
+        return shape != (B, cols) if exact else len(shape) != 2 or shape[0] != B or shape[1] < cols
+
+    if isinstance(prices, np.ndarray):
+        if prices.dtype != np.float64:
+            raise ValueError(f"Buffer dtype mismatch, expected 'double' but got '{_cname(prices.dtype)}'")
+        if bad_shape(tuple(prices.shape)):
+            raise ValueError(f"prices must have shape {want}, got {tuple(prices.shape)}")
+        if on_device:
+            import torch
+            p = torch.from_numpy(np.ascontiguousarray(prices)).to(src.device)
+            return p, p.data_ptr(), int(prices.shape[1])
+        p = np.ascontiguousarray(prices)
+        return p, p.ctypes.data, int(prices.shape[1])
+    if _is_device_tensor(prices):
+        import torch
+        if not on_device:
+            raise TypeError(f"prices on the device need {need} on the device")
+        if prices.dtype != torch.float64:
+            raise ValueError(f"prices must be float64, got {prices.dtype}")
+        if bad_shape(tuple(prices.shape)):
+            raise ValueError(f"prices must have shape {want}, got {tuple(prices.shape)}")
+        p = prices.contiguous()
+        return p, p.data_ptr(), int(prices.shape[1])
+    raise TypeError("prices must be a numpy array or a tensor on the device")
+
+
+def _options(on_device, src, **fields):
+    """The Options of a batch call: the device (the device input's, else the environment's), the input stream (the
+    current stream of the device input's device) and `fields`.  No tuning knob applies to these paths: only the fields
+    the entry point reads are set."""
+    opts = _lib.Options()
+    opts.struct_size = C.sizeof(_lib.Options)
+    opts.device = int(os.environ.get(_ENV_DEVICE, 0))
+    stream = None
+    if on_device:
+        import torch
+        if src.device.index is not None:
+            opts.device = src.device.index
+        stream = torch.cuda.current_stream(src.device).cuda_stream
+    for name, value in fields.items():
+        setattr(opts, name, value)
+    opts.input_on_device = 1 if on_device else 0
+    opts.input_stream = None if stream is None else C.c_void_p(int(stream))
+    return opts
+
+
+def _solve_options(on_device, src, problem, eps_start, max_iter):
+    # (every string other than 'min' is 'max', auction_.pyx:236)
+    return _options(on_device, src, maximize=1 if problem != "min" else 0, eps_start=float(np.float32(eps_start)),
+                    max_iter=int(max_iter))
+
+
+def _new_meta(B):
+    """The per-problem records and the info of a solve call, struct_size set."""
+    metas = (_lib.DenseBatchMeta * B)()
+    metas[0].struct_size = C.sizeof(_lib.DenseBatchMeta)
+    return metas, _lib.DenseBatchInfo()
+
+
+def _decode_meta(metas, info):
+    """misslap_dense_batch_meta records and misslap_dense_batch_info -> the meta dict of length-B arrays."""
+    raw = np.ctypeslib.as_array(metas)  # structured view, one record per problem
+    obj_f32 = raw["obj_f32"].astype(np.float32)
+    start_f32, final_f32 = raw["start_eps"].astype(np.float32), raw["final_eps"].astype(np.float32)
+    meta = dict(
+        its=raw["its"].astype(np.int64), nreductions=raw["nreductions"].astype(np.int64), eCE=raw["eCE"].astype(np.int64),
+        soln_found=raw["soln_found"].astype(np.int64), n_assigned=raw["n_assigned"].astype(np.int64),
+        # rounded as the reference rounds them (auction_.pyx:264, :302-303: Python's round of the float)
+        obj=np.array([round(float(x), 3) for x in obj_f32]), obj_f64=raw["obj_f64"].astype(np.float64),
+        start_eps=np.array([round(float(x), 3) for x in start_f32]),
+        final_eps=np.array([round(float(x), 3) for x in final_f32]),
+        start_eps_f32=start_f32, final_eps_f32=final_f32, n_rows=raw["n_rows"].astype(np.int64),
+        n_cols=raw["n_cols"].astype(np.int64), nnz=raw["nnz"].astype(np.int64), bids_made=raw["bids_made"].astype(np.int64),
+    )
+    meta["timer"] = {"solve": f"{info.wall_ms:.2f}ms"}
+    meta["gpu"] = dict(threads=int(info.threads), lds_bytes=int(info.lds_bytes), check_ms=float(info.check_ms),
+                       matching_ms=float(info.matching_ms), kernel_ms=float(info.solve_ms), wall_ms=float(info.wall_ms))
+    return meta

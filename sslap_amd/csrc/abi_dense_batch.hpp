@@ -1,24 +1,9 @@
 // abi_dense_batch.hpp -- C ABI: many small dense problems in one call, one workgroup per problem
-// (misslap_solve_dense_batch; the kernels are in kernels_dense_batch.hpp).
-// (part of the single translation unit misslap.hip; included in the order given there)
+// (misslap_solve_dense_batch; the kernels are in kernels_dense_batch.hpp, the shared host helpers in abi_batch_common.hpp).
+// (part of the single translation unit misslap.hip; included in the order given there, after abi_batch_common.hpp)
 #pragma once
 
 namespace {
-// the calling thread's stream on a device (created on first use, kept for the life of the thread's process)
-int dense_batch_stream(int device, hipStream_t *out) {
-    static thread_local std::vector<std::pair<int, hipStream_t>> streams;
-    for (const auto &s : streams)
-        if (s.first == device) {
-            *out = s.second;
-            return MISSLAP_OK;
-        }
-    hipStream_t st = nullptr;
-    HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    streams.emplace_back(device, st);
-    *out = st;
-    return MISSLAP_OK;
-}
-
 // "v >= 0" of _from_matrix (auction_.pyx:549) on the host, by bit pattern (the library is built with -fno-honor-nans)
 inline bool dense_entry_valid_host(double v) {
     uint64_t b;
@@ -39,33 +24,6 @@ int dense_slice_matching(const double *A, int64_t M, int n, int m) {
     HopcroftKarp hk(loc.data(), (int64_t)(loc.size() / 2), n, m);
     return hk.solve();
 }
-
-// Whether the matching guard of a batch runs on the device (k_matching_batch behind the check pass) or on the host
-// threads.  One graph on one CU is slower than the host matcher (a DFS step waits on L2), so the device wins only once
-// the batch spreads over the GPU: measured it lost at B = 1 (dense and sparse) and at sparse 64 x 2048,
-// and won at dense B >= 64 and sparse B >= 256.
-inline bool dense_guard_on_device(int64_t B) { return B >= 64; }
-inline bool sparse_guard_on_device(int64_t B) { return B >= 256; }
-
-// the two events around a guard launch
-struct GuardEvents {
-    hipEvent_t e[2] = {nullptr, nullptr};
-    int create() {
-        HIP_TRY(hipEventCreate(&e[0]));
-        HIP_TRY(hipEventCreate(&e[1]));
-        return MISSLAP_OK;
-    }
-    int elapsed(double *ms) {
-        float f = 0;
-        HIP_TRY(hipEventElapsedTime(&f, e[0], e[1]));
-        *ms = f;
-        return MISSLAP_OK;
-    }
-    ~GuardEvents() {
-        if (e[0]) (void)hipEventDestroy(e[0]);
-        if (e[1]) (void)hipEventDestroy(e[1]);
-    }
-};
 }  // namespace
 
 MISSLAP_API int misslap_solve_dense_batch(int64_t B, int64_t N, int64_t M, const double *mat, const int32_t *shapes,
@@ -75,14 +33,9 @@ MISSLAP_API int misslap_solve_dense_batch(int64_t B, int64_t N, int64_t M, const
                                           misslap_dense_batch_info *info) {
     const double t_start = now_ms();
     misslap_options opt;
-    int abi = 0;
-    int rc = normalise_options(opt_in, &opt, &abi);
+    int rc = batch_options(opt_in, &opt, "misslap_solve_dense_batch",
+                           "device, maximize, eps_start, max_iter, input_on_device and input_stream");
     if (rc) return rc;
-    if (opt.tail_threshold > 0 || opt.force_f64_values || opt.profile || opt.shard_world > 1 || opt.rounds_per_sync ||
-        opt.tiled_min_K || opt.tiled_shape || opt.tiled_force || opt.shard_min_K || opt.cand_mode || opt.nnz_limit ||
-        opt.cand_build_max_K || opt.cand_refresh_min)
-        return fail(MISSLAP_ERR_INVALID, "misslap_solve_dense_batch takes device, maximize, eps_start, max_iter, "
-                                         "input_on_device and input_stream only: every other option must be 0");
     if (!mat || !sol) return fail(MISSLAP_ERR_INVALID, "null mat / sol");
     if (B < 1 || B > 0x7fffffff) return fail(MISSLAP_ERR_INVALID, "B = %lld: 1 .. 2^31 - 1 problems", (long long)B);
     if (N < 1 || M < 1 || N > kDenseBatchMaxDim || M > kDenseBatchMaxDim)
@@ -91,54 +44,27 @@ MISSLAP_API int misslap_solve_dense_batch(int64_t B, int64_t N, int64_t M, const
                     "problems with misslap_create_dense / misslap_solve_batch",
                     (long long)N, (long long)M, kDenseBatchMaxDim, kDenseBatchMaxDim);
     int32_t stride = 0;
-    if (meta) {
-        stride = meta[0].struct_size;
-        if (stride < (int32_t)offsetof(misslap_dense_batch_meta, its) || stride > 4096)
-            return fail(MISSLAP_ERR_INVALID, "misslap_dense_batch_meta.struct_size = %d: set it to sizeof (%d) in meta[0]",
-                        stride, (int)sizeof(misslap_dense_batch_meta));
-    }
+    if ((rc = batch_meta_stride(meta, &stride))) return rc;
     if (shapes)
         for (int64_t b = 0; b < B; ++b)
             if (shapes[2 * b] < 1 || shapes[2 * b] > N || shapes[2 * b + 1] < 1 || shapes[2 * b + 1] > M)
                 return fail(MISSLAP_ERR_INVALID, "problem %lld: shape (%d, %d) outside 1 .. %lld x 1 .. %lld", (long long)b,
                             shapes[2 * b], shapes[2 * b + 1], (long long)N, (long long)M);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(MISSLAP_ERR_NO_DEVICE, "no HIP device available: libmisslap has no CPU fallback");
-    if (opt.device < 0 || opt.device >= ndev) return fail(MISSLAP_ERR_INVALID, "device %d out of range", opt.device);
-    HIP_TRY(hipSetDevice(opt.device));
     hipStream_t st = nullptr;
-    if ((rc = dense_batch_stream(opt.device, &st))) return rc;
-    if ((rc = sync_device_inputs(&opt, st))) return rc;
+    if ((rc = batch_device(opt, &st))) return rc;
 
     const size_t cells = (size_t)B * (size_t)N * (size_t)M, pcells = (size_t)B * (size_t)M;
     DevScratch tmp;
     const double *d_mat = mat, *d_p0 = prices_in;
-    if (!opt.input_on_device) {
-        double *p = nullptr;
-        if ((rc = tmp.alloc(&p, cells))) return rc;
-        HIP_TRY(hipMemcpyAsync(p, mat, sizeof(double) * cells, hipMemcpyHostToDevice, st));
-        d_mat = p;
-        if (prices_in) {
-            double *q = nullptr;
-            if ((rc = tmp.alloc(&q, pcells))) return rc;
-            HIP_TRY(hipMemcpyAsync(q, prices_in, sizeof(double) * pcells, hipMemcpyHostToDevice, st));
-            d_p0 = q;
-        }
-    }
-    int *d_shapes = nullptr;
-    float *d_eps = nullptr;
+    if (!opt.input_on_device &&
+        ((rc = upload(tmp, &d_mat, mat, cells, st)) || (prices_in && (rc = upload(tmp, &d_p0, prices_in, pcells, st)))))
+        return rc;
+    const int *d_shapes = nullptr;
+    const float *d_eps = nullptr;
     DenseBatchCheck *d_chk = nullptr;
-    misslap_dense_batch_meta *d_meta = nullptr;
-    if ((rc = tmp.alloc(&d_chk, (size_t)B)) || (rc = tmp.alloc(&d_meta, (size_t)B))) return rc;
-    if (shapes) {
-        if ((rc = tmp.alloc(&d_shapes, (size_t)B * 2))) return rc;
-        HIP_TRY(hipMemcpyAsync(d_shapes, shapes, sizeof(int32_t) * 2 * (size_t)B, hipMemcpyHostToDevice, st));
-    }
-    if (eps_start) {
-        if ((rc = tmp.alloc(&d_eps, (size_t)B))) return rc;
-        HIP_TRY(hipMemcpyAsync(d_eps, eps_start, sizeof(float) * (size_t)B, hipMemcpyHostToDevice, st));
-    }
+    if ((rc = tmp.alloc(&d_chk, (size_t)B)) || (shapes && (rc = upload(tmp, &d_shapes, shapes, (size_t)B * 2, st))) ||
+        (eps_start && (rc = upload(tmp, &d_eps, eps_start, (size_t)B, st))))
+        return rc;
 
     // ---- validation: every problem before any is solved
     hipLaunchKernelGGL(k_dense_batch_check, dim3((unsigned)B), dim3(256), 0, st, d_mat, (long long)N, (long long)M,
@@ -147,7 +73,7 @@ MISSLAP_API int misslap_solve_dense_batch(int64_t B, int64_t N, int64_t M, const
     // the matching guard of every problem on the device, behind the validation pass and read back with it
     const bool device_guard = cardinality_check && dense_guard_on_device(B);
     std::vector<int> card;
-    GuardEvents gev;
+    EventPair gev;
     if (device_guard) {
         int *d_card = nullptr;
         if ((rc = tmp.alloc(&d_card, (size_t)B))) return rc;
@@ -203,27 +129,14 @@ MISSLAP_API int misslap_solve_dense_batch(int64_t B, int64_t N, int64_t M, const
             H = host_copy.data();
         }
         card.assign((size_t)B, -1);
-        std::atomic<int64_t> next{0};
-        std::atomic<int> oom{0};
-        auto work = [&]() {
+        rc = run_host_guards(B, [&](int64_t b) {
             char buf[256];
-            for (int64_t b; (b = next.fetch_add(1)) < B;) {
-                if (first_error(b, buf, sizeof(buf))) continue;
-                int n, m;
-                dims(b, n, m);
-                try {
-                    card[(size_t)b] = dense_slice_matching(H + (size_t)b * (size_t)N * (size_t)M, M, n, m);
-                } catch (const std::bad_alloc &) {
-                    oom = 1;
-                }
-            }
-        };
-        const int nthr = (int)std::min<int64_t>(B, std::max(1u, std::min(16u, std::thread::hardware_concurrency())));
-        std::vector<std::thread> pool;
-        for (int t = 1; t < nthr; ++t) pool.emplace_back(work);
-        work();
-        for (auto &t : pool) t.join();
-        if (oom) return fail(MISSLAP_ERR_HIP, "out of host memory in the matching guard");
+            if (first_error(b, buf, sizeof(buf))) return;
+            int n, m;
+            dims(b, n, m);
+            card[(size_t)b] = dense_slice_matching(H + (size_t)b * (size_t)N * (size_t)M, M, n, m);
+        });
+        if (rc) return rc;
     }
     const double t_matched = now_ms();
     for (int64_t b = 0; b < B; ++b) {
@@ -234,76 +147,19 @@ MISSLAP_API int misslap_solve_dense_batch(int64_t B, int64_t N, int64_t M, const
         if (cardinality_check && card[(size_t)b] < n)  // :562-566
             return fail(MISSLAP_ERR_INVALID, "problem %lld: Matrix is infeasible (Maximum matching possible only involves %d "
                         "out of %d rows.)", (long long)b, card[(size_t)b], n);
-        const int bad = chk[(size_t)b].bad_price;  // (the checks of AuctionSolver.resolve)
-        if (bad & 1) return fail(MISSLAP_ERR_INVALID, "problem %lld: prices hold a NaN or an infinity", (long long)b);
-        if (bad & 2)
-            return fail(MISSLAP_ERR_INVALID, "problem %lld: prices must be >= 0 (with the sign bit clear: -0.0 is rejected)",
-                        (long long)b);
+        if ((rc = reject_bad_prices(b, chk[(size_t)b].bad_price))) return rc;  // (the checks of AuctionSolver.resolve)
     }
 
     // ---- the solve: one launch, one workgroup per problem
-    int32_t *d_sol = sol;
-    double *d_prices = prices_out;
-    if (!out_on_device) {
-        if ((rc = tmp.alloc(&d_sol, (size_t)B * (size_t)N))) return rc;
-        if (prices_out && (rc = tmp.alloc(&d_prices, pcells))) return rc;
-    }
-    DenseBatchArgs a;
+    DenseBatchArgs a{};
+    a.s.eps_b = d_eps;
+    a.s.p0 = d_p0;
+    a.s.p0_ld = M;
     a.mat = d_mat;
     a.N = N;
     a.M = M;
     a.shapes = d_shapes;
-    a.eps_b = d_eps;
-    a.eps_opt = opt.eps_start;
-    a.p0 = d_p0;
     a.chk = d_chk;
-    a.maximize = opt.maximize ? 1 : 0;
-    a.max_iter = opt.max_iter;
-    a.sol = d_sol;
-    a.prices = d_prices;
-    a.meta = d_meta;
-    // a wavefront bids for one list position at a time: enough wavefronts for the first round's bidders, at most 16
-    const int threads = N <= 256 ? 256 : (N <= 512 ? 512 : 1024);
-    const size_t lds = dense_batch_lds_bytes(N, M);
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    HIP_TRY(hipEventCreate(&ev[0]));
-    HIP_TRY(hipEventCreate(&ev[1]));
-    struct EvGuard {
-        hipEvent_t *e;
-        ~EvGuard() {
-            (void)hipEventDestroy(e[0]);
-            (void)hipEventDestroy(e[1]);
-        }
-    } ev_guard{ev};
-    HIP_TRY(hipEventRecord(ev[0], st));
-    hipLaunchKernelGGL(k_dense_batch_solve, dim3((unsigned)B), dim3(threads), lds, st, a);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ev[1], st));
-    if (!out_on_device) {
-        HIP_TRY(hipMemcpyAsync(sol, d_sol, sizeof(int32_t) * (size_t)B * (size_t)N, hipMemcpyDeviceToHost, st));
-        if (prices_out)
-            HIP_TRY(hipMemcpyAsync(prices_out, d_prices, sizeof(double) * pcells, hipMemcpyDeviceToHost, st));
-    }
-    if (meta) {
-        const size_t w = std::min((size_t)stride, sizeof(misslap_dense_batch_meta));
-        HIP_TRY(hipMemcpy2DAsync(meta, (size_t)stride, d_meta, sizeof(misslap_dense_batch_meta), w, (size_t)B,
-                                 hipMemcpyDeviceToHost, st));
-    }
-    HIP_TRY(hipStreamSynchronize(st));
-    tmp.drained = true;
-    if (meta)  // (struct_size is an input field: the caller's value stays)
-        for (int64_t b = 0; b < B; ++b)
-            reinterpret_cast<misslap_dense_batch_meta *>(reinterpret_cast<char *>(meta) + (size_t)b * (size_t)stride)
-                ->struct_size = stride;
-    if (info) {
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
-        info->threads = threads;
-        info->lds_bytes = (int32_t)lds;
-        info->check_ms = t_checked - t_start - guard_ms;
-        info->matching_ms = guard_ms + (t_matched - t_checked);
-        info->solve_ms = ms;
-        info->wall_ms = now_ms() - t_start;
-    }
-    return MISSLAP_OK;
+    return batch_solve_run(k_dense_batch_solve, a, st, tmp, opt, B, (int)N, (int)M, sol, N, prices_out, M, out_on_device,
+                           meta, stride, info, t_start, t_checked, t_matched, guard_ms);
 }

@@ -1,22 +1,10 @@
 // abi_matching_batch.hpp -- C ABI: the reference's Hopcroft-Karp on many small graphs in one call, one workgroup per
-// graph (misslap_matching_batch / misslap_matching_dense_batch; the kernels are in kernels_matching_batch.hpp).
+// graph (misslap_matching_batch / misslap_matching_dense_batch; the kernels are in kernels_matching_batch.hpp, the shared
+// host helpers in abi_batch_common.hpp).
 // (part of the single translation unit misslap.hip; included in the order given there, after abi_sparse_batch.hpp)
 #pragma once
 
 namespace {
-// the options both entry points take: device, input_on_device, input_stream (the solver fields are ignored)
-int matching_batch_options(const misslap_options *opt_in, misslap_options *opt, const char *who) {
-    int abi = 0;
-    int rc = normalise_options(opt_in, opt, &abi);
-    if (rc) return rc;
-    if (opt->tail_threshold > 0 || opt->force_f64_values || opt->profile || opt->shard_world > 1 || opt->rounds_per_sync ||
-        opt->tiled_min_K || opt->tiled_shape || opt->tiled_force || opt->shard_min_K || opt->cand_mode || opt->nnz_limit ||
-        opt->cand_build_max_K || opt->cand_refresh_min)
-        return fail(MISSLAP_ERR_INVALID, "%s takes device, input_on_device and input_stream only: every other option "
-                                         "must be 0", who);
-    return MISSLAP_OK;
-}
-
 // Launch the matcher on a stream (LDS carve Ns x Ms; the > 64 KB opt-in is never needed: 48 KB at the cap).
 template <bool kDense>
 int launch_matching_batch(hipStream_t st, int64_t B, const MatchBatchArgs &a, size_t *lds_out) {
@@ -44,20 +32,12 @@ int matching_batch_run(hipStream_t st, DevScratch &tmp, int64_t B, MatchBatchArg
         if (left && (rc = tmp.alloc(&a.left, (size_t)B * (size_t)left_ld))) return rc;
         if (right && (rc = tmp.alloc(&a.right, (size_t)B * (size_t)right_ld))) return rc;
     }
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    HIP_TRY(hipEventCreate(&ev[0]));
-    HIP_TRY(hipEventCreate(&ev[1]));
-    struct EvGuard {
-        hipEvent_t *e;
-        ~EvGuard() {
-            (void)hipEventDestroy(e[0]);
-            (void)hipEventDestroy(e[1]);
-        }
-    } ev_guard{ev};
+    EventPair ev;
+    if ((rc = ev.create())) return rc;
     size_t lds = 0;
-    HIP_TRY(hipEventRecord(ev[0], st));
+    HIP_TRY(hipEventRecord(ev.e[0], st));
     if ((rc = launch_matching_batch<kDense>(st, B, a, &lds))) return rc;
-    HIP_TRY(hipEventRecord(ev[1], st));
+    HIP_TRY(hipEventRecord(ev.e[1], st));
     HIP_TRY(hipMemcpyAsync(size, d_size, sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToHost, st));
     if (!out_on_device) {
         if (left)
@@ -69,8 +49,8 @@ int matching_batch_run(hipStream_t st, DevScratch &tmp, int64_t B, MatchBatchArg
     HIP_TRY(hipStreamSynchronize(st));
     tmp.drained = true;
     if (info) {
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
+        double ms = 0;
+        if ((rc = ev.elapsed(&ms))) return rc;
         info->threads = kMatchBatchThreads;
         info->lds_bytes = (int32_t)lds;
         info->check_ms = t_checked - t_start;
@@ -86,17 +66,6 @@ int matching_batch_info_size(const misslap_matching_batch_info *info) {
                     info->struct_size, (int)sizeof(misslap_matching_batch_info));
     return MISSLAP_OK;
 }
-
-int matching_batch_device(const misslap_options &opt, hipStream_t *st) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(MISSLAP_ERR_NO_DEVICE, "no HIP device available: libmisslap has no CPU fallback");
-    if (opt.device < 0 || opt.device >= ndev) return fail(MISSLAP_ERR_INVALID, "device %d out of range", opt.device);
-    HIP_TRY(hipSetDevice(opt.device));
-    int rc = dense_batch_stream(opt.device, st);
-    if (rc) return rc;
-    return sync_device_inputs(&opt, *st);
-}
 }  // namespace
 
 MISSLAP_API int misslap_matching_batch(int64_t B, const int32_t *loc, const int64_t *offsets, const misslap_options *opt_in,
@@ -105,7 +74,7 @@ MISSLAP_API int misslap_matching_batch(int64_t B, const int32_t *loc, const int6
                                        misslap_matching_batch_info *info) {
     const double t_start = now_ms();
     misslap_options opt;
-    int rc = matching_batch_options(opt_in, &opt, "misslap_matching_batch");
+    int rc = batch_options(opt_in, &opt, "misslap_matching_batch", "device, input_on_device and input_stream");
     if (rc) return rc;
     if ((rc = matching_batch_info_size(info))) return rc;
     if (!loc || !offsets || !size || !n_rows || !n_cols) return fail(MISSLAP_ERR_INVALID, "null loc / offsets / size / n_rows / n_cols");
@@ -122,21 +91,16 @@ MISSLAP_API int misslap_matching_batch(int64_t B, const int32_t *loc, const int6
                         (long long)z, kMatchBatchMaxEntries);
     }
     hipStream_t st = nullptr;
-    if ((rc = matching_batch_device(opt, &st))) return rc;
+    if ((rc = batch_device(opt, &st))) return rc;
 
     const size_t nnz = (size_t)offsets[B];
     DevScratch tmp;
     const int32_t *d_loc = loc;
-    if (!opt.input_on_device) {
-        int32_t *p = nullptr;
-        if ((rc = tmp.alloc(&p, 2 * nnz))) return rc;
-        HIP_TRY(hipMemcpyAsync(p, loc, sizeof(int32_t) * 2 * nnz, hipMemcpyHostToDevice, st));
-        d_loc = p;
-    }
-    long long *d_off = nullptr;
+    const long long *d_off = nullptr;
     MatchBatchCheck *d_chk = nullptr;
-    if ((rc = tmp.alloc(&d_off, (size_t)B + 1)) || (rc = tmp.alloc(&d_chk, (size_t)B))) return rc;
-    HIP_TRY(hipMemcpyAsync(d_off, offsets, sizeof(int64_t) * ((size_t)B + 1), hipMemcpyHostToDevice, st));
+    if ((!opt.input_on_device && (rc = upload(tmp, &d_loc, loc, 2 * nnz, st))) ||
+        (rc = upload(tmp, &d_off, offsets, (size_t)B + 1, st)) || (rc = tmp.alloc(&d_chk, (size_t)B)))
+        return rc;
     hipLaunchKernelGGL(k_matching_batch_check, dim3((unsigned)B), dim3(256), 0, st, d_loc, d_off, d_chk);
     HIP_TRY(hipGetLastError());
     std::vector<MatchBatchCheck> chk((size_t)B);
@@ -187,7 +151,7 @@ MISSLAP_API int misslap_matching_dense_batch(int64_t B, int64_t N, int64_t M, co
                                              misslap_matching_batch_info *info) {
     const double t_start = now_ms();
     misslap_options opt;
-    int rc = matching_batch_options(opt_in, &opt, "misslap_matching_dense_batch");
+    int rc = batch_options(opt_in, &opt, "misslap_matching_dense_batch", "device, input_on_device and input_stream");
     if (rc) return rc;
     if ((rc = matching_batch_info_size(info))) return rc;
     if (!mat || !size || !n_rows || !n_cols) return fail(MISSLAP_ERR_INVALID, "null mat / size / n_rows / n_cols");
@@ -213,21 +177,13 @@ MISSLAP_API int misslap_matching_dense_batch(int64_t B, int64_t N, int64_t M, co
         Ms = std::max(Ms, (int)m);
     }
     hipStream_t st = nullptr;
-    if ((rc = matching_batch_device(opt, &st))) return rc;
+    if ((rc = batch_device(opt, &st))) return rc;
     DevScratch tmp;
     const double *d_mat = mat;
-    if (!opt.input_on_device) {
-        const size_t cells = (size_t)B * (size_t)N * (size_t)M;
-        double *p = nullptr;
-        if ((rc = tmp.alloc(&p, cells))) return rc;
-        HIP_TRY(hipMemcpyAsync(p, mat, sizeof(double) * cells, hipMemcpyHostToDevice, st));
-        d_mat = p;
-    }
-    int *d_shapes = nullptr;
-    if (shapes) {
-        if ((rc = tmp.alloc(&d_shapes, (size_t)B * 2))) return rc;
-        HIP_TRY(hipMemcpyAsync(d_shapes, shapes, sizeof(int32_t) * 2 * (size_t)B, hipMemcpyHostToDevice, st));
-    }
+    const int *d_shapes = nullptr;
+    if ((!opt.input_on_device && (rc = upload(tmp, &d_mat, mat, (size_t)B * (size_t)N * (size_t)M, st))) ||
+        (shapes && (rc = upload(tmp, &d_shapes, shapes, (size_t)B * 2, st))))
+        return rc;
     for (int64_t b = 0; b < B; ++b) {
         n_rows[b] = shapes ? shapes[2 * b] : (int32_t)N;
         n_cols[b] = shapes ? shapes[2 * b + 1] : (int32_t)M;

@@ -1,5 +1,6 @@
 // abi_sparse_batch.hpp -- C ABI: many small sparse (loc / val) problems in one call, one workgroup per problem
-// (misslap_solve_sparse_batch; the kernels are in kernels_sparse_batch.hpp).
+// (misslap_solve_sparse_batch; the kernels are in kernels_sparse_batch.hpp, the shared host helpers in
+// abi_batch_common.hpp).
 // (part of the single translation unit misslap.hip; included in the order given there, after abi_dense_batch.hpp)
 #pragma once
 
@@ -64,14 +65,9 @@ MISSLAP_API int misslap_solve_sparse_batch(int64_t B, const int32_t *loc, const 
                                            misslap_dense_batch_info *info) {
     const double t_start = now_ms();
     misslap_options opt;
-    int abi = 0;
-    int rc = normalise_options(opt_in, &opt, &abi);
+    int rc = batch_options(opt_in, &opt, "misslap_solve_sparse_batch",
+                           "device, maximize, eps_start, max_iter, input_on_device and input_stream");
     if (rc) return rc;
-    if (opt.tail_threshold > 0 || opt.force_f64_values || opt.profile || opt.shard_world > 1 || opt.rounds_per_sync ||
-        opt.tiled_min_K || opt.tiled_shape || opt.tiled_force || opt.shard_min_K || opt.cand_mode || opt.nnz_limit ||
-        opt.cand_build_max_K || opt.cand_refresh_min)
-        return fail(MISSLAP_ERR_INVALID, "misslap_solve_sparse_batch takes device, maximize, eps_start, max_iter, "
-                                         "input_on_device and input_stream only: every other option must be 0");
     if (!loc || !val || !offsets || !sol) return fail(MISSLAP_ERR_INVALID, "null loc / val / offsets / sol");
     if (B < 1 || B > 0x7fffffff) return fail(MISSLAP_ERR_INVALID, "B = %lld: 1 .. 2^31 - 1 problems", (long long)B);
     if (offsets[0] != 0) return fail(MISSLAP_ERR_INVALID, "offsets[0] = %lld: must be 0", (long long)offsets[0]);
@@ -86,54 +82,25 @@ MISSLAP_API int misslap_solve_sparse_batch(int64_t B, const int32_t *loc, const 
     if (sol_ld < 1 || (prices_out && prices_out_ld < 1) || (prices_in && prices_ld < 1))
         return fail(MISSLAP_ERR_INVALID, "sol_ld / prices_out_ld / prices_ld must be >= 1");
     int32_t stride = 0;
-    if (meta) {
-        stride = meta[0].struct_size;
-        if (stride < (int32_t)offsetof(misslap_dense_batch_meta, its) || stride > 4096)
-            return fail(MISSLAP_ERR_INVALID, "misslap_dense_batch_meta.struct_size = %d: set it to sizeof (%d) in meta[0]",
-                        stride, (int)sizeof(misslap_dense_batch_meta));
-    }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(MISSLAP_ERR_NO_DEVICE, "no HIP device available: libmisslap has no CPU fallback");
-    if (opt.device < 0 || opt.device >= ndev) return fail(MISSLAP_ERR_INVALID, "device %d out of range", opt.device);
-    HIP_TRY(hipSetDevice(opt.device));
+    if ((rc = batch_meta_stride(meta, &stride))) return rc;
     hipStream_t st = nullptr;
-    if ((rc = dense_batch_stream(opt.device, &st))) return rc;
-    if ((rc = sync_device_inputs(&opt, st))) return rc;
+    if ((rc = batch_device(opt, &st))) return rc;
 
     const size_t nnz = (size_t)offsets[B];
     DevScratch tmp;
     const int32_t *d_loc = loc;
     const double *d_val = val, *d_p0 = prices_in;
-    if (!opt.input_on_device) {
-        int32_t *p = nullptr;
-        double *q = nullptr;
-        if ((rc = tmp.alloc(&p, 2 * nnz)) || (rc = tmp.alloc(&q, nnz))) return rc;
-        HIP_TRY(hipMemcpyAsync(p, loc, sizeof(int32_t) * 2 * nnz, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(q, val, sizeof(double) * nnz, hipMemcpyHostToDevice, st));
-        d_loc = p;
-        d_val = q;
-        if (prices_in) {
-            double *r = nullptr;
-            const size_t pcells = (size_t)B * (size_t)prices_ld;
-            if ((rc = tmp.alloc(&r, pcells))) return rc;
-            HIP_TRY(hipMemcpyAsync(r, prices_in, sizeof(double) * pcells, hipMemcpyHostToDevice, st));
-            d_p0 = r;
-        }
-    }
-    long long *d_off = nullptr;
-    int *d_rs = nullptr;
-    float *d_eps = nullptr;
-    SparseBatchCheck *d_chk = nullptr;
-    misslap_dense_batch_meta *d_meta = nullptr;
-    if ((rc = tmp.alloc(&d_off, (size_t)B + 1)) || (rc = tmp.alloc(&d_rs, nnz + (size_t)B)) ||
-        (rc = tmp.alloc(&d_chk, (size_t)B)) || (rc = tmp.alloc(&d_meta, (size_t)B)))
+    if (!opt.input_on_device &&
+        ((rc = upload(tmp, &d_loc, loc, 2 * nnz, st)) || (rc = upload(tmp, &d_val, val, nnz, st)) ||
+         (prices_in && (rc = upload(tmp, &d_p0, prices_in, (size_t)B * (size_t)prices_ld, st)))))
         return rc;
-    HIP_TRY(hipMemcpyAsync(d_off, offsets, sizeof(int64_t) * ((size_t)B + 1), hipMemcpyHostToDevice, st));
-    if (eps_start) {
-        if ((rc = tmp.alloc(&d_eps, (size_t)B))) return rc;
-        HIP_TRY(hipMemcpyAsync(d_eps, eps_start, sizeof(float) * (size_t)B, hipMemcpyHostToDevice, st));
-    }
+    const long long *d_off = nullptr;
+    int *d_rs = nullptr;
+    const float *d_eps = nullptr;
+    SparseBatchCheck *d_chk = nullptr;
+    if ((rc = upload(tmp, &d_off, offsets, (size_t)B + 1, st)) || (rc = tmp.alloc(&d_rs, nnz + (size_t)B)) ||
+        (rc = tmp.alloc(&d_chk, (size_t)B)) || (eps_start && (rc = upload(tmp, &d_eps, eps_start, (size_t)B, st))))
+        return rc;
 
     // ---- check pass: every problem before any is solved
     hipLaunchKernelGGL(k_sparse_batch_check, dim3((unsigned)B), dim3(256), 0, st, d_loc, d_val, d_off, d_p0,
@@ -145,7 +112,7 @@ MISSLAP_API int misslap_solve_sparse_batch(int64_t B, const int32_t *loc, const 
     // keep the host guard for every problem (card[b] = -1; sparse_guard_on_device).
     const bool device_guard = cardinality_check && sparse_guard_on_device(B);
     std::vector<int> card((size_t)B, -1);
-    GuardEvents gev;
+    EventPair gev;
     if (device_guard) {
         int64_t zmax = 1;
         for (int64_t b = 0; b < B; ++b) zmax = std::max<int64_t>(zmax, offsets[b + 1] - offsets[b]);
@@ -235,31 +202,17 @@ MISSLAP_API int misslap_solve_sparse_batch(int64_t B, const int32_t *loc, const 
                 HIP_TRY(hipStreamSynchronize(st));
             }
         }
-        std::atomic<int64_t> next{0};
-        std::atomic<int> oom{0};
-        const int64_t nh = (int64_t)on_host.size();
-        auto work = [&]() {
+        rc = run_host_guards((int64_t)on_host.size(), [&](int64_t t) {
             char buf[256];
-            for (int64_t t; (t = next.fetch_add(1)) < nh;) {
-                const int64_t b = on_host[(size_t)t];
-                const SparseBatchCheck &c = chk[(size_t)b];
-                const int32_t *H = opt.input_on_device ? host_copy.data() + 2 * host_at[(size_t)t] : loc + 2 * offsets[b];
-                try {
-                    // n_true = max row + 1, m_true = max column + 1 (int arithmetic of the front-end's int())
-                    if (!sparse_problem_guard(H, offsets[b + 1] - offsets[b], (int)((int64_t)c.max_row + 1),
-                                              (int)((int64_t)c.max_col + 1), buf, sizeof(buf)))
-                        guard_err[(size_t)b] = buf;
-                } catch (const std::bad_alloc &) {
-                    oom = 1;
-                }
-            }
-        };
-        const int nthr = (int)std::min<int64_t>(nh, std::max(1u, std::min(16u, std::thread::hardware_concurrency())));
-        std::vector<std::thread> pool;
-        for (int t = 1; t < nthr; ++t) pool.emplace_back(work);
-        work();
-        for (auto &t : pool) t.join();
-        if (oom) return fail(MISSLAP_ERR_HIP, "out of host memory in the matching guard");
+            const int64_t b = on_host[(size_t)t];
+            const SparseBatchCheck &c = chk[(size_t)b];
+            const int32_t *H = opt.input_on_device ? host_copy.data() + 2 * host_at[(size_t)t] : loc + 2 * offsets[b];
+            // n_true = max row + 1, m_true = max column + 1 (int arithmetic of the front-end's int())
+            if (!sparse_problem_guard(H, offsets[b + 1] - offsets[b], (int)((int64_t)c.max_row + 1),
+                                      (int)((int64_t)c.max_col + 1), buf, sizeof(buf)))
+                guard_err[(size_t)b] = buf;
+        });
+        if (rc) return rc;
     }
     const double t_matched = now_ms();
     int Ns = 1, Ms = 1;
@@ -286,10 +239,7 @@ MISSLAP_API int misslap_solve_sparse_batch(int64_t B, const int32_t *loc, const 
             if (m > prices_ld)
                 return fail(MISSLAP_ERR_INVALID, "problem %lld: prices hold %lld columns, the problem has %d", (long long)b,
                             (long long)prices_ld, m);
-            if (c.bad_price & 1) return fail(MISSLAP_ERR_INVALID, "problem %lld: prices hold a NaN or an infinity", (long long)b);
-            if (c.bad_price & 2)
-                return fail(MISSLAP_ERR_INVALID, "problem %lld: prices must be >= 0 (with the sign bit clear: -0.0 is "
-                            "rejected)", (long long)b);
+            if ((rc = reject_bad_prices(b, c.bad_price))) return rc;
         }
         if (n > sol_ld || (prices_out && m > prices_out_ld))
             return fail(MISSLAP_ERR_INVALID, "problem %lld: %d x %d does not fit sol_ld = %lld / prices_out_ld = %lld",
@@ -299,76 +249,15 @@ MISSLAP_API int misslap_solve_sparse_batch(int64_t B, const int32_t *loc, const 
     }
 
     // ---- the solve: one launch, one workgroup per problem
-    int32_t *d_sol = sol;
-    double *d_prices = prices_out;
-    if (!out_on_device) {
-        if ((rc = tmp.alloc(&d_sol, (size_t)B * (size_t)sol_ld))) return rc;
-        if (prices_out && (rc = tmp.alloc(&d_prices, (size_t)B * (size_t)prices_out_ld))) return rc;
-    }
-    SparseBatchArgs a;
+    SparseBatchArgs a{};
+    a.s.eps_b = d_eps;
+    a.s.p0 = d_p0;
+    a.s.p0_ld = prices_ld;
     a.loc = d_loc;
     a.val = d_val;
     a.offsets = d_off;
     a.row_start = d_rs;
-    a.eps_b = d_eps;
-    a.eps_opt = opt.eps_start;
-    a.p0 = d_p0;
-    a.p0_ld = prices_ld;
     a.chk = d_chk;
-    a.maximize = opt.maximize ? 1 : 0;
-    a.max_iter = opt.max_iter;
-    a.Ns = Ns;
-    a.Ms = Ms;
-    a.sol = d_sol;
-    a.sol_ld = sol_ld;
-    a.prices = d_prices;
-    a.prices_ld = prices_out_ld;
-    a.meta = d_meta;
-    // a wavefront bids for one list position at a time: enough wavefronts for the first round's bidders, at most 16
-    const int threads = Ns <= 256 ? 256 : (Ns <= 512 ? 512 : 1024);
-    const size_t lds = sparse_batch_lds_bytes(Ns, Ms);
-    if (lds > 65536)  // (per call: the > 64 KB dynamic-LDS opt-in is a property of the function on the current device)
-        HIP_TRY(hipFuncSetAttribute((const void *)k_sparse_batch_solve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    HIP_TRY(hipEventCreate(&ev[0]));
-    HIP_TRY(hipEventCreate(&ev[1]));
-    struct EvGuard {
-        hipEvent_t *e;
-        ~EvGuard() {
-            (void)hipEventDestroy(e[0]);
-            (void)hipEventDestroy(e[1]);
-        }
-    } ev_guard{ev};
-    HIP_TRY(hipEventRecord(ev[0], st));
-    hipLaunchKernelGGL(k_sparse_batch_solve, dim3((unsigned)B), dim3(threads), lds, st, a);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ev[1], st));
-    if (!out_on_device) {
-        HIP_TRY(hipMemcpyAsync(sol, d_sol, sizeof(int32_t) * (size_t)B * (size_t)sol_ld, hipMemcpyDeviceToHost, st));
-        if (prices_out)
-            HIP_TRY(hipMemcpyAsync(prices_out, d_prices, sizeof(double) * (size_t)B * (size_t)prices_out_ld,
-                                   hipMemcpyDeviceToHost, st));
-    }
-    if (meta) {
-        const size_t w = std::min((size_t)stride, sizeof(misslap_dense_batch_meta));
-        HIP_TRY(hipMemcpy2DAsync(meta, (size_t)stride, d_meta, sizeof(misslap_dense_batch_meta), w, (size_t)B,
-                                 hipMemcpyDeviceToHost, st));
-    }
-    HIP_TRY(hipStreamSynchronize(st));
-    tmp.drained = true;
-    if (meta)  // (struct_size is an input field: the caller's value stays)
-        for (int64_t b = 0; b < B; ++b)
-            reinterpret_cast<misslap_dense_batch_meta *>(reinterpret_cast<char *>(meta) + (size_t)b * (size_t)stride)
-                ->struct_size = stride;
-    if (info) {
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
-        info->threads = threads;
-        info->lds_bytes = (int32_t)lds;
-        info->check_ms = t_checked - t_start - guard_ms;
-        info->matching_ms = guard_ms + (t_matched - t_checked);
-        info->solve_ms = ms;
-        info->wall_ms = now_ms() - t_start;
-    }
-    return MISSLAP_OK;
+    return batch_solve_run(k_sparse_batch_solve, a, st, tmp, opt, B, Ns, Ms, sol, sol_ld, prices_out, prices_out_ld,
+                           out_on_device, meta, stride, info, t_start, t_checked, t_matched, guard_ms);
 }

@@ -1,0 +1,255 @@
+// kernels_batch_solve.hpp -- the round loop of the one-workgroup-per-problem batch solves, shared by
+// k_dense_batch_solve (kernels_dense_batch.hpp) and k_sparse_batch_solve (kernels_sparse_batch.hpp); the host side is
+// batch_solve_run in abi_batch_common.hpp.
+//
+// A problem within the batch caps (MISSLAP_DENSE_BATCH_MAX_DIM, MISSLAP_SPARSE_BATCH_MAX_DIM) keeps the whole state of
+// the reference's solver (auction_.pyx:167-200) in LDS: prices, person_to_object, object_to_person, the unassigned
+// list, the per-object best key / position and the round's bids.  One workgroup runs the epsilon-scaling loop of solve()
+// (:268-306) from the first bid to the last eCE check without returning to the host, so B problems take one launch.
+//
+// Per round, each step separated from the next by a workgroup barrier:
+//   BID      one wavefront per unassigned list position: the row source scans person i's row, reduces the row's top two
+//            of a_ij - p_j under the reference's ">=" rule across lanes (top2_wave_reduce) and names the winning object;
+//            bid = (costbest - wi) + eps in fp64 with fp32 eps (:339-365).  The bid's key goes into bid_key[k] and
+//            through ds_max_u64 into bkey[j].
+//   RESOLVE  among the positions holding an object's best key, the smallest wins (ds_min_u32): strict ">" in list
+//            order (:375-385).
+//   ASSIGN   every winner at once.  The writes of distinct winners touch distinct objects, persons and list slots, so
+//            this is the reference's ascending-j walk (:388-427): the winner's price, the evicted owner takes the
+//            winner's slot, else the slot becomes a hole.
+//   COMPACT  push_all_left (:137-162, :430): the k-th hole in [0, K') receives the k-th person in [K', K).  (With N <= M
+//            the reference's bound `size = num_cols` is never reached; with N > M the problem has no complete
+//            assignment and the reference reads past its list.)
+// After the round: terminate() (:308-309), and at the end of a phase eps *= theta or stop (:275-292), with the eCE test
+// of :443-485 at target eps = 1 / N.
+//
+// A row source (DenseBatchRows, SparseBatchRows) supplies what differs between the two layouts:
+//   bid(i, price, cb, obj)          the wavefront's reduced Top2 of row i, the winner's cost (all lanes) and its object
+//   ece_bad(i, j, price, tol, eps)  this lane's part of the eCE row test of row i assigned to object j
+//   gather(p2o, n, selv, nsel)      the objective's per-row gather into LDS (after the last barrier of the loop)
+//   objective(p2o, n, selv, nsel)   the sum of get_obj, on one lane, in the reference's order
+//   meta_cols(m), meta_nnz()        the meta record's n_cols and nnz
+// Only the problem's own m objects and n persons are initialised and reset; the slots beyond them in the carve are
+// never read.
+#pragma once
+
+namespace misslap {
+
+// What both solves take per batch (the first member of DenseBatchArgs / SparseBatchArgs; filled by batch_solve_run)
+struct BatchSolveArgs {
+    const float *eps_b;        // [B] or null
+    float eps_opt;
+    const double *p0;          // [B][p0_ld] or null
+    long long p0_ld;
+    int maximize;
+    long long max_iter;
+    int Ns, Ms;                // the batch's largest n_b / m_b: the LDS carve
+    int *sol;                  // [B][sol_ld]
+    long long sol_ld;
+    double *prices;            // [B][prices_ld] or null
+    long long prices_ld;
+    misslap_dense_batch_meta *meta;  // [B]
+};
+
+// LDS of one problem, carved from the dynamic allocation (sized by the batch's Ns and Ms): 24 M + 28 N bytes
+__host__ __device__ constexpr size_t batch_solve_lds_bytes(long long N, long long M) {
+    return (size_t)M * (8 + 8 + 4 + 4) + (size_t)N * (8 + 4 + 4 + 4 + 4 + 4);
+}
+
+// The starting prices p[0 .. m) of one problem in a check pass: bit 0 NaN / infinity, bit 1 sign bit set, into *s_badp
+__device__ __forceinline__ void batch_check_prices(const double *p, int m, int *s_badp) {
+    int bad = 0;
+    for (int j = threadIdx.x; j < m; j += blockDim.x) {
+        const unsigned long long bits = (unsigned long long)__double_as_longlong(p[j]);
+        bad |= (bits & 0x7ff0000000000000ull) == 0x7ff0000000000000ull ? 1 : 0;
+        bad |= (bits >> 63) ? 2 : 0;
+    }
+    if (bad) atomicOr(s_badp, bad);
+}
+
+// eCE_satisfied(eps) (auction_.pyx:443-485, tol = 1e-7) on a state with everybody assigned; one wavefront per row.
+template <class Rows>
+__device__ __forceinline__ bool batch_ece(const Rows &rows, int n, const double *price, const int *p2o, float eps_f,
+                                          int *s_fail) {
+    const int lane = lane_id(), wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    const double tol = 1e-7, eps = (double)eps_f;
+    if (threadIdx.x == 0) *s_fail = 0;
+    __syncthreads();
+    for (int i = wave; i < n; i += nw) {
+        const bool bad = rows.ece_bad(i, p2o[i], price, tol, eps);
+        if (__ballot(bad) && lane == 0) *s_fail = 1;
+    }
+    __syncthreads();
+    const bool ok = *s_fail == 0;
+    __syncthreads();  // (s_fail is rewritten by the next call)
+    return ok;
+}
+
+// The solve of problem blockIdx.x: n persons, m objects, C = max |a_ij| as bits.
+template <class Rows>
+__device__ __forceinline__ void batch_solve(const BatchSolveArgs &a, const Rows &rows, int n, int m,
+                                            unsigned long long absmax_bits) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
+    __shared__ int s_holes, s_nmove, s_fail;
+    const int b = blockIdx.x, tid = threadIdx.x, T = blockDim.x, lane = lane_id(), wave = tid >> 6, nw = T >> 6;
+    const int Ns = a.Ns, Ms = a.Ms;
+    double *price = reinterpret_cast<double *>(s_raw);                           // [M]  auction_.pyx:169
+    unsigned long long *bkey = reinterpret_cast<unsigned long long *>(price + Ms); // [M]  :193 best bid as key, 0 = none
+    unsigned long long *bid_key = bkey + Ms;                                       // [N]  the round's bids by list position
+    int *o2p = reinterpret_cast<int *>(bid_key + Ns);                              // [M]  :178
+    int *bpos = o2p + Ms;                                                          // [M]  :194 winning list position
+    int *p2o = bpos + Ms;                                                          // [N]  :177
+    int *U = p2o + Ns;                                                             // [N]  :199 unassigned list
+    int *bid_obj = U + Ns;                                                         // [N]
+    int *hole = bid_obj + Ns;                                                      // [N]  push_all_left lists
+    int *mover = hole + Ns;                                                        // [N]
+
+    const double *P0 = a.p0 ? a.p0 + (size_t)b * (size_t)a.p0_ld : nullptr;
+    // AuctionSolver.__init__ (:241-252): C = max |a_ij| as a float, eps0 = C / 2 unless eps_start > 0
+    const float C = (float)__longlong_as_double((long long)absmax_bits);
+    float eps = (float)((double)C / 2.0);
+    const float target_eps = (float)(1.0 / (double)n);
+    const float theta = (float)0.15;
+    const float e0 = a.eps_b ? a.eps_b[b] : a.eps_opt;
+    if (e0 > 0) eps = e0;
+    const float start_eps = eps;
+
+    for (int j = tid; j < m; j += T) {
+        price[j] = P0 ? P0[j] : 0.0;
+        bkey[j] = 0ull;
+        bpos[j] = kPosNone;
+        o2p[j] = -1;
+    }
+    for (int i = tid; i < n; i += T) {
+        p2o[i] = -1;
+        U[i] = i;
+    }
+    int K = n;  // num_unassigned, uniform
+    long long nits = 0;
+    int nred = 0;
+    unsigned long long bids = 0;
+    __syncthreads();
+
+    for (;;) {  // solve() (:271-292); leaves after at most max_iter rounds
+        // ---- BID (:339-365)
+        for (int k = wave; k < K; k += nw) {
+            double costbest;
+            int j;
+            const Top2 r = rows.bid(U[k], price, costbest, j);
+            const double bid = costbest - r.w + (double)eps;  // :360
+            if (lane == 0) {
+                const unsigned long long key = bid_to_key(bid);
+                bid_key[k] = key;
+                bid_obj[k] = j;
+                atomicMax(&bkey[j], key);
+            }
+        }
+        bids += (unsigned long long)K;
+        __syncthreads();
+        // ---- RESOLVE (:375-385): earliest list position among the holders of the best bid
+        for (int k = tid; k < K; k += T) {
+            const int j = bid_obj[k];
+            if (bid_key[k] == bkey[j]) atomicMin(&bpos[j], k);
+        }
+        if (tid == 0) s_holes = 0;
+        __syncthreads();
+        // ---- ASSIGN (:388-427)
+        int holes = 0;
+        for (int k = tid; k < K; k += T) {
+            const int j = bid_obj[k];
+            if (bpos[j] == k) {  // (a loser reads the winner's position or kPosNone, never its own)
+                const int i = U[k], prev = o2p[j];
+                price[j] = key_to_bid(bid_key[k]);  // :397
+                if (prev != -1) {
+                    p2o[prev] = -1;  // :404
+                    U[k] = prev;     // :409
+                } else {
+                    U[k] = -1;  // :412
+                    ++holes;
+                }
+                p2o[i] = j;  // :417
+                o2p[j] = i;  // :418
+                bkey[j] = 0ull;     // :421-422
+                bpos[j] = kPosNone;
+            }
+        }
+        if (holes) atomicAdd(&s_holes, holes);
+        __syncthreads();
+        const int Kn = K - s_holes;  // :429
+        // ---- push_all_left (:137-162): k-th hole in [0, Kn) <- k-th person in [Kn, K), one wavefront
+        if (wave == 0) {
+            int cl = 0, cm = 0;
+            for (int base = 0; base < K; base += kWave) {
+                const int pos = base + lane;
+                const int u = pos < K ? U[pos] : -1;
+                const bool isl = pos < Kn && u == -1, ism = pos >= Kn && pos < K && u != -1;
+                const unsigned long long bl = __ballot(isl), bm = __ballot(ism);
+                if (isl) hole[cl + __popcll(bl & lanemask_lt())] = pos;
+                if (ism) mover[cm + __popcll(bm & lanemask_lt())] = u;
+                cl += __popcll(bl);
+                cm += __popcll(bm);
+            }
+            if (lane == 0) s_nmove = cl;
+        }
+        __syncthreads();
+        for (int q = tid; q < s_nmove; q += T) U[hole[q]] = mover[q];
+        __syncthreads();
+        K = Kn;
+        ++nits;
+        // ---- terminate() (:308-309) and the end of an eps-phase (:275-292)
+        const bool optimal = K == 0 && batch_ece(rows, n, price, p2o, target_eps, &s_fail);
+        if (nits >= a.max_iter || optimal) break;
+        if (K == 0) {
+            if (eps < target_eps) break;  // :280
+            eps = eps * theta;            // :283
+            for (int j = tid; j < m; j += T) o2p[j] = -1;  // :287
+            for (int i = tid; i < n; i += T) {
+                p2o[i] = -1;  // :286
+                U[i] = i;     // :289
+            }
+            K = n;   // :288
+            ++nred;  // :292
+            __syncthreads();
+        }
+    }
+
+    // ---- meta (:297-304) and the outputs
+    const bool ece = K == 0 && batch_ece(rows, n, price, p2o, target_eps, &s_fail);
+    // (int loop bounds: a 64-bit bound costs the dense kernel a VGPR; a row is written up to 2^31 - 1 entries)
+    const int sol_n = (int)(a.sol_ld < INT_MAX ? a.sol_ld : INT_MAX);
+    const int prices_n = (int)(a.prices_ld < INT_MAX ? a.prices_ld : INT_MAX);
+    int *sol = a.sol + (size_t)b * (size_t)a.sol_ld;
+    for (int i = tid; i < sol_n; i += T) sol[i] = i < n ? p2o[i] : -1;
+    if (a.prices) {
+        double *po = a.prices + (size_t)b * (size_t)a.prices_ld;
+        for (int j = tid; j < prices_n; j += T) po[j] = j < m ? price[j] : 0.0;
+    }
+    // get_obj (:489-523): the chosen values are gathered into LDS (the bid keys and objects are no longer needed), then
+    // one lane adds them in row order.
+    double *selv = reinterpret_cast<double *>(bid_key);
+    int *nsel = bid_obj;
+    rows.gather(p2o, n, selv, nsel);
+    __syncthreads();
+    if (tid == 0) {
+        const double obj = rows.objective(p2o, n, selv, nsel);
+        misslap_dense_batch_meta r;
+        r.struct_size = (int32_t)sizeof(misslap_dense_batch_meta);
+        r.n_rows = n;
+        r.n_cols = rows.meta_cols(m);
+        r.eCE = ece ? 1 : 0;
+        r.nnz = rows.meta_nnz();
+        r.its = nits;
+        r.n_assigned = n - K;
+        r.nreductions = nred;
+        r.soln_found = ece ? 1 : 0;  // is_optimal (:433-439)
+        r.start_eps = start_eps;
+        r.final_eps = eps;
+        r.target_eps = target_eps;
+        r.obj_f32 = (float)obj;
+        r.obj_f64 = obj;
+        r.bids_made = bids;
+        a.meta[b] = r;
+    }
+}
+
+}  // namespace misslap

@@ -39,6 +39,7 @@
 #include "kernels_matching.hpp"
 #include "kernels_tiled.hpp"
 #include "kernels_warm.hpp"
+#include "kernels_batch_solve.hpp"
 #include "kernels_dense_batch.hpp"
 #include "kernels_sparse_batch.hpp"
 #include "kernels_matching_batch.hpp"
@@ -506,6 +507,7 @@ MISSLAP_API int misslap_get_state(misslap_solver *h, double *prices, int32_t *un
 }
 #include "abi_diag.hpp"
 #include "abi_warm.hpp"
+#include "abi_batch_common.hpp"
 #include "abi_dense_batch.hpp"
 #include "abi_sparse_batch.hpp"
 #include "abi_matching_batch.hpp"

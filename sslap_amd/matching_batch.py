@@ -6,14 +6,11 @@ and its result is exactly the reference's HopcroftKarpSolverCython.solve() on th
 pairing arrays (csrc/kernels_matching_batch.hpp).  The reference has no counterpart; it matches one graph per call.
 """
 import ctypes as C
-import os
 
 import numpy as np
 
 from . import _lib
-from .auction_solve import _ENV_DEVICE, _cname
-from .dense_batch import _is_device_tensor
-from .sparse_batch import _maxima
+from ._batch import _check_offsets, _check_shapes, _check_stack, _is_device_tensor, _maxima, _options
 
 MAX_DIM = _lib.MATCHING_BATCH_MAX_DIM
 
@@ -54,76 +51,24 @@ def _check_loc(loc, offsets):
             raise ValueError("a device tensor must be contiguous (it is read in place)")
     else:
         raise TypeError("loc must be a numpy array, a contiguous int32 tensor on the device or a list of numpy arrays")
-    nnz = int(loc.shape[0])
-    if offsets is None:
-        raise ValueError("offsets is required with a packed loc (a list of per-graph loc arrays needs none)")
-    if _is_device_tensor(offsets):
-        raise TypeError("offsets must be a host array")
-    off = np.asarray(offsets)
-    if off.ndim != 1 or off.shape[0] < 2 or not np.issubdtype(off.dtype, np.integer):
-        raise ValueError(f"offsets must be a 1-d integer array of length B + 1 >= 2, got {off.dtype} {off.shape}")
-    off = off.astype(np.int64)
-    if off[0] != 0 or off[-1] != nnz:
-        raise ValueError(f"offsets must start at 0 and end at nnz = {nnz}, got {int(off[0])} .. {int(off[-1])}")
-    if (np.diff(off) < 0).any():
-        b = int(np.flatnonzero(np.diff(off) < 0)[0])
-        raise ValueError(f"offsets must be non-decreasing (offsets[{b}] > offsets[{b + 1}])")
-    return loc, off.shape[0] - 1, np.ascontiguousarray(off), on_device
+    B, off = _check_offsets(offsets, int(loc.shape[0]),
+                            "offsets is required with a packed loc (a list of per-graph loc arrays needs none)")
+    return loc, B, off, on_device
 
 
 def _check_mats(mats, shapes):
     """mats (numpy or device float64, (B, N, M)) and optional shapes; returns (B, N, M, shapes int32 or None, on_device)."""
-    if isinstance(mats, np.ndarray):
-        on_device = False
-        if mats.ndim != 3:
-            raise ValueError(f"mats must have 3 dimensions (B, N, M), got {mats.ndim}")
-        if mats.dtype != np.float64:
-            raise ValueError(f"Buffer dtype mismatch, expected 'double' but got '{_cname(mats.dtype)}'")
-    elif _is_device_tensor(mats):
-        import torch
-        on_device = True
-        if mats.dim() != 3:
-            raise ValueError(f"mats must have 3 dimensions (B, N, M), got {mats.dim()}")
-        if mats.dtype != torch.float64:
-            raise ValueError(f"mats must be float64, got {mats.dtype}")
-        if not mats.is_contiguous():
-            raise ValueError("a device tensor must be contiguous (it is read in place)")
-    else:
-        raise TypeError("mats must be a numpy array or a contiguous tensor on the device")
-    B, N, M = (int(d) for d in mats.shape)
-    if B < 1 or N < 1 or M < 1:
-        raise ValueError(f"empty stack of shape {(B, N, M)}")
+    B, N, M, on_device = _check_stack(mats)
     if shapes is None:
         if N > MAX_DIM or M > MAX_DIM:
             raise ValueError(f"graph 0: {N} x {M} exceeds MISSLAP_MATCHING_BATCH_MAX_DIM ({MAX_DIM})")
         return B, N, M, None, on_device
-    s = np.asarray(shapes)
-    if s.shape != (B, 2) or not np.issubdtype(s.dtype, np.integer):
-        raise ValueError(f"shapes must be an integer array of shape ({B}, 2), got {s.dtype} {s.shape}")
-    bad = (s[:, 0] < 1) | (s[:, 0] > N) | (s[:, 1] < 1) | (s[:, 1] > M)
-    if bad.any():
-        b = int(np.flatnonzero(bad)[0])
-        raise ValueError(f"graph {b}: shape ({int(s[b, 0])}, {int(s[b, 1])}) outside 1 .. {N} x 1 .. {M}")
+    s = _check_shapes(shapes, B, N, M, "graph")
     big = (s[:, 0] > MAX_DIM) | (s[:, 1] > MAX_DIM)
     if big.any():
         b = int(np.flatnonzero(big)[0])
         raise ValueError(f"graph {b}: {int(s[b, 0])} x {int(s[b, 1])} exceeds MISSLAP_MATCHING_BATCH_MAX_DIM ({MAX_DIM})")
-    return B, N, M, np.ascontiguousarray(s, dtype=np.int32), on_device
-
-
-def _options(on_device, dev_tensor):
-    opts = _lib.Options()
-    opts.struct_size = C.sizeof(_lib.Options)
-    opts.device = int(os.environ.get(_ENV_DEVICE, 0))
-    stream = None
-    if on_device:
-        import torch
-        if dev_tensor.device.index is not None:
-            opts.device = dev_tensor.device.index
-        stream = torch.cuda.current_stream(dev_tensor.device).cuda_stream
-    opts.input_on_device = 1 if on_device else 0
-    opts.input_stream = None if stream is None else C.c_void_p(int(stream))
-    return opts
+    return B, N, M, s, on_device
 
 
 def hopcroft_solve_batch(loc=None, offsets=None, mats=None, shapes=None):

@@ -2,16 +2,17 @@
 
 The batch form of `auction_solve(loc=, val=, size=)`: problem b of a packed (loc, val) is solved by one workgroup of one
 launch, and its result is exactly what `from_sparse(loc_b, val_b, size=sizes[b], ...).solve()` returns
-(csrc/kernels_sparse_batch.hpp).  The reference has no counterpart; it solves one problem per AuctionSolver.
+(csrc/kernels_batch_solve.hpp, csrc/kernels_sparse_batch.hpp).  The reference has no counterpart; it solves one
+problem per AuctionSolver.
 """
 import ctypes as C
-import os
 
 import numpy as np
 
 from . import _lib
-from .auction_solve import _ENV_DEVICE, _cname
-from .dense_batch import _is_device_tensor
+from ._batch import (_check_offsets, _decode_meta, _is_device_tensor, _maxima, _new_meta, _solve_options,
+                     _starting_prices)
+from .auction_solve import _cname
 
 MAX_DIM = _lib.SPARSE_BATCH_MAX_DIM
 
@@ -74,20 +75,9 @@ def _check_input(loc, val, offsets):
     nnz = int(loc.shape[0])
     if int(val.shape[0]) != nnz:
         raise ValueError(f"loc holds {nnz} entries, val {int(val.shape[0])}")
-    if offsets is None:
-        raise ValueError("offsets is required with packed loc / val (a list of (loc, val) pairs needs none)")
-    if _is_device_tensor(offsets):
-        raise TypeError("offsets must be a host array")
-    off = np.asarray(offsets)
-    if off.ndim != 1 or off.shape[0] < 2 or not np.issubdtype(off.dtype, np.integer):
-        raise ValueError(f"offsets must be a 1-d integer array of length B + 1 >= 2, got {off.dtype} {off.shape}")
-    off = off.astype(np.int64)
-    if off[0] != 0 or off[-1] != nnz:
-        raise ValueError(f"offsets must start at 0 and end at nnz = {nnz}, got {int(off[0])} .. {int(off[-1])}")
-    if (np.diff(off) < 0).any():
-        b = int(np.flatnonzero(np.diff(off) < 0)[0])
-        raise ValueError(f"offsets must be non-decreasing (offsets[{b}] > offsets[{b + 1}])")
-    return off.shape[0] - 1, nnz, np.ascontiguousarray(off), on_device
+    B, off = _check_offsets(offsets, nnz, "offsets is required with packed loc / val (a list of (loc, val) pairs needs "
+                                          "none)")
+    return B, nnz, off, on_device
 
 
 def _check_sizes(sizes, B):
@@ -97,32 +87,6 @@ def _check_sizes(sizes, B):
     if s.shape != (B, 2) or not np.issubdtype(s.dtype, np.integer):
         raise ValueError(f"sizes must be an integer array of shape ({B}, 2), got {s.dtype} {s.shape}")
     return np.ascontiguousarray(s, dtype=np.int64)
-
-
-def _maxima(loc, offsets, on_device, per_problem):
-    """(max row, max column) over all of loc, and per problem the max row (per_problem; empty problems: 0)."""
-    B = offsets.shape[0] - 1
-    nnz = int(offsets[-1])
-    if nnz == 0:
-        return -1, -1, np.zeros(B, dtype=np.int64)
-    starts = offsets[:-1]
-    nonempty = offsets[1:] > starts
-    rows = np.zeros(B, dtype=np.int64)
-    if on_device:
-        import torch
-        mx = loc.amax(dim=0).cpu().numpy()  # (ordered behind the current stream, like every read of loc)
-        if per_problem:
-            counts = torch.from_numpy(np.diff(offsets)).to(loc.device)
-            seg = torch.repeat_interleave(torch.arange(B, device=loc.device), counts)
-            r = torch.full((B,), np.iinfo(np.int32).min, dtype=torch.int32, device=loc.device)
-            r = r.scatter_reduce(0, seg, loc[:, 0], reduce="amax", include_self=True)
-            rows = r.cpu().numpy().astype(np.int64)
-    else:
-        mx = (loc[:, 0].max(), loc[:, 1].max())  # (a column at a time: 25x faster than an axis-0 reduction of (nnz, 2))
-        if per_problem:
-            rows[nonempty] = np.maximum.reduceat(loc[:, 0], starts[nonempty])
-    rows[~nonempty] = 0
-    return int(mx[0]), int(mx[1]), rows
 
 
 def auction_solve_sparse_batch(loc, val=None, offsets=None, problem="min", eps_start=0., max_iter=1000000, fast=False,
@@ -156,37 +120,10 @@ def auction_solve_sparse_batch(loc, val=None, offsets=None, problem="min", eps_s
     max_row, max_col, rows = _maxima(loc, off, on_device, per_problem=fast and szs is None)
     Nmax = min(max(max_row + 1, 1), MAX_DIM)  # (a problem beyond the cap is rejected by the library, in its order)
     Mmax = min(max(max_col + 1, 1), MAX_DIM)
-    keep = []  # buffers that must live through the call
-    p_ptr, p_ld = None, 0
-    if prices is not None:
-        if isinstance(prices, np.ndarray):
-            if prices.dtype != np.float64:
-                raise ValueError(f"Buffer dtype mismatch, expected 'double' but got '{_cname(prices.dtype)}'")
-            if prices.ndim != 2 or prices.shape[0] != B or prices.shape[1] < Mmax:
-                raise ValueError(f"prices must have shape ({B}, P) with P >= {Mmax}, got {tuple(prices.shape)}")
-            if on_device:
-                import torch
-                p = torch.from_numpy(np.ascontiguousarray(prices)).to(loc.device)
-                p_ptr = p.data_ptr()
-            else:
-                p = np.ascontiguousarray(prices)
-                p_ptr = p.ctypes.data
-        elif _is_device_tensor(prices):
-            import torch
-            if not on_device:
-                raise TypeError("prices on the device need loc / val on the device")
-            if prices.dtype != torch.float64:
-                raise ValueError(f"prices must be float64, got {prices.dtype}")
-            if prices.dim() != 2 or prices.shape[0] != B or prices.shape[1] < Mmax:
-                raise ValueError(f"prices must have shape ({B}, P) with P >= {Mmax}, got {tuple(prices.shape)}")
-            if prices.device != loc.device:
-                raise ValueError(f"prices are on {prices.device}, loc on {loc.device}")
-            p = prices.contiguous()
-            p_ptr = p.data_ptr()
-        else:
-            raise TypeError("prices must be a numpy array or a tensor on the device")
-        p_ld = int(prices.shape[1])
-        keep.append(p)
+    p, p_ptr, p_ld = _starting_prices(prices, B, Mmax, False, on_device, loc, "loc / val")
+    if _is_device_tensor(prices) and prices.device != loc.device:
+        raise ValueError(f"prices are on {prices.device}, loc on {loc.device}")
+    keep = [p]  # buffers that must live through the call
     eps_b = None
     if fast:  # auction_.pyx:614-615: eps_start = 1 / N of each problem (from_sparse's N: size[1], or the max row)
         N = szs[:, 1] if szs is not None else rows
@@ -196,21 +133,7 @@ def auction_solve_sparse_batch(loc, val=None, offsets=None, problem="min", eps_s
             raise ZeroDivisionError(f"problem {int(np.flatnonzero(zero)[0])}: division by zero")
         Nf = np.where(nonempty, N, 1).astype(np.float64)
         eps_b = np.ascontiguousarray((1.0 / Nf).astype(np.float32))
-    stream = None
-    if on_device:
-        import torch
-        stream = torch.cuda.current_stream(loc.device).cuda_stream
-    # (no tuning knob applies to this path: only the fields the entry point reads are set)
-    opts = _lib.Options()
-    opts.struct_size = C.sizeof(_lib.Options)
-    opts.device = int(os.environ.get(_ENV_DEVICE, 0))
-    if on_device and loc.device.index is not None:
-        opts.device = loc.device.index
-    opts.maximize = 1 if problem != "min" else 0  # (every string other than 'min' is 'max', auction_.pyx:236)
-    opts.eps_start = float(np.float32(e))
-    opts.max_iter = int(max_iter)
-    opts.input_on_device = 1 if on_device else 0
-    opts.input_stream = None if stream is None else C.c_void_p(int(stream))
+    opts = _solve_options(on_device, loc, problem, e, max_iter)
     if on_device:
         import torch
         sol = torch.empty((B, Nmax), dtype=torch.int32, device=loc.device)
@@ -222,28 +145,10 @@ def auction_solve_sparse_batch(loc, val=None, offsets=None, problem="min", eps_s
         sol = np.empty((B, Nmax), dtype=np.int32)
         pout = np.empty((B, Mmax), dtype=np.float64)
         sol_ptr, pout_ptr, loc_ptr, val_ptr = sol.ctypes.data, pout.ctypes.data, lc.ctypes.data, vc.ctypes.data
-    metas = (_lib.DenseBatchMeta * B)()
-    metas[0].struct_size = C.sizeof(_lib.DenseBatchMeta)
-    info = _lib.DenseBatchInfo()
+    metas, info = _new_meta(B)
     _lib.check(_lib.load().misslap_solve_sparse_batch(
         B, C.c_void_p(loc_ptr), C.c_void_p(val_ptr), off.ctypes.data, None if szs is None else szs.ctypes.data,
         None if eps_b is None else eps_b.ctypes.data, None if p_ptr is None else C.c_void_p(p_ptr), p_ld,
         1 if cardinality_check else 0, C.byref(opts), C.c_void_p(sol_ptr), Nmax, C.c_void_p(pout_ptr), Mmax,
         1 if on_device else 0, metas, C.byref(info)))
-    raw = np.ctypeslib.as_array(metas)  # structured view, one record per problem
-    obj_f32 = raw["obj_f32"].astype(np.float32)
-    start_f32, final_f32 = raw["start_eps"].astype(np.float32), raw["final_eps"].astype(np.float32)
-    meta = dict(
-        its=raw["its"].astype(np.int64), nreductions=raw["nreductions"].astype(np.int64), eCE=raw["eCE"].astype(np.int64),
-        soln_found=raw["soln_found"].astype(np.int64), n_assigned=raw["n_assigned"].astype(np.int64),
-        # rounded as the reference rounds them (auction_.pyx:264, :302-303: Python's round of the float)
-        obj=np.array([round(float(x), 3) for x in obj_f32]), obj_f64=raw["obj_f64"].astype(np.float64),
-        start_eps=np.array([round(float(x), 3) for x in start_f32]),
-        final_eps=np.array([round(float(x), 3) for x in final_f32]),
-        start_eps_f32=start_f32, final_eps_f32=final_f32, n_rows=raw["n_rows"].astype(np.int64),
-        n_cols=raw["n_cols"].astype(np.int64), nnz=raw["nnz"].astype(np.int64), bids_made=raw["bids_made"].astype(np.int64),
-    )
-    meta["timer"] = {"solve": f"{info.wall_ms:.2f}ms"}
-    meta["gpu"] = dict(threads=int(info.threads), lds_bytes=int(info.lds_bytes), check_ms=float(info.check_ms),
-                       matching_ms=float(info.matching_ms), kernel_ms=float(info.solve_ms), wall_ms=float(info.wall_ms))
-    return dict(sol=sol, prices=pout, meta=meta)
+    return dict(sol=sol, prices=pout, meta=_decode_meta(metas, info))
