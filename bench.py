@@ -9,9 +9,13 @@ Contract (one JSON line on rank 0):
   roofline = the bid kernel (k_bid, the "bid-phase CSR scan"): algorithmic 8 B/edge over the summed
              HIP-event durations of its launches inside the timed steps, against 8 TB/s HBM;
   cpu_baseline = the C oracle (oracle/, a port of the reference's algorithm) on a bounded sample of the
-             same workload, one host core, rank 0, N = 1 only.
+             same workload, one host core, rank 0, N = 1 only (--full).
+A plain run sets up, warms up, times the K steps, dumps (--dump-outputs) and prints the line; every figure of the line
+that is formed from the timed steps is in it.  --full adds what takes runs of its own after the timed steps: the CPU
+baseline (not with --no-cpu), one untimed solve with every bid launch timed (bid_phase.grid_all_launches), one untimed
+solve from host arrays (solve_incl_h2d) and the measured HBM peaks (roofline.peak_measured_*); without it those are null.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3] [--no-cpu] [--mode sharded|replicas]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3] [--full] [--no-cpu] [--mode sharded|replicas]
   [--dump-outputs DIR]
 N > 1: one rank per GPU.  Under torch.distributed.run (RANK / WORLD_SIZE in the environment) this process IS a rank;
 without a launcher `python bench.py --gpus N` starts the N ranks itself -- fresh child processes, spawned before this
@@ -32,6 +36,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X spec (MI355X_MICROARCH.md); measured copy peak is ~6300
+RANK_FAILURE_GRACE_S = 30.0  # launch_ranks: how long the other ranks may still run after one of them failed
 
 
 def cpu_baseline(cfg, budget_rounds, whole, args=None):
@@ -124,8 +129,12 @@ def launch_ranks(n, argv):
         deadline = time.time() + float(os.environ.get("MISSLAP_BENCH_TIMEOUT_S", 3000))
         try:
             while any(p.poll() is None for p in procs):
-                if any(p.poll() not in (None, 0) for p in procs) or time.time() > deadline:
-                    break  # one rank failed (or the run hangs): the others would wait in a collective for ever
+                if any(p.poll() not in (None, 0) for p in procs):
+                    # one rank failed: the others may be failing on their own a moment later (their messages belong to the
+                    # report) or wait in a collective for ever -- a grace period, then they are killed
+                    deadline = min(deadline, time.time() + RANK_FAILURE_GRACE_S)
+                if time.time() > deadline:
+                    break  # (or the run hangs)
                 time.sleep(0.2)
         finally:
             for p in procs:
@@ -315,7 +324,10 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--config", default="C3")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also what takes runs of its own: the cpu_baseline leg, an untimed solve with "
+                         "every bid launch timed, an untimed solve from host arrays and the measured HBM peaks")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the cpu_baseline leg")
     ap.add_argument("--cpu-rounds", type=int, default=100_000)
     ap.add_argument("--cpu-sample-only", action="store_true", help="cpu_baseline: the bounded sample only")
     ap.add_argument("--tail-threshold", type=int, default=None)
@@ -592,7 +604,7 @@ def run_rank(args, rank, world, local_rank, ranks, comm, shared, backend):
         # one extra, untimed solve with every bid launch bracketed by HIP events (profile level 3 costs host time,
         # so it is kept out of the timed steps)
         grid_all = None
-        if world == 1 or replicas:
+        if args.full and (world == 1 or replicas):
             gpu_opts3 = dict(gpu_opts, profile=3)
             s3 = AuctionSolver.from_device_pointers(d_loc.data_ptr(), d_val.data_ptr(), nnz, problem="max",
                                                     max_iter=10**8, **gpu_opts3)
@@ -612,7 +624,7 @@ def run_rank(args, rank, world, local_rank, ranks, comm, shared, backend):
         # brackets the CSR build from host arrays (auction_.pyx:206-207, :265), here that includes the H2D copy of the
         # COO input (16 B per entry, pageable numpy memory)
         incl_h2d = None
-        if world == 1 and args.config != "C5":
+        if args.full and world == 1 and args.config != "C5":
             loc_h, val_h = workload(args, synth)
             t_h = time.perf_counter()
             sh = AuctionSolver(loc_h, val_h, problem="max", max_iter=10**8, device=local_rank)
@@ -623,7 +635,7 @@ def run_rank(args, rank, world, local_rank, ranks, comm, shared, backend):
                         "h2d_bytes": int(loc_h.nbytes + val_h.nbytes),
                         "note": "create from host numpy arrays (H2D of the COO input + CSR build) + solve; never part of `value`"}
             del sh, loc_h, val_h
-        read_peak, copy_peak = measured_hbm_peaks(local_rank)
+        read_peak, copy_peak = measured_hbm_peaks(local_rank) if args.full else (None, None)
         conc = None
         if args.concurrent > 1 and world == 1:
             opts_c = dict(gpu_opts, profile=False)
@@ -657,7 +669,7 @@ def run_rank(args, rank, world, local_rank, ranks, comm, shared, backend):
             "metric": "Medges/s (bid-phase CSR nnz/s) + solve ms, N=200k d=0.1% sparse LAP",
             "value": round(edges_all / dt / 1e6, 2),
             "unit": "Medges/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "full": args.full,
             "ms_per_step": round(1e3 * dt / args.steps, 3),
             "higher_is_better": True,
             "scaling": "weak" if replicas else "strong",
@@ -721,9 +733,10 @@ def run_rank(args, rank, world, local_rank, ranks, comm, shared, backend):
                 "algorithmic_bytes_per_launch": round(rk_edges * bpe / max(rk_launches, 1)),
                 # the same achieved rate against what the library's own streaming kernels reach on this GPU in this
                 # process: a read-only pass (the roofline kernel only reads: the fractions are against THIS) and a copy
-                "peak_measured_read": round(read_peak, 1), "peak_measured_copy": round(copy_peak, 1),
-                "frac_of_measured": round(achieved / read_peak, 5),
-                "fullscan_frac_of_measured": round(fs_achieved / read_peak, 5),
+                "peak_measured_read": round(read_peak, 1) if read_peak else None,
+                "peak_measured_copy": round(copy_peak, 1) if copy_peak else None,
+                "frac_of_measured": round(achieved / read_peak, 5) if read_peak else None,
+                "fullscan_frac_of_measured": round(fs_achieved / read_peak, 5) if read_peak else None,
                 "timing": "HIP events handed to the launch (hipExtLaunchKernel): begin / end of the kernel itself",
                 "traffic": traffic,
                 "traffic_over_algorithmic": (round(traffic / max(rk_edges * bpe / max(rk_launches, 1), 1.0), 3)
@@ -775,7 +788,7 @@ def run_rank(args, rank, world, local_rank, ranks, comm, shared, backend):
             "concurrent": conc,
             "batch": batch,
         }
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             whole = not args.cpu_sample_only and args.config != "C5"  # (C5: ~20 min of oracle time)
             out["cpu_baseline"] = cpu_baseline(args.config, args.cpu_rounds, whole, args)
         else:

@@ -238,3 +238,33 @@ def test_bench_batch_leg_reports_beside_the_single_solve_value(gpu_lib):
     assert d["sol_sha256"] == g["sol_sha256"] and b["all_sha256_equal_reference_run"] is True
     assert b["B"] == 12 and b["groups"] == 3 and 0 < b["launches_issued"] < b["calls_recorded"]
     assert b["throughput_vs_single_solve"] > 1.0 and d["value"] > 0 and d["n_gpus"] == 1
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_is_the_timed_steps_and_full_adds_the_legs_of_their_own(gpu_lib):
+    """A plain `python bench.py` prints the line formed from the timed steps and nothing that needs a run of its own;
+    `--full` adds the CPU baseline, the two extra untimed solves and the measured HBM peaks."""
+    import subprocess
+    import sys
+    g = json.load(open(os.path.join(ROOT, "tests", "golden", "large_cases.json")))["cases"]["C1"]
+    lines = {}
+    for extra in ((), ("--full",)):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0", "--config", "C1",
+                            *extra], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        for k in ("metric", "value", "unit", "ms_per_step", "higher_is_better", "dtype", "roofline", "bid_phase"):
+            assert k in d, k
+        assert d["sol_sha256"] == g["sol_sha256"] and d["value"] > 0 and d["full"] == bool(extra)
+        assert abs(d["roofline"]["frac"] - d["roofline"]["achieved"] / d["roofline"]["peak"]) < 1e-4
+        lines[bool(extra)] = d
+    plain, full = lines[False], lines[True]
+    assert plain["cpu_baseline"] is None and plain["solve_incl_h2d"] is None
+    assert plain["bid_phase"]["grid_all_launches"] is None
+    assert plain["roofline"]["peak_measured_read"] is None and plain["roofline"]["frac_of_measured"] is None
+    c = full["cpu_baseline"]
+    assert c["kind"] == "port" and c["value"] > 0 and c["optimised_same_assignment"] is True
+    assert full["solve_incl_h2d"]["h2d_bytes"] == 16 * full["config"]["nnz"]
+    assert full["bid_phase"]["grid_all_launches"]["launches"] > 0
+    r = full["roofline"]
+    assert r["peak_measured_read"] > 0 and abs(r["frac_of_measured"] - r["achieved"] / r["peak_measured_read"]) < 1e-3

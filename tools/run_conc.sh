@@ -5,7 +5,7 @@ for spec in "$@"; do
   B=${spec%%:*}; envs=""; [ "$spec" != "$B" ] && envs=${spec#*:}
   tag=${C}_B$B$(echo "$envs" | tr -c 'A-Za-z0-9=\n' '_')
   ( IFS=,; for kv in $envs; do export "$kv"; done
-    timeout -k 10 500 python3 bench.py --config "$C" --no-cpu --steps 3 --warmup 1 --concurrent "$B" > "$O/conc_$tag.json" 2> "$O/conc_$tag.err" ); rc=$?
+    timeout -k 10 500 python3 bench.py --config "$C" --full --no-cpu --steps 3 --warmup 1 --concurrent "$B" > "$O/conc_$tag.json" 2> "$O/conc_$tag.err" ); rc=$?
   python3 - "$O/conc_$tag.json" "$tag" <<'PY'
 import json, sys
 try:

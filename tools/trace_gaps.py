@@ -6,8 +6,8 @@ around them.
     rocprofv3 --kernel-trace -d D -o t --output-format csv -- python3 bench.py --config C4 --no-cpu ...
     python3 tools/trace_gaps.py D/t_kernel_trace.csv [solve_index]
 
-solve_index: which solve of the trace (default 3: with --warmup 1 --steps 3 the last timed step; the solves behind it are
-bench.py's profiled extra solve and the one from host arrays)."""
+solve_index: which solve of the trace (default 3: with --warmup 1 --steps 3 the last timed step; under bench.py --full the
+solves behind it are its profiled extra solve and the one from host arrays)."""
 import csv
 import json
 import sys
