@@ -328,6 +328,16 @@ __device__ __forceinline__ int half_max_i32(int v) {
     v = max(v, (dpp_i32<kDppBcast15, 0xA>(v)));
     return v;
 }
+// ... valid in EVERY lane of each half: the last step swaps rows 0 <-> 1 and 2 <-> 3 (one v_permlane16_swap, gfx950)
+// instead of broadcasting row 0 / 2 into row 1 / 3, so a lane compares with its own half's maximum without a readlane
+__device__ __forceinline__ int half_allmax_i32(int v) {
+    v = max(v, dppf_i32<kDppXor1>(v));
+    v = max(v, dppf_i32<kDppXor2>(v));
+    v = max(v, dppf_i32<kDppHalfMirror>(v));
+    v = max(v, dppf_i32<kDppMirror>(v));
+    const auto s = __builtin_amdgcn_permlane16_swap(v, v, false, false);
+    return max((int)s[0], (int)s[1]);
+}
 
 // the cost of a line slot's candidate (lane-wise / of lane `sl`, wave-uniform), and the lines in memory
 __device__ __forceinline__ double slot_cost(const int2 &s) { return (double)__int_as_float(s.y); }

@@ -494,7 +494,7 @@ int launch_tail(misslap_solver *h) {
     const int min_alive_long = kLongRowMinAlive;
     // every line checked at today's prices (kernels_round.hpp); then the rounds with more than kTeamMax bidders, with
     // sixteen wavefronts (kernels_tail.hpp); then -- lines only -- the rounds with 3..kTeamMax bidders, one list slot
-    // per wavefront; then the rest: with lines the two-wavefront duo / chain instance, without them the 512-thread
+    // per wavefront; then the rest: with lines the one-wavefront pair / chain instance, without them the 512-thread
     // instance that holds every mode
     // (inside a batch all three instances are launched whatever K: an instance that finds K outside its range returns
     // at once, and the problems of a group then issue the same sequence of kernels, i.e. share every launch)
@@ -520,8 +520,7 @@ int launch_tail(misslap_solver *h) {
         if ((h->K_ub > 2 || in_batch) && lines)                                                                          \
             MISSLAP_LAUNCH(h, (k_tail<E, 2 * kTailMax, true>), (F_k_tail<E, 2 * kTailMax, true>), 2 * kTailMax, dim3(1), \
                            dim3(2 * kTailMax), a, ED);                                                                   \
-        if (lines) MISSLAP_LAUNCH(h, (k_tail<E, 2 * kWave>), (F_k_tail<E, 2 * kWave, false>), 2 * kWave, dim3(1),        \
-                                  dim3(2 * kWave), a, ED);                                                               \
+        if (lines) MISSLAP_LAUNCH(h, (k_tail<E, kWave>), (F_k_tail<E, kWave, false>), kWave, dim3(1), dim3(kWave), a, ED); \
         else MISSLAP_LAUNCH(h, (k_tail<E, kTailMax>), (F_k_tail<E, kTailMax, false>), kTailMax, dim3(1), dim3(kTailMax), a, ED); \
     } while (0)
     if (h->f32) MISSLAP_LAUNCH_TAIL(EdgesF32, e32);

@@ -21,10 +21,9 @@
 //         both), misses queued and scanned in a second pass, wavefront 0 resolves (LDS hash table above 64 bidders);
 //   team  (3 <= K <= 16; 1024 threads): wavefront w serves slot w alone; ONE LDS-only barrier per round, every
 //         serving wavefront finishes the round for the whole list on lanes = slots;
-//   duo / chain (K <= 2; 512 threads): K = 2: wavefronts 0 and 1, one bidder each, one LDS-only barrier per round --
-//         the other six wavefronts END when K reaches 2, so that barrier is between two wavefronts; K = 1: wavefront 0
-//         alone, no barrier, no LDS.  (Solo mode -- both bidders in the two halves of wavefront 0 -- is what the
-//         layout without lines uses for K = 2.)
+//   pair / chain (K <= 2; 64 threads): one wavefront, no barrier, no LDS; K = 2: both bidders' lines in the two
+//         32-lane halves, one evaluation for both (tail_pair_mode); K = 1: the chain.  (Solo mode -- the older form of
+//         the same idea -- is what the layout without lines uses for K = 2.)
 // The 512-thread instance still holds every mode (two slots per wavefront in team mode): a handle whose lines are
 // switched off runs in it alone (plus the block instance).  Both edge layouts keep lines; in the 12 B/edge layout a
 // slot's cost comes from a parallel line of fp64 costs (device_common.hpp: Slot64).
@@ -399,6 +398,181 @@ __device__ __forceinline__ void tail_solo_mode(const TailArgs &a, const E &ed, i
     }
 }
 
+// ---- pair mode: K == 2, handles with lines ---------------------------------------------------------------------------
+// Wavefront 0 alone, in the form of the chain round: person A's line in lanes 0..31, person B's in lanes 32..63, ONE line
+// load, ONE record gather and ONE evaluation serve both bids; no LDS, no barrier.  Per half the chain's "winner first"
+// shortcut: one 32-bit reduction of the values' high words (half_allmax_i32: every lane holds its half's maximum), one
+// ballot, popc / ffs per half; the exact 64-bit passes only when a half has a tie on the high word.  Both next lines
+// are requested with one load as soon as both winners are known ("both bidders win, nobody moves").
+// Both bids use the prices of the previous round: this round's records are stored after both bids are formed, and the
+// next gather follows those stores in program order (the wavefront's memory path is in order), so nothing gathered
+// ahead has to be patched.  A clean round -- two different objects, both owned: 99.9 % -- needs no RESOLVE: both
+// bidders win, each slot passes to the owner its bidder evicts (:409), and both records go out as ONE store on lanes 0
+// and 32.  Any other round runs RESOLVE (:375-385, strict ">": the earlier list position keeps an object on equal
+// bids), ASSIGN (:396-418) and push_all_left on two slots (:137-162) as tail_solo_mode does.  A line that does not
+// decide is answered by a full scan of the row, and the line is rebuilt, inside the miss block.  When K falls to 1 the
+// wavefront goes on in tail_chain_mode.
+template <class E>
+__device__ __forceinline__ void tail_pair_mode(const TailArgs &a, const E &ed, int *sU, int *sStart, int &K,
+                                               long long &nits, const long long max_iter, const double eps,
+                                               TailStats &st) {
+    const int lane = lane_id(), l32 = lane & (kCandLanes - 1);
+    const bool upper = lane >= kCandLanes;  // the lane serves slot 1
+    const RecSource src{a.rec};
+    const bool cls = (l32 >= 1) & (l32 <= kCandMax);
+    const double ninf = -__builtin_huge_val();
+    int pi[2], ps[2];
+#pragma unroll
+    for (int X = 0; X < 2; ++X) {
+        pi[X] = __builtin_amdgcn_readfirstlane(sU[X]);
+        ps[X] = __builtin_amdgcn_readfirstlane(sStart[X]);
+    }
+    typename E::Slot slot;
+    auto request = [&](int p0, int p1) { slot = line_of<E>(a, upper ? p1 : p0, l32); };
+    const int rmax = round_limit(nits, max_iter);
+    int r = 0;
+    if (K == 2) request(pi[0], pi[1]);
+#ifdef MISSLAP_TAIL_STAMP_DUO
+    // diagnostic build: cycles per segment of a K = 2 round -> Ctl::dbg[6..11]: [6] wait for the lines, [7] record gather,
+    // [8] both winners known + next lines requested, [9] rest of the evaluation, [10] full scans of missed persons,
+    // [11] resolve / stores / re-request
+    unsigned long long sacc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, sprev = __builtin_amdgcn_s_memtime();
+    const CycleStamp stamp{sacc, &sprev, true};
+#else
+    const NoStamp stamp;
+#endif
+    while (K == 2) {  // (wave-uniform: the loop ends by `break`)
+        stamp(1);
+        const PriceRec g = cand_gather1(slot, cls, src);
+        stamp(2);
+        // both line evaluations (cand_eval1_r per half)
+        const bool is_cand = cls & (slot.x >= 0);
+        const double v = is_cand ? slot_cost(slot) - g.price : ninf;  // vi = cost - p[j]   (:350)
+        const int hw = __double2hiint(v);
+        const int k = hw ^ ((hw >> 31) & 0x7fffffff);  // signed order of k == order of the doubles' high words
+        const unsigned long long eq = __ballot(k == half_allmax_i32(k));
+        const unsigned eq0 = (unsigned)eq, eq1 = (unsigned)(eq >> 32);
+        int G[2];  // winning lane of each half (-1: no candidate)
+        double V[2];
+        if ((int)(__popc(eq0) == 1) & (int)(__popc(eq1) == 1)) {  // wave-uniform, the common case
+            G[0] = __ffs((int)eq0) - 1;
+            G[1] = __ffs((int)eq1) + (kCandLanes - 1);
+            V[0] = readlane_f64(v, G[0]);
+            V[1] = readlane_f64(v, G[1]);
+        } else {  // a tie on the high word: the exact passes (for both halves, in the same instructions)
+            const double vm = half_max_f64(v);
+            V[0] = readlane_f64(vm, kCandLanes - 1);
+            V[1] = readlane_f64(vm, kWave - 1);
+            const int gm = half_max_i32((is_cand & (v == (upper ? V[1] : V[0]))) ? lane : -1);  // the LAST slot holding it
+            G[0] = __builtin_amdgcn_readlane(gm, kCandLanes - 1);
+            G[1] = __builtin_amdgcn_readlane(gm, kWave - 1);
+        }
+        CandBid b[2];
+        double tau[2], c1[2];
+#pragma unroll
+        for (int X = 0; X < 2; ++X) {
+            const int sl = max(G[X], kCandLanes * X);
+            tau[X] = readlane_f64(__hiloint2double(slot.y, slot.x), kCandLanes * X);
+            b[X].len = __builtin_amdgcn_readlane(slot.x, kCandLanes * X + kCandLanes - 1);
+            b[X].obj = __builtin_amdgcn_readlane(slot.x, sl);
+            b[X].prev = __builtin_amdgcn_readlane(g.owner, sl);
+            b[X].pstart = __builtin_amdgcn_readlane(g.ostart, sl);
+            c1[X] = slot_cost_at(slot, sl);
+        }
+        const int sp0 = b[0].prev, sp1 = b[1].prev;  // the persons whose lines are requested early
+        request(sp0, sp1);  // `slot` is dead from here on
+        stamp.light(3);
+        const double wm = half_max_f64(((lane == G[0]) | (lane == G[1])) ? ninf : v);  // second best, counting multiplicity
+        const double W[2] = {readlane_f64(wm, kCandLanes - 1), readlane_f64(wm, kWave - 1)};
+#pragma unroll
+        for (int X = 0; X < 2; ++X) {
+            b[X].hit = (G[X] >= 0) & (V[X] > tau[X]) & (W[X] >= tau[X]);
+            const double bid = (c1[X] - W[X]) + eps;  // bbest = costbest - wi + eps   (:360)
+            st.bad_hi = max(st.bad_hi, b[X].hit ? (unsigned)__double2hiint(bid) : 0u);  // (see cand_eval1_r)
+            b[X].key = bid_to_key(bid);
+        }
+        stamp.light(4);
+#pragma unroll
+        for (int X = 0; X < 2; ++X) {
+            if (!b[X].hit) {  // wave-uniform (rare behind the maintenance pass: the scan and the line's rebuild stay inside
+                              // this block -- what the rebuild needs must not be carried across the join with the common path)
+                CandBuildArgs bd;
+                const typename E::Raw none[4] = {};
+                const int e = a.row_ptr[pi[X] + 1];
+                wave_bid_full<E, RecSource, true, false>(ed, src, ps[X], e, none, eps, b[X], bd, st.err);
+                st.misses += 1;
+                st.miss_edges += (unsigned long long)b[X].len;
+                if (bd.want) tail_build(a, pi[X], bd, eps, st);
+            }
+        }
+        stamp.light(5);
+        st.edges += (unsigned long long)(b[0].len + b[1].len);
+        st.bids += 2;
+        r += 1;
+        if ((b[0].obj != b[1].obj) & (b[0].prev >= 0) & (b[1].prev >= 0)) {  // wave-uniform
+            // CLEAN: both bidders win (:375-385 has nothing to resolve); ASSIGN (:396-418) of both as one store on
+            // lanes 0 and 32; each slot passes to the owner its bidder evicts (:409)
+            if (l32 == 0) {
+                PriceRec w;
+                w.price = key_to_bid(upper ? b[1].key : b[0].key);
+                w.owner = upper ? pi[1] : pi[0];
+                w.ostart = upper ? ps[1] : ps[0];
+                a.rec[upper ? b[1].obj : b[0].obj] = w;
+            }
+#pragma unroll
+            for (int X = 0; X < 2; ++X) {
+                pi[X] = b[X].prev;
+                ps[X] = b[X].pstart;
+            }
+        } else {
+            // RESOLVE (:375-385): strict ">" -- the earlier list position keeps an object on equal bids
+            bool win0 = true, win1 = true;
+            if (b[0].obj == b[1].obj) {
+                if (b[1].key > b[0].key) win0 = false;
+                else win1 = false;
+            }
+            // ASSIGN (:396-418): a winner's slot goes to the evicted owner (or becomes a hole), a loser stays
+            if (lane == 0) {
+                if (win0) apply_winner(a, pi[0], ps[0], b[0].obj, b[0].prev, b[0].key);
+                if (win1) apply_winner(a, pi[1], ps[1], b[1].obj, b[1].prev, b[1].key);
+            }
+            if (win0) {
+                pi[0] = b[0].prev;
+                ps[0] = b[0].pstart;
+            }
+            if (win1) {
+                pi[1] = b[1].prev;
+                ps[1] = b[1].pstart;
+            }
+            // push_all_left (:137-162) on two slots
+            if (pi[0] == -1 && pi[1] != -1) {
+                pi[0] = pi[1];
+                ps[0] = ps[1];
+                pi[1] = -1;
+            }
+            K = (pi[0] != -1) + (pi[1] != -1);
+        }
+        const bool done = K <= 1 || r >= rmax;
+        // the early request assumed "both bidders win, nobody moves"; otherwise (a scanned row that decided differently
+        // from its line, a lost bid, the end of a chain) request again
+        if (!done && (sp0 != pi[0] || sp1 != pi[1])) request(pi[0], pi[1]);
+        stamp.light(6);
+        if (done) break;
+    }
+    nits += r;
+#ifdef MISSLAP_TAIL_STAMP_DUO
+    if (lane == 0)
+        for (int k = 1; k <= 6; ++k) a.ctl->dbg[5 + k] += sacc[k];
+#endif
+    if (K == 1 && nits < max_iter) tail_chain_mode(a, ed, pi[0], ps[0], K, nits, max_iter, eps, st);
+    if (lane == 0) {
+        sU[0] = pi[0];
+        sU[1] = pi[1];
+        sStart[0] = ps[0];
+        sStart[1] = ps[1];
+    }
+}
+
 // ---- team mode: 3 <= K <= 16 -----------------------------------------------------------------------------------
 // Wavefront w serves list slots 2w and 2w + 1 (the two halves of its lines).  ONE barrier per round: the bids AND the
 // bidders go to LDS (double-buffered by round parity), and behind the barrier EVERY wavefront finishes the round for
@@ -578,10 +752,10 @@ __device__ __forceinline__ void tail_team_mode(const TailArgs &a, const E &ed, i
     __syncthreads();
 }
 
-// ---- the team and duo rounds of handles with lines: few instructions, one barrier, the next gather issued ahead ---------
+// ---- the team rounds of handles with lines: few instructions, one barrier, the next gather issued ahead ----------------
 // A wavefront of the tail issues one instruction every ~8 cycles whatever the instruction is (tools/micro/
 // exec_mask_bench.hip: dependent VALU 8.2 cycles, independent 6.1; profiles/r06_tail_overheads.txt), so a round is as long
-// as the instructions on its wavefront plus the memory waits it cannot hide.  What a team / duo round does BESIDES the
+// as the instructions on its wavefront plus the memory waits it cannot hide.  What a team round does BESIDES the
 // evaluation of its line is therefore written to be few instructions:
 //   * a slot publishes TWO 16-byte LDS entries ahead of the barrier: the price record its winning bid would write
 //     {bid, bidder, bidder's row start} and {object, its owner, the owner's row start};
@@ -608,11 +782,6 @@ __device__ __forceinline__ void tail_team_mode(const TailArgs &a, const E &ed, i
 constexpr int kPipeTab = 4096;  // (K = 16: 3 % false positives of the clean test, K = 6: 0.4 %)
 __device__ __forceinline__ int pipe_hash(int obj) { return (int)(((unsigned)obj * 2654435761u) >> 20); }
 static_assert((1 << 12) == kPipeTab, "pipe_hash keeps the top 12 bits");
-__device__ __forceinline__ void patch_rec(PriceRec &r, const bool take, const PriceRec &nw) {
-    r.price = take ? nw.price : r.price;
-    r.owner = take ? nw.owner : r.owner;
-    r.ostart = take ? nw.ostart : r.ostart;
-}
 struct __attribute__((aligned(16))) PipeSlot {
     PriceRec rec;  // what the slot's winning bid writes: {bid, bidder, bidder's row start}
     int4 aux;      // {object bid on, its owner, the owner's row start, -}
@@ -804,183 +973,19 @@ __device__ __forceinline__ bool tail_team1_pipe(const TailArgs &a, const E &ed, 
     return false;
 }
 
-// duo mode in the same form: two wavefronts, one bidder each; clean = two different objects, both owned
-template <class E>
-__device__ __forceinline__ void tail_duo_pipe(const TailArgs &a, const E &ed, int *sU, int *sStart, int &K,
-                                              long long &nits, const long long max_iter, const double eps,
-                                              TailStats &st) {
-    const int lane = lane_id(), l32 = lane & (kCandLanes - 1);
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // 0 or 1: my slot
-    const int o = w ^ 1;
-    __shared__ PipeSlot D[2][2];
-    const RecSource src{a.rec};
-    const bool cls = (lane >= 1) & (lane <= kCandMax);
-    int me = __builtin_amdgcn_readfirstlane(sU[w]), mys = __builtin_amdgcn_readfirstlane(sStart[w]);
-    typename E::Slot slot = cand_no_line<typename E::Slot>();
-    auto request = [&](int person) { slot = line_of<E>(a, person, l32); };
-    request(me);
-    tail_barrier_lds();  // (sU / sStart have been read by both)
-#ifdef MISSLAP_TAIL_STAMP_DUO
-    // diagnostic build: cycles of wavefront 0 per segment of a duo round -> Ctl::dbg[6..10]: [6] evaluation up to the bid
-    // (incl. what is left of the gather's latency), [7] publish + wait for the next line + next gather issued, [8]
-    // barrier (= the other wavefront), [9] exchange / patch / stores, [10] re-request, line rebuild
-    unsigned long long sacc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, sprev = __builtin_amdgcn_s_memtime();
-    const CycleStamp stamp{sacc, &sprev, w == 0};
-#else
-    const NoStamp stamp;
-#endif
-    const int rmax = round_limit(nits, max_iter);
-    int r = 0;
-    PriceRec grec = PriceRec{0.0, -1, 0};
-    bool have_g = false;
-    int par = 0;
-    // (the two stores of a clean round are issued in the NEXT round, behind its evaluation: see tail_team1_pipe)
-    bool pend = false;
-    PriceRec prec = PriceRec{0.0, -1, 0};
-    int pobj = 0;
-    auto flush_store = [&]() {
-        if (pend) {  // wave-uniform
-            if (lane < 2) a.rec[pobj] = prec;  // ASSIGN (:396-418): lane 0 my record, lane 1 the other's
-            pend = false;
-        }
-    };
-    for (;;) {
-        int sp = -2;  // the person whose line was requested early (-2: nothing requested)
-        CandBid b;
-        b.hit = false;
-        stamp.light(0);
-        if (!have_g) {
-            flush_store();
-            grec = cand_gather1(slot, cls, src);
-        }
-        cand_eval1_r(slot, grec, cls, eps, b, st.bad_hi, [&](const CandBid &x) {
-            sp = x.prev;
-            request(sp);  // the owner my bidder evicts if it wins
-        });
-        if (!b.hit) {  // (rare behind the maintenance pass: the scan and the line's rebuild stay inside this block)
-            flush_store();
-            CandBuildArgs bd;
-            const typename E::Raw none[4] = {};
-            const int e = a.row_ptr[me + 1 + lane_zero()];
-            wave_bid_full<E, RecSource, true, false>(ed, src, mys, e, none, eps, b, bd, st.err);
-            st.misses += 1;
-            st.miss_edges += (unsigned long long)b.len;
-            if (bd.want) tail_build(a, me, bd, eps, st);
-            b.hit = false;
-        }
-        flush_store();  // (the common case: the previous round's stores, behind this round's evaluation)
-        st.edges += (unsigned long long)b.len;
-        st.bids += 1;
-        stamp.light(1);
-        PriceRec mine;
-        mine.price = key_to_bid(b.key);
-        mine.owner = me;
-        mine.ostart = mys;
-        if (lane == 0) {
-            D[par][w].rec = mine;
-            D[par][w].aux = make_int4(b.obj, b.prev, b.pstart, 0);
-        }
-        // the gather of the NEXT round, ahead of the barrier (into grec itself: its old contents are dead, and a second
-        // variable is a copy at the loop's back edge with a wait for every outstanding store in front of it)
-        have_g = b.hit && b.prev >= 0;
-        if (have_g) grec = cand_gather1(slot, cls, src);
-        stamp.light(2);
-        tail_barrier_lds();  // both bids are in LDS and both gathers of the round have been issued against the old records
-        stamp.light(3);
-        const PriceRec orec = D[par][o].rec;  // (one address for the whole wavefront)
-        const int4 oaux = D[par][o].aux;
-        r += 1;
-        const int unclean = __builtin_amdgcn_readfirstlane((int)(oaux.x == b.obj) | (int)(oaux.y < 0)) | (int)(b.prev < 0);
-        if (!unclean) {
-            // both bidders win different owned objects (:375-385 has nothing to resolve) and both slots pass to the
-            // evicted owners.  The records gathered ahead are made exact FIRST, the stores (ASSIGN, :396-418, by both
-            // wavefronts alike: lane 0 my record, lane 1 the other's) are issued behind that
-            if (have_g) {
-                const int c = slot.x;
-                patch_rec(grec, c == b.obj, mine);
-                patch_rec(grec, c == oaux.x, orec);
-            }
-            pend = true;
-            prec = mine;
-            patch_rec(prec, lane == 1, orec);
-            pobj = lane == 1 ? oaux.x : b.obj;
-            me = b.prev;
-            mys = b.pstart;
-        } else {
-            // the two bids by slot, RESOLVE (:375-385: strict ">", the earlier list position keeps an object on equal
-            // bids), ASSIGN (:396-418) by both wavefronts alike, push_all_left (:137-162) on two slots
-            const unsigned long long okey = bid_to_key(readlane_f64(orec.price, 0));
-            const int oobj = __builtin_amdgcn_readfirstlane(oaux.x), oprev = __builtin_amdgcn_readfirstlane(oaux.y);
-            const int opst = __builtin_amdgcn_readfirstlane(oaux.z);
-            const int ome = __builtin_amdgcn_readfirstlane(orec.owner), omys = __builtin_amdgcn_readfirstlane(orec.ostart);
-            int pi[2], ps[2];
-            pi[0] = w ? ome : me, pi[1] = w ? me : ome;
-            ps[0] = w ? omys : mys, ps[1] = w ? mys : omys;
-            const unsigned long long key0 = w ? okey : b.key, key1 = w ? b.key : okey;
-            const int obj0 = w ? oobj : b.obj, obj1 = w ? b.obj : oobj;
-            const int prev0 = w ? oprev : b.prev, prev1 = w ? b.prev : oprev;
-            const int pst0 = w ? opst : b.pstart, pst1 = w ? b.pstart : opst;
-            bool win0 = true, win1 = true;
-            if (obj0 == obj1) {
-                if (key1 > key0) win0 = false;
-                else win1 = false;
-            }
-            if (lane == 0) {
-                if (win0) apply_winner(a, pi[0], ps[0], obj0, prev0, key0);
-                if (win1) apply_winner(a, pi[1], ps[1], obj1, prev1, key1);
-            }
-            if (win0) {
-                pi[0] = prev0;
-                ps[0] = pst0;
-            }
-            if (win1) {
-                pi[1] = prev1;
-                ps[1] = pst1;
-            }
-            if (pi[0] == -1 && pi[1] != -1) {
-                pi[0] = pi[1];
-                ps[0] = ps[1];
-                pi[1] = -1;
-            }
-            K = (pi[0] != -1) + (pi[1] != -1);
-            me = w ? pi[1] : pi[0];
-            mys = w ? ps[1] : ps[0];
-            have_g = false;
-        }
-        stamp.light(4);
-        par ^= 1;
-        const bool done = K <= 1 || r >= rmax;
-        // the early request assumed "my bidder wins, nobody moves"; otherwise request again
-        if (!done && sp != me) request(me);
-        stamp.light(5);
-        if (done) break;
-    }
-    flush_store();
-    nits += r;
-#ifdef MISSLAP_TAIL_STAMP_DUO
-    if (w == 0 && lane == 0)
-        for (int k = 1; k <= 5; ++k) a.ctl->dbg[5 + k] += sacc[k];
-#endif
-    if (lane == 0) {  // every wavefront hands its own slot back
-        sU[w] = me;
-        sStart[w] = mys;
-    }
-    tail_barrier_lds();
-}
-
 // kThreads = kTailMax (512): every mode.  kThreads = 1024 ("block only"): the rounds with more than kTeamMax bidders
 // with SIXTEEN wavefronts -- half the sweeps per wavefront in pass A, which is where a block round spends its time --
 // and nothing else: the solo / team code needs more than the 128 registers a 1024-thread workgroup leaves a
 // wavefront.  The host launches it ahead of the 512-thread kernel, which then finds K <= kTeamMax.
 // kTeamOnly (1024 threads as well): the rounds with 3..kTeamMax bidders, one slot per wavefront (tail_team1_pipe).
-// kThreads = 128 ("duo / chain only", handles with lines): the rounds with K <= 2 and nothing else -- two wavefronts
-// for duo mode, wavefront 0 alone for the chain; the instance that carries every mode needs 185 VGPRs and spills 14
-// SGPRs, each spill a v_writelane / v_readlane pair inside a chain that is bound by its instruction count.
+// kThreads = 64 ("pair / chain only", handles with lines): the rounds with K <= 2 and nothing else, on one wavefront
+// (tail_pair_mode, then tail_chain_mode); the instance that carries every mode needs 185 VGPRs and spills 14 SGPRs,
+// each spill a v_writelane / v_readlane pair inside a chain that is bound by its instruction count.
 template <class E, int kThreads, bool kTeamOnly>
 __device__ __forceinline__ void k_tail_body(TailArgs a, E ed) {
     static_assert(!kTeamOnly || (kThreads == 2 * kTailMax && kThreads / kWave == kTeamMax), "one slot per wavefront");
     constexpr bool kBlockOnly = kThreads > kTailMax && !kTeamOnly;
-    constexpr bool kDuoOnly = kThreads == 2 * kWave;
+    constexpr bool kDuoOnly = kThreads == kWave;
     static_assert(!kDuoOnly || !kTeamOnly, "roles are exclusive");
     __shared__ int sU[kTailMax];
     __shared__ unsigned long long sKey[kTailMax];
@@ -1069,23 +1074,9 @@ __device__ __forceinline__ void k_tail_body(TailArgs a, E ed) {
     for (;;) {
         if (kBlockOnly && K <= kTeamMax) break;  // the next kernel takes over
         if (kDuoOnly) {
-            // ---- K <= 2, lines: duo mode while two bidders are left (wavefronts 0 and 1, one bidder each), then
-            // wavefront 0 runs the single-bidder chain alone
+            // ---- K <= 2, lines: wavefront 0 alone, pair rounds while two bidders are left, then the chain
             mode_begin(0);
-            if (K == 2) tail_duo_pipe(a, ed, sU, sStart, K, nits, max_iter, eps, st);
-            if (wave == 1) {
-                flush_stats();
-                return;
-            }
-            if (K == 1 && nits < max_iter) {
-                int pi = __builtin_amdgcn_readfirstlane(sU[0]), ps = __builtin_amdgcn_readfirstlane(sStart[0]);
-                tail_chain_mode(a, ed, pi, ps, K, nits, max_iter, eps, st);
-                if (lane == 0) {
-                    sU[0] = pi;
-                    sU[1] = -1;
-                    sStart[0] = ps;
-                }
-            }
+            tail_pair_mode(a, ed, sU, sStart, K, nits, max_iter, eps, st);
             mode_end(0);
             break;  // K == 0 or nits == max_iter
         }
@@ -1099,24 +1090,6 @@ __device__ __forceinline__ void k_tail_body(TailArgs a, E ed) {
                 mode_end(1);
             }
             break;
-        }
-        if (!kBlockOnly && !kTeamOnly && K == 2 && K0 <= 2 && E::kCand && a.cand != nullptr) {
-            // ---- duo mode: wavefronts 0 and 1 run the two-bidder rounds, one bidder each; the other wavefronts have
-            // nothing left to do in this phase (K never grows) and END here, so the barriers of duo mode are between
-            // two wavefronts.  Then wavefront 0 runs the single-bidder chain alone.
-            if (wave >= 2) {
-                flush_stats();
-                return;
-            }
-            mode_begin(0);
-            tail_duo_pipe(a, ed, sU, sStart, K, nits, max_iter, eps, st);
-            if (wave == 1) {
-                flush_stats();
-                return;
-            }
-            if (K > 0 && nits < max_iter) tail_solo_mode(a, ed, sU, sStart, K, nits, max_iter, eps, st);
-            mode_end(0);
-            break;  // K == 0 or nits == max_iter
         }
         if (!kBlockOnly && K <= 2) {
             // ---- solo mode: wavefront 0 runs the rest of the phase alone, see tail_solo_mode
