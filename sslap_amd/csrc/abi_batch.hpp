@@ -60,7 +60,7 @@ hipError_t batch_flush(BatchGroup &g, bool release) {
             }
             same.clear();
             for (size_t b = a; b < heads.size(); ++b)
-                if (!done[b] && heads[b]->merge == c->merge && heads[b]->block.x == c->block.x) {
+                if (!done[b] && heads[b]->merge == c->merge) {  // (the same kernel: the same block size)
                     same.push_back(heads[b]);
                     done[b] = true;
                 }

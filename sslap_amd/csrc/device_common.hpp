@@ -24,6 +24,22 @@ constexpr int kWave = 64;
 constexpr int kPosNone = 0x7fffffff;
 constexpr int kTailMax = 512;  // threads of the persistent tail workgroup (8 wavefronts: 256 VGPRs each) = max K it handles
 
+// A kernel of the solve loop that a batch can merge (host_batch.hpp) is ONE struct k_X: its block size, its body
+// `static __device__ __forceinline__ void run(parameters...)`, and -- this line, first in the struct -- the __global__
+// entry of a launch by itself, whose parameter types the launch function (launch<k_X>) takes from run's signature.  A
+// trace shows that entry as misslap::k_X<template arguments>::entry<parameter types>; a batched launch runs
+// k_batched<k_X, ...> under the same block size and bound.
+#define MISSLAP_KERNEL(BLOCK) MISSLAP_KERNEL_BOUND(BLOCK, BLOCK)
+// (BOUND above BLOCK: the one-thread kernels that post a status keep the default bound, 1024, they were compiled under)
+#define MISSLAP_KERNEL_BOUND(BLOCK, BOUND)                                                          \
+    static constexpr int kBlock = (BLOCK); /* threads of a workgroup: what every launch passes */   \
+    static constexpr int kBound = (BOUND); /* the launch bound of the entry and of k_batched */     \
+    static_assert(kBlock <= kBound, "a launch above the kernel's bound fails");                     \
+    template <class... A_>                                                                          \
+    static __global__ __launch_bounds__(BOUND) void entry(A_... a_) {                               \
+        run(a_...);                                                                                 \
+    }
+
 // sticky device-side error bits (Ctl::err)
 constexpr int kErrNegativeBid = 1;   // a bid < 0 was formed (breaks the bits-as-integer ordering)
 constexpr int kErrRowsUnsorted = 2;  // loc rows not ascending

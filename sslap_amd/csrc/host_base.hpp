@@ -123,20 +123,7 @@ inline size_t tiled_lds_bytes(int tile_cols) {  // see the LDS map in k_bid_tile
     return doubles * sizeof(double) + kTileStatBytes + kTileTouchBytes;  // + statistics scratch (incl. the arrival word of a column-split shape) + the loaders' touch scratch
 }
 
-// Profiled launches (options.profile): the two events are handed to the launch itself (hipExtLaunchKernel), so they
-// carry the begin / end timestamps of the KERNEL -- what a rocprofv3 kernel trace reports.  Events recorded around a
-// launch on the stream bracket the dispatch gap as well (~7 us per launch at C3: 92.4 against 85.6 us in round 2).
-#define MISSLAP_LAUNCH_TIMED(PR, KERNEL, GRID, BLOCK, LDS, STREAM, ...)                              \
-    do {                                                                                            \
-        if (PR) {                                                              \
-            hipExtLaunchKernelGGL(KERNEL, GRID, BLOCK, LDS, STREAM, (PR)->start, (PR)->stop, 0, __VA_ARGS__); \
-        } else {                                                                                    \
-            if (PR) (void)hipEventRecord((PR)->start, STREAM);                                      \
-            hipLaunchKernelGGL(KERNEL, GRID, BLOCK, LDS, STREAM, __VA_ARGS__);                      \
-            if (PR) (void)hipEventRecord((PR)->stop, STREAM);                                       \
-        }                                                                                           \
-    } while (0)
-
+// A profiled launch (options.profile) and the two events it was given (launch_timed / launch_alone, host_batch.hpp)
 struct ProfRec {
     hipEvent_t start, stop;
     int kind;        // 0 = k_bid, 1 = k_tail, 2 = k_bid_tiled

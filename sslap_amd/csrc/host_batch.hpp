@@ -6,14 +6,15 @@
 // only ~90 000 launches per second over all of them (round 4: every small launch takes 47-67 us next to 15 busy queues):
 // 16 solves at a time from 16 host threads / streams stall at 6-8x the single-solve throughput.  The reference's own use
 // is a loop over problems (benchmarking.py:84-142).  Here the problems of a GROUP share one stream and every launch of
-// the solve loop that several of them issue at the same point is ONE launch: the kernels' bodies are device functions
-// (k_X_body, functor F_k_X), and k_batched<F> runs F for problem blockIdx.y with that problem's own arguments, passed
-// by value in the kernel-argument block (a few hundred bytes per problem: up to kMax of them per launch).
+// the solve loop that several of them issue at the same point is ONE launch: every such kernel is a struct k_X with its
+// block size and its body as a static device function (MISSLAP_KERNEL, device_common.hpp), and k_batched<k_X> runs that
+// body for problem blockIdx.y with that problem's own arguments, passed by value in the kernel-argument block (a few
+// hundred bytes per problem: up to kMax of them per launch).
 //
 // How.  Nothing of the per-handle driver is re-derived: every handle of a group runs the ordinary solve loop
 // (drive_sharded + misslap_finish) on a FIBER of its own (ucontext), and the launch sites of host_rounds.hpp go through
-// MISSLAP_LAUNCH*: outside a batch they launch as before; inside, they RECORD the call in the handle's pending list and
-// return.  A fiber runs until it needs something from the device -- a status word that has not been posted yet
+// launch<k_X> / launch_alone (below): outside a batch they launch on the handle's stream; inside, they RECORD the call in
+// the handle's pending list and return.  A fiber runs until it needs something from the device -- a status word that has not been posted yet
 // (live_poll), or a drained stream (read_ctl) -- and yields.  When every fiber of the group has yielded, the scheduler
 // flushes: it pops the head call of every pending list, issues the heads that name the same kernel as one batched
 // launch (anything else -- the full-scan engine, asynchronous copies / fills -- goes out by itself, in order), and
@@ -61,14 +62,14 @@ struct BatchSlots {
 // problem blockIdx.y of the launch runs F with its own arguments; blockIdx.x / gridDim.x are what F's body expects (the
 // grid is the LARGEST of the merged launches' grids: every kernel of the solve loop tolerates a grid above the one the
 // host computed -- the host's K is an upper bound anyway)
-template <class F, int kBounds, class... A>
-__global__ __launch_bounds__(kBounds) void k_batched(BatchSlots<A...> p) {
+template <class F, class... A>
+__global__ __launch_bounds__(F::kBound) void k_batched(BatchSlots<A...> p) {
     if ((int)blockIdx.y < p.n) pack_call<F>(p.s[blockIdx.y]);
 }
 // ... the same for more problems than a kernel-argument block carries: their arguments staged in device memory (a ring of
 // the group, filled by an asynchronous copy on the same stream right in front of the launch)
-template <class F, int kBounds, class... A>
-__global__ __launch_bounds__(kBounds) void k_batched_ptr(const ArgPack<A...> *slots, int n) {
+template <class F, class... A>
+__global__ __launch_bounds__(F::kBound) void k_batched_ptr(const ArgPack<A...> *slots, int n) {
     if ((int)blockIdx.y < n) pack_call<F>(slots[blockIdx.y]);
 }
 
@@ -80,7 +81,7 @@ constexpr size_t kBatchArgBytes = 640;  // the largest by-value argument pack of
 
 struct BatchGroup;
 struct BatchCall {
-    // the identity of a mergeable launch (same pointer = same kernel body, bounds and argument types); launches
+    // the identity of a mergeable launch (same pointer = same kernel k_X); launches
     // calls[0 .. n) as one batched launch per kMax of them.  nullptr: `single` goes onto the stream by itself
     void (*merge)(BatchGroup &, BatchCall *const *calls, int n) = nullptr;
     std::function<void(hipStream_t)> single;
@@ -88,12 +89,10 @@ struct BatchCall {
     // reached its own (batch_flush).  The tail kernels run for milliseconds on one workgroup each: issued as the problems
     // get there, one after the other on the group's in-order stream, they would serialise; issued together they overlap
     bool hold = false;
-    dim3 grid, block;
+    dim3 grid;
     alignas(16) unsigned char args[kBatchArgBytes];
 };
 
-struct BatchGroup;
-struct BatchCall;
 // A fiber's stack: its own mapping with an inaccessible page below it, so that running out of it is a fault at the
 // guard page and not a silent write into whatever the heap had next to it.
 struct FiberStack {
@@ -167,8 +166,9 @@ inline const void *batch_stage_args(BatchGroup &g, BatchCall *const *calls, int 
     return dp;
 }
 
-// ---- recording (called from the launch sites through MISSLAP_LAUNCH*) -------------------------------------------------
-template <class F, int kBounds, class... A>
+// ---- recording (called from the launch sites through launch<k_X> / launch_alone) -------------------------------------
+// calls[0 .. n) of kernel F (a struct k_X; A = the parameter types of F::run)
+template <class F, class... A>
 void batch_merge(BatchGroup &g, BatchCall *const *calls, int n) {
     using Slots = BatchSlots<A...>;
     unsigned gx = 1;
@@ -176,7 +176,7 @@ void batch_merge(BatchGroup &g, BatchCall *const *calls, int n) {
     if (n > Slots::kMax) {  // through the device ring: ONE launch whatever n
         const void *d = batch_stage_args(g, calls, n, sizeof(ArgPack<A...>));
         if (d) {
-            hipLaunchKernelGGL((k_batched_ptr<F, kBounds, A...>), dim3(gx, (unsigned)n), calls[0]->block, 0, g.stream,
+            hipLaunchKernelGGL((k_batched_ptr<F, A...>), dim3(gx, (unsigned)n), dim3(F::kBlock), 0, g.stream,
                                static_cast<const ArgPack<A...> *>(d), n);
             return;
         }
@@ -185,19 +185,18 @@ void batch_merge(BatchGroup &g, BatchCall *const *calls, int n) {
         Slots p;
         p.n = std::min(Slots::kMax, n - k0);
         for (int k = 0; k < p.n; ++k) std::memcpy(static_cast<void *>(&p.s[k]), calls[k0 + k]->args, sizeof(ArgPack<A...>));
-        hipLaunchKernelGGL((k_batched<F, kBounds, A...>), dim3(gx, (unsigned)p.n), calls[k0]->block, 0, g.stream, p);
+        hipLaunchKernelGGL((k_batched<F, A...>), dim3(gx, (unsigned)p.n), dim3(F::kBlock), 0, g.stream, p);
     }
 }
-template <class F, int kBounds, class... A>
-void batch_record(misslap_solver *h, dim3 g, dim3 b, const A &...a) {
+template <class F, class... A>
+void batch_record(misslap_solver *h, dim3 g, const A &...a) {
     static_assert(sizeof(ArgPack<A...>) <= kBatchArgBytes, "raise kBatchArgBytes");
     static_assert(std::is_trivially_copyable<ArgPack<A...>>::value, "kernel arguments are copied as bytes");
     BatchFiber *f = h->batch;
     f->pending.emplace_back();
     BatchCall &c = f->pending.back();
-    c.merge = &batch_merge<F, kBounds, A...>;
+    c.merge = &batch_merge<F, A...>;
     c.grid = g;
-    c.block = b;
     c.hold = f->hold_next;
     f->hold_next = false;
     new (c.args) ArgPack<A...>(a...);
@@ -216,27 +215,45 @@ inline void batch_yield(misslap_solver *h, BatchFiber::State why) {
     swapcontext(&f->ctx, &f->grp->sched);
 }
 
-#define MISSLAP_UNPAREN(...) __VA_ARGS__
-// a launch of the solve loop that several problems of a batch can share: KERNEL = the __global__ wrapper (a batch-less
-// launch looks exactly as before: same kernel name in a trace), FUNCTOR = its body as a callable, BOUNDS = its block size
-#define MISSLAP_LAUNCH(H, KERNEL, FUNCTOR, BOUNDS, GRID, BLOCK, ...)                                    \
-    do {                                                                                               \
-        if (!(H)->batch) hipLaunchKernelGGL(KERNEL, GRID, BLOCK, 0, (H)->stream, __VA_ARGS__);         \
-        else batch_record<MISSLAP_UNPAREN FUNCTOR, BOUNDS>((H), GRID, BLOCK, __VA_ARGS__);             \
-    } while (0)
-// ... and one that goes out by itself also inside a batch (the full-scan engine: dynamic LDS, one workgroup per CU)
-#define MISSLAP_LAUNCH_PLAIN(H, KERNEL, GRID, BLOCK, LDS, ...)                                                          \
-    do {                                                                                                               \
-        if (!(H)->batch) {                                                                                             \
-            hipLaunchKernelGGL(KERNEL, GRID, BLOCK, LDS, (H)->stream, __VA_ARGS__);                                    \
-        } else {                                                                                                       \
-            const dim3 g_ = (GRID), b_ = (BLOCK);                                                                      \
-            const unsigned l_ = (unsigned)(LDS);                                                                       \
-            batch_record_plain((H), [g_, b_, l_, args_ = std::make_tuple(__VA_ARGS__)](hipStream_t st_) {              \
-                std::apply([&](const auto &...x_) { hipLaunchKernelGGL(KERNEL, g_, b_, l_, st_, x_...); }, args_);     \
-            });                                                                                                        \
-        }                                                                                                              \
-    } while (0)
+// ---- the launches of the solve loop ----------------------------------------------------------------------------------
+// A launch of kernel K (a struct k_X: MISSLAP_KERNEL, device_common.hpp) that several problems of a batch can share.
+// The argument types P are those of K::run and the block is K::kBlock: the entry of a launch by itself, the batched
+// instance and the launch bound of both follow from K alone.  Outside a batch: K::entry on the handle's stream -- with
+// `pr`, the two events are handed to the launch itself (hipExtLaunchKernel), so they carry the begin / end timestamps of
+// the KERNEL, what a rocprofv3 kernel trace reports (events recorded around a launch on the stream bracket the dispatch
+// gap as well: ~7 us per launch at C3, 92.4 against 85.6 us in round 2).  Inside a batch: recorded, never profiled.
+template <class K, class Run = decltype(&K::run)>
+struct KernelLaunch;
+template <class K, class... P>
+struct KernelLaunch<K, void (*)(P...)> {
+    static void go(misslap_solver *h, ProfRec *pr, dim3 grid, const P &...a) {
+        if (h->batch) batch_record<K, P...>(h, grid, a...);
+        else if (pr) hipExtLaunchKernelGGL((K::template entry<P...>), grid, dim3(K::kBlock), 0, h->stream, pr->start, pr->stop, 0, a...);
+        else hipLaunchKernelGGL((K::template entry<P...>), grid, dim3(K::kBlock), 0, h->stream, a...);
+    }
+};
+template <class K, class... A>
+void launch_timed(misslap_solver *h, ProfRec *pr, dim3 grid, const A &...a) {
+    KernelLaunch<K>::go(h, pr, grid, a...);
+}
+template <class K, class... A>
+void launch(misslap_solver *h, dim3 grid, const A &...a) {
+    KernelLaunch<K>::go(h, nullptr, grid, a...);
+}
+// ... and a launch that goes out by itself also inside a batch (the full-scan engine: dynamic LDS, one workgroup per
+// CU; the single-workgroup kernels of misslap_finish): any __global__ function
+template <class... P, class... A>
+void launch_alone(misslap_solver *h, ProfRec *pr, void (*kernel)(P...), dim3 grid, dim3 block, unsigned lds, const A &...a) {
+    if (h->batch) {
+        batch_record_plain(h, [kernel, grid, block, lds, args = std::tuple<P...>(a...)](hipStream_t st) {
+            std::apply([&](const P &...x) { hipLaunchKernelGGL(kernel, grid, block, lds, st, x...); }, args);
+        });
+    } else if (pr) {
+        hipExtLaunchKernelGGL(kernel, grid, block, lds, h->stream, pr->start, pr->stop, 0, static_cast<P>(a)...);
+    } else {
+        hipLaunchKernelGGL(kernel, grid, block, lds, h->stream, static_cast<P>(a)...);
+    }
+}
 
 // asynchronous fills / copies of the solve loop, in stream order
 inline hipError_t stream_memset(misslap_solver *h, void *p, int v, size_t n) {

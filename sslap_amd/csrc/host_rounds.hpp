@@ -138,7 +138,7 @@ bool live_poll(misslap_solver *h, unsigned want, bool exact, int *K, int *err, l
 // posts the status is enqueued behind it
 void ensure_posted(misslap_solver *h) {
     if (h->live_valid || h->live_off) return;
-    MISSLAP_LAUNCH(h, k_post_status, (F_k_post_status), 1, dim3(1), dim3(1), (const Ctl *)h->ctl, h->live_dev, ++h->ticket);
+    launch<k_post_status>(h, dim3(1), h->ctl, h->live_dev, ++h->ticket);
     h->live_valid = true;
 }
 int read_status(misslap_solver *h) {
@@ -248,10 +248,9 @@ int launch_bid_tiled(misslap_solver *h) {
         int *pos_of = h->nmatch, *order_person = h->hole_list, *order_pos = h->mover_list, *sums = h->cnt;
         const int nchunks = (h->n_rows + kScanChunk - 1) / kScanChunk;
         // (each returns at once when the scan itself will: a round enqueued on a stale upper bound of K)
-        MISSLAP_LAUNCH(h, k_order_prepare, (F_k_order_prepare), 1024, dim3(std::max(nchunks, blocks_for(h->K_ub, 1024))), dim3(1024),
-                       (const Ctl *)h->ctl, (const int *)h->U, pos_of, (const int *)h->p2o, h->n_rows, nchunks, sums, h->thr, h->tiled_min_K);
-        MISSLAP_LAUNCH(h, k_order_scatter, (F_k_order_scatter), 1024, dim3(nchunks), dim3(1024), (const Ctl *)h->ctl, (const int *)h->p2o,
-                       h->n_rows, (const int *)sums, (const int *)pos_of, order_person, order_pos, h->thr, h->tiled_min_K);
+        launch<k_order_prepare>(h, dim3(std::max(nchunks, blocks_for(h->K_ub, k_order_prepare::kBlock))), h->ctl, h->U, pos_of, h->p2o,
+                                h->n_rows, nchunks, sums, h->thr, h->tiled_min_K);
+        launch<k_order_scatter>(h, dim3(nchunks), h->ctl, h->p2o, h->n_rows, sums, pos_of, order_person, order_pos, h->thr, h->tiled_min_K);
         ta.order_person = order_person;
         ta.order_pos = order_pos;
     }
@@ -273,10 +272,7 @@ int launch_bid_tiled(misslap_solver *h) {
         const int key = h->tiled_fmt * 100 + shp[6];
         switch (key) {
 #define X(FMT, GL) \
-    case FMT * 100 + GL:                                                                                               \
-        if (h->batch) MISSLAP_LAUNCH_PLAIN(h, (MISSLAP_BID_KERNEL_REV(GL, FMT)), g, dim3(1024), lds, a, ta);                  \
-        else MISSLAP_LAUNCH_TIMED(pr, (MISSLAP_BID_KERNEL_REV(GL, FMT)), g, dim3(1024), (unsigned)lds, h->stream, a, ta);     \
-        break;
+    case FMT * 100 + GL: launch_alone(h, pr, MISSLAP_BID_KERNEL_REV(GL, FMT), g, dim3(1024), lds, a, ta); break;
             X(0, 4) X(0, 8) X(0, 16) X(1, 4) X(1, 8) X(1, 16)
 #undef X
             default: return fail(MISSLAP_ERR_STATE, "no backward instance for format %d with %d lanes per person", h->tiled_fmt, shp[6]);
@@ -284,10 +280,7 @@ int launch_bid_tiled(misslap_solver *h) {
     } else if (h->tiled_fmt == 0) {
         switch (h->tiled_shape) {
 #define X(I, TH, R, B, D, TC, LD, GL, CS) \
-    case I:                                                                                                            \
-        if (h->batch) MISSLAP_LAUNCH_PLAIN(h, (k_bid_tiled<TH, R, B, D, TC, LD, 0, GL, CS>), g, dim3(TH), lds, a, ta);        \
-        else MISSLAP_LAUNCH_TIMED(pr, (k_bid_tiled<TH, R, B, D, TC, LD, 0, GL, CS>), g, dim3(TH), (unsigned)lds, h->stream, a, ta); \
-        break;
+    case I: launch_alone(h, pr, k_bid_tiled<TH, R, B, D, TC, LD, 0, GL, CS>, g, dim3(TH), lds, a, ta); break;
             MISSLAP_FOR_TILED_SHAPES(X)
 #undef X
             default: return fail(MISSLAP_ERR_STATE, "bad tiled shape");
@@ -296,10 +289,7 @@ int launch_bid_tiled(misslap_solver *h) {
         const int key = h->tiled_fmt * 100 + shp[6];
         switch (key) {
 #define X(FMT, GL) \
-    case FMT * 100 + GL:                                                                                               \
-        if (h->batch) MISSLAP_LAUNCH_PLAIN(h, (MISSLAP_BID_KERNEL_FMT(GL, FMT)), g, dim3(1024), lds, a, ta);                  \
-        else MISSLAP_LAUNCH_TIMED(pr, (MISSLAP_BID_KERNEL_FMT(GL, FMT)), g, dim3(1024), (unsigned)lds, h->stream, a, ta);     \
-        break;
+    case FMT * 100 + GL: launch_alone(h, pr, MISSLAP_BID_KERNEL_FMT(GL, FMT), g, dim3(1024), lds, a, ta); break;
             MISSLAP_FOR_FMT_LANES(X)
 #undef X
             default: return fail(MISSLAP_ERR_STATE, "no full-scan instance for format %d with %d lanes per person", h->tiled_fmt, shp[6]);
@@ -353,7 +343,7 @@ int launch_bid(misslap_solver *h) {
     }
     const EdgesF32 e32{h->edges32};
     const EdgesF64 e64{h->col, h->val64};
-    const dim3 g(grid), b(fused ? 1024 : kBidBlock);
+    const dim3 g(grid);
     if (fused) {  // the launch closes the round: it carries the round's ticket (launch_apply has nothing left to do)
         a.live = (h->live_off || !h->live_every_round) ? nullptr : h->live_dev;
         a.ticket = ++h->ticket;
@@ -365,27 +355,20 @@ int launch_bid(misslap_solver *h) {
     // (wave_bid_filter); the mirror is rebuilt from the prices in front of the launch (12 bytes per object)
     if (h->price32 && !h->round_small && variant != 2 && (long long)h->K_ub * 8 >= h->n_rows) {
         HIP_TRY(stream_memset(h, h->pmax_bits, 0, sizeof(int)));
-        MISSLAP_LAUNCH(h, k_price_mirror, (F_k_price_mirror), 1024, dim3(std::min(blocks_for(h->n_cols, 1024 * 4), h->n_cus)), dim3(1024),
-                       (const Ctl *)h->ctl, (const double *)h->price, h->price32, h->n_cols, h->pmax_bits, h->thr, a.gather_max_K);
+        launch<k_price_mirror>(h, dim3(std::min(blocks_for(h->n_cols, k_price_mirror::kBlock * 4), h->n_cus)), h->ctl, h->price, h->price32,
+                               h->n_cols, h->pmax_bits, h->thr, a.gather_max_K);
         a.price32 = h->price32;
     }
-#define MISSLAP_LAUNCH_BID(E, ED)                                                                                   \
-    do {                                                                                                            \
-        if (h->batch) {  /* (no profiling inside a batch) */                                                        \
-            if (fused) MISSLAP_LAUNCH(h, (k_round_fused<E>), (F_k_round_fused<E>), 1024, g, b, a, ED);              \
-            else if (h->round_small) MISSLAP_LAUNCH(h, (k_bid<E, RecSource, 2>), (F_k_bid<E, RecSource, 2>), kBidBlock, g, b, a, ED); \
-            else if (variant == 0) MISSLAP_LAUNCH(h, (k_bid<E, PriceSource, 0>), (F_k_bid<E, PriceSource, 0>), kBidBlock, g, b, a, ED); \
-            else if (variant == 1) MISSLAP_LAUNCH(h, (k_bid<E, PriceSource, 1>), (F_k_bid<E, PriceSource, 1>), kBidBlock, g, b, a, ED); \
-            else MISSLAP_LAUNCH(h, (k_bid<E, PriceSource, 2>), (F_k_bid<E, PriceSource, 2>), kBidBlock, g, b, a, ED); \
-        } else if (fused) MISSLAP_LAUNCH_TIMED(pr, (k_round_fused<E>), g, b, 0, h->stream, a, ED);                  \
-        else if (h->round_small) MISSLAP_LAUNCH_TIMED(pr, (k_bid<E, RecSource, 2>), g, b, 0, h->stream, a, ED);     \
-        else if (variant == 0) MISSLAP_LAUNCH_TIMED(pr, (k_bid<E, PriceSource, 0>), g, b, 0, h->stream, a, ED);     \
-        else if (variant == 1) MISSLAP_LAUNCH_TIMED(pr, (k_bid<E, PriceSource, 1>), g, b, 0, h->stream, a, ED);     \
-        else MISSLAP_LAUNCH_TIMED(pr, (k_bid<E, PriceSource, 2>), g, b, 0, h->stream, a, ED);                       \
-    } while (0)
-    if (h->f32) MISSLAP_LAUNCH_BID(EdgesF32, e32);  // (rounds that k_round_small finishes: bids with the owners)
-    else MISSLAP_LAUNCH_BID(EdgesF64, e64);
-#undef MISSLAP_LAUNCH_BID
+    const auto bid = [&](auto ed) {  // (profiled outside a batch only)
+        using E = decltype(ed);
+        if (fused) launch_timed<k_round_fused<E>>(h, pr, g, a, ed);
+        else if (h->round_small) launch_timed<k_bid<E, RecSource, 2>>(h, pr, g, a, ed);  // (k_round_small finishes: bids with the owners)
+        else if (variant == 0) launch_timed<k_bid<E, PriceSource, 0>>(h, pr, g, a, ed);
+        else if (variant == 1) launch_timed<k_bid<E, PriceSource, 1>>(h, pr, g, a, ed);
+        else launch_timed<k_bid<E, PriceSource, 2>>(h, pr, g, a, ed);
+    };
+    if (h->f32) bid(e32);
+    else bid(e64);
     if (pr && !h->round_small) {
         h->take_edges_n = std::max(h->take_edges_n, grid);  // (a full-scan engine launch of the same round may be pending too)
         h->take_edges_out = h->launch_edges + 2 * (size_t)pr->launch_idx;
@@ -403,8 +386,8 @@ int launch_tiebreak(misslap_solver *h) {
     if (h->round_small) return MISSLAP_OK;  // k_round_small (launch_apply) resolves the ties itself
     RoundArgs a = round_args(h);
     const long long share = h->K_ub;
-    MISSLAP_LAUNCH(h, k_tiebreak, (F_k_tiebreak), 256, dim3(blocks_for(share, 256)), dim3(256), a,
-                   (const int *)(h->round_ordered ? h->mover_list : nullptr), h->tiled_min_K, h->take_edges_n, h->take_edges_out);
+    launch<k_tiebreak>(h, dim3(blocks_for(share, k_tiebreak::kBlock)), a, h->round_ordered ? h->mover_list : nullptr, h->tiled_min_K,
+                       h->take_edges_n, h->take_edges_out);
     h->take_edges_n = 0;
     h->take_edges_out = nullptr;
     HIP_TRY(hipGetLastError());
@@ -427,7 +410,7 @@ int launch_apply(misslap_solver *h) {
     if (h->round_small) {
         h->round_small = false;
         h->K_exact = false;
-        MISSLAP_LAUNCH(h, k_round_small, (F_k_round_small), 1024, dim3(1), dim3(1024), a);
+        launch<k_round_small>(h, dim3(1), a);
         HIP_TRY(hipGetLastError());
         return MISSLAP_OK;
     }
@@ -435,16 +418,16 @@ int launch_apply(misslap_solver *h) {
     h->round_ordered = false;
     // by the bidders where they are few against the objects (every rank holds every bid only in unsharded rounds)
     if ((h->world == 1 || h->K_ub < h->shard_min_K) && (long long)h->K_ub * h->apply_bidders_ratio <= h->n_cols)
-        MISSLAP_LAUNCH(h, k_apply_bidders, (F_k_apply_bidders), 256, dim3(blocks_for(h->K_ub, 256)), dim3(256), a);
+        launch<k_apply_bidders>(h, dim3(blocks_for(h->K_ub, k_apply_bidders::kBlock)), a);
     else
-        MISSLAP_LAUNCH(h, k_apply, (F_k_apply), 256, dim3(blocks_for(h->n_cols, 256)), dim3(256), a);
+        launch<k_apply>(h, dim3(blocks_for(h->n_cols, k_apply::kBlock)), a);
     if (h->K_ub <= kCompactSmallMax) {
-        MISSLAP_LAUNCH(h, k_compact_small, (F_k_compact_small), 1024, dim3(1), dim3(1024), a);
+        launch<k_compact_small>(h, dim3(1), a);
     } else {
         const int cb = blocks_for(h->K_ub, kChunk);
-        MISSLAP_LAUNCH(h, k_compact_count, (F_k_compact_count), 256, dim3(cb), dim3(256), a);
-        MISSLAP_LAUNCH(h, k_compact_scatter, (F_k_compact_scatter), 256, dim3(cb), dim3(256), a);
-        MISSLAP_LAUNCH(h, k_compact_fill, (F_k_compact_fill), 256, dim3(blocks_for(h->K_ub, 256)), dim3(256), a);
+        launch<k_compact_count>(h, dim3(cb), a);
+        launch<k_compact_scatter>(h, dim3(cb), a);
+        launch<k_compact_fill>(h, dim3(blocks_for(h->K_ub, k_compact_fill::kBlock)), a);
     }
     HIP_TRY(hipGetLastError());
     return MISSLAP_OK;
@@ -500,39 +483,27 @@ int launch_tail(misslap_solver *h) {
     // at once, and the problems of a group then issue the same sequence of kernels, i.e. share every launch)
     const bool in_batch = h->batch != nullptr;
     if (in_batch) h->batch->hold_next = true;  // ... and the sequence waits for the other problems of the group (host_batch.hpp)
-#define MISSLAP_LAUNCH_TAIL(E, ED)                                                                                       \
-    do {                                                                                                                 \
-        if (lines && h->line_maintenance)                                                                                \
-            MISSLAP_LAUNCH(h, k_refresh_lines<E>, (F_k_refresh_lines<E>), kBidBlock,                                     \
-                           dim3(blocks_for((h->n_rows + 1) / 2, kBidBlock / kWave)), dim3(kBidBlock), round_args(h), ED, \
-                           (int)kCandMaintenanceMin, long_max, min_alive_long);                                          \
-        if (lines && h->line_maintenance && h->long_rows) {                                                              \
-            if (h->max_row_len <= 256 * kLongPer)                                                                        \
-                MISSLAP_LAUNCH(h, (k_refresh_long<E, 256>), (F_k_refresh_long<E, 256>), 256, dim3(blocks_for(h->n_rows, 1)), \
-                               dim3(256), round_args(h), ED);                                                            \
-            else                                                                                                         \
-                MISSLAP_LAUNCH(h, (k_refresh_long<E, 512>), (F_k_refresh_long<E, 512>), 512, dim3(blocks_for(h->n_rows, 1)), \
-                               dim3(512), round_args(h), ED);                                                            \
-        }                                                                                                                \
-        if (h->K_ub > kTeamMax || in_batch)                                                                              \
-            MISSLAP_LAUNCH(h, (k_tail<E, 2 * kTailMax>), (F_k_tail<E, 2 * kTailMax, false>), 2 * kTailMax, dim3(1),      \
-                           dim3(2 * kTailMax), a, ED);                                                                   \
-        if ((h->K_ub > 2 || in_batch) && lines)                                                                          \
-            MISSLAP_LAUNCH(h, (k_tail<E, 2 * kTailMax, true>), (F_k_tail<E, 2 * kTailMax, true>), 2 * kTailMax, dim3(1), \
-                           dim3(2 * kTailMax), a, ED);                                                                   \
-        if (lines) MISSLAP_LAUNCH(h, (k_tail<E, kWave>), (F_k_tail<E, kWave, false>), kWave, dim3(1), dim3(kWave), a, ED); \
-        else MISSLAP_LAUNCH(h, (k_tail<E, kTailMax>), (F_k_tail<E, kTailMax, false>), kTailMax, dim3(1), dim3(kTailMax), a, ED); \
-    } while (0)
-    if (h->f32) MISSLAP_LAUNCH_TAIL(EdgesF32, e32);
-    else MISSLAP_LAUNCH_TAIL(EdgesF64, e64);
-#undef MISSLAP_LAUNCH_TAIL
+    const auto tail = [&](auto ed) {
+        using E = decltype(ed);
+        if (lines && h->line_maintenance)
+            launch<k_refresh_lines<E>>(h, dim3(blocks_for((h->n_rows + 1) / 2, kBidBlock / kWave)), round_args(h), ed,
+                                       kCandMaintenanceMin, long_max, min_alive_long);
+        if (lines && h->line_maintenance && h->long_rows) {
+            if (h->max_row_len <= 256 * kLongPer) launch<k_refresh_long<E, 256>>(h, dim3(blocks_for(h->n_rows, 1)), round_args(h), ed);
+            else launch<k_refresh_long<E, 512>>(h, dim3(blocks_for(h->n_rows, 1)), round_args(h), ed);
+        }
+        if (h->K_ub > kTeamMax || in_batch) launch<k_tail<E, 2 * kTailMax>>(h, dim3(1), a, ed);
+        if ((h->K_ub > 2 || in_batch) && lines) launch<k_tail<E, 2 * kTailMax, true>>(h, dim3(1), a, ed);
+        if (lines) launch<k_tail<E, kWave>>(h, dim3(1), a, ed);
+        else launch<k_tail<E, kTailMax>>(h, dim3(1), a, ed);
+    };
+    if (h->f32) tail(e32);
+    else tail(e64);
     if (pr) HIP_TRY(hipEventRecord(pr->stop, h->stream));
     // the tail keeps only the price records current: rebuild price / o2p / p2o from them
     h->live_valid = !h->live_off && h->live_dev != nullptr;
-    MISSLAP_LAUNCH(h, k_sync_from_rec, (F_k_sync_from_rec), 256, dim3(blocks_for(h->n_cols, 256)), dim3(256), h->ctl,
-                   (const PriceRec *)h->rec, h->price, h->o2p, h->p2o, (const int *)h->U, h->n_cols,
-                   (h->cand != nullptr && !h->lines_dropped) ? 1 : 0, h->live_valid ? h->live_dev : (unsigned long long *)nullptr,
-                   ++h->ticket);
+    launch<k_sync_from_rec>(h, dim3(blocks_for(h->n_cols, k_sync_from_rec::kBlock)), h->ctl, h->rec, h->price, h->o2p, h->p2o, h->U, h->n_cols,
+                            (h->cand != nullptr && !h->lines_dropped) ? 1 : 0, h->live_valid ? h->live_dev : nullptr, ++h->ticket);
     HIP_TRY(hipGetLastError());
     h->phase_fresh = false;
     if (h->tail_nits0 < 0) h->tail_nits0 = h->h_ctl->nits;  // (the status read in front of this launch)
@@ -560,15 +531,8 @@ size_t final_pass_grid_max(size_t n_rows, int n_cus) {
 int launch_rows_gather(misslap_solver *h, float eps, const FinalOut &fo, int n_rows, int *n_blocks = nullptr) {
     const int grid = blocks_for(n_rows, 4);
     if (n_blocks) *n_blocks = grid;
-    if (h->f32) {
-        EdgesF32 ed{h->edges32};
-        MISSLAP_LAUNCH(h, k_ece<EdgesF32>, (F_k_ece<EdgesF32>), 256, dim3(grid), dim3(256), h->ctl, ed, (const int *)h->row_ptr,
-                       (const double *)h->price, (const int *)h->p2o, n_rows, eps, fo);
-    } else {
-        EdgesF64 ed{h->col, h->val64};
-        MISSLAP_LAUNCH(h, k_ece<EdgesF64>, (F_k_ece<EdgesF64>), 256, dim3(grid), dim3(256), h->ctl, ed, (const int *)h->row_ptr,
-                       (const double *)h->price, (const int *)h->p2o, n_rows, eps, fo);
-    }
+    if (h->f32) launch<k_ece<EdgesF32>>(h, dim3(grid), h->ctl, EdgesF32{h->edges32}, h->row_ptr, h->price, h->p2o, n_rows, eps, fo);
+    else launch<k_ece<EdgesF64>>(h, dim3(grid), h->ctl, EdgesF64{h->col, h->val64}, h->row_ptr, h->price, h->p2o, n_rows, eps, fo);
     HIP_TRY(hipGetLastError());
     return MISSLAP_OK;
 }
@@ -591,14 +555,14 @@ int launch_rows_all(misslap_solver *h, float eps, const FinalOut &fo, int *n_blo
     if (h->tiled_fmt == 0) {
         switch (gl) {
 #define X(GL) \
-    case GL: MISSLAP_LAUNCH_PLAIN(h, (MISSLAP_CHECK_KERNEL(GL)), dim3((unsigned)grid), dim3(1024), lds, a, ta); break;
+    case GL: launch_alone(h, nullptr, MISSLAP_CHECK_KERNEL(GL), dim3((unsigned)grid), dim3(1024), lds, a, ta); break;
             MISSLAP_FOR_CHECK_LANES(X)
 #undef X
         }
     } else {
         switch (h->tiled_fmt * 100 + gl) {
 #define X(FMT, GL) \
-    case FMT * 100 + GL: MISSLAP_LAUNCH_PLAIN(h, (MISSLAP_CHECK_KERNEL_FMT(GL, FMT)), dim3((unsigned)grid), dim3(1024), lds, a, ta); break;
+    case FMT * 100 + GL: launch_alone(h, nullptr, MISSLAP_CHECK_KERNEL_FMT(GL, FMT), dim3((unsigned)grid), dim3(1024), lds, a, ta); break;
             MISSLAP_FOR_FMT_LANES(X)
 #undef X
         }
@@ -626,7 +590,7 @@ int run_ece(misslap_solver *h, float eps, int *ok) {
     if ((rc = launch_rows_gather(h, eps, fo, sample))) return rc;
     if (sample < h->n_rows && (rc = launch_rows_all(h, eps, fo))) return rc;
     if (!h->live_off) {  // the verdict through the live words: no copy of the control block, no stream drain
-        MISSLAP_LAUNCH(h, k_post_ece, (F_k_post_ece), 1, dim3(1), dim3(1), (const Ctl *)h->ctl, h->live_dev, ++h->ticket);
+        launch<k_post_ece>(h, dim3(1), h->ctl, h->live_dev, ++h->ticket);
         h->live_valid = true;
         int K = 0, err = 0;
         long long nits = 0;

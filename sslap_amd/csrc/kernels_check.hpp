@@ -142,56 +142,51 @@ __device__ __forceinline__ void flush_final_wg(const FinalOut &fo, FinalAcc acc,
 // Branch-free: every load is unconditional (clamped index), a masked-off element has value -inf and matches nothing.
 // fo.fin = 0 (eCE only): every wavefront stops as soon as any row has failed.
 template <class E>
-__device__ __forceinline__ void k_ece_body(Ctl *ctl, E ed, const int *row_ptr, const double *price,
-                                             const int *p2o, int n_rows, float eps_f, FinalOut fo) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const double eps = (double)eps_f;
-    const double ninf = -__builtin_huge_val();
-    FinalAcc acc;
-    for (int i = blockIdx.x * 4 + wave; i < n_rows; i += gridDim.x * 4) {
-        if (!fo.fin && __atomic_load_n(&ctl->ece_fail, __ATOMIC_RELAXED)) break;  // wave-uniform
-        const int s = row_ptr[i], e = row_ptr[i + 1];
-        const int j = p2o[i];
-        const int want = wanted_column(j, fo.n_cols);
-        const double pj = price[max(want, 0)];
-        double vmax = ninf, asel = 0.0;
-        int gsel = -1, cnt = 0;
-        for (int base = s; base < e; base += 4 * kWave) {  // four 64-edge chunks in flight, like wave_bid
-            int c[4];
-            double a[4], pr[4];
+struct k_ece {
+    MISSLAP_KERNEL(256)
+    static __device__ __forceinline__ void run(Ctl *ctl, E ed, const int *row_ptr, const double *price, const int *p2o, int n_rows, float eps_f, FinalOut fo) {
+        const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+        const double eps = (double)eps_f;
+        const double ninf = -__builtin_huge_val();
+        FinalAcc acc;
+        for (int i = blockIdx.x * 4 + wave; i < n_rows; i += gridDim.x * 4) {
+            if (!fo.fin && __atomic_load_n(&ctl->ece_fail, __ATOMIC_RELAXED)) break;  // wave-uniform
+            const int s = row_ptr[i], e = row_ptr[i + 1];
+            const int j = p2o[i];
+            const int want = wanted_column(j, fo.n_cols);
+            const double pj = price[max(want, 0)];
+            double vmax = ninf, asel = 0.0;
+            int gsel = -1, cnt = 0;
+            for (int base = s; base < e; base += 4 * kWave) {  // four 64-edge chunks in flight, like wave_bid
+                int c[4];
+                double a[4], pr[4];
 #pragma unroll
-            for (int u = 0; u < 4; ++u) ed.load(min(base + u * kWave + lane, e - 1), c[u], a[u]);
+                for (int u = 0; u < 4; ++u) ed.load(min(base + u * kWave + lane, e - 1), c[u], a[u]);
 #pragma unroll
-            for (int u = 0; u < 4; ++u) pr[u] = price[c[u]];
+                for (int u = 0; u < 4; ++u) pr[u] = price[c[u]];
 #pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int g = base + u * kWave + lane;
-                const bool ok = g < e;
-                const double v = ok ? a[u] - pr[u] : ninf;
-                vmax = __builtin_fmax(vmax, v);
-                const bool m = ok & (c[u] == want);  // ascending g per lane: keeps the last match
-                gsel = m ? g : gsel;
-                asel = m ? a[u] : asel;
-                cnt += m;
+                for (int u = 0; u < 4; ++u) {
+                    const int g = base + u * kWave + lane;
+                    const bool ok = g < e;
+                    const double v = ok ? a[u] - pr[u] : ninf;
+                    vmax = __builtin_fmax(vmax, v);
+                    const bool m = ok & (c[u] == want);  // ascending g per lane: keeps the last match
+                    gsel = m ? g : gsel;
+                    asel = m ? a[u] : asel;
+                    cnt += m;
+                }
             }
+            vmax = wave_max_f64(vmax);
+            const int gmax = wave_max_i32(gsel);
+            for (int off = 32; off >= 1; off >>= 1) cnt += __shfl_xor(cnt, off);
+            const int sl = __ffsll((long long)__ballot(gsel == gmax)) - 1;  // (gmax = -1: any lane, the value is unused)
+            const double cost = readlane_f64(asel, sl);
+            if (lane == 0) final_person(acc, fo, i, j, gmax >= 0, cnt, cost, vmax, pj, eps);
         }
-        vmax = wave_max_f64(vmax);
-        const int gmax = wave_max_i32(gsel);
-        for (int off = 32; off >= 1; off >>= 1) cnt += __shfl_xor(cnt, off);
-        const int sl = __ffsll((long long)__ballot(gsel == gmax)) - 1;  // (gmax = -1: any lane, the value is unused)
-        const double cost = readlane_f64(asel, sl);
-        if (lane == 0) final_person(acc, fo, i, j, gmax >= 0, cnt, cost, vmax, pj, eps);
+        flag_ece_failure(ctl, acc.bad);
+        __shared__ double s_fin[8 * 4];
+        if (fo.fin) flush_final_wg(fo, acc, s_fin);  // (uniform over the launch)
     }
-    flag_ece_failure(ctl, acc.bad);
-    __shared__ double s_fin[8 * 4];
-    if (fo.fin) flush_final_wg(fo, acc, s_fin);  // (uniform over the launch)
-}
-template <class E>
-__global__ __launch_bounds__(256) void k_ece(Ctl *ctl, E ed, const int *row_ptr, const double *price,
-                                             const int *p2o, int n_rows, float eps_f, FinalOut fo) { k_ece_body<E>(ctl, ed, row_ptr, price, p2o, n_rows, eps_f, fo); }
-template <class E>
-struct F_k_ece {  // (the body as a callable: what a batched launch runs per problem, csrc/host_batch.hpp)
-    static __device__ __forceinline__ void run(Ctl *ctl, E ed, const int *row_ptr, const double *price, const int *p2o, int n_rows, float eps_f, FinalOut fo) { k_ece_body<E>(ctl, ed, row_ptr, price, p2o, n_rows, eps_f, fo); }
 };
 
 

@@ -237,55 +237,49 @@ __device__ __forceinline__ void tally_flush(const RoundArgs &a, const BidTally &
 }
 
 template <class E, class Src, int kLines>
-__device__ __forceinline__ void k_bid_body(RoundArgs a, E ed) {
-    static_assert(kLines == 2 || !SrcOf<Src>::kOwners, "the lean scan does not carry the owners k_round_small needs");
-    const int wave = threadIdx.x >> 6;
-    const int wpb = kBidBlock / kWave;
-    const int first = blockIdx.x * wpb + wave;
-    const Ctl *ctl = a.ctl;
-    const CtlHead head(ctl);
-    const int i_first = a.U[min(first, a.n_rows - 1)];
-    if (!head.live(a.thr, i_first < -1)) return;  // (list entries are persons or -1)
-    if (a.gather_max_K > 0 && head.K >= a.gather_max_K) return;
-    int lo, hi;
-    shard_range(head.K, a.rank, a.world, a.shard_min_K, lo, hi);
-    BidTally tl;
-    bid_positions<E, Src, kLines, false>(a, ed, lo, hi, first, gridDim.x * wpb, i_first, tl);
-    tally_flush<kBidBlock / kWave>(a, tl, head.K);
-}
-template <class E, class Src, int kLines>
-__global__ __launch_bounds__(kBidBlock) void k_bid(RoundArgs a, E ed) { k_bid_body<E, Src, kLines>(a, ed); }
-template <class E, class Src, int kLines>
-struct F_k_bid {  // (the body as a callable: what a batched launch runs per problem, csrc/host_batch.hpp)
-    static __device__ __forceinline__ void run(RoundArgs a, E ed) { k_bid_body<E, Src, kLines>(a, ed); }
+struct k_bid {
+    MISSLAP_KERNEL(kBidBlock)
+    static __device__ __forceinline__ void run(RoundArgs a, E ed) {
+        static_assert(kLines == 2 || !SrcOf<Src>::kOwners, "the lean scan does not carry the owners k_round_small needs");
+        const int wave = threadIdx.x >> 6;
+        const int wpb = kBidBlock / kWave;
+        const int first = blockIdx.x * wpb + wave;
+        const Ctl *ctl = a.ctl;
+        const CtlHead head(ctl);
+        const int i_first = a.U[min(first, a.n_rows - 1)];
+        if (!head.live(a.thr, i_first < -1)) return;  // (list entries are persons or -1)
+        if (a.gather_max_K > 0 && head.K >= a.gather_max_K) return;
+        int lo, hi;
+        shard_range(head.K, a.rank, a.world, a.shard_min_K, lo, hi);
+        BidTally tl;
+        bid_positions<E, Src, kLines, false>(a, ed, lo, hi, first, gridDim.x * wpb, i_first, tl);
+        tally_flush<kBidBlock / kWave>(a, tl, head.K);
+    }
 };
 
 
 // The fp32 mirror of the prices for wave_bid_filter, and the largest price (bit pattern: prices are >= 0, so the patterns
 // order like integers; *pmax_bits is zeroed by the host in front of the launch).  Only in a live round that k_bid serves.
-__device__ __forceinline__ void k_price_mirror_body(const Ctl *ctl, const double *price, float *price32, int n_cols,
-                                                       int *pmax_bits, int thr, int gather_max_K) {
-    if (!round_live(ctl, thr) || (gather_max_K > 0 && ctl->K >= gather_max_K)) return;
-    __shared__ int s_w[16];
-    float m = 0.f;
-    for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < n_cols; j += gridDim.x * blockDim.x) {
-        const float p = (float)price[j];  // round to nearest
-        price32[j] = p;
-        m = __builtin_fmaxf(m, __builtin_fabsf(p));
+struct k_price_mirror {
+    MISSLAP_KERNEL(1024)
+    static __device__ __forceinline__ void run(const Ctl *ctl, const double *price, float *price32, int n_cols, int *pmax_bits, int thr, int gather_max_K) {
+        if (!round_live(ctl, thr) || (gather_max_K > 0 && ctl->K >= gather_max_K)) return;
+        __shared__ int s_w[16];
+        float m = 0.f;
+        for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < n_cols; j += gridDim.x * blockDim.x) {
+            const float p = (float)price[j];  // round to nearest
+            price32[j] = p;
+            m = __builtin_fmaxf(m, __builtin_fabsf(p));
+        }
+        int b = __float_as_int(m);
+        for (int off = 32; off >= 1; off >>= 1) b = max(b, __shfl_xor(b, off));
+        if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = b;
+        __syncthreads();
+        if (threadIdx.x == 0) {  // ONE atomic per workgroup: same-address atomics retire one after the other, ~5.5 ns each
+            for (int w = 1; w < (int)blockDim.x / kWave; ++w) b = max(b, s_w[w]);
+            if (b > 0) atomicMax(pmax_bits, b);
+        }
     }
-    int b = __float_as_int(m);
-    for (int off = 32; off >= 1; off >>= 1) b = max(b, __shfl_xor(b, off));
-    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = b;
-    __syncthreads();
-    if (threadIdx.x == 0) {  // ONE atomic per workgroup: same-address atomics retire one after the other, ~5.5 ns each
-        for (int w = 1; w < (int)blockDim.x / kWave; ++w) b = max(b, s_w[w]);
-        if (b > 0) atomicMax(pmax_bits, b);
-    }
-}
-__global__ __launch_bounds__(1024) void k_price_mirror(const Ctl *ctl, const double *price, float *price32, int n_cols,
-                                                       int *pmax_bits, int thr, int gather_max_K) { k_price_mirror_body(ctl, price, price32, n_cols, pmax_bits, thr, gather_max_K); }
-struct F_k_price_mirror {  // (the body as a callable: what a batched launch runs per problem, csrc/host_batch.hpp)
-    static __device__ __forceinline__ void run(const Ctl *ctl, const double *price, float *price32, int n_cols, int *pmax_bits, int thr, int gather_max_K) { k_price_mirror_body(ctl, price, price32, n_cols, pmax_bits, thr, gather_max_K); }
 };
 
 
@@ -299,49 +293,46 @@ struct F_k_price_mirror {  // (the body as a callable: what a batched launch run
 // long_max > 0: the long-row builder runs behind this pass and takes rows of up to so many edges; their lines are
 // rebuilt below min_alive_long live candidates.
 template <class E>
-__device__ __forceinline__ void k_refresh_lines_body(RoundArgs a, E ed, int min_alive, int long_max, int min_alive_long) {
-    if (!E::kCand || a.cand == nullptr) return;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int wpb = kBidBlock / kWave;
-    const double eps = (double)a.eps;
-    const PriceSource src{a.price};
-    double hint = 0.0;
-    int err = 0;
-    for (int w = blockIdx.x * wpb + wave; 2 * w < a.n_rows; w += gridDim.x * wpb) {
-        const int i0 = 2 * w, i1 = 2 * w + 1;
-        const bool act1 = i1 < a.n_rows;
-        const int ime = (lane < kCandLanes || !act1) ? i0 : i1;
-        typename E::Slot sl = LineIO<typename E::Slot>::load(a.cand, a.cand64,
-                                                             (size_t)ime * kCandLanes + (lane & (kCandLanes - 1)));
-        CandBid b[2];
-        int alive[2];
-        cand_eval2(sl, true, act1, src, eps, b, err, NoEarly(), NoStamp(), alive);
+struct k_refresh_lines {
+    MISSLAP_KERNEL(kBidBlock)
+    static __device__ __forceinline__ void run(RoundArgs a, E ed, int min_alive, int long_max, int min_alive_long) {
+        if (!E::kCand || a.cand == nullptr) return;
+        const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+        const int wpb = kBidBlock / kWave;
+        const double eps = (double)a.eps;
+        const PriceSource src{a.price};
+        double hint = 0.0;
+        int err = 0;
+        for (int w = blockIdx.x * wpb + wave; 2 * w < a.n_rows; w += gridDim.x * wpb) {
+            const int i0 = 2 * w, i1 = 2 * w + 1;
+            const bool act1 = i1 < a.n_rows;
+            const int ime = (lane < kCandLanes || !act1) ? i0 : i1;
+            typename E::Slot sl = LineIO<typename E::Slot>::load(a.cand, a.cand64,
+                                                                 (size_t)ime * kCandLanes + (lane & (kCandLanes - 1)));
+            CandBid b[2];
+            int alive[2];
+            cand_eval2(sl, true, act1, src, eps, b, err, NoEarly(), NoStamp(), alive);
 #pragma unroll
-        for (int X = 0; X < 2; ++X) {
-            if (X == 1 && !act1) continue;  // wave-uniform
-            if (b[X].hit && alive[X] >= max(min_alive, min_alive_long)) continue;
-            const int i = X ? i1 : i0;
-            const int s = a.row_ptr[i], e = a.row_ptr[i + 1];
-            if (e - s > kCandRowMax) {  // (wave-uniform) too long for a rebuild here: k_refresh_long's, if it can hold the row
-                if (long_max > 0 && e - s <= long_max && !(b[X].hit && alive[X] >= min_alive_long) && lane == 0)
-                    a.need_list[atomicAdd(&a.ctl->n_need, 1)] = i;
-                continue;
+            for (int X = 0; X < 2; ++X) {
+                if (X == 1 && !act1) continue;  // wave-uniform
+                if (b[X].hit && alive[X] >= max(min_alive, min_alive_long)) continue;
+                const int i = X ? i1 : i0;
+                const int s = a.row_ptr[i], e = a.row_ptr[i + 1];
+                if (e - s > kCandRowMax) {  // (wave-uniform) too long for a rebuild here: k_refresh_long's, if it can hold the row
+                    if (long_max > 0 && e - s <= long_max && !(b[X].hit && alive[X] >= min_alive_long) && lane == 0)
+                        a.need_list[atomicAdd(&a.ctl->n_need, 1)] = i;
+                    continue;
+                }
+                if (b[X].hit && alive[X] >= min_alive) continue;
+                CandBid full;
+                CandBuildArgs ba;
+                const typename E::Raw none[4] = {};
+                wave_bid_full<E, PriceSource, false, false>(ed, src, s, e, none, eps, full, ba, err);
+                if (ba.want) cand_build(a.cand, a.cand64, i, ba, eps, hint);
             }
-            if (b[X].hit && alive[X] >= min_alive) continue;
-            CandBid full;
-            CandBuildArgs ba;
-            const typename E::Raw none[4] = {};
-            wave_bid_full<E, PriceSource, false, false>(ed, src, s, e, none, eps, full, ba, err);
-            if (ba.want) cand_build(a.cand, a.cand64, i, ba, eps, hint);
         }
+        if (lane == 0 && err) atomicOr(&a.ctl->err, err);
     }
-    if (lane == 0 && err) atomicOr(&a.ctl->err, err);
-}
-template <class E>
-__global__ __launch_bounds__(kBidBlock) void k_refresh_lines(RoundArgs a, E ed, int min_alive, int long_max, int min_alive_long) { k_refresh_lines_body<E>(a, ed, min_alive, long_max, min_alive_long); }
-template <class E>
-struct F_k_refresh_lines {  // (the body as a callable: what a batched launch runs per problem, csrc/host_batch.hpp)
-    static __device__ __forceinline__ void run(RoundArgs a, E ed, int min_alive, int long_max, int min_alive_long) { k_refresh_lines_body<E>(a, ed, min_alive, long_max, min_alive_long); }
 };
 
 
@@ -356,143 +347,140 @@ constexpr int kLongPer = 32;                   // values per thread
 constexpr int kCandLongMax = 512 * kLongPer;  // 16384: the longest row that keeps a line (512-thread instance; 1024
                                               // threads leave 128 registers per thread, which spills the row's values)
 template <class E, int kLongThreads>          // 256 threads: rows <= 8192 edges; 512 threads: rows <= 16384
-__device__ __forceinline__ void k_refresh_long_body(RoundArgs a, E ed) {
-    if (!E::kCand || a.cand == nullptr) return;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    __shared__ int s_cnt[2], s_n, s_g[kCandMax + 2], s_col[kCandMax + 2];
-    __shared__ double s_cost[kCandMax + 2], s_red[2][kLongThreads / kWave];
-    const double ninf = -__builtin_huge_val();
-    const PriceSource src{a.price};
-    // (the persons come from k_refresh_lines, which has evaluated every line at today's prices two per wavefront: a
-    // workgroup per person re-doing that evaluation for ALL persons was 179 us per pass at dense 8000 x 8000, where a
-    // pass finds a few hundred spent lines)
-    const int n_need = a.ctl->n_need;
-    for (int idx = blockIdx.x; idx < n_need; idx += gridDim.x) {
-        const int i = a.need_list[idx];
-        const int s = a.row_ptr[i], e = a.row_ptr[i + 1], len = e - s;
-        if (len <= kCandRowMax || len > kLongThreads * kLongPer) continue;  // uniform over the workgroup (never: the list's rule)
-        if (t == 0) s_n = 0;
-        __syncthreads();
-        // the row's values, in registers
-        double v[kLongPer];
-        double m1 = ninf, m2 = ninf;  // my best two (multiplicity counted)
-#pragma unroll
-        for (int k = 0; k < kLongPer; ++k) {
-            const int g = s + k * kLongThreads + t;
-            int c;
-            double cost;
-            ed.load(min(g, e - 1), c, cost);
-            const double x = g < e ? cost - src.get(c).price : ninf;
-            v[k] = x;
-            m2 = __builtin_fmax(m2, __builtin_fmin(x, m1));
-            m1 = __builtin_fmax(m1, x);
-        }
-        // W = the row's second-best value (multiplicity counted), lo = its smallest: wave-wide, then across wavefronts
-        double lo = __builtin_huge_val();
-#pragma unroll
-        for (int k = 0; k < kLongPer; ++k) lo = v[k] == ninf ? lo : __builtin_fmin(lo, v[k]);
-        {
-            Top2 x;
-            x.v = m1;
-            x.w = m2;
-            x.g = t;
-            const Top2 r = top2_wave_reduce(x);
-            const double wl = -wave_max_f64(-lo);
-            if (lane == 0) {
-                s_red[0][wave] = r.v;
-                s_red[1][wave] = r.w;
-                s_cost[wave] = wl;  // (scratch)
-            }
-        }
-        __syncthreads();
-        double V = ninf, W = ninf, LO = __builtin_huge_val();
-        for (int w2 = 0; w2 < kLongThreads / kWave; ++w2) {
-            const double bv = s_red[0][w2], bw = s_red[1][w2];
-            W = __builtin_fmax(W, __builtin_fmax(__builtin_fmin(bv, V), bw));
-            V = __builtin_fmax(V, bv);
-            LO = __builtin_fmin(LO, s_cost[w2]);
-        }
-        __syncthreads();
-        auto count_ge = [&](double thr, int par) {  // rows' values >= thr, uniform over the workgroup
-            int n = 0;
-#pragma unroll
-            for (int k = 0; k < kLongPer; ++k) n += v[k] >= thr;
-            for (int off = 32; off >= 1; off >>= 1) n += __shfl_xor(n, off);
-            if (t == 0) s_cnt[par] = 0;
+struct k_refresh_long {
+    MISSLAP_KERNEL(kLongThreads)
+    static __device__ __forceinline__ void run(RoundArgs a, E ed) {
+        if (!E::kCand || a.cand == nullptr) return;
+        const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+        __shared__ int s_cnt[2], s_n, s_g[kCandMax + 2], s_col[kCandMax + 2];
+        __shared__ double s_cost[kCandMax + 2], s_red[2][kLongThreads / kWave];
+        const double ninf = -__builtin_huge_val();
+        const PriceSource src{a.price};
+        // (the persons come from k_refresh_lines, which has evaluated every line at today's prices two per wavefront: a
+        // workgroup per person re-doing that evaluation for ALL persons was 179 us per pass at dense 8000 x 8000, where a
+        // pass finds a few hundred spent lines)
+        const int n_need = a.ctl->n_need;
+        for (int idx = blockIdx.x; idx < n_need; idx += gridDim.x) {
+            const int i = a.need_list[idx];
+            const int s = a.row_ptr[i], e = a.row_ptr[i + 1], len = e - s;
+            if (len <= kCandRowMax || len > kLongThreads * kLongPer) continue;  // uniform over the workgroup (never: the list's rule)
+            if (t == 0) s_n = 0;
             __syncthreads();
-            if (lane == 0) atomicAdd(&s_cnt[par], n);
-            __syncthreads();
-            return s_cnt[par];
-        };
-        // threshold: count(v >= W) >= 2; more than kCandMax ties at the top: no line
-        double tsel = W;
-        int par = 0;
-        int nsel = count_ge(W, par);
-        par ^= 1;
-        bool ok = nsel <= kCandMax && W > ninf;
-        if (ok && nsel < kCandMin && LO < W) {
-            double hi_t = W, lo_t = LO;  // count(hi_t) = nsel < kCandMin; count(lo_t) = len > kCandMax
-            for (int it = 0; it < 48; ++it) {
-                const double mid = 0.5 * (hi_t + lo_t);
-                if (!(mid < hi_t) || !(mid > lo_t)) break;
-                const int n = count_ge(mid, par);
-                par ^= 1;
-                if (n > kCandMax) lo_t = mid;
-                else {
-                    hi_t = mid;
-                    tsel = mid;
-                    nsel = n;
-                    if (n >= kCandMin) break;
-                }
-            }
-        }
-        // collect the qualifying edges (at most kCandMax) and order them by stored index
-        if (ok) {
+            // the row's values, in registers
+            double v[kLongPer];
+            double m1 = ninf, m2 = ninf;  // my best two (multiplicity counted)
 #pragma unroll
             for (int k = 0; k < kLongPer; ++k) {
-                if (v[k] >= tsel) {
-                    const int g = s + k * kLongThreads + t;
-                    int c;
-                    double cost;
-                    ed.load(g, c, cost);
-                    const int at = atomicAdd(&s_n, 1);
-                    if (at < kCandMax) {
-                        s_g[at] = g;
-                        s_col[at] = c;
-                        s_cost[at] = cost;
+                const int g = s + k * kLongThreads + t;
+                int c;
+                double cost;
+                ed.load(min(g, e - 1), c, cost);
+                const double x = g < e ? cost - src.get(c).price : ninf;
+                v[k] = x;
+                m2 = __builtin_fmax(m2, __builtin_fmin(x, m1));
+                m1 = __builtin_fmax(m1, x);
+            }
+            // W = the row's second-best value (multiplicity counted), lo = its smallest: wave-wide, then across wavefronts
+            double lo = __builtin_huge_val();
+#pragma unroll
+            for (int k = 0; k < kLongPer; ++k) lo = v[k] == ninf ? lo : __builtin_fmin(lo, v[k]);
+            {
+                Top2 x;
+                x.v = m1;
+                x.w = m2;
+                x.g = t;
+                const Top2 r = top2_wave_reduce(x);
+                const double wl = -wave_max_f64(-lo);
+                if (lane == 0) {
+                    s_red[0][wave] = r.v;
+                    s_red[1][wave] = r.w;
+                    s_cost[wave] = wl;  // (scratch)
+                }
+            }
+            __syncthreads();
+            double V = ninf, W = ninf, LO = __builtin_huge_val();
+            for (int w2 = 0; w2 < kLongThreads / kWave; ++w2) {
+                const double bv = s_red[0][w2], bw = s_red[1][w2];
+                W = __builtin_fmax(W, __builtin_fmax(__builtin_fmin(bv, V), bw));
+                V = __builtin_fmax(V, bv);
+                LO = __builtin_fmin(LO, s_cost[w2]);
+            }
+            __syncthreads();
+            auto count_ge = [&](double thr, int par) {  // rows' values >= thr, uniform over the workgroup
+                int n = 0;
+#pragma unroll
+                for (int k = 0; k < kLongPer; ++k) n += v[k] >= thr;
+                for (int off = 32; off >= 1; off >>= 1) n += __shfl_xor(n, off);
+                if (t == 0) s_cnt[par] = 0;
+                __syncthreads();
+                if (lane == 0) atomicAdd(&s_cnt[par], n);
+                __syncthreads();
+                return s_cnt[par];
+            };
+            // threshold: count(v >= W) >= 2; more than kCandMax ties at the top: no line
+            double tsel = W;
+            int par = 0;
+            int nsel = count_ge(W, par);
+            par ^= 1;
+            bool ok = nsel <= kCandMax && W > ninf;
+            if (ok && nsel < kCandMin && LO < W) {
+                double hi_t = W, lo_t = LO;  // count(hi_t) = nsel < kCandMin; count(lo_t) = len > kCandMax
+                for (int it = 0; it < 48; ++it) {
+                    const double mid = 0.5 * (hi_t + lo_t);
+                    if (!(mid < hi_t) || !(mid > lo_t)) break;
+                    const int n = count_ge(mid, par);
+                    par ^= 1;
+                    if (n > kCandMax) lo_t = mid;
+                    else {
+                        hi_t = mid;
+                        tsel = mid;
+                        nsel = n;
+                        if (n >= kCandMin) break;
                     }
                 }
             }
-        }
-        __syncthreads();
-        if (wave == 0 && lane < kCandLanes) {
-            const int n = ok ? min(s_n, kCandMax) : 0;
-            int2 x = make_int2(-1, 0);  // empty slot
-            size_t at = (size_t)i * kCandLanes + lane;
-            if (lane == 0) {
-                const double tau = ok ? tsel : __builtin_huge_val();  // +inf: a line that never answers
-                x = make_int2(__double2loint(tau), __double2hiint(tau));
-            } else if (lane == kCandLanes - 1) {
-                x = make_int2(len, 0);
+            // collect the qualifying edges (at most kCandMax) and order them by stored index
+            if (ok) {
+#pragma unroll
+                for (int k = 0; k < kLongPer; ++k) {
+                    if (v[k] >= tsel) {
+                        const int g = s + k * kLongThreads + t;
+                        int c;
+                        double cost;
+                        ed.load(g, c, cost);
+                        const int at = atomicAdd(&s_n, 1);
+                        if (at < kCandMax) {
+                            s_g[at] = g;
+                            s_col[at] = c;
+                            s_cost[at] = cost;
+                        }
+                    }
+                }
             }
-            a.cand[at] = x;
-            __builtin_amdgcn_wave_barrier();
-            if (lane < n) {  // entry `lane` goes to slot 1 + (number of entries with a smaller stored index)
-                int rank = 0;
-                for (int q = 0; q < n; ++q) rank += s_g[q] < s_g[lane];
-                at = (size_t)i * kCandLanes + 1 + rank;
-                a.cand[at] = make_int2(s_col[lane], a.cand64 ? 0 : __float_as_int((float)s_cost[lane]));
-                if (a.cand64) a.cand64[at] = s_cost[lane];
+            __syncthreads();
+            if (wave == 0 && lane < kCandLanes) {
+                const int n = ok ? min(s_n, kCandMax) : 0;
+                int2 x = make_int2(-1, 0);  // empty slot
+                size_t at = (size_t)i * kCandLanes + lane;
+                if (lane == 0) {
+                    const double tau = ok ? tsel : __builtin_huge_val();  // +inf: a line that never answers
+                    x = make_int2(__double2loint(tau), __double2hiint(tau));
+                } else if (lane == kCandLanes - 1) {
+                    x = make_int2(len, 0);
+                }
+                a.cand[at] = x;
+                __builtin_amdgcn_wave_barrier();
+                if (lane < n) {  // entry `lane` goes to slot 1 + (number of entries with a smaller stored index)
+                    int rank = 0;
+                    for (int q = 0; q < n; ++q) rank += s_g[q] < s_g[lane];
+                    at = (size_t)i * kCandLanes + 1 + rank;
+                    a.cand[at] = make_int2(s_col[lane], a.cand64 ? 0 : __float_as_int((float)s_cost[lane]));
+                    if (a.cand64) a.cand64[at] = s_cost[lane];
+                }
             }
+            __syncthreads();
         }
-        __syncthreads();
     }
-}
-template <class E, int kLongThreads>
-__global__ __launch_bounds__(kLongThreads) void k_refresh_long(RoundArgs a, E ed) { k_refresh_long_body<E, kLongThreads>(a, ed); }
-template <class E, int kLongThreads>
-struct F_k_refresh_long {  // (the body as a callable: what a batched launch runs per problem, csrc/host_batch.hpp)
-    static __device__ __forceinline__ void run(RoundArgs a, E ed) { k_refresh_long_body<E, kLongThreads>(a, ed); }
 };
 
 
@@ -502,39 +490,38 @@ struct F_k_refresh_long {  // (the body as a callable: what a batched launch run
 // take_n workgroups scanned (RoundArgs::wg_stats), like k_take_launch_edges, without a launch of its own
 // order_min_K: the person-ordered scan (and the kernels that prepare order_pos) ran only if K >= order_min_K -- a round
 // enqueued on a stale upper bound of K may have been bid by k_bid instead, in list order
-__device__ __forceinline__ void k_tiebreak_body(RoundArgs a, const int *order_pos, int order_min_K, int take_n, unsigned long long *take_out) {
-    const Ctl *ctl = a.ctl;
-    if (!round_live(ctl, a.thr)) return;
-    if (ctl->K < order_min_K) order_pos = nullptr;
-    if (take_n > 0 && blockIdx.x == 0 && threadIdx.x < kWave) {
-        unsigned long long v = 0, vh = 0;
-        for (int k = threadIdx.x; k < take_n; k += kWave) {
-            unsigned long long *st = a.wg_stats + (size_t)kStatWords * k;
-            v += st[kStatLaunchEdges];
-            vh += st[kStatLaunchHitEdges];
-            st[kStatLaunchEdges] = 0ull;
-            st[kStatLaunchHitEdges] = 0ull;
+struct k_tiebreak {
+    MISSLAP_KERNEL(256)
+    static __device__ __forceinline__ void run(RoundArgs a, const int *order_pos, int order_min_K, int take_n, unsigned long long *take_out) {
+        const Ctl *ctl = a.ctl;
+        if (!round_live(ctl, a.thr)) return;
+        if (ctl->K < order_min_K) order_pos = nullptr;
+        if (take_n > 0 && blockIdx.x == 0 && threadIdx.x < kWave) {
+            unsigned long long v = 0, vh = 0;
+            for (int k = threadIdx.x; k < take_n; k += kWave) {
+                unsigned long long *st = a.wg_stats + (size_t)kStatWords * k;
+                v += st[kStatLaunchEdges];
+                vh += st[kStatLaunchHitEdges];
+                st[kStatLaunchEdges] = 0ull;
+                st[kStatLaunchHitEdges] = 0ull;
+            }
+            for (int off = 32; off >= 1; off >>= 1) {
+                v += ((unsigned long long)__shfl_xor((unsigned)(v >> 32), off) << 32) | (unsigned long long)__shfl_xor((unsigned)(v & 0xffffffffull), off);
+                vh += ((unsigned long long)__shfl_xor((unsigned)(vh >> 32), off) << 32) | (unsigned long long)__shfl_xor((unsigned)(vh & 0xffffffffull), off);
+            }
+            if (threadIdx.x == 0) {  // {edges of the bidders' rows, of which answered from lines}
+                take_out[0] += v;
+                take_out[1] += vh;
+            }
         }
-        for (int off = 32; off >= 1; off >>= 1) {
-            v += ((unsigned long long)__shfl_xor((unsigned)(v >> 32), off) << 32) | (unsigned long long)__shfl_xor((unsigned)(v & 0xffffffffull), off);
-            vh += ((unsigned long long)__shfl_xor((unsigned)(vh >> 32), off) << 32) | (unsigned long long)__shfl_xor((unsigned)(vh & 0xffffffffull), off);
-        }
-        if (threadIdx.x == 0) {  // {edges of the bidders' rows, of which answered from lines}
-            take_out[0] += v;
-            take_out[1] += vh;
+        int lo, hi;
+        shard_range(ctl->K, a.rank, a.world, a.shard_min_K, lo, hi);
+        for (int r = lo + blockIdx.x * blockDim.x + threadIdx.x; r < hi; r += gridDim.x * blockDim.x) {
+            const int n = order_pos ? order_pos[r] : r;
+            const int j = a.bid_obj[n];
+            if (a.bid_key[n] == a.best_key[j]) atomicMin(&a.best_pos[j], n);
         }
     }
-    int lo, hi;
-    shard_range(ctl->K, a.rank, a.world, a.shard_min_K, lo, hi);
-    for (int r = lo + blockIdx.x * blockDim.x + threadIdx.x; r < hi; r += gridDim.x * blockDim.x) {
-        const int n = order_pos ? order_pos[r] : r;
-        const int j = a.bid_obj[n];
-        if (a.bid_key[n] == a.best_key[j]) atomicMin(&a.best_pos[j], n);
-    }
-}
-__global__ __launch_bounds__(256) void k_tiebreak(RoundArgs a, const int *order_pos, int order_min_K, int take_n, unsigned long long *take_out) { k_tiebreak_body(a, order_pos, order_min_K, take_n, take_out); }
-struct F_k_tiebreak {  // (the body as a callable: what a batched launch runs per problem, csrc/host_batch.hpp)
-    static __device__ __forceinline__ void run(RoundArgs a, const int *order_pos, int order_min_K, int take_n, unsigned long long *take_out) { k_tiebreak_body(a, order_pos, order_min_K, take_n, take_out); }
 };
 
 
@@ -625,184 +612,179 @@ __device__ __forceinline__ void count_holes(Ctl *ctl, int holes) {  // one atomi
     }
 }
 // One thread per object: instead of the reference's O(M) sequential walk (:394).
-__device__ __forceinline__ void k_apply_body(RoundArgs a) {
-    Ctl *ctl = a.ctl;
-    if (!round_live(ctl, a.thr)) return;
-    int holes = 0;
-    for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < a.n_cols; j += gridDim.x * blockDim.x) {
-        const int n = a.best_pos[j];
-        if (n != kPosNone) holes += apply_winner_of(a, ctl, j, n);
+struct k_apply {
+    MISSLAP_KERNEL(256)
+    static __device__ __forceinline__ void run(RoundArgs a) {
+        Ctl *ctl = a.ctl;
+        if (!round_live(ctl, a.thr)) return;
+        int holes = 0;
+        for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < a.n_cols; j += gridDim.x * blockDim.x) {
+            const int n = a.best_pos[j];
+            if (n != kPosNone) holes += apply_winner_of(a, ctl, j, n);
+        }
+        count_holes(ctl, holes);
     }
-    count_holes(ctl, holes);
-}
-__global__ __launch_bounds__(256) void k_apply(RoundArgs a) { k_apply_body(a); }
-struct F_k_apply {  // (the body as a callable: what a batched launch runs per problem, csrc/host_batch.hpp)
-    static __device__ __forceinline__ void run(RoundArgs a) { k_apply_body(a); }
 };
 
 // One thread per BIDDER, for rounds with far fewer bidders than objects (every list position below K has bid in this
 // round, so bid_obj[n] is this round's -- on every rank only in rounds that are not sharded): position n has won the
 // object it bid on iff k_tiebreak left n in best_pos.  A loser that reads best_pos after the winner has reset it sees
 // "none", which is not its position either.
-__device__ __forceinline__ void k_apply_bidders_body(RoundArgs a) {
-    Ctl *ctl = a.ctl;
-    if (!round_live(ctl, a.thr)) return;
-    const int K = ctl->K;
-    int holes = 0;
-    for (int n = blockIdx.x * blockDim.x + threadIdx.x; n < K; n += gridDim.x * blockDim.x) {
-        const int j = a.bid_obj[n];
-        if (a.best_pos[j] == n) holes += apply_winner_of(a, ctl, j, n);
+struct k_apply_bidders {
+    MISSLAP_KERNEL(256)
+    static __device__ __forceinline__ void run(RoundArgs a) {
+        Ctl *ctl = a.ctl;
+        if (!round_live(ctl, a.thr)) return;
+        const int K = ctl->K;
+        int holes = 0;
+        for (int n = blockIdx.x * blockDim.x + threadIdx.x; n < K; n += gridDim.x * blockDim.x) {
+            const int j = a.bid_obj[n];
+            if (a.best_pos[j] == n) holes += apply_winner_of(a, ctl, j, n);
+        }
+        count_holes(ctl, holes);
     }
-    count_holes(ctl, holes);
-}
-__global__ __launch_bounds__(256) void k_apply_bidders(RoundArgs a) { k_apply_bidders_body(a); }
-struct F_k_apply_bidders {  // (the body as a callable: what a batched launch runs per problem, csrc/host_batch.hpp)
-    static __device__ __forceinline__ void run(RoundArgs a) { k_apply_bidders_body(a); }
 };
 
 
 // push_all_left: the k-th empty slot in [0, K') receives the k-th person found in [K', K).
 constexpr int kChunk = 1024;  // U positions per block (256 threads x 4)
-__device__ __forceinline__ void k_compact_count_body(RoundArgs a) {
-    const Ctl *ctl = a.ctl;
-    if (!round_live(ctl, a.thr)) return;
-    const int K = ctl->K, Kn = K - ctl->nholes;
-    if (ctl->nholes == 0) return;
-    const int nchunks = (K + kChunk - 1) / kChunk;
-    __shared__ int sl[4], sm[4];
-    for (int b = blockIdx.x; b < nchunks; b += gridDim.x) {
-        int l = 0, m = 0;
+struct k_compact_count {
+    MISSLAP_KERNEL(256)
+    static __device__ __forceinline__ void run(RoundArgs a) {
+        const Ctl *ctl = a.ctl;
+        if (!round_live(ctl, a.thr)) return;
+        const int K = ctl->K, Kn = K - ctl->nholes;
+        if (ctl->nholes == 0) return;
+        const int nchunks = (K + kChunk - 1) / kChunk;
+        __shared__ int sl[4], sm[4];
+        for (int b = blockIdx.x; b < nchunks; b += gridDim.x) {
+            int l = 0, m = 0;
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int n = b * kChunk + q * 256 + threadIdx.x;
-            if (n < K) {
-                const int u = a.U[n];
-                l += (n < Kn && u == -1);
-                m += (n >= Kn && u != -1);
+            for (int q = 0; q < 4; ++q) {
+                const int n = b * kChunk + q * 256 + threadIdx.x;
+                if (n < K) {
+                    const int u = a.U[n];
+                    l += (n < Kn && u == -1);
+                    m += (n >= Kn && u != -1);
+                }
             }
+            for (int off = 32; off >= 1; off >>= 1) {
+                l += __shfl_xor(l, off);
+                m += __shfl_xor(m, off);
+            }
+            if ((threadIdx.x & 63) == 0) {
+                sl[threadIdx.x >> 6] = l;
+                sm[threadIdx.x >> 6] = m;
+            }
+            __syncthreads();
+            if (threadIdx.x == 0) {
+                a.cnt[2 * b] = sl[0] + sl[1] + sl[2] + sl[3];
+                a.cnt[2 * b + 1] = sm[0] + sm[1] + sm[2] + sm[3];
+            }
+            __syncthreads();
         }
-        for (int off = 32; off >= 1; off >>= 1) {
-            l += __shfl_xor(l, off);
-            m += __shfl_xor(m, off);
-        }
-        if ((threadIdx.x & 63) == 0) {
-            sl[threadIdx.x >> 6] = l;
-            sm[threadIdx.x >> 6] = m;
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            a.cnt[2 * b] = sl[0] + sl[1] + sl[2] + sl[3];
-            a.cnt[2 * b + 1] = sm[0] + sm[1] + sm[2] + sm[3];
-        }
-        __syncthreads();
     }
-}
-__global__ __launch_bounds__(256) void k_compact_count(RoundArgs a) { k_compact_count_body(a); }
-struct F_k_compact_count {  // (the body as a callable: what a batched launch runs per problem, csrc/host_batch.hpp)
-    static __device__ __forceinline__ void run(RoundArgs a) { k_compact_count_body(a); }
 };
 
 
-__device__ __forceinline__ void k_compact_scatter_body(RoundArgs a) {
-    Ctl *ctl = a.ctl;
-    if (!round_live(ctl, a.thr)) return;
-    const int K = ctl->K, Kn = K - ctl->nholes;
-    if (ctl->nholes == 0) return;
-    const int nchunks = (K + kChunk - 1) / kChunk;
-    __shared__ int s_red[2][4];
-    __shared__ int s_wl[4], s_wm[4];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    for (int b = blockIdx.x; b < nchunks; b += gridDim.x) {
-        // exclusive offsets of this chunk = sum of the counts of all earlier chunks
-        int pl = 0, pm = 0;
-        for (int c = threadIdx.x; c < b; c += 256) {
-            pl += a.cnt[2 * c];
-            pm += a.cnt[2 * c + 1];
-        }
-        for (int off = 32; off >= 1; off >>= 1) {
-            pl += __shfl_xor(pl, off);
-            pm += __shfl_xor(pm, off);
-        }
-        if (lane == 0) {
-            s_red[0][wave] = pl;
-            s_red[1][wave] = pm;
-        }
-        __syncthreads();
-        int offl = s_red[0][0] + s_red[0][1] + s_red[0][2] + s_red[0][3];
-        int offm = s_red[1][0] + s_red[1][1] + s_red[1][2] + s_red[1][3];
-        __syncthreads();
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int n = b * kChunk + q * 256 + threadIdx.x;
-            int u = -1;
-            if (n < K) u = a.U[n];
-            const bool isl = (n < Kn) && (u == -1);
-            const bool ism = (n >= Kn) && (n < K) && (u != -1);
-            const unsigned long long bl = __ballot(isl), bm = __ballot(ism);
+struct k_compact_scatter {
+    MISSLAP_KERNEL(256)
+    static __device__ __forceinline__ void run(RoundArgs a) {
+        Ctl *ctl = a.ctl;
+        if (!round_live(ctl, a.thr)) return;
+        const int K = ctl->K, Kn = K - ctl->nholes;
+        if (ctl->nholes == 0) return;
+        const int nchunks = (K + kChunk - 1) / kChunk;
+        __shared__ int s_red[2][4];
+        __shared__ int s_wl[4], s_wm[4];
+        const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+        for (int b = blockIdx.x; b < nchunks; b += gridDim.x) {
+            // exclusive offsets of this chunk = sum of the counts of all earlier chunks
+            int pl = 0, pm = 0;
+            for (int c = threadIdx.x; c < b; c += 256) {
+                pl += a.cnt[2 * c];
+                pm += a.cnt[2 * c + 1];
+            }
+            for (int off = 32; off >= 1; off >>= 1) {
+                pl += __shfl_xor(pl, off);
+                pm += __shfl_xor(pm, off);
+            }
             if (lane == 0) {
-                s_wl[wave] = __popcll(bl);
-                s_wm[wave] = __popcll(bm);
+                s_red[0][wave] = pl;
+                s_red[1][wave] = pm;
             }
             __syncthreads();
-            int wl = 0, wm = 0, tl = 0, tm = 0;
-            for (int w2 = 0; w2 < 4; ++w2) {
-                if (w2 < wave) {
-                    wl += s_wl[w2];
-                    wm += s_wm[w2];
+            int offl = s_red[0][0] + s_red[0][1] + s_red[0][2] + s_red[0][3];
+            int offm = s_red[1][0] + s_red[1][1] + s_red[1][2] + s_red[1][3];
+            __syncthreads();
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int n = b * kChunk + q * 256 + threadIdx.x;
+                int u = -1;
+                if (n < K) u = a.U[n];
+                const bool isl = (n < Kn) && (u == -1);
+                const bool ism = (n >= Kn) && (n < K) && (u != -1);
+                const unsigned long long bl = __ballot(isl), bm = __ballot(ism);
+                if (lane == 0) {
+                    s_wl[wave] = __popcll(bl);
+                    s_wm[wave] = __popcll(bm);
                 }
-                tl += s_wl[w2];
-                tm += s_wm[w2];
+                __syncthreads();
+                int wl = 0, wm = 0, tl = 0, tm = 0;
+                for (int w2 = 0; w2 < 4; ++w2) {
+                    if (w2 < wave) {
+                        wl += s_wl[w2];
+                        wm += s_wm[w2];
+                    }
+                    tl += s_wl[w2];
+                    tm += s_wm[w2];
+                }
+                if (isl) a.hole_list[offl + wl + __popcll(bl & lanemask_lt())] = n;
+                if (ism) {
+                    a.mover_list[offm + wm + __popcll(bm & lanemask_lt())] = u;
+                    a.U[n] = -1;  // data[right_track] = -1   (:159)
+                }
+                offl += tl;
+                offm += tm;
+                __syncthreads();
             }
-            if (isl) a.hole_list[offl + wl + __popcll(bl & lanemask_lt())] = n;
-            if (ism) {
-                a.mover_list[offm + wm + __popcll(bm & lanemask_lt())] = u;
-                a.U[n] = -1;  // data[right_track] = -1   (:159)
-            }
-            offl += tl;
-            offm += tm;
-            __syncthreads();
+            if (b == nchunks - 1 && threadIdx.x == 0) ctl->nleft = offl;  // total left holes (== movers)
         }
-        if (b == nchunks - 1 && threadIdx.x == 0) ctl->nleft = offl;  // total left holes (== movers)
     }
-}
-__global__ __launch_bounds__(256) void k_compact_scatter(RoundArgs a) { k_compact_scatter_body(a); }
-struct F_k_compact_scatter {  // (the body as a callable: what a batched launch runs per problem, csrc/host_batch.hpp)
-    static __device__ __forceinline__ void run(RoundArgs a) { k_compact_scatter_body(a); }
 };
 
 
 // ... and the round's end (K += evicted - assigned :429, nits += 1 :273; a launch of one thread until round 4): every
 // workgroup reads the control block when it starts and counts itself in on Ctl::arrive when it is done; the one that
 // arrives last knows that nobody reads the old K any more and writes the new one.
-__device__ __forceinline__ void k_compact_fill_body(RoundArgs a) {
-    Ctl *ctl = a.ctl;
-    const CtlHead head(ctl);
-    if (!head.live(a.thr, false)) {  // (uniform over the launch)
-        if (blockIdx.x == 0 && threadIdx.x == 0) post_live_status(a.live, a.ticket, head.K, head.err, head.nits);
-        return;
+struct k_compact_fill {
+    MISSLAP_KERNEL(256)
+    static __device__ __forceinline__ void run(RoundArgs a) {
+        Ctl *ctl = a.ctl;
+        const CtlHead head(ctl);
+        if (!head.live(a.thr, false)) {  // (uniform over the launch)
+            if (blockIdx.x == 0 && threadIdx.x == 0) post_live_status(a.live, a.ticket, head.K, head.err, head.nits);
+            return;
+        }
+        const int nholes = ctl->nholes;
+        if (nholes != 0) {
+            const int nl = ctl->nleft;
+            for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < nl; k += gridDim.x * blockDim.x)
+                a.U[a.hole_list[k]] = a.mover_list[k];  // data[left_track] = i   (:158)
+        }
+        __syncthreads();  // (every thread of the workgroup has read what it needs of the control block)
+        if (threadIdx.x == 0 &&
+            __hip_atomic_fetch_add(&ctl->arrive, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (int)gridDim.x - 1) {
+            __hip_atomic_store(&ctl->arrive, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // for the next launch
+            const int Kn = head.K - nholes;
+            ctl->K = Kn;  // :429
+            ctl->nholes = 0;
+            ctl->nleft = 0;
+            ctl->nits = head.nits + 1;  // :273
+            ctl->grid_rounds += 1;
+            post_live_status(a.live, a.ticket, Kn, head.err, head.nits + 1);
+        }
     }
-    const int nholes = ctl->nholes;
-    if (nholes != 0) {
-        const int nl = ctl->nleft;
-        for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < nl; k += gridDim.x * blockDim.x)
-            a.U[a.hole_list[k]] = a.mover_list[k];  // data[left_track] = i   (:158)
-    }
-    __syncthreads();  // (every thread of the workgroup has read what it needs of the control block)
-    if (threadIdx.x == 0 &&
-        __hip_atomic_fetch_add(&ctl->arrive, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (int)gridDim.x - 1) {
-        __hip_atomic_store(&ctl->arrive, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // for the next launch
-        const int Kn = head.K - nholes;
-        ctl->K = Kn;  // :429
-        ctl->nholes = 0;
-        ctl->nleft = 0;
-        ctl->nits = head.nits + 1;  // :273
-        ctl->grid_rounds += 1;
-        post_live_status(a.live, a.ticket, Kn, head.err, head.nits + 1);
-    }
-}
-__global__ __launch_bounds__(256) void k_compact_fill(RoundArgs a) { k_compact_fill_body(a); }
-struct F_k_compact_fill {  // (the body as a callable: what a batched launch runs per problem, csrc/host_batch.hpp)
-    static __device__ __forceinline__ void run(RoundArgs a) { k_compact_fill_body(a); }
 };
 
 
@@ -895,18 +877,17 @@ __device__ __forceinline__ void compact_small_body(const RoundArgs &a, Ctl *ctl,
     }
 }
 
-__device__ __forceinline__ void k_compact_small_body(RoundArgs a) {
-    Ctl *ctl = a.ctl;
-    const CtlHead head(ctl);
-    if (!head.live(a.thr, false)) {  // (the round was not live: its ticket is posted all the same -- the host waits for it)
-        if (threadIdx.x == 0) post_live_status(a.live, a.ticket, head.K, head.err, head.nits);
-        return;
+struct k_compact_small {
+    MISSLAP_KERNEL(1024)
+    static __device__ __forceinline__ void run(RoundArgs a) {
+        Ctl *ctl = a.ctl;
+        const CtlHead head(ctl);
+        if (!head.live(a.thr, false)) {  // (the round was not live: its ticket is posted all the same -- the host waits for it)
+            if (threadIdx.x == 0) post_live_status(a.live, a.ticket, head.K, head.err, head.nits);
+            return;
+        }
+        compact_small_body(a, ctl, head.K, ctl->nholes, head.err);
     }
-    compact_small_body(a, ctl, head.K, ctl->nholes, head.err);
-}
-__global__ __launch_bounds__(1024) void k_compact_small(RoundArgs a) { k_compact_small_body(a); }
-struct F_k_compact_small {  // (the body as a callable: what a batched launch runs per problem, csrc/host_batch.hpp)
-    static __device__ __forceinline__ void run(RoundArgs a) { k_compact_small_body(a); }
 };
 
 
@@ -1056,30 +1037,29 @@ __device__ __forceinline__ void round_small_body(const RoundArgs &a, Ctl *ctl, c
     }
 }
 
-__device__ __forceinline__ void k_round_small_body(RoundArgs a) {
-    const int t = threadIdx.x;
-    // Everything a position needs comes from its bidder (k_bid<E, RecSource>) in two loads, requested before the
-    // control block is read (positions at or beyond K hold stale bids, masked below) and kept in registers.
-    Ctl *ctl = a.ctl;
-    const CtlHead head(ctl);
-    int4 br[kRoundSmallSlots];
-    unsigned long long key[kRoundSmallSlots];
-    bool never = false;  // (objects are >= 0, a key is the bit pattern of a finite bid + 1)
+struct k_round_small {
+    MISSLAP_KERNEL(1024)
+    static __device__ __forceinline__ void run(RoundArgs a) {
+        const int t = threadIdx.x;
+        // Everything a position needs comes from its bidder (k_bid<E, RecSource>) in two loads, requested before the
+        // control block is read (positions at or beyond K hold stale bids, masked below) and kept in registers.
+        Ctl *ctl = a.ctl;
+        const CtlHead head(ctl);
+        int4 br[kRoundSmallSlots];
+        unsigned long long key[kRoundSmallSlots];
+        bool never = false;  // (objects are >= 0, a key is the bit pattern of a finite bid + 1)
 #pragma unroll
-    for (int q = 0; q < kRoundSmallSlots; ++q) {
-        br[q] = a.bid_rec[q * 1024 + t];
-        key[q] = a.bid_key[min(q * 1024 + t, a.n_rows - 1)];
-        never |= (br[q].x < 0) | (key[q] == ~0ull);
+        for (int q = 0; q < kRoundSmallSlots; ++q) {
+            br[q] = a.bid_rec[q * 1024 + t];
+            key[q] = a.bid_key[min(q * 1024 + t, a.n_rows - 1)];
+            never |= (br[q].x < 0) | (key[q] == ~0ull);
+        }
+        if (!head.live(a.thr, never)) {
+            if (t == 0) post_live_status(a.live, a.ticket, head.K, head.err, head.nits);
+            return;
+        }
+        round_small_body(a, ctl, head, br, key);
     }
-    if (!head.live(a.thr, never)) {
-        if (t == 0) post_live_status(a.live, a.ticket, head.K, head.err, head.nits);
-        return;
-    }
-    round_small_body(a, ctl, head, br, key);
-}
-__global__ __launch_bounds__(1024) void k_round_small(RoundArgs a) { k_round_small_body(a); }
-struct F_k_round_small {  // (the body as a callable: what a batched launch runs per problem, csrc/host_batch.hpp)
-    static __device__ __forceinline__ void run(RoundArgs a) { k_round_small_body(a); }
 };
 
 
@@ -1093,99 +1073,91 @@ struct F_k_round_small {  // (the body as a callable: what a batched launch runs
 // Saves one launch boundary per round (~5 us of ~10.5; 1 400 - 2 100 such rounds per C3 solve), and one launch in four
 // of a solve is what bounds several solves in flight on one GPU.
 template <class E>
-__device__ __forceinline__ void k_round_fused_body(RoundArgs a, E ed) {
-    const int t = threadIdx.x, wave = t >> 6;
-    constexpr int wpb = 1024 / kWave;
-    const int first = blockIdx.x * wpb + wave;
-    Ctl *ctl = a.ctl;
-    const CtlHead head(ctl);
-    const int i_first = a.U[min(first, a.n_rows - 1)];
-    // (the exit below depends on the control block ALONE -- it must be the same in every workgroup of the launch, or
-    // the count-in would never complete -- and the list entry is requested ahead of it all the same: the empty asm
-    // makes it a value the code in front of the exit needs)
-    asm volatile("" ::"v"(i_first));
-    if (!head.live(a.thr, false)) {  // (uniform over the launch: nobody counts in)
-        if (blockIdx.x == 0 && t == 0) post_live_status(a.live, a.ticket, head.K, head.err, head.nits);
-        return;
-    }
-    BidTally tl;
-    bid_positions<E, RecSource, 2, true>(a, ed, 0, head.K, first, gridDim.x * wpb, i_first, tl);
-    tally_flush<wpb>(a, tl, head.K);
-    __shared__ int s_arrived;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (t == 0) s_arrived = __hip_atomic_fetch_add(&ctl->arrive, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    if (s_arrived != (int)gridDim.x - 1) return;  // uniform over the workgroup
-    if (t == 0) __hip_atomic_store(&ctl->arrive, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // for the next launch
-    int4 br[kRoundSmallSlots];
-    unsigned long long key[kRoundSmallSlots];
+struct k_round_fused {
+    MISSLAP_KERNEL(1024)
+    static __device__ __forceinline__ void run(RoundArgs a, E ed) {
+        const int t = threadIdx.x, wave = t >> 6;
+        constexpr int wpb = 1024 / kWave;
+        const int first = blockIdx.x * wpb + wave;
+        Ctl *ctl = a.ctl;
+        const CtlHead head(ctl);
+        const int i_first = a.U[min(first, a.n_rows - 1)];
+        // (the exit below depends on the control block ALONE -- it must be the same in every workgroup of the launch, or
+        // the count-in would never complete -- and the list entry is requested ahead of it all the same: the empty asm
+        // makes it a value the code in front of the exit needs)
+        asm volatile("" ::"v"(i_first));
+        if (!head.live(a.thr, false)) {  // (uniform over the launch: nobody counts in)
+            if (blockIdx.x == 0 && t == 0) post_live_status(a.live, a.ticket, head.K, head.err, head.nits);
+            return;
+        }
+        BidTally tl;
+        bid_positions<E, RecSource, 2, true>(a, ed, 0, head.K, first, gridDim.x * wpb, i_first, tl);
+        tally_flush<wpb>(a, tl, head.K);
+        __shared__ int s_arrived;
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        if (t == 0) s_arrived = __hip_atomic_fetch_add(&ctl->arrive, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __syncthreads();
+        if (s_arrived != (int)gridDim.x - 1) return;  // uniform over the workgroup
+        if (t == 0) __hip_atomic_store(&ctl->arrive, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // for the next launch
+        int4 br[kRoundSmallSlots];
+        unsigned long long key[kRoundSmallSlots];
 #pragma unroll
-    for (int q = 0; q < kRoundSmallSlots; ++q) {
-        const int n = min(q * 1024 + t, a.n_rows - 1);
-        const unsigned long long *r = reinterpret_cast<const unsigned long long *>(&a.bid_rec[q * 1024 + t]);
-        const unsigned long long r0 = handover_load(r), r1 = handover_load(r + 1);
-        br[q] = make_int4((int)(unsigned)(r0 & 0xffffffffull), (int)(unsigned)(r0 >> 32), (int)(unsigned)(r1 & 0xffffffffull),
-                          (int)(unsigned)(r1 >> 32));
-        key[q] = handover_load(&a.bid_key[n]);
+        for (int q = 0; q < kRoundSmallSlots; ++q) {
+            const int n = min(q * 1024 + t, a.n_rows - 1);
+            const unsigned long long *r = reinterpret_cast<const unsigned long long *>(&a.bid_rec[q * 1024 + t]);
+            const unsigned long long r0 = handover_load(r), r1 = handover_load(r + 1);
+            br[q] = make_int4((int)(unsigned)(r0 & 0xffffffffull), (int)(unsigned)(r0 >> 32), (int)(unsigned)(r1 & 0xffffffffull),
+                              (int)(unsigned)(r1 >> 32));
+            key[q] = handover_load(&a.bid_key[n]);
+        }
+        round_small_body(a, ctl, head, br, key);
     }
-    round_small_body(a, ctl, head, br, key);
-}
-template <class E>
-__global__ __launch_bounds__(1024) void k_round_fused(RoundArgs a, E ed) { k_round_fused_body<E>(a, ed); }
-template <class E>
-struct F_k_round_fused {  // (the body as a callable: what a batched launch runs per problem, csrc/host_batch.hpp)
-    static __device__ __forceinline__ void run(RoundArgs a, E ed) { k_round_fused_body<E>(a, ed); }
 };
 
 
 // The status of everything enqueued so far, posted by a launch of its own: behind a batch of small rounds, whose
 // closing kernel (k_round_small, a few microseconds each, thousands per solve) does not pay for four stores to host
 // memory every round.
-__device__ __forceinline__ void k_post_status_body(const Ctl *ctl, unsigned long long *live, unsigned ticket) {
-    post_live_status(live, ticket, ctl->K, ctl->err, ctl->nits);
-}
-__global__ void k_post_status(const Ctl *ctl, unsigned long long *live, unsigned ticket) { k_post_status_body(ctl, live, ticket); }
-struct F_k_post_status {  // (the body as a callable: what a batched launch runs per problem, csrc/host_batch.hpp)
-    static __device__ __forceinline__ void run(const Ctl *ctl, unsigned long long *live, unsigned ticket) { k_post_status_body(ctl, live, ticket); }
+struct k_post_status {
+    MISSLAP_KERNEL_BOUND(1, 1024)
+    static __device__ __forceinline__ void run(const Ctl *ctl, unsigned long long *live, unsigned ticket) {
+        post_live_status(live, ticket, ctl->K, ctl->err, ctl->nits);
+    }
 };
 
 // ... and, behind the eCE pass of a phase end, its verdict in a fifth word
-__device__ __forceinline__ void k_post_ece_body(const Ctl *ctl, unsigned long long *live, unsigned ticket) {
-    post_live_status(live, ticket, ctl->K, ctl->err, ctl->nits);
-    __hip_atomic_store(&live[4], ((unsigned long long)ticket << 32) | (unsigned)ctl->ece_fail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-__global__ void k_post_ece(const Ctl *ctl, unsigned long long *live, unsigned ticket) { k_post_ece_body(ctl, live, ticket); }
-struct F_k_post_ece {  // (the body as a callable: what a batched launch runs per problem, csrc/host_batch.hpp)
-    static __device__ __forceinline__ void run(const Ctl *ctl, unsigned long long *live, unsigned ticket) { k_post_ece_body(ctl, live, ticket); }
+struct k_post_ece {
+    MISSLAP_KERNEL_BOUND(1, 1024)
+    static __device__ __forceinline__ void run(const Ctl *ctl, unsigned long long *live, unsigned ticket) {
+        post_live_status(live, ticket, ctl->K, ctl->err, ctl->nits);
+        __hip_atomic_store(&live[4], ((unsigned long long)ticket << 32) | (unsigned)ctl->ece_fail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
 };
 
 
 // eps-phase restart (auction_.pyx:286-290): forget assignments, keep prices.
-__device__ __forceinline__ void k_reset_phase_body(Ctl *ctl, int *p2o, int *o2p, PriceRec *rec, int *U,
-                                                     int n_rows, int n_cols) {
-    const int stride = gridDim.x * blockDim.x;
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    for (int i = t; i < n_rows; i += stride) {
-        p2o[i] = -1;
-        U[i] = i;
+struct k_reset_phase {
+    MISSLAP_KERNEL(256)
+    static __device__ __forceinline__ void run(Ctl *ctl, int *p2o, int *o2p, PriceRec *rec, int *U, int n_rows, int n_cols) {
+        const int stride = gridDim.x * blockDim.x;
+        const int t = blockIdx.x * blockDim.x + threadIdx.x;
+        for (int i = t; i < n_rows; i += stride) {
+            p2o[i] = -1;
+            U[i] = i;
+        }
+        for (int j = t; j < n_cols; j += stride) {
+            o2p[j] = -1;
+            rec[j].owner = -1;  // the price stays
+        }
+        if (t == 0) {
+            ctl->K = n_rows;
+            ctl->nholes = 0;
+            ctl->nleft = 0;
+            ctl->arrive = 0;  // (k_round_fused leaves it at 0 itself; a phase starts from a known count whatever came before)
+            ctl->ece_fail = 0;  // (the eCE test at the end of this phase finds its flag clear: no fill launch in front of it)
+        }
     }
-    for (int j = t; j < n_cols; j += stride) {
-        o2p[j] = -1;
-        rec[j].owner = -1;  // the price stays
-    }
-    if (t == 0) {
-        ctl->K = n_rows;
-        ctl->nholes = 0;
-        ctl->nleft = 0;
-        ctl->arrive = 0;  // (k_round_fused leaves it at 0 itself; a phase starts from a known count whatever came before)
-        ctl->ece_fail = 0;  // (the eCE test at the end of this phase finds its flag clear: no fill launch in front of it)
-    }
-}
-__global__ __launch_bounds__(256) void k_reset_phase(Ctl *ctl, int *p2o, int *o2p, PriceRec *rec, int *U,
-                                                     int n_rows, int n_cols) { k_reset_phase_body(ctl, p2o, o2p, rec, U, n_rows, n_cols); }
-struct F_k_reset_phase {  // (the body as a callable: what a batched launch runs per problem, csrc/host_batch.hpp)
-    static __device__ __forceinline__ void run(Ctl *ctl, int *p2o, int *o2p, PriceRec *rec, int *U, int n_rows, int n_cols) { k_reset_phase_body(ctl, p2o, o2p, rec, U, n_rows, n_cols); }
 };
 
 

@@ -76,35 +76,30 @@ __device__ __forceinline__ int apply_winner(const TailArgs &a, int person, int p
 // After the tail kernels: price[j], o2p[j] from the records, and p2o as the inverse of o2p.  p2o needs no clearing pass:
 // every person is either the owner of exactly one record (written below) or unassigned, and the unassigned persons are
 // the list U[0, K) -- K <= the tail threshold of them.
-__device__ __forceinline__ void k_sync_from_rec_body(Ctl *ctl, const PriceRec *rec, double *price, int *o2p, int *p2o,
-                                                       const int *U, int n_cols, int lines, unsigned long long *live,
-                                                       unsigned ticket) {
-    const int K = ctl->K;
-    // (closes a run of tail kernels: K / nits are theirs; an error bit raised below reaches the host with the next status)
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        post_live_status(live, ticket, K, ctl->err, ctl->nits);
-        ctl->n_need = 0;  // the maintenance pass's work list has been consumed
+struct k_sync_from_rec {
+    MISSLAP_KERNEL(256)
+    static __device__ __forceinline__ void run(Ctl *ctl, const PriceRec *rec, double *price, int *o2p, int *p2o, const int *U, int n_cols, int lines, unsigned long long *live, unsigned ticket) {
+        const int K = ctl->K;
+        // (closes a run of tail kernels: K / nits are theirs; an error bit raised below reaches the host with the next status)
+        if (blockIdx.x == 0 && threadIdx.x == 0) {
+            post_live_status(live, ticket, K, ctl->err, ctl->nits);
+            ctl->n_need = 0;  // the maintenance pass's work list has been consumed
+        }
+        for (int n = blockIdx.x * blockDim.x + threadIdx.x; n < K; n += gridDim.x * blockDim.x) {
+            const int i = U[n];
+            if (i >= 0) p2o[i] = -1;
+        }
+        for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < n_cols; j += gridDim.x * blockDim.x) {
+            const PriceRec r = rec[j];
+            // price[] still holds the prices the tail kernels started from: a price may only have risen since (the
+            // candidate lines rely on it; a net fall means eps is below the rounding error of a price update).  A handle
+            // WITHOUT lines does not depend on the invariant -- there a falling price is what the reference computes too
+            if (lines && r.price < price[j]) atomicOr(&ctl->err, kErrPriceFell);
+            price[j] = r.price;
+            o2p[j] = r.owner;
+            if (r.owner >= 0) p2o[r.owner] = j;
+        }
     }
-    for (int n = blockIdx.x * blockDim.x + threadIdx.x; n < K; n += gridDim.x * blockDim.x) {
-        const int i = U[n];
-        if (i >= 0) p2o[i] = -1;
-    }
-    for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < n_cols; j += gridDim.x * blockDim.x) {
-        const PriceRec r = rec[j];
-        // price[] still holds the prices the tail kernels started from: a price may only have risen since (the
-        // candidate lines rely on it; a net fall means eps is below the rounding error of a price update).  A handle
-        // WITHOUT lines does not depend on the invariant -- there a falling price is what the reference computes too
-        if (lines && r.price < price[j]) atomicOr(&ctl->err, kErrPriceFell);
-        price[j] = r.price;
-        o2p[j] = r.owner;
-        if (r.owner >= 0) p2o[r.owner] = j;
-    }
-}
-__global__ __launch_bounds__(256) void k_sync_from_rec(Ctl *ctl, const PriceRec *rec, double *price, int *o2p, int *p2o,
-                                                       const int *U, int n_cols, int lines, unsigned long long *live,
-                                                       unsigned ticket) { k_sync_from_rec_body(ctl, rec, price, o2p, p2o, U, n_cols, lines, live, ticket); }
-struct F_k_sync_from_rec {  // (the body as a callable: what a batched launch runs per problem, csrc/host_batch.hpp)
-    static __device__ __forceinline__ void run(Ctl *ctl, const PriceRec *rec, double *price, int *o2p, int *p2o, const int *U, int n_cols, int lines, unsigned long long *live, unsigned ticket) { k_sync_from_rec_body(ctl, rec, price, o2p, p2o, U, n_cols, lines, live, ticket); }
 };
 
 
@@ -981,414 +976,411 @@ __device__ __forceinline__ bool tail_team1_pipe(const TailArgs &a, const E &ed, 
 // kThreads = 64 ("pair / chain only", handles with lines): the rounds with K <= 2 and nothing else, on one wavefront
 // (tail_pair_mode, then tail_chain_mode); the instance that carries every mode needs 185 VGPRs and spills 14 SGPRs,
 // each spill a v_writelane / v_readlane pair inside a chain that is bound by its instruction count.
-template <class E, int kThreads, bool kTeamOnly>
-__device__ __forceinline__ void k_tail_body(TailArgs a, E ed) {
-    static_assert(!kTeamOnly || (kThreads == 2 * kTailMax && kThreads / kWave == kTeamMax), "one slot per wavefront");
-    constexpr bool kBlockOnly = kThreads > kTailMax && !kTeamOnly;
-    constexpr bool kDuoOnly = kThreads == kWave;
-    static_assert(!kDuoOnly || !kTeamOnly, "roles are exclusive");
-    __shared__ int sU[kTailMax];
-    __shared__ unsigned long long sKey[kTailMax];
-    __shared__ int sObj[kTailMax];
-    __shared__ int sPrev[kTailMax];
-    __shared__ int sStart[kTailMax];  // row start of the person in slot n, kept next to sU: evicted owners bring
-                                      // theirs with the price record, so no row_ptr load precedes a row fetch
-    __shared__ int sPst[kTailMax];    // row start of the owner of the object slot n bid on
-    __shared__ int sList[kTailMax];
-    __shared__ int hObj[kHashSize];
-    __shared__ unsigned long long hKey[kHashSize];
-    __shared__ int hPos[kHashSize];
-    __shared__ int sCnt[3][kThreads / kWave];
-    __shared__ int sK, sMissCnt;
-    __shared__ long long sNits;
+template <class E, int kThreads, bool kTeamOnly = false>
+struct k_tail {
+    MISSLAP_KERNEL(kThreads)
+    static __device__ __forceinline__ void run(TailArgs a, E ed) {
+        static_assert(!kTeamOnly || (kThreads == 2 * kTailMax && kThreads / kWave == kTeamMax), "one slot per wavefront");
+        constexpr bool kBlockOnly = kThreads > kTailMax && !kTeamOnly;
+        constexpr bool kDuoOnly = kThreads == kWave;
+        static_assert(!kDuoOnly || !kTeamOnly, "roles are exclusive");
+        __shared__ int sU[kTailMax];
+        __shared__ unsigned long long sKey[kTailMax];
+        __shared__ int sObj[kTailMax];
+        __shared__ int sPrev[kTailMax];
+        __shared__ int sStart[kTailMax];  // row start of the person in slot n, kept next to sU: evicted owners bring
+                                          // theirs with the price record, so no row_ptr load precedes a row fetch
+        __shared__ int sPst[kTailMax];    // row start of the owner of the object slot n bid on
+        __shared__ int sList[kTailMax];
+        __shared__ int hObj[kHashSize];
+        __shared__ unsigned long long hKey[kHashSize];
+        __shared__ int hPos[kHashSize];
+        __shared__ int sCnt[3][kThreads / kWave];
+        __shared__ int sK, sMissCnt;
+        __shared__ long long sNits;
 
-    Ctl *ctl = a.ctl;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    constexpr int nwaves = kThreads / kWave;
-    int K = ctl->K;
-    long long nits = ctl->nits;
-    const long long max_iter =
-        a.round_budget > 0 ? min(ctl->max_iter, nits + (long long)(kBlockOnly ? max(a.round_budget / 4, 1) : a.round_budget))
-                           : ctl->max_iter;  // (block rounds have the most bidders, i.e. spend the most lines)
-    if (K == 0 || K > a.thr || nits >= max_iter) return;  // uniform
-    if (kBlockOnly && K <= kTeamMax) return;
-    if (kTeamOnly && (K <= 2 || K > kTeamMax)) return;
-    if (kDuoOnly && (K > 2 || !E::kCand || a.cand == nullptr)) return;
-    // (budgeted launches: an instance that ran out of rounds leaves K to the NEXT launch's instance of the right role)
-    if (!kBlockOnly && !kTeamOnly && a.round_budget > 0 && K > 2 && E::kCand && a.cand != nullptr) return;
-    const int K0 = K;
-    const long long nits0 = nits;
-    for (int n = t; n < kTailMax; n += kThreads) {
-        sU[n] = (n < K) ? a.U[n] : -1;
-        sStart[n] = (n < K) ? a.row_ptr[sU[n]] : 0;
-    }
-    if (!kDuoOnly)
-        for (int h = t; h < kHashSize; h += kThreads) {
-            hObj[h] = -1;
-            hKey[h] = 0ull;
-            hPos[h] = kPosNone;
+        Ctl *ctl = a.ctl;
+        const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+        constexpr int nwaves = kThreads / kWave;
+        int K = ctl->K;
+        long long nits = ctl->nits;
+        const long long max_iter =
+            a.round_budget > 0 ? min(ctl->max_iter, nits + (long long)(kBlockOnly ? max(a.round_budget / 4, 1) : a.round_budget))
+                               : ctl->max_iter;  // (block rounds have the most bidders, i.e. spend the most lines)
+        if (K == 0 || K > a.thr || nits >= max_iter) return;  // uniform
+        if (kBlockOnly && K <= kTeamMax) return;
+        if (kTeamOnly && (K <= 2 || K > kTeamMax)) return;
+        if (kDuoOnly && (K > 2 || !E::kCand || a.cand == nullptr)) return;
+        // (budgeted launches: an instance that ran out of rounds leaves K to the NEXT launch's instance of the right role)
+        if (!kBlockOnly && !kTeamOnly && a.round_budget > 0 && K > 2 && E::kCand && a.cand != nullptr) return;
+        const int K0 = K;
+        const long long nits0 = nits;
+        for (int n = t; n < kTailMax; n += kThreads) {
+            sU[n] = (n < K) ? a.U[n] : -1;
+            sStart[n] = (n < K) ? a.row_ptr[sU[n]] : 0;
         }
-    const double eps = (double)a.eps;
-    TailStats st;
-    st.edges = st.miss_edges = st.builds = 0ull;
-    st.bids = st.misses = st.bad_hi = 0u;
-    st.err = 0;
-    st.hint = 0.0;
-    if (t == 0) sMissCnt = 0;
-    __syncthreads();
-
-    // per-mode accounting (always on: two s_memrealtime reads per mode entry, 100 MHz ticks), Ctl::dbg:
-    //   [0..2] rounds in chain + solo / team / block mode, [3..5] ticks
-    unsigned long long md[6] = {0, 0, 0, 0, 0, 0};
-#ifdef MISSLAP_TAIL_STAMP_BLOCK
-    unsigned long long bacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#endif
-    auto mode_begin = [&](int m) {
-        md[3 + m] -= __builtin_amdgcn_s_memrealtime();
-        md[m] -= (unsigned long long)nits;
-    };
-    auto mode_end = [&](int m) {
-        md[3 + m] += __builtin_amdgcn_s_memrealtime();
-        md[m] += (unsigned long long)nits;
-    };
-    auto flush_stats = [&]() {  // a wavefront's statistics, once, when it leaves the kernel
-        if (lane == 0) {
-            if (st.bids) {
-                const unsigned long long hits = (unsigned long long)(st.bids - st.misses), hit_edges = st.edges - st.miss_edges;
-                atomicAdd(&ctl->edges, st.edges);
-                atomicAdd(&ctl->tail_edges, st.edges);
-                atomicAdd(&ctl->bids, (unsigned long long)st.bids);
-                if (hits) {
-                    atomicAdd(&ctl->cand_hits, hits);
-                    atomicAdd(&ctl->cand_edges, hit_edges);
-                }
-                atomicAdd(&ctl->dbg[12], (unsigned long long)st.bids);  // the tail's own totals: bids, line hits, line builds
-                atomicAdd(&ctl->dbg[13], hits);
-                atomicAdd(&ctl->dbg[14], st.builds);
-                atomicAdd(&ctl->dbg[15], hit_edges);
-            }
-            if (bad_hi_is_error(st.bad_hi)) st.err |= kErrNegativeBid;
-            if (st.err) atomicOr(&ctl->err, st.err);
-        }
-    };
-    for (;;) {
-        if (kBlockOnly && K <= kTeamMax) break;  // the next kernel takes over
-        if (kDuoOnly) {
-            // ---- K <= 2, lines: wavefront 0 alone, pair rounds while two bidders are left, then the chain
-            mode_begin(0);
-            tail_pair_mode(a, ed, sU, sStart, K, nits, max_iter, eps, st);
-            mode_end(0);
-            break;  // K == 0 or nits == max_iter
-        }
-        if (kTeamOnly) {
-            if (K > 2 && nits < max_iter) {
-                mode_begin(1);
-                if (tail_team1_pipe(a, ed, sU, sStart, K, nits, max_iter, eps, st)) {  // (this wavefront's slot fell away)
-                    flush_stats();
-                    return;
-                }
-                mode_end(1);
-            }
-            break;
-        }
-        if (!kBlockOnly && K <= 2) {
-            // ---- solo mode: wavefront 0 runs the rest of the phase alone, see tail_solo_mode
-            if (wave == 0) {
-                mode_begin(0);
-                tail_solo_mode(a, ed, sU, sStart, K, nits, max_iter, eps, st);
-                mode_end(0);
-                if (lane == 0) {
-                    sK = K;
-                    sNits = nits;
-                }
-            }
-            __syncthreads();
-            K = sK;
-            nits = sNits;
-            break;  // K == 0 or nits == max_iter
-        }
-        if (!kBlockOnly && K <= kTeamMax) {
-            // ---- team mode: every wavefront, until K <= 2 (or max_iter), see tail_team_mode
-            mode_begin(1);
-            tail_team_mode(a, ed, sU, sStart, K, nits, max_iter, eps, st);
-            mode_end(1);
-            if (K == 0 || nits >= max_iter) break;
-            continue;
-        }
-        // ---- block mode, BID in two passes.  Pass A: the lines, two list slots per wavefront (one per 32-lane
-        // half, one gather serves both); a hit goes straight to LDS, a miss is queued.  Pass B: the queued persons,
-        // one wavefront each, by a full scan of their rows (+ line rebuild).
-        mode_begin(2);
-#ifdef MISSLAP_TAIL_STAMP_BLOCK
-        // diagnostic build: cycles of wavefront 0 per segment of a block round -> Ctl::dbg[6..11]: [6] lines landed,
-        // [7] records landed, [8] evaluated + barrier, [9] scan pass + barrier, [10] resolve / assign / compaction,
-        // [11] closing barrier
-        unsigned long long sprev_b = __builtin_amdgcn_s_memtime();
-        const CycleStamp bstamp{bacc, &sprev_b, wave == 0};
-#else
-        const NoStamp bstamp;
-#endif
-        {
-            const RecSource src{a.rec};
-            // kBlockDepth sweeps of 2 * nwaves slots are in flight together: all their lines are requested first,
-            // then all record gathers are issued (each as its line lands), then they are evaluated one after the
-            // other -- the two memory latencies are paid once per group of sweeps, not once per sweep
-            // (sixteen wavefronts -- four per SIMD -- hide the two latencies by themselves: measured per block round
-            // 3.51 us with one sweep in flight, 3.69 with two, 3.96 with three, 4.06 with four)
-            constexpr int kBlockDepth = kBlockOnly ? 1 : 3;
-            for (int base = 0; base < K; base += kBlockDepth * 2 * nwaves) {
-                typename E::Slot sl[kBlockDepth];
-                PriceRec rr[kBlockDepth];
-#pragma unroll
-                for (int c = 0; c < kBlockDepth; ++c) {
-                    const int nme = base + c * 2 * nwaves + 2 * wave + (lane >> 5);
-                    const int pme = nme < K ? sU[min(nme, kTailMax - 1)] : -1;
-                    sl[c] = cand_no_line<typename E::Slot>();
-                    if (E::kCand && a.cand != nullptr) sl[c] = line_of<E>(a, pme, lane & (kCandLanes - 1));
-                }
-                bstamp(1);
-#pragma unroll
-                for (int c = 0; c < kBlockDepth; ++c) {
-                    const int n0 = base + c * 2 * nwaves + 2 * wave;
-                    if (E::kCand) rr[c] = cand_gather2(sl[c], n0 < K, n0 + 1 < K, src);
-                }
-                bstamp(2);
-#pragma unroll
-                for (int c = 0; c < kBlockDepth; ++c) {
-                    const int n0 = base + c * 2 * nwaves + 2 * wave;
-                    if (n0 >= K) continue;  // wave-uniform
-                    CandBid b[2];
-                    b[0].hit = b[1].hit = false;
-                    if (E::kCand) cand_eval2_r(sl[c], rr[c], n0 < K, n0 + 1 < K, eps, b, st.err, NoEarly());
-#pragma unroll
-                    for (int X = 0; X < 2; ++X) {
-                        const int n = n0 + X;
-                        if (n >= K) continue;  // wave-uniform
-                        if (b[X].hit) {
-                            if (lane == 0) {
-                                sKey[n] = b[X].key;
-                                sObj[n] = b[X].obj;
-                                // owner at the start of the round == what the assignment phase reads (:401): the
-                                // record of obj is only rewritten by this round's winner of obj, after every bid
-                                // has been made.
-                                sPrev[n] = b[X].prev;
-                                sPst[n] = b[X].pstart;
-                            }
-                            st.edges += (unsigned long long)b[X].len;
-                            st.bids += 1;
-                        } else if (lane == 0) {
-                            sList[atomicAdd(&sMissCnt, 1)] = n;
-                        }
-                    }
-                }
-            }
-            __syncthreads();
-            bstamp(3);
-            const int nmiss = sMissCnt;
-            for (int m = wave; m < nmiss; m += nwaves) {
-                const int n = __builtin_amdgcn_readfirstlane(sList[m]);
-                const int i = __builtin_amdgcn_readfirstlane(sU[n]);
-                const int s0 = __builtin_amdgcn_readfirstlane(sStart[n]);
-                const typename E::Raw none[4] = {};
-                const int ev = a.row_ptr[i + 1 + lane_zero()];
-                CandBid bm;
-                CandBuildArgs ba;
-                wave_bid_full<E, RecSource, true, false>(ed, src, s0, ev, none, eps, bm, ba, st.err);
-                ba.want = ba.want && a.cand != nullptr;
-                if (lane == 0) {
-                    sKey[n] = bm.key;
-                    sObj[n] = bm.obj;
-                    sPrev[n] = bm.prev;
-                    sPst[n] = bm.pstart;
-                }
-                st.edges += (unsigned long long)bm.len;
-                st.miss_edges += (unsigned long long)bm.len;
-                st.bids += 1;
-                st.misses += 1;
-                if (ba.want) tail_build(a, i, ba, eps, st);
-            }
-        }
-        __syncthreads();
-        bstamp(4);
-
-        if (K <= kWave) {
-            // ---- fast path: the whole rest of the round in wavefront 0, no LDS atomics ------------
-            if (wave == 0) {
-                const bool act = lane < K;
-                const unsigned long long key = act ? sKey[lane] : 0ull;
-                const int obj = act ? sObj[lane] : (-2 - lane);
-                // RESOLVE (:375-385).  Two bidders on one object are the exception: every bidder inserts its object
-                // into the (empty) LDS hash table with one compare-and-swap; only if some insert meets its own object
-                // -- a contested object -- is the all-pairs loop run.  The table is emptied again right away.
-                bool lose = false;
-                int hs = 0;
-                bool dup = false;
-                if (act) {
-                    hs = (int)(((unsigned)obj * 2654435761u) >> 21) & (kHashSize - 1);
-                    for (;;) {
-                        const int old = atomicCAS(&hObj[hs], -1, obj);
-                        if (old == -1) break;
-                        if (old == obj) {
-                            dup = true;
-                            break;
-                        }
-                        hs = (hs + 1) & (kHashSize - 1);
-                    }
-                }
-                const bool contested = __any(dup);
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                if (act && !dup) hObj[hs] = -1;
-                if (contested) {
-                    for (int m = 0; m < K; ++m) {  // all pairs via readlane
-                        const int om = __builtin_amdgcn_readlane(obj, m);
-                        const bool same = (om == obj) && (m != lane);
-                        if (__any(same)) {  // wave-uniform
-                            const unsigned long long km = readlane_u64(key, m);
-                            lose |= same && (km > key || (km == key && m < lane));
-                        }
-                    }
-                }
-                int u = act ? sU[lane] : -1;
-                int sx = act ? sStart[lane] : 0;  // row start travelling with the slot's person
-                if (act && !lose) {
-                    u = apply_winner(a, u, sx, obj, sPrev[lane], key);
-                    sx = sPst[lane];
-                }
-                // push_all_left with ballots
-                const unsigned long long kmask = (K >= 64) ? ~0ull : ((1ull << K) - 1ull);
-                const unsigned long long holes = __ballot(act && u == -1) & kmask;
-                const int Kn = K - __popcll(holes);
-                const unsigned long long lmask = (Kn >= 64) ? ~0ull : ((1ull << Kn) - 1ull);
-                const unsigned long long hl = holes & lmask;            // empty slots left of K'
-                if (hl == 0ull) {  // wave-uniform: nothing to move (no hole, or only holes at the end)
-                    if (act) {
-                        sU[lane] = (lane < Kn) ? u : -1;
-                        sStart[lane] = sx;
-                    }
-                } else {
-                    const unsigned long long mv = ~holes & ~lmask & kmask;  // persons right of K'
-                    const bool is_hl = (hl >> lane) & 1ull, is_mv = (mv >> lane) & 1ull;
-                    if (is_hl) sList[__popcll(hl & lanemask_lt())] = lane;
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                    if (is_mv) {
-                        const int dst = sList[__popcll(mv & lanemask_lt())];
-                        sU[dst] = u;
-                        sStart[dst] = sx;
-                    }
-                    if (act) {
-                        if (lane >= Kn) sU[lane] = -1;
-                        else if (!is_hl) {
-                            sU[lane] = u;
-                            sStart[lane] = sx;
-                        }
-                    }
-                }
-                if (lane == 0) {
-                    sK = Kn;
-                    sMissCnt = 0;
-                }
-            }
-        } else {
-            // ---- general path (64 < K <= 512): LDS hash table keyed by object ---------------------
-            const bool act = t < K;
-            unsigned long long key = 0ull;
-            int obj = -1, h = 0;
-            if (act) {
-                key = sKey[t];
-                obj = sObj[t];
-                h = (int)(((unsigned)obj * 2654435761u) >> 21) & (kHashSize - 1);
-                for (;;) {
-                    const int old = atomicCAS(&hObj[h], -1, obj);
-                    if (old == -1 || old == obj) break;
-                    h = (h + 1) & (kHashSize - 1);
-                }
-                atomicMax(&hKey[h], key);
-            }
-            __syncthreads();
-            if (act && hKey[h] == key) atomicMin(&hPos[h], t);
-            __syncthreads();
-            const bool win = act && hPos[h] == t;
-            __syncthreads();
-            if (act) {  // several threads may clear one slot: identical values
+        if (!kDuoOnly)
+            for (int h = t; h < kHashSize; h += kThreads) {
                 hObj[h] = -1;
                 hKey[h] = 0ull;
                 hPos[h] = kPosNone;
             }
-            int u = act ? sU[t] : -1;
-            int sx = act ? sStart[t] : 0;
-            if (win) {
-                u = apply_winner(a, u, sx, obj, sPrev[t], key);
-                sx = sPst[t];
-            }
-            const bool hole = act && u == -1;
-            const unsigned long long bh = __ballot(hole);
-            if (lane == 0) sCnt[0][wave] = __popcll(bh);
-            __syncthreads();
-            int total = 0;
-            for (int w2 = 0; w2 < nwaves; ++w2) total += sCnt[0][w2];
-            const int Kn = K - total;
-            const bool is_hl = hole && t < Kn;
-            const bool is_mv = act && !hole && t >= Kn;
-            const unsigned long long bl = __ballot(is_hl), bm = __ballot(is_mv);
+        const double eps = (double)a.eps;
+        TailStats st;
+        st.edges = st.miss_edges = st.builds = 0ull;
+        st.bids = st.misses = st.bad_hi = 0u;
+        st.err = 0;
+        st.hint = 0.0;
+        if (t == 0) sMissCnt = 0;
+        __syncthreads();
+
+        // per-mode accounting (always on: two s_memrealtime reads per mode entry, 100 MHz ticks), Ctl::dbg:
+        //   [0..2] rounds in chain + solo / team / block mode, [3..5] ticks
+        unsigned long long md[6] = {0, 0, 0, 0, 0, 0};
+#ifdef MISSLAP_TAIL_STAMP_BLOCK
+        unsigned long long bacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#endif
+        auto mode_begin = [&](int m) {
+            md[3 + m] -= __builtin_amdgcn_s_memrealtime();
+            md[m] -= (unsigned long long)nits;
+        };
+        auto mode_end = [&](int m) {
+            md[3 + m] += __builtin_amdgcn_s_memrealtime();
+            md[m] += (unsigned long long)nits;
+        };
+        auto flush_stats = [&]() {  // a wavefront's statistics, once, when it leaves the kernel
             if (lane == 0) {
-                sCnt[1][wave] = __popcll(bl);
-                sCnt[2][wave] = __popcll(bm);
+                if (st.bids) {
+                    const unsigned long long hits = (unsigned long long)(st.bids - st.misses), hit_edges = st.edges - st.miss_edges;
+                    atomicAdd(&ctl->edges, st.edges);
+                    atomicAdd(&ctl->tail_edges, st.edges);
+                    atomicAdd(&ctl->bids, (unsigned long long)st.bids);
+                    if (hits) {
+                        atomicAdd(&ctl->cand_hits, hits);
+                        atomicAdd(&ctl->cand_edges, hit_edges);
+                    }
+                    atomicAdd(&ctl->dbg[12], (unsigned long long)st.bids);  // the tail's own totals: bids, line hits, line builds
+                    atomicAdd(&ctl->dbg[13], hits);
+                    atomicAdd(&ctl->dbg[14], st.builds);
+                    atomicAdd(&ctl->dbg[15], hit_edges);
+                }
+                if (bad_hi_is_error(st.bad_hi)) st.err |= kErrNegativeBid;
+                if (st.err) atomicOr(&ctl->err, st.err);
             }
-            __syncthreads();
-            int pl = __popcll(bl & lanemask_lt()), pm = __popcll(bm & lanemask_lt());
-            for (int w2 = 0; w2 < wave; ++w2) {
-                pl += sCnt[1][w2];
-                pm += sCnt[2][w2];
+        };
+        for (;;) {
+            if (kBlockOnly && K <= kTeamMax) break;  // the next kernel takes over
+            if (kDuoOnly) {
+                // ---- K <= 2, lines: wavefront 0 alone, pair rounds while two bidders are left, then the chain
+                mode_begin(0);
+                tail_pair_mode(a, ed, sU, sStart, K, nits, max_iter, eps, st);
+                mode_end(0);
+                break;  // K == 0 or nits == max_iter
             }
-            if (is_hl) sList[pl] = t;
-            __syncthreads();
-            if (is_mv) {
-                sU[sList[pm]] = u;
-                sStart[sList[pm]] = sx;
+            if (kTeamOnly) {
+                if (K > 2 && nits < max_iter) {
+                    mode_begin(1);
+                    if (tail_team1_pipe(a, ed, sU, sStart, K, nits, max_iter, eps, st)) {  // (this wavefront's slot fell away)
+                        flush_stats();
+                        return;
+                    }
+                    mode_end(1);
+                }
+                break;
             }
-            if (act) {
-                if (t >= Kn) sU[t] = -1;
-                else if (!is_hl) {
-                    sU[t] = u;
-                    sStart[t] = sx;
+            if (!kBlockOnly && K <= 2) {
+                // ---- solo mode: wavefront 0 runs the rest of the phase alone, see tail_solo_mode
+                if (wave == 0) {
+                    mode_begin(0);
+                    tail_solo_mode(a, ed, sU, sStart, K, nits, max_iter, eps, st);
+                    mode_end(0);
+                    if (lane == 0) {
+                        sK = K;
+                        sNits = nits;
+                    }
+                }
+                __syncthreads();
+                K = sK;
+                nits = sNits;
+                break;  // K == 0 or nits == max_iter
+            }
+            if (!kBlockOnly && K <= kTeamMax) {
+                // ---- team mode: every wavefront, until K <= 2 (or max_iter), see tail_team_mode
+                mode_begin(1);
+                tail_team_mode(a, ed, sU, sStart, K, nits, max_iter, eps, st);
+                mode_end(1);
+                if (K == 0 || nits >= max_iter) break;
+                continue;
+            }
+            // ---- block mode, BID in two passes.  Pass A: the lines, two list slots per wavefront (one per 32-lane
+            // half, one gather serves both); a hit goes straight to LDS, a miss is queued.  Pass B: the queued persons,
+            // one wavefront each, by a full scan of their rows (+ line rebuild).
+            mode_begin(2);
+#ifdef MISSLAP_TAIL_STAMP_BLOCK
+            // diagnostic build: cycles of wavefront 0 per segment of a block round -> Ctl::dbg[6..11]: [6] lines landed,
+            // [7] records landed, [8] evaluated + barrier, [9] scan pass + barrier, [10] resolve / assign / compaction,
+            // [11] closing barrier
+            unsigned long long sprev_b = __builtin_amdgcn_s_memtime();
+            const CycleStamp bstamp{bacc, &sprev_b, wave == 0};
+#else
+            const NoStamp bstamp;
+#endif
+            {
+                const RecSource src{a.rec};
+                // kBlockDepth sweeps of 2 * nwaves slots are in flight together: all their lines are requested first,
+                // then all record gathers are issued (each as its line lands), then they are evaluated one after the
+                // other -- the two memory latencies are paid once per group of sweeps, not once per sweep
+                // (sixteen wavefronts -- four per SIMD -- hide the two latencies by themselves: measured per block round
+                // 3.51 us with one sweep in flight, 3.69 with two, 3.96 with three, 4.06 with four)
+                constexpr int kBlockDepth = kBlockOnly ? 1 : 3;
+                for (int base = 0; base < K; base += kBlockDepth * 2 * nwaves) {
+                    typename E::Slot sl[kBlockDepth];
+                    PriceRec rr[kBlockDepth];
+#pragma unroll
+                    for (int c = 0; c < kBlockDepth; ++c) {
+                        const int nme = base + c * 2 * nwaves + 2 * wave + (lane >> 5);
+                        const int pme = nme < K ? sU[min(nme, kTailMax - 1)] : -1;
+                        sl[c] = cand_no_line<typename E::Slot>();
+                        if (E::kCand && a.cand != nullptr) sl[c] = line_of<E>(a, pme, lane & (kCandLanes - 1));
+                    }
+                    bstamp(1);
+#pragma unroll
+                    for (int c = 0; c < kBlockDepth; ++c) {
+                        const int n0 = base + c * 2 * nwaves + 2 * wave;
+                        if (E::kCand) rr[c] = cand_gather2(sl[c], n0 < K, n0 + 1 < K, src);
+                    }
+                    bstamp(2);
+#pragma unroll
+                    for (int c = 0; c < kBlockDepth; ++c) {
+                        const int n0 = base + c * 2 * nwaves + 2 * wave;
+                        if (n0 >= K) continue;  // wave-uniform
+                        CandBid b[2];
+                        b[0].hit = b[1].hit = false;
+                        if (E::kCand) cand_eval2_r(sl[c], rr[c], n0 < K, n0 + 1 < K, eps, b, st.err, NoEarly());
+#pragma unroll
+                        for (int X = 0; X < 2; ++X) {
+                            const int n = n0 + X;
+                            if (n >= K) continue;  // wave-uniform
+                            if (b[X].hit) {
+                                if (lane == 0) {
+                                    sKey[n] = b[X].key;
+                                    sObj[n] = b[X].obj;
+                                    // owner at the start of the round == what the assignment phase reads (:401): the
+                                    // record of obj is only rewritten by this round's winner of obj, after every bid
+                                    // has been made.
+                                    sPrev[n] = b[X].prev;
+                                    sPst[n] = b[X].pstart;
+                                }
+                                st.edges += (unsigned long long)b[X].len;
+                                st.bids += 1;
+                            } else if (lane == 0) {
+                                sList[atomicAdd(&sMissCnt, 1)] = n;
+                            }
+                        }
+                    }
+                }
+                __syncthreads();
+                bstamp(3);
+                const int nmiss = sMissCnt;
+                for (int m = wave; m < nmiss; m += nwaves) {
+                    const int n = __builtin_amdgcn_readfirstlane(sList[m]);
+                    const int i = __builtin_amdgcn_readfirstlane(sU[n]);
+                    const int s0 = __builtin_amdgcn_readfirstlane(sStart[n]);
+                    const typename E::Raw none[4] = {};
+                    const int ev = a.row_ptr[i + 1 + lane_zero()];
+                    CandBid bm;
+                    CandBuildArgs ba;
+                    wave_bid_full<E, RecSource, true, false>(ed, src, s0, ev, none, eps, bm, ba, st.err);
+                    ba.want = ba.want && a.cand != nullptr;
+                    if (lane == 0) {
+                        sKey[n] = bm.key;
+                        sObj[n] = bm.obj;
+                        sPrev[n] = bm.prev;
+                        sPst[n] = bm.pstart;
+                    }
+                    st.edges += (unsigned long long)bm.len;
+                    st.miss_edges += (unsigned long long)bm.len;
+                    st.bids += 1;
+                    st.misses += 1;
+                    if (ba.want) tail_build(a, i, ba, eps, st);
                 }
             }
-            if (t == 0) {
-                sK = Kn;
-                sMissCnt = 0;
+            __syncthreads();
+            bstamp(4);
+
+            if (K <= kWave) {
+                // ---- fast path: the whole rest of the round in wavefront 0, no LDS atomics ------------
+                if (wave == 0) {
+                    const bool act = lane < K;
+                    const unsigned long long key = act ? sKey[lane] : 0ull;
+                    const int obj = act ? sObj[lane] : (-2 - lane);
+                    // RESOLVE (:375-385).  Two bidders on one object are the exception: every bidder inserts its object
+                    // into the (empty) LDS hash table with one compare-and-swap; only if some insert meets its own object
+                    // -- a contested object -- is the all-pairs loop run.  The table is emptied again right away.
+                    bool lose = false;
+                    int hs = 0;
+                    bool dup = false;
+                    if (act) {
+                        hs = (int)(((unsigned)obj * 2654435761u) >> 21) & (kHashSize - 1);
+                        for (;;) {
+                            const int old = atomicCAS(&hObj[hs], -1, obj);
+                            if (old == -1) break;
+                            if (old == obj) {
+                                dup = true;
+                                break;
+                            }
+                            hs = (hs + 1) & (kHashSize - 1);
+                        }
+                    }
+                    const bool contested = __any(dup);
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                    __builtin_amdgcn_wave_barrier();
+                    if (act && !dup) hObj[hs] = -1;
+                    if (contested) {
+                        for (int m = 0; m < K; ++m) {  // all pairs via readlane
+                            const int om = __builtin_amdgcn_readlane(obj, m);
+                            const bool same = (om == obj) && (m != lane);
+                            if (__any(same)) {  // wave-uniform
+                                const unsigned long long km = readlane_u64(key, m);
+                                lose |= same && (km > key || (km == key && m < lane));
+                            }
+                        }
+                    }
+                    int u = act ? sU[lane] : -1;
+                    int sx = act ? sStart[lane] : 0;  // row start travelling with the slot's person
+                    if (act && !lose) {
+                        u = apply_winner(a, u, sx, obj, sPrev[lane], key);
+                        sx = sPst[lane];
+                    }
+                    // push_all_left with ballots
+                    const unsigned long long kmask = (K >= 64) ? ~0ull : ((1ull << K) - 1ull);
+                    const unsigned long long holes = __ballot(act && u == -1) & kmask;
+                    const int Kn = K - __popcll(holes);
+                    const unsigned long long lmask = (Kn >= 64) ? ~0ull : ((1ull << Kn) - 1ull);
+                    const unsigned long long hl = holes & lmask;            // empty slots left of K'
+                    if (hl == 0ull) {  // wave-uniform: nothing to move (no hole, or only holes at the end)
+                        if (act) {
+                            sU[lane] = (lane < Kn) ? u : -1;
+                            sStart[lane] = sx;
+                        }
+                    } else {
+                        const unsigned long long mv = ~holes & ~lmask & kmask;  // persons right of K'
+                        const bool is_hl = (hl >> lane) & 1ull, is_mv = (mv >> lane) & 1ull;
+                        if (is_hl) sList[__popcll(hl & lanemask_lt())] = lane;
+                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                        __builtin_amdgcn_wave_barrier();
+                        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                        if (is_mv) {
+                            const int dst = sList[__popcll(mv & lanemask_lt())];
+                            sU[dst] = u;
+                            sStart[dst] = sx;
+                        }
+                        if (act) {
+                            if (lane >= Kn) sU[lane] = -1;
+                            else if (!is_hl) {
+                                sU[lane] = u;
+                                sStart[lane] = sx;
+                            }
+                        }
+                    }
+                    if (lane == 0) {
+                        sK = Kn;
+                        sMissCnt = 0;
+                    }
+                }
+            } else {
+                // ---- general path (64 < K <= 512): LDS hash table keyed by object ---------------------
+                const bool act = t < K;
+                unsigned long long key = 0ull;
+                int obj = -1, h = 0;
+                if (act) {
+                    key = sKey[t];
+                    obj = sObj[t];
+                    h = (int)(((unsigned)obj * 2654435761u) >> 21) & (kHashSize - 1);
+                    for (;;) {
+                        const int old = atomicCAS(&hObj[h], -1, obj);
+                        if (old == -1 || old == obj) break;
+                        h = (h + 1) & (kHashSize - 1);
+                    }
+                    atomicMax(&hKey[h], key);
+                }
+                __syncthreads();
+                if (act && hKey[h] == key) atomicMin(&hPos[h], t);
+                __syncthreads();
+                const bool win = act && hPos[h] == t;
+                __syncthreads();
+                if (act) {  // several threads may clear one slot: identical values
+                    hObj[h] = -1;
+                    hKey[h] = 0ull;
+                    hPos[h] = kPosNone;
+                }
+                int u = act ? sU[t] : -1;
+                int sx = act ? sStart[t] : 0;
+                if (win) {
+                    u = apply_winner(a, u, sx, obj, sPrev[t], key);
+                    sx = sPst[t];
+                }
+                const bool hole = act && u == -1;
+                const unsigned long long bh = __ballot(hole);
+                if (lane == 0) sCnt[0][wave] = __popcll(bh);
+                __syncthreads();
+                int total = 0;
+                for (int w2 = 0; w2 < nwaves; ++w2) total += sCnt[0][w2];
+                const int Kn = K - total;
+                const bool is_hl = hole && t < Kn;
+                const bool is_mv = act && !hole && t >= Kn;
+                const unsigned long long bl = __ballot(is_hl), bm = __ballot(is_mv);
+                if (lane == 0) {
+                    sCnt[1][wave] = __popcll(bl);
+                    sCnt[2][wave] = __popcll(bm);
+                }
+                __syncthreads();
+                int pl = __popcll(bl & lanemask_lt()), pm = __popcll(bm & lanemask_lt());
+                for (int w2 = 0; w2 < wave; ++w2) {
+                    pl += sCnt[1][w2];
+                    pm += sCnt[2][w2];
+                }
+                if (is_hl) sList[pl] = t;
+                __syncthreads();
+                if (is_mv) {
+                    sU[sList[pm]] = u;
+                    sStart[sList[pm]] = sx;
+                }
+                if (act) {
+                    if (t >= Kn) sU[t] = -1;
+                    else if (!is_hl) {
+                        sU[t] = u;
+                        sStart[t] = sx;
+                    }
+                }
+                if (t == 0) {
+                    sK = Kn;
+                    sMissCnt = 0;
+                }
             }
+            bstamp(5);
+            __syncthreads();
+            bstamp(6);
+            K = sK;
+            nits += 1;
+            mode_end(2);
+            if (K == 0 || nits >= max_iter) break;
         }
-        bstamp(5);
-        __syncthreads();
-        bstamp(6);
-        K = sK;
-        nits += 1;
-        mode_end(2);
-        if (K == 0 || nits >= max_iter) break;
-    }
-    if (t == 0)
-        for (int k = 0; k < 6; ++k) ctl->dbg[k] += md[k];
+        if (t == 0)
+            for (int k = 0; k < 6; ++k) ctl->dbg[k] += md[k];
 #ifdef MISSLAP_TAIL_STAMP_BLOCK
-    if (t == 0)
-        for (int k = 1; k <= 6; ++k) ctl->dbg[5 + k] += bacc[k];
+        if (t == 0)
+            for (int k = 1; k <= 6; ++k) ctl->dbg[5 + k] += bacc[k];
 #endif
 
-    for (int n = t; n < K0; n += kThreads) a.U[n] = sU[n];
-    flush_stats();
-    if (t == 0) {
-        ctl->K = K;
-        ctl->nits = nits;
-        ctl->tail_rounds += nits - nits0;
+        for (int n = t; n < K0; n += kThreads) a.U[n] = sU[n];
+        flush_stats();
+        if (t == 0) {
+            ctl->K = K;
+            ctl->nits = nits;
+            ctl->tail_rounds += nits - nits0;
+        }
     }
-}
-template <class E, int kThreads, bool kTeamOnly = false>
-__global__ __launch_bounds__(kThreads) void k_tail(TailArgs a, E ed) { k_tail_body<E, kThreads, kTeamOnly>(a, ed); }
-template <class E, int kThreads, bool kTeamOnly>
-struct F_k_tail {  // (the body as a callable: what a batched launch runs per problem, csrc/host_batch.hpp)
-    static __device__ __forceinline__ void run(TailArgs a, E ed) { k_tail_body<E, kThreads, kTeamOnly>(a, ed); }
 };
 
 

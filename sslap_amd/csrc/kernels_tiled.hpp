@@ -357,73 +357,67 @@ __global__ __launch_bounds__(256) void k_tile_scatter(E ed, const int *row_ptr, 
 // chunks in front of theirs themselves (at most a few hundred) instead of waiting for a scan launch.
 // (thr / min_K: the scan these kernels prepare runs only in a live round with K >= min_K -- otherwise nothing to do)
 __device__ __forceinline__ bool order_needed(const Ctl *ctl, int thr, int min_K) { return round_live(ctl, thr) && ctl->K >= min_K; }
-__device__ __forceinline__ void k_order_prepare_body(const Ctl *ctl, const int *U, int *pos_of, const int *p2o, int n_rows,
-                                                        int nchunks, int *sums, int thr, int min_K) {
-    if (!order_needed(ctl, thr, min_K)) return;
-    const int K = ctl->K;
-    for (int n = blockIdx.x * blockDim.x + threadIdx.x; n < K; n += gridDim.x * blockDim.x) pos_of[U[n]] = n;
-    if ((int)blockIdx.x >= nchunks) return;  // (uniform over the workgroup; the grid covers the list AND the chunks)
-    __shared__ int s_w[16];
-    const int base = blockIdx.x * kScanChunk;
-    int v = 0;
-    for (int q = 0; q < 4; ++q) {
-        const int k = base + q * 1024 + threadIdx.x;
-        v += (k < n_rows && p2o[k] == -1);
+struct k_order_prepare {
+    MISSLAP_KERNEL(1024)
+    static __device__ __forceinline__ void run(const Ctl *ctl, const int *U, int *pos_of, const int *p2o, int n_rows, int nchunks, int *sums, int thr, int min_K) {
+        if (!order_needed(ctl, thr, min_K)) return;
+        const int K = ctl->K;
+        for (int n = blockIdx.x * blockDim.x + threadIdx.x; n < K; n += gridDim.x * blockDim.x) pos_of[U[n]] = n;
+        if ((int)blockIdx.x >= nchunks) return;  // (uniform over the workgroup; the grid covers the list AND the chunks)
+        __shared__ int s_w[16];
+        const int base = blockIdx.x * kScanChunk;
+        int v = 0;
+        for (int q = 0; q < 4; ++q) {
+            const int k = base + q * 1024 + threadIdx.x;
+            v += (k < n_rows && p2o[k] == -1);
+        }
+        for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+        if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = v;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            int t = 0;
+            for (int w = 0; w < 16; ++w) t += s_w[w];
+            sums[blockIdx.x] = t;
+        }
     }
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int t = 0;
-        for (int w = 0; w < 16; ++w) t += s_w[w];
-        sums[blockIdx.x] = t;
-    }
-}
-__global__ __launch_bounds__(1024) void k_order_prepare(const Ctl *ctl, const int *U, int *pos_of, const int *p2o, int n_rows,
-                                                        int nchunks, int *sums, int thr, int min_K) { k_order_prepare_body(ctl, U, pos_of, p2o, n_rows, nchunks, sums, thr, min_K); }
-struct F_k_order_prepare {  // (the body as a callable: what a batched launch runs per problem, csrc/host_batch.hpp)
-    static __device__ __forceinline__ void run(const Ctl *ctl, const int *U, int *pos_of, const int *p2o, int n_rows, int nchunks, int *sums, int thr, int min_K) { k_order_prepare_body(ctl, U, pos_of, p2o, n_rows, nchunks, sums, thr, min_K); }
 };
 
-__device__ __forceinline__ void k_order_scatter_body(const Ctl *ctl, const int *p2o, int n_rows, const int *sums, const int *pos_of,
-                                                        int *order_person, int *order_pos, int thr, int min_K) {
-    if (!order_needed(ctl, thr, min_K)) return;
-    __shared__ int s_w[16];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    // unassigned persons in the chunks before this one: the chunk counts of k_order_prepare, added up here
-    int carry = 0;
-    {
-        int v = 0;
-        for (int b = t; b < (int)blockIdx.x; b += 1024) v += sums[b];
-        for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-        if (lane == 0) s_w[wave] = v;
-        __syncthreads();
-        for (int w = 0; w < 16; ++w) carry += s_w[w];
-    }
-    for (int q = 0; q < 4; ++q) {
-        const int i = blockIdx.x * kScanChunk + q * 1024 + t;
-        const bool un = i < n_rows && p2o[i] == -1;
-        const unsigned long long b = __ballot(un);
-        __syncthreads();  // s_w of the previous pass is no longer read
-        if (lane == 0) s_w[wave] = __popcll(b);
-        __syncthreads();
-        int wpre = 0, tot = 0;
-        for (int w2 = 0; w2 < 16; ++w2) {
-            if (w2 < wave) wpre += s_w[w2];
-            tot += s_w[w2];
+struct k_order_scatter {
+    MISSLAP_KERNEL(1024)
+    static __device__ __forceinline__ void run(const Ctl *ctl, const int *p2o, int n_rows, const int *sums, const int *pos_of, int *order_person, int *order_pos, int thr, int min_K) {
+        if (!order_needed(ctl, thr, min_K)) return;
+        __shared__ int s_w[16];
+        const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+        // unassigned persons in the chunks before this one: the chunk counts of k_order_prepare, added up here
+        int carry = 0;
+        {
+            int v = 0;
+            for (int b = t; b < (int)blockIdx.x; b += 1024) v += sums[b];
+            for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+            if (lane == 0) s_w[wave] = v;
+            __syncthreads();
+            for (int w = 0; w < 16; ++w) carry += s_w[w];
         }
-        if (un) {
-            const int r = carry + wpre + __popcll(b & lanemask_lt());
-            order_person[r] = i;
-            order_pos[r] = pos_of[i];
+        for (int q = 0; q < 4; ++q) {
+            const int i = blockIdx.x * kScanChunk + q * 1024 + t;
+            const bool un = i < n_rows && p2o[i] == -1;
+            const unsigned long long b = __ballot(un);
+            __syncthreads();  // s_w of the previous pass is no longer read
+            if (lane == 0) s_w[wave] = __popcll(b);
+            __syncthreads();
+            int wpre = 0, tot = 0;
+            for (int w2 = 0; w2 < 16; ++w2) {
+                if (w2 < wave) wpre += s_w[w2];
+                tot += s_w[w2];
+            }
+            if (un) {
+                const int r = carry + wpre + __popcll(b & lanemask_lt());
+                order_person[r] = i;
+                order_pos[r] = pos_of[i];
+            }
+            carry += tot;
         }
-        carry += tot;
     }
-}
-__global__ __launch_bounds__(1024) void k_order_scatter(const Ctl *ctl, const int *p2o, int n_rows, const int *sums, const int *pos_of,
-                                                        int *order_person, int *order_pos, int thr, int min_K) { k_order_scatter_body(ctl, p2o, n_rows, sums, pos_of, order_person, order_pos, thr, min_K); }
-struct F_k_order_scatter {  // (the body as a callable: what a batched launch runs per problem, csrc/host_batch.hpp)
-    static __device__ __forceinline__ void run(const Ctl *ctl, const int *p2o, int n_rows, const int *sums, const int *pos_of, int *order_person, int *order_pos, int thr, int min_K) { k_order_scatter_body(ctl, p2o, n_rows, sums, pos_of, order_person, order_pos, thr, min_K); }
 };
 
 

@@ -1475,6 +1475,9 @@ _BATCH_CASES = [
     ("no_lines", dict(kind="sparse", n=3000, m=3000, density=0.01), "max", 5, 0, dict(cand=False)),
     ("one_problem", dict(kind="sparse", n=2000, m=2000, density=0.01), "max", 1, 0, dict()),
     ("many_groups", dict(kind="sparse", n=1500, m=1500, density=0.02), "max", 40, 6, dict()),
+    # one group of more problems than a kernel-argument block carries (at most 16): every merged launch goes through
+    # the device ring of arguments (k_batched_ptr)
+    ("device_ring", dict(kind="sparse", n=300, m=300, density=0.05, ints=4), "max", 20, 20, dict()),
 ]
 
 
