@@ -31,7 +31,8 @@ extern "C" {
  *   2  the knobs are named fields, misslap_meta starts with `struct_size` (the library writes min(struct_size,
  *      sizeof) bytes: a caller built against a shorter version-2 header keeps working when fields are appended),
  *      validity flags of the assignment, misslap_trim_caches.  Additions since: the warm-start entry points,
- *      misslap_solve_dense_batch, misslap_solve_sparse_batch. */
+ *      misslap_solve_dense_batch, misslap_solve_sparse_batch, misslap_solve_dense_batch_status,
+ *      misslap_dense_batch_workspace_bytes. */
 
 #define MISSLAP_OK 0
 #define MISSLAP_ERR_INVALID 1    /* malformed arguments / input contract violated */
@@ -478,6 +479,61 @@ int misslap_solve_dense_batch(int64_t B, int64_t N, int64_t M, const double *mat
                               const float *eps_start, const double *prices_in, int32_t cardinality_check,
                               const misslap_options *opt, int32_t *sol, double *prices_out, int32_t out_on_device,
                               misslap_dense_batch_meta *meta, misslap_dense_batch_info *info);
+
+/* ---- the dense batch with a verdict per problem instead of all or nothing, and in stream order.
+ * misslap_solve_dense_batch_status takes the stack of misslap_solve_dense_batch and never fails for a reason that belongs
+ * to one problem: status[b] names the first check problem b failed, in misslap_solve_dense_batch's order, and every
+ * problem with status 0 is solved -- sol, prices and meta bit for bit what misslap_solve_dense_batch gives for it.  A
+ * problem with another status takes no part in the solve launch (its workgroup leaves at once): sol[b][:] = -1,
+ * prices_out[b][:] = 0, meta[b] = {n_rows = n_b, n_cols = max valid column + 1, nnz = valid entries, every other
+ * result field 0} (all three 0 for MISSLAP_BATCH_STATUS_BAD_SHAPE).  Hitting max_iter is no error, as before.
+ *   shapes, prices_in, cardinality_check, sol, prices_out   as for misslap_solve_dense_batch.  The guard always runs
+ *                  on the device here (its kernel needs no read-back), also below 64 problems, where one graph on one
+ *                  compute unit is slower than the host matcher.
+ *   fast           != 0: problem b starts at eps = (float)(1.0 / n_b), formed in the kernel (auction_.pyx:568-569);
+ *                  0: opt->eps_start for every problem.
+ *   opt            as for misslap_solve_dense_batch; with a workspace input_on_device must be set and input_stream is
+ *                  not read.
+ *   stream         a hipStream_t; NULL is the null stream.  Only read with a workspace.
+ *   workspace      NULL: the library uploads host arrays, allocates its scratch, works on its own stream and
+ *                  synchronises once, at the end; mat / prices_in follow opt->input_on_device, sol / prices_out / status /
+ *                  matching_size follow out_on_device, shapes and meta are host arrays, and shapes is checked on the host
+ *                  (an entry outside 1 .. N x 1 .. M is MISSLAP_ERR_INVALID, as before).
+ *                  Not NULL: device memory of at least misslap_dense_batch_workspace_bytes(...) bytes, 256-byte aligned.
+ *                  EVERY pointer argument except opt and info is then a device pointer (meta: B records of
+ *                  sizeof(misslap_dense_batch_meta), struct_size not read; out_on_device must be set) and the call is
+ *                  stream-ordered: its three launches go onto `stream`, it allocates and frees nothing, creates no
+ *                  event, waits for nothing, copies nothing, and returns once the launches are enqueued.  The
+ *                  workspace and every argument array belong to the call until the stream has passed it.  A device
+ *                  shapes entry outside 1 .. N x 1 .. M gives MISSLAP_BATCH_STATUS_BAD_SHAPE and nothing of that
+ *                  problem is read: the check pass writes the shapes the later kernels use into the workspace.
+ *   status         int32[B], required.
+ *   matching_size  int32[B] or NULL: the guard's cardinality of problem b (for MISSLAP_BATCH_STATUS_INFEASIBLE: "only
+ *                  involves <matching_size> out of <n_b> rows"); -1 where the guard did not run.
+ *   meta           required with a workspace; else as for misslap_solve_dense_batch.
+ *   info           may be NULL; threads and lds_bytes are set (without a workspace wall_ms too), the other times are 0.
+ * Only what is wrong with the whole call is an error: B, N, M, a NULL mat / sol / status, the options, a workspace that
+ * is too small or misaligned. */
+#define MISSLAP_BATCH_STATUS_OK 0                /* solved */
+#define MISSLAP_BATCH_STATUS_TOO_FEW_VALUES 1    /* fewer valid values than rows */
+#define MISSLAP_BATCH_STATUS_EMPTY_ROW 2         /* a row without a valid entry */
+#define MISSLAP_BATCH_STATUS_INFINITE_VALUE 3    /* a valid entry is +inf */
+#define MISSLAP_BATCH_STATUS_INFEASIBLE 4        /* the matching guard: no assignment of every row (cardinality_check) */
+#define MISSLAP_BATCH_STATUS_PRICE_NOT_FINITE 5  /* starting prices hold a NaN or an infinity */
+#define MISSLAP_BATCH_STATUS_PRICE_NEGATIVE 6    /* starting prices with the sign bit set */
+#define MISSLAP_BATCH_STATUS_BAD_SHAPE 7         /* shape outside 1 .. N x 1 .. M (device shapes only) */
+int misslap_solve_dense_batch_status(int64_t B, int64_t N, int64_t M, const double *mat, const int32_t *shapes,
+                                     int32_t fast, const double *prices_in, int32_t cardinality_check,
+                                     const misslap_options *opt, void *stream, void *workspace, int64_t workspace_bytes,
+                                     int32_t *sol, double *prices_out, int32_t out_on_device, int32_t *status,
+                                     int32_t *matching_size, misslap_dense_batch_meta *meta,
+                                     misslap_dense_batch_info *info);
+/* Bytes of workspace a stream-ordered misslap_solve_dense_batch_status of this size needs (the check records, the
+ * sanitised shapes and, with cardinality_check, the cardinalities); -1 for B < 1 or N, M outside
+ * 1 .. MISSLAP_DENSE_BATCH_MAX_DIM.  Needs no GPU.  has_prices is accepted for the day a layout depends on it: today's
+ * does not. */
+int64_t misslap_dense_batch_workspace_bytes(int64_t B, int64_t N, int64_t M, int32_t has_prices,
+                                            int32_t cardinality_check);
 
 /* ---- many small SPARSE problems in one call: the batch form of _from_sparse(loc, val, size=...) (auction_.pyx:575-617).
  * loc is int32[nnz][2] and val double[nnz]; problem b is the entries offsets[b] .. offsets[b + 1] (offsets: host

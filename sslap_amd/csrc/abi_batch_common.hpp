@@ -33,14 +33,21 @@ int thread_stream(int device, hipStream_t *out) {
     return MISSLAP_OK;
 }
 
-// opt.device made current, the calling thread's stream on it, ordered behind the producer stream of device inputs
-int batch_device(const misslap_options &opt, hipStream_t *st) {
+// opt.device made current
+int batch_set_device(const misslap_options &opt) {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail(MISSLAP_ERR_NO_DEVICE, "no HIP device available: libmisslap has no CPU fallback");
     if (opt.device < 0 || opt.device >= ndev) return fail(MISSLAP_ERR_INVALID, "device %d out of range", opt.device);
     HIP_TRY(hipSetDevice(opt.device));
-    int rc = thread_stream(opt.device, st);
+    return MISSLAP_OK;
+}
+
+// opt.device made current, the calling thread's stream on it, ordered behind the producer stream of device inputs
+int batch_device(const misslap_options &opt, hipStream_t *st) {
+    int rc = batch_set_device(opt);
+    if (rc) return rc;
+    rc = thread_stream(opt.device, st);
     if (rc) return rc;
     return sync_device_inputs(&opt, *st);
 }
@@ -126,6 +133,9 @@ int reject_bad_prices(int64_t b, int bad) {
     return MISSLAP_OK;
 }
 
+// a wavefront bids for one list position at a time: enough wavefronts for the first round's bidders, at most 16
+inline int batch_solve_threads(int Ns) { return Ns <= 256 ? 256 : (Ns <= 512 ? 512 : 1024); }
+
 // The solve once every problem is accepted: one launch of `kernel` (k_dense_batch_solve / k_sparse_batch_solve), one
 // workgroup per problem, on the LDS carve Ns x Ms; then the outputs, the meta records and the info.  The caller has set
 // a's own fields and a.s.eps_b / p0 / p0_ld; the rest of a.s is set here.
@@ -153,8 +163,7 @@ int batch_solve_run(void (*kernel)(Args), Args a, hipStream_t st, DevScratch &tm
     a.s.prices = d_prices;
     a.s.prices_ld = prices_ld;
     a.s.meta = d_meta;
-    // a wavefront bids for one list position at a time: enough wavefronts for the first round's bidders, at most 16
-    const int threads = Ns <= 256 ? 256 : (Ns <= 512 ? 512 : 1024);
+    const int threads = batch_solve_threads(Ns);
     const size_t lds = batch_solve_lds_bytes(Ns, Ms);
     // (per call: the > 64 KB dynamic-LDS opt-in is a property of the function on the current device.  Only a sparse
     // carve needs it: the dense one is at most 53 248 B, at MISSLAP_DENSE_BATCH_MAX_DIM x MISSLAP_DENSE_BATCH_MAX_DIM.)

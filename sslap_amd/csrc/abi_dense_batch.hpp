@@ -24,6 +24,27 @@ int dense_slice_matching(const double *A, int64_t M, int n, int m) {
     HopcroftKarp hk(loc.data(), (int64_t)(loc.size() / 2), n, m);
     return hk.solve();
 }
+
+// the size of a dense stack: 1 .. 2^31 - 1 problems within the cap
+int dense_batch_dims(int64_t B, int64_t N, int64_t M) {
+    if (B < 1 || B > 0x7fffffff) return fail(MISSLAP_ERR_INVALID, "B = %lld: 1 .. 2^31 - 1 problems", (long long)B);
+    if (N < 1 || M < 1 || N > kDenseBatchMaxDim || M > kDenseBatchMaxDim)
+        return fail(MISSLAP_ERR_INVALID,
+                    "a %lld x %lld problem: the dense batch takes at most %d x %d (MISSLAP_DENSE_BATCH_MAX_DIM); solve larger "
+                    "problems with misslap_create_dense / misslap_solve_batch",
+                    (long long)N, (long long)M, kDenseBatchMaxDim, kDenseBatchMaxDim);
+    return MISSLAP_OK;
+}
+
+// a host shapes array (or null): every problem within the stack
+int dense_batch_host_shapes(const int32_t *shapes, int64_t B, int64_t N, int64_t M) {
+    if (shapes)
+        for (int64_t b = 0; b < B; ++b)
+            if (shapes[2 * b] < 1 || shapes[2 * b] > N || shapes[2 * b + 1] < 1 || shapes[2 * b + 1] > M)
+                return fail(MISSLAP_ERR_INVALID, "problem %lld: shape (%d, %d) outside 1 .. %lld x 1 .. %lld", (long long)b,
+                            shapes[2 * b], shapes[2 * b + 1], (long long)N, (long long)M);
+    return MISSLAP_OK;
+}
 }  // namespace
 
 MISSLAP_API int misslap_solve_dense_batch(int64_t B, int64_t N, int64_t M, const double *mat, const int32_t *shapes,
@@ -37,19 +58,10 @@ MISSLAP_API int misslap_solve_dense_batch(int64_t B, int64_t N, int64_t M, const
                            "device, maximize, eps_start, max_iter, input_on_device and input_stream");
     if (rc) return rc;
     if (!mat || !sol) return fail(MISSLAP_ERR_INVALID, "null mat / sol");
-    if (B < 1 || B > 0x7fffffff) return fail(MISSLAP_ERR_INVALID, "B = %lld: 1 .. 2^31 - 1 problems", (long long)B);
-    if (N < 1 || M < 1 || N > kDenseBatchMaxDim || M > kDenseBatchMaxDim)
-        return fail(MISSLAP_ERR_INVALID,
-                    "a %lld x %lld problem: the dense batch takes at most %d x %d (MISSLAP_DENSE_BATCH_MAX_DIM); solve larger "
-                    "problems with misslap_create_dense / misslap_solve_batch",
-                    (long long)N, (long long)M, kDenseBatchMaxDim, kDenseBatchMaxDim);
+    if ((rc = dense_batch_dims(B, N, M))) return rc;
     int32_t stride = 0;
     if ((rc = batch_meta_stride(meta, &stride))) return rc;
-    if (shapes)
-        for (int64_t b = 0; b < B; ++b)
-            if (shapes[2 * b] < 1 || shapes[2 * b] > N || shapes[2 * b + 1] < 1 || shapes[2 * b + 1] > M)
-                return fail(MISSLAP_ERR_INVALID, "problem %lld: shape (%d, %d) outside 1 .. %lld x 1 .. %lld", (long long)b,
-                            shapes[2 * b], shapes[2 * b + 1], (long long)N, (long long)M);
+    if ((rc = dense_batch_host_shapes(shapes, B, N, M))) return rc;
     hipStream_t st = nullptr;
     if ((rc = batch_device(opt, &st))) return rc;
 
@@ -68,7 +80,7 @@ MISSLAP_API int misslap_solve_dense_batch(int64_t B, int64_t N, int64_t M, const
 
     // ---- validation: every problem before any is solved
     hipLaunchKernelGGL(k_dense_batch_check, dim3((unsigned)B), dim3(256), 0, st, d_mat, (long long)N, (long long)M,
-                       d_shapes, d_p0, d_chk);
+                       d_shapes, d_p0, d_chk, (int *)nullptr);
     HIP_TRY(hipGetLastError());
     // the matching guard of every problem on the device, behind the validation pass and read back with it
     const bool device_guard = cardinality_check && dense_guard_on_device(B);

@@ -67,6 +67,37 @@ __device__ __forceinline__ void batch_check_prices(const double *p, int m, int *
     if (bad) atomicOr(s_badp, bad);
 }
 
+// The part of a status-mode verdict (MISSLAP_BATCH_STATUS_*, include/misslap.h) that every layout shares.  `code` is
+// what the layout's own checks of the values gave (0: none failed); behind them, in the order of the all-or-nothing
+// calls: the matching guard (card: its cardinality; guarded: it ran for this call), then the starting prices.
+__device__ __forceinline__ int batch_verdict(int code, bool guarded, int card, int n, int bad_price) {
+    if (code) return code;
+    if (guarded && card < n) return MISSLAP_BATCH_STATUS_INFEASIBLE;
+    if (bad_price & 1) return MISSLAP_BATCH_STATUS_PRICE_NOT_FINITE;
+    if (bad_price & 2) return MISSLAP_BATCH_STATUS_PRICE_NEGATIVE;
+    return MISSLAP_BATCH_STATUS_OK;
+}
+
+// The outputs of a condemned problem (status != 0), written by its whole workgroup before any LDS state exists:
+// sol[b][:] = -1, prices[b][:] = 0, and a meta record that holds the three counts of the check pass and zeros.
+__device__ __forceinline__ void batch_condemn(const BatchSolveArgs &a, int n, int n_cols, long long nnz) {
+    const int b = blockIdx.x, tid = threadIdx.x, T = blockDim.x;
+    int *sol = a.sol + (size_t)b * (size_t)a.sol_ld;
+    for (long long i = tid; i < a.sol_ld; i += T) sol[i] = -1;
+    if (a.prices) {
+        double *po = a.prices + (size_t)b * (size_t)a.prices_ld;
+        for (long long j = tid; j < a.prices_ld; j += T) po[j] = 0.0;
+    }
+    if (tid == 0) {
+        misslap_dense_batch_meta r{};
+        r.struct_size = (int32_t)sizeof(misslap_dense_batch_meta);
+        r.n_rows = n;
+        r.n_cols = n_cols;
+        r.nnz = nnz;
+        a.meta[b] = r;
+    }
+}
+
 // eCE_satisfied(eps) (auction_.pyx:443-485, tol = 1e-7) on a state with everybody assigned; one wavefront per row.
 template <class Rows>
 __device__ __forceinline__ bool batch_ece(const Rows &rows, int n, const double *price, const int *p2o, float eps_f,

@@ -40,11 +40,21 @@ __device__ __forceinline__ void dense_batch_shape(const int *shapes, long long N
 }
 
 // Validation, one workgroup per problem: valid count, empty rows, +inf, C = max |v|, the reference's M, prices.
+// With shapes_out (status mode: `shapes` may be a caller's device array that no host has seen) a shape outside
+// 1 .. N x 1 .. M becomes (0, 0), nothing of that problem is read, and the shape every later kernel uses is written
+// to shapes_out[b]: the guard and the solve read those, never the caller's.
 __global__ __launch_bounds__(256) void k_dense_batch_check(const double *mat, long long N, long long M, const int *shapes,
-                                                           const double *p0, DenseBatchCheck *out) {
+                                                           const double *p0, DenseBatchCheck *out, int *shapes_out) {
     const int b = blockIdx.x, lane = lane_id(), wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
     int n, m;
     dense_batch_shape(shapes, N, M, b, n, m);
+    if (shapes_out) {
+        if (n < 1 || n > N || m < 1 || m > M) n = m = 0;
+        if (threadIdx.x == 0) {
+            shapes_out[2 * b] = n;
+            shapes_out[2 * b + 1] = m;
+        }
+    }
     const double *A = mat + (size_t)b * (size_t)N * (size_t)M;
     __shared__ unsigned long long s_cnt, s_abs;
     __shared__ int s_empty, s_inf, s_mref, s_badp;
@@ -190,6 +200,53 @@ __global__ __launch_bounds__(1024) void k_dense_batch_solve(DenseBatchArgs a) {
     double vals[kDenseBatchCols];
     const DenseBatchRows rows{a.mat + (size_t)b * (size_t)a.N * (size_t)a.M, a.M, m, a.s.maximize, ck.mref, ck.nvalid, vals};
     batch_solve(a.s, rows, n, m, ck.absmax_bits);
+}
+
+// ---- status mode (misslap_solve_dense_batch_status): a verdict per problem instead of all or nothing
+
+struct DenseBatchStatusArgs {
+    DenseBatchArgs d;      // d.shapes: the check pass's sanitised shapes (never null)
+    const int *card;       // [B] the guard's cardinalities, or null: no guard in this call
+    int fast;              // eps_start = 1 / n_b of each problem (auction_.pyx:568-569)
+    int *status;           // [B] MISSLAP_BATCH_STATUS_*
+    int *matching_size;    // [B] or null: the guard's cardinality, -1 where it did not run
+};
+
+// The dense checks of a verdict, in first_error's order (abi_dense_batch.hpp); batch_verdict adds the shared rest.
+__device__ __forceinline__ int dense_batch_verdict(const DenseBatchCheck &c, int n) {
+    if (n < 1) return MISSLAP_BATCH_STATUS_BAD_SHAPE;
+    if (c.nvalid < (unsigned long long)n) return MISSLAP_BATCH_STATUS_TOO_FEW_VALUES;
+    if (c.empty_row != 0x7fffffff) return MISSLAP_BATCH_STATUS_EMPTY_ROW;
+    if (c.has_inf) return MISSLAP_BATCH_STATUS_INFINITE_VALUE;
+    return MISSLAP_BATCH_STATUS_OK;
+}
+
+// k_dense_batch_solve with the verdict formed here, from what the check pass and the guard left on the device.  A
+// condemned problem's workgroup writes the defined outputs and leaves before any LDS state exists; the others run the
+// same batch_solve on the same row source.
+__global__ __launch_bounds__(1024) void k_dense_batch_solve_status(DenseBatchStatusArgs a) {
+    const int b = blockIdx.x;
+    const int n = a.d.shapes[2 * b], m = a.d.shapes[2 * b + 1];
+    const DenseBatchCheck ck = a.d.chk[b];
+    const int card = a.card && n >= 1 ? a.card[b] : -1;
+    const int code = batch_verdict(dense_batch_verdict(ck, n), a.card != nullptr, card, n, ck.bad_price);
+    if (threadIdx.x == 0) {
+        a.status[b] = code;
+        if (a.matching_size) a.matching_size[b] = card;
+    }
+    if (code != MISSLAP_BATCH_STATUS_OK) {
+        batch_condemn(a.d.s, n, ck.mref, (long long)ck.nvalid);
+        return;
+    }
+    BatchSolveArgs s = a.d.s;
+    if (a.fast) {  // the front-end's (1.0 / float64(n)).astype(float32): the same two IEEE operations
+        s.eps_b = nullptr;
+        s.eps_opt = (float)(1.0 / (double)n);
+    }
+    double vals[kDenseBatchCols];
+    const DenseBatchRows rows{a.d.mat + (size_t)b * (size_t)a.d.N * (size_t)a.d.M, a.d.M, m, s.maximize, ck.mref, ck.nvalid,
+                              vals};
+    batch_solve(s, rows, n, m, ck.absmax_bits);
 }
 
 }  // namespace misslap

@@ -10,13 +10,29 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._batch import _check_shapes, _check_stack, _decode_meta, _new_meta, _solve_options, _starting_prices
+from ._batch import _check_shapes, _check_stack, _decode_meta, _is_device_tensor, _new_meta, _solve_options, _starting_prices
 
 MAX_DIM = _lib.DENSE_BATCH_MAX_DIM
 
 
+# what each status code of misslap_solve_dense_batch_status says in the default mode's words (abi_dense_batch.hpp,
+# abi_batch_common.hpp: reject_bad_prices, _batch._check_shapes)
+_STATUS_TEXT = {
+    _lib.BATCH_STATUS_TOO_FEW_VALUES: "Matrix is infeasible - Fewer than {n} valid values provided for {n} rows.",
+    _lib.BATCH_STATUS_EMPTY_ROW: "every row must have at least one valid (>= 0) entry",
+    _lib.BATCH_STATUS_INFINITE_VALUE: "val holds a NaN or an infinity",
+    _lib.BATCH_STATUS_INFEASIBLE: "Matrix is infeasible (Maximum matching possible only involves {card} out of {n} rows.)",
+    _lib.BATCH_STATUS_PRICE_NOT_FINITE: "prices hold a NaN or an infinity",
+    _lib.BATCH_STATUS_PRICE_NEGATIVE: "prices must be >= 0 (with the sign bit clear: -0.0 is rejected)",
+    _lib.BATCH_STATUS_BAD_SHAPE: "shape ({n}, {m}) outside 1 .. {N} x 1 .. {M}",
+}
+# the meta fields a status-mode call on the device returns as views of its record buffer
+_META_VIEWS = ("its", "nreductions", "eCE", "soln_found", "n_assigned", "obj_f64", "start_eps_f32", "final_eps_f32",
+               "n_rows", "n_cols", "nnz", "bids_made")
+
+
 def auction_solve_batch(mats, problem="min", eps_start=0., max_iter=1000000, fast=False, cardinality_check=True,
-                        shapes=None, prices=None):
+                        shapes=None, prices=None, errors="raise"):
     """Solve B independent dense problems in one call, one workgroup per problem.
 
     mats: float64 (B, N, M), a numpy array or a contiguous tensor on the device (read in place, ordered behind
@@ -28,11 +44,27 @@ def auction_solve_batch(mats, problem="min", eps_start=0., max_iter=1000000, fas
     arrays).  Device input gives device tensors for sol and prices.  All or nothing: a failing problem raises
     ValueError("problem <b>: <what from_matrix raises for that slice>") and nothing is solved.  The caller's arrays are
     never written.
+
+    errors="status": a verdict per problem instead.  The call only raises for what is wrong with the whole call; the
+    result also holds status (int32 (B,), the MISSLAP_BATCH_STATUS_* codes of include/misslap.h) and matching_size
+    (int32 (B,), the guard's cardinality, -1 where it did not run).  Every problem with status 0 is solved, with exactly
+    the default mode's results; the others have sol -1, prices 0 and a meta of n_rows, n_cols, nnz and zeros.
+    raise_for_status(res) raises what the default mode would have raised.  With a device stack the call is
+    stream-ordered: its kernels go onto torch.cuda.current_stream(mats.device), it waits for nothing, and sol, prices,
+    status, matching_size and the meta fields are device tensors ordered on that stream (batch_meta_to_host(res) gives
+    the default mode's meta dict).  shapes and prices may then be device tensors; a device shapes entry outside the
+    stack gives MISSLAP_BATCH_STATUS_BAD_SHAPE.  The matching guard always runs on the device in this mode, which at
+    B = 1 is slower than the default mode's host guard.
     """
+    if errors not in ("raise", "status"):
+        raise ValueError(f"errors must be 'raise' or 'status', got {errors!r}")
     B, N, M, on_device = _check_stack(mats)
     if N > MAX_DIM or M > MAX_DIM:
         raise ValueError(f"problems of {N} x {M}: auction_solve_batch takes at most {MAX_DIM} x {MAX_DIM} "
                          f"(MISSLAP_DENSE_BATCH_MAX_DIM); solve larger problems with from_matrix / solve_batch")
+    if errors == "status":
+        return _solve_status(mats, B, N, M, on_device, problem, eps_start, max_iter, fast, cardinality_check, shapes,
+                             prices)
     shp = _check_shapes(shapes, B, N, M, "problem")
     ns = shp[:, 0] if shp is not None else np.full(B, N, dtype=np.int32)
     e = float(eps_start)
@@ -62,3 +94,108 @@ def auction_solve_batch(mats, problem="min", eps_start=0., max_iter=1000000, fas
         1 if cardinality_check else 0, C.byref(opts), C.c_void_p(sol_ptr), C.c_void_p(pout_ptr),
         1 if on_device else 0, metas, C.byref(info)))
     return dict(sol=sol, prices=pout, meta=_decode_meta(metas, info))
+
+
+def _eps(eps_start):
+    e = float(eps_start)
+    if e != e:
+        raise ValueError("eps_start is NaN")
+    return e
+
+
+def _solve_status(mats, B, N, M, on_device, problem, eps_start, max_iter, fast, cardinality_check, shapes, prices):
+    """errors="status" of auction_solve_batch (misslap_solve_dense_batch_status); the whole-call checks in the default
+    mode's order: shapes, eps_start, prices."""
+    check = 1 if cardinality_check else 0
+    if not on_device:  # synchronous: the library uploads, uses its own scratch and waits once
+        shp = _check_shapes(shapes, B, N, M, "problem")
+        opts = _solve_options(False, mats, problem, _eps(eps_start), max_iter)
+        p, p_ptr, _ = _starting_prices(prices, B, M, True, False, mats, "mats")
+        mc = np.ascontiguousarray(mats)
+        sol, pout = np.empty((B, N), dtype=np.int32), np.empty((B, M), dtype=np.float64)
+        status, msize = np.empty(B, dtype=np.int32), np.empty(B, dtype=np.int32)
+        metas, info = _new_meta(B)
+        _lib.check(_lib.load().misslap_solve_dense_batch_status(
+            B, N, M, mc.ctypes.data, None if shp is None else shp.ctypes.data, 1 if fast else 0, p_ptr, check,
+            C.byref(opts), None, None, 0, sol.ctypes.data, pout.ctypes.data, 0, status.ctypes.data, msize.ctypes.data,
+            C.cast(metas, C.c_void_p), C.byref(info)))
+        return dict(sol=sol, prices=pout, status=status, matching_size=msize, meta=_decode_meta(metas, info),
+                    shapes=shp, stack=(N, M))
+    import torch
+    dev = mats.device
+    if shapes is None or _is_device_tensor(shapes):
+        shp = shapes
+        if shp is not None and (shp.dtype != torch.int32 or tuple(shp.shape) != (B, 2) or shp.device != dev or
+                                not shp.is_contiguous()):
+            raise ValueError(f"a device shapes tensor must be contiguous int32 of shape ({B}, 2) on {dev}, got "
+                             f"{shp.dtype} {tuple(shp.shape)} on {shp.device}")
+    else:  # a host array: validated as in the default mode, sent from pinned memory without a wait
+        shp = torch.from_numpy(_check_shapes(shapes, B, N, M, "problem")).pin_memory().to(dev, non_blocking=True)
+    opts = _solve_options(True, mats, problem, _eps(eps_start), max_iter)
+    if isinstance(prices, np.ndarray):
+        _starting_prices(prices, B, M, True, False, mats, "mats")  # (dtype and shape)
+        prices = torch.from_numpy(np.ascontiguousarray(prices)).pin_memory().to(dev, non_blocking=True)
+    p, p_ptr, _ = _starting_prices(prices, B, M, True, True, mats, "mats")
+    lib = _lib.load()
+    nbytes = int(lib.misslap_dense_batch_workspace_bytes(B, N, M, 0 if p is None else 1, check))
+    with torch.cuda.device(dev):  # (the allocations below are made on the current stream of the stack's device)
+        stream = torch.cuda.current_stream(dev)
+        work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        sol = torch.empty((B, N), dtype=torch.int32, device=dev)
+        pout = torch.empty((B, M), dtype=torch.float64, device=dev)
+        status = torch.empty(B, dtype=torch.int32, device=dev)
+        msize = torch.empty(B, dtype=torch.int32, device=dev)
+        rec = torch.empty((B, C.sizeof(_lib.DenseBatchMeta)), dtype=torch.uint8, device=dev)
+    info = _lib.DenseBatchInfo()
+    _lib.check(lib.misslap_solve_dense_batch_status(
+        B, N, M, mats.data_ptr(), None if shp is None else shp.data_ptr(), 1 if fast else 0, p_ptr, check, C.byref(opts),
+        C.c_void_p(int(stream.cuda_stream)), work.data_ptr(), nbytes, sol.data_ptr(), pout.data_ptr(), 1, status.data_ptr(),
+        msize.data_ptr(), rec.data_ptr(), C.byref(info)))
+    # the workspace and the inputs stay referenced by the result: nothing of this call is recycled before it
+    return dict(sol=sol, prices=pout, status=status, matching_size=msize, meta=_meta_views(rec), shapes=shp,
+                stack=(N, M), records=rec, info=info, stream=stream, keep=(work, mats, p))
+
+
+def _meta_views(rec):
+    """The fields of a device buffer of misslap_dense_batch_meta records as column views, one tensor of length B each."""
+    import torch
+    kinds = {C.c_int32: torch.int32, C.c_int64: torch.int64, C.c_uint64: torch.int64, C.c_float: torch.float32,
+             C.c_double: torch.float64}
+    names = dict(start_eps_f32="start_eps", final_eps_f32="final_eps")
+    fields = dict(_lib.DenseBatchMeta._fields_)
+    out = {}
+    for key in _META_VIEWS:
+        f = names.get(key, key)
+        dt = kinds[fields[f]]
+        out[key] = rec.view(dt)[:, getattr(_lib.DenseBatchMeta, f).offset // C.sizeof(fields[f])]
+    return out
+
+
+def batch_meta_to_host(res):
+    """The meta of a status-mode result as the default mode returns it: a dict of length-B numpy arrays with the
+    Python-rounded obj, start_eps and final_eps.  For a device result this waits for the call's stream once."""
+    if "records" not in res:
+        return res["meta"]
+    res["stream"].synchronize()
+    raw = res["records"].cpu().numpy()
+    metas = (_lib.DenseBatchMeta * raw.shape[0]).from_buffer_copy(raw.tobytes())
+    return _decode_meta(metas, res["info"])
+
+
+def raise_for_status(res):
+    """Raise, for the first problem of a status-mode result whose status is not 0, the ValueError the default mode
+    raises for the same batch ("problem <b>: ..."); return res when every status is 0."""
+    def host(x):
+        return x if isinstance(x, np.ndarray) else x.cpu().numpy()
+    if "stream" in res:
+        res["stream"].synchronize()
+    status = host(res["status"])
+    bad = np.flatnonzero(status)
+    if bad.size == 0:
+        return res
+    b = int(bad[0])
+    N, M = res["stack"]
+    n, m, card = int(host(res["meta"]["n_rows"])[b]), 0, int(host(res["matching_size"])[b])
+    if status[b] == _lib.BATCH_STATUS_BAD_SHAPE:
+        n, m = (int(x) for x in host(res["shapes"])[b])
+    raise ValueError(f"problem {b}: " + _STATUS_TEXT[int(status[b])].format(n=n, m=m, N=N, M=M, card=card))

@@ -8,19 +8,34 @@ synchronise, and for `dense` the kernel time from HIP events.  One JSON line per
 results of the three paths are compared problem by problem before anything is timed.  Needs the GPU.
 
   python tools/dense_batch.py [--reps 5] [--out profiles/dense_batch.jsonl] [--points 1x10,1024x64]
+
+--status times the status mode (auction_solve_batch(errors="status")) against the default mode instead, on a device
+stack with the cardinality check on, legs interleaved within every repetition:
+  a  default mode, wall time of the call (it synchronises itself)
+  b  status mode, host time of the call (it returns once its launches are enqueued)
+  c  status mode, the call plus torch.cuda.synchronize(); stream_ms is the time of its kernels from events around it
+  d  as c, on a copy of the stack in which every fourth problem holds a +inf (status 3: its workgroup leaves at once)
+With --parent-tree DIR (a built checkout of the commit to compare with) leg a is also run there, as `a_parent`, by a
+child process of this script per round, the rounds alternating between the two trees.
+
+  python tools/dense_batch.py --status [--reps 30] [--rounds 3] [--parent-tree DIR] [--out profiles/dense_batch_status.jsonl]
 """
 import argparse
 import json
 import os
+import subprocess
 import sys
 import time
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+# (--tree: the package of another checkout, for the child process of --status --parent-tree)
+TREE = sys.argv[sys.argv.index("--tree") + 1] if "--tree" in sys.argv else ROOT
+sys.path.insert(0, TREE)
 
 POINTS = ((1, 10), (1, 100), (1, 300), (1024, 64), (1024, 100), (256, 256), (64, 1000))
+STATUS_POINTS = ((1, 10), (1, 100), (1024, 64), (1024, 100), (256, 256), (64, 1000))
 
 
 def stack(B, N, recipe, seed):
@@ -30,13 +45,111 @@ def stack(B, N, recipe, seed):
     return rng.uniform(0.0, 100.0, (B, N, N))
 
 
+def status_times(points, reps, legs):
+    """{(B, N, leg): [ms per repetition]} (and "stream_ms" lists for c), the legs interleaved within a repetition."""
+    import torch
+    from sslap_amd import auction_solve_batch
+    sync = torch.cuda.synchronize
+    out = {}
+    for B, N in points:
+        host = stack(B, N, "float", seed=B * 7919 + N)
+        mats = torch.from_numpy(host).cuda()
+        host[::4, 0, 0] = np.inf
+        quarter = torch.from_numpy(host).cuda()
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        if "c" in legs:  # the two modes give the same results at the sizes that are timed
+            want, got, part = (auction_solve_batch(mats), auction_solve_batch(mats, errors="status"),
+                               auction_solve_batch(quarter, errors="status"))
+            assert torch.equal(want["sol"], got["sol"]) and not got["status"].any()
+            assert torch.equal(want["prices"].view(torch.int64), got["prices"].view(torch.int64))
+            keep = part["status"] == 0
+            assert int(keep.sum()) == B - len(range(0, B, 4)) and torch.equal(part["sol"][keep], want["sol"][keep])
+
+        def run(leg):
+            sync()
+            t0 = time.perf_counter()
+            if leg in ("a", "a_parent"):
+                auction_solve_batch(mats)
+            elif leg == "b":
+                auction_solve_batch(mats, errors="status")
+            else:
+                ev[0].record()
+                auction_solve_batch(mats if leg == "c" else quarter, errors="status")
+                ev[1].record()
+                sync()
+            t = (time.perf_counter() - t0) * 1e3
+            sync()
+            return t, ev[0].elapsed_time(ev[1]) if leg in ("c", "d") else None
+
+        for leg in legs:  # warm-up
+            run(leg)
+        for r in range(reps):
+            for leg in legs[r % len(legs):] + legs[:r % len(legs)]:  # (no leg always runs behind the same other)
+                t, g = run(leg)
+                out.setdefault((B, N, leg), []).append(t)
+                if g is not None:
+                    out.setdefault((B, N, leg + ":stream_ms"), []).append(g)
+    return out
+
+
+def status_main(args, points):
+    """The --status legs; as a child (--legs a_parent) the times go to stdout as one JSON line."""
+    if args.legs:
+        t = status_times(points, args.reps, args.legs.split(","))
+        print("TIMES " + json.dumps({f"{B}x{N}/{leg}": v for (B, N, leg), v in t.items()}), flush=True)
+        return
+    import torch
+    torch.zeros(1).cuda()
+    times = {}
+    per_round = -(-args.reps // args.rounds)
+    for _ in range(args.rounds):
+        if args.parent_tree:
+            cmd = [sys.executable, os.path.abspath(__file__), "--status", "--tree", args.parent_tree, "--legs", "a_parent",
+                   "--reps", str(per_round), "--points", ",".join(f"{B}x{N}" for B, N in points)]
+            txt = subprocess.run(cmd, check=True, capture_output=True, text=True, timeout=900).stdout
+            line = [x for x in txt.splitlines() if x.startswith("TIMES ")][-1]
+            for k, v in json.loads(line[6:]).items():
+                bn, leg = k.split("/")
+                B, N = (int(x) for x in bn.split("x"))
+                times.setdefault((B, N, leg), []).extend(v)
+        for k, v in status_times(points, per_round, ["a", "b", "c", "d"]).items():
+            times.setdefault(k, []).extend(v)
+    rows = []
+    for (B, N, leg), v in times.items():
+        if ":" in leg:
+            continue
+        row = dict(B=B, N=N, leg=leg, reps=len(v), median_ms=round(float(np.median(v)), 4),
+                   p10_ms=round(float(np.percentile(v, 10)), 4), p90_ms=round(float(np.percentile(v, 90)), 4))
+        g = times.get((B, N, leg + ":stream_ms"))
+        if g:
+            row["stream_ms"] = round(float(np.median(g)), 4)
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        for row in rows:
+            f.write(json.dumps(row) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "dense_batch.jsonl"))
+    ap.add_argument("--reps", type=int, default=None)
+    ap.add_argument("--out", default=None)
     ap.add_argument("--points", default=None, help="BxN,BxN,...")
     ap.add_argument("--loop-max", type=int, default=256, help="time the per-problem paths on at most so many problems")
+    ap.add_argument("--status", action="store_true", help="time the status mode against the default mode")
+    ap.add_argument("--rounds", type=int, default=3, help="--status: the repetitions are split over so many rounds")
+    ap.add_argument("--parent-tree", default=None, help="--status: a built checkout whose default mode is leg a_parent")
+    ap.add_argument("--tree", default=None, help="(child of --parent-tree) import sslap_amd from this checkout")
+    ap.add_argument("--legs", default=None, help="(child of --parent-tree) time these legs only, print the raw times")
     args = ap.parse_args()
+    if args.reps is None:
+        args.reps = 30 if args.status else 5
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "dense_batch_status.jsonl" if args.status else "dense_batch.jsonl")
+    if args.status:
+        pts = STATUS_POINTS if not args.points else [tuple(int(x) for x in p.split("x")) for p in args.points.split(",")]
+        return status_main(args, pts)
     import torch
     from sslap_amd import AuctionSolver, auction_solve, auction_solve_batch, from_matrix
     points = POINTS if not args.points else [tuple(int(x) for x in p.split("x")) for p in args.points.split(",")]
