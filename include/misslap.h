@@ -32,7 +32,8 @@ extern "C" {
  *      sizeof) bytes: a caller built against a shorter version-2 header keeps working when fields are appended),
  *      validity flags of the assignment, misslap_trim_caches.  Additions since: the warm-start entry points,
  *      misslap_solve_dense_batch, misslap_solve_sparse_batch, misslap_solve_dense_batch_status,
- *      misslap_dense_batch_workspace_bytes. */
+ *      misslap_dense_batch_workspace_bytes, misslap_solve_sparse_batch_status, misslap_sparse_batch_workspace_bytes
+ *      (with MISSLAP_BATCH_STATUS_NO_ENTRIES .. MISSLAP_BATCH_STATUS_PRICES_TOO_NARROW, codes 8 .. 14). */
 
 #define MISSLAP_OK 0
 #define MISSLAP_ERR_INVALID 1    /* malformed arguments / input contract violated */
@@ -572,6 +573,71 @@ int misslap_solve_sparse_batch(int64_t B, const int32_t *loc, const double *val,
                                int32_t cardinality_check, const misslap_options *opt, int32_t *sol, int64_t sol_ld,
                                double *prices_out, int64_t prices_out_ld, int32_t out_on_device,
                                misslap_dense_batch_meta *meta, misslap_dense_batch_info *info);
+
+/* ---- the sparse batch with a verdict per problem instead of all or nothing, and in stream order.
+ * misslap_solve_sparse_batch_status takes the packed loc / val of misslap_solve_sparse_batch and never fails for a reason
+ * that belongs to one problem: status[b] is the first check problem b fails, and every problem with status 0 is solved --
+ * sol, prices and meta bit for bit what misslap_solve_sparse_batch gives for it.  A problem with another status takes no
+ * part in the solve launch (its workgroup leaves at once, before it reads any entry): sol[b][:] = -1,
+ * prices_out[b][:] = 0, meta[b] = {n_rows = max row + 1, n_cols = max column + 1 (0 without a non-negative index), nnz =
+ * the problem's entries, every other result field 0}.  The checks, in their order (codes 0 .. 7 are the dense batch's):
+ *    8 NO_ENTRIES            offsets[b + 1] == offsets[b]
+ *    9 DIVISION_BY_ZERO      fast != 0 and the reference's N is 0 (N = sizes[b][1], without sizes the MAX ROW INDEX,
+ *                            auction_.pyx:592 / :594)
+ *    1 TOO_FEW_VALUES        fewer entries than N
+ *    4 INFEASIBLE            cardinality_check, the guard matched the problem (matching_size[b] >= 0) and found fewer
+ *                            than max row + 1 rows matchable
+ *   10 NEGATIVE_INDEX        a negative row or column index
+ *   11 ROWS_UNSORTED         a row index below the one stored before it
+ *   12 ROW_GAP               a row of 0 .. max row without an entry
+ *    3 INFINITE_VALUE        val holds a NaN or an infinity
+ *   13 TOO_LARGE             more than Nmax rows or Mmax columns (a column index whose + 1 does not fit an int32 included)
+ *   14 PRICES_TOO_NARROW     prices_in given and prices_ld < the problem's columns
+ *    5 PRICE_NOT_FINITE, 6 PRICE_NEGATIVE   as for the dense batch, over prices_in[b][:n_cols_b]
+ * This is misslap_solve_sparse_batch's order without cardinality_check, and with it for every problem the guard matches:
+ * a graph that is clean (rows ascending from 0 without a gap, no negative index) with at most
+ * MISSLAP_SPARSE_BATCH_MAX_DIM rows and columns.  The one difference: for any other graph misslap_solve_sparse_batch lets
+ * its host guard speak first ("loc entry ... outside", "rows must be sorted", or an infeasibility); here no host work is
+ * done, the structural code is reported and matching_size[b] is -1.  The guard always runs on the device.
+ *   loc, val, prices_in, prices_ld, cardinality_check   as for misslap_solve_sparse_batch.
+ *   offsets        host int64[B + 1], always: checked as misslap_solve_sparse_batch checks it, and the guard's LDS carve
+ *                  is sized from the largest problem.
+ *   offsets_dev    with a workspace: the same B + 1 values in device memory.  Else not read.
+ *   sizes          int64[B][2] or NULL, as for misslap_solve_sparse_batch; a DEVICE array with a workspace.
+ *   fast           != 0: problem b starts at eps = (float)(1.0 / (double)N_b), formed in the kernel (:614-615);
+ *                  0: opt->eps_start for every problem.
+ *   Nmax, Mmax     1 .. MISSLAP_SPARSE_BATCH_MAX_DIM: the caller's bound on every problem's rows and columns.  They are
+ *                  the leading dimensions of sol (int32[B][Nmax]) and prices_out (double[B][Mmax], may be NULL) and size
+ *                  the LDS carve and the workgroup.  A problem beyond them is MISSLAP_BATCH_STATUS_TOO_LARGE and is
+ *                  condemned before any LDS state exists: no kernel of the call reads outside offsets[b] ..
+ *                  offsets[b + 1] of loc / val or outside the problem's own nnz_b + 1 row-start slots, or writes
+ *                  outside the problem's own row of sol / prices_out.
+ *   opt, stream, workspace, workspace_bytes, out_on_device, status, matching_size, meta, info
+ *                  as for misslap_solve_dense_batch_status (workspace: misslap_sparse_batch_workspace_bytes).  With a
+ *                  workspace EVERY pointer argument except offsets, opt and info is a device pointer, the three
+ *                  launches (check, guard, solve with verdict) go onto `stream`, and the call allocates and frees
+ *                  nothing, creates no event, waits for nothing and copies nothing.  Above 64 KB of LDS it opts the solve
+ *                  kernel into the larger carve first (hipFuncSetAttribute: a host-side setting, no wait).
+ * Only what is wrong with the whole call is an error: B, offsets, Nmax, Mmax, prices_ld < 1, a NULL loc / val (with
+ * entries) / sol / status, the options, a workspace that is too small or misaligned. */
+#define MISSLAP_BATCH_STATUS_NO_ENTRIES 8          /* the problem has no entries */
+#define MISSLAP_BATCH_STATUS_DIVISION_BY_ZERO 9    /* fast with N = 0 (sizes[b][1], or the max row index) */
+#define MISSLAP_BATCH_STATUS_NEGATIVE_INDEX 10     /* a negative row or column index */
+#define MISSLAP_BATCH_STATUS_ROWS_UNSORTED 11      /* rows not in ascending order */
+#define MISSLAP_BATCH_STATUS_ROW_GAP 12            /* a row of 0 .. N-1 without an entry */
+#define MISSLAP_BATCH_STATUS_TOO_LARGE 13          /* more rows or columns than Nmax / Mmax (dims, at most the cap) */
+#define MISSLAP_BATCH_STATUS_PRICES_TOO_NARROW 14  /* prices hold fewer columns than the problem has */
+int misslap_solve_sparse_batch_status(int64_t B, const int32_t *loc, const double *val, const int64_t *offsets,
+                                      const int64_t *offsets_dev, const int64_t *sizes, int32_t fast,
+                                      const double *prices_in, int64_t prices_ld, int32_t cardinality_check,
+                                      const misslap_options *opt, void *stream, void *workspace, int64_t workspace_bytes,
+                                      int64_t Nmax, int64_t Mmax, int32_t *sol, double *prices_out, int32_t out_on_device,
+                                      int32_t *status, int32_t *matching_size, misslap_dense_batch_meta *meta,
+                                      misslap_dense_batch_info *info);
+/* Bytes of workspace a stream-ordered misslap_solve_sparse_batch_status over B problems of nnz entries in all needs (the
+ * check records, the nnz + B row starts and, with cardinality_check, the cardinalities, each 256-byte aligned); -1 for
+ * B < 1 or nnz < 0.  Needs no GPU.  has_prices is accepted for the day a layout depends on it: today's does not. */
+int64_t misslap_sparse_batch_workspace_bytes(int64_t B, int64_t nnz, int32_t has_prices, int32_t cardinality_check);
 
 /* ---- the matching of many small graphs in one call: the batch form of misslap_hopcroft_karp / sslap.hopcroft_solve
  * (feasibility_.pyx:227-283).  Each graph is matched by ONE workgroup of ONE launch, its state in LDS

@@ -85,6 +85,9 @@ MATCHING_BATCH_MAX_DIM = 2048  # MISSLAP_MATCHING_BATCH_MAX_DIM
 # MISSLAP_BATCH_STATUS_*: the verdict of one problem of misslap_solve_dense_batch_status
 (BATCH_STATUS_OK, BATCH_STATUS_TOO_FEW_VALUES, BATCH_STATUS_EMPTY_ROW, BATCH_STATUS_INFINITE_VALUE,
  BATCH_STATUS_INFEASIBLE, BATCH_STATUS_PRICE_NOT_FINITE, BATCH_STATUS_PRICE_NEGATIVE, BATCH_STATUS_BAD_SHAPE) = range(8)
+# ... and those misslap_solve_sparse_batch_status adds
+(BATCH_STATUS_NO_ENTRIES, BATCH_STATUS_DIVISION_BY_ZERO, BATCH_STATUS_NEGATIVE_INDEX, BATCH_STATUS_ROWS_UNSORTED,
+ BATCH_STATUS_ROW_GAP, BATCH_STATUS_TOO_LARGE, BATCH_STATUS_PRICES_TOO_NARROW) = range(8, 15)
 
 
 def new_meta():
@@ -179,6 +182,10 @@ SYMBOLS = {
     "misslap_solve_sparse_batch": (C.c_int, [C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int64, C.c_int32,
                                              C.POINTER(Options), _VP, C.c_int64, _VP, C.c_int64, C.c_int32,
                                              C.POINTER(DenseBatchMeta), C.POINTER(DenseBatchInfo)]),
+    "misslap_solve_sparse_batch_status": (C.c_int, [C.c_int64, _VP, _VP, _VP, _VP, _VP, C.c_int32, _VP, C.c_int64, C.c_int32,
+                                                    C.POINTER(Options), _VP, _VP, C.c_int64, C.c_int64, C.c_int64, _VP, _VP,
+                                                    C.c_int32, _VP, _VP, _VP, C.POINTER(DenseBatchInfo)]),
+    "misslap_sparse_batch_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
     "misslap_matching_batch": (C.c_int, [C.c_int64, _VP, _VP, C.POINTER(Options), _VP, _VP, _VP, _VP, C.c_int64, _VP,
                                          C.c_int64, C.c_int32, C.POINTER(MatchingBatchInfo)]),
     "misslap_matching_dense_batch": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, _VP, _VP, C.POINTER(Options), _VP, _VP,

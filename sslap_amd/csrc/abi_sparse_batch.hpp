@@ -55,6 +55,22 @@ bool sparse_problem_guard(const int32_t *loc, int64_t nnz, int n_true, int m_tru
     }
     return true;
 }
+// B and the host offsets of a sparse batch; *zmax: the largest problem's entries (at least 1)
+int sparse_batch_offsets(int64_t B, const int64_t *offsets, int64_t *zmax) {
+    if (B < 1 || B > 0x7fffffff) return fail(MISSLAP_ERR_INVALID, "B = %lld: 1 .. 2^31 - 1 problems", (long long)B);
+    if (offsets[0] != 0) return fail(MISSLAP_ERR_INVALID, "offsets[0] = %lld: must be 0", (long long)offsets[0]);
+    *zmax = 1;
+    for (int64_t b = 0; b < B; ++b) {
+        const int64_t z = offsets[b + 1] - offsets[b];
+        if (z < 0) return fail(MISSLAP_ERR_INVALID, "offsets must be non-decreasing (offsets[%lld] > offsets[%lld])",
+                               (long long)b, (long long)b + 1);
+        if (z >= 0x7fffffff)
+            return fail(MISSLAP_ERR_INVALID, "problem %lld: %lld entries; a problem takes fewer than 2^31 - 1", (long long)b,
+                        (long long)z);
+        *zmax = std::max(*zmax, z);
+    }
+    return MISSLAP_OK;
+}
 }  // namespace
 
 MISSLAP_API int misslap_solve_sparse_batch(int64_t B, const int32_t *loc, const double *val, const int64_t *offsets,
@@ -69,16 +85,8 @@ MISSLAP_API int misslap_solve_sparse_batch(int64_t B, const int32_t *loc, const 
                            "device, maximize, eps_start, max_iter, input_on_device and input_stream");
     if (rc) return rc;
     if (!loc || !val || !offsets || !sol) return fail(MISSLAP_ERR_INVALID, "null loc / val / offsets / sol");
-    if (B < 1 || B > 0x7fffffff) return fail(MISSLAP_ERR_INVALID, "B = %lld: 1 .. 2^31 - 1 problems", (long long)B);
-    if (offsets[0] != 0) return fail(MISSLAP_ERR_INVALID, "offsets[0] = %lld: must be 0", (long long)offsets[0]);
-    for (int64_t b = 0; b < B; ++b) {
-        const int64_t z = offsets[b + 1] - offsets[b];
-        if (z < 0) return fail(MISSLAP_ERR_INVALID, "offsets must be non-decreasing (offsets[%lld] > offsets[%lld])",
-                               (long long)b, (long long)b + 1);
-        if (z >= 0x7fffffff)
-            return fail(MISSLAP_ERR_INVALID, "problem %lld: %lld entries; a problem takes fewer than 2^31 - 1", (long long)b,
-                        (long long)z);
-    }
+    int64_t zmax = 1;
+    if ((rc = sparse_batch_offsets(B, offsets, &zmax))) return rc;
     if (sol_ld < 1 || (prices_out && prices_out_ld < 1) || (prices_in && prices_ld < 1))
         return fail(MISSLAP_ERR_INVALID, "sol_ld / prices_out_ld / prices_ld must be >= 1");
     int32_t stride = 0;
@@ -114,8 +122,6 @@ MISSLAP_API int misslap_solve_sparse_batch(int64_t B, const int32_t *loc, const 
     std::vector<int> card((size_t)B, -1);
     EventPair gev;
     if (device_guard) {
-        int64_t zmax = 1;
-        for (int64_t b = 0; b < B; ++b) zmax = std::max<int64_t>(zmax, offsets[b + 1] - offsets[b]);
         int *d_card = nullptr;
         if ((rc = tmp.alloc(&d_card, (size_t)B))) return rc;
         MatchBatchArgs g{};

@@ -1,5 +1,6 @@
 // kernels_sparse_batch.hpp -- many small SPARSE problems, one workgroup per problem for its whole solve
-// (misslap_solve_sparse_batch, include/misslap.h; the host side is abi_sparse_batch.hpp).
+// (misslap_solve_sparse_batch, include/misslap.h; the host side is abi_sparse_batch.hpp), and the same solve with a
+// verdict per problem (misslap_solve_sparse_batch_status; abi_sparse_batch_status.hpp).
 //
 // The round loop is batch_solve (kernels_batch_solve.hpp); this file has the check pass and the sparse row source.
 // What differs from the dense source is where a row comes from.  Problem b is the entries offsets[b] .. offsets[b + 1]
@@ -227,6 +228,70 @@ __global__ __launch_bounds__(1024) void k_sparse_batch_solve(SparseBatchArgs a) 
     const long long s = a.offsets[b];
     const SparseBatchRows rows{a.loc, a.val, a.offsets, s, a.row_start + s + b, a.s.maximize};
     batch_solve(a.s, rows, ck.last_row + 1, ck.max_col + 1, ck.absmax_bits);
+}
+
+// ---- status mode (misslap_solve_sparse_batch_status): a verdict per problem instead of all or nothing
+
+struct SparseBatchStatusArgs {
+    SparseBatchArgs d;       // d.s.Ns / Ms = sol_ld / prices_ld: the caller's bound on every problem (dims), the LDS carve
+    const long long *sizes;  // [B][2] or null: from_sparse's `size` of each problem (N = sizes[b][1], auction_.pyx:592)
+    const int *card;         // [B] the guard's cardinalities (-1: not matched), or null: no guard in this call
+    int fast;                // eps_start = 1 / N of each problem (:614-615)
+    int *status;             // [B] MISSLAP_BATCH_STATUS_*
+    int *matching_size;      // [B] or null: the guard's cardinality, -1 where it did not run
+};
+
+// a check record's maximum as a count: max + 1, 0 without a non-negative index, saturated at INT_MAX
+__device__ __forceinline__ int sparse_batch_count(int mx) { return mx < 0 ? 0 : (mx == INT_MAX ? INT_MAX : mx + 1); }
+
+// The sparse checks of a verdict ahead of the starting prices, in the order of misslap_solve_sparse_batch
+// (abi_sparse_batch.hpp: pre_guard_error, the guard, AuctionSolver.__init__, the cap, the leading dimensions);
+// batch_verdict adds the prices.  N: the reference's N of :592 / :594; card: the guard's cardinality, -1 without one.
+__device__ __forceinline__ int sparse_batch_verdict(const SparseBatchCheck &c, long long nnz, long long N, int fast,
+                                                    int card, int Ns, int Ms, long long p0_ld, bool has_p0) {
+    if (nnz == 0) return MISSLAP_BATCH_STATUS_NO_ENTRIES;
+    if (fast && N == 0) return MISSLAP_BATCH_STATUS_DIVISION_BY_ZERO;
+    if (nnz < N) return MISSLAP_BATCH_STATUS_TOO_FEW_VALUES;
+    if (card >= 0 && card < c.max_row + 1) return MISSLAP_BATCH_STATUS_INFEASIBLE;  // (matched: max_row + 1 <= the cap)
+    if (c.last_row < 0 || (c.err & kErrColNegative)) return MISSLAP_BATCH_STATUS_NEGATIVE_INDEX;
+    if (c.err & kErrRowsUnsorted) return MISSLAP_BATCH_STATUS_ROWS_UNSORTED;
+    if (c.err & kErrRowGap) return MISSLAP_BATCH_STATUS_ROW_GAP;
+    if (c.err & kErrNonFinite) return MISSLAP_BATCH_STATUS_INFINITE_VALUE;
+    // (from here on rows ascend from 0 without a gap and no index is negative: n = last_row + 1 = max_row + 1 <= nnz)
+    // (Ns, Ms <= MISSLAP_SPARSE_BATCH_MAX_DIM: a column whose + 1 does not fit an int32 is beyond Ms too)
+    if (c.last_row >= Ns || c.max_col >= Ms) return MISSLAP_BATCH_STATUS_TOO_LARGE;
+    if (has_p0 && c.max_col >= p0_ld) return MISSLAP_BATCH_STATUS_PRICES_TOO_NARROW;
+    return MISSLAP_BATCH_STATUS_OK;
+}
+
+// k_sparse_batch_solve with the verdict formed here, from what the check pass and the guard left on the device.  A
+// condemned problem's workgroup writes the defined outputs and leaves before any LDS state exists and before anything of
+// loc, val or the row starts is read: an index beyond the carve never reaches the price array.  The others run the same
+// batch_solve on the same row source.
+__global__ __launch_bounds__(1024) void k_sparse_batch_solve_status(SparseBatchStatusArgs a) {
+    const int b = blockIdx.x;
+    const SparseBatchCheck ck = a.d.chk[b];
+    const long long s = a.d.offsets[b];
+    const long long nnz = a.d.offsets[b + 1] - s;
+    const long long N = a.sizes ? a.sizes[2 * b + 1] : (long long)ck.max_row;  // sic, :592 / :594
+    const int card = a.card ? a.card[b] : -1;
+    const int own = sparse_batch_verdict(ck, nnz, N, a.fast, card, a.d.s.Ns, a.d.s.Ms, a.d.s.p0_ld, a.d.s.p0 != nullptr);
+    const int code = batch_verdict(own, false, 0, 0, ck.bad_price);
+    if (threadIdx.x == 0) {
+        a.status[b] = code;
+        if (a.matching_size) a.matching_size[b] = card;
+    }
+    if (code != MISSLAP_BATCH_STATUS_OK) {
+        batch_condemn(a.d.s, sparse_batch_count(ck.max_row), sparse_batch_count(ck.max_col), nnz);
+        return;
+    }
+    BatchSolveArgs bs = a.d.s;
+    if (a.fast) {  // the front-end's (1.0 / float64(N)).astype(float32): the same two IEEE operations
+        bs.eps_b = nullptr;
+        bs.eps_opt = (float)(1.0 / (double)N);
+    }
+    const SparseBatchRows rows{a.d.loc, a.d.val, a.d.offsets, s, a.d.row_start + s + b, bs.maximize};
+    batch_solve(bs, rows, ck.last_row + 1, ck.max_col + 1, ck.absmax_bits);
 }
 
 }  // namespace misslap

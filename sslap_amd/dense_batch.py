@@ -184,7 +184,9 @@ def batch_meta_to_host(res):
 
 def raise_for_status(res):
     """Raise, for the first problem of a status-mode result whose status is not 0, the ValueError the default mode
-    raises for the same batch ("problem <b>: ..."); return res when every status is 0."""
+    raises for the same batch ("problem <b>: ..."); return res when every status is 0.  For a result of
+    auction_solve_sparse_batch: what its default mode raises with cardinality_check=False for that check, a
+    ZeroDivisionError for `fast` with N = 0 included."""
     def host(x):
         return x if isinstance(x, np.ndarray) else x.cpu().numpy()
     if "stream" in res:
@@ -194,6 +196,10 @@ def raise_for_status(res):
     if bad.size == 0:
         return res
     b = int(bad[0])
+    if res.get("layout") == "sparse":
+        from .sparse_batch import _status_error
+        raise _status_error(res, b, int(status[b]), int(host(res["meta"]["n_rows"])[b]),
+                            int(host(res["meta"]["n_cols"])[b]), int(host(res["matching_size"])[b]))
     N, M = res["stack"]
     n, m, card = int(host(res["meta"]["n_rows"])[b]), 0, int(host(res["matching_size"])[b])
     if status[b] == _lib.BATCH_STATUS_BAD_SHAPE:

@@ -15,6 +15,22 @@ from ._batch import (_check_offsets, _decode_meta, _is_device_tensor, _maxima, _
 from .auction_solve import _cname
 
 MAX_DIM = _lib.SPARSE_BATCH_MAX_DIM
+_INT_MAX = 2**31 - 1
+
+# what each status code of misslap_solve_sparse_batch_status says in the words of the default mode without its host
+# guard (abi_sparse_batch.hpp, abi_batch_common.hpp: reject_bad_prices)
+_STATUS_TEXT = {
+    _lib.BATCH_STATUS_NO_ENTRIES: "no entries",
+    _lib.BATCH_STATUS_DIVISION_BY_ZERO: "division by zero",
+    _lib.BATCH_STATUS_TOO_FEW_VALUES: "Matrix is infeasible - Fewer than {N} valid values provided for {N} rows.",
+    _lib.BATCH_STATUS_INFEASIBLE: "Matrix is infeasible (Maximum matching possible only involves {card} out of {n} rows.)",
+    _lib.BATCH_STATUS_ROWS_UNSORTED: "loc rows must be sorted in ascending order (auction_.pyx:33-48 contract)",
+    _lib.BATCH_STATUS_ROW_GAP: "every row 0..N-1 must have at least one entry (auction_.pyx:33-48 contract)",
+    _lib.BATCH_STATUS_INFINITE_VALUE: "val holds a NaN or an infinity",
+    _lib.BATCH_STATUS_PRICES_TOO_NARROW: "prices hold {P} columns, the problem has {m}",
+    _lib.BATCH_STATUS_PRICE_NOT_FINITE: "prices hold a NaN or an infinity",
+    _lib.BATCH_STATUS_PRICE_NEGATIVE: "prices must be >= 0 (with the sign bit clear: -0.0 is rejected)",
+}
 
 
 def _pack(pairs):
@@ -90,7 +106,7 @@ def _check_sizes(sizes, B):
 
 
 def auction_solve_sparse_batch(loc, val=None, offsets=None, problem="min", eps_start=0., max_iter=1000000, fast=False,
-                               sizes=None, cardinality_check=True, prices=None):
+                               sizes=None, cardinality_check=True, prices=None, errors="raise", dims=None):
     """Solve B independent sparse problems in one call, one workgroup per problem.
 
     loc: int32 (nnz, 2) and val: float64 (nnz,), both numpy arrays or both contiguous tensors on the device (read in place,
@@ -106,7 +122,33 @@ def auction_solve_sparse_batch(loc, val=None, offsets=None, problem="min", eps_s
     All or nothing: a failing problem raises ValueError("problem <b>: <what from_sparse raises for it>") and nothing is
     solved.  The one check made before the call is `fast` with N_b = 0 (ZeroDivisionError, as from_sparse raises it).
     The caller's arrays are never written, problem='min' included.
+
+    errors="status": a verdict per problem instead.  The call only raises for what is wrong with the whole call (dtypes,
+    the shapes of loc / val / offsets / sizes / prices, a NaN eps_start, dims); the result also holds status (int32 (B,),
+    the MISSLAP_BATCH_STATUS_* codes of include/misslap.h) and matching_size (int32 (B,), the device guard's cardinality,
+    -1 where it did not run).  Every problem with status 0 is solved, with exactly the default mode's results; the others
+    have sol -1, prices 0 and a meta of n_rows, n_cols, nnz and zeros.  status[b] is the first check problem b fails in
+    the default mode's order without its host guard: no entries, `fast` with N = 0, fewer entries than N, the matching
+    guard (cardinality_check, on every graph that is clean -- rows ascending from 0 without a gap, no negative index --
+    and within the cap), a negative index, rows not ascending, a row gap, a NaN / infinity in val, beyond dims or the cap,
+    prices with fewer columns than the problem (prices may have any P >= 1 here), a bad starting price.  The one
+    difference from the default mode: for a graph that is not clean or beyond the cap, the default mode with
+    cardinality_check lets its host guard speak first ("loc entry ... outside", "rows must be sorted", an
+    infeasibility); this mode does no host work and reports the structural code, with matching_size -1.  The guard
+    always runs on the device here.  raise_for_status(res) raises what the default mode with cardinality_check=False
+    raises for those codes (ZeroDivisionError for `fast` with N = 0).
+    dims=(Nmax, Mmax), each 1 .. MISSLAP_SPARSE_BATCH_MAX_DIM: the caller's bound on every problem's rows and columns;
+    sol is (B, Nmax), prices (B, Mmax), and a problem beyond them gets MISSLAP_BATCH_STATUS_TOO_LARGE and is not solved.
+    With loc / val on the device the call is stream-ordered: its kernels go onto torch.cuda.current_stream(loc.device),
+    and sol, prices, status, matching_size and the meta fields are device tensors ordered on that stream
+    (batch_meta_to_host(res) gives the default mode's meta dict).  With dims it waits for nothing and copies nothing
+    back; without dims the maxima of loc are read back once before the call, the mode's only wait.  offsets stays a host
+    array; sizes and prices may be host arrays (sent from pinned memory without a wait), prices also a device tensor.
     """
+    if errors not in ("raise", "status"):
+        raise ValueError(f"errors must be 'raise' or 'status', got {errors!r}")
+    if dims is not None and errors != "status":
+        raise ValueError("dims is taken with errors='status' only")
     if isinstance(loc, (list, tuple)):
         if val is not None or offsets is not None:
             raise TypeError("a list of (loc, val) pairs takes no val / offsets; packed loc and val are numpy arrays or "
@@ -117,6 +159,9 @@ def auction_solve_sparse_batch(loc, val=None, offsets=None, problem="min", eps_s
     e = float(eps_start)
     if e != e:
         raise ValueError("eps_start is NaN")
+    if errors == "status":
+        return _solve_status(loc, val, B, nnz, off, on_device, problem, e, max_iter, fast, szs, cardinality_check, prices,
+                             dims)
     max_row, max_col, rows = _maxima(loc, off, on_device, per_problem=fast and szs is None)
     Nmax = min(max(max_row + 1, 1), MAX_DIM)  # (a problem beyond the cap is rejected by the library, in its order)
     Mmax = min(max(max_col + 1, 1), MAX_DIM)
@@ -152,3 +197,101 @@ def auction_solve_sparse_batch(loc, val=None, offsets=None, problem="min", eps_s
         1 if cardinality_check else 0, C.byref(opts), C.c_void_p(sol_ptr), Nmax, C.c_void_p(pout_ptr), Mmax,
         1 if on_device else 0, metas, C.byref(info)))
     return dict(sol=sol, prices=pout, meta=_decode_meta(metas, info))
+
+
+def _check_dims(dims):
+    try:
+        ok = len(dims) == 2 and all(int(d) == d and 1 <= int(d) <= MAX_DIM for d in dims)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"dims must be (Nmax, Mmax), each an integer in 1 .. {MAX_DIM} (MISSLAP_SPARSE_BATCH_MAX_DIM), "
+                         f"got {dims!r}")
+    return int(dims[0]), int(dims[1])
+
+
+def _status_prices(prices, B, on_device, loc):
+    """Starting prices of a status-mode call: float64 (B, P), any P >= 1 (a problem with more columns gets its status)."""
+    if prices is None:
+        return None
+    if isinstance(prices, np.ndarray):  # (with device input it is sent by the caller, from pinned memory)
+        return _starting_prices(prices, B, 1, False, False, loc, "loc / val")[0]
+    p = _starting_prices(prices, B, 1, False, on_device, loc, "loc / val")[0]
+    if p.device != loc.device:
+        raise ValueError(f"prices are on {p.device}, loc on {loc.device}")
+    return p
+
+
+def _solve_status(loc, val, B, nnz, off, on_device, problem, e, max_iter, fast, szs, cardinality_check, prices, dims):
+    """errors="status" of auction_solve_sparse_batch (misslap_solve_sparse_batch_status)."""
+    check = 1 if cardinality_check else 0
+    p = _status_prices(prices, B, on_device, loc)  # (a host array, or with device input possibly a device tensor)
+    if dims is not None:
+        Nmax, Mmax = _check_dims(dims)
+    else:  # as the default mode sizes its outputs; with device input this is the mode's one read-back
+        max_row, max_col, _ = _maxima(loc, off, on_device, per_problem=False)
+        Nmax, Mmax = min(max(max_row + 1, 1), MAX_DIM), min(max(max_col + 1, 1), MAX_DIM)
+    opts = _solve_options(on_device, loc, problem, e, max_iter)
+    lib = _lib.load()
+    common = dict(layout="sparse", dims=(Nmax, Mmax), sizes=szs, offsets=off, loc=loc,
+                  prices_ld=0 if p is None else int(p.shape[1]))
+    if not on_device:  # synchronous: the library uploads, uses its own scratch and waits once
+        lc, vc = np.ascontiguousarray(loc), np.ascontiguousarray(val)
+        sol, pout = np.empty((B, Nmax), dtype=np.int32), np.empty((B, Mmax), dtype=np.float64)
+        status, msize = np.empty(B, dtype=np.int32), np.empty(B, dtype=np.int32)
+        metas, info = _new_meta(B)
+        _lib.check(lib.misslap_solve_sparse_batch_status(
+            B, lc.ctypes.data, vc.ctypes.data, off.ctypes.data, None, None if szs is None else szs.ctypes.data,
+            1 if fast else 0, None if p is None else p.ctypes.data, common["prices_ld"], check, C.byref(opts), None, None,
+            0, Nmax, Mmax, sol.ctypes.data, pout.ctypes.data, 0, status.ctypes.data, msize.ctypes.data,
+            C.cast(metas, C.c_void_p), C.byref(info)))
+        return dict(sol=sol, prices=pout, status=status, matching_size=msize, meta=_decode_meta(metas, info), **common)
+    import torch
+    from .dense_batch import _meta_views
+    dev = loc.device
+
+    def send(a):  # a host array from pinned memory, without a wait
+        return None if a is None else torch.from_numpy(a).pin_memory().to(dev, non_blocking=True)
+    with torch.cuda.device(dev):  # (the allocations and copies below are made on the current stream of loc's device)
+        stream = torch.cuda.current_stream(dev)
+        d_off, d_sizes = send(off), send(szs)
+        d_p = send(p) if isinstance(p, np.ndarray) else p
+        nbytes = int(lib.misslap_sparse_batch_workspace_bytes(B, nnz, 0 if p is None else 1, check))
+        work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        sol = torch.empty((B, Nmax), dtype=torch.int32, device=dev)
+        pout = torch.empty((B, Mmax), dtype=torch.float64, device=dev)
+        status = torch.empty(B, dtype=torch.int32, device=dev)
+        msize = torch.empty(B, dtype=torch.int32, device=dev)
+        rec = torch.empty((B, C.sizeof(_lib.DenseBatchMeta)), dtype=torch.uint8, device=dev)
+    info = _lib.DenseBatchInfo()
+    _lib.check(lib.misslap_solve_sparse_batch_status(
+        B, loc.data_ptr(), val.data_ptr(), off.ctypes.data, d_off.data_ptr(), None if d_sizes is None else d_sizes.data_ptr(),
+        1 if fast else 0, None if d_p is None else d_p.data_ptr(), common["prices_ld"], check, C.byref(opts),
+        C.c_void_p(int(stream.cuda_stream)), work.data_ptr(), nbytes, Nmax, Mmax, sol.data_ptr(), pout.data_ptr(), 1,
+        status.data_ptr(), msize.data_ptr(), rec.data_ptr(), C.byref(info)))
+    # the workspace and the inputs stay referenced by the result: nothing of this call is recycled before it
+    return dict(sol=sol, prices=pout, status=status, matching_size=msize, meta=_meta_views(rec), records=rec, info=info,
+                stream=stream, keep=(work, loc, val, d_off, d_sizes, d_p), **common)
+
+
+def _status_error(res, b, code, n, m, card):
+    """The exception of problem b of a sparse status-mode result: what the default mode with cardinality_check=False
+    raises for the same check (n, m: the record's n_rows and n_cols; card: its matching_size)."""
+    if code == _lib.BATCH_STATUS_DIVISION_BY_ZERO:
+        return ZeroDivisionError(f"problem {b}: division by zero")
+    Nmax, Mmax = res["dims"]
+    if code == _lib.BATCH_STATUS_NEGATIVE_INDEX:
+        last_row = int(res["loc"][int(res["offsets"][b + 1]) - 1, 0])
+        text = "negative row index" if last_row < 0 else "loc holds a negative row or column index"
+    elif code == _lib.BATCH_STATUS_TOO_LARGE:
+        if m >= _INT_MAX:
+            text = "column index too large (max + 1 must fit an int32)"
+        elif n > MAX_DIM or m > MAX_DIM:
+            text = (f"{n} x {m} exceeds MISSLAP_SPARSE_BATCH_MAX_DIM ({MAX_DIM}); solve it with from_sparse / "
+                    f"solve_batch")
+        else:
+            text = f"{n} x {m} does not fit sol_ld = {Nmax} / prices_out_ld = {Mmax}"
+    else:
+        N = int(res["sizes"][b, 1]) if res["sizes"] is not None else n - 1  # from_sparse's N (sic, :592 / :594)
+        text = _STATUS_TEXT[code].format(N=N, n=n, m=m, card=card, P=res["prices_ld"])
+    return ValueError(f"problem {b}: {text}")

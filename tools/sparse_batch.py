@@ -10,17 +10,31 @@ on at most --loop-max problems and are scaled per problem.  Before anything is t
 problem by problem with the loop and with the dense batch.  One JSON line per (shape, check, path).  Needs the GPU.
 
   python tools/sparse_batch.py [--reps 5] [--out profiles/sparse_batch.jsonl] [--shapes 1x10x3,1024x64x8]
+
+--status times the status mode (auction_solve_sparse_batch(errors="status", dims=(N, N))) against the default mode
+instead, on device tensors with the cardinality check on, legs interleaved within every repetition:
+  a  default mode, wall time of the call (it synchronises itself)
+  b  status mode, host time of the call (it returns once its launches are enqueued)
+  c  status mode, the call plus torch.cuda.synchronize(); stream_ms is the time of its kernels from events around it
+  d  as c, on a copy of the batch in which every fourth problem holds a +inf (status 3: its workgroup leaves at once)
+With --parent-tree DIR (a built checkout of the commit to compare with) leg a is also run there, as `a_parent`, by a
+child process of this script per round, the rounds alternating between the two trees.
+
+  python tools/sparse_batch.py --status [--reps 30] [--rounds 3] [--parent-tree DIR] [--out profiles/sparse_batch_status.jsonl]
 """
 import argparse
 import json
 import os
+import subprocess
 import sys
 import time
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+# (--tree: the package of another checkout, for the child process of --status --parent-tree)
+TREE = sys.argv[sys.argv.index("--tree") + 1] if "--tree" in sys.argv else ROOT
+sys.path.insert(0, TREE)
 
 SHAPES = ((1, 10, 3), (1024, 64, 8), (1024, 256, 8), (256, 1024, 16), (64, 2048, 16))  # (B, N, entries per row)
 
@@ -48,13 +62,114 @@ def densify(loc, val, offsets, N):
     return mats
 
 
+def status_times(shapes, reps, legs):
+    """{(B, N, leg): [ms per repetition]} (and "stream_ms" lists for c and d), the legs interleaved within a repetition."""
+    import torch
+    from sslap_amd import auction_solve_sparse_batch
+    sync = torch.cuda.synchronize
+    out = {}
+    for B, N, k in shapes:
+        loc, val, off = batch(B, N, k, seed=B * 7919 + N)
+        dl, dv = torch.from_numpy(loc).cuda(), torch.from_numpy(val).cuda()
+        val[off[:-1][::4]] = np.inf
+        quarter = torch.from_numpy(val).cuda()
+        st = dict(errors="status", dims=(N, N))
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        if "c" in legs:  # the two modes give the same results at the sizes that are timed
+            want, got, part = (auction_solve_sparse_batch(dl, dv, off), auction_solve_sparse_batch(dl, dv, off, **st),
+                               auction_solve_sparse_batch(dl, quarter, off, **st))
+            assert torch.equal(want["sol"], got["sol"]) and not got["status"].any()
+            assert torch.equal(want["prices"].view(torch.int64), got["prices"].view(torch.int64))
+            keep = part["status"] == 0
+            assert int(keep.sum()) == B - len(range(0, B, 4)) and torch.equal(part["sol"][keep], want["sol"][keep])
+            assert bool((part["status"][~keep] == 3).all()) and bool((part["sol"][~keep] == -1).all())
+
+        def run(leg):
+            sync()
+            t0 = time.perf_counter()
+            if leg in ("a", "a_parent"):
+                auction_solve_sparse_batch(dl, dv, off)
+            elif leg == "b":
+                auction_solve_sparse_batch(dl, dv, off, **st)
+            else:
+                ev[0].record()
+                auction_solve_sparse_batch(dl, dv if leg == "c" else quarter, off, **st)
+                ev[1].record()
+                sync()
+            t = (time.perf_counter() - t0) * 1e3
+            sync()
+            return t, ev[0].elapsed_time(ev[1]) if leg in ("c", "d") else None
+
+        for leg in legs:  # warm-up
+            run(leg)
+        for r in range(reps):
+            for leg in legs[r % len(legs):] + legs[:r % len(legs)]:  # (no leg always runs behind the same other)
+                t, g = run(leg)
+                out.setdefault((B, N, leg), []).append(t)
+                if g is not None:
+                    out.setdefault((B, N, leg + ":stream_ms"), []).append(g)
+    return out
+
+
+def status_main(args, shapes):
+    """The --status legs; as a child (--legs a_parent) the times go to stdout as one JSON line."""
+    if args.legs:
+        t = status_times(shapes, args.reps, args.legs.split(","))
+        print("TIMES " + json.dumps({f"{B}x{N}/{leg}": v for (B, N, leg), v in t.items()}), flush=True)
+        return
+    import torch
+    torch.zeros(1).cuda()
+    times = {}
+    per_round = -(-args.reps // args.rounds)
+    for _ in range(args.rounds):
+        if args.parent_tree:
+            cmd = [sys.executable, os.path.abspath(__file__), "--status", "--tree", args.parent_tree, "--legs", "a_parent",
+                   "--reps", str(per_round), "--shapes", ",".join(f"{B}x{N}x{k}" for B, N, k in shapes)]
+            txt = subprocess.run(cmd, check=True, capture_output=True, text=True, timeout=900).stdout
+            line = [x for x in txt.splitlines() if x.startswith("TIMES ")][-1]
+            for key, v in json.loads(line[6:]).items():
+                bn, leg = key.split("/")
+                B, N = (int(x) for x in bn.split("x"))
+                times.setdefault((B, N, leg), []).extend(v)
+        for key, v in status_times(shapes, per_round, ["a", "b", "c", "d"]).items():
+            times.setdefault(key, []).extend(v)
+    per_row = {(B, N): k for B, N, k in shapes}
+    rows = []
+    for (B, N, leg), v in times.items():
+        if ":" in leg:
+            continue
+        row = dict(B=B, N=N, per_row=per_row[(B, N)], leg=leg, reps=len(v), median_ms=round(float(np.median(v)), 4),
+                   p10_ms=round(float(np.percentile(v, 10)), 4), p90_ms=round(float(np.percentile(v, 90)), 4))
+        g = times.get((B, N, leg + ":stream_ms"))
+        if g:
+            row["stream_ms"] = round(float(np.median(g)), 4)
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        for row in rows:
+            f.write(json.dumps(row) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "sparse_batch.jsonl"))
+    ap.add_argument("--reps", type=int, default=None)
+    ap.add_argument("--out", default=None)
     ap.add_argument("--shapes", default=None, help="BxNxK,... (K = entries per row)")
     ap.add_argument("--loop-max", type=int, default=256, help="time the per-problem paths on at most so many problems")
+    ap.add_argument("--status", action="store_true", help="time the status mode against the default mode")
+    ap.add_argument("--rounds", type=int, default=3, help="--status: the repetitions are split over so many rounds")
+    ap.add_argument("--parent-tree", default=None, help="--status: a built checkout whose default mode is leg a_parent")
+    ap.add_argument("--tree", default=None, help="(child of --parent-tree) import sslap_amd from this checkout")
+    ap.add_argument("--legs", default=None, help="(child of --parent-tree) time these legs only, print the raw times")
     args = ap.parse_args()
+    if args.reps is None:
+        args.reps = 30 if args.status else 5
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "sparse_batch_status.jsonl" if args.status else "sparse_batch.jsonl")
+    if args.status:
+        return status_main(args, SHAPES if not args.shapes else
+                           [tuple(int(x) for x in p.split("x")) for p in args.shapes.split(",")])
     import torch
     from sslap_amd import AuctionSolver, auction_solve, auction_solve_batch, auction_solve_sparse_batch, from_sparse
     shapes = SHAPES if not args.shapes else [tuple(int(x) for x in p.split("x")) for p in args.shapes.split(",")]
