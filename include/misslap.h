@@ -33,7 +33,15 @@ extern "C" {
  *      validity flags of the assignment, misslap_trim_caches.  Additions since: the warm-start entry points,
  *      misslap_solve_dense_batch, misslap_solve_sparse_batch, misslap_solve_dense_batch_status,
  *      misslap_dense_batch_workspace_bytes, misslap_solve_sparse_batch_status, misslap_sparse_batch_workspace_bytes
- *      (with MISSLAP_BATCH_STATUS_NO_ENTRIES .. MISSLAP_BATCH_STATUS_PRICES_TOO_NARROW, codes 8 .. 14). */
+ *      (with MISSLAP_BATCH_STATUS_NO_ENTRIES .. MISSLAP_BATCH_STATUS_PRICES_TOO_NARROW, codes 8 .. 14),
+ *      misslap_options.mat_dtype with MISSLAP_DTYPE_F64 .. MISSLAP_DTYPE_BF16 (the first word of reserved[], which
+ *      had to be 0 = MISSLAP_DTYPE_F64 until then; size and offsets of the struct did not change). */
+
+/* misslap_options.mat_dtype: the element type of a dense stack */
+#define MISSLAP_DTYPE_F64 0   /* double */
+#define MISSLAP_DTYPE_F32 1   /* float */
+#define MISSLAP_DTYPE_F16 2   /* IEEE binary16 */
+#define MISSLAP_DTYPE_BF16 3  /* bfloat16: the upper 16 bits of a float */
 
 #define MISSLAP_OK 0
 #define MISSLAP_ERR_INVALID 1    /* malformed arguments / input contract violated */
@@ -42,6 +50,13 @@ extern "C" {
 #define MISSLAP_ERR_STATE 4      /* call not valid in the handle's current state */
 
 typedef struct misslap_solver misslap_solver;
+
+/* an anonymous union is C11 and C++; this lets a strict C99 build of a GNU-compatible compiler take it as well */
+#if defined(__GNUC__) && !defined(__cplusplus) && (!defined(__STDC_VERSION__) || __STDC_VERSION__ < 201112L)
+#define MISSLAP_ANONYMOUS __extension__
+#else
+#define MISSLAP_ANONYMOUS
+#endif
 
 /* Options of misslap_create.  Zero-initialise, set struct_size = sizeof, then fill. */
 typedef struct misslap_options {
@@ -78,7 +93,13 @@ typedef struct misslap_options {
     int32_t cand_build_max_K;/* > 0: k_bid (re)builds lines only in rounds with at most so many bidders */
     int32_t cand_refresh_min;/* r + 1: a line hit with fewer than r live candidates is rebuilt by k_bid (0 = library
                                 default, 1 = never) */
-    int32_t reserved[7];     /* must be zero */
+    MISSLAP_ANONYMOUS union { /* seven words that had to be zero; the first one now has a name, and nothing moved */
+        int32_t mat_dtype;   /* MISSLAP_DTYPE_*: the element type of `mat` in misslap_solve_dense_batch,
+                                misslap_solve_dense_batch_status and misslap_matching_dense_batch (see there); every
+                                other entry point takes float64 only and rejects a non-zero value.  An ABI-1 struct
+                                and a shorter ABI-2 struct mean 0 */
+        int32_t reserved[7]; /* reserved[0] is mat_dtype; reserved[1..6] must be zero */
+    };
     void *input_stream;      /* input_on_device only: the hipStream_t the caller's buffers were produced on.  The library
                                 then orders its own stream behind that one with an event instead of waiting for the
                                 whole device (NULL: hipDeviceSynchronize before the inputs are read -- always safe, but
@@ -431,8 +452,8 @@ int misslap_solve_batch(misslap_solver *const *handles, int32_t n, int32_t *cons
  * entry; negatives and NaN are not, auction_.pyx:546-557).  Each problem is solved by ONE workgroup of ONE launch, its
  * whole state in LDS (csrc/kernels_dense_batch.hpp), and its result is exactly what _from_matrix(mat[b][:n_b][:m_b],
  * ...).solve() returns: same assignment, its, nreductions, eCE, objective and price bits.
- *   opt            device, maximize, eps_start, max_iter, input_on_device (mat and prices_in are device pointers) and
- *                  input_stream (as for misslap_create_dense); every other field must be 0.
+ *   opt            device, maximize, eps_start, max_iter, mat_dtype (below), input_on_device (mat and prices_in are device
+ *                  pointers) and input_stream (as for misslap_create_dense); every other field must be 0.
  *   eps_start      float[B] host array or NULL: problem b's eps_start (> 0 overrides C / 2, auction_.pyx:251-252); NULL =
  *                  opt->eps_start for every problem.  (The front-end's `fast` passes 1 / n_b here, :568-569.)
  *   prices_in      double[B][M] or NULL: problem b starts from prices_in[b][:m_b] as misslap_resolve does (every person
@@ -449,7 +470,17 @@ int misslap_solve_batch(misslap_solver *const *handles, int32_t n, int32_t *cons
  * text "problem <b>: <what _from_matrix raises for that slice>" for the first failing b, in _from_matrix's order: fewer
  * valid values than rows, an empty row, +inf, the matching guard, then bad starting prices.  N and M are at most
  * MISSLAP_DENSE_BATCH_MAX_DIM (larger problems: misslap_create_dense / misslap_solve_batch).  Every solve ends after at
- * most max_iter rounds. */
+ * most max_iter rounds.
+ *   The element type of mat is opt->mat_dtype (MISSLAP_DTYPE_F64 = 0, _F32, _F16, _BF16).  The parameter keeps its
+ * declared type: with another mat_dtype, pass the stack's address cast to const double *.  mat then points to B * N * M
+ * elements of that type, read in place: strides are counted in elements and only the element's own alignment is needed
+ * (a row of a 2-byte stack may start on any 2-byte boundary), on the host and on the device, with and without a
+ * workspace (misslap_dense_batch_workspace_bytes does not depend on the type).  An entry is valid iff v >= 0 in its own
+ * type -- the same set as after widening: -0.0 and +inf are entries, NaN and negatives are not -- and +inf is
+ * MISSLAP_BATCH_STATUS_INFINITE_VALUE as before.  Every value is widened to double as it is read, which is exact
+ * (binary16 subnormals included), and everything downstream is the double arithmetic of the float64 path on that value:
+ * C = max |v|, eps0, bids, prices, eCE, obj_f64, obj_f32.  prices_in, prices_out and meta stay float64.  The result is
+ * bit for bit that of the same call on the widened stack.  A mat_dtype outside 0 .. 3 is MISSLAP_ERR_INVALID. */
 #define MISSLAP_DENSE_BATCH_MAX_DIM 1024
 typedef struct misslap_dense_batch_meta {
     int32_t struct_size;  /* IN (element 0 only): sizeof(misslap_dense_batch_meta); the stride of the array */
@@ -651,8 +682,11 @@ int64_t misslap_sparse_batch_workspace_bytes(int64_t B, int64_t nnz, int32_t has
  *   misslap_matching_dense_batch  mat is double[B][N][M] (problem stride N * M, counted in 64 bits); graph b is
  *                                 mat[b][:n_b][:m_b] with (n_b, m_b) = shapes[2b], shapes[2b + 1] (shapes NULL: N x M),
  *                                 entry (i, j) iff mat[b][i][j] >= 0 (:256-262; NaN is not an entry, -0.0 and +inf are).
+ *                                 The element type of mat is opt->mat_dtype, as for misslap_solve_dense_batch (the
+ *                                 parameter keeps its declared type; the pairings are those of the widened stack).
  *   opt            device, input_on_device (loc / mat are device pointers) and input_stream, as for the batch solves;
- *                  maximize, eps_start and max_iter are ignored, every other field must be 0.
+ *                  mat_dtype for misslap_matching_dense_batch; maximize, eps_start and max_iter are ignored, every
+ *                  other field must be 0.
  *   size, n_rows, n_cols   host int32[B]: the cardinality and the graph's dimensions.
  *   left_pairings  int32[B][left_ld] or NULL: Pair_U of graph b in [:n_b], -1 beyond (and for a free row).
  *   right_pairings int32[B][right_ld] or NULL: Pair_V of graph b in [:m_b], -1 beyond.

@@ -16,22 +16,51 @@ def _is_device_tensor(x):
     return hasattr(x, "data_ptr") and getattr(x, "is_cuda", False)
 
 
-def _check_stack(mats):
-    """dtype / rank / layout of a float64 (B, N, M) stack (numpy array or device tensor); returns (B, N, M, on_device).
-    The cap is the caller's check."""
+# mat_dtype: the element types a dense stack may have (MISSLAP_DTYPE_* of include/misslap.h)
+_MAT_DTYPES = {"float64": _lib.DTYPE_F64, "float32": _lib.DTYPE_F32, "float16": _lib.DTYPE_F16,
+               "bfloat16": _lib.DTYPE_BF16}
+
+
+def _mat_dtype_name(mat_dtype):
+    """The name of a mat_dtype keyword: one of the four names, or the numpy / torch dtype object of one."""
+    if isinstance(mat_dtype, str):
+        name = mat_dtype
+    elif type(mat_dtype).__module__.split(".")[0] == "torch":
+        name = str(mat_dtype).split(".")[-1]
+    elif isinstance(mat_dtype, (np.dtype, type)):  # (np.dtype(None) is float64: only a dtype or a scalar type names one)
+        try:
+            name = np.dtype(mat_dtype).name
+        except TypeError:
+            name = repr(mat_dtype)
+    else:
+        name = repr(mat_dtype)
+    if name not in _MAT_DTYPES:
+        raise ValueError(f"mat_dtype must be one of {', '.join(_MAT_DTYPES)} (or that numpy / torch dtype), got {mat_dtype!r}")
+    return name
+
+
+def _check_stack(mats, mat_dtype="float64"):
+    """dtype / rank / layout of a (B, N, M) stack of mat_dtype (numpy array or device tensor); returns (B, N, M,
+    on_device, the MISSLAP_DTYPE_* code).  The stack must have exactly that dtype: nothing is converted.  The cap is the
+    caller's check."""
+    want = _mat_dtype_name(mat_dtype)
     if isinstance(mats, np.ndarray):
         on_device = False
         if mats.ndim != 3:
             raise ValueError(f"mats must have 3 dimensions (B, N, M), got {mats.ndim}")
-        if mats.dtype != np.float64:
+        if mats.dtype != np.float64 and want == "float64":
             raise ValueError(f"Buffer dtype mismatch, expected 'double' but got '{_cname(mats.dtype)}'")
+        if mats.dtype.name != want:
+            raise ValueError(f"Buffer dtype mismatch, expected '{want}' (mat_dtype) but got '{mats.dtype.name}'")
     elif _is_device_tensor(mats):
         import torch
         on_device = True
         if mats.dim() != 3:
             raise ValueError(f"mats must have 3 dimensions (B, N, M), got {mats.dim()}")
-        if mats.dtype != torch.float64:
+        if mats.dtype != torch.float64 and want == "float64":
             raise ValueError(f"mats must be float64, got {mats.dtype}")
+        if mats.dtype != getattr(torch, want):
+            raise ValueError(f"mats dtype mismatch: mat_dtype is {want}, the tensor is {mats.dtype}")
         if not mats.is_contiguous():
             raise ValueError("a device tensor must be contiguous (it is read in place)")
     else:
@@ -39,7 +68,7 @@ def _check_stack(mats):
     B, N, M = (int(d) for d in mats.shape)
     if B < 1 or N < 1 or M < 1:
         raise ValueError(f"empty stack of shape {(B, N, M)}")
-    return B, N, M, on_device
+    return B, N, M, on_device, _MAT_DTYPES[want]
 
 
 def _check_shapes(shapes, B, N, M, what):
@@ -155,10 +184,10 @@ def _options(on_device, src, **fields):
     return opts
 
 
-def _solve_options(on_device, src, problem, eps_start, max_iter):
+def _solve_options(on_device, src, problem, eps_start, max_iter, mat_dtype=_lib.DTYPE_F64):
     # (every string other than 'min' is 'max', auction_.pyx:236)
     return _options(on_device, src, maximize=1 if problem != "min" else 0, eps_start=float(np.float32(eps_start)),
-                    max_iter=int(max_iter))
+                    max_iter=int(max_iter), mat_dtype=mat_dtype)
 
 
 def _new_meta(B):

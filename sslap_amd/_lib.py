@@ -10,7 +10,17 @@ LIB_PATH = os.environ.get("MISSLAP_LIB") or os.path.join(_PKG, "libmisslap.so")
 MISSLAP_OK, ERR_INVALID, ERR_HIP, ERR_NO_DEVICE, ERR_STATE = 0, 1, 2, 3, 4
 
 
+# misslap_options.mat_dtype: the element type of a dense stack
+DTYPE_F64, DTYPE_F32, DTYPE_F16, DTYPE_BF16 = range(4)
+
+
+class _DtypeOrReserved(C.Union):
+    """The header's anonymous union: mat_dtype is the first word of reserved[7]."""
+    _fields_ = [("mat_dtype", C.c_int32), ("reserved", C.c_int32 * 7)]
+
+
 class Options(C.Structure):
+    _anonymous_ = ("_typed",)
     _fields_ = [
         ("struct_size", C.c_int32), ("device", C.c_int32), ("maximize", C.c_int32), ("eps_start", C.c_float),
         ("max_iter", C.c_int64), ("input_on_device", C.c_int32), ("tail_threshold", C.c_int32),
@@ -20,7 +30,7 @@ class Options(C.Structure):
         ("tiled_min_K", C.c_int32), ("tiled_shape", C.c_int32), ("tiled_force", C.c_int32),
         ("shard_min_K", C.c_int32), ("cand_mode", C.c_int32), ("partial_in_list_order", C.c_int32),
         ("nnz_limit", C.c_int32), ("cand_build_max_K", C.c_int32), ("cand_refresh_min", C.c_int32),
-        ("reserved", C.c_int32 * 7),
+        ("_typed", _DtypeOrReserved),  # mat_dtype / reserved
         ("input_stream", C.c_void_p),
     ]
 

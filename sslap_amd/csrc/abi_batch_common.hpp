@@ -6,11 +6,13 @@
 #pragma once
 
 namespace {
-// normalise_options, then `who` takes the fields listed in `takes` only (the solver's other options must be 0)
-int batch_options(const misslap_options *opt_in, misslap_options *opt, const char *who, const char *takes) {
+// normalise_options, then `who` takes the fields listed in `takes` only (the solver's other options must be 0);
+// typed_mat: `who` reads mat_dtype (the dense stacks), every other entry point takes float64 only
+int batch_options(const misslap_options *opt_in, misslap_options *opt, const char *who, const char *takes,
+                  bool typed_mat = false) {
     int abi = 0;
     int rc = normalise_options(opt_in, opt, &abi);
-    if (rc) return rc;
+    if (rc || (!typed_mat && (rc = float64_only(*opt, who)))) return rc;
     if (opt->tail_threshold > 0 || opt->force_f64_values || opt->profile || opt->shard_world > 1 || opt->rounds_per_sync ||
         opt->tiled_min_K || opt->tiled_shape || opt->tiled_force || opt->shard_min_K || opt->cand_mode || opt->nnz_limit ||
         opt->cand_build_max_K || opt->cand_refresh_min)

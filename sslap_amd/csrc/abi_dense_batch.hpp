@@ -11,8 +11,36 @@ inline bool dense_entry_valid_host(double v) {
     return b <= 0x7ff0000000000000ull || b == 0x8000000000000000ull;
 }
 
+template <class T>
+inline bool dense_entry_valid_host(T v) {  // float, F16, Bf16: by bit pattern in the element's own type (device_common.hpp)
+    return dense_entry_valid(v);
+}
+
+// f(T{}) with T the element type mat_dtype names (normalise_options has checked the range)
+template <class F>
+auto dense_dtype_dispatch(int32_t mat_dtype, F &&f) {
+    switch (mat_dtype) {
+    case MISSLAP_DTYPE_F32: return f(float{});
+    case MISSLAP_DTYPE_F16: return f(F16{});
+    case MISSLAP_DTYPE_BF16: return f(Bf16{});
+    default: return f(double{});
+    }
+}
+inline size_t dense_dtype_bytes(int32_t mat_dtype) {
+    return dense_dtype_dispatch(mat_dtype, [](auto t) { return sizeof(t); });
+}
+
+// a host stack of `cells` elements of mat_dtype into a new scratch buffer on the device (*d), copied on st
+int upload_stack(DevScratch &tmp, const void **d, const void *h, size_t cells, int32_t mat_dtype, hipStream_t st) {
+    const char *p = nullptr;
+    const int rc = upload(tmp, &p, h, cells * dense_dtype_bytes(mat_dtype), st);
+    *d = p;
+    return rc;
+}
+
 // maximum-matching cardinality of one dense slice (row stride M): the guard of _from_matrix (auction_.pyx:562-566)
-int dense_slice_matching(const double *A, int64_t M, int n, int m) {
+template <class T>
+int dense_slice_matching(const T *A, int64_t M, int n, int m) {
     std::vector<int32_t> loc;
     loc.reserve((size_t)n * 2 * 8);
     for (int i = 0; i < n; ++i)
@@ -55,7 +83,7 @@ MISSLAP_API int misslap_solve_dense_batch(int64_t B, int64_t N, int64_t M, const
     const double t_start = now_ms();
     misslap_options opt;
     int rc = batch_options(opt_in, &opt, "misslap_solve_dense_batch",
-                           "device, maximize, eps_start, max_iter, input_on_device and input_stream");
+                           "device, maximize, eps_start, max_iter, mat_dtype, input_on_device and input_stream", true);
     if (rc) return rc;
     if (!mat || !sol) return fail(MISSLAP_ERR_INVALID, "null mat / sol");
     if ((rc = dense_batch_dims(B, N, M))) return rc;
@@ -67,9 +95,10 @@ MISSLAP_API int misslap_solve_dense_batch(int64_t B, int64_t N, int64_t M, const
 
     const size_t cells = (size_t)B * (size_t)N * (size_t)M, pcells = (size_t)B * (size_t)M;
     DevScratch tmp;
-    const double *d_mat = mat, *d_p0 = prices_in;
-    if (!opt.input_on_device &&
-        ((rc = upload(tmp, &d_mat, mat, cells, st)) || (prices_in && (rc = upload(tmp, &d_p0, prices_in, pcells, st)))))
+    const void *d_mat = mat;  // elements of opt.mat_dtype, whatever the parameter's declared type
+    const double *d_p0 = prices_in;
+    if (!opt.input_on_device && ((rc = upload_stack(tmp, &d_mat, mat, cells, opt.mat_dtype, st)) ||
+                                 (prices_in && (rc = upload(tmp, &d_p0, prices_in, pcells, st)))))
         return rc;
     const int *d_shapes = nullptr;
     const float *d_eps = nullptr;
@@ -79,8 +108,11 @@ MISSLAP_API int misslap_solve_dense_batch(int64_t B, int64_t N, int64_t M, const
         return rc;
 
     // ---- validation: every problem before any is solved
-    hipLaunchKernelGGL(k_dense_batch_check, dim3((unsigned)B), dim3(256), 0, st, d_mat, (long long)N, (long long)M,
-                       d_shapes, d_p0, d_chk, (int *)nullptr);
+    dense_dtype_dispatch(opt.mat_dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(k_dense_batch_check<T>, dim3((unsigned)B), dim3(256), 0, st, static_cast<const T *>(d_mat),
+                           (long long)N, (long long)M, d_shapes, d_p0, d_chk, (int *)nullptr);
+    });
     HIP_TRY(hipGetLastError());
     // the matching guard of every problem on the device, behind the validation pass and read back with it
     const bool device_guard = cardinality_check && dense_guard_on_device(B);
@@ -99,8 +131,10 @@ MISSLAP_API int misslap_solve_dense_batch(int64_t B, int64_t N, int64_t M, const
         g.size = d_card;
         if ((rc = gev.create())) return rc;
         HIP_TRY(hipEventRecord(gev.e[0], st));
-        hipLaunchKernelGGL(k_matching_batch<true>, dim3((unsigned)B), dim3(kMatchBatchThreads),
-                           matching_batch_lds_bytes(N, M, true), st, g);
+        dense_dtype_dispatch(opt.mat_dtype, [&](auto t) {
+            hipLaunchKernelGGL((k_matching_batch<true, decltype(t)>), dim3((unsigned)B), dim3(kMatchBatchThreads),
+                               matching_batch_lds_bytes(N, M, true), st, g);
+        });
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(gev.e[1], st));
         card.assign((size_t)B, -1);
@@ -133,11 +167,11 @@ MISSLAP_API int misslap_solve_dense_batch(int64_t B, int64_t N, int64_t M, const
     };
     if (cardinality_check && !device_guard) {
         // the host copy of the matrix the guard reads (device input: copied back once)
-        std::vector<double> host_copy;
-        const double *H = mat;
+        std::vector<unsigned char> host_copy;
+        const void *H = mat;
         if (opt.input_on_device) {
-            host_copy.resize(cells);
-            HIP_TRY(hipMemcpy(host_copy.data(), mat, sizeof(double) * cells, hipMemcpyDeviceToHost));
+            host_copy.resize(cells * dense_dtype_bytes(opt.mat_dtype));
+            HIP_TRY(hipMemcpy(host_copy.data(), mat, host_copy.size(), hipMemcpyDeviceToHost));
             H = host_copy.data();
         }
         card.assign((size_t)B, -1);
@@ -146,7 +180,9 @@ MISSLAP_API int misslap_solve_dense_batch(int64_t B, int64_t N, int64_t M, const
             if (first_error(b, buf, sizeof(buf))) return;
             int n, m;
             dims(b, n, m);
-            card[(size_t)b] = dense_slice_matching(H + (size_t)b * (size_t)N * (size_t)M, M, n, m);
+            card[(size_t)b] = dense_dtype_dispatch(opt.mat_dtype, [&](auto t) {
+                return dense_slice_matching(static_cast<const decltype(t) *>(H) + (size_t)b * (size_t)N * (size_t)M, M, n, m);
+            });
         });
         if (rc) return rc;
     }
@@ -172,6 +208,8 @@ MISSLAP_API int misslap_solve_dense_batch(int64_t B, int64_t N, int64_t M, const
     a.M = M;
     a.shapes = d_shapes;
     a.chk = d_chk;
-    return batch_solve_run(k_dense_batch_solve, a, st, tmp, opt, B, (int)N, (int)M, sol, N, prices_out, M, out_on_device,
-                           meta, stride, info, t_start, t_checked, t_matched, guard_ms);
+    return dense_dtype_dispatch(opt.mat_dtype, [&](auto t) {
+        return batch_solve_run(k_dense_batch_solve<decltype(t)>, a, st, tmp, opt, B, (int)N, (int)M, sol, N, prices_out, M,
+                               out_on_device, meta, stride, info, t_start, t_checked, t_matched, guard_ms);
+    });
 }

@@ -19,9 +19,9 @@ struct DenseStatusCarve {
 };
 
 // The three launches of a call on st: the check pass, the guard, the solve with its verdict.  Every pointer is a device
-// pointer; nothing here allocates, waits or copies.
+// pointer (d_mat: elements of opt.mat_dtype); nothing here allocates, waits or copies.
 int dense_batch_status_enqueue(hipStream_t st, const misslap_options &opt, int64_t B, int64_t N, int64_t M,
-                               const double *d_mat, const int32_t *d_shapes, int32_t fast, const double *d_p0, bool guard,
+                               const void *d_mat, const int32_t *d_shapes, int32_t fast, const double *d_p0, bool guard,
                                void *ws, int32_t *d_sol, double *d_prices, int32_t *d_status, int32_t *d_msize,
                                misslap_dense_batch_meta *d_meta, misslap_dense_batch_info *info) {
     const DenseStatusCarve carve(B, guard);
@@ -30,8 +30,11 @@ int dense_batch_status_enqueue(hipStream_t st, const misslap_options &opt, int64
     int *d_san = reinterpret_cast<int *>(base + carve.shapes);
     int *d_card = guard ? reinterpret_cast<int *>(base + carve.card) : nullptr;
 
-    hipLaunchKernelGGL(k_dense_batch_check, dim3((unsigned)B), dim3(256), 0, st, d_mat, (long long)N, (long long)M,
-                       d_shapes, d_p0, d_chk, d_san);
+    dense_dtype_dispatch(opt.mat_dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(k_dense_batch_check<T>, dim3((unsigned)B), dim3(256), 0, st, static_cast<const T *>(d_mat),
+                           (long long)N, (long long)M, d_shapes, d_p0, d_chk, d_san);
+    });
     HIP_TRY(hipGetLastError());
     if (guard) {  // every problem's matching on the device: a shape the check pass zeroed is skipped (size -1)
         MatchBatchArgs g{};
@@ -42,8 +45,10 @@ int dense_batch_status_enqueue(hipStream_t st, const misslap_options &opt, int64
         g.Ns = (int)N;
         g.Ms = (int)M;
         g.size = d_card;
-        hipLaunchKernelGGL(k_matching_batch<true>, dim3((unsigned)B), dim3(kMatchBatchThreads),
-                           matching_batch_lds_bytes(N, M, true), st, g);
+        dense_dtype_dispatch(opt.mat_dtype, [&](auto t) {
+            hipLaunchKernelGGL((k_matching_batch<true, decltype(t)>), dim3((unsigned)B), dim3(kMatchBatchThreads),
+                               matching_batch_lds_bytes(N, M, true), st, g);
+        });
         HIP_TRY(hipGetLastError());
     }
     DenseBatchStatusArgs a{};
@@ -71,7 +76,9 @@ int dense_batch_status_enqueue(hipStream_t st, const misslap_options &opt, int64
     a.matching_size = d_msize;
     const int threads = batch_solve_threads((int)N);
     const size_t lds = batch_solve_lds_bytes(N, M);  // (at most 53 248 B at the cap: no dynamic-LDS opt-in)
-    hipLaunchKernelGGL(k_dense_batch_solve_status, dim3((unsigned)B), dim3(threads), lds, st, a);
+    dense_dtype_dispatch(opt.mat_dtype, [&](auto t) {
+        hipLaunchKernelGGL(k_dense_batch_solve_status<decltype(t)>, dim3((unsigned)B), dim3(threads), lds, st, a);
+    });
     HIP_TRY(hipGetLastError());
     if (info) {
         std::memset(info, 0, sizeof(*info));
@@ -99,7 +106,7 @@ MISSLAP_API int misslap_solve_dense_batch_status(int64_t B, int64_t N, int64_t M
     const double t_start = now_ms();
     misslap_options opt;
     int rc = batch_options(opt_in, &opt, "misslap_solve_dense_batch_status",
-                           "device, maximize, eps_start, max_iter, input_on_device and input_stream");
+                           "device, maximize, eps_start, max_iter, mat_dtype, input_on_device and input_stream", true);
     if (rc) return rc;
     if (!mat || !sol || !status) return fail(MISSLAP_ERR_INVALID, "null mat / sol / status");
     if ((rc = dense_batch_dims(B, N, M))) return rc;
@@ -126,9 +133,10 @@ MISSLAP_API int misslap_solve_dense_batch_status(int64_t B, int64_t N, int64_t M
     if ((rc = batch_device(opt, &st))) return rc;
     const size_t cells = (size_t)B * (size_t)N * (size_t)M, pcells = (size_t)B * (size_t)M;
     DevScratch tmp;
-    const double *d_mat = mat, *d_p0 = prices_in;
-    if (!opt.input_on_device &&
-        ((rc = upload(tmp, &d_mat, mat, cells, st)) || (prices_in && (rc = upload(tmp, &d_p0, prices_in, pcells, st)))))
+    const void *d_mat = mat;
+    const double *d_p0 = prices_in;
+    if (!opt.input_on_device && ((rc = upload_stack(tmp, &d_mat, mat, cells, opt.mat_dtype, st)) ||
+                                 (prices_in && (rc = upload(tmp, &d_p0, prices_in, pcells, st)))))
         return rc;
     const int *d_shapes = nullptr;
     char *ws = nullptr;

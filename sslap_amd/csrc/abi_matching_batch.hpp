@@ -5,11 +5,17 @@
 #pragma once
 
 namespace {
-// Launch the matcher on a stream (LDS carve Ns x Ms; the > 64 KB opt-in is never needed: 48 KB at the cap).
+// Launch the matcher on a stream (LDS carve Ns x Ms; the > 64 KB opt-in is never needed: 48 KB at the cap).  mat_dtype:
+// the element type of a dense stack.
 template <bool kDense>
-int launch_matching_batch(hipStream_t st, int64_t B, const MatchBatchArgs &a, size_t *lds_out) {
+int launch_matching_batch(hipStream_t st, int64_t B, const MatchBatchArgs &a, int32_t mat_dtype, size_t *lds_out) {
     const size_t lds = matching_batch_lds_bytes(a.Ns, a.Ms, kDense);
-    hipLaunchKernelGGL(k_matching_batch<kDense>, dim3((unsigned)B), dim3(kMatchBatchThreads), lds, st, a);
+    if constexpr (kDense)
+        dense_dtype_dispatch(mat_dtype, [&](auto t) {
+            hipLaunchKernelGGL((k_matching_batch<kDense, decltype(t)>), dim3((unsigned)B), dim3(kMatchBatchThreads), lds, st, a);
+        });
+    else
+        hipLaunchKernelGGL(k_matching_batch<kDense>, dim3((unsigned)B), dim3(kMatchBatchThreads), lds, st, a);
     HIP_TRY(hipGetLastError());
     if (lds_out) *lds_out = lds;
     return MISSLAP_OK;
@@ -19,7 +25,8 @@ int launch_matching_batch(hipStream_t st, int64_t B, const MatchBatchArgs &a, si
 template <bool kDense>
 int matching_batch_run(hipStream_t st, DevScratch &tmp, int64_t B, MatchBatchArgs a, int32_t *size, int32_t *left,
                        int64_t left_ld, int32_t *right, int64_t right_ld, int32_t out_on_device,
-                       misslap_matching_batch_info *info, double t_start, double t_checked) {
+                       misslap_matching_batch_info *info, double t_start, double t_checked,
+                       int32_t mat_dtype = MISSLAP_DTYPE_F64) {
     int rc = 0;
     int *d_size = nullptr;
     if ((rc = tmp.alloc(&d_size, (size_t)B))) return rc;
@@ -36,7 +43,7 @@ int matching_batch_run(hipStream_t st, DevScratch &tmp, int64_t B, MatchBatchArg
     if ((rc = ev.create())) return rc;
     size_t lds = 0;
     HIP_TRY(hipEventRecord(ev.e[0], st));
-    if ((rc = launch_matching_batch<kDense>(st, B, a, &lds))) return rc;
+    if ((rc = launch_matching_batch<kDense>(st, B, a, mat_dtype, &lds))) return rc;
     HIP_TRY(hipEventRecord(ev.e[1], st));
     HIP_TRY(hipMemcpyAsync(size, d_size, sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToHost, st));
     if (!out_on_device) {
@@ -151,7 +158,8 @@ MISSLAP_API int misslap_matching_dense_batch(int64_t B, int64_t N, int64_t M, co
                                              misslap_matching_batch_info *info) {
     const double t_start = now_ms();
     misslap_options opt;
-    int rc = batch_options(opt_in, &opt, "misslap_matching_dense_batch", "device, input_on_device and input_stream");
+    int rc = batch_options(opt_in, &opt, "misslap_matching_dense_batch",
+                           "device, mat_dtype, input_on_device and input_stream", true);
     if (rc) return rc;
     if ((rc = matching_batch_info_size(info))) return rc;
     if (!mat || !size || !n_rows || !n_cols) return fail(MISSLAP_ERR_INVALID, "null mat / size / n_rows / n_cols");
@@ -179,9 +187,10 @@ MISSLAP_API int misslap_matching_dense_batch(int64_t B, int64_t N, int64_t M, co
     hipStream_t st = nullptr;
     if ((rc = batch_device(opt, &st))) return rc;
     DevScratch tmp;
-    const double *d_mat = mat;
+    const void *d_mat = mat;  // elements of opt.mat_dtype
     const int *d_shapes = nullptr;
-    if ((!opt.input_on_device && (rc = upload(tmp, &d_mat, mat, (size_t)B * (size_t)N * (size_t)M, st))) ||
+    if ((!opt.input_on_device &&
+         (rc = upload_stack(tmp, &d_mat, mat, (size_t)B * (size_t)N * (size_t)M, opt.mat_dtype, st))) ||
         (shapes && (rc = upload(tmp, &d_shapes, shapes, (size_t)B * 2, st))))
         return rc;
     for (int64_t b = 0; b < B; ++b) {
@@ -196,5 +205,5 @@ MISSLAP_API int misslap_matching_dense_batch(int64_t B, int64_t N, int64_t M, co
     a.Ns = Ns;
     a.Ms = Ms;
     return matching_batch_run<true>(st, tmp, B, a, size, left_pairings, left_ld, right_pairings, right_ld, out_on_device,
-                                    info, t_start, now_ms());
+                                    info, t_start, now_ms(), opt.mat_dtype);
 }

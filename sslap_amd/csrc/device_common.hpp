@@ -175,6 +175,46 @@ __device__ __forceinline__ bool dense_entry_valid(double v) {
     const unsigned long long b = (unsigned long long)__double_as_longlong(v);
     return b <= 0x7ff0000000000000ull || b == 0x8000000000000000ull;
 }
+// The element types of a dense stack besides double and float (misslap_options.mat_dtype): 16 bits held as bits, so the
+// same type names an element on the host and on the device.
+struct F16 {
+    unsigned short bits;  // IEEE binary16
+};
+struct Bf16 {
+    unsigned short bits;  // the upper half of a float
+};
+// "v >= 0" in the element's own type: the same set of entries as after widening
+__host__ __device__ __forceinline__ bool dense_entry_valid(float v) {
+    const unsigned b = __builtin_bit_cast(unsigned, v);
+    return b <= 0x7f800000u || b == 0x80000000u;
+}
+__host__ __device__ __forceinline__ bool dense_entry_valid(F16 v) { return v.bits <= 0x7c00 || v.bits == 0x8000; }
+__host__ __device__ __forceinline__ bool dense_entry_valid(Bf16 v) { return v.bits <= 0x7f80 || v.bits == 0x8000; }
+// The value as a double.  Every step is exact, subnormals included: binary16 -> float -> double, and a bfloat16 is the
+// float with its bits in the upper half (the code object keeps denormals: no flush-to-zero flag in build.FLAGS).
+__device__ __forceinline__ double dense_widen(double v) { return v; }
+__device__ __forceinline__ double dense_widen(float v) { return (double)v; }
+__device__ __forceinline__ double dense_widen(F16 v) { return (double)(float)__builtin_bit_cast(_Float16, v.bits); }
+__device__ __forceinline__ double dense_widen(Bf16 v) { return (double)__uint_as_float((unsigned)v.bits << 16); }
+// what a staging slot beyond the row holds (never an entry)
+template <class T>
+__device__ __forceinline__ T dense_hole();
+template <>
+__device__ __forceinline__ double dense_hole<double>() {
+    return -1.0;
+}
+template <>
+__device__ __forceinline__ float dense_hole<float>() {
+    return -1.0f;
+}
+template <>
+__device__ __forceinline__ F16 dense_hole<F16>() {
+    return F16{0xbc00};
+}
+template <>
+__device__ __forceinline__ Bf16 dense_hole<Bf16>() {
+    return Bf16{0xbf80};
+}
 // a bid that would break the bits-as-integer ordering of bid keys: negative (sign bit set) or NaN
 __device__ __forceinline__ bool bid_is_bad(double bid) {
     const unsigned long long b = (unsigned long long)__double_as_longlong(bid);

@@ -516,7 +516,8 @@ int sync_device_inputs(const misslap_options *opt, hipStream_t solver_stream) {
 // The caller's options in the current layout.  struct_size 88 = a version-1 caller (abi_v1.hpp): its reserved[] knobs
 // are mapped onto the named fields and the handle remembers to answer with the version-1 misslap_meta.  A version-2
 // struct may be shorter than this library's (built against an older version-2 header: the missing tail is zero =
-// defaults) but not longer than it knows how to read.
+// defaults) but not longer than it knows how to read.  mat_dtype is range-checked here; who takes which is the entry
+// point's check (float64_only).
 int normalise_options(const misslap_options *in, misslap_options *out, int *abi) {
     if (!in) return fail(MISSLAP_ERR_INVALID, "null options");
     std::memset(out, 0, sizeof(*out));
@@ -542,17 +543,26 @@ int normalise_options(const misslap_options *in, misslap_options *out, int *abi)
             return fail(MISSLAP_ERR_INVALID, "misslap_options.struct_size %d: expected %d (ABI %d; %d = ABI 1 is accepted too)",
                         in->struct_size, (int)sizeof(misslap_options), MISSLAP_ABI_VERSION, (int)sizeof(misslap_options_v1));
         std::memcpy(out, in, (size_t)in->struct_size);
-        for (int32_t r : out->reserved)
-            if (r != 0) return fail(MISSLAP_ERR_INVALID, "misslap_options.reserved must be zero");
+        for (int k = 1; k < 7; ++k)  // (reserved[0] is mat_dtype)
+            if (out->reserved[k] != 0) return fail(MISSLAP_ERR_INVALID, "misslap_options.reserved must be zero");
         *abi = 2;
     }
     out->struct_size = (int32_t)sizeof(misslap_options);
+    if (out->mat_dtype < MISSLAP_DTYPE_F64 || out->mat_dtype > MISSLAP_DTYPE_BF16)
+        return fail(MISSLAP_ERR_INVALID, "mat_dtype %d: 0 (float64), 1 (float32), 2 (float16) or 3 (bfloat16)", out->mat_dtype);
     if (out->cand_mode < 0 || out->cand_mode > 2) return fail(MISSLAP_ERR_INVALID, "cand_mode %d: 0, 1 or 2", out->cand_mode);
     if (out->cand_refresh_min < 0 || out->cand_refresh_min > 32)
         return fail(MISSLAP_ERR_INVALID, "cand_refresh_min %d: 0 .. 32", out->cand_refresh_min);
     if (out->cand_build_max_K < 0) return fail(MISSLAP_ERR_INVALID, "cand_build_max_K must not be negative");
     if (out->tiled_shape < 0 || out->tiled_shape > kNumTiledShapes)
         return fail(MISSLAP_ERR_INVALID, "tiled_shape %d: 0 (automatic) .. %d", out->tiled_shape, kNumTiledShapes);
+    return MISSLAP_OK;
+}
+
+// the entry points that read float64 values only: a typed stack is the dense batch's (abi_dense_batch.hpp)
+int float64_only(const misslap_options &opt, const char *who) {
+    if (opt.mat_dtype != MISSLAP_DTYPE_F64)
+        return fail(MISSLAP_ERR_INVALID, "%s takes float64 only: mat_dtype must be 0 (got %d)", who, opt.mat_dtype);
     return MISSLAP_OK;
 }
 

@@ -3,7 +3,9 @@
 //
 // The round loop is batch_solve (kernels_batch_solve.hpp); this file has the check pass and the dense row source.
 // Values are read from the caller's dense rows (row stride = the stack's M) in global memory, where a small problem
-// stays in L2:
+// stays in L2.  The rows have the caller's element type T (double, float, F16, Bf16: misslap_options.mat_dtype); the
+// three kernels that read them are templates on T, every value is widened to double where it is used (dense_widen,
+// exact), and batch_solve only ever sees doubles:
 //   BID      lanes scan the row in column order (lane l holds columns l, l + 64, ...), staged in registers with up to
 //            kDenseBatchCols loads in flight; the object is the winning column r.g.
 //   eCE      every column is stored once, so choice_cost -- never reset per row in the reference -- is the cost of the
@@ -28,8 +30,8 @@ struct DenseBatchCheck {
 
 struct DenseBatchArgs {
     BatchSolveArgs s;         // p0_ld = prices_ld = M, sol_ld = Ns = N, Ms = M
-    const double *mat;
-    long long N, M;           // the stack: row stride M, problem stride N * M
+    const void *mat;          // elements of the kernel's T
+    long long N, M;           // the stack: row stride M, problem stride N * M, in elements
     const int *shapes;        // [B][2] (n_b, m_b) or null
     const DenseBatchCheck *chk;
 };
@@ -43,7 +45,8 @@ __device__ __forceinline__ void dense_batch_shape(const int *shapes, long long N
 // With shapes_out (status mode: `shapes` may be a caller's device array that no host has seen) a shape outside
 // 1 .. N x 1 .. M becomes (0, 0), nothing of that problem is read, and the shape every later kernel uses is written
 // to shapes_out[b]: the guard and the solve read those, never the caller's.
-__global__ __launch_bounds__(256) void k_dense_batch_check(const double *mat, long long N, long long M, const int *shapes,
+template <class T>
+__global__ __launch_bounds__(256) void k_dense_batch_check(const T *mat, long long N, long long M, const int *shapes,
                                                            const double *p0, DenseBatchCheck *out, int *shapes_out) {
     const int b = blockIdx.x, lane = lane_id(), wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
     int n, m;
@@ -55,7 +58,7 @@ __global__ __launch_bounds__(256) void k_dense_batch_check(const double *mat, lo
             shapes_out[2 * b + 1] = m;
         }
     }
-    const double *A = mat + (size_t)b * (size_t)N * (size_t)M;
+    const T *A = mat + (size_t)b * (size_t)N * (size_t)M;
     __shared__ unsigned long long s_cnt, s_abs;
     __shared__ int s_empty, s_inf, s_mref, s_badp;
     if (threadIdx.x == 0) {
@@ -70,12 +73,13 @@ __global__ __launch_bounds__(256) void k_dense_batch_check(const double *mat, lo
     unsigned long long cnt = 0, am = 0;
     int inf = 0, mx = -1;
     for (int r = wave; r < n; r += nw) {
-        const double *row = A + (size_t)r * (size_t)M;
+        const T *row = A + (size_t)r * (size_t)M;
         int rc = 0;
         for (int c = lane; c < m; c += kWave) {
-            const double v = row[c];
+            const T v = row[c];
             if (dense_entry_valid(v)) {
-                const unsigned long long bits = (unsigned long long)__double_as_longlong(v) & 0x7fffffffffffffffull;
+                const unsigned long long bits =
+                    (unsigned long long)__double_as_longlong(dense_widen(v)) & 0x7fffffffffffffffull;
                 ++rc;
                 am = bits > am ? bits : am;
                 inf |= bits == 0x7ff0000000000000ull;
@@ -107,22 +111,25 @@ __global__ __launch_bounds__(256) void k_dense_batch_check(const double *mat, lo
 // The dense row source of batch_solve: problem b's slice A (row stride M) of n x m, its reference M and valid count.
 // The bid's staging array `vals` belongs to k_dense_batch_solve: declared in bid() it is promoted to a vector while bid()
 // is optimised on its own, and every staging step then zeroes the rest of it (measured: 3.8 % more kernel time at
-// 64 x 1000).  Declared in the kernel, it becomes 16 register pairs as in a hand-inlined scan.
+// 64 x 1000).  Declared in the kernel, it becomes 16 register pairs as in a hand-inlined scan.  The row is staged in its
+// own type T -- 16 registers for float and for the 16-bit types, one element per lane per load with the same
+// column-to-lane map -- and widened where the scan uses it.
+template <class T>
 struct DenseBatchRows {
-    const double *A;
+    const T *A;
     long long M;
     int m, maximize, mref;
     unsigned long long nvalid;
-    double *vals;  // [kDenseBatchCols]
+    T *vals;  // [kDenseBatchCols]
 
     __device__ __forceinline__ Top2 bid(int i, const double *price, double &costbest, int &obj) const {
         const int lane = lane_id();
-        const double *row = A + (size_t)i * (size_t)M;
+        const T *row = A + (size_t)i * (size_t)M;
 #pragma unroll
         for (int q = 0; q < kDenseBatchCols; ++q) {
             if (q * kWave >= m) break;
             const int c = lane + q * kWave;
-            vals[q] = c < m ? row[c] : -1.0;
+            vals[q] = c < m ? row[c] : dense_hole<T>();
         }
         Top2 x;
         x.v = -__builtin_huge_val();
@@ -134,7 +141,8 @@ struct DenseBatchRows {
             if (q * kWave >= m) break;
             const int c = lane + q * kWave;
             if (c < m && dense_entry_valid(vals[q])) {
-                const double cost = maximize ? vals[q] : vals[q] * -1.0;  // :236-237
+                const double v = dense_widen(vals[q]);
+                const double cost = maximize ? v : v * -1.0;  // :236-237
                 const double vi = cost - price[c];
                 if (vi >= x.v) {  // :351 (the first entry is always taken: vi >= -inf for every non-NaN vi)
                     x.w = x.v;
@@ -154,14 +162,15 @@ struct DenseBatchRows {
 
     // eCE_satisfied (auction_.pyx:443-485) for row i: choice_cost is the cost of column j, every valid column is tested
     __device__ __forceinline__ bool ece_bad(int i, int j, const double *price, double tol, double eps) const {
-        const double *row = A + (size_t)i * (size_t)M;
-        const double vj = row[j];
+        const T *row = A + (size_t)i * (size_t)M;
+        const double vj = dense_widen(row[j]);
         const double choice_cost = maximize ? vj : vj * -1.0;
         const double LHS = choice_cost - price[j] + tol;  // :475
         bool bad = false;
         for (int c = lane_id(); c < m; c += kWave) {
-            const double v = row[c];
-            if (!dense_entry_valid(v)) continue;
+            const T e = row[c];
+            if (!dense_entry_valid(e)) continue;
+            const double v = dense_widen(e);
             const double cost = maximize ? v : v * -1.0;
             if (LHS < (cost - price[c]) - eps) bad = true;  // :482
         }
@@ -172,7 +181,7 @@ struct DenseBatchRows {
     __device__ __forceinline__ void gather(const int *p2o, int n, double *selv, int *) const {
         for (int i = threadIdx.x; i < n; i += blockDim.x) {
             const int j = p2o[i];
-            selv[i] = j >= 0 ? A[(size_t)i * (size_t)M + j] : 0.0;
+            selv[i] = j >= 0 ? dense_widen(A[(size_t)i * (size_t)M + j]) : 0.0;
         }
     }
 
@@ -192,13 +201,15 @@ struct DenseBatchRows {
     __device__ __forceinline__ int64_t meta_nnz() const { return (int64_t)nvalid; }
 };
 
+template <class T>
 __global__ __launch_bounds__(1024) void k_dense_batch_solve(DenseBatchArgs a) {
     const int b = blockIdx.x;
     int n, m;
     dense_batch_shape(a.shapes, a.N, a.M, b, n, m);
     const DenseBatchCheck ck = a.chk[b];
-    double vals[kDenseBatchCols];
-    const DenseBatchRows rows{a.mat + (size_t)b * (size_t)a.N * (size_t)a.M, a.M, m, a.s.maximize, ck.mref, ck.nvalid, vals};
+    T vals[kDenseBatchCols];
+    const DenseBatchRows<T> rows{static_cast<const T *>(a.mat) + (size_t)b * (size_t)a.N * (size_t)a.M, a.M, m, a.s.maximize,
+                                 ck.mref, ck.nvalid, vals};
     batch_solve(a.s, rows, n, m, ck.absmax_bits);
 }
 
@@ -224,6 +235,7 @@ __device__ __forceinline__ int dense_batch_verdict(const DenseBatchCheck &c, int
 // k_dense_batch_solve with the verdict formed here, from what the check pass and the guard left on the device.  A
 // condemned problem's workgroup writes the defined outputs and leaves before any LDS state exists; the others run the
 // same batch_solve on the same row source.
+template <class T>
 __global__ __launch_bounds__(1024) void k_dense_batch_solve_status(DenseBatchStatusArgs a) {
     const int b = blockIdx.x;
     const int n = a.d.shapes[2 * b], m = a.d.shapes[2 * b + 1];
@@ -243,9 +255,9 @@ __global__ __launch_bounds__(1024) void k_dense_batch_solve_status(DenseBatchSta
         s.eps_b = nullptr;
         s.eps_opt = (float)(1.0 / (double)n);
     }
-    double vals[kDenseBatchCols];
-    const DenseBatchRows rows{a.d.mat + (size_t)b * (size_t)a.d.N * (size_t)a.d.M, a.d.M, m, s.maximize, ck.mref, ck.nvalid,
-                              vals};
+    T vals[kDenseBatchCols];
+    const DenseBatchRows<T> rows{static_cast<const T *>(a.d.mat) + (size_t)b * (size_t)a.d.N * (size_t)a.d.M, a.d.M, m,
+                                 s.maximize, ck.mref, ck.nvalid, vals};
     batch_solve(s, rows, n, m, ck.absmax_bits);
 }
 

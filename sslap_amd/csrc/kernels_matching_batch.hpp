@@ -15,8 +15,9 @@
 //        INF, the parent rescans from the entry after the child's) or the whole path succeeds, so the entries are
 //        visited in the reference's order.  On a path the row at depth d has Dist d, so Dist[u] is the depth.
 // Adjacency is read in stored order from (a) a slice of a packed loc, rows ascending (gaps allowed: an absent row has
-// no entries, as cumulative_idxs gives it, :22-46), or (b) the rows of a dense float64 stack, entry iff v >= 0 by bit
-// pattern (dense_entry_valid: NaN is not an entry, -0.0 and +inf are).
+// no entries, as cumulative_idxs gives it, :22-46), or (b) the rows of a dense stack of element type E (double, float,
+// F16, Bf16: misslap_options.mat_dtype), entry iff v >= 0 by bit pattern in that type (dense_entry_valid: NaN is not an
+// entry, -0.0 and +inf are).  No value is ever widened here: only the pattern is read.
 #pragma once
 
 namespace misslap {
@@ -41,7 +42,7 @@ struct MatchBatchArgs {
     const MatchBatchCheck *mchk;   // misslap_matching_batch: every graph was accepted by the host
     const SparseBatchCheck *schk;  // the sparse solve's guard: only clean problems within the carve are matched
     // source (b): dense stack [B][N][M], graph b = mat[b][:n_b][:m_b]
-    const double *mat;
+    const void *mat;               // elements of the kernel's E
     long long N, M;
     const int *shapes;             // [B][2] or null
     int Ns, Ms;                    // the LDS carve: largest n_b / m_b the launch takes
@@ -112,17 +113,17 @@ __device__ __forceinline__ void match_bfs_visit(int v, int L, const int *pair_v,
     }
 }
 
-template <bool kDense>
+template <bool kDense, class E = double>
 __global__ __launch_bounds__(kMatchBatchThreads) void k_matching_batch(MatchBatchArgs a) {
     const int b = blockIdx.x, tid = threadIdx.x, T = blockDim.x, lane = lane_id(), wave = tid >> 6, nw = T >> 6;
     int n = 0, m = 0;
     long long s = 0;
     int nnz = 0;
-    const double *A = nullptr;
+    const E *A = nullptr;
     if (kDense) {
         n = a.shapes ? a.shapes[2 * b] : (int)a.N;
         m = a.shapes ? a.shapes[2 * b + 1] : (int)a.M;
-        A = a.mat + (size_t)b * (size_t)a.N * (size_t)a.M;
+        A = static_cast<const E *>(a.mat) + (size_t)b * (size_t)a.N * (size_t)a.M;
     } else {
         s = a.offsets[b];
         nnz = (int)(a.offsets[b + 1] - s);
@@ -190,7 +191,7 @@ __global__ __launch_bounds__(kMatchBatchThreads) void k_matching_batch(MatchBatc
             bool found = false;
             if (kDense) {
                 for (int x = qs + wave; x < qe; x += nw) {
-                    const double *row = A + (size_t)queue[x] * (size_t)a.M;
+                    const E *row = A + (size_t)queue[x] * (size_t)a.M;
                     for (int c = lane; c < m; c += kWave)
                         if (dense_entry_valid(row[c])) match_bfs_visit(c, L, pair_v, dist, queue, &s_tail, found);
                 }

@@ -64,7 +64,7 @@ MISSLAP_API int misslap_create(misslap_solver **out, int64_t nnz, const int32_t 
     misslap_options o2;
     int abi = 0;
     int rc = normalise_options(opt_in, &o2, &abi);
-    if (rc) return rc;
+    if (rc || (rc = float64_only(o2, "misslap_create"))) return rc;
     const misslap_options *opt = &o2;
     if (!loc || !val) return fail(MISSLAP_ERR_INVALID, "null loc / val");
     if (nnz <= 0) return fail(MISSLAP_ERR_INVALID, "empty problem (nnz = %lld)", (long long)nnz);
@@ -124,7 +124,7 @@ MISSLAP_API int misslap_create_dense(misslap_solver **out, int64_t n_rows, int64
     misslap_options o2;
     int abi = 0;
     int rc = normalise_options(opt_in, &o2, &abi);
-    if (rc) return rc;
+    if (rc || (rc = float64_only(o2, "misslap_create_dense"))) return rc;
     const misslap_options *opt = &o2;
     if (!mat) return fail(MISSLAP_ERR_INVALID, "null mat");
     if (n_rows <= 0 || n_cols <= 0 || n_rows > 0x7ffffffe || n_cols > 0x7ffffffe)

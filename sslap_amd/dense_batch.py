@@ -32,10 +32,10 @@ _META_VIEWS = ("its", "nreductions", "eCE", "soln_found", "n_assigned", "obj_f64
 
 
 def auction_solve_batch(mats, problem="min", eps_start=0., max_iter=1000000, fast=False, cardinality_check=True,
-                        shapes=None, prices=None, errors="raise"):
+                        shapes=None, prices=None, errors="raise", mat_dtype="float64"):
     """Solve B independent dense problems in one call, one workgroup per problem.
 
-    mats: float64 (B, N, M), a numpy array or a contiguous tensor on the device (read in place, ordered behind
+    mats: float64 (or mat_dtype, below) (B, N, M), a numpy array or a contiguous tensor on the device (read in place, ordered behind
     torch.cuda.current_stream()); entries v >= 0 are edges, anything else (-1, NaN) is not.  shapes: optional int
     (B, 2); problem b is then mats[b, :n_b, :m_b].  prices: optional float64 (B, M) starting prices (of the maximised
     problem) as AuctionSolver.resolve takes them.  N, M <= MISSLAP_DENSE_BATCH_MAX_DIM.
@@ -49,6 +49,14 @@ def auction_solve_batch(mats, problem="min", eps_start=0., max_iter=1000000, fas
     result also holds status (int32 (B,), the MISSLAP_BATCH_STATUS_* codes of include/misslap.h) and matching_size
     (int32 (B,), the guard's cardinality, -1 where it did not run).  Every problem with status 0 is solved, with exactly
     the default mode's results; the others have sol -1, prices 0 and a meta of n_rows, n_cols, nnz and zeros.
+    mat_dtype: "float64" (default), "float32", "float16" or "bfloat16", or that numpy / torch dtype: the element type of
+    mats, which must have exactly that dtype (nothing is converted; a mismatch raises ValueError).  The stack is read in
+    place in its own type and every value is widened to float64 as it is read, which is exact: the result is bit for
+    bit the float64 result on the widened stack (mats.astype(float64) / mats.double()).  An entry is valid iff it is
+    >= 0 in its own type.  prices and every output keep their types.  numpy has no bfloat16, so a bfloat16 stack is a
+    device tensor.  Only this call and hopcroft_solve_batch(mats=) take the keyword: auction_solve(mat=), from_matrix
+    and the sparse batch take float64, and a strided (non-contiguous) stack is not accepted.
+
     raise_for_status(res) raises what the default mode would have raised.  With a device stack the call is
     stream-ordered: its kernels go onto torch.cuda.current_stream(mats.device), it waits for nothing, and sol, prices,
     status, matching_size and the meta fields are device tensors ordered on that stream (batch_meta_to_host(res) gives
@@ -58,13 +66,13 @@ def auction_solve_batch(mats, problem="min", eps_start=0., max_iter=1000000, fas
     """
     if errors not in ("raise", "status"):
         raise ValueError(f"errors must be 'raise' or 'status', got {errors!r}")
-    B, N, M, on_device = _check_stack(mats)
+    B, N, M, on_device, dtype = _check_stack(mats, mat_dtype)
     if N > MAX_DIM or M > MAX_DIM:
         raise ValueError(f"problems of {N} x {M}: auction_solve_batch takes at most {MAX_DIM} x {MAX_DIM} "
                          f"(MISSLAP_DENSE_BATCH_MAX_DIM); solve larger problems with from_matrix / solve_batch")
     if errors == "status":
         return _solve_status(mats, B, N, M, on_device, problem, eps_start, max_iter, fast, cardinality_check, shapes,
-                             prices)
+                             prices, dtype)
     shp = _check_shapes(shapes, B, N, M, "problem")
     ns = shp[:, 0] if shp is not None else np.full(B, N, dtype=np.int32)
     e = float(eps_start)
@@ -75,7 +83,7 @@ def auction_solve_batch(mats, problem="min", eps_start=0., max_iter=1000000, fas
     eps_b = None
     if fast:  # auction_.pyx:568-569: eps_start = 1 / N of each problem, as a C float
         eps_b = (1.0 / ns.astype(np.float64)).astype(np.float32)
-    opts = _solve_options(on_device, mats, problem, e, max_iter)
+    opts = _solve_options(on_device, mats, problem, e, max_iter, dtype)
     if on_device:
         import torch
         sol = torch.empty((B, N), dtype=torch.int32, device=mats.device)
@@ -103,13 +111,14 @@ def _eps(eps_start):
     return e
 
 
-def _solve_status(mats, B, N, M, on_device, problem, eps_start, max_iter, fast, cardinality_check, shapes, prices):
+def _solve_status(mats, B, N, M, on_device, problem, eps_start, max_iter, fast, cardinality_check, shapes, prices,
+                  dtype):
     """errors="status" of auction_solve_batch (misslap_solve_dense_batch_status); the whole-call checks in the default
     mode's order: shapes, eps_start, prices."""
     check = 1 if cardinality_check else 0
     if not on_device:  # synchronous: the library uploads, uses its own scratch and waits once
         shp = _check_shapes(shapes, B, N, M, "problem")
-        opts = _solve_options(False, mats, problem, _eps(eps_start), max_iter)
+        opts = _solve_options(False, mats, problem, _eps(eps_start), max_iter, dtype)
         p, p_ptr, _ = _starting_prices(prices, B, M, True, False, mats, "mats")
         mc = np.ascontiguousarray(mats)
         sol, pout = np.empty((B, N), dtype=np.int32), np.empty((B, M), dtype=np.float64)
@@ -131,7 +140,7 @@ def _solve_status(mats, B, N, M, on_device, problem, eps_start, max_iter, fast, 
                              f"{shp.dtype} {tuple(shp.shape)} on {shp.device}")
     else:  # a host array: validated as in the default mode, sent from pinned memory without a wait
         shp = torch.from_numpy(_check_shapes(shapes, B, N, M, "problem")).pin_memory().to(dev, non_blocking=True)
-    opts = _solve_options(True, mats, problem, _eps(eps_start), max_iter)
+    opts = _solve_options(True, mats, problem, _eps(eps_start), max_iter, dtype)
     if isinstance(prices, np.ndarray):
         _starting_prices(prices, B, M, True, False, mats, "mats")  # (dtype and shape)
         prices = torch.from_numpy(np.ascontiguousarray(prices)).pin_memory().to(dev, non_blocking=True)

@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._batch import _check_offsets, _check_shapes, _check_stack, _is_device_tensor, _maxima, _options
+from ._batch import _check_offsets, _check_shapes, _check_stack, _is_device_tensor, _mat_dtype_name, _maxima, _options
 
 MAX_DIM = _lib.MATCHING_BATCH_MAX_DIM
 
@@ -56,22 +56,23 @@ def _check_loc(loc, offsets):
     return loc, B, off, on_device
 
 
-def _check_mats(mats, shapes):
-    """mats (numpy or device float64, (B, N, M)) and optional shapes; returns (B, N, M, shapes int32 or None, on_device)."""
-    B, N, M, on_device = _check_stack(mats)
+def _check_mats(mats, shapes, mat_dtype):
+    """mats (numpy or device, (B, N, M) of mat_dtype) and optional shapes; returns (B, N, M, shapes int32 or None,
+    on_device, the MISSLAP_DTYPE_* code)."""
+    B, N, M, on_device, dtype = _check_stack(mats, mat_dtype)
     if shapes is None:
         if N > MAX_DIM or M > MAX_DIM:
             raise ValueError(f"graph 0: {N} x {M} exceeds MISSLAP_MATCHING_BATCH_MAX_DIM ({MAX_DIM})")
-        return B, N, M, None, on_device
+        return B, N, M, None, on_device, dtype
     s = _check_shapes(shapes, B, N, M, "graph")
     big = (s[:, 0] > MAX_DIM) | (s[:, 1] > MAX_DIM)
     if big.any():
         b = int(np.flatnonzero(big)[0])
         raise ValueError(f"graph {b}: {int(s[b, 0])} x {int(s[b, 1])} exceeds MISSLAP_MATCHING_BATCH_MAX_DIM ({MAX_DIM})")
-    return B, N, M, s, on_device
+    return B, N, M, s, on_device, dtype
 
 
-def hopcroft_solve_batch(loc=None, offsets=None, mats=None, shapes=None):
+def hopcroft_solve_batch(loc=None, offsets=None, mats=None, shapes=None, mat_dtype="float64"):
     """Maximum matching of B small bipartite graphs in one call, one workgroup per graph.
 
     Exactly ONE of
@@ -81,6 +82,8 @@ def hopcroft_solve_batch(loc=None, offsets=None, mats=None, shapes=None):
           list of per-graph loc numpy arrays, with offsets None.
     mats: a float64 (B, N, M) stack, numpy or a contiguous device tensor; graph b is mats[b, :n_b, :m_b] with
           (n_b, m_b) = shapes[b] (optional integer (B, 2); default N x M), edge (i, j) iff the entry is >= 0.
+          mat_dtype ("float64", "float32", "float16", "bfloat16", or that numpy / torch dtype) names the stack's element
+          type, which it must have exactly; the stack is read in place and the pairings are those of the widened stack.
     A graph has at most MISSLAP_MATCHING_BATCH_MAX_DIM rows and columns.
 
     Returns dict(size=int32 (B,), left_pairings=int32 (B, Nmax), right_pairings=int32 (B, Mmax), n_rows, n_cols);
@@ -93,13 +96,15 @@ def hopcroft_solve_batch(loc=None, offsets=None, mats=None, shapes=None):
     if mats is not None:
         if offsets is not None:
             raise TypeError("offsets goes with loc, not with mats")
-        B, N, M, shp, on_device = _check_mats(mats, shapes)
+        B, N, M, shp, on_device, dtype = _check_mats(mats, shapes, mat_dtype)
         Nmax = int(shp[:, 0].max()) if shp is not None else N
         Mmax = int(shp[:, 1].max()) if shp is not None else M
         src = mats
     else:
         if shapes is not None:
             raise TypeError("shapes goes with mats, not with loc")
+        if _mat_dtype_name(mat_dtype) != "float64":
+            raise TypeError("mat_dtype goes with mats, not with loc")
         if isinstance(loc, (list, tuple)):
             if offsets is not None:
                 raise TypeError("a list of per-graph loc arrays takes no offsets")
@@ -109,7 +114,7 @@ def hopcroft_solve_batch(loc=None, offsets=None, mats=None, shapes=None):
         Nmax = min(max(max_row + 1, 1), MAX_DIM)  # (a graph beyond the cap is rejected by the library, in its order)
         Mmax = min(max(max_col + 1, 1), MAX_DIM)
         src = loc
-    opts = _options(on_device, src)
+    opts = _options(on_device, src) if mats is None else _options(on_device, src, mat_dtype=dtype)
     size = np.empty(B, dtype=np.int32)
     n_rows = np.empty(B, dtype=np.int32)
     n_cols = np.empty(B, dtype=np.int32)
