@@ -6,12 +6,9 @@ import pytest
 
 from oracle import oracle as orc
 from sslap_amd import auction_solve_batch, from_matrix
+from tests._batch_shapes import bits as _bits, dense_compare, dense_expect, dense_values as _values
 
 pytestmark = pytest.mark.gpu
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
 
 
 def _oracle(mat, problem, eps_start=0.0, max_iter=1000000, fast=False, p0=None):
@@ -23,22 +20,8 @@ def _oracle(mat, problem, eps_start=0.0, max_iter=1000000, fast=False, p0=None):
 
 
 def _check_problem(res, b, mat, problem, n, m, p0=None, **kw):
-    sol_o, o = _oracle(mat, problem, p0=p0, **kw)
-    meta = res["meta"]
-    sol = np.asarray(res["sol"][b])
-    assert np.array_equal(sol[:n], sol_o), b
-    assert (sol[n:] == -1).all(), b
-    for k in ("its", "nreductions", "eCE", "soln_found", "n_assigned", "obj", "start_eps", "final_eps"):
-        assert meta[k][b] == o.meta[k], (b, k, meta[k][b], o.meta[k])
-    assert meta["obj_f64"][b] == o.extra["obj_f64"], b
-    assert np.float32(meta["start_eps_f32"][b]).view(np.uint32) == np.float32(o.extra["start_eps_f32"]).view(np.uint32)
-    assert np.float32(meta["final_eps_f32"][b]).view(np.uint32) == np.float32(o.extra["final_eps_f32"]).view(np.uint32)
-    assert meta["n_cols"][b] == o.M and meta["n_rows"][b] == n
-    p = np.asarray(res["prices"][b])
-    assert np.array_equal(_bits(p[:o.M]), _bits(o.state()["p"])), b
-    rest = np.zeros(m - o.M) if p0 is None else p0[o.M:m]  # columns without a valid entry are never bid for
-    assert np.array_equal(_bits(p[o.M:m]), _bits(rest)), b
-    assert (p[m:] == 0).all(), b
+    """Problem b of a result against the oracle on its slice: every field of tests/_batch_shapes.dense_compare."""
+    dense_compare(res, b, dense_expect(mat, problem, p0=p0, **kw), n, m, p0=p0)
 
 
 def _check_all(res, mats, problem, shapes=None, prices=None, **kw):
@@ -46,22 +29,6 @@ def _check_all(res, mats, problem, shapes=None, prices=None, **kw):
     for b in range(B):
         n, m = (N, M) if shapes is None else (int(shapes[b][0]), int(shapes[b][1]))
         _check_problem(res, b, mats[b, :n, :m], problem, n, m, p0=None if prices is None else prices[b], **kw)
-
-
-def _values(kind, shape, rng):
-    if kind == "uniform":  # benchmarking.py's recipe: doubles that are not fp32-exact
-        return rng.uniform(0, 100, shape)
-    if kind == "ints":  # many ties
-        return rng.integers(0, 5, shape).astype(np.float64)
-    if kind == "fp32":
-        return rng.uniform(0, 100, shape).astype(np.float32).astype(np.float64)
-    if kind == "holes":  # 30 % invalid, as -1 and NaN
-        v = rng.uniform(0, 100, shape)
-        h = rng.random(shape) < 0.3
-        v[h] = np.where(rng.random(shape) < 0.5, -1.0, np.nan)[h]
-        v[..., np.arange(shape[-2]), np.arange(shape[-2]) % shape[-1]] = rng.uniform(0, 100, shape[:-2] + (shape[-2],))
-        return v
-    raise AssertionError(kind)
 
 
 @pytest.mark.parametrize("problem", ["min", "max"])
@@ -76,7 +43,7 @@ def test_value_kinds(problem, kind):
 
 
 @pytest.mark.parametrize("opts", [dict(eps_start=0.5), dict(fast=True), dict(max_iter=1), dict(max_iter=7),
-                                  dict(max_iter=7, problem="max")])
+                                  dict(max_iter=7, problem="max"), dict(max_iter=0)])
 def test_eps_and_max_iter(opts):
     rng = np.random.default_rng(7)
     mats = _values("uniform", (5, 40, 40), rng)

@@ -9,20 +9,13 @@ import functools
 import numpy as np
 import pytest
 
-from oracle import oracle as orc
 from sslap_amd import auction_solve_batch, hopcroft_solve_batch
+from tests._batch_shapes import (bits as _bits, dense_compare as _check_problem, dense_expect as _oracle,
+                                 dense_values as _values, host as _host)
 
 pytestmark = pytest.mark.gpu
 
 DTYPES = ["float32", "float16", "bfloat16"]
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def _host(x):
-    return x if isinstance(x, np.ndarray) else x.cpu().numpy()
 
 
 def _typed(draw, dtype, device=False):
@@ -43,53 +36,11 @@ def _raw_bytes(stack):
     return stack.contiguous().view(torch.uint8).cpu().numpy().tobytes()
 
 
-def _oracle(mat, problem, p0=None, **kw):
-    """What the reference gives for one float64 slice, as plain values."""
-    o = orc.from_matrix(np.ascontiguousarray(mat), problem=problem, **kw)
-    if p0 is not None:  # the reference's solve() with self.p starting at p0 instead of zeros (auction_.pyx:220)
-        np.ctypeslib.as_array(orc.lib().oracle_prices(o._h), (o.M,))[:] = p0[:o.M]
-    sol = o.solve()
-    return dict(sol=sol.copy(), meta=dict(o.meta), extra=dict(o.extra), M=o.M, p=o.state()["p"].copy())
-
-
-def _check_problem(res, b, want, n, m, p0=None):
-    meta = res["meta"]
-    sol = _host(res["sol"])[b]
-    assert np.array_equal(sol[:n], want["sol"]), b
-    assert (sol[n:] == -1).all(), b
-    for k in ("its", "nreductions", "eCE", "soln_found", "n_assigned", "obj", "start_eps", "final_eps"):
-        assert meta[k][b] == want["meta"][k], (b, k, meta[k][b], want["meta"][k])
-    assert meta["obj_f64"][b] == want["extra"]["obj_f64"], b
-    for k in ("start_eps_f32", "final_eps_f32"):
-        assert np.float32(meta[k][b]).view(np.uint32) == np.float32(want["extra"][k]).view(np.uint32), (b, k)
-    assert meta["n_cols"][b] == want["M"] and meta["n_rows"][b] == n, b
-    p = _host(res["prices"])[b]
-    assert p.dtype == np.float64
-    assert np.array_equal(_bits(p[:want["M"]]), _bits(want["p"])), b
-    rest = np.zeros(m - want["M"]) if p0 is None else p0[want["M"]:m]  # columns without a valid entry are never bid for
-    assert np.array_equal(_bits(p[want["M"]:m]), _bits(rest)), b
-    assert (p[m:] == 0).all(), b
-
-
 def _check_all(res, wide, problem, shapes=None, **kw):
     B, N, M = wide.shape
     for b in range(B):
         n, m = (N, M) if shapes is None else (int(shapes[b][0]), int(shapes[b][1]))
         _check_problem(res, b, _oracle(wide[b, :n, :m], problem, **kw), n, m)
-
-
-def _values(kind, shape, rng):
-    if kind == "uniform":  # rounded to a 16-bit type these are full of equal values: the tie rule decides
-        return rng.uniform(0, 100, shape)
-    if kind == "ints":
-        return rng.integers(0, 5, shape).astype(np.float64)
-    if kind == "holes":  # 30 % invalid, as -1 and NaN; the diagonal stays
-        v = rng.uniform(0, 100, shape)
-        h = rng.random(shape) < 0.3
-        v[h] = np.where(rng.random(shape) < 0.5, -1.0, np.nan)[h]
-        v[..., np.arange(shape[-2]), np.arange(shape[-2]) % shape[-1]] = rng.uniform(0, 100, shape[:-2] + (shape[-2],))
-        return v
-    raise AssertionError(kind)
 
 
 def _error_of(call):

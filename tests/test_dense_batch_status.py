@@ -71,7 +71,7 @@ def test_parity_value_kinds(problem, kind):
 
 
 @pytest.mark.parametrize("opts", [dict(eps_start=0.5), dict(fast=True), dict(max_iter=1), dict(max_iter=7),
-                                  dict(max_iter=7, problem="max")])
+                                  dict(max_iter=7, problem="max"), dict(max_iter=0)])
 def test_parity_eps_and_max_iter(opts):
     rng = np.random.default_rng(7)
     opts = dict(opts)

@@ -6,66 +6,18 @@ import numpy as np
 import pytest
 
 import cases
-from oracle import oracle as orc
 from sslap_amd import auction_solve_sparse_batch, from_sparse
+from tests._batch_shapes import (bits as _bits, sparse_compare, sparse_expect, sparse_pack as _pack,
+                                 sparse_problem as _problem)
 
 pytestmark = pytest.mark.gpu
 
 CAP = 2048
 
 
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def _problem(rng, n, m, per_row, kind="uniform", shuffle=True):
-    """n x m (n <= m) with per_row stored entries in every row, rows ascending; column perm[i] planted in row i (a perfect
-    matching of the rows exists).  Random columns may repeat: duplicate (i, j) entries are part of the input class."""
-    k = min(per_row, m) if per_row > 0 else m
-    cols = rng.integers(0, m, (n, k)).astype(np.int32)
-    cols[:, 0] = rng.permutation(m)[:n]
-    if shuffle:
-        cols = rng.permuted(cols, axis=1)
-    else:
-        cols.sort(axis=1)
-    loc = np.ascontiguousarray(np.stack([np.repeat(np.arange(n, dtype=np.int32), k), cols.ravel()], axis=1))
-    shape = (n * k,)
-    if kind == "uniform":
-        val = rng.uniform(0, 100, shape)
-    elif kind == "ints":  # many ties
-        val = rng.integers(0, 5, shape).astype(np.float64)
-    elif kind == "fp32":
-        val = rng.uniform(0, 100, shape).astype(np.float32).astype(np.float64)
-    else:
-        raise AssertionError(kind)
-    return loc, val
-
-
-def _pack(probs):
-    loc = np.ascontiguousarray(np.concatenate([p[0] for p in probs]), dtype=np.int32)
-    val = np.ascontiguousarray(np.concatenate([p[1] for p in probs]))
-    offsets = np.concatenate([[0], np.cumsum([p[0].shape[0] for p in probs])]).astype(np.int64)
-    return loc, val, offsets
-
-
 def _check_problem(res, b, loc, val, problem, size=None, p0=None, **kw):
-    o = orc.from_sparse(loc, val.copy(), problem=problem, size=size, **kw)
-    if p0 is not None:  # the reference's solve() with self.p starting at p0 instead of zeros (auction_.pyx:220)
-        np.ctypeslib.as_array(orc.lib().oracle_prices(o._h), (o.M,))[:] = p0[:o.M]
-    sol_o = o.solve()
-    meta = res["meta"]
-    sol = np.asarray(res["sol"][b])
-    assert np.array_equal(sol[:o.N], sol_o), b
-    assert (sol[o.N:] == -1).all(), b
-    for k in ("its", "nreductions", "eCE", "soln_found", "n_assigned", "obj", "start_eps", "final_eps"):
-        assert meta[k][b] == o.meta[k], (b, k, meta[k][b], o.meta[k])
-    assert meta["obj_f64"][b] == o.extra["obj_f64"], b
-    assert np.float32(meta["start_eps_f32"][b]).view(np.uint32) == np.float32(o.extra["start_eps_f32"]).view(np.uint32)
-    assert np.float32(meta["final_eps_f32"][b]).view(np.uint32) == np.float32(o.extra["final_eps_f32"]).view(np.uint32)
-    assert meta["n_cols"][b] == o.M and meta["n_rows"][b] == o.N and meta["nnz"][b] == loc.shape[0]
-    p = np.asarray(res["prices"][b])
-    assert np.array_equal(_bits(p[:o.M]), _bits(o.state()["p"])), b
-    assert (p[o.M:] == 0).all(), b
+    """Problem b of a result against the oracle on its loc / val: every field of tests/_batch_shapes.sparse_compare."""
+    sparse_compare(res, b, sparse_expect(loc, val, problem, size=size, p0=p0, **kw))
 
 
 def _check_all(res, probs, problem, sizes=None, prices=None, **kw):
