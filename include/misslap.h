@@ -35,7 +35,8 @@ extern "C" {
  *      misslap_dense_batch_workspace_bytes, misslap_solve_sparse_batch_status, misslap_sparse_batch_workspace_bytes
  *      (with MISSLAP_BATCH_STATUS_NO_ENTRIES .. MISSLAP_BATCH_STATUS_PRICES_TOO_NARROW, codes 8 .. 14),
  *      misslap_options.mat_dtype with MISSLAP_DTYPE_F64 .. MISSLAP_DTYPE_BF16 (the first word of reserved[], which
- *      had to be 0 = MISSLAP_DTYPE_F64 until then; size and offsets of the struct did not change). */
+ *      had to be 0 = MISSLAP_DTYPE_F64 until then; size and offsets of the struct did not change),
+ *      misslap_solve_ell_batch, misslap_ell_batch_workspace_bytes. */
 
 /* misslap_options.mat_dtype: the element type of a dense stack */
 #define MISSLAP_DTYPE_F64 0   /* double */
@@ -669,6 +670,54 @@ int misslap_solve_sparse_batch_status(int64_t B, const int32_t *loc, const doubl
  * check records, the nnz + B row starts and, with cardinality_check, the cardinalities, each 256-byte aligned); -1 for
  * B < 1 or nnz < 0.  Needs no GPU.  has_prices is accepted for the day a layout depends on it: today's does not. */
 int64_t misslap_sparse_batch_workspace_bytes(int64_t B, int64_t nnz, int32_t has_prices, int32_t cardinality_check);
+
+/* ---- the sparse batch from padded candidate lists (ELL), the layout a top-k, a gating step or a nearest-neighbour
+ * search leaves on the device: cols[B][N][K] (int32, or int64 with cols_int64 != 0) and vals[B][N][K] (double, or float
+ * with opt->mat_dtype = MISSLAP_DTYPE_F32; F16 / BF16 are MISSLAP_ERR_INVALID here).  Problem b is rows 0 .. n_b - 1 of
+ * cols[b] / vals[b] (n_b = rows[b]; rows NULL: N).  Slot (i, k) is an entry iff cols[b][i][k] >= 0: a negative column is
+ * a hole, in any position, and the value stored in a hole is never interpreted.  With loc_b / val_b the entries of problem
+ * b in row order, within a row in slot order, holes dropped, and m_b = max column + 1, the result of problem b is bit for
+ * bit that of misslap_solve_sparse_batch_status on (loc_b, val_b) with sizes[b] = (m_b, n_b), i.e. of the reference's
+ * from_sparse(loc_b, val_b, size=(m_b, n_b)).solve(): N = n_b, so `fast` starts at (float)(1.0 / n_b).  A column may
+ * repeat within a row, with the meaning it has in the sparse batch.  float values are widened to double as they are read
+ * (exact); the result is that of the widened values.  Neither array is written.
+ * The call always gives a verdict per problem (there is no all-or-nothing form); no new codes.  The checks, in their order:
+ *    7 BAD_SHAPE             rows[b] outside 1 .. N: nothing of the problem is read
+ *    2 EMPTY_ROW             a row of 0 .. n_b - 1 without an entry
+ *    3 INFINITE_VALUE        a NaN or an infinity in an entry (never in a hole)
+ *   13 TOO_LARGE             a column at or above Mmax (an int64 column is compared in 64 bits: 2^31 + 5 is too large, not
+ *                            a hole and not column 5)
+ *   14 PRICES_TOO_NARROW     prices_in given and prices_ld < m_b
+ *    4 INFEASIBLE            cardinality_check and the guard found fewer than n_b rows matchable.  The guard matches the
+ *                            problems the checks 7, 2 and 13 pass; matching_size[b] is -1 for every other one.
+ *    5 PRICE_NOT_FINITE, 6 PRICE_NEGATIVE   over prices_in[b][:m_b]
+ * A problem with a status other than 0 takes no part in the solve (its workgroup leaves before it reads cols or vals):
+ * sol[b][:] = -1, prices_out[b][:] = 0, meta[b] = {n_rows = n_b, n_cols = m_b (saturated at INT32_MAX), nnz = its entries,
+ * every other result field 0}, all three counts 0 for BAD_SHAPE.
+ *   N, Mmax        1 .. MISSLAP_SPARSE_BATCH_MAX_DIM; K >= 1; N * K <= INT32_MAX - 128.  Mmax is the caller's bound on
+ *                  every column: sol is int32[B][N], prices_out double[B][Mmax] (may be NULL), and N and Mmax size the LDS
+ *                  carve and the workgroup as Nmax and Mmax do for misslap_solve_sparse_batch_status.
+ *   rows           int32[B] or NULL.      prices_in      double[B][prices_ld] or NULL, prices_ld >= 1.
+ *   fast           != 0: problem b starts at eps = (float)(1.0 / (double)n_b), formed in the kernel.
+ *   opt, stream, workspace, workspace_bytes, out_on_device, status, matching_size, meta, info
+ *                  as for misslap_solve_sparse_batch_status (workspace: misslap_ell_batch_workspace_bytes); opt->mat_dtype
+ *                  names the type of vals.  Without a workspace the library uploads host arrays (device pointers with
+ *                  input_on_device), uses its own scratch and synchronises once.  With a workspace EVERY pointer argument
+ *                  except opt and info is a device pointer, the three launches (check, guard, solve with verdict) go
+ *                  onto `stream`, and the call allocates nothing, creates no event, waits for nothing, copies nothing and
+ *                  reads no host array of per-problem data.
+ * Only what is wrong with the whole call is an error: B, N, K, Mmax, the caps, prices_ld < 1, a NULL cols / vals / sol /
+ * status, the options, a workspace that is too small or misaligned. */
+int misslap_solve_ell_batch(int64_t B, int64_t N, int64_t K, const void *cols, int32_t cols_int64, const void *vals,
+                            const int32_t *rows, int32_t fast, const double *prices_in, int64_t prices_ld,
+                            int32_t cardinality_check, const misslap_options *opt, void *stream, void *workspace,
+                            int64_t workspace_bytes, int64_t Mmax, int32_t *sol, double *prices_out,
+                            int32_t out_on_device, int32_t *status, int32_t *matching_size,
+                            misslap_dense_batch_meta *meta, misslap_dense_batch_info *info);
+/* Bytes of workspace a stream-ordered misslap_solve_ell_batch over B problems of N x K slots needs (the check records
+ * and, with cardinality_check, the cardinalities, each 256-byte aligned); -1 for B < 1, N or K out of range or N * K over
+ * its cap.  Needs no GPU.  has_prices is accepted for the day a layout depends on it: today's does not. */
+int64_t misslap_ell_batch_workspace_bytes(int64_t B, int64_t N, int64_t K, int32_t has_prices, int32_t cardinality_check);
 
 /* ---- the matching of many small graphs in one call: the batch form of misslap_hopcroft_karp / sslap.hopcroft_solve
  * (feasibility_.pyx:227-283).  Each graph is matched by ONE workgroup of ONE launch, its state in LDS

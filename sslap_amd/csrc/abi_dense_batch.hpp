@@ -132,7 +132,7 @@ MISSLAP_API int misslap_solve_dense_batch(int64_t B, int64_t N, int64_t M, const
         if ((rc = gev.create())) return rc;
         HIP_TRY(hipEventRecord(gev.e[0], st));
         dense_dtype_dispatch(opt.mat_dtype, [&](auto t) {
-            hipLaunchKernelGGL((k_matching_batch<true, decltype(t)>), dim3((unsigned)B), dim3(kMatchBatchThreads),
+            hipLaunchKernelGGL((k_matching_batch<MatchSrc::Dense, decltype(t)>), dim3((unsigned)B), dim3(kMatchBatchThreads),
                                matching_batch_lds_bytes(N, M, true), st, g);
         });
         HIP_TRY(hipGetLastError());

@@ -46,7 +46,7 @@ int dense_batch_status_enqueue(hipStream_t st, const misslap_options &opt, int64
         g.Ms = (int)M;
         g.size = d_card;
         dense_dtype_dispatch(opt.mat_dtype, [&](auto t) {
-            hipLaunchKernelGGL((k_matching_batch<true, decltype(t)>), dim3((unsigned)B), dim3(kMatchBatchThreads),
+            hipLaunchKernelGGL((k_matching_batch<MatchSrc::Dense, decltype(t)>), dim3((unsigned)B), dim3(kMatchBatchThreads),
                                matching_batch_lds_bytes(N, M, true), st, g);
         });
         HIP_TRY(hipGetLastError());

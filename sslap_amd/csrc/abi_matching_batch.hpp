@@ -12,10 +12,10 @@ int launch_matching_batch(hipStream_t st, int64_t B, const MatchBatchArgs &a, in
     const size_t lds = matching_batch_lds_bytes(a.Ns, a.Ms, kDense);
     if constexpr (kDense)
         dense_dtype_dispatch(mat_dtype, [&](auto t) {
-            hipLaunchKernelGGL((k_matching_batch<kDense, decltype(t)>), dim3((unsigned)B), dim3(kMatchBatchThreads), lds, st, a);
+            hipLaunchKernelGGL((k_matching_batch<MatchSrc::Dense, decltype(t)>), dim3((unsigned)B), dim3(kMatchBatchThreads), lds, st, a);
         });
     else
-        hipLaunchKernelGGL(k_matching_batch<kDense>, dim3((unsigned)B), dim3(kMatchBatchThreads), lds, st, a);
+        hipLaunchKernelGGL(k_matching_batch<MatchSrc::Loc>, dim3((unsigned)B), dim3(kMatchBatchThreads), lds, st, a);
     HIP_TRY(hipGetLastError());
     if (lds_out) *lds_out = lds;
     return MISSLAP_OK;

@@ -133,7 +133,7 @@ MISSLAP_API int misslap_solve_sparse_batch(int64_t B, const int32_t *loc, const 
         g.size = d_card;
         if ((rc = gev.create())) return rc;
         HIP_TRY(hipEventRecord(gev.e[0], st));
-        hipLaunchKernelGGL(k_matching_batch<false>, dim3((unsigned)B), dim3(kMatchBatchThreads),
+        hipLaunchKernelGGL(k_matching_batch<MatchSrc::Loc>, dim3((unsigned)B), dim3(kMatchBatchThreads),
                            matching_batch_lds_bytes(g.Ns, g.Ms, false), st, g);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(gev.e[1], st));

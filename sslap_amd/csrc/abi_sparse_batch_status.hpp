@@ -50,7 +50,7 @@ int sparse_batch_status_enqueue(hipStream_t st, const misslap_options &opt, cons
         g.Ns = (int)std::min<int64_t>(c.zmax, kSparseBatchMaxDim);
         g.Ms = kSparseBatchMaxDim;
         g.size = d_card;
-        hipLaunchKernelGGL(k_matching_batch<false>, dim3((unsigned)c.B), dim3(kMatchBatchThreads),
+        hipLaunchKernelGGL(k_matching_batch<MatchSrc::Loc>, dim3((unsigned)c.B), dim3(kMatchBatchThreads),
                            matching_batch_lds_bytes(g.Ns, g.Ms, false), st, g);
         HIP_TRY(hipGetLastError());
     }

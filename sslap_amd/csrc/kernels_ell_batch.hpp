@@ -1,0 +1,271 @@
+// kernels_ell_batch.hpp -- many small sparse problems given as padded candidate lists (ELL), one workgroup per problem
+// for its whole solve (misslap_solve_ell_batch, include/misslap.h; the host side is abi_ell_batch.hpp).
+//
+// The round loop is batch_solve (kernels_batch_solve.hpp); this file has the check pass, the ELL row source and the
+// solve with its verdict.  The input is what a top-k, a gating step or a nearest-neighbour search leaves on the device:
+// cols[B][N][K] (int32 or int64: the kernels' I) and vals[B][N][K] (double or float: V, widened where it is used by
+// dense_widen, exact).  Problem b is rows 0 .. n_b - 1 of its slice; slot (i, k) is an entry iff cols[b][i][k] >= 0, a
+// negative column is a hole in any position and the value stored in a hole is never interpreted.  The result is that of
+// the packed problem with the holes dropped (rows in order, within a row in slot order) under
+// from_sparse(loc_b, val_b, size=(m_b, n_b)): dropping holes keeps the order of the entries, and the bid's tie key is
+// only ever compared (top2_wave_reduce), so the slot index k serves as the stored index.
+//   BID      one wavefront per unassigned list position; lane l holds slots l, l + 64, ... of the row, both loads
+//            unit-stride.  A hole is skipped before anything is done with its column: it never indexes price[].
+//   eCE      choice_cost is the value at the LAST slot of row i whose column is p2o[i]; every entry is tested against it.
+//   get_obj  every entry whose column is p2o[i] is added, in row order and slot order.
+#pragma once
+
+namespace misslap {
+
+// per problem, from the check pass ahead of the guard and the solve
+struct EllBatchCheck {
+    unsigned long long nvalid;       // entries (valid slots) of rows 0 .. n - 1
+    unsigned long long absmax_bits;  // max |v| over them, as bits
+    int n;                           // rows[b], 0 where it lies outside 1 .. N (nothing of the problem is read then)
+    int empty_row;                   // first row without an entry (INT_MAX: none)
+    int max_col;                     // max column over the entries (-1: none), INT_MAX where it does not fit below that
+    int nonfinite;                   // an entry's value is a NaN or an infinity
+    int bad_price;                   // starting prices: bit 0 NaN / infinity, bit 1 sign bit set
+    int pad;
+};
+
+struct EllBatchArgs {
+    BatchSolveArgs s;          // Ns / Ms = N / Mmax: the LDS carve, sol_ld and prices_ld
+    const void *cols;          // [B][N][K] of the kernel's I
+    const void *vals;          // [B][N][K] of the kernel's V
+    long long N, K;
+    const EllBatchCheck *chk;  // [B]
+    const int *card;           // [B] the guard's cardinalities (-1: not matched), or null: no guard in this call
+    int fast;                  // eps_start = 1 / n_b of each problem
+    int *status;               // [B] MISSLAP_BATCH_STATUS_*
+    int *matching_size;        // [B] or null
+};
+
+// Check pass, one workgroup per problem, a wavefront per row: the entries per row and in all, the first empty row, the
+// largest column (compared in the index's own width: an int64 column at or above 2^31 is too large, not wrapped), NaN /
+// infinity and C = max |v| among the entries only, and the starting prices of the problem's columns.
+template <class I, class V>
+__global__ __launch_bounds__(256) void k_ell_batch_check(const I *cols, const V *vals, long long N, long long K,
+                                                         const int *rows, const double *p0, long long p0_ld,
+                                                         EllBatchCheck *out) {
+    const int b = blockIdx.x, lane = lane_id(), wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    int n = rows ? rows[b] : (int)N;
+    if (n < 1 || n > N) n = 0;
+    const size_t base = (size_t)b * (size_t)N * (size_t)K;
+    __shared__ unsigned long long s_cnt, s_abs;
+    __shared__ int s_empty, s_bad, s_maxc, s_badp;
+    if (threadIdx.x == 0) {
+        s_cnt = 0;
+        s_abs = 0;
+        s_empty = INT_MAX;
+        s_bad = 0;
+        s_maxc = -1;
+        s_badp = 0;
+    }
+    __syncthreads();
+    unsigned long long cnt = 0, am = 0;
+    int bad = 0;
+    I mc = -1;
+    for (int r = wave; r < n; r += nw) {
+        const size_t g0 = base + (size_t)r * (size_t)K;
+        int rc = 0;
+        for (long long q = lane; q < K; q += kWave) {
+            const I c = cols[g0 + q];
+            if (c < 0) continue;
+            const unsigned long long bits =
+                (unsigned long long)__double_as_longlong(dense_widen(vals[g0 + q])) & 0x7fffffffffffffffull;
+            ++rc;
+            am = bits > am ? bits : am;
+            bad |= bits >= 0x7ff0000000000000ull;
+            mc = c > mc ? c : mc;
+        }
+        for (int off = 32; off >= 1; off >>= 1) rc += __shfl_xor(rc, off);
+        if (rc == 0 && lane == 0) atomicMin(&s_empty, r);
+        cnt += (unsigned long long)rc;  // (uniform; lane 0's copy is added below)
+    }
+    if (lane == 0) atomicAdd(&s_cnt, cnt);
+    if (am) atomicMax(&s_abs, am);
+    if (bad) atomicOr(&s_bad, 1);
+    if (mc >= 0) atomicMax(&s_maxc, mc >= (I)INT_MAX ? INT_MAX : (int)mc);
+    __syncthreads();
+    if (p0 && s_maxc >= 0) {
+        const long long m = (long long)s_maxc + 1;
+        batch_check_prices(p0 + (size_t)b * (size_t)p0_ld, (int)(m < p0_ld ? m : p0_ld), &s_badp);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        EllBatchCheck r;
+        r.nvalid = s_cnt;
+        r.absmax_bits = s_abs;
+        r.n = n;
+        r.empty_row = s_empty;
+        r.max_col = s_maxc;
+        r.nonfinite = s_bad;
+        r.bad_price = s_badp;
+        r.pad = 0;
+        out[b] = r;
+    }
+}
+
+// The ELL row source of batch_solve: problem b's slices C / A (at (size_t)b * N * K, formed in 64 bits), row i at slot
+// i * K of them (an int: the host caps N * K at INT_MAX - 128).  Every valid column is below the carve's Ms once the
+// verdict is 0, so an int64 column narrows safely.
+template <class I, class V>
+struct EllBatchRows {
+    const I *C;
+    const V *A;
+    int K, maximize;
+    unsigned long long nvalid;
+
+    // the row in slot order, lane l at slots l, l + 64, ...; the tie key is the slot index
+    __device__ __forceinline__ Top2 bid(int i, const double *price, double &costbest, int &obj) const {
+        const int lane = lane_id();
+        const int g0 = i * K;
+        Top2 x;
+        x.v = -__builtin_huge_val();
+        x.w = -__builtin_huge_val();
+        x.g = -1;
+        double cb = 0.0;
+        int cj = 0;
+        for (int q = lane; q < K; q += kWave) {
+            const I c = C[g0 + q];
+            const V e = A[g0 + q];
+            if (c < 0) continue;  // a hole: its column never reaches price[], its value is not interpreted
+            const double v = dense_widen(e);
+            const double cost = maximize ? v : v * -1.0;  // :236-237
+            const double vi = cost - price[(int)c];
+            if (vi >= x.v) {  // :351 (the first entry is always taken: vi >= -inf for every non-NaN vi)
+                x.w = x.v;
+                x.v = vi;
+                x.g = q;
+                cb = cost;
+                cj = (int)c;
+            } else if (vi > x.w) {
+                x.w = vi;
+            }
+        }
+        const Top2 r = top2_wave_reduce(x);
+        const int gl = r.g & (kWave - 1);  // the lane that holds slot r.g
+        costbest = readlane_f64(cb, gl);
+        obj = __builtin_amdgcn_readlane(cj, gl);
+        return r;
+    }
+
+    // eCE_satisfied (auction_.pyx:443-485) for row i: choice_cost from the last slot of column j (j >= 0: never a hole)
+    __device__ __forceinline__ bool ece_bad(int i, int j, const double *price, double tol, double eps) const {
+        const int lane = lane_id();
+        const int g0 = i * K;
+        int last = -1;  // :462-467
+        for (int q = lane; q < K; q += kWave)
+            if (C[g0 + q] == (I)j) last = q;
+        last = wave_max_i32(last);
+        const double vj = dense_widen(A[g0 + last]);
+        const double choice_cost = maximize ? vj : vj * -1.0;
+        const double LHS = choice_cost - price[j] + tol;  // :475
+        bool bad = false;
+        for (int q = lane; q < K; q += kWave) {
+            const I c = C[g0 + q];
+            if (c < 0) continue;
+            const double v = dense_widen(A[g0 + q]);
+            const double cost = maximize ? v : v * -1.0;
+            if (LHS < (cost - price[(int)c]) - eps) bad = true;  // :482
+        }
+        return bad;
+    }
+
+    // get_obj (:489-523) over EVERY entry of the chosen column: a wavefront per row gathers the row's one matching value;
+    // a row with several matches (a repeated column) is marked (nsel[i] > 1) and re-walked by the summing lane.
+    __device__ __forceinline__ void gather(const int *p2o, int n, double *selv, int *nsel) const {
+        const int lane = lane_id(), wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+        for (int i = wave; i < n; i += nw) {
+            const int j = p2o[i];
+            if (j < 0) continue;
+            const int g0 = i * K;
+            int cnt = 0, at = -1;
+            for (int q = lane; q < K; q += kWave)
+                if (C[g0 + q] == (I)j) {
+                    ++cnt;
+                    at = q;
+                }
+            for (int off = 32; off >= 1; off >>= 1) cnt += __shfl_xor(cnt, off);
+            at = wave_max_i32(at);
+            if (lane == 0) {
+                nsel[i] = cnt;
+                selv[i] = dense_widen(A[g0 + at]);
+            }
+        }
+    }
+
+    // a double sum in row order, within a row in slot order
+    __device__ __forceinline__ double objective(const int *p2o, int n, const double *selv, const int *nsel) const {
+        double obj = 0;
+        for (int i = 0; i < n; ++i) {
+            const int j = p2o[i];
+            if (j == -1) continue;
+            if (nsel[i] == 1) {
+                const double v = maximize ? selv[i] : selv[i] * -1.0;
+                if (maximize) obj += v;
+                else obj -= v;
+                continue;
+            }
+            const int g0 = i * K;
+            for (int q = 0; q < K; ++q)
+                if (C[g0 + q] == (I)j) {
+                    const double e = dense_widen(A[g0 + q]);
+                    const double v = maximize ? e : e * -1.0;
+                    if (maximize) obj += v;
+                    else obj -= v;
+                }
+        }
+        return obj;
+    }
+
+    __device__ __forceinline__ int meta_cols(int m) const { return m; }
+    __device__ __forceinline__ int64_t meta_nnz() const { return (int64_t)nvalid; }
+};
+
+// The ELL checks of a verdict ahead of the guard and the starting prices, in their order (include/misslap.h);
+// batch_verdict adds those two.
+__device__ __forceinline__ int ell_batch_verdict(const EllBatchCheck &c, int Ms, long long p0_ld, bool has_p0) {
+    if (c.n < 1) return MISSLAP_BATCH_STATUS_BAD_SHAPE;
+    if (c.empty_row != INT_MAX) return MISSLAP_BATCH_STATUS_EMPTY_ROW;
+    if (c.nonfinite) return MISSLAP_BATCH_STATUS_INFINITE_VALUE;
+    if (c.max_col >= Ms) return MISSLAP_BATCH_STATUS_TOO_LARGE;
+    if (has_p0 && c.max_col >= p0_ld) return MISSLAP_BATCH_STATUS_PRICES_TOO_NARROW;
+    return MISSLAP_BATCH_STATUS_OK;
+}
+
+// The solve with the verdict formed here, from what the check pass and the guard left on the device.  A condemned
+// problem's workgroup writes the defined outputs and leaves before any LDS state exists and before anything of cols or
+// vals is read: a column beyond the carve never reaches the price array.  The others run batch_solve on the ELL source.
+template <class I, class V>
+__global__ __launch_bounds__(1024) void k_ell_batch_solve(EllBatchArgs a) {
+    const int b = blockIdx.x;
+    const EllBatchCheck ck = a.chk[b];
+    const int card = a.card ? a.card[b] : -1;
+    const int own = ell_batch_verdict(ck, a.s.Ms, a.s.p0_ld, a.s.p0 != nullptr);
+    const int code = batch_verdict(own, a.card != nullptr, card, ck.n, ck.bad_price);
+    if (threadIdx.x == 0) {
+        a.status[b] = code;
+        if (a.matching_size) a.matching_size[b] = card;
+    }
+    if (code != MISSLAP_BATCH_STATUS_OK) {
+        batch_condemn(a.s, ck.n, sparse_batch_count(ck.max_col), (long long)ck.nvalid);
+        return;
+    }
+    BatchSolveArgs bs = a.s;
+    if (a.fast) {  // the front-end's (1.0 / float64(N)).astype(float32) with N = n_b: the same two IEEE operations
+        bs.eps_b = nullptr;
+        bs.eps_opt = (float)(1.0 / (double)ck.n);
+    }
+    const size_t base = (size_t)b * (size_t)a.N * (size_t)a.K;
+    const I *C = static_cast<const I *>(a.cols) + base;
+    const V *A = static_cast<const V *>(a.vals) + base;
+    // (the two slice pointers as opaque scalars: left to itself the compiler also keeps base * sizeof(I) and
+    // base * sizeof(V) alive for the objective's scalar re-walk, and those four registers are the ones that spill)
+    asm volatile("" : "+s"(C), "+s"(A));
+    const EllBatchRows<I, V> rows{C, A, (int)a.K, bs.maximize, ck.nvalid};
+    batch_solve(bs, rows, ck.n, ck.max_col + 1, ck.absmax_bits);
+}
+
+}  // namespace misslap

@@ -17,7 +17,9 @@
 // Adjacency is read in stored order from (a) a slice of a packed loc, rows ascending (gaps allowed: an absent row has
 // no entries, as cumulative_idxs gives it, :22-46), or (b) the rows of a dense stack of element type E (double, float,
 // F16, Bf16: misslap_options.mat_dtype), entry iff v >= 0 by bit pattern in that type (dense_entry_valid: NaN is not an
-// entry, -0.0 and +inf are).  No value is ever widened here: only the pattern is read.
+// entry, -0.0 and +inf are), or (c) the padded candidate lists of the ELL batch (kernels_ell_batch.hpp): the loc source
+// with implicit row bounds u * K .. (u + 1) * K and a unit-stride column read of index type E (int, long long), a
+// negative column being a hole that no step visits.  No value is ever widened here: only the pattern is read.
 #pragma once
 
 namespace misslap {
@@ -26,6 +28,7 @@ constexpr int kMatchBatchMaxDim = MISSLAP_MATCHING_BATCH_MAX_DIM;
 constexpr int kMatchBatchThreads = 256;
 constexpr int kMatchInf = INT_MAX;  // the reference's inf of Dist
 constexpr int kMatchBatchMaxEntries = INT_MAX - 2 * kWave;  // entries of one graph
+enum class MatchSrc { Loc, Dense, Ell };  // where k_matching_batch reads its adjacency from
 
 // per graph of a packed loc, from k_matching_batch_check
 struct MatchBatchCheck {
@@ -42,8 +45,10 @@ struct MatchBatchArgs {
     const MatchBatchCheck *mchk;   // misslap_matching_batch: every graph was accepted by the host
     const SparseBatchCheck *schk;  // the sparse solve's guard: only clean problems within the carve are matched
     // source (b): dense stack [B][N][M], graph b = mat[b][:n_b][:m_b]
+    // source (c): ELL columns [B][N][M] (M = the K slots of a row), graph b = rows 0 .. n_b - 1 of mat[b]
     const void *mat;               // elements of the kernel's E
     long long N, M;
+    const EllBatchCheck *echk;     // source (c): only problems the check pass found clean are matched
     const int *shapes;             // [B][2] or null
     int Ns, Ms;                    // the LDS carve: largest n_b / m_b the launch takes
     int *size;                     // [B] cardinality; -1: not matched by this launch (the host guards it)
@@ -113,8 +118,9 @@ __device__ __forceinline__ void match_bfs_visit(int v, int L, const int *pair_v,
     }
 }
 
-template <bool kDense, class E = double>
+template <MatchSrc kSrc, class E = double>
 __global__ __launch_bounds__(kMatchBatchThreads) void k_matching_batch(MatchBatchArgs a) {
+    constexpr bool kDense = kSrc == MatchSrc::Dense, kEll = kSrc == MatchSrc::Ell, kLoc = kSrc == MatchSrc::Loc;
     const int b = blockIdx.x, tid = threadIdx.x, T = blockDim.x, lane = lane_id(), wave = tid >> 6, nw = T >> 6;
     int n = 0, m = 0;
     long long s = 0;
@@ -123,6 +129,14 @@ __global__ __launch_bounds__(kMatchBatchThreads) void k_matching_batch(MatchBatc
     if (kDense) {
         n = a.shapes ? a.shapes[2 * b] : (int)a.N;
         m = a.shapes ? a.shapes[2 * b + 1] : (int)a.M;
+        A = static_cast<const E *>(a.mat) + (size_t)b * (size_t)a.N * (size_t)a.M;
+    } else if (kEll) {
+        // clean: n_b within the stack, no empty row, every column within the carve (none negative: those are holes)
+        const EllBatchCheck c = a.echk[b];
+        const bool clean = c.n >= 1 && c.empty_row == INT_MAX && c.max_col < a.Ms;
+        n = clean ? c.n : 0;
+        m = clean ? c.max_col + 1 : 0;
+        nnz = (int)(a.N * a.M);  // slots, holes included (the host caps N * K at kMatchBatchMaxEntries)
         A = static_cast<const E *>(a.mat) + (size_t)b * (size_t)a.N * (size_t)a.M;
     } else {
         s = a.offsets[b];
@@ -153,21 +167,33 @@ __global__ __launch_bounds__(kMatchBatchThreads) void k_matching_batch(MatchBatc
     int *row_ptr = pair_v + a.Ms;  // loc input only
     __shared__ int s_tail, s_found, s_cnt;
     // the graph's entries: row and column of local index k (64-bit offsets: 2k overflows an int above 2^30 entries)
-    const int *lc = kDense ? nullptr : a.loc + 2 * s;
+    const int *lc = kLoc ? a.loc + 2 * s : nullptr;
+    const int ek = kEll ? (int)a.M : 0;
     auto row_of = [lc](int k) { return lc[2 * (long long)k]; };
-    auto col_of = [lc](int k) { return lc[2 * (long long)k + 1]; };
+    auto col_of = [=](int k) {  // (ELL: a hole reads as -1; a clean graph's columns are below Ms and narrow safely)
+        if constexpr (kEll) {
+            const E c = A[k];
+            return c < 0 ? -1 : (int)c;
+        } else {
+            return lc[2 * (long long)k + 1];
+        }
+    };
+    // the stored entries (ELL: the slots) of row u: g_begin(u) .. g_end(u)
+    auto g_begin = [=](int u) { return kDense ? 0 : kEll ? u * ek : row_ptr[u]; };
+    auto g_end = [=](int u) { return kDense ? m : kEll ? (u + 1) * ek : row_ptr[u + 1]; };
 
     for (int i = tid; i < n; i += T) pair_u[i] = -1;
     for (int j = tid; j < m; j += T) pair_v[j] = -1;
-    if (!kDense) {  // row starts of cumulative_idxs (:22-46): an absent row is an empty run
+    if (kLoc) {  // row starts of cumulative_idxs (:22-46): an absent row is an empty run
         for (int k = tid; k < nnz; k += T) {
             const int r = row_of(k), rp = k ? row_of(k - 1) : -1;
             for (int q = rp + 1; q <= r; ++q) row_ptr[q] = k;
         }
         if (tid == 0) row_ptr[n] = nnz;  // (the last entry's row is n - 1)
     }
-    // loc rows this short are expanded one per lane in the BFS, longer ones one per wavefront
-    const bool lane_rows = !kDense && nnz <= 16 * n;
+    // loc rows this short (ELL: rows of at most 16 slots) are expanded one per lane in the BFS, longer ones one per
+    // wavefront
+    const bool lane_rows = kLoc ? nnz <= 16 * n : kEll && ek <= 16;
     __syncthreads();
 
     for (int phase = 0;; ++phase) {
@@ -189,7 +215,7 @@ __global__ __launch_bounds__(kMatchBatchThreads) void k_matching_batch(MatchBatc
         int qs = 0, qe = s_tail, nil = kMatchInf;
         for (int L = 0; qs < qe; ++L) {
             bool found = false;
-            if (kDense) {
+            if constexpr (kDense) {
                 for (int x = qs + wave; x < qe; x += nw) {
                     const E *row = A + (size_t)queue[x] * (size_t)a.M;
                     for (int c = lane; c < m; c += kWave)
@@ -198,14 +224,18 @@ __global__ __launch_bounds__(kMatchBatchThreads) void k_matching_batch(MatchBatc
             } else if (lane_rows) {
                 for (int x = qs + tid; x < qe; x += T) {
                     const int u = queue[x];
-                    for (int g = row_ptr[u]; g < row_ptr[u + 1]; ++g)
-                        match_bfs_visit(col_of(g), L, pair_v, dist, queue, &s_tail, found);
+                    for (int g = g_begin(u); g < g_end(u); ++g) {
+                        const int v = col_of(g);
+                        if (!kEll || v >= 0) match_bfs_visit(v, L, pair_v, dist, queue, &s_tail, found);
+                    }
                 }
             } else {
                 for (int x = qs + wave; x < qe; x += nw) {
-                    const int u = queue[x], g1 = row_ptr[u + 1];
-                    for (int g = row_ptr[u] + lane; g < g1; g += kWave)
-                        match_bfs_visit(col_of(g), L, pair_v, dist, queue, &s_tail, found);
+                    const int u = queue[x], g1 = g_end(u);
+                    for (int g = g_begin(u) + lane; g < g1; g += kWave) {
+                        const int v = col_of(g);
+                        if (!kEll || v >= 0) match_bfs_visit(v, L, pair_v, dist, queue, &s_tail, found);
+                    }
                 }
             }
             if (found) s_found = 1;
@@ -232,14 +262,14 @@ __global__ __launch_bounds__(kMatchBatchThreads) void k_matching_batch(MatchBatc
                     const int root = base + __ffsll((long long)roots) - 1;
                     roots &= roots - 1;
                     int depth = 0, u = root;
-                    int g = kDense ? 0 : row_ptr[u], g1 = kDense ? m : row_ptr[u + 1];
+                    int g = g_begin(u), g1 = g_end(u);
                     for (;;) {
                         int v = -1, pu = -1, k = -1;
                         for (; g < g1; g += kWave) {
                             const int pos = g + lane;
                             int cv = -1;
                             if (pos < g1) {
-                                if (kDense) cv = dense_entry_valid(A[(size_t)u * (size_t)a.M + pos]) ? pos : -1;
+                                if constexpr (kDense) cv = dense_entry_valid(A[(size_t)u * (size_t)a.M + pos]) ? pos : -1;
                                 else cv = col_of(pos);
                             }
                             int cp = -1;
@@ -263,8 +293,8 @@ __global__ __launch_bounds__(kMatchBatchThreads) void k_matching_batch(MatchBatc
                             st_g[depth] = g;
                             ++depth;
                             u = pu;
-                            g = kDense ? 0 : row_ptr[u];
-                            g1 = kDense ? m : row_ptr[u + 1];
+                            g = g_begin(u);
+                            g1 = g_end(u);
                             continue;
                         }
                         if (k >= 0) {  // a free column: the path succeeds, every level takes its chosen column
@@ -284,7 +314,7 @@ __global__ __launch_bounds__(kMatchBatchThreads) void k_matching_batch(MatchBatc
                         --depth;  // the parent goes on after the child's entry
                         u = queue[depth];
                         g = st_g[depth];
-                        g1 = kDense ? m : row_ptr[u + 1];
+                        g1 = g_end(u);
                     }
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 }

@@ -195,7 +195,8 @@ def raise_for_status(res):
     """Raise, for the first problem of a status-mode result whose status is not 0, the ValueError the default mode
     raises for the same batch ("problem <b>: ..."); return res when every status is 0.  For a result of
     auction_solve_sparse_batch: what its default mode raises with cardinality_check=False for that check, a
-    ZeroDivisionError for `fast` with N = 0 included."""
+    ZeroDivisionError for `fast` with N = 0 included.  For a result of auction_solve_ell_batch: the ValueError its own
+    default mode raises."""
     def host(x):
         return x if isinstance(x, np.ndarray) else x.cpu().numpy()
     if "stream" in res:
@@ -205,8 +206,11 @@ def raise_for_status(res):
     if bad.size == 0:
         return res
     b = int(bad[0])
-    if res.get("layout") == "sparse":
-        from .sparse_batch import _status_error
+    if res.get("layout") in ("sparse", "ell"):
+        if res["layout"] == "sparse":
+            from .sparse_batch import _status_error
+        else:
+            from .ell_batch import _status_error
         raise _status_error(res, b, int(status[b]), int(host(res["meta"]["n_rows"])[b]),
                             int(host(res["meta"]["n_cols"])[b]), int(host(res["matching_size"])[b]))
     N, M = res["stack"]

@@ -1,0 +1,225 @@
+"""Many small sparse assignment problems given as padded candidate lists (misslap_solve_ell_batch, include/misslap.h).
+
+The layout a top-k, a gating step or a nearest-neighbour search leaves on the device: `cols` (B, N, K) and `vals`
+(B, N, K).  Problem b is rows 0 .. n_b - 1 of cols[b] / vals[b]; slot (i, k) is an entry iff cols[b, i, k] >= 0, a
+negative column is a hole in any position and the value stored in a hole is never interpreted.  `ell_to_packed` is the
+definition: the result of problem b is bit for bit `auction_solve(loc=loc_b, val=val_b, size=(m_b, n_b), ...)` on its
+output (csrc/kernels_batch_solve.hpp, csrc/kernels_ell_batch.hpp).  The reference has no counterpart.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from ._batch import _decode_meta, _is_device_tensor, _new_meta, _solve_options, _starting_prices
+
+MAX_DIM = _lib.SPARSE_BATCH_MAX_DIM
+_INT_MAX = 2**31 - 1
+_MAX_SLOTS = _INT_MAX - 128  # N * K: the guard indexes the slots of a problem with an int
+
+# what each status code of misslap_solve_ell_batch says, in the words of the dense and the sparse batch where a code is
+# theirs
+_STATUS_TEXT = {
+    _lib.BATCH_STATUS_BAD_SHAPE: "rows = {r} outside 1 .. {N}",
+    _lib.BATCH_STATUS_EMPTY_ROW: "every row 0..N-1 must have at least one entry (auction_.pyx:33-48 contract)",
+    _lib.BATCH_STATUS_INFINITE_VALUE: "val holds a NaN or an infinity",
+    _lib.BATCH_STATUS_PRICES_TOO_NARROW: "prices hold {P} columns, the problem has {m}",
+    _lib.BATCH_STATUS_INFEASIBLE: "Matrix is infeasible (Maximum matching possible only involves {card} out of {n} rows.)",
+    _lib.BATCH_STATUS_PRICE_NOT_FINITE: "prices hold a NaN or an infinity",
+    _lib.BATCH_STATUS_PRICE_NEGATIVE: "prices must be >= 0 (with the sign bit clear: -0.0 is rejected)",
+}
+
+
+def ell_to_packed(cols, vals, rows=None):
+    """numpy (B, N, K) cols / vals -> [(loc_b int32 (nnz_b, 2), val_b float64 (nnz_b,))]: the entries of rows
+    0 .. rows[b] - 1 of problem b in row order, within a row in slot order, the holes (cols < 0) dropped.  The
+    definition of auction_solve_ell_batch: problem b is auction_solve(loc=loc_b, val=val_b, size=(m_b, n_b)) with
+    n_b = rows[b] and m_b = loc_b[:, 1].max() + 1."""
+    cols, vals = np.asarray(cols), np.asarray(vals)
+    if cols.ndim != 3 or vals.shape != cols.shape:
+        raise ValueError(f"cols and vals must have one shape (B, N, K), got {cols.shape} and {vals.shape}")
+    B, N, _ = cols.shape
+    ns = np.full(B, N) if rows is None else np.asarray(rows)
+    out = []
+    for b in range(B):
+        c = cols[b, :max(int(ns[b]), 0)]
+        i, k = np.nonzero(c >= 0)  # (row-major: row order, then slot order)
+        loc = np.ascontiguousarray(np.stack([i, c[i, k]], axis=1), dtype=np.int32)
+        out.append((loc, np.ascontiguousarray(vals[b, i, k], dtype=np.float64)))
+    return out
+
+
+def _check_input(cols, vals):
+    """dtype / shape / device of cols and vals; returns (B, N, K, on_device, cols_int64, the MISSLAP_DTYPE_* of vals)."""
+    if isinstance(cols, np.ndarray) and isinstance(vals, np.ndarray):
+        on_device = False
+        names = (cols.dtype.name, vals.dtype.name)
+        ndims = (cols.ndim, vals.ndim)
+    elif _is_device_tensor(cols) and _is_device_tensor(vals):
+        on_device = True
+        names = (str(cols.dtype).split(".")[-1], str(vals.dtype).split(".")[-1])
+        ndims = (cols.dim(), vals.dim())
+    else:
+        raise TypeError("cols and vals must both be numpy arrays or both tensors on the device")
+    if names[0] not in ("int32", "int64"):
+        raise ValueError(f"cols must be int32 or int64, got {names[0]}")
+    if names[1] not in ("float64", "float32"):
+        raise ValueError(f"vals must be float64 or float32, got {names[1]}")
+    if ndims[0] != 3:
+        raise ValueError(f"cols must have 3 dimensions (B, N, K), got {ndims[0]}")
+    if tuple(vals.shape) != tuple(cols.shape):
+        raise ValueError(f"cols has shape {tuple(cols.shape)}, vals {tuple(vals.shape)}")
+    if on_device:
+        if cols.device != vals.device:
+            raise ValueError(f"cols is on {cols.device}, vals on {vals.device}")
+        if not cols.is_contiguous() or not vals.is_contiguous():
+            raise ValueError("device tensors must be contiguous (they are read in place)")
+    B, N, K = (int(d) for d in cols.shape)
+    if B < 1 or N < 1 or K < 1:
+        raise ValueError(f"empty stack of shape {(B, N, K)}")
+    if N > MAX_DIM:
+        raise ValueError(f"problems of {N} rows: auction_solve_ell_batch takes at most {MAX_DIM} "
+                         f"(MISSLAP_SPARSE_BATCH_MAX_DIM)")
+    if N * K > _MAX_SLOTS:
+        raise ValueError(f"N * K = {N * K} slots per problem: at most {_MAX_SLOTS}")
+    return B, N, K, on_device, names[0] == "int64", _lib.DTYPE_F32 if names[1] == "float32" else _lib.DTYPE_F64
+
+
+def _check_rows(rows, B, on_device, dev):
+    """Optional int32 (B,) row counts, on the host or (with device input) on the device.  Their values are the
+    library's to judge: a count outside 1 .. N is the problem's status."""
+    if rows is None:
+        return None
+    if _is_device_tensor(rows):
+        import torch
+        if not on_device:
+            raise TypeError("rows on the device need cols / vals on the device")
+        if rows.dtype != torch.int32 or tuple(rows.shape) != (B,) or rows.device != dev or not rows.is_contiguous():
+            raise ValueError(f"a device rows tensor must be contiguous int32 of shape ({B},) on {dev}, got {rows.dtype} "
+                             f"{tuple(rows.shape)} on {rows.device}")
+        return rows
+    r = np.asarray(rows)
+    if r.shape != (B,) or not np.issubdtype(r.dtype, np.integer):
+        raise ValueError(f"rows must be an integer array of shape ({B},), got {r.dtype} {r.shape}")
+    return np.ascontiguousarray(np.clip(r, -1, _INT_MAX), dtype=np.int32)  # (whatever is out of range stays so)
+
+
+def _check_n_cols(n_cols):
+    try:
+        ok = int(n_cols) == n_cols and 1 <= int(n_cols) <= MAX_DIM
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"n_cols must be an integer in 1 .. {MAX_DIM} (MISSLAP_SPARSE_BATCH_MAX_DIM), got {n_cols!r}")
+    return int(n_cols)
+
+
+def auction_solve_ell_batch(cols, vals, rows=None, n_cols=None, problem="min", eps_start=0., max_iter=1000000, fast=False,
+                            cardinality_check=True, prices=None, errors="raise"):
+    """Solve B independent sparse problems given as padded candidate lists, one workgroup per problem.
+
+    cols: int32 or int64 (B, N, K) and vals: float64 or float32 of the same shape, both numpy arrays or both contiguous
+    tensors on one device (read in place, never written, problem='min' included).  Problem b is rows 0 .. rows[b] - 1
+    (rows: optional int32 (B,), on the host or the device; default N); slot (i, k) is an entry iff cols[b, i, k] >= 0,
+    any negative column is a hole and its value is never interpreted.  The result of problem b is bit for bit
+    auction_solve(loc=loc_b, val=val_b, size=(m_b, n_b)) on ell_to_packed's (loc_b, val_b); float32 values are widened to
+    float64 as they are read, which is exact.  N <= MISSLAP_SPARSE_BATCH_MAX_DIM, N * K <= 2^31 - 129.
+    n_cols: Mmax in 1 .. MISSLAP_SPARSE_BATCH_MAX_DIM, the caller's bound on every column (a column at or above it is
+    MISSLAP_BATCH_STATUS_TOO_LARGE for its problem).  Without it the maximum of cols is taken: with device input that is
+    the call's one read-back; with it a call on device input waits for nothing.
+    prices: optional float64 (B, P) starting prices, on the host or the device; a problem with more than P columns gets
+    MISSLAP_BATCH_STATUS_PRICES_TOO_NARROW.
+
+    errors="status" returns dict(sol=int32 (B, N) with -1 beyond n_b, prices=float64 (B, n_cols) with 0 beyond m_b,
+    status=int32 (B,) MISSLAP_BATCH_STATUS_* codes, matching_size=int32 (B,), meta, layout="ell", ...): the dict of the
+    other status modes, for device input device tensors ordered on torch.cuda.current_stream(cols.device).  The checks,
+    in their order: rows[b] outside 1 .. N (BAD_SHAPE), an empty row, a NaN / infinity in an entry, a column >= n_cols,
+    prices narrower than the problem, the matching guard (cardinality_check), a bad starting price.  A problem with a
+    status other than 0 has sol -1, prices 0 and a meta of n_rows, n_cols, nnz and zeros.  batch_meta_to_host and
+    raise_for_status take the result.
+    errors="raise" (default) runs the same call and raises ValueError("problem <b>: ...") for the first problem whose
+    status is not 0; else it returns the same dict.
+    """
+    if errors not in ("raise", "status"):
+        raise ValueError(f"errors must be 'raise' or 'status', got {errors!r}")
+    B, N, K, on_device, wide, dtype = _check_input(cols, vals)
+    dev = cols.device if on_device else None
+    rws = _check_rows(rows, B, on_device, dev)
+    e = float(eps_start)
+    if e != e:
+        raise ValueError("eps_start is NaN")
+    if prices is not None:  # dtype and shape: float64 (B, P), any P >= 1; a device tensor only with device input
+        _starting_prices(prices, B, 1, False, on_device and not isinstance(prices, np.ndarray), cols, "cols / vals")
+        if _is_device_tensor(prices) and prices.device != dev:
+            raise ValueError(f"prices are on {prices.device}, cols on {dev}")
+    if n_cols is not None:
+        Mmax = _check_n_cols(n_cols)
+    else:  # (with device input the call's one read-back, ordered behind the current stream like every read of cols)
+        Mmax = min(max(int(cols.max()) + 1, 1), MAX_DIM)
+    check = 1 if cardinality_check else 0
+    opts = _solve_options(on_device, cols, problem, e, max_iter, dtype)
+    lib = _lib.load()
+    common = dict(layout="ell", stack=(N, K), n_cols=Mmax, prices_ld=0 if prices is None else int(prices.shape[1]))
+    if not on_device:  # synchronous: the library uploads, uses its own scratch and waits once
+        cc, vc = np.ascontiguousarray(cols), np.ascontiguousarray(vals)
+        p = None if prices is None else np.ascontiguousarray(prices)
+        sol, pout = np.empty((B, N), dtype=np.int32), np.empty((B, Mmax), dtype=np.float64)
+        status, msize = np.empty(B, dtype=np.int32), np.empty(B, dtype=np.int32)
+        metas, info = _new_meta(B)
+        _lib.check(lib.misslap_solve_ell_batch(
+            B, N, K, cc.ctypes.data, 1 if wide else 0, vc.ctypes.data, None if rws is None else rws.ctypes.data,
+            1 if fast else 0, None if p is None else p.ctypes.data, common["prices_ld"], check, C.byref(opts), None, None, 0,
+            Mmax, sol.ctypes.data, pout.ctypes.data, 0, status.ctypes.data, msize.ctypes.data, C.cast(metas, C.c_void_p),
+            C.byref(info)))
+        res = dict(sol=sol, prices=pout, status=status, matching_size=msize, meta=_decode_meta(metas, info), rows=rws,
+                   **common)
+    else:
+        import torch
+        from .dense_batch import _meta_views
+
+        def send(a):  # a host array from pinned memory, without a wait (torch takes no read-only array: a copy then)
+            if not isinstance(a, np.ndarray):
+                return a
+            return torch.from_numpy(a if a.flags.writeable else a.copy()).pin_memory().to(dev, non_blocking=True)
+        with torch.cuda.device(dev):  # (the allocations and copies below are made on the current stream of cols' device)
+            stream = torch.cuda.current_stream(dev)
+            d_rows = send(rws)
+            d_p = None if prices is None else send(np.ascontiguousarray(prices) if isinstance(prices, np.ndarray)
+                                                   else prices.contiguous())
+            nbytes = int(lib.misslap_ell_batch_workspace_bytes(B, N, K, 0 if d_p is None else 1, check))
+            work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            sol = torch.empty((B, N), dtype=torch.int32, device=dev)
+            pout = torch.empty((B, Mmax), dtype=torch.float64, device=dev)
+            status = torch.empty(B, dtype=torch.int32, device=dev)
+            msize = torch.empty(B, dtype=torch.int32, device=dev)
+            rec = torch.empty((B, C.sizeof(_lib.DenseBatchMeta)), dtype=torch.uint8, device=dev)
+        info = _lib.DenseBatchInfo()
+        _lib.check(lib.misslap_solve_ell_batch(
+            B, N, K, cols.data_ptr(), 1 if wide else 0, vals.data_ptr(), None if d_rows is None else d_rows.data_ptr(),
+            1 if fast else 0, None if d_p is None else d_p.data_ptr(), common["prices_ld"], check, C.byref(opts),
+            C.c_void_p(int(stream.cuda_stream)), work.data_ptr(), nbytes, Mmax, sol.data_ptr(), pout.data_ptr(), 1,
+            status.data_ptr(), msize.data_ptr(), rec.data_ptr(), C.byref(info)))
+        # the workspace and the inputs stay referenced by the result: nothing of this call is recycled before it
+        res = dict(sol=sol, prices=pout, status=status, matching_size=msize, meta=_meta_views(rec), rows=d_rows, records=rec,
+                   info=info, stream=stream, keep=(work, cols, vals, d_rows, d_p), **common)
+    if errors == "raise":
+        from .dense_batch import raise_for_status
+        raise_for_status(res)
+    return res
+
+
+def _status_error(res, b, code, n, m, card):
+    """The exception of problem b of an ELL result (n, m: the record's n_rows and n_cols; card: its matching_size)."""
+    N, Mmax = res["stack"][0], res["n_cols"]
+    if code == _lib.BATCH_STATUS_TOO_LARGE:
+        if m >= _INT_MAX:
+            text = "column index too large (max + 1 must fit an int32)"
+        else:
+            text = f"{n} x {m} does not fit n_cols = {Mmax}"
+    else:
+        r = N
+        if code == _lib.BATCH_STATUS_BAD_SHAPE:
+            rows = res["rows"]
+            r = int(rows[b] if isinstance(rows, np.ndarray) else rows[b].item())
+        text = _STATUS_TEXT[code].format(r=r, N=N, n=n, m=m, card=card, P=res["prices_ld"])
+    return ValueError(f"problem {b}: {text}")

@@ -23,7 +23,13 @@ KEYS = (("sgpr", r"TotalSGPRs"), ("vgpr", r"VGPRs"), ("scratch", r"ScratchSize \
         ("lds", r"LDS Size \[bytes/block\]"))
 for b in re.split(r"remark: Function Name: ", txt)[1:]:
     name = subprocess.run(["c++filt", b.split()[0]], capture_output=True, text=True).stdout.strip()
-    name = re.sub(r"^void misslap::", "", name).split("(")[0]
+    name = re.sub(r"^void misslap::", "", name)
+    depth = 0  # the name without its parameter list (a template argument may hold parentheses of its own)
+    for k in range(len(name) - 1, -1, -1):
+        depth += (name[k] == ")") - (name[k] == "(")
+        if depth == 0:
+            name = name[:k] if name[k] == "(" else name
+            break
     if args and not any(a in name for a in args):
         continue
     vals = []
