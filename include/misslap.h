@@ -36,7 +36,8 @@ extern "C" {
  *      (with MISSLAP_BATCH_STATUS_NO_ENTRIES .. MISSLAP_BATCH_STATUS_PRICES_TOO_NARROW, codes 8 .. 14),
  *      misslap_options.mat_dtype with MISSLAP_DTYPE_F64 .. MISSLAP_DTYPE_BF16 (the first word of reserved[], which
  *      had to be 0 = MISSLAP_DTYPE_F64 until then; size and offsets of the struct did not change),
- *      misslap_solve_ell_batch, misslap_ell_batch_workspace_bytes. */
+ *      misslap_solve_ell_batch, misslap_ell_batch_workspace_bytes, misslap_solve_ell_batch_outside,
+ *      misslap_ell_batch_outside_workspace_bytes. */
 
 /* misslap_options.mat_dtype: the element type of a dense stack */
 #define MISSLAP_DTYPE_F64 0   /* double */
@@ -718,6 +719,49 @@ int misslap_solve_ell_batch(int64_t B, int64_t N, int64_t K, const void *cols, i
  * and, with cardinality_check, the cardinalities, each 256-byte aligned); -1 for B < 1, N or K out of range or N * K over
  * its cap.  Needs no GPU.  has_prices is accepted for the day a layout depends on it: today's does not. */
 int64_t misslap_ell_batch_workspace_bytes(int64_t B, int64_t N, int64_t K, int32_t has_prices, int32_t cardinality_check);
+
+/* ---- the ELL batch with an outside option per row: partial assignments.  Problem b is the packed problem of
+ * misslap_solve_ell_batch plus ONE entry per row, stored last in its row behind every slot: row i (i < n_b) gets
+ * (i, m_b + i) with the row's outside value -- with opt->maximize = 0 the cost of leaving row i unmatched, else the value
+ * of doing so; m_b = max real column + 1, 0 for a problem without any entry.  The object m_b + i is private to row i, so
+ * every row can always be assigned and a row may stay without a real column.  The result of problem b is bit for bit the
+ * reference's from_sparse(loc_b, val_b, size=(m_b + n_b, n_b)).solve() on that packing (with prices_in: started from
+ * [prices_in[b][:m_b], zeros(n_b)]; the outside objects always start at 0), given in the caller's terms:
+ *   sol[b][i]              the real column of row i, or -1 where the row took its outside option (and beyond n_b, on a
+ *                          condemned problem, and where max_iter cut the solve before the row was assigned)
+ *   prices_out[b][:Mmax]   the prices of the real columns, 0 beyond m_b
+ *   outside_prices_out     double[B][N] or NULL: the price of row i's outside object, 0 beyond n_b.  A row without any
+ *                          real entry is a one-entry row of the reference: it bids +inf, and that is its outside price.
+ *   meta[b]                the augmented problem's record: n_cols = m_b + n_b, nnz = entries + n_b; n_assigned counts the
+ *                          rows on their outside option too.
+ *   outside, outside_ld    outside_ld == 0: double[B], one value per problem; outside_ld >= N: double[B][outside_ld], the
+ *                          value of row i at outside[b * outside_ld + i]; anything else is MISSLAP_ERR_INVALID.  The
+ *                          values of rows >= n_b are never read.
+ * The checks, in their order: 7 BAD_SHAPE; 3 INFINITE_VALUE (an entry, or the outside value of a row < n_b, is a NaN or an
+ * infinity); 13 TOO_LARGE (a real column >= Mmax); 14 PRICES_TOO_NARROW; 5 PRICE_NOT_FINITE; 6 PRICE_NEGATIVE.  EMPTY_ROW
+ * and INFEASIBLE cannot occur: a row without entries, a graph without a complete matching, n_b > m_b and a problem of
+ * holes only (every row comes back -1) are all solved.  No guard is launched and matching_size[b] (may be NULL) is -1.  A
+ * problem with a status other than 0 has sol -1, prices_out 0, outside_prices_out 0 and meta[b] = {n_rows = n_b, n_cols =
+ * m_b + n_b (saturated at INT32_MAX), nnz = its entries + n_b, every other result field 0}.
+ * Mmax stays the bound on the REAL columns (1 .. MISSLAP_SPARSE_BATCH_MAX_DIM); the LDS carve is sized for N rows and
+ * Mmax + N objects (155 648 bytes at 2048 / 2048).  Every other argument is misslap_solve_ell_batch's, in both of its
+ * modes: with a workspace (misslap_ell_batch_outside_workspace_bytes) every pointer except opt and info is a device
+ * pointer and the call enqueues two launches (check, solve with verdict) on `stream` and waits for nothing; without one
+ * the library uploads host arrays, uses its own scratch and synchronises once.
+ * On eps: the augmented problem is rectangular (more objects than rows), where the reference's eps-scaling (eps_start = 0,
+ * fast = 0) keeps the prices of earlier phases and is NOT optimal in general.  A single phase -- fast != 0, or
+ * 0 < eps_start <= 1 / n_b -- from zero prices is optimal within n_b * eps. */
+int misslap_solve_ell_batch_outside(int64_t B, int64_t N, int64_t K, const void *cols, int32_t cols_int64,
+                                    const void *vals, const int32_t *rows, int32_t fast, const double *prices_in,
+                                    int64_t prices_ld, const misslap_options *opt, void *stream, void *workspace,
+                                    int64_t workspace_bytes, int64_t Mmax, const double *outside, int64_t outside_ld,
+                                    int32_t *sol, double *prices_out, double *outside_prices_out, int32_t out_on_device,
+                                    int32_t *status, int32_t *matching_size, misslap_dense_batch_meta *meta,
+                                    misslap_dense_batch_info *info);
+/* Bytes of workspace a stream-ordered misslap_solve_ell_batch_outside needs: the check records and, with has_prices, the
+ * staged starting prices of the augmented problems (B x (Mmax + N) doubles), each 256-byte aligned; -1 where B, N, K or
+ * Mmax are out of range.  Needs no GPU. */
+int64_t misslap_ell_batch_outside_workspace_bytes(int64_t B, int64_t N, int64_t K, int64_t Mmax, int32_t has_prices);
 
 /* ---- the matching of many small graphs in one call: the batch form of misslap_hopcroft_karp / sslap.hopcroft_solve
  * (feasibility_.pyx:227-283).  Each graph is matched by ONE workgroup of ONE launch, its state in LDS

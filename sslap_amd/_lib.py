@@ -200,6 +200,11 @@ SYMBOLS = {
                                           C.c_int32, C.POINTER(Options), _VP, _VP, C.c_int64, C.c_int64, _VP, _VP, C.c_int32,
                                           _VP, _VP, _VP, C.POINTER(DenseBatchInfo)]),
     "misslap_ell_batch_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
+    "misslap_solve_ell_batch_outside": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, _VP, C.c_int32, _VP, _VP, C.c_int32, _VP,
+                                                  C.c_int64, C.POINTER(Options), _VP, _VP, C.c_int64, C.c_int64, _VP,
+                                                  C.c_int64, _VP, _VP, _VP, C.c_int32, _VP, _VP, _VP,
+                                                  C.POINTER(DenseBatchInfo)]),
+    "misslap_ell_batch_outside_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32]),
     "misslap_matching_batch": (C.c_int, [C.c_int64, _VP, _VP, C.POINTER(Options), _VP, _VP, _VP, _VP, C.c_int64, _VP,
                                          C.c_int64, C.c_int32, C.POINTER(MatchingBatchInfo)]),
     "misslap_matching_dense_batch": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, _VP, _VP, C.POINTER(Options), _VP, _VP,

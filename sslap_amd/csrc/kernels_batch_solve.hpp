@@ -56,6 +56,17 @@ __host__ __device__ constexpr size_t batch_solve_lds_bytes(long long N, long lon
     return (size_t)M * (8 + 8 + 4 + 4) + (size_t)N * (8 + 4 + 4 + 4 + 4 + 4);
 }
 
+// Where batch_solve keeps the prices and person_to_object of its problem in that allocation (s_raw: its start), for a
+// kernel that reads them behind it: both hold the final state once batch_solve has returned.  The offsets follow the
+// carve at the top of batch_solve -- price[Ms], bkey[Ms], bid_key[Ns], o2p[Ms], bpos[Ms], p2o[Ns], ... -- and must move
+// with it.
+__device__ __forceinline__ const double *batch_solve_price(const unsigned char *s_raw) {
+    return reinterpret_cast<const double *>(s_raw);
+}
+__device__ __forceinline__ const int *batch_solve_p2o(const unsigned char *s_raw, int Ns, int Ms) {
+    return reinterpret_cast<const int *>(s_raw + (size_t)Ms * (8 + 8 + 4 + 4) + (size_t)Ns * 8);
+}
+
 // The starting prices p[0 .. m) of one problem in a check pass: bit 0 NaN / infinity, bit 1 sign bit set, into *s_badp
 __device__ __forceinline__ void batch_check_prices(const double *p, int m, int *s_badp) {
     int bad = 0;
@@ -120,6 +131,8 @@ __device__ __forceinline__ bool batch_ece(const Rows &rows, int n, const double 
 template <class Rows>
 __device__ __forceinline__ void batch_solve(const BatchSolveArgs &a, const Rows &rows, int n, int m,
                                             unsigned long long absmax_bits) {
+    // (the order of the carve below is restated by batch_solve_price / batch_solve_p2o above, for the kernel that reads
+    // the final state behind this function: k_ell_outside_solve.  Change both together.)
     extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
     __shared__ int s_holes, s_nmove, s_fail;
     const int b = blockIdx.x, tid = threadIdx.x, T = blockDim.x, lane = lane_id(), wave = tid >> 6, nw = T >> 6;

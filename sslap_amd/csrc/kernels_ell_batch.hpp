@@ -13,6 +13,14 @@
 //            unit-stride.  A hole is skipped before anything is done with its column: it never indexes price[].
 //   eCE      choice_cost is the value at the LAST slot of row i whose column is p2o[i]; every entry is tested against it.
 //   get_obj  every entry whose column is p2o[i] is added, in row order and slot order.
+//
+// The outside mode (misslap_solve_ell_batch_outside; the <.., true> instances below): row i of problem b also holds one
+// virtual entry (i, m_b + i), stored LAST in its row, whose value is the row's outside value -- a private object that
+// only row i can bid for, so a row may stay unmatched.  The problem solved is the n_b x (m_b + n_b) packed problem; the
+// round loop is batch_solve unchanged, on a carve of Mmax + N objects.  The row source presents the virtual entry (tie
+// key K, above every slot), the check pass folds the outside values into C = max |v| and the non-finite flag and never
+// reports an empty row, and the solve kernel rewrites the outputs behind batch_solve: an object >= m_b becomes -1 in
+// sol, price[0 .. m_b) are the real prices and price[m_b .. m_b + n_b) the outside prices.
 #pragma once
 
 namespace misslap {
@@ -44,10 +52,14 @@ struct EllBatchArgs {
 // Check pass, one workgroup per problem, a wavefront per row: the entries per row and in all, the first empty row, the
 // largest column (compared in the index's own width: an int64 column at or above 2^31 is too large, not wrapped), NaN /
 // infinity and C = max |v| among the entries only, and the starting prices of the problem's columns.
-template <class I, class V>
-__global__ __launch_bounds__(256) void k_ell_batch_check(const I *cols, const V *vals, long long N, long long K,
-                                                         const int *rows, const double *p0, long long p0_ld,
-                                                         EllBatchCheck *out) {
+// Out (the outside mode): the outside value of every row < n_b counts as an entry's value does (ov: outside[b] with
+// ov_ld == 0, else outside[b * ov_ld + i]), no row is empty, and with starting prices the problem's augmented starting
+// prices [p0[:m_b], zeros(n_b)] are staged at aug[b * aug_ld ..] (aug_ld = Ms + N) for batch_solve to load -- only where
+// the real columns fit both Ms and p0_ld, i.e. where the verdict can still be 0 (m_b + n_b <= aug_ld then).
+template <class I, class V, bool Out>
+__device__ __forceinline__ void ell_batch_check(const I *cols, const V *vals, long long N, long long K, const int *rows,
+                                                const double *p0, long long p0_ld, EllBatchCheck *out, const double *ov,
+                                                long long ov_ld, double *aug, long long aug_ld, int Ms) {
     const int b = blockIdx.x, lane = lane_id(), wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
     int n = rows ? rows[b] : (int)N;
     if (n < 1 || n > N) n = 0;
@@ -80,7 +92,17 @@ __global__ __launch_bounds__(256) void k_ell_batch_check(const I *cols, const V 
             mc = c > mc ? c : mc;
         }
         for (int off = 32; off >= 1; off >>= 1) rc += __shfl_xor(rc, off);
-        if (rc == 0 && lane == 0) atomicMin(&s_empty, r);
+        if constexpr (Out) {
+            if (lane == 0) {
+                const unsigned long long bits =
+                    (unsigned long long)__double_as_longlong(ov[ov_ld ? (size_t)b * (size_t)ov_ld + (size_t)r : (size_t)b]) &
+                    0x7fffffffffffffffull;
+                am = bits > am ? bits : am;
+                bad |= bits >= 0x7ff0000000000000ull;
+            }
+        } else {
+            if (rc == 0 && lane == 0) atomicMin(&s_empty, r);
+        }
         cnt += (unsigned long long)rc;  // (uniform; lane 0's copy is added below)
     }
     if (lane == 0) atomicAdd(&s_cnt, cnt);
@@ -91,6 +113,14 @@ __global__ __launch_bounds__(256) void k_ell_batch_check(const I *cols, const V 
     if (p0 && s_maxc >= 0) {
         const long long m = (long long)s_maxc + 1;
         batch_check_prices(p0 + (size_t)b * (size_t)p0_ld, (int)(m < p0_ld ? m : p0_ld), &s_badp);
+    }
+    if constexpr (Out) {
+        const long long m = (long long)s_maxc + 1;
+        if (p0 && m <= (long long)Ms && m <= p0_ld) {
+            const double *src = p0 + (size_t)b * (size_t)p0_ld;
+            double *dst = aug + (size_t)b * (size_t)aug_ld;
+            for (int j = threadIdx.x; j < (int)m + n; j += blockDim.x) dst[j] = j < (int)m ? src[j] : 0.0;
+        }
     }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -107,15 +137,57 @@ __global__ __launch_bounds__(256) void k_ell_batch_check(const I *cols, const V 
     }
 }
 
+template <class I, class V>
+__global__ __launch_bounds__(256) void k_ell_batch_check(const I *cols, const V *vals, long long N, long long K,
+                                                         const int *rows, const double *p0, long long p0_ld,
+                                                         EllBatchCheck *out) {
+    ell_batch_check<I, V, false>(cols, vals, N, K, rows, p0, p0_ld, out, nullptr, 0, nullptr, 0, 0);
+}
+
+struct EllOutsideCheckArgs {
+    const void *cols, *vals;
+    long long N, K;
+    const int *rows;
+    const double *p0;
+    long long p0_ld;
+    EllBatchCheck *out;
+    const double *outside;  // [B] (outside_ld == 0) or [B][outside_ld]
+    long long outside_ld;
+    double *aug;            // [B][aug_ld] or null (no starting prices)
+    long long aug_ld;       // Mmax + N
+    int Ms;                 // Mmax: the bound on the real columns
+};
+
+template <class I, class V>
+__global__ __launch_bounds__(256) void k_ell_outside_check(EllOutsideCheckArgs a) {
+    ell_batch_check<I, V, true>(static_cast<const I *>(a.cols), static_cast<const V *>(a.vals), a.N, a.K, a.rows, a.p0,
+                                a.p0_ld, a.out, a.outside, a.outside_ld, a.aug, a.aug_ld, a.Ms);
+}
+
+// The outside option of the rows of one problem (EllBatchRows<I, V, true>): row i's value is O[i * stride] (stride 0: one
+// value for the problem), its object is m + i.  Empty in the plain mode.
+template <bool Out>
+struct EllOutside {};
+template <>
+struct EllOutside<true> {
+    const double *O;
+    int stride, m;
+    __device__ __forceinline__ double value(int i) const { return O[i * stride]; }
+};
+
 // The ELL row source of batch_solve: problem b's slices C / A (at (size_t)b * N * K, formed in 64 bits), row i at slot
 // i * K of them (an int: the host caps N * K at INT_MAX - 128).  Every valid column is below the carve's Ms once the
 // verdict is 0, so an int64 column narrows safely.
-template <class I, class V>
+// Out: the row's virtual last entry (i, m + i) with the row's outside value.  Its tie key is K, above every slot, and
+// lane K & 63 takes it AFTER its own slots (slot K would be that lane's next one), so every lane still scans in
+// ascending stored order and the winner's lane is r.g & 63 as before.  A chosen object j >= m is that entry.
+template <class I, class V, bool Out = false>
 struct EllBatchRows {
     const I *C;
     const V *A;
     int K, maximize;
     unsigned long long nvalid;
+    EllOutside<Out> out;
 
     // the row in slot order, lane l at slots l, l + 64, ...; the tie key is the slot index
     __device__ __forceinline__ Top2 bid(int i, const double *price, double &costbest, int &obj) const {
@@ -144,6 +216,22 @@ struct EllBatchRows {
                 x.w = vi;
             }
         }
+        if constexpr (Out) {
+            if (lane == (K & (kWave - 1))) {
+                const double v = out.value(i);
+                const double cost = maximize ? v : v * -1.0;
+                const double vi = cost - price[out.m + i];
+                if (vi >= x.v) {
+                    x.w = x.v;
+                    x.v = vi;
+                    x.g = K;
+                    cb = cost;
+                    cj = out.m + i;
+                } else if (vi > x.w) {
+                    x.w = vi;
+                }
+            }
+        }
         const Top2 r = top2_wave_reduce(x);
         const int gl = r.g & (kWave - 1);  // the lane that holds slot r.g
         costbest = readlane_f64(cb, gl);
@@ -159,10 +247,19 @@ struct EllBatchRows {
         for (int q = lane; q < K; q += kWave)
             if (C[g0 + q] == (I)j) last = q;
         last = wave_max_i32(last);
-        const double vj = dense_widen(A[g0 + last]);
+        double vj;
+        if constexpr (Out) vj = j >= out.m ? out.value(i) : dense_widen(A[g0 + (last < 0 ? 0 : last)]);
+        else vj = dense_widen(A[g0 + last]);
         const double choice_cost = maximize ? vj : vj * -1.0;
         const double LHS = choice_cost - price[j] + tol;  // :475
         bool bad = false;
+        if constexpr (Out) {
+            if (lane == 0) {
+                const double v = out.value(i);
+                const double cost = maximize ? v : v * -1.0;
+                if (LHS < (cost - price[out.m + i]) - eps) bad = true;
+            }
+        }
         for (int q = lane; q < K; q += kWave) {
             const I c = C[g0 + q];
             if (c < 0) continue;
@@ -180,6 +277,15 @@ struct EllBatchRows {
         for (int i = wave; i < n; i += nw) {
             const int j = p2o[i];
             if (j < 0) continue;
+            if constexpr (Out) {
+                if (j >= out.m) {  // the row's outside entry: exactly one match
+                    if (lane == 0) {
+                        nsel[i] = 1;
+                        selv[i] = out.value(i);
+                    }
+                    continue;
+                }
+            }
             const int g0 = i * K;
             int cnt = 0, at = -1;
             for (int q = lane; q < K; q += kWave)
@@ -264,8 +370,70 @@ __global__ __launch_bounds__(1024) void k_ell_batch_solve(EllBatchArgs a) {
     // (the two slice pointers as opaque scalars: left to itself the compiler also keeps base * sizeof(I) and
     // base * sizeof(V) alive for the objective's scalar re-walk, and those four registers are the ones that spill)
     asm volatile("" : "+s"(C), "+s"(A));
-    const EllBatchRows<I, V> rows{C, A, (int)a.K, bs.maximize, ck.nvalid};
+    const EllBatchRows<I, V> rows{C, A, (int)a.K, bs.maximize, ck.nvalid, {}};
     batch_solve(bs, rows, ck.n, ck.max_col + 1, ck.absmax_bits);
+}
+
+
+struct EllOutsideArgs {
+    EllBatchArgs e;          // s.Ms = Mmax + N (the carve), s.p0 / p0_ld the staged augmented prices, s.prices null
+    const double *outside;   // [B] (outside_ld == 0) or [B][outside_ld]
+    long long outside_ld;
+    double *prices;          // [B][Mmax] or null: the real columns
+    double *outside_prices;  // [B][N] or null
+    int Mmax;                // the bound on the real columns
+    long long p0_ld;         // of the caller's starting prices (the PRICES_TOO_NARROW check)
+};
+
+// The solve of the outside mode: the verdict without EMPTY_ROW and INFEASIBLE (neither can occur), batch_solve on the
+// n x (m + n) problem, then the outputs in the caller's terms from the LDS state batch_solve leaves (nothing writes
+// price[] or p2o[] behind its last barrier, and every thread rewrites only the sol cells it wrote itself).
+template <class I, class V>
+__global__ __launch_bounds__(1024) void k_ell_outside_solve(EllOutsideArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
+    const int b = blockIdx.x, tid = threadIdx.x, T = blockDim.x;
+    const EllBatchCheck ck = a.e.chk[b];
+    const int own = ell_batch_verdict(ck, a.Mmax, a.p0_ld, a.e.s.p0 != nullptr);
+    const int code = batch_verdict(own, false, -1, ck.n, ck.bad_price);
+    if (tid == 0) {
+        a.e.status[b] = code;
+        if (a.e.matching_size) a.e.matching_size[b] = -1;
+    }
+    const int N = (int)a.e.N;
+    double *po = a.prices ? a.prices + (size_t)b * (size_t)a.Mmax : nullptr;
+    double *oo = a.outside_prices ? a.outside_prices + (size_t)b * (size_t)N : nullptr;
+    if (code != MISSLAP_BATCH_STATUS_OK) {
+        const long long mc = (long long)sparse_batch_count(ck.max_col) + ck.n;
+        batch_condemn(a.e.s, ck.n, (int)(mc < INT_MAX ? mc : INT_MAX), (long long)ck.nvalid + ck.n);
+        if (po)
+            for (int j = tid; j < a.Mmax; j += T) po[j] = 0.0;
+        if (oo)
+            for (int i = tid; i < N; i += T) oo[i] = 0.0;
+        return;
+    }
+    BatchSolveArgs bs = a.e.s;
+    if (a.e.fast) {
+        bs.eps_b = nullptr;
+        bs.eps_opt = (float)(1.0 / (double)ck.n);
+    }
+    const size_t base = (size_t)b * (size_t)a.e.N * (size_t)a.e.K;
+    const I *C = static_cast<const I *>(a.e.cols) + base;
+    const V *A = static_cast<const V *>(a.e.vals) + base;
+    asm volatile("" : "+s"(C), "+s"(A));
+    const int n = ck.n, m = ck.max_col + 1;
+    const double *O = a.outside + (a.outside_ld ? (size_t)b * (size_t)a.outside_ld : (size_t)b);
+    const EllBatchRows<I, V, true> rows{C, A, (int)a.e.K, bs.maximize, ck.nvalid + (unsigned long long)n,
+                                        {O, a.outside_ld ? 1 : 0, m}};
+    batch_solve(bs, rows, n, m + n, ck.absmax_bits);
+    const double *price = batch_solve_price(s_raw);
+    const int *p2o = batch_solve_p2o(s_raw, bs.Ns, bs.Ms);
+    int *sol = a.e.s.sol + (size_t)b * (size_t)a.e.s.sol_ld;
+    for (int i = tid; i < n; i += T)
+        if (p2o[i] >= m) sol[i] = -1;
+    if (po)
+        for (int j = tid; j < a.Mmax; j += T) po[j] = j < m ? price[j] : 0.0;
+    if (oo)
+        for (int i = tid; i < N; i += T) oo[i] = i < n ? price[m + i] : 0.0;
 }
 
 }  // namespace misslap

@@ -5,6 +5,10 @@ The layout a top-k, a gating step or a nearest-neighbour search leaves on the de
 negative column is a hole in any position and the value stored in a hole is never interpreted.  `ell_to_packed` is the
 definition: the result of problem b is bit for bit `auction_solve(loc=loc_b, val=val_b, size=(m_b, n_b), ...)` on its
 output (csrc/kernels_batch_solve.hpp, csrc/kernels_ell_batch.hpp).  The reference has no counterpart.
+
+With `outside` every row also holds an outside option, so a row may stay unmatched (a partial assignment): problem b is
+the packed problem plus one entry (i, m_b + i) per row, stored last in its row, and its result is the reference's on
+that n_b x (m_b + n_b) problem (misslap_solve_ell_batch_outside).
 """
 import ctypes as C
 
@@ -22,7 +26,7 @@ _MAX_SLOTS = _INT_MAX - 128  # N * K: the guard indexes the slots of a problem w
 _STATUS_TEXT = {
     _lib.BATCH_STATUS_BAD_SHAPE: "rows = {r} outside 1 .. {N}",
     _lib.BATCH_STATUS_EMPTY_ROW: "every row 0..N-1 must have at least one entry (auction_.pyx:33-48 contract)",
-    _lib.BATCH_STATUS_INFINITE_VALUE: "val holds a NaN or an infinity",
+    _lib.BATCH_STATUS_INFINITE_VALUE: "val holds a NaN or an infinity{also}",
     _lib.BATCH_STATUS_PRICES_TOO_NARROW: "prices hold {P} columns, the problem has {m}",
     _lib.BATCH_STATUS_INFEASIBLE: "Matrix is infeasible (Maximum matching possible only involves {card} out of {n} rows.)",
     _lib.BATCH_STATUS_PRICE_NOT_FINITE: "prices hold a NaN or an infinity",
@@ -30,22 +34,35 @@ _STATUS_TEXT = {
 }
 
 
-def ell_to_packed(cols, vals, rows=None):
+def ell_to_packed(cols, vals, rows=None, outside=None):
     """numpy (B, N, K) cols / vals -> [(loc_b int32 (nnz_b, 2), val_b float64 (nnz_b,))]: the entries of rows
     0 .. rows[b] - 1 of problem b in row order, within a row in slot order, the holes (cols < 0) dropped.  The
     definition of auction_solve_ell_batch: problem b is auction_solve(loc=loc_b, val=val_b, size=(m_b, n_b)) with
-    n_b = rows[b] and m_b = loc_b[:, 1].max() + 1."""
+    n_b = rows[b] and m_b = loc_b[:, 1].max() + 1.
+    outside (a float, float64 (B,) or float64 (B, N)): every row i < n_b gets one more entry (i, m_b + i), stored last in
+    its row behind every slot, whose value is the row's outside value; m_b = max real column + 1, 0 for a problem without
+    any entry.  Problem b is then auction_solve(loc=loc_b, val=val_b, size=(m_b + n_b, n_b))."""
     cols, vals = np.asarray(cols), np.asarray(vals)
     if cols.ndim != 3 or vals.shape != cols.shape:
         raise ValueError(f"cols and vals must have one shape (B, N, K), got {cols.shape} and {vals.shape}")
     B, N, _ = cols.shape
     ns = np.full(B, N) if rows is None else np.asarray(rows)
+    if outside is not None:
+        o = np.asarray(outside, dtype=np.float64)
+        if o.shape not in ((), (B,), (B, N)):
+            raise ValueError(f"outside must be a float or have shape ({B},) or ({B}, {N}), got {o.shape}")
+        o = np.broadcast_to(o if o.ndim != 1 else o[:, None], (B, N))
     out = []
     for b in range(B):
-        c = cols[b, :max(int(ns[b]), 0)]
+        n = max(int(ns[b]), 0)
+        c, v = cols[b, :n], vals[b, :n]
+        if outside is not None:  # one more slot behind the K of every row
+            m = int(c.max()) + 1 if n and (c >= 0).any() else 0
+            c = np.concatenate([c.astype(np.int64), (m + np.arange(n, dtype=np.int64))[:, None]], axis=1)
+            v = np.concatenate([v.astype(np.float64), o[b, :n, None]], axis=1)
         i, k = np.nonzero(c >= 0)  # (row-major: row order, then slot order)
         loc = np.ascontiguousarray(np.stack([i, c[i, k]], axis=1), dtype=np.int32)
-        out.append((loc, np.ascontiguousarray(vals[b, i, k], dtype=np.float64)))
+        out.append((loc, np.ascontiguousarray(v[i, k], dtype=np.float64)))
     return out
 
 
@@ -104,6 +121,40 @@ def _check_rows(rows, B, on_device, dev):
     return np.ascontiguousarray(np.clip(r, -1, _INT_MAX), dtype=np.int32)  # (whatever is out of range stays so)
 
 
+def _check_outside(outside, B, N, on_device, dev):
+    """The outside values of a call: a finite float (broadcast to (B,) where the input lives, nothing read back), or
+    float64 (B,) / (B, N) on the host or (with device input) contiguous on the input's device.  Returns (array or tensor,
+    outside_ld); the values are the library's to judge."""
+    if _is_device_tensor(outside):
+        import torch
+        if not on_device:
+            raise TypeError("outside on the device needs cols / vals on the device")
+        if outside.dtype != torch.float64:
+            raise ValueError(f"outside must be float64, got {outside.dtype}")
+        if tuple(outside.shape) not in ((B,), (B, N)):
+            raise ValueError(f"outside must have shape ({B},) or ({B}, {N}), got {tuple(outside.shape)}")
+        if outside.device != dev:
+            raise ValueError(f"outside is on {outside.device}, cols on {dev}")
+        if not outside.is_contiguous():
+            raise ValueError("a device outside tensor must be contiguous (it is read in place)")
+        return outside, (N if outside.dim() == 2 else 0)
+    if isinstance(outside, np.ndarray):
+        if outside.dtype != np.float64:
+            raise ValueError(f"outside must be float64, got {outside.dtype.name}")
+        if outside.shape not in ((B,), (B, N)):
+            raise ValueError(f"outside must have shape ({B},) or ({B}, {N}), got {outside.shape}")
+        return np.ascontiguousarray(outside), (N if outside.ndim == 2 else 0)
+    if isinstance(outside, (bool, str, bytes)) or not isinstance(outside, (int, float, np.integer, np.floating)):
+        raise TypeError("outside must be a float, a float64 numpy array or a float64 tensor on the device")
+    x = float(outside)
+    if not np.isfinite(x):
+        raise ValueError(f"outside must be finite, got {x!r}")
+    if on_device:
+        import torch
+        return torch.full((B,), x, dtype=torch.float64, device=dev), 0
+    return np.full(B, x, dtype=np.float64), 0
+
+
 def _check_n_cols(n_cols):
     try:
         ok = int(n_cols) == n_cols and 1 <= int(n_cols) <= MAX_DIM
@@ -114,8 +165,8 @@ def _check_n_cols(n_cols):
     return int(n_cols)
 
 
-def auction_solve_ell_batch(cols, vals, rows=None, n_cols=None, problem="min", eps_start=0., max_iter=1000000, fast=False,
-                            cardinality_check=True, prices=None, errors="raise"):
+def auction_solve_ell_batch(cols, vals, rows=None, n_cols=None, problem="min", eps_start=0., max_iter=1000000, fast=None,
+                            cardinality_check=True, prices=None, errors="raise", outside=None):
     """Solve B independent sparse problems given as padded candidate lists, one workgroup per problem.
 
     cols: int32 or int64 (B, N, K) and vals: float64 or float32 of the same shape, both numpy arrays or both contiguous
@@ -139,6 +190,29 @@ def auction_solve_ell_batch(cols, vals, rows=None, n_cols=None, problem="min", e
     raise_for_status take the result.
     errors="raise" (default) runs the same call and raises ValueError("problem <b>: ...") for the first problem whose
     status is not 0; else it returns the same dict.
+
+    outside: partial assignments (misslap_solve_ell_batch_outside).  A finite float, float64 (B,) or float64 (B, N) -- a
+    numpy array or, with device input, a contiguous tensor on the same device: the outside value of every row, in the
+    units of vals (problem="min": the cost of leaving row i unmatched; "max": the value of doing so).  Problem b is then
+    the packed problem plus one entry (i, m_b + i) per row, stored last in its row, and its result is bit for bit
+    auction_solve(loc=loc_b, val=val_b, size=(m_b + n_b, n_b)) on ell_to_packed(cols, vals, rows, outside=outside); with
+    prices the solve starts from [p0[:m_b], zeros(n_b)].  sol[b, i] is the real column, or -1 where row i took its outside
+    option (and beyond n_b, on a condemned problem, or where max_iter cut the solve).  prices stays (B, n_cols), the real
+    columns; the new key outside_prices is float64 (B, N), the price of row i's outside object and 0 beyond n_b (a row
+    without any real entry bids +inf as a one-entry row of the reference does, so its outside price is +inf).  meta is the
+    augmented problem's record (n_cols = m_b + n_b, nnz = entries + n_b; n_assigned counts rows on their outside option).
+    The checks, in their order: BAD_SHAPE, INFINITE_VALUE (an entry or the outside value of a row < n_b is a NaN or an
+    infinity), TOO_LARGE (a real column >= n_cols), PRICES_TOO_NARROW, PRICE_NOT_FINITE, PRICE_NEGATIVE.  EMPTY_ROW and
+    INFEASIBLE cannot occur: rows without entries, graphs without a complete matching, n_b > m_b and problems of holes
+    only are solved; the guard is not launched whatever cardinality_check says and matching_size is -1.  The values of
+    rows >= n_b are never read.
+
+    fast=None (default) is False without outside (the call is what it always was) and with outside True, unless
+    eps_start > 0 was given (then False); an explicit fast= or eps_start= is passed through as it is.  Why: the augmented
+    problem is rectangular (n rows, m + n columns).  A single phase (fast=True, or 0 < eps_start <= 1 / n) from zero prices
+    is optimal within n * eps.  The reference's eps-scaling (fast=False, eps_start=0) keeps prices between phases and has no
+    reverse phase: it gives the reference's answer on the augmented problem, which is NOT the optimum in general.  The
+    same holds for every rectangular problem (n < m) of the batch solves.
     """
     if errors not in ("raise", "status"):
         raise ValueError(f"errors must be 'raise' or 'status', got {errors!r}")
@@ -157,9 +231,15 @@ def auction_solve_ell_batch(cols, vals, rows=None, n_cols=None, problem="min", e
     else:  # (with device input the call's one read-back, ordered behind the current stream like every read of cols)
         Mmax = min(max(int(cols.max()) + 1, 1), MAX_DIM)
     check = 1 if cardinality_check else 0
+    out_v, out_ld = (None, 0) if outside is None else _check_outside(outside, B, N, on_device, dev)
+    if fast is None:  # (resolved here: the library gets a plain flag)
+        fast = outside is not None and not e > 0
     opts = _solve_options(on_device, cols, problem, e, max_iter, dtype)
     lib = _lib.load()
     common = dict(layout="ell", stack=(N, K), n_cols=Mmax, prices_ld=0 if prices is None else int(prices.shape[1]))
+    if outside is not None:
+        return _finish(_solve_outside(lib, opts, cols, vals, rws, prices, out_v, out_ld, 1 if fast else 0, B, N, K, Mmax,
+                                      on_device, wide, dev, common), errors)
     if not on_device:  # synchronous: the library uploads, uses its own scratch and waits once
         cc, vc = np.ascontiguousarray(cols), np.ascontiguousarray(vals)
         p = None if prices is None else np.ascontiguousarray(prices)
@@ -177,15 +257,11 @@ def auction_solve_ell_batch(cols, vals, rows=None, n_cols=None, problem="min", e
         import torch
         from .dense_batch import _meta_views
 
-        def send(a):  # a host array from pinned memory, without a wait (torch takes no read-only array: a copy then)
-            if not isinstance(a, np.ndarray):
-                return a
-            return torch.from_numpy(a if a.flags.writeable else a.copy()).pin_memory().to(dev, non_blocking=True)
         with torch.cuda.device(dev):  # (the allocations and copies below are made on the current stream of cols' device)
             stream = torch.cuda.current_stream(dev)
-            d_rows = send(rws)
-            d_p = None if prices is None else send(np.ascontiguousarray(prices) if isinstance(prices, np.ndarray)
-                                                   else prices.contiguous())
+            d_rows = _send(rws, dev)
+            d_p = None if prices is None else _send(np.ascontiguousarray(prices) if isinstance(prices, np.ndarray)
+                                                    else prices.contiguous(), dev)
             nbytes = int(lib.misslap_ell_batch_workspace_bytes(B, N, K, 0 if d_p is None else 1, check))
             work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
             sol = torch.empty((B, N), dtype=torch.int32, device=dev)
@@ -202,15 +278,73 @@ def auction_solve_ell_batch(cols, vals, rows=None, n_cols=None, problem="min", e
         # the workspace and the inputs stay referenced by the result: nothing of this call is recycled before it
         res = dict(sol=sol, prices=pout, status=status, matching_size=msize, meta=_meta_views(rec), rows=d_rows, records=rec,
                    info=info, stream=stream, keep=(work, cols, vals, d_rows, d_p), **common)
+    return _finish(res, errors)
+
+
+def _finish(res, errors):
     if errors == "raise":
         from .dense_batch import raise_for_status
         raise_for_status(res)
     return res
 
 
+def _send(a, dev):
+    """A host array to dev from pinned memory, without a wait (torch takes no read-only array: a copy then)."""
+    import torch
+    if not isinstance(a, np.ndarray):
+        return a
+    return torch.from_numpy(a if a.flags.writeable else a.copy()).pin_memory().to(dev, non_blocking=True)
+
+
+def _solve_outside(lib, opts, cols, vals, rws, prices, out_v, out_ld, fast, B, N, K, Mmax, on_device, wide, dev, common):
+    """The call of misslap_solve_ell_batch_outside, in either mode; the result dict of auction_solve_ell_batch plus
+    outside_prices."""
+    p_ld = common["prices_ld"]
+    if not on_device:  # synchronous: the library uploads, uses its own scratch and waits once
+        cc, vc = np.ascontiguousarray(cols), np.ascontiguousarray(vals)
+        p = None if prices is None else np.ascontiguousarray(prices)
+        sol, pout = np.empty((B, N), dtype=np.int32), np.empty((B, Mmax), dtype=np.float64)
+        oout = np.empty((B, N), dtype=np.float64)
+        status, msize = np.empty(B, dtype=np.int32), np.empty(B, dtype=np.int32)
+        metas, info = _new_meta(B)
+        _lib.check(lib.misslap_solve_ell_batch_outside(
+            B, N, K, cc.ctypes.data, 1 if wide else 0, vc.ctypes.data, None if rws is None else rws.ctypes.data, fast,
+            None if p is None else p.ctypes.data, p_ld, C.byref(opts), None, None, 0, Mmax, out_v.ctypes.data, out_ld,
+            sol.ctypes.data, pout.ctypes.data, oout.ctypes.data, 0, status.ctypes.data, msize.ctypes.data,
+            C.cast(metas, C.c_void_p), C.byref(info)))
+        return dict(sol=sol, prices=pout, outside_prices=oout, status=status, matching_size=msize,
+                    meta=_decode_meta(metas, info), rows=rws, **common)
+    import torch
+    from .dense_batch import _meta_views
+    with torch.cuda.device(dev):  # (the allocations and copies below are made on the current stream of cols' device)
+        stream = torch.cuda.current_stream(dev)
+        d_rows = _send(rws, dev)
+        d_out = _send(out_v, dev)
+        d_p = None if prices is None else _send(np.ascontiguousarray(prices) if isinstance(prices, np.ndarray)
+                                                else prices.contiguous(), dev)
+        nbytes = int(lib.misslap_ell_batch_outside_workspace_bytes(B, N, K, Mmax, 0 if d_p is None else 1))
+        work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        sol = torch.empty((B, N), dtype=torch.int32, device=dev)
+        pout = torch.empty((B, Mmax), dtype=torch.float64, device=dev)
+        oout = torch.empty((B, N), dtype=torch.float64, device=dev)
+        status = torch.empty(B, dtype=torch.int32, device=dev)
+        msize = torch.empty(B, dtype=torch.int32, device=dev)
+        rec = torch.empty((B, C.sizeof(_lib.DenseBatchMeta)), dtype=torch.uint8, device=dev)
+    info = _lib.DenseBatchInfo()
+    _lib.check(lib.misslap_solve_ell_batch_outside(
+        B, N, K, cols.data_ptr(), 1 if wide else 0, vals.data_ptr(), None if d_rows is None else d_rows.data_ptr(), fast,
+        None if d_p is None else d_p.data_ptr(), p_ld, C.byref(opts), C.c_void_p(int(stream.cuda_stream)),
+        work.data_ptr(), nbytes, Mmax, d_out.data_ptr(), out_ld, sol.data_ptr(), pout.data_ptr(), oout.data_ptr(), 1,
+        status.data_ptr(), msize.data_ptr(), rec.data_ptr(), C.byref(info)))
+    return dict(sol=sol, prices=pout, outside_prices=oout, status=status, matching_size=msize, meta=_meta_views(rec),
+                rows=d_rows, records=rec, info=info, stream=stream, keep=(work, cols, vals, d_rows, d_p, d_out), **common)
+
+
 def _status_error(res, b, code, n, m, card):
     """The exception of problem b of an ELL result (n, m: the record's n_rows and n_cols; card: its matching_size)."""
     N, Mmax = res["stack"][0], res["n_cols"]
+    if "outside_prices" in res and m < _INT_MAX:  # (the record counts the n outside objects too)
+        m -= n
     if code == _lib.BATCH_STATUS_TOO_LARGE:
         if m >= _INT_MAX:
             text = "column index too large (max + 1 must fit an int32)"
@@ -221,5 +355,6 @@ def _status_error(res, b, code, n, m, card):
         if code == _lib.BATCH_STATUS_BAD_SHAPE:
             rows = res["rows"]
             r = int(rows[b] if isinstance(rows, np.ndarray) else rows[b].item())
-        text = _STATUS_TEXT[code].format(r=r, N=N, n=n, m=m, card=card, P=res["prices_ld"])
+        also = " (in an entry or in the outside value of a row)" if "outside_prices" in res else ""
+        text = _STATUS_TEXT[code].format(r=r, N=N, n=n, m=m, card=card, P=res["prices_ld"], also=also)
     return ValueError(f"problem {b}: {text}")
