@@ -37,7 +37,8 @@ extern "C" {
  *      misslap_options.mat_dtype with MISSLAP_DTYPE_F64 .. MISSLAP_DTYPE_BF16 (the first word of reserved[], which
  *      had to be 0 = MISSLAP_DTYPE_F64 until then; size and offsets of the struct did not change),
  *      misslap_solve_ell_batch, misslap_ell_batch_workspace_bytes, misslap_solve_ell_batch_outside,
- *      misslap_ell_batch_outside_workspace_bytes. */
+ *      misslap_ell_batch_outside_workspace_bytes, misslap_solve_dense_batch_outside,
+ *      misslap_dense_batch_outside_workspace_bytes (with MISSLAP_BATCH_STATUS_BAD_OUTSIDE, code 15). */
 
 /* misslap_options.mat_dtype: the element type of a dense stack */
 #define MISSLAP_DTYPE_F64 0   /* double */
@@ -568,6 +569,53 @@ int misslap_solve_dense_batch_status(int64_t B, int64_t N, int64_t M, const doub
  * does not. */
 int64_t misslap_dense_batch_workspace_bytes(int64_t B, int64_t N, int64_t M, int32_t has_prices,
                                             int32_t cardinality_check);
+
+/* ---- the dense batch with an outside option per row: partial assignments (the dense form of
+ * misslap_solve_ell_batch_outside, below).  Problem b has shape (n_b, m_b) and an outside value o_i per row -- with
+ * opt->maximize = 0 the cost of leaving row i unmatched, else the value of doing so.  It is the dense n_b x (m_b + n_b)
+ * matrix aug_b = hstack([mat[b][:n_b][:m_b] widened to double, D_b]), D_b holding o_i at (i, i) and -1 elsewhere: the
+ * object m_b + i is private to row i, so every row can always be assigned and a row may stay without a real column.  The
+ * result of problem b is bit for bit the reference's from_matrix(aug_b).solve() (with prices_in: started from
+ * [prices_in[b][:m_b], zeros(n_b)]; the outside objects always start at 0), given in the caller's terms:
+ *   sol[b][i]              the real column of row i, or -1 where the row took its outside option (and beyond n_b, on a
+ *                          condemned problem, and where max_iter cut the solve before the row was assigned)
+ *   prices_out[b][:M]      the prices of the real columns, 0 beyond m_b
+ *   outside_prices_out     double[B][N] or NULL: the price of row i's outside object, 0 beyond n_b.  A row without any
+ *                          valid entry is a one-entry row of the reference: it bids +inf, and that is its outside price.
+ *   meta[b]                the augmented problem's record: n_cols = m_b + n_b, nnz = valid entries + n_b; n_assigned
+ *                          counts the rows on their outside option too.
+ *   outside, outside_ld    always double, whatever opt->mat_dtype is.  outside_ld == 0: double[B], one value per problem;
+ *                          outside_ld >= N: double[B][outside_ld], the value of row i at outside[b * outside_ld + i];
+ *                          anything else is MISSLAP_ERR_INVALID.  The values of rows >= n_b are never read.  An outside
+ *                          value is an entry of a dense matrix and obeys the dense rule: -0.0 is valid, +inf condemns the
+ *                          problem as a +inf entry does, and a negative value or a NaN -- which would be an ABSENT entry,
+ *                          a row that must be matched: not offered -- is MISSLAP_BATCH_STATUS_BAD_OUTSIDE.
+ * The checks, in their order: 7 BAD_SHAPE; 15 BAD_OUTSIDE; 3 INFINITE_VALUE (a valid entry, or the outside value of a row
+ * < n_b, is +inf); 5 PRICE_NOT_FINITE; 6 PRICE_NEGATIVE.  TOO_FEW_VALUES, EMPTY_ROW and INFEASIBLE cannot occur: a row
+ * without a valid entry, a graph without a complete matching and n_b > m_b are all solved.  No guard is launched and
+ * matching_size[b] (may be NULL) is -1.  A problem with a status other than 0 has sol -1, prices_out 0,
+ * outside_prices_out 0 and meta[b] = {n_rows = n_b, n_cols = m_b + n_b, nnz = valid entries + n_b, every other result
+ * field 0} (all three 0 for MISSLAP_BATCH_STATUS_BAD_SHAPE).
+ * mat holds elements of opt->mat_dtype (all four types).  The LDS carve is sized for N rows and M + N objects (77 824
+ * bytes at 1024 / 1024).  Every other argument is misslap_solve_dense_batch_status's, in both of its modes: with a
+ * workspace (misslap_dense_batch_outside_workspace_bytes) every pointer except opt and info is a device pointer and the
+ * call enqueues two launches (check, solve with verdict) on `stream`, allocates nothing, copies nothing and waits for
+ * nothing; without one the library uploads host arrays, checks host shapes as before, uses its own scratch and
+ * synchronises once.
+ * On eps: the augmented problem is rectangular (more objects than rows), where the reference's eps-scaling (eps_start = 0,
+ * fast = 0) keeps the prices of earlier phases and is NOT optimal in general.  A single phase -- fast != 0, or
+ * 0 < eps_start <= 1 / n_b -- from zero prices is optimal within n_b * eps. */
+#define MISSLAP_BATCH_STATUS_BAD_OUTSIDE 15  /* the outside value of a row is negative or a NaN (an absent entry) */
+int misslap_solve_dense_batch_outside(int64_t B, int64_t N, int64_t M, const void *mat, const int32_t *shapes,
+                                      int32_t fast, const double *prices_in, const misslap_options *opt, void *stream,
+                                      void *workspace, int64_t workspace_bytes, const double *outside, int64_t outside_ld,
+                                      int32_t *sol, double *prices_out, double *outside_prices_out,
+                                      int32_t out_on_device, int32_t *status, int32_t *matching_size,
+                                      misslap_dense_batch_meta *meta, misslap_dense_batch_info *info);
+/* Bytes of workspace a stream-ordered misslap_solve_dense_batch_outside needs: the check records, the sanitised shapes
+ * and, with has_prices, the staged starting prices of the augmented problems (B x (M + N) doubles), each 256-byte
+ * aligned; -1 for B < 1 or N, M outside 1 .. MISSLAP_DENSE_BATCH_MAX_DIM.  Needs no GPU. */
+int64_t misslap_dense_batch_outside_workspace_bytes(int64_t B, int64_t N, int64_t M, int32_t has_prices);
 
 /* ---- many small SPARSE problems in one call: the batch form of _from_sparse(loc, val, size=...) (auction_.pyx:575-617).
  * loc is int32[nnz][2] and val double[nnz]; problem b is the entries offsets[b] .. offsets[b + 1] (offsets: host

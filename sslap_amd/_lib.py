@@ -98,6 +98,7 @@ MATCHING_BATCH_MAX_DIM = 2048  # MISSLAP_MATCHING_BATCH_MAX_DIM
 # ... and those misslap_solve_sparse_batch_status adds
 (BATCH_STATUS_NO_ENTRIES, BATCH_STATUS_DIVISION_BY_ZERO, BATCH_STATUS_NEGATIVE_INDEX, BATCH_STATUS_ROWS_UNSORTED,
  BATCH_STATUS_ROW_GAP, BATCH_STATUS_TOO_LARGE, BATCH_STATUS_PRICES_TOO_NARROW) = range(8, 15)
+BATCH_STATUS_BAD_OUTSIDE = 15  # ... and the one misslap_solve_dense_batch_outside adds
 
 
 def new_meta():
@@ -189,6 +190,10 @@ SYMBOLS = {
                                                    C.POINTER(Options), _VP, _VP, C.c_int64, _VP, _VP, C.c_int32, _VP, _VP,
                                                    _VP, C.POINTER(DenseBatchInfo)]),
     "misslap_dense_batch_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
+    "misslap_solve_dense_batch_outside": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, _VP, _VP, C.c_int32, _VP,
+                                                    C.POINTER(Options), _VP, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP,
+                                                    _VP, C.c_int32, _VP, _VP, _VP, C.POINTER(DenseBatchInfo)]),
+    "misslap_dense_batch_outside_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64, C.c_int32]),
     "misslap_solve_sparse_batch": (C.c_int, [C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int64, C.c_int32,
                                              C.POINTER(Options), _VP, C.c_int64, _VP, C.c_int64, C.c_int32,
                                              C.POINTER(DenseBatchMeta), C.POINTER(DenseBatchInfo)]),

@@ -132,7 +132,7 @@ template <class Rows>
 __device__ __forceinline__ void batch_solve(const BatchSolveArgs &a, const Rows &rows, int n, int m,
                                             unsigned long long absmax_bits) {
     // (the order of the carve below is restated by batch_solve_price / batch_solve_p2o above, for the kernel that reads
-    // the final state behind this function: k_ell_outside_solve.  Change both together.)
+    // the final state behind this function: k_ell_outside_solve, k_dense_outside_solve.  Change both together.)
     extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
     __shared__ int s_holes, s_nmove, s_fail;
     const int b = blockIdx.x, tid = threadIdx.x, T = blockDim.x, lane = lane_id(), wave = tid >> 6, nw = T >> 6;

@@ -11,6 +11,15 @@
 //   eCE      every column is stored once, so choice_cost -- never reset per row in the reference -- is the cost of the
 //            row's own column.
 //   get_obj  the selected values are gathered into LDS, then one lane adds them in row order.
+//
+// The outside mode (misslap_solve_dense_batch_outside; the <T, true> instances below): row i of problem b also holds one
+// virtual entry (i, m_b + i) whose value is the row's outside value -- a private object that only row i can bid for, so
+// a row may stay unmatched.  The problem solved is the dense n_b x (m_b + n_b) matrix hstack([slice, D_b]) with D_b the
+// outside values on its diagonal and -1 elsewhere; the round loop is batch_solve unchanged, on a carve of M + N objects.
+// The row source presents the virtual entry (column m_b + i, above every real column), the check pass folds the outside
+// values into C = max |v| and the +inf flag, flags a negative or NaN one and never reports an empty row, and the solve
+// kernel rewrites the outputs behind batch_solve: an object >= m_b becomes -1 in sol, price[0 .. m_b) are the real
+// prices and price[m_b .. m_b + n_b) the outside prices.
 #pragma once
 
 namespace misslap {
@@ -23,7 +32,8 @@ struct DenseBatchCheck {
     unsigned long long nvalid;       // valid entries of the slice
     unsigned long long absmax_bits;  // max |v| over them, as bits (non-negative doubles order like their bit patterns)
     int empty_row;                   // first row without a valid entry (INT_MAX: none)
-    int has_inf;                     // a valid entry is +inf
+    int has_inf;                     // bit 0: a valid entry is +inf (outside mode: or the outside value of a row < n);
+                                     // bit 1 (outside mode only): the outside value of a row < n is negative or a NaN
     int mref;                        // max valid column + 1 (auction_.pyx:209-212)
     int bad_price;                   // starting prices: bit 0 NaN / infinity, bit 1 sign bit set
 };
@@ -45,9 +55,14 @@ __device__ __forceinline__ void dense_batch_shape(const int *shapes, long long N
 // With shapes_out (status mode: `shapes` may be a caller's device array that no host has seen) a shape outside
 // 1 .. N x 1 .. M becomes (0, 0), nothing of that problem is read, and the shape every later kernel uses is written
 // to shapes_out[b]: the guard and the solve read those, never the caller's.
-template <class T>
-__global__ __launch_bounds__(256) void k_dense_batch_check(const T *mat, long long N, long long M, const int *shapes,
-                                                           const double *p0, DenseBatchCheck *out, int *shapes_out) {
+// Out (the outside mode): the outside value of every row < n_b counts as an entry's value does (ov: outside[b] with
+// ov_ld == 0, else outside[b * ov_ld + i]; a negative one or a NaN raises bit 1 of has_inf instead), no row is empty,
+// and with starting prices the problem's augmented starting prices [p0[:m_b], zeros(n_b)] are staged at
+// aug[b * (M + N) ..] for batch_solve to load.
+template <class T, bool Out>
+__device__ __forceinline__ void dense_batch_check(const T *mat, long long N, long long M, const int *shapes,
+                                                  const double *p0, DenseBatchCheck *out, int *shapes_out,
+                                                  const double *ov, long long ov_ld, double *aug) {
     const int b = blockIdx.x, lane = lane_id(), wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
     int n, m;
     dense_batch_shape(shapes, N, M, b, n, m);
@@ -87,14 +102,34 @@ __global__ __launch_bounds__(256) void k_dense_batch_check(const T *mat, long lo
             }
         }
         for (int off = 32; off >= 1; off >>= 1) rc += __shfl_xor(rc, off);
-        if (rc == 0 && lane == 0) atomicMin(&s_empty, r);
+        if constexpr (Out) {
+            if (lane == 0) {
+                const double o = ov[ov_ld ? (size_t)b * (size_t)ov_ld + (size_t)r : (size_t)b];
+                if (dense_entry_valid(o)) {
+                    const unsigned long long bits = (unsigned long long)__double_as_longlong(o) & 0x7fffffffffffffffull;
+                    am = bits > am ? bits : am;
+                    inf |= bits == 0x7ff0000000000000ull;
+                } else {
+                    inf |= 2;
+                }
+            }
+        } else {
+            if (rc == 0 && lane == 0) atomicMin(&s_empty, r);
+        }
         cnt += (unsigned long long)rc;  // (uniform; lane 0's copy is added below)
     }
     if (lane == 0) atomicAdd(&s_cnt, cnt);
     if (am) atomicMax(&s_abs, am);
-    if (inf) atomicOr(&s_inf, 1);
+    if (inf) atomicOr(&s_inf, Out ? inf : 1);
     if (mx >= 0) atomicMax(&s_mref, mx + 1);
     if (p0) batch_check_prices(p0 + (size_t)b * (size_t)M, m, &s_badp);
+    if constexpr (Out) {
+        if (p0) {
+            const double *src = p0 + (size_t)b * (size_t)M;
+            double *dst = aug + (size_t)b * (size_t)(M + N);
+            for (int j = threadIdx.x; j < m + n; j += blockDim.x) dst[j] = j < m ? src[j] : 0.0;
+        }
+    }
     __syncthreads();
     if (threadIdx.x == 0) {
         DenseBatchCheck r;
@@ -108,19 +143,59 @@ __global__ __launch_bounds__(256) void k_dense_batch_check(const T *mat, long lo
     }
 }
 
+template <class T>
+__global__ __launch_bounds__(256) void k_dense_batch_check(const T *mat, long long N, long long M, const int *shapes,
+                                                           const double *p0, DenseBatchCheck *out, int *shapes_out) {
+    dense_batch_check<T, false>(mat, N, M, shapes, p0, out, shapes_out, nullptr, 0, nullptr);
+}
+
+struct DenseOutsideCheckArgs {
+    const void *mat;        // elements of the kernel's T
+    long long N, M;
+    const int *shapes;      // [B][2] or null
+    const double *p0;       // [B][M] or null
+    DenseBatchCheck *out;   // [B]
+    int *shapes_out;        // [B][2]: the sanitised shapes (never null)
+    const double *outside;  // [B] (outside_ld == 0) or [B][outside_ld]
+    long long outside_ld;
+    double *aug;            // [B][M + N] or null (no starting prices)
+};
+
+template <class T>
+__global__ __launch_bounds__(256) void k_dense_outside_check(DenseOutsideCheckArgs a) {
+    dense_batch_check<T, true>(static_cast<const T *>(a.mat), a.N, a.M, a.shapes, a.p0, a.out, a.shapes_out, a.outside,
+                               a.outside_ld, a.aug);
+}
+
+// The outside option of the rows of one problem (DenseBatchRows<T, true>): row i's value is O[i * stride] (stride 0: one
+// value for the problem).  Empty in the plain mode.
+template <bool Out>
+struct DenseOutside {};
+template <>
+struct DenseOutside<true> {
+    const double *O;
+    int stride;
+    __device__ __forceinline__ double value(int i) const { return O[i * stride]; }
+};
+
 // The dense row source of batch_solve: problem b's slice A (row stride M) of n x m, its reference M and valid count.
 // The bid's staging array `vals` belongs to k_dense_batch_solve: declared in bid() it is promoted to a vector while bid()
 // is optimised on its own, and every staging step then zeroes the rest of it (measured: 3.8 % more kernel time at
 // 64 x 1000).  Declared in the kernel, it becomes 16 register pairs as in a hand-inlined scan.  The row is staged in its
 // own type T -- 16 registers for float and for the 16-bit types, one element per lane per load with the same
 // column-to-lane map -- and widened where the scan uses it.
-template <class T>
+// Out: row i's virtual last entry (i, m + i) with the row's outside value; mref and nvalid then count the augmented
+// problem (m + n columns, n more entries).  Column m + i is above every real column, and lane (m + i) & 63 takes it AFTER
+// its own real columns, so every lane still scans in ascending column order and the winner's lane is r.g & 63 as before.
+// A chosen object j >= m is that entry: nothing of the slice is read for it.
+template <class T, bool Out = false>
 struct DenseBatchRows {
     const T *A;
     long long M;
     int m, maximize, mref;
     unsigned long long nvalid;
     T *vals;  // [kDenseBatchCols]
+    DenseOutside<Out> out{};
 
     __device__ __forceinline__ Top2 bid(int i, const double *price, double &costbest, int &obj) const {
         const int lane = lane_id();
@@ -154,6 +229,21 @@ struct DenseBatchRows {
                 }
             }
         }
+        if constexpr (Out) {
+            if (lane == ((m + i) & (kWave - 1))) {
+                const double v = out.value(i);
+                const double cost = maximize ? v : v * -1.0;
+                const double vi = cost - price[m + i];
+                if (vi >= x.v) {
+                    x.w = x.v;
+                    x.v = vi;
+                    x.g = m + i;
+                    cb = cost;
+                } else if (vi > x.w) {
+                    x.w = vi;
+                }
+            }
+        }
         const Top2 r = top2_wave_reduce(x);
         costbest = readlane_f64(cb, r.g & (kWave - 1));  // the lane that holds column r.g
         obj = r.g;
@@ -163,10 +253,19 @@ struct DenseBatchRows {
     // eCE_satisfied (auction_.pyx:443-485) for row i: choice_cost is the cost of column j, every valid column is tested
     __device__ __forceinline__ bool ece_bad(int i, int j, const double *price, double tol, double eps) const {
         const T *row = A + (size_t)i * (size_t)M;
-        const double vj = dense_widen(row[j]);
+        double vj;
+        if constexpr (Out) vj = j >= m ? out.value(i) : dense_widen(row[j]);
+        else vj = dense_widen(row[j]);
         const double choice_cost = maximize ? vj : vj * -1.0;
         const double LHS = choice_cost - price[j] + tol;  // :475
         bool bad = false;
+        if constexpr (Out) {
+            if (lane_id() == 0) {
+                const double v = out.value(i);
+                const double cost = maximize ? v : v * -1.0;
+                if (LHS < (cost - price[m + i]) - eps) bad = true;
+            }
+        }
         for (int c = lane_id(); c < m; c += kWave) {
             const T e = row[c];
             if (!dense_entry_valid(e)) continue;
@@ -181,6 +280,12 @@ struct DenseBatchRows {
     __device__ __forceinline__ void gather(const int *p2o, int n, double *selv, int *) const {
         for (int i = threadIdx.x; i < n; i += blockDim.x) {
             const int j = p2o[i];
+            if constexpr (Out) {
+                if (j >= m) {  // the row's outside entry
+                    selv[i] = out.value(i);
+                    continue;
+                }
+            }
             selv[i] = j >= 0 ? dense_widen(A[(size_t)i * (size_t)M + j]) : 0.0;
         }
     }
@@ -259,6 +364,79 @@ __global__ __launch_bounds__(1024) void k_dense_batch_solve_status(DenseBatchSta
     const DenseBatchRows<T> rows{static_cast<const T *>(a.d.mat) + (size_t)b * (size_t)a.d.N * (size_t)a.d.M, a.d.M, m,
                                  s.maximize, ck.mref, ck.nvalid, vals};
     batch_solve(s, rows, n, m, ck.absmax_bits);
+}
+
+
+// ---- outside mode (misslap_solve_dense_batch_outside): an outside option per row, for partial assignments
+
+struct DenseOutsideArgs {
+    DenseBatchStatusArgs t;  // t.d.s: Ms = M + N (the carve), p0 / p0_ld the staged augmented prices, prices null;
+                             // t.card null: no guard in this call
+    const double *outside;   // [B] (outside_ld == 0) or [B][outside_ld]
+    long long outside_ld;
+    double *prices;          // [B][M] or null: the real columns
+    double *outside_prices;  // [B][N] or null
+};
+
+// The checks of an outside verdict in their order; EMPTY_ROW, TOO_FEW_VALUES and INFEASIBLE cannot occur.
+__device__ __forceinline__ int dense_outside_verdict(const DenseBatchCheck &c, int n) {
+    if (n < 1) return MISSLAP_BATCH_STATUS_BAD_SHAPE;
+    if (c.has_inf & 2) return MISSLAP_BATCH_STATUS_BAD_OUTSIDE;
+    if (c.has_inf & 1) return MISSLAP_BATCH_STATUS_INFINITE_VALUE;
+    return MISSLAP_BATCH_STATUS_OK;
+}
+
+// The solve of the outside mode: the verdict, batch_solve on the n x (m + n) problem, then the outputs in the caller's
+// terms from the LDS state batch_solve leaves (nothing writes price[] or p2o[] behind its last barrier, and every thread
+// rewrites only the sol cells it wrote itself).
+template <class T>
+__global__ __launch_bounds__(1024) void k_dense_outside_solve(DenseOutsideArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
+    const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
+    const DenseBatchArgs &d = a.t.d;
+    const int n = d.shapes[2 * b], m = d.shapes[2 * b + 1];
+    const DenseBatchCheck ck = d.chk[b];
+    const int code = batch_verdict(dense_outside_verdict(ck, n), false, -1, n, ck.bad_price);
+    if (tid == 0) {
+        a.t.status[b] = code;
+        if (a.t.matching_size) a.t.matching_size[b] = -1;
+    }
+    const int N = (int)d.N, M = (int)d.M;
+    double *po = a.prices ? a.prices + (size_t)b * (size_t)M : nullptr;
+    double *oo = a.outside_prices ? a.outside_prices + (size_t)b * (size_t)N : nullptr;
+    if (code != MISSLAP_BATCH_STATUS_OK) {
+        batch_condemn(d.s, n, m + n, (long long)ck.nvalid + n);
+        if (po)
+            for (int j = tid; j < M; j += nt) po[j] = 0.0;
+        if (oo)
+            for (int i = tid; i < N; i += nt) oo[i] = 0.0;
+        return;
+    }
+    BatchSolveArgs s = d.s;
+    if (a.t.fast) {
+        s.eps_b = nullptr;
+        s.eps_opt = (float)(1.0 / (double)n);
+    }
+    T vals[kDenseBatchCols];
+    const double *O = a.outside + (a.outside_ld ? (size_t)b * (size_t)a.outside_ld : (size_t)b);
+    const DenseBatchRows<T, true> rows{static_cast<const T *>(d.mat) + (size_t)b * (size_t)d.N * (size_t)d.M,
+                                       d.M,
+                                       m,
+                                       s.maximize,
+                                       m + n,
+                                       ck.nvalid + (unsigned long long)n,
+                                       vals,
+                                       {O, a.outside_ld ? 1 : 0}};
+    batch_solve(s, rows, n, m + n, ck.absmax_bits);
+    const double *price = batch_solve_price(s_raw);
+    const int *p2o = batch_solve_p2o(s_raw, s.Ns, s.Ms);
+    int *sol = d.s.sol + (size_t)b * (size_t)d.s.sol_ld;
+    for (int i = tid; i < n; i += nt)
+        if (p2o[i] >= m) sol[i] = -1;
+    if (po)
+        for (int j = tid; j < M; j += nt) po[j] = j < m ? price[j] : 0.0;
+    if (oo)
+        for (int i = tid; i < N; i += nt) oo[i] = i < n ? price[m + i] : 0.0;
 }
 
 }  // namespace misslap

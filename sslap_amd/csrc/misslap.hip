@@ -511,6 +511,7 @@ MISSLAP_API int misslap_get_state(misslap_solver *h, double *prices, int32_t *un
 #include "abi_batch_common.hpp"
 #include "abi_dense_batch.hpp"
 #include "abi_dense_batch_status.hpp"
+#include "abi_dense_batch_outside.hpp"
 #include "abi_sparse_batch.hpp"
 #include "abi_sparse_batch_status.hpp"
 #include "abi_matching_batch.hpp"

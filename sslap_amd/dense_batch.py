@@ -4,6 +4,10 @@ No counterpart in the reference, whose own benchmark solves small dense matrices
 (benchmarking.py:146).  Problem b of a (B, N, M) stack is solved by one workgroup of one launch, and its result is
 exactly what `auction_solve(mat=mats[b, :n_b, :m_b], ...)` returns (csrc/kernels_batch_solve.hpp,
 csrc/kernels_dense_batch.hpp).
+
+With `outside` every row also holds an outside option, so a row may stay unmatched (a partial assignment): problem b is
+the dense matrix `dense_to_augmented` returns, its slice plus an n_b x n_b block with the outside values on the diagonal
+and -1 elsewhere, and its result is the reference's on that n_b x (m_b + n_b) matrix (misslap_solve_dense_batch_outside).
 """
 import ctypes as C
 
@@ -25,14 +29,41 @@ _STATUS_TEXT = {
     _lib.BATCH_STATUS_PRICE_NOT_FINITE: "prices hold a NaN or an infinity",
     _lib.BATCH_STATUS_PRICE_NEGATIVE: "prices must be >= 0 (with the sign bit clear: -0.0 is rejected)",
     _lib.BATCH_STATUS_BAD_SHAPE: "shape ({n}, {m}) outside 1 .. {N} x 1 .. {M}",
+    _lib.BATCH_STATUS_BAD_OUTSIDE: "the outside value of row {row} is {value!r}: it must be >= 0 (a negative value or a NaN "
+                                   "would be an absent entry)",
 }
 # the meta fields a status-mode call on the device returns as views of its record buffer
 _META_VIEWS = ("its", "nreductions", "eCE", "soln_found", "n_assigned", "obj_f64", "start_eps_f32", "final_eps_f32",
                "n_rows", "n_cols", "nnz", "bids_made")
 
 
-def auction_solve_batch(mats, problem="min", eps_start=0., max_iter=1000000, fast=False, cardinality_check=True,
-                        shapes=None, prices=None, errors="raise", mat_dtype="float64"):
+def dense_to_augmented(mats, shapes=None, outside=0.):
+    """(B, N, M) stack -> [aug_b float64 (n_b, m_b + n_b)]: the definition of auction_solve_batch(outside=).
+    aug_b = hstack([mats[b, :n_b, :m_b] widened to float64, D_b]) with D_b holding row i's outside value at (i, i) and
+    -1.0 elsewhere; problem b is auction_solve(mat=aug_b, ..., cardinality_check=False).  mats: a numpy array of any float
+    type or a tensor; shapes: optional integer (B, 2); outside: a float, float64 (B,) or float64 (B, N)."""
+    if hasattr(mats, "cpu"):
+        mats = mats.double().cpu().numpy()
+    mats = np.asarray(mats)
+    if mats.ndim != 3:
+        raise ValueError(f"mats must have 3 dimensions (B, N, M), got {mats.ndim}")
+    B, N, M = mats.shape
+    shp = np.tile([N, M], (B, 1)) if shapes is None else np.asarray(shapes.cpu() if hasattr(shapes, "cpu") else shapes)
+    o = np.asarray(outside.cpu() if hasattr(outside, "cpu") else outside, dtype=np.float64)
+    if o.shape not in ((), (B,), (B, N)):
+        raise ValueError(f"outside must be a float or have shape ({B},) or ({B}, {N}), got {o.shape}")
+    o = np.broadcast_to(o if o.ndim != 1 else o[:, None], (B, N))
+    out = []
+    for b in range(B):
+        n, m = (max(int(x), 0) for x in shp[b])
+        d = np.full((n, n), -1.0)
+        d[np.arange(n), np.arange(n)] = o[b, :n]
+        out.append(np.ascontiguousarray(np.hstack([mats[b, :n, :m].astype(np.float64), d])))
+    return out
+
+
+def auction_solve_batch(mats, problem="min", eps_start=0., max_iter=1000000, fast=None, cardinality_check=True,
+                        shapes=None, prices=None, errors="raise", mat_dtype="float64", outside=None):
     """Solve B independent dense problems in one call, one workgroup per problem.
 
     mats: float64 (or mat_dtype, below) (B, N, M), a numpy array or a contiguous tensor on the device (read in place, ordered behind
@@ -63,6 +94,32 @@ def auction_solve_batch(mats, problem="min", eps_start=0., max_iter=1000000, fas
     the default mode's meta dict).  shapes and prices may then be device tensors; a device shapes entry outside the
     stack gives MISSLAP_BATCH_STATUS_BAD_SHAPE.  The matching guard always runs on the device in this mode, which at
     B = 1 is slower than the default mode's host guard.
+
+    outside: partial assignments (misslap_solve_dense_batch_outside).  A finite float >= 0, float64 (B,) or float64
+    (B, N) -- a numpy array or, with a device stack, a contiguous tensor on the same device: the outside value of every
+    row, in the units of the stack (problem="min": the cost of leaving row i unmatched; "max": the value of doing so),
+    always float64 whatever mat_dtype is.  Problem b is then aug_b = hstack([mats[b, :n_b, :m_b], D_b]), D_b holding the
+    outside values on its diagonal and -1 elsewhere, and its result is bit for bit
+    auction_solve(mat=aug_b, ..., cardinality_check=False) on dense_to_augmented(mats, shapes, outside); with prices the
+    solve starts from [p0[b, :m_b], zeros(n_b)].  sol[b, i] is the real column, or -1 where row i took its outside option
+    (and beyond n_b, on a condemned problem, or where max_iter cut the solve).  prices stays (B, M), the real columns; the
+    new key outside_prices is float64 (B, N), the price of row i's outside object and 0 beyond n_b (a row without any valid
+    entry bids +inf as a one-entry row of the reference does, so its outside price is +inf).  meta is the augmented
+    problem's record (n_cols = m_b + n_b, nnz = valid entries + n_b; n_assigned counts rows on their outside option).
+    Both errors= modes run the same call and return the status-mode dict; "raise" then applies raise_for_status.  An
+    outside value is an entry of a dense matrix: -0.0 is valid, +inf gives MISSLAP_BATCH_STATUS_INFINITE_VALUE, and a
+    negative value or a NaN in a row < n_b -- an absent entry, "this row must be matched": not offered -- gives
+    MISSLAP_BATCH_STATUS_BAD_OUTSIDE (15).  The checks, in their order: BAD_SHAPE, BAD_OUTSIDE, INFINITE_VALUE,
+    PRICE_NOT_FINITE, PRICE_NEGATIVE.  TOO_FEW_VALUES, EMPTY_ROW and INFEASIBLE cannot occur: fully gated rows, graphs
+    without a complete matching and n_b > m_b are solved; the guard is not launched whatever cardinality_check says and
+    matching_size is -1.  The values of rows >= n_b are never read.
+
+    fast=None (default) is False without outside (the call is what it always was) and with outside True, unless
+    eps_start > 0 was given (then False); an explicit fast= or eps_start= is passed through as it is.  Why: the augmented
+    problem is rectangular (n rows, m + n columns).  A single phase (fast=True, or 0 < eps_start <= 1 / n) from zero prices
+    is optimal within n * eps.  The reference's eps-scaling (fast=False, eps_start=0) keeps prices between phases and has no
+    reverse phase: it gives the reference's answer on the augmented problem, which is NOT the optimum in general.  The
+    same holds for every rectangular problem (n < m) of the batch solves.
     """
     if errors not in ("raise", "status"):
         raise ValueError(f"errors must be 'raise' or 'status', got {errors!r}")
@@ -70,6 +127,11 @@ def auction_solve_batch(mats, problem="min", eps_start=0., max_iter=1000000, fas
     if N > MAX_DIM or M > MAX_DIM:
         raise ValueError(f"problems of {N} x {M}: auction_solve_batch takes at most {MAX_DIM} x {MAX_DIM} "
                          f"(MISSLAP_DENSE_BATCH_MAX_DIM); solve larger problems with from_matrix / solve_batch")
+    if outside is not None:
+        res = _solve_outside(mats, B, N, M, on_device, problem, eps_start, max_iter, fast, shapes, prices, dtype, outside)
+        return raise_for_status(res) if errors == "raise" else res
+    if fast is None:  # (resolved here: the library gets a plain flag)
+        fast = False
     if errors == "status":
         return _solve_status(mats, B, N, M, on_device, problem, eps_start, max_iter, fast, cardinality_check, shapes,
                              prices, dtype)
@@ -165,6 +227,70 @@ def _solve_status(mats, B, N, M, on_device, problem, eps_start, max_iter, fast, 
                 stack=(N, M), records=rec, info=info, stream=stream, keep=(work, mats, p))
 
 
+def _solve_outside(mats, B, N, M, on_device, problem, eps_start, max_iter, fast, shapes, prices, dtype, outside):
+    """auction_solve_batch(outside=) in either mode (misslap_solve_dense_batch_outside): the result dict of the status
+    mode plus outside_prices.  The whole-call checks in the status mode's order, then outside."""
+    from .ell_batch import _check_outside, _send
+    if not on_device:  # synchronous: the library uploads, uses its own scratch and waits once
+        shp = _check_shapes(shapes, B, N, M, "problem")
+        e = _eps(eps_start)
+        p, p_ptr, _ = _starting_prices(prices, B, M, True, False, mats, "mats")
+        out_v, out_ld = _check_outside(outside, B, N, False, None, "mats", "mats", True)
+        if fast is None:
+            fast = not e > 0
+        opts = _solve_options(False, mats, problem, e, max_iter, dtype)
+        mc = np.ascontiguousarray(mats)
+        sol, pout = np.empty((B, N), dtype=np.int32), np.empty((B, M), dtype=np.float64)
+        oout = np.empty((B, N), dtype=np.float64)
+        status, msize = np.empty(B, dtype=np.int32), np.empty(B, dtype=np.int32)
+        metas, info = _new_meta(B)
+        _lib.check(_lib.load().misslap_solve_dense_batch_outside(
+            B, N, M, mc.ctypes.data, None if shp is None else shp.ctypes.data, 1 if fast else 0, p_ptr, C.byref(opts), None,
+            None, 0, out_v.ctypes.data, out_ld, sol.ctypes.data, pout.ctypes.data, oout.ctypes.data, 0, status.ctypes.data,
+            msize.ctypes.data, C.cast(metas, C.c_void_p), C.byref(info)))
+        return dict(sol=sol, prices=pout, outside_prices=oout, status=status, matching_size=msize,
+                    meta=_decode_meta(metas, info), shapes=shp, stack=(N, M), outside=out_v)
+    import torch
+    dev = mats.device
+    if shapes is None or _is_device_tensor(shapes):
+        shp = shapes
+        if shp is not None and (shp.dtype != torch.int32 or tuple(shp.shape) != (B, 2) or shp.device != dev or
+                                not shp.is_contiguous()):
+            raise ValueError(f"a device shapes tensor must be contiguous int32 of shape ({B}, 2) on {dev}, got "
+                             f"{shp.dtype} {tuple(shp.shape)} on {shp.device}")
+    else:  # a host array: validated as in the default mode, sent from pinned memory without a wait
+        shp = _send(_check_shapes(shapes, B, N, M, "problem"), dev)
+    e = _eps(eps_start)
+    if isinstance(prices, np.ndarray):
+        _starting_prices(prices, B, M, True, False, mats, "mats")  # (dtype and shape)
+        prices = _send(np.ascontiguousarray(prices), dev)
+    p, p_ptr, _ = _starting_prices(prices, B, M, True, True, mats, "mats")
+    out_v, out_ld = _check_outside(outside, B, N, True, dev, "mats", "mats", True)
+    if fast is None:
+        fast = not e > 0
+    opts = _solve_options(True, mats, problem, e, max_iter, dtype)
+    lib = _lib.load()
+    nbytes = int(lib.misslap_dense_batch_outside_workspace_bytes(B, N, M, 0 if p is None else 1))
+    with torch.cuda.device(dev):  # (the allocations and copies below are made on the current stream of the stack's device)
+        stream = torch.cuda.current_stream(dev)
+        d_out = _send(out_v, dev)
+        work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        sol = torch.empty((B, N), dtype=torch.int32, device=dev)
+        pout = torch.empty((B, M), dtype=torch.float64, device=dev)
+        oout = torch.empty((B, N), dtype=torch.float64, device=dev)
+        status = torch.empty(B, dtype=torch.int32, device=dev)
+        msize = torch.empty(B, dtype=torch.int32, device=dev)
+        rec = torch.empty((B, C.sizeof(_lib.DenseBatchMeta)), dtype=torch.uint8, device=dev)
+    info = _lib.DenseBatchInfo()
+    _lib.check(lib.misslap_solve_dense_batch_outside(
+        B, N, M, mats.data_ptr(), None if shp is None else shp.data_ptr(), 1 if fast else 0, p_ptr, C.byref(opts),
+        C.c_void_p(int(stream.cuda_stream)), work.data_ptr(), nbytes, d_out.data_ptr(), out_ld, sol.data_ptr(),
+        pout.data_ptr(), oout.data_ptr(), 1, status.data_ptr(), msize.data_ptr(), rec.data_ptr(), C.byref(info)))
+    # the workspace and the inputs stay referenced by the result: nothing of this call is recycled before it
+    return dict(sol=sol, prices=pout, outside_prices=oout, status=status, matching_size=msize, meta=_meta_views(rec),
+                shapes=shp, stack=(N, M), outside=d_out, records=rec, info=info, stream=stream, keep=(work, mats, p))
+
+
 def _meta_views(rec):
     """The fields of a device buffer of misslap_dense_batch_meta records as column views, one tensor of length B each."""
     import torch
@@ -217,4 +343,13 @@ def raise_for_status(res):
     n, m, card = int(host(res["meta"]["n_rows"])[b]), 0, int(host(res["matching_size"])[b])
     if status[b] == _lib.BATCH_STATUS_BAD_SHAPE:
         n, m = (int(x) for x in host(res["shapes"])[b])
-    raise ValueError(f"problem {b}: " + _STATUS_TEXT[int(status[b])].format(n=n, m=m, N=N, M=M, card=card))
+    row, value = 0, 0.0
+    if status[b] == _lib.BATCH_STATUS_BAD_OUTSIDE:  # the first row < n_b whose outside value is no entry
+        o = host(res["outside"])[b]
+        o = np.broadcast_to(o, (n,)) if o.ndim == 0 else o[:n]
+        row = int(np.flatnonzero(~(o >= 0))[0])
+        value = float(o[row])
+    text = _STATUS_TEXT[int(status[b])].format(n=n, m=m, N=N, M=M, card=card, row=row, value=value)
+    if status[b] == _lib.BATCH_STATUS_INFINITE_VALUE and "outside_prices" in res:
+        text += " (in an entry or in the outside value of a row)"
+    raise ValueError(f"problem {b}: {text}")

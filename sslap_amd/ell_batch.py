@@ -121,20 +121,21 @@ def _check_rows(rows, B, on_device, dev):
     return np.ascontiguousarray(np.clip(r, -1, _INT_MAX), dtype=np.int32)  # (whatever is out of range stays so)
 
 
-def _check_outside(outside, B, N, on_device, dev):
+def _check_outside(outside, B, N, on_device, dev, need="cols / vals", src="cols", nonneg=False):
     """The outside values of a call: a finite float (broadcast to (B,) where the input lives, nothing read back), or
     float64 (B,) / (B, N) on the host or (with device input) contiguous on the input's device.  Returns (array or tensor,
-    outside_ld); the values are the library's to judge."""
+    outside_ld); the values are the library's to judge.  need / src: what the input is called in the texts; nonneg: a
+    float must also be >= 0 (the dense batch, where a negative entry is an absent one)."""
     if _is_device_tensor(outside):
         import torch
         if not on_device:
-            raise TypeError("outside on the device needs cols / vals on the device")
+            raise TypeError(f"outside on the device needs {need} on the device")
         if outside.dtype != torch.float64:
             raise ValueError(f"outside must be float64, got {outside.dtype}")
         if tuple(outside.shape) not in ((B,), (B, N)):
             raise ValueError(f"outside must have shape ({B},) or ({B}, {N}), got {tuple(outside.shape)}")
         if outside.device != dev:
-            raise ValueError(f"outside is on {outside.device}, cols on {dev}")
+            raise ValueError(f"outside is on {outside.device}, {src} on {dev}")
         if not outside.is_contiguous():
             raise ValueError("a device outside tensor must be contiguous (it is read in place)")
         return outside, (N if outside.dim() == 2 else 0)
@@ -149,6 +150,8 @@ def _check_outside(outside, B, N, on_device, dev):
     x = float(outside)
     if not np.isfinite(x):
         raise ValueError(f"outside must be finite, got {x!r}")
+    if nonneg and not x >= 0:
+        raise ValueError(f"outside must be >= 0 (a negative entry of a dense matrix is an absent one), got {x!r}")
     if on_device:
         import torch
         return torch.full((B,), x, dtype=torch.float64, device=dev), 0
