@@ -395,9 +395,28 @@ __device__ __forceinline__ int half_allmax_i32(int v) {
     return max((int)s[0], (int)s[1]);
 }
 
+// wave-uniform maximum over the 32-lane half H (a scalar): after the row_mirror step EVERY lane of a 16-lane row holds its
+// row's maximum, so two v_readlane and one s_max_i32 replace the row broadcast, its v_max and the wait states around them
+template <int H>
+__device__ __forceinline__ int half_max_i32_s(int v) {
+    v = max(v, dppf_i32<kDppXor1>(v));
+    v = max(v, dppf_i32<kDppXor2>(v));
+    v = max(v, dppf_i32<kDppHalfMirror>(v));
+    v = max(v, dppf_i32<kDppMirror>(v));
+    return max(__builtin_amdgcn_readlane(v, kCandLanes * H), __builtin_amdgcn_readlane(v, kCandLanes * H + 16));
+}
+
 // the cost of a line slot's candidate (lane-wise / of lane `sl`, wave-uniform), and the lines in memory
 __device__ __forceinline__ double slot_cost(const int2 &s) { return (double)__int_as_float(s.y); }
 __device__ __forceinline__ double slot_cost(const Slot64 &s) { return s.c; }
+// ... -inf where the lane holds no candidate: the value  cost - price  is then -inf by itself (prices are finite or +inf,
+// never NaN: -inf - (+inf) = -inf), so no select stands between the record gather and the reduction
+__device__ __forceinline__ double slot_cost_or_ninf(const int2 &s, bool is_cand) {
+    return (double)(is_cand ? __int_as_float(s.y) : -__builtin_huge_valf());
+}
+__device__ __forceinline__ double slot_cost_or_ninf(const Slot64 &s, bool is_cand) {
+    return is_cand ? s.c : -__builtin_huge_val();
+}
 __device__ __forceinline__ double slot_cost_at(const int2 &s, int sl) {
     return (double)__int_as_float(__builtin_amdgcn_readlane(s.y, sl));
 }
@@ -541,13 +560,17 @@ __device__ __forceinline__ void cand_eval2_r(Slot &slot, const PriceRec r, const
 }
 // The same for ONE person (lanes 0..31 hold its line, `cls` = the lane is one of them and its slot is a candidate
 // slot, i.e. 1 <= lane <= kCandMax): the chain of single-bidder rounds is half of all rounds at C3 and two thirds
-// at C5, and a round is bound by the length of this dependent instruction sequence, not by memory.
+// at C5, and a round is bound by the length of this dependent instruction sequence, not by memory.  What needs the line
+// alone (tau, the row length, the lane's cost -- -inf where the lane holds no candidate) is formed while the record gather
+// is in flight; behind it: the subtraction, one 32-bit reduction of the high words, ballot, the winner's data, the request
+// of the next line (`early`), then the second-best pass and the bid.  (Requesting the next line from the ballot's first
+// lane BEFORE the uniqueness test, into a second slot variable, was measured slower: profiles/tail_winner_path.txt.)
 // the lane's record gather of a one-person line evaluation (split off: a caller may issue the gather of the NEXT round's
 // line ahead of a barrier and evaluate it behind it, kernels_tail.hpp)
 template <class Slot, class Src>
 __device__ __forceinline__ PriceRec cand_gather1(const Slot &slot, const bool cls, const Src &src) {
-    const bool is_cand = cls & (slot.x >= 0);
-    return src.get(is_cand ? slot.x : 0);
+    return src.get(cls ? max(slot.x, 0) : 0);  // (an empty slot reads record 0 like a lane outside the line; the index is
+                                               // known to be >= 0, so no sign extension stands in front of the gather)
 }
 template <class Slot, class Early, class S = NoStamp>
 __device__ __forceinline__ void cand_eval1_r(Slot &slot, const PriceRec r, const bool cls, const double eps, CandBid &out,
@@ -566,24 +589,24 @@ __device__ __forceinline__ void cand_eval1_r(Slot &slot, const PriceRec r, const
     const int lane = lane_id();
     const double ninf = -__builtin_huge_val();
     const bool is_cand = cls & (slot.x >= 0);
-    const double cost = slot_cost(slot);
+    const double cost = slot_cost_or_ninf(slot, is_cand);  // (everything that needs the line alone: under the gather)
     const double tau = readlane_f64(__hiloint2double(slot.y, slot.x), 0);
     out.len = __builtin_amdgcn_readlane(slot.x, kCandLanes - 1);
-    const double v = is_cand ? cost - r.price : ninf;  // vi = cost - p[j]   (:350)
+    const double v = cost - r.price;  // vi = cost - p[j]   (:350); -inf where the lane holds no candidate
     const int hi = __double2hiint(v);
     const int k = hi ^ ((hi >> 31) & 0x7fffffff);  // signed order of k == order of the doubles' high words
-    const int km = __builtin_amdgcn_readlane(half_max_i32(k), 31);
-    const unsigned eq = (unsigned)(__ballot(k == km) & 0xffffffffull);
+    const int km = half_max_i32_s<0>(k);
+    const unsigned eq = (unsigned)(__ballot(k == km) & 0xffffffffull);  // (never 0: a lane of 0..31 holds the maximum)
     double V;
-    int G;
+    int G, sl;
     if (__popc(eq) == 1) {  // wave-uniform, the common case: the winner is known after one 32-bit reduction
-        G = __ffs((int)eq) - 1;
+        G = sl = __ffs((int)eq) - 1;
         V = readlane_f64(v, G);
     } else {
         V = readlane_f64(half_max_f64(v), 31);
         G = __builtin_amdgcn_readlane(half_max_i32((is_cand & (v == V)) ? lane : -1), 31);  // the LAST slot holding it
+        sl = max(G, 0);  // (-1: no candidate at all)
     }
-    const int sl = max(G, 0);
     out.obj = __builtin_amdgcn_readlane(slot.x, sl);
     out.prev = __builtin_amdgcn_readlane(r.owner, sl);
     out.pstart = __builtin_amdgcn_readlane(r.ostart, sl);

@@ -439,10 +439,18 @@ __device__ __forceinline__ void tail_pair_mode(const TailArgs &a, const E &ed, i
     while (K == 2) {  // (wave-uniform: the loop ends by `break`)
         stamp(1);
         const PriceRec g = cand_gather1(slot, cls, src);
-        stamp(2);
-        // both line evaluations (cand_eval1_r per half)
+        // both line evaluations (cand_eval1_r per half).  Under the gather: what needs the lines alone
         const bool is_cand = cls & (slot.x >= 0);
-        const double v = is_cand ? slot_cost(slot) - g.price : ninf;  // vi = cost - p[j]   (:350)
+        const double cost = slot_cost_or_ninf(slot, is_cand);
+        CandBid b[2];
+        double tau[2], c1[2];
+#pragma unroll
+        for (int X = 0; X < 2; ++X) {
+            tau[X] = readlane_f64(__hiloint2double(slot.y, slot.x), kCandLanes * X);
+            b[X].len = __builtin_amdgcn_readlane(slot.x, kCandLanes * X + kCandLanes - 1);
+        }
+        stamp(2);
+        const double v = cost - g.price;  // vi = cost - p[j]   (:350); -inf where the lane holds no candidate
         const int hw = __double2hiint(v);
         const int k = hw ^ ((hw >> 31) & 0x7fffffff);  // signed order of k == order of the doubles' high words
         const unsigned long long eq = __ballot(k == half_allmax_i32(k));
@@ -462,13 +470,9 @@ __device__ __forceinline__ void tail_pair_mode(const TailArgs &a, const E &ed, i
             G[0] = __builtin_amdgcn_readlane(gm, kCandLanes - 1);
             G[1] = __builtin_amdgcn_readlane(gm, kWave - 1);
         }
-        CandBid b[2];
-        double tau[2], c1[2];
 #pragma unroll
         for (int X = 0; X < 2; ++X) {
             const int sl = max(G[X], kCandLanes * X);
-            tau[X] = readlane_f64(__hiloint2double(slot.y, slot.x), kCandLanes * X);
-            b[X].len = __builtin_amdgcn_readlane(slot.x, kCandLanes * X + kCandLanes - 1);
             b[X].obj = __builtin_amdgcn_readlane(slot.x, sl);
             b[X].prev = __builtin_amdgcn_readlane(g.owner, sl);
             b[X].pstart = __builtin_amdgcn_readlane(g.ostart, sl);
