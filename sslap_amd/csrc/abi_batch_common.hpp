@@ -1,8 +1,9 @@
-// abi_batch_common.hpp -- what the one-workgroup-per-problem entry points share: misslap_solve_dense_batch
-// (abi_dense_batch.hpp), misslap_solve_sparse_batch (abi_sparse_batch.hpp) and misslap_matching_batch /
-// misslap_matching_dense_batch (abi_matching_batch.hpp).  The options whitelist, the device and stream, the meta stride,
-// the host guards' thread pool, the starting-price texts and the solve's launch (batch_solve_run).
-// (part of the single translation unit misslap.hip; included in the order given there, before abi_dense_batch.hpp)
+// abi_batch_common.hpp -- what the one-workgroup-per-problem entry points share: the all-or-nothing solves
+// (abi_dense_batch.hpp, abi_sparse_batch.hpp), the matching batch (abi_matching_batch.hpp) and the five solves with a
+// verdict per problem (abi_batch_stream.hpp and its users).  The options whitelist, the device and stream, the meta
+// stride and the records' way back to it, the host guards' thread pool, the starting-price texts, the workspace carve
+// (batch_carve), the one solve launch (batch_solve_launch) and the all-or-nothing solve around it (batch_solve_run).
+// (part of the single translation unit misslap.hip; included in the order given there, before abi_batch_stream.hpp)
 #pragma once
 
 namespace {
@@ -138,9 +139,82 @@ int reject_bad_prices(int64_t b, int bad) {
 // a wavefront bids for one list position at a time: enough wavefronts for the first round's bidders, at most 16
 inline int batch_solve_threads(int Ns) { return Ns <= 256 ? 256 : (Ns <= 512 ? 512 : 1024); }
 
-// The solve once every problem is accepted: one launch of `kernel` (k_dense_batch_solve / k_sparse_batch_solve), one
-// workgroup per problem, on the LDS carve Ns x Ms; then the outputs, the meta records and the info.  The caller has set
-// a's own fields and a.s.eps_b / p0 / p0_ld; the rest of a.s is set here.
+// Byte offsets of the segments of a workspace, each on a 256-byte boundary, and their total (a segment of 0 bytes takes
+// no room).  Every *_workspace_bytes function returns the total of the carve its enqueue step reads.
+struct BatchCarve {
+    size_t off[4] = {0, 0, 0, 0}, total = 0;
+    template <class T>
+    T *at(void *ws, int seg) const {
+        return reinterpret_cast<T *>(static_cast<char *>(ws) + off[seg]);
+    }
+};
+inline BatchCarve batch_carve(std::initializer_list<size_t> bytes) {
+    BatchCarve c;
+    int i = 0;
+    for (size_t b : bytes) {
+        c.off[i++] = c.total;
+        c.total += (b + 255) & ~(size_t)255;
+    }
+    return c;
+}
+
+// The solve launch of every batch entry point: one workgroup per problem on the LDS carve Ns x Ms.  `s` is the
+// BatchSolveArgs inside `a`; the caller has set a's own fields and s.eps_b (null unless the call takes an eps per
+// problem), the rest of s is set here.  The > 64 KB dynamic-LDS opt-in is a property of the function on the current
+// device, set on the host without a wait.  ev: the two events recorded around the launch, or null.  Nothing here
+// allocates, waits or copies; info (or null) is zeroed but for the launch geometry.
+template <class Args>
+int batch_solve_launch(void (*kernel)(Args), Args &a, BatchSolveArgs &s, const misslap_options &opt, int64_t B, int64_t Ns,
+                       int64_t Ms, int32_t *sol, int64_t sol_ld, double *prices, int64_t prices_ld, const double *p0,
+                       int64_t p0_ld, misslap_dense_batch_meta *meta, misslap_dense_batch_info *info, hipStream_t st,
+                       EventPair *ev = nullptr) {
+    s.eps_opt = opt.eps_start;
+    s.p0 = p0;
+    s.p0_ld = p0_ld;
+    s.maximize = opt.maximize ? 1 : 0;
+    s.max_iter = opt.max_iter;
+    s.Ns = (int)Ns;
+    s.Ms = (int)Ms;
+    s.sol = sol;
+    s.sol_ld = sol_ld;
+    s.prices = prices;
+    s.prices_ld = prices_ld;
+    s.meta = meta;
+    const int threads = batch_solve_threads((int)Ns);
+    const size_t lds = batch_solve_lds_bytes(Ns, Ms);
+    if (lds > 65536) HIP_TRY(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (ev) HIP_TRY(hipEventRecord(ev->e[0], st));
+    hipLaunchKernelGGL(kernel, dim3((unsigned)B), dim3(threads), lds, st, a);
+    HIP_TRY(hipGetLastError());
+    if (ev) HIP_TRY(hipEventRecord(ev->e[1], st));
+    if (info) {
+        std::memset(info, 0, sizeof(*info));
+        info->threads = threads;
+        info->lds_bytes = (int32_t)lds;
+    }
+    return MISSLAP_OK;
+}
+
+// The meta records of a call back into the caller's host array of `stride`-byte records: the copy on st, and, once st
+// has been waited for, the caller's struct_size put back (it is an input field).  Both do nothing without meta.
+int batch_meta_copy_back(misslap_dense_batch_meta *meta, int32_t stride, const misslap_dense_batch_meta *d_meta, int64_t B,
+                         hipStream_t st) {
+    if (!meta) return MISSLAP_OK;
+    const size_t w = std::min((size_t)stride, sizeof(misslap_dense_batch_meta));
+    HIP_TRY(hipMemcpy2DAsync(meta, (size_t)stride, d_meta, sizeof(misslap_dense_batch_meta), w, (size_t)B,
+                             hipMemcpyDeviceToHost, st));
+    return MISSLAP_OK;
+}
+void batch_meta_keep_stride(misslap_dense_batch_meta *meta, int32_t stride, int64_t B) {
+    if (!meta) return;
+    for (int64_t b = 0; b < B; ++b)
+        reinterpret_cast<misslap_dense_batch_meta *>(reinterpret_cast<char *>(meta) + (size_t)b * (size_t)stride)
+            ->struct_size = stride;
+}
+
+// The solve of an all-or-nothing call once every problem is accepted: the launch of `kernel` (k_dense_batch_solve /
+// k_sparse_batch_solve), then the outputs, the meta records and the info.  The caller has set a's own fields, a.s.eps_b
+// and a.s.p0 / p0_ld.
 template <class Args>
 int batch_solve_run(void (*kernel)(Args), Args a, hipStream_t st, DevScratch &tmp, const misslap_options &opt, int64_t B,
                     int Ns, int Ms, int32_t *sol, int64_t sol_ld, double *prices_out, int64_t prices_ld,
@@ -155,49 +229,26 @@ int batch_solve_run(void (*kernel)(Args), Args a, hipStream_t st, DevScratch &tm
         if ((rc = tmp.alloc(&d_sol, (size_t)B * (size_t)sol_ld))) return rc;
         if (prices_out && (rc = tmp.alloc(&d_prices, (size_t)B * (size_t)prices_ld))) return rc;
     }
-    a.s.eps_opt = opt.eps_start;
-    a.s.maximize = opt.maximize ? 1 : 0;
-    a.s.max_iter = opt.max_iter;
-    a.s.Ns = Ns;
-    a.s.Ms = Ms;
-    a.s.sol = d_sol;
-    a.s.sol_ld = sol_ld;
-    a.s.prices = d_prices;
-    a.s.prices_ld = prices_ld;
-    a.s.meta = d_meta;
-    const int threads = batch_solve_threads(Ns);
-    const size_t lds = batch_solve_lds_bytes(Ns, Ms);
-    // (per call: the > 64 KB dynamic-LDS opt-in is a property of the function on the current device.  Only a sparse
-    // carve needs it: the dense one is at most 53 248 B, at MISSLAP_DENSE_BATCH_MAX_DIM x MISSLAP_DENSE_BATCH_MAX_DIM.)
-    if (lds > 65536) HIP_TRY(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     EventPair ev;
     if ((rc = ev.create())) return rc;
-    HIP_TRY(hipEventRecord(ev.e[0], st));
-    hipLaunchKernelGGL(kernel, dim3((unsigned)B), dim3(threads), lds, st, a);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ev.e[1], st));
+    misslap_dense_batch_info launch{};
+    if ((rc = batch_solve_launch(kernel, a, a.s, opt, B, Ns, Ms, d_sol, sol_ld, d_prices, prices_ld, a.s.p0, a.s.p0_ld,
+                                 d_meta, &launch, st, &ev)))
+        return rc;
     if (!out_on_device) {
         HIP_TRY(hipMemcpyAsync(sol, d_sol, sizeof(int32_t) * (size_t)B * (size_t)sol_ld, hipMemcpyDeviceToHost, st));
         if (prices_out)
             HIP_TRY(hipMemcpyAsync(prices_out, d_prices, sizeof(double) * (size_t)B * (size_t)prices_ld,
                                    hipMemcpyDeviceToHost, st));
     }
-    if (meta) {
-        const size_t w = std::min((size_t)stride, sizeof(misslap_dense_batch_meta));
-        HIP_TRY(hipMemcpy2DAsync(meta, (size_t)stride, d_meta, sizeof(misslap_dense_batch_meta), w, (size_t)B,
-                                 hipMemcpyDeviceToHost, st));
-    }
+    if ((rc = batch_meta_copy_back(meta, stride, d_meta, B, st))) return rc;
     HIP_TRY(hipStreamSynchronize(st));
     tmp.drained = true;
-    if (meta)  // (struct_size is an input field: the caller's value stays)
-        for (int64_t b = 0; b < B; ++b)
-            reinterpret_cast<misslap_dense_batch_meta *>(reinterpret_cast<char *>(meta) + (size_t)b * (size_t)stride)
-                ->struct_size = stride;
+    batch_meta_keep_stride(meta, stride, B);
     if (info) {
         double ms = 0;
         if ((rc = ev.elapsed(&ms))) return rc;
-        info->threads = threads;
-        info->lds_bytes = (int32_t)lds;
+        *info = launch;
         info->check_ms = t_checked - t_start - guard_ms;
         info->matching_ms = guard_ms + (t_matched - t_checked);
         info->solve_ms = ms;

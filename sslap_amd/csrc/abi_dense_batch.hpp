@@ -1,6 +1,6 @@
 // abi_dense_batch.hpp -- C ABI: many small dense problems in one call, one workgroup per problem
 // (misslap_solve_dense_batch; the kernels are in kernels_dense_batch.hpp, the shared host helpers in abi_batch_common.hpp).
-// (part of the single translation unit misslap.hip; included in the order given there, after abi_batch_common.hpp)
+// (part of the single translation unit misslap.hip; included in the order given there, after abi_batch_stream.hpp)
 #pragma once
 
 namespace {

@@ -1,6 +1,8 @@
 // kernels_batch_solve.hpp -- the round loop of the one-workgroup-per-problem batch solves, shared by
-// k_dense_batch_solve (kernels_dense_batch.hpp) and k_sparse_batch_solve (kernels_sparse_batch.hpp); the host side is
-// batch_solve_run in abi_batch_common.hpp.
+// every solve kernel of kernels_dense_batch.hpp, kernels_sparse_batch.hpp and kernels_ell_batch.hpp, and what those
+// kernels share around it: the verdict of a status-mode problem, the outputs of a condemned one, the eps of `fast`, the
+// outside option of a row and the outputs of an outside call.  The host side is batch_solve_launch in
+// abi_batch_common.hpp.
 //
 // A problem within the batch caps (MISSLAP_DENSE_BATCH_MAX_DIM, MISSLAP_SPARSE_BATCH_MAX_DIM) keeps the whole state of
 // the reference's solver (auction_.pyx:167-200) in LDS: prices, person_to_object, object_to_person, the unassigned
@@ -35,7 +37,8 @@
 
 namespace misslap {
 
-// What both solves take per batch (the first member of DenseBatchArgs / SparseBatchArgs; filled by batch_solve_run)
+// What every solve takes per batch (the first member of DenseBatchArgs / SparseBatchArgs / EllBatchArgs; filled by
+// batch_solve_launch)
 struct BatchSolveArgs {
     const float *eps_b;        // [B] or null
     float eps_opt;
@@ -109,6 +112,73 @@ __device__ __forceinline__ void batch_condemn(const BatchSolveArgs &a, int n, in
     }
 }
 
+// The verdict of problem b and the guard's cardinality (-1 where it did not run), published by thread 0
+__device__ __forceinline__ void batch_publish_verdict(int *status, int *matching_size, int b, int code, int card) {
+    if (threadIdx.x == 0) {
+        status[b] = code;
+        if (matching_size) matching_size[b] = card;
+    }
+}
+
+// `fast`: the problem starts at eps = 1 / n (auction_.pyx:568-569, :614-615) -- the front end's
+// (1.0 / float64(n)).astype(float32), the same two IEEE operations
+__device__ __forceinline__ void batch_fast_eps(BatchSolveArgs &s, double n) {
+    s.eps_b = nullptr;
+    s.eps_opt = (float)(1.0 / n);
+}
+
+// One entry's net value vi, with tie key `key`, into a lane's running top two under the reference's ">=" rule (:351; the
+// first entry is always taken: vi >= -inf for every non-NaN vi).  True where it became the best: the caller then keeps
+// its cost and its object.
+__device__ __forceinline__ bool top2_take(Top2 &x, double vi, int key) {
+    if (vi >= x.v) {
+        x.w = x.v;
+        x.v = vi;
+        x.g = key;
+        return true;
+    }
+    if (vi > x.w) x.w = vi;
+    return false;
+}
+
+// The outside option of the rows of one problem (the <.., true> row sources): row i's value is O[i * stride] (stride 0:
+// one value for the problem), its object is the problem's m + i.  Empty in the plain mode.
+template <bool Out>
+struct BatchOutside {};
+template <>
+struct BatchOutside<true> {
+    const double *O;
+    int stride;
+    __device__ __forceinline__ double value(int i) const { return O[i * stride]; }
+};
+
+// The price outputs of an outside call (po: [M_ld] the real columns, oo: [N_ld] the outside objects, either may be null)
+// for a condemned problem, next to batch_condemn: zeros.  (tid, T: threadIdx.x and blockDim.x as the kernel read them at
+// its top -- read here instead, the same values change the schedule of the whole kernel.)
+__device__ __forceinline__ void batch_outside_condemn(double *po, int M_ld, double *oo, int N_ld, int tid, int T) {
+    if (po)
+        for (int j = tid; j < M_ld; j += T) po[j] = 0.0;
+    if (oo)
+        for (int i = tid; i < N_ld; i += T) oo[i] = 0.0;
+}
+
+// The outputs of an outside call in the caller's terms, behind batch_solve(s, ..) on the n x (m + n) problem, from the LDS
+// state it leaves (nothing writes price[] or p2o[] behind its last barrier, and every thread rewrites only the sol cells
+// it wrote itself): an object >= m becomes -1 in sol, price[0 .. m) are the real prices, price[m .. m + n) the outside ones.
+__device__ __forceinline__ void batch_outside_outputs(const unsigned char *s_raw, const BatchSolveArgs &s, int b, int n,
+                                                      int m, int M_ld, int N_ld, double *po, double *oo, int tid,
+                                                      int T) {
+    const double *price = batch_solve_price(s_raw);
+    const int *p2o = batch_solve_p2o(s_raw, s.Ns, s.Ms);
+    int *sol = s.sol + (size_t)b * (size_t)s.sol_ld;
+    for (int i = tid; i < n; i += T)
+        if (p2o[i] >= m) sol[i] = -1;
+    if (po)
+        for (int j = tid; j < M_ld; j += T) po[j] = j < m ? price[j] : 0.0;
+    if (oo)
+        for (int i = tid; i < N_ld; i += T) oo[i] = i < n ? price[m + i] : 0.0;
+}
+
 // eCE_satisfied(eps) (auction_.pyx:443-485, tol = 1e-7) on a state with everybody assigned; one wavefront per row.
 template <class Rows>
 __device__ __forceinline__ bool batch_ece(const Rows &rows, int n, const double *price, const int *p2o, float eps_f,
@@ -131,8 +201,8 @@ __device__ __forceinline__ bool batch_ece(const Rows &rows, int n, const double 
 template <class Rows>
 __device__ __forceinline__ void batch_solve(const BatchSolveArgs &a, const Rows &rows, int n, int m,
                                             unsigned long long absmax_bits) {
-    // (the order of the carve below is restated by batch_solve_price / batch_solve_p2o above, for the kernel that reads
-    // the final state behind this function: k_ell_outside_solve, k_dense_outside_solve.  Change both together.)
+    // (the order of the carve below is restated by batch_solve_price / batch_solve_p2o above, for batch_outside_outputs,
+    // which reads the final state behind this function.  Change both together.)
     extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
     __shared__ int s_holes, s_nmove, s_fail;
     const int b = blockIdx.x, tid = threadIdx.x, T = blockDim.x, lane = lane_id(), wave = tid >> 6, nw = T >> 6;

@@ -167,17 +167,6 @@ __global__ __launch_bounds__(256) void k_dense_outside_check(DenseOutsideCheckAr
                                a.outside_ld, a.aug);
 }
 
-// The outside option of the rows of one problem (DenseBatchRows<T, true>): row i's value is O[i * stride] (stride 0: one
-// value for the problem).  Empty in the plain mode.
-template <bool Out>
-struct DenseOutside {};
-template <>
-struct DenseOutside<true> {
-    const double *O;
-    int stride;
-    __device__ __forceinline__ double value(int i) const { return O[i * stride]; }
-};
-
 // The dense row source of batch_solve: problem b's slice A (row stride M) of n x m, its reference M and valid count.
 // The bid's staging array `vals` belongs to k_dense_batch_solve: declared in bid() it is promoted to a vector while bid()
 // is optimised on its own, and every staging step then zeroes the rest of it (measured: 3.8 % more kernel time at
@@ -195,7 +184,7 @@ struct DenseBatchRows {
     int m, maximize, mref;
     unsigned long long nvalid;
     T *vals;  // [kDenseBatchCols]
-    DenseOutside<Out> out{};
+    BatchOutside<Out> out{};
 
     __device__ __forceinline__ Top2 bid(int i, const double *price, double &costbest, int &obj) const {
         const int lane = lane_id();
@@ -219,14 +208,7 @@ struct DenseBatchRows {
                 const double v = dense_widen(vals[q]);
                 const double cost = maximize ? v : v * -1.0;  // :236-237
                 const double vi = cost - price[c];
-                if (vi >= x.v) {  // :351 (the first entry is always taken: vi >= -inf for every non-NaN vi)
-                    x.w = x.v;
-                    x.v = vi;
-                    x.g = c;
-                    cb = cost;
-                } else if (vi > x.w) {
-                    x.w = vi;
-                }
+                if (top2_take(x, vi, c)) cb = cost;
             }
         }
         if constexpr (Out) {
@@ -234,14 +216,7 @@ struct DenseBatchRows {
                 const double v = out.value(i);
                 const double cost = maximize ? v : v * -1.0;
                 const double vi = cost - price[m + i];
-                if (vi >= x.v) {
-                    x.w = x.v;
-                    x.v = vi;
-                    x.g = m + i;
-                    cb = cost;
-                } else if (vi > x.w) {
-                    x.w = vi;
-                }
+                if (top2_take(x, vi, m + i)) cb = cost;
             }
         }
         const Top2 r = top2_wave_reduce(x);
@@ -347,19 +322,13 @@ __global__ __launch_bounds__(1024) void k_dense_batch_solve_status(DenseBatchSta
     const DenseBatchCheck ck = a.d.chk[b];
     const int card = a.card && n >= 1 ? a.card[b] : -1;
     const int code = batch_verdict(dense_batch_verdict(ck, n), a.card != nullptr, card, n, ck.bad_price);
-    if (threadIdx.x == 0) {
-        a.status[b] = code;
-        if (a.matching_size) a.matching_size[b] = card;
-    }
+    batch_publish_verdict(a.status, a.matching_size, b, code, card);
     if (code != MISSLAP_BATCH_STATUS_OK) {
         batch_condemn(a.d.s, n, ck.mref, (long long)ck.nvalid);
         return;
     }
     BatchSolveArgs s = a.d.s;
-    if (a.fast) {  // the front-end's (1.0 / float64(n)).astype(float32): the same two IEEE operations
-        s.eps_b = nullptr;
-        s.eps_opt = (float)(1.0 / (double)n);
-    }
+    if (a.fast) batch_fast_eps(s, n);
     T vals[kDenseBatchCols];
     const DenseBatchRows<T> rows{static_cast<const T *>(a.d.mat) + (size_t)b * (size_t)a.d.N * (size_t)a.d.M, a.d.M, m,
                                  s.maximize, ck.mref, ck.nvalid, vals};
@@ -387,8 +356,7 @@ __device__ __forceinline__ int dense_outside_verdict(const DenseBatchCheck &c, i
 }
 
 // The solve of the outside mode: the verdict, batch_solve on the n x (m + n) problem, then the outputs in the caller's
-// terms from the LDS state batch_solve leaves (nothing writes price[] or p2o[] behind its last barrier, and every thread
-// rewrites only the sol cells it wrote itself).
+// terms (batch_outside_outputs).
 template <class T>
 __global__ __launch_bounds__(1024) void k_dense_outside_solve(DenseOutsideArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
@@ -397,26 +365,17 @@ __global__ __launch_bounds__(1024) void k_dense_outside_solve(DenseOutsideArgs a
     const int n = d.shapes[2 * b], m = d.shapes[2 * b + 1];
     const DenseBatchCheck ck = d.chk[b];
     const int code = batch_verdict(dense_outside_verdict(ck, n), false, -1, n, ck.bad_price);
-    if (tid == 0) {
-        a.t.status[b] = code;
-        if (a.t.matching_size) a.t.matching_size[b] = -1;
-    }
+    batch_publish_verdict(a.t.status, a.t.matching_size, b, code, -1);
     const int N = (int)d.N, M = (int)d.M;
     double *po = a.prices ? a.prices + (size_t)b * (size_t)M : nullptr;
     double *oo = a.outside_prices ? a.outside_prices + (size_t)b * (size_t)N : nullptr;
     if (code != MISSLAP_BATCH_STATUS_OK) {
         batch_condemn(d.s, n, m + n, (long long)ck.nvalid + n);
-        if (po)
-            for (int j = tid; j < M; j += nt) po[j] = 0.0;
-        if (oo)
-            for (int i = tid; i < N; i += nt) oo[i] = 0.0;
+        batch_outside_condemn(po, M, oo, N, tid, nt);
         return;
     }
     BatchSolveArgs s = d.s;
-    if (a.t.fast) {
-        s.eps_b = nullptr;
-        s.eps_opt = (float)(1.0 / (double)n);
-    }
+    if (a.t.fast) batch_fast_eps(s, n);
     T vals[kDenseBatchCols];
     const double *O = a.outside + (a.outside_ld ? (size_t)b * (size_t)a.outside_ld : (size_t)b);
     const DenseBatchRows<T, true> rows{static_cast<const T *>(d.mat) + (size_t)b * (size_t)d.N * (size_t)d.M,
@@ -428,15 +387,7 @@ __global__ __launch_bounds__(1024) void k_dense_outside_solve(DenseOutsideArgs a
                                        vals,
                                        {O, a.outside_ld ? 1 : 0}};
     batch_solve(s, rows, n, m + n, ck.absmax_bits);
-    const double *price = batch_solve_price(s_raw);
-    const int *p2o = batch_solve_p2o(s_raw, s.Ns, s.Ms);
-    int *sol = d.s.sol + (size_t)b * (size_t)d.s.sol_ld;
-    for (int i = tid; i < n; i += nt)
-        if (p2o[i] >= m) sol[i] = -1;
-    if (po)
-        for (int j = tid; j < M; j += nt) po[j] = j < m ? price[j] : 0.0;
-    if (oo)
-        for (int i = tid; i < N; i += nt) oo[i] = i < n ? price[m + i] : 0.0;
+    batch_outside_outputs(s_raw, d.s, b, n, m, M, N, po, oo, tid, nt);
 }
 
 }  // namespace misslap

@@ -1,5 +1,6 @@
 // kernels_ell_batch.hpp -- many small sparse problems given as padded candidate lists (ELL), one workgroup per problem
-// for its whole solve (misslap_solve_ell_batch, include/misslap.h; the host side is abi_ell_batch.hpp).
+// for its whole solve (misslap_solve_ell_batch, include/misslap.h; the host side is abi_ell_batch.hpp, for the outside
+// mode abi_ell_batch_outside.hpp).
 //
 // The round loop is batch_solve (kernels_batch_solve.hpp); this file has the check pass, the ELL row source and the
 // solve with its verdict.  The input is what a top-k, a gating step or a nearest-neighbour search leaves on the device:
@@ -164,17 +165,6 @@ __global__ __launch_bounds__(256) void k_ell_outside_check(EllOutsideCheckArgs a
                                 a.p0_ld, a.out, a.outside, a.outside_ld, a.aug, a.aug_ld, a.Ms);
 }
 
-// The outside option of the rows of one problem (EllBatchRows<I, V, true>): row i's value is O[i * stride] (stride 0: one
-// value for the problem), its object is m + i.  Empty in the plain mode.
-template <bool Out>
-struct EllOutside {};
-template <>
-struct EllOutside<true> {
-    const double *O;
-    int stride, m;
-    __device__ __forceinline__ double value(int i) const { return O[i * stride]; }
-};
-
 // The ELL row source of batch_solve: problem b's slices C / A (at (size_t)b * N * K, formed in 64 bits), row i at slot
 // i * K of them (an int: the host caps N * K at INT_MAX - 128).  Every valid column is below the carve's Ms once the
 // verdict is 0, so an int64 column narrows safely.
@@ -187,7 +177,8 @@ struct EllBatchRows {
     const V *A;
     int K, maximize;
     unsigned long long nvalid;
-    EllOutside<Out> out;
+    int m;  // the real columns (read in the outside mode only)
+    BatchOutside<Out> out;
 
     // the row in slot order, lane l at slots l, l + 64, ...; the tie key is the slot index
     __device__ __forceinline__ Top2 bid(int i, const double *price, double &costbest, int &obj) const {
@@ -206,29 +197,19 @@ struct EllBatchRows {
             const double v = dense_widen(e);
             const double cost = maximize ? v : v * -1.0;  // :236-237
             const double vi = cost - price[(int)c];
-            if (vi >= x.v) {  // :351 (the first entry is always taken: vi >= -inf for every non-NaN vi)
-                x.w = x.v;
-                x.v = vi;
-                x.g = q;
+            if (top2_take(x, vi, q)) {
                 cb = cost;
                 cj = (int)c;
-            } else if (vi > x.w) {
-                x.w = vi;
             }
         }
         if constexpr (Out) {
             if (lane == (K & (kWave - 1))) {
                 const double v = out.value(i);
                 const double cost = maximize ? v : v * -1.0;
-                const double vi = cost - price[out.m + i];
-                if (vi >= x.v) {
-                    x.w = x.v;
-                    x.v = vi;
-                    x.g = K;
+                const double vi = cost - price[m + i];
+                if (top2_take(x, vi, K)) {
                     cb = cost;
-                    cj = out.m + i;
-                } else if (vi > x.w) {
-                    x.w = vi;
+                    cj = m + i;
                 }
             }
         }
@@ -248,7 +229,7 @@ struct EllBatchRows {
             if (C[g0 + q] == (I)j) last = q;
         last = wave_max_i32(last);
         double vj;
-        if constexpr (Out) vj = j >= out.m ? out.value(i) : dense_widen(A[g0 + (last < 0 ? 0 : last)]);
+        if constexpr (Out) vj = j >= m ? out.value(i) : dense_widen(A[g0 + (last < 0 ? 0 : last)]);
         else vj = dense_widen(A[g0 + last]);
         const double choice_cost = maximize ? vj : vj * -1.0;
         const double LHS = choice_cost - price[j] + tol;  // :475
@@ -257,7 +238,7 @@ struct EllBatchRows {
             if (lane == 0) {
                 const double v = out.value(i);
                 const double cost = maximize ? v : v * -1.0;
-                if (LHS < (cost - price[out.m + i]) - eps) bad = true;
+                if (LHS < (cost - price[m + i]) - eps) bad = true;
             }
         }
         for (int q = lane; q < K; q += kWave) {
@@ -278,7 +259,7 @@ struct EllBatchRows {
             const int j = p2o[i];
             if (j < 0) continue;
             if constexpr (Out) {
-                if (j >= out.m) {  // the row's outside entry: exactly one match
+                if (j >= m) {  // the row's outside entry: exactly one match
                     if (lane == 0) {
                         nsel[i] = 1;
                         selv[i] = out.value(i);
@@ -351,26 +332,20 @@ __global__ __launch_bounds__(1024) void k_ell_batch_solve(EllBatchArgs a) {
     const int card = a.card ? a.card[b] : -1;
     const int own = ell_batch_verdict(ck, a.s.Ms, a.s.p0_ld, a.s.p0 != nullptr);
     const int code = batch_verdict(own, a.card != nullptr, card, ck.n, ck.bad_price);
-    if (threadIdx.x == 0) {
-        a.status[b] = code;
-        if (a.matching_size) a.matching_size[b] = card;
-    }
+    batch_publish_verdict(a.status, a.matching_size, b, code, card);
     if (code != MISSLAP_BATCH_STATUS_OK) {
         batch_condemn(a.s, ck.n, sparse_batch_count(ck.max_col), (long long)ck.nvalid);
         return;
     }
     BatchSolveArgs bs = a.s;
-    if (a.fast) {  // the front-end's (1.0 / float64(N)).astype(float32) with N = n_b: the same two IEEE operations
-        bs.eps_b = nullptr;
-        bs.eps_opt = (float)(1.0 / (double)ck.n);
-    }
+    if (a.fast) batch_fast_eps(bs, ck.n);
     const size_t base = (size_t)b * (size_t)a.N * (size_t)a.K;
     const I *C = static_cast<const I *>(a.cols) + base;
     const V *A = static_cast<const V *>(a.vals) + base;
     // (the two slice pointers as opaque scalars: left to itself the compiler also keeps base * sizeof(I) and
     // base * sizeof(V) alive for the objective's scalar re-walk, and those four registers are the ones that spill)
     asm volatile("" : "+s"(C), "+s"(A));
-    const EllBatchRows<I, V> rows{C, A, (int)a.K, bs.maximize, ck.nvalid, {}};
+    const EllBatchRows<I, V> rows{C, A, (int)a.K, bs.maximize, ck.nvalid, ck.max_col + 1, {}};
     batch_solve(bs, rows, ck.n, ck.max_col + 1, ck.absmax_bits);
 }
 
@@ -386,8 +361,7 @@ struct EllOutsideArgs {
 };
 
 // The solve of the outside mode: the verdict without EMPTY_ROW and INFEASIBLE (neither can occur), batch_solve on the
-// n x (m + n) problem, then the outputs in the caller's terms from the LDS state batch_solve leaves (nothing writes
-// price[] or p2o[] behind its last barrier, and every thread rewrites only the sol cells it wrote itself).
+// n x (m + n) problem, then the outputs in the caller's terms (batch_outside_outputs).
 template <class I, class V>
 __global__ __launch_bounds__(1024) void k_ell_outside_solve(EllOutsideArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
@@ -395,45 +369,28 @@ __global__ __launch_bounds__(1024) void k_ell_outside_solve(EllOutsideArgs a) {
     const EllBatchCheck ck = a.e.chk[b];
     const int own = ell_batch_verdict(ck, a.Mmax, a.p0_ld, a.e.s.p0 != nullptr);
     const int code = batch_verdict(own, false, -1, ck.n, ck.bad_price);
-    if (tid == 0) {
-        a.e.status[b] = code;
-        if (a.e.matching_size) a.e.matching_size[b] = -1;
-    }
+    batch_publish_verdict(a.e.status, a.e.matching_size, b, code, -1);
     const int N = (int)a.e.N;
     double *po = a.prices ? a.prices + (size_t)b * (size_t)a.Mmax : nullptr;
     double *oo = a.outside_prices ? a.outside_prices + (size_t)b * (size_t)N : nullptr;
     if (code != MISSLAP_BATCH_STATUS_OK) {
         const long long mc = (long long)sparse_batch_count(ck.max_col) + ck.n;
         batch_condemn(a.e.s, ck.n, (int)(mc < INT_MAX ? mc : INT_MAX), (long long)ck.nvalid + ck.n);
-        if (po)
-            for (int j = tid; j < a.Mmax; j += T) po[j] = 0.0;
-        if (oo)
-            for (int i = tid; i < N; i += T) oo[i] = 0.0;
+        batch_outside_condemn(po, a.Mmax, oo, N, tid, T);
         return;
     }
     BatchSolveArgs bs = a.e.s;
-    if (a.e.fast) {
-        bs.eps_b = nullptr;
-        bs.eps_opt = (float)(1.0 / (double)ck.n);
-    }
+    if (a.e.fast) batch_fast_eps(bs, ck.n);
     const size_t base = (size_t)b * (size_t)a.e.N * (size_t)a.e.K;
     const I *C = static_cast<const I *>(a.e.cols) + base;
     const V *A = static_cast<const V *>(a.e.vals) + base;
     asm volatile("" : "+s"(C), "+s"(A));
     const int n = ck.n, m = ck.max_col + 1;
     const double *O = a.outside + (a.outside_ld ? (size_t)b * (size_t)a.outside_ld : (size_t)b);
-    const EllBatchRows<I, V, true> rows{C, A, (int)a.e.K, bs.maximize, ck.nvalid + (unsigned long long)n,
-                                        {O, a.outside_ld ? 1 : 0, m}};
+    const EllBatchRows<I, V, true> rows{C, A, (int)a.e.K, bs.maximize, ck.nvalid + (unsigned long long)n, m,
+                                        {O, a.outside_ld ? 1 : 0}};
     batch_solve(bs, rows, n, m + n, ck.absmax_bits);
-    const double *price = batch_solve_price(s_raw);
-    const int *p2o = batch_solve_p2o(s_raw, bs.Ns, bs.Ms);
-    int *sol = a.e.s.sol + (size_t)b * (size_t)a.e.s.sol_ld;
-    for (int i = tid; i < n; i += T)
-        if (p2o[i] >= m) sol[i] = -1;
-    if (po)
-        for (int j = tid; j < a.Mmax; j += T) po[j] = j < m ? price[j] : 0.0;
-    if (oo)
-        for (int i = tid; i < N; i += T) oo[i] = i < n ? price[m + i] : 0.0;
+    batch_outside_outputs(s_raw, a.e.s, b, n, m, a.Mmax, N, po, oo, tid, T);
 }
 
 }  // namespace misslap

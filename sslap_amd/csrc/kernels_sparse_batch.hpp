@@ -277,19 +277,13 @@ __global__ __launch_bounds__(1024) void k_sparse_batch_solve_status(SparseBatchS
     const int card = a.card ? a.card[b] : -1;
     const int own = sparse_batch_verdict(ck, nnz, N, a.fast, card, a.d.s.Ns, a.d.s.Ms, a.d.s.p0_ld, a.d.s.p0 != nullptr);
     const int code = batch_verdict(own, false, 0, 0, ck.bad_price);
-    if (threadIdx.x == 0) {
-        a.status[b] = code;
-        if (a.matching_size) a.matching_size[b] = card;
-    }
+    batch_publish_verdict(a.status, a.matching_size, b, code, card);
     if (code != MISSLAP_BATCH_STATUS_OK) {
         batch_condemn(a.d.s, sparse_batch_count(ck.max_row), sparse_batch_count(ck.max_col), nnz);
         return;
     }
     BatchSolveArgs bs = a.d.s;
-    if (a.fast) {  // the front-end's (1.0 / float64(N)).astype(float32): the same two IEEE operations
-        bs.eps_b = nullptr;
-        bs.eps_opt = (float)(1.0 / (double)N);
-    }
+    if (a.fast) batch_fast_eps(bs, (double)N);
     const SparseBatchRows rows{a.d.loc, a.d.val, a.d.offsets, s, a.d.row_start + s + b, bs.maximize};
     batch_solve(bs, rows, ck.last_row + 1, ck.max_col + 1, ck.absmax_bits);
 }

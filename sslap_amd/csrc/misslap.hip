@@ -17,6 +17,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <mutex>
 #include <thread>
 #include <string>
@@ -509,6 +510,7 @@ MISSLAP_API int misslap_get_state(misslap_solver *h, double *prices, int32_t *un
 #include "abi_diag.hpp"
 #include "abi_warm.hpp"
 #include "abi_batch_common.hpp"
+#include "abi_batch_stream.hpp"
 #include "abi_dense_batch.hpp"
 #include "abi_dense_batch_status.hpp"
 #include "abi_dense_batch_outside.hpp"
@@ -516,3 +518,4 @@ MISSLAP_API int misslap_get_state(misslap_solver *h, double *prices, int32_t *un
 #include "abi_sparse_batch_status.hpp"
 #include "abi_matching_batch.hpp"
 #include "abi_ell_batch.hpp"
+#include "abi_ell_batch_outside.hpp"
