@@ -38,7 +38,8 @@ extern "C" {
  *      had to be 0 = MISSLAP_DTYPE_F64 until then; size and offsets of the struct did not change),
  *      misslap_solve_ell_batch, misslap_ell_batch_workspace_bytes, misslap_solve_ell_batch_outside,
  *      misslap_ell_batch_outside_workspace_bytes, misslap_solve_dense_batch_outside,
- *      misslap_dense_batch_outside_workspace_bytes (with MISSLAP_BATCH_STATUS_BAD_OUTSIDE, code 15). */
+ *      misslap_dense_batch_outside_workspace_bytes (with MISSLAP_BATCH_STATUS_BAD_OUTSIDE, code 15),
+ *      misslap_solve_sparse_batch_outside, misslap_sparse_batch_outside_workspace_bytes. */
 
 /* misslap_options.mat_dtype: the element type of a dense stack */
 #define MISSLAP_DTYPE_F64 0   /* double */
@@ -719,6 +720,66 @@ int misslap_solve_sparse_batch_status(int64_t B, const int32_t *loc, const doubl
  * check records, the nnz + B row starts and, with cardinality_check, the cardinalities, each 256-byte aligned); -1 for
  * B < 1 or nnz < 0.  Needs no GPU.  has_prices is accepted for the day a layout depends on it: today's does not. */
 int64_t misslap_sparse_batch_workspace_bytes(int64_t B, int64_t nnz, int32_t has_prices, int32_t cardinality_check);
+
+/* ---- the sparse batch with an outside option per row: partial assignments from packed loc / val, the layout a radius
+ * or chi-square gate leaves (ragged rows).  Problem b is the entries offsets[b] .. offsets[b + 1] in stored order, duplicates
+ * of an (i, j) kept, plus ONE entry per row, stored last in its row: row i (i < n_b) gets (i, m_b + i) with the row's
+ * outside value -- with opt->maximize = 0 the cost of leaving row i unmatched, else the value of doing so.  n_b is
+ * sizes[b][1] where sizes is given, else the last stored row + 1; m_b is the largest real column + 1, 0 for a problem
+ * without an entry; sizes[b][0] is not read.  Rows WITHOUT ANY ENTRY are legal -- in front, in the middle, and behind the
+ * last stored row when sizes names them -- and so is a problem with offsets[b + 1] == offsets[b], provided sizes names its
+ * rows.  The object m_b + i is private to row i, so every row can always be assigned.  The result of problem b is bit for
+ * bit the reference's from_sparse(loc_b, val_b, size=(m_b + n_b, n_b)).solve() on that packing (with prices_in: started
+ * from [prices_in[b][:m_b], zeros(n_b)]), given in the caller's terms exactly as misslap_solve_ell_batch_outside gives it:
+ *   sol[b][i]              int32[B][Nmax]: the real column of row i, or -1 where the row took its outside option (and
+ *                          beyond n_b, on a condemned problem, and where max_iter cut the solve short)
+ *   prices_out             double[B][Mmax] or NULL: the prices of the real columns, 0 beyond m_b
+ *   outside_prices_out     double[B][Nmax] or NULL: the price of row i's outside object, 0 beyond n_b (+inf for a row
+ *                          without any real entry: a one-entry row of the reference bids +inf)
+ *   meta[b]                the augmented problem's record: n_rows = n_b, n_cols = m_b + n_b, nnz = nnz_b + n_b
+ *   outside, outside_ld    outside_ld == 0: double[B], one value per problem; outside_ld >= Nmax: double[B][outside_ld],
+ *                          the value of row i at outside[b * outside_ld + i]; anything else is MISSLAP_ERR_INVALID.  Only
+ *                          the values of rows < min(n_b, Nmax) are read.  Where loc / val live (host, or device with
+ *                          opt->input_on_device).
+ *   fast                   != 0: problem b starts at eps = (float)(1.0 / (double)n_b), formed in the kernel.
+ * The checks, in their order:
+ *    8 NO_ENTRIES            offsets[b + 1] == offsets[b] and sizes is NULL
+ *   10 NEGATIVE_INDEX        a negative row or column index
+ *   11 ROWS_UNSORTED         a row index below the one stored before it
+ *    7 BAD_SHAPE             sizes given and sizes[b][1] < max(1, last stored row + 1)
+ *    3 INFINITE_VALUE        a NaN or an infinity in val, or in the outside value of a row < min(n_b, Nmax)
+ *   13 TOO_LARGE             n_b > Nmax or m_b > Mmax (a column index whose + 1 does not fit an int32 included)
+ *   14 PRICES_TOO_NARROW     prices_in given and prices_ld < m_b
+ *    5 PRICE_NOT_FINITE, 6 PRICE_NEGATIVE   over prices_in[b][:m_b]
+ * Codes 1, 2, 4, 9, 12 and 15 never occur: graphs without a complete matching and n_b > m_b are solved.  No guard is
+ * launched and matching_size[b] (may be NULL) is -1.  A problem with a status other than 0 has sol -1, prices_out 0,
+ * outside_prices_out 0 and meta[b] = {n_rows = n_b, n_cols = m_b + n_b (each saturated at INT32_MAX), nnz = nnz_b + n_b,
+ * every other result field 0} behind the codes 3, 13, 14, 5 and 6, and an all-zero record behind 8, 10, 11 and 7.  Its
+ * workgroup leaves before any LDS state exists and before it reads a row start, a loc or a val of the problem.
+ * Nmax and Mmax (1 .. MISSLAP_SPARSE_BATCH_MAX_DIM) bound the rows and the REAL columns; the LDS carve is sized for Nmax
+ * rows and Mmax + Nmax objects (155 648 bytes at 2048 / 2048).  No kernel of the call reads outside offsets[b] ..
+ * offsets[b + 1] of loc / val, or writes outside the problem's own Nmax + 1 row starts of the workspace and its own rows
+ * of the outputs.  offsets, offsets_dev, sizes, prices_in, prices_ld, opt, stream, workspace, workspace_bytes,
+ * out_on_device, status, meta and info are misslap_solve_sparse_batch_status's, in both of its modes: with a workspace
+ * (misslap_sparse_batch_outside_workspace_bytes) every pointer except offsets, opt and info is a device pointer and the
+ * call enqueues two launches (check, solve with verdict) on `stream` and waits for nothing; without one the library
+ * uploads host arrays, uses its own scratch and synchronises once.
+ * On eps: see misslap_solve_ell_batch_outside below -- a single phase (fast != 0, or 0 < eps_start <= 1 / n_b) from zero
+ * prices is optimal within n_b * eps; the reference's eps-scaling is not, on a rectangular problem.
+ * Only what is wrong with the whole call is an error: B, offsets, Nmax, Mmax, outside_ld, prices_ld < 1, a NULL loc / val
+ * (with entries) / sol / status / outside, the options, a workspace that is too small or misaligned. */
+int misslap_solve_sparse_batch_outside(int64_t B, const int32_t *loc, const double *val, const int64_t *offsets,
+                                       const int64_t *offsets_dev, const int64_t *sizes, int32_t fast,
+                                       const double *prices_in, int64_t prices_ld, const misslap_options *opt, void *stream,
+                                       void *workspace, int64_t workspace_bytes, int64_t Nmax, int64_t Mmax,
+                                       const double *outside, int64_t outside_ld, int32_t *sol, double *prices_out,
+                                       double *outside_prices_out, int32_t out_on_device, int32_t *status,
+                                       int32_t *matching_size, misslap_dense_batch_meta *meta,
+                                       misslap_dense_batch_info *info);
+/* Bytes of workspace a stream-ordered misslap_solve_sparse_batch_outside needs: the check records, B x (Nmax + 1) row
+ * starts and, with has_prices, the staged starting prices of the augmented problems (B x (Mmax + Nmax) doubles), each
+ * 256-byte aligned; -1 where B, Nmax or Mmax are out of range.  Needs no GPU. */
+int64_t misslap_sparse_batch_outside_workspace_bytes(int64_t B, int64_t Nmax, int64_t Mmax, int32_t has_prices);
 
 /* ---- the sparse batch from padded candidate lists (ELL), the layout a top-k, a gating step or a nearest-neighbour
  * search leaves on the device: cols[B][N][K] (int32, or int64 with cols_int64 != 0) and vals[B][N][K] (double, or float

@@ -201,6 +201,11 @@ SYMBOLS = {
                                                     C.POINTER(Options), _VP, _VP, C.c_int64, C.c_int64, C.c_int64, _VP, _VP,
                                                     C.c_int32, _VP, _VP, _VP, C.POINTER(DenseBatchInfo)]),
     "misslap_sparse_batch_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
+    "misslap_solve_sparse_batch_outside": (C.c_int, [C.c_int64, _VP, _VP, _VP, _VP, _VP, C.c_int32, _VP, C.c_int64,
+                                                     C.POINTER(Options), _VP, _VP, C.c_int64, C.c_int64, C.c_int64, _VP,
+                                                     C.c_int64, _VP, _VP, _VP, C.c_int32, _VP, _VP, _VP,
+                                                     C.POINTER(DenseBatchInfo)]),
+    "misslap_sparse_batch_outside_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64, C.c_int32]),
     "misslap_solve_ell_batch": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, _VP, C.c_int32, _VP, _VP, C.c_int32, _VP, C.c_int64,
                                           C.c_int32, C.POINTER(Options), _VP, _VP, C.c_int64, C.c_int64, _VP, _VP, C.c_int32,
                                           _VP, _VP, _VP, C.POINTER(DenseBatchInfo)]),

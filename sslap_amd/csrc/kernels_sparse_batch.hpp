@@ -15,6 +15,17 @@
 //            overwrites it on every match), then every stored entry is tested against it (:475-485).
 //   get_obj  every stored entry whose column is p2o[i] is added, in row order and stored order (:508-521): a
 //            duplicate of the chosen entry counts once per copy.
+//
+// The outside mode (misslap_solve_sparse_batch_outside; the <true> instances below; the host side is
+// abi_sparse_batch_outside.hpp): row i of problem b also holds one virtual entry (i, m_b + i), stored LAST in its row,
+// whose value is the row's outside value -- a private object that only row i can bid for, so a row may stay unmatched
+// and a row may have no stored entry at all.  n_b is sizes[b][1] (without sizes the last stored row + 1), m_b the
+// largest real column + 1; the problem solved is the n_b x (m_b + n_b) packed problem, the round loop is batch_solve
+// unchanged on a carve of Mmax + Nmax objects.  The row starts live in a block of Nmax + 1 ints per problem (n_b may
+// exceed nnz_b, so the plain mode's nnz_b + 1 slots do not fit) and a row gap is legal: the check pass fills the starts
+// of the empty rows too.  The row source presents the virtual entry (tie key len, above every stored index), the check
+// pass folds the outside values into C = max |v| and the non-finite flag, and the solve kernel rewrites the outputs
+// behind batch_solve as the ELL outside mode does (batch_outside_outputs).
 #pragma once
 
 namespace misslap {
@@ -29,7 +40,7 @@ struct SparseBatchCheck {
     int last_row;   // row of the last stored entry (AuctionSolver's N - 1 with rows ascending, :209)
     int err;        // kErrColNegative / kErrRowsUnsorted / kErrRowGap / kErrNonFinite, as k_ingest_rows / _vals set them
     int bad_price;  // starting prices: bit 0 NaN / infinity, bit 1 sign bit set
-    int pad;
+    int n;          // the outside mode: n_b = sizes[b][1] clamped to -1 .. INT_MAX, without sizes last_row + 1; else 0
 };
 
 struct SparseBatchArgs {
@@ -45,13 +56,21 @@ struct SparseBatchArgs {
 // same rules), the maxima of from_sparse (:594-595) and of the guard (n_true, m_true), C = max |v|, the starting prices,
 // and the row starts.  A row start is written only where the rows seen so far are gap-free (r <= local index), so a
 // malformed problem never writes outside its own nnz_b + 1 slots.
-__global__ __launch_bounds__(256) void k_sparse_batch_check(const int *loc, const double *val, const long long *offsets,
-                                                            const double *p0, long long p0_ld, int *row_start,
-                                                            SparseBatchCheck *out) {
+// Out (the outside mode): rs is the problem's own block of Ns + 1 row starts.  The thread that sees the row change
+// rp -> r at local index k fills rs[rp + 1 .. r] = k (the rows rp + 1 .. r - 1 are empty), thread 0 fills
+// rs[last_row + 1 .. n_b] = nnz_b; every index written is clamped to 0 .. Ns, so a malformed or oversized problem stays
+// within its block.  No row gap is reported.  The outside values of the rows < min(n_b, Ns) (ov: outside[b] with
+// ov_ld == 0, else outside[b * ov_ld + i]; ov_ld >= Ns) count as an entry's value does, and with starting prices the
+// augmented start [p0[:m_b], zeros(n_b)] is staged at aug[b * aug_ld ..] (aug_ld = Ms + Ns) -- only where the verdict
+// can still be 0 (no error, 1 <= n_b <= Ns, m_b <= Ms and m_b <= p0_ld, so m_b + n_b <= aug_ld).
+template <bool Out>
+__device__ __forceinline__ void sparse_batch_check(const int *loc, const double *val, const long long *offsets,
+                                                   const double *p0, long long p0_ld, int *rs, SparseBatchCheck *out,
+                                                   const long long *sizes, const double *ov, long long ov_ld,
+                                                   double *aug, long long aug_ld, int Ns, int Ms) {
     const int b = blockIdx.x;
     const long long s = offsets[b], e = offsets[b + 1];
     const int nnz = (int)(e - s);  // (the host rejects problems of 2^31 - 1 entries or more)
-    int *rs = row_start + s + b;
     __shared__ unsigned long long s_abs;
     __shared__ int s_err, s_maxr, s_maxc, s_badp;
     if (threadIdx.x == 0) {
@@ -65,6 +84,23 @@ __global__ __launch_bounds__(256) void k_sparse_batch_check(const int *loc, cons
     const int last_row = nnz > 0 ? loc[2 * (e - 1)] : -1;
     int err = 0, mr = INT_MIN, mc = INT_MIN;
     unsigned long long am = 0ull;
+    int n = 0;  // the outside mode's n_b
+    if constexpr (Out) {
+        if (sizes) {
+            const long long v = sizes[2 * b + 1];
+            n = (int)(v < -1 ? -1 : (v > INT_MAX ? INT_MAX : v));
+        } else {
+            n = last_row < 0 ? 0 : (last_row == INT_MAX ? INT_MAX : last_row + 1);
+        }
+        const int nr = n < Ns ? n : Ns;  // the rows whose outside value is read
+        for (int i = threadIdx.x; i < (ov_ld ? nr : (nr > 0 ? 1 : 0)); i += blockDim.x) {
+            const unsigned long long bits =
+                (unsigned long long)__double_as_longlong(ov[ov_ld ? (size_t)b * (size_t)ov_ld + (size_t)i : (size_t)b]) &
+                0x7fffffffffffffffull;
+            if (bits >= 0x7ff0000000000000ull) err |= kErrNonFinite;
+            am = bits > am ? bits : am;
+        }
+    }
     for (int k = threadIdx.x; k < nnz; k += blockDim.x) {
         const long long g = s + k;
         const int r = loc[2 * g], c = loc[2 * g + 1];
@@ -80,8 +116,13 @@ __global__ __launch_bounds__(256) void k_sparse_batch_check(const int *loc, cons
         const int rp = k ? loc[2 * (g - 1)] : -1;
         if (r < rp) err |= kErrRowsUnsorted;
         else if (r > rp) {
-            if (r != rp + 1 || r > last_row) err |= kErrRowGap;
-            else if (r <= k) rs[r] = k;  // (r > k implies a gap earlier in the problem)
+            if constexpr (Out) {
+                const int hi = r < Ns ? r : Ns;
+                for (int i = rp < 0 ? 0 : rp + 1; i <= hi; ++i) rs[i] = k;
+            } else {
+                if (r != rp + 1 || r > last_row) err |= kErrRowGap;
+                else if (r <= k) rs[r] = k;  // (r > k implies a gap earlier in the problem)
+            }
         }
     }
     if (err) atomicOr(&s_err, err);
@@ -89,12 +130,28 @@ __global__ __launch_bounds__(256) void k_sparse_batch_check(const int *loc, cons
     if (mc != INT_MIN) atomicMax(&s_maxc, mc);
     if (am) atomicMax(&s_abs, am);
     __syncthreads();
-    const int m = s_maxc + 1;  // n_cols (only meaningful without errors)
-    if (p0 && s_err == 0 && m > 0)  // (the host rejects m > p0_ld)
-        batch_check_prices(p0 + (size_t)b * (size_t)p0_ld, (long long)m < p0_ld ? m : (int)p0_ld, &s_badp);
+    if constexpr (Out) {
+        const long long m = s_maxc < 0 ? 0 : (long long)s_maxc + 1;  // m_b (0 without an entry)
+        if (p0 && s_err == 0 && m > 0)
+            batch_check_prices(p0 + (size_t)b * (size_t)p0_ld, (int)(m < p0_ld ? m : p0_ld), &s_badp);
+        if (p0 && s_err == 0 && n >= 1 && n <= Ns && m <= (long long)Ms && m <= p0_ld) {
+            const double *src = p0 + (size_t)b * (size_t)p0_ld;
+            double *dst = aug + (size_t)b * (size_t)aug_ld;
+            for (int j = threadIdx.x; j < (int)m + n; j += blockDim.x) dst[j] = j < (int)m ? src[j] : 0.0;
+        }
+    } else {
+        const int m = s_maxc + 1;  // n_cols (only meaningful without errors)
+        if (p0 && s_err == 0 && m > 0)  // (the host rejects m > p0_ld)
+            batch_check_prices(p0 + (size_t)b * (size_t)p0_ld, (long long)m < p0_ld ? m : (int)p0_ld, &s_badp);
+    }
     __syncthreads();
     if (threadIdx.x == 0) {
-        if (last_row >= 0 && last_row < nnz) rs[last_row + 1] = nnz;  // :47
+        if constexpr (Out) {
+            const int hi = n < Ns ? n : Ns;
+            for (int i = last_row < 0 ? 0 : (last_row < Ns ? last_row + 1 : Ns + 1); i <= hi; ++i) rs[i] = nnz;
+        } else {
+            if (last_row >= 0 && last_row < nnz) rs[last_row + 1] = nnz;  // :47
+        }
         SparseBatchCheck c;
         c.absmax_bits = s_abs;
         c.max_row = s_maxr;
@@ -102,12 +159,46 @@ __global__ __launch_bounds__(256) void k_sparse_batch_check(const int *loc, cons
         c.last_row = last_row;
         c.err = s_err;
         c.bad_price = s_badp;
-        c.pad = 0;
+        c.n = n;
         out[b] = c;
     }
 }
 
+__global__ __launch_bounds__(256) void k_sparse_batch_check(const int *loc, const double *val, const long long *offsets,
+                                                            const double *p0, long long p0_ld, int *row_start,
+                                                            SparseBatchCheck *out) {
+    sparse_batch_check<false>(loc, val, offsets, p0, p0_ld, row_start + offsets[blockIdx.x] + blockIdx.x, out, nullptr,
+                              nullptr, 0, nullptr, 0, 0, 0);
+}
+
+struct SparseOutsideCheckArgs {
+    const int *loc;
+    const double *val;
+    const long long *offsets, *sizes;  // sizes: [B][2] or null
+    const double *p0;
+    long long p0_ld;
+    int *row_start;  // [B][Nmax + 1]
+    SparseBatchCheck *out;
+    const double *outside;  // [B] (outside_ld == 0) or [B][outside_ld], outside_ld >= Nmax
+    long long outside_ld;
+    double *aug;            // [B][aug_ld] or null (no starting prices)
+    long long aug_ld;       // Mmax + Nmax
+    int Nmax, Mmax;         // the bounds on the rows and on the real columns
+};
+
+__global__ __launch_bounds__(256) void k_sparse_outside_check(SparseOutsideCheckArgs a) {
+    sparse_batch_check<true>(a.loc, a.val, a.offsets, a.p0, a.p0_ld,
+                             a.row_start + (size_t)blockIdx.x * ((size_t)a.Nmax + 1), a.out, a.sizes, a.outside,
+                             a.outside_ld, a.aug, a.aug_ld, a.Nmax, a.Mmax);
+}
+
 // The sparse row source of batch_solve: problem b's entries from global index s, row i at s + rs[i] .. s + rs[i + 1].
+// Out: the row's virtual last entry (i, m + i) with the row's outside value.  Its tie key is len, above every stored
+// index, and lane len & 63 takes it AFTER its own stored indices (index len would be that lane's next one), so every
+// lane still scans in ascending stored order, the virtual entry wins ">=" ties as the last stored entry must, and the
+// winner's lane is r.g & 63 as before.  A row of len = 0 is a one-entry row: its second best is -inf and it bids +inf.
+// A chosen object j >= m is that entry: nothing of loc / val is read for it.
+template <bool Out = false>
 struct SparseBatchRows {
     const int *loc;
     const double *val;
@@ -115,6 +206,8 @@ struct SparseBatchRows {
     long long s;
     const int *rs;
     int maximize;
+    int m, n;  // the real columns and the rows (read in the outside mode only)
+    BatchOutside<Out> out;
 
     // the row in stored order, lane l at stored indices l, l + 64, ...; the tie key is the stored index
     __device__ __forceinline__ Top2 bid(int i, const double *price, double &costbest, int &obj) const {
@@ -142,6 +235,17 @@ struct SparseBatchRows {
                 x.w = vi;
             }
         }
+        if constexpr (Out) {
+            if (lane == (len & (kWave - 1))) {
+                const double v = out.value(i);
+                const double cost = maximize ? v : v * -1.0;
+                const double vi = cost - price[m + i];
+                if (top2_take(x, vi, len)) {
+                    cb = cost;
+                    cj = m + i;
+                }
+            }
+        }
         const Top2 r = top2_wave_reduce(x);
         const int gl = r.g & (kWave - 1);  // the lane that holds stored index r.g
         costbest = readlane_f64(cb, gl);
@@ -158,10 +262,19 @@ struct SparseBatchRows {
         for (int q = lane; q < len; q += kWave)
             if (loc[2 * (g0 + q) + 1] == j) last = q;
         last = wave_max_i32(last);
-        const double vj = val[g0 + last];
+        double vj;
+        if constexpr (Out) vj = j >= m ? out.value(i) : val[g0 + (last < 0 ? 0 : last)];  // (j < m: stored, last >= 0)
+        else vj = val[g0 + last];
         const double choice_cost = maximize ? vj : vj * -1.0;
         const double LHS = choice_cost - price[j] + tol;  // :475
         bool bad = false;
+        if constexpr (Out) {
+            if (lane == 0) {
+                const double v = out.value(i);
+                const double cost = maximize ? v : v * -1.0;
+                if (LHS < (cost - price[m + i]) - eps) bad = true;
+            }
+        }
         for (int q = lane; q < len; q += kWave) {
             const double v = val[g0 + q];
             const double cost = maximize ? v : v * -1.0;
@@ -177,6 +290,15 @@ struct SparseBatchRows {
         for (int i = wave; i < n; i += nw) {
             const int j = p2o[i];
             if (j < 0) continue;
+            if constexpr (Out) {
+                if (j >= m) {  // the row's outside entry: exactly one match
+                    if (lane == 0) {
+                        nsel[i] = 1;
+                        selv[i] = out.value(i);
+                    }
+                    continue;
+                }
+            }
             const long long g0 = s + rs[i];
             const int len = rs[i + 1] - rs[i];
             int cnt = 0, at = -1;
@@ -218,15 +340,18 @@ struct SparseBatchRows {
         return obj;
     }
 
-    __device__ __forceinline__ int meta_cols(int m) const { return m; }
-    __device__ __forceinline__ int64_t meta_nnz() const { return (int64_t)(offsets[blockIdx.x + 1] - s); }
+    // (m_: batch_solve's object count, in the outside mode m + n)
+    __device__ __forceinline__ int meta_cols(int m_) const { return m_; }
+    __device__ __forceinline__ int64_t meta_nnz() const {
+        return (int64_t)(offsets[blockIdx.x + 1] - s) + (Out ? (int64_t)n : 0);
+    }
 };
 
 __global__ __launch_bounds__(1024) void k_sparse_batch_solve(SparseBatchArgs a) {
     const int b = blockIdx.x;
     const SparseBatchCheck ck = a.chk[b];
     const long long s = a.offsets[b];
-    const SparseBatchRows rows{a.loc, a.val, a.offsets, s, a.row_start + s + b, a.s.maximize};
+    const SparseBatchRows<> rows{a.loc, a.val, a.offsets, s, a.row_start + s + b, a.s.maximize, 0, 0, {}};
     batch_solve(a.s, rows, ck.last_row + 1, ck.max_col + 1, ck.absmax_bits);
 }
 
@@ -284,8 +409,78 @@ __global__ __launch_bounds__(1024) void k_sparse_batch_solve_status(SparseBatchS
     }
     BatchSolveArgs bs = a.d.s;
     if (a.fast) batch_fast_eps(bs, (double)N);
-    const SparseBatchRows rows{a.d.loc, a.d.val, a.d.offsets, s, a.d.row_start + s + b, bs.maximize};
+    const SparseBatchRows<> rows{a.d.loc, a.d.val, a.d.offsets, s, a.d.row_start + s + b, bs.maximize, 0, 0, {}};
     batch_solve(bs, rows, ck.last_row + 1, ck.max_col + 1, ck.absmax_bits);
+}
+
+// ---- outside mode (misslap_solve_sparse_batch_outside): an outside option per row, for partial assignments
+
+struct SparseOutsideArgs {
+    SparseBatchArgs d;       // d.s.Ns / Ms = Nmax / Mmax + Nmax (the carve), d.s.p0 / p0_ld the staged augmented prices,
+                             // d.s.prices null, d.row_start [B][Nmax + 1]
+    const long long *sizes;  // [B][2] or null: n_b = sizes[b][1] (sizes[b][0] is not read)
+    int fast;                // eps_start = 1 / n_b of each problem
+    int *status;             // [B] MISSLAP_BATCH_STATUS_*
+    int *matching_size;      // [B] or null: always -1 (no guard in this mode)
+    const double *outside;   // [B] (outside_ld == 0) or [B][outside_ld]
+    long long outside_ld;
+    double *prices;          // [B][Mmax] or null: the real columns
+    double *outside_prices;  // [B][Nmax] or null
+    int Mmax;                // the bound on the real columns
+    long long p0_ld;         // of the caller's starting prices (the PRICES_TOO_NARROW check)
+};
+
+// The checks of an outside-mode verdict ahead of the starting prices, in their order (include/misslap.h); batch_verdict
+// adds the prices.  A row gap is legal, a problem without entries too once sizes names its rows; TOO_FEW_VALUES,
+// EMPTY_ROW, INFEASIBLE, DIVISION_BY_ZERO, ROW_GAP and BAD_OUTSIDE never occur.
+__device__ __forceinline__ int sparse_outside_verdict(const SparseBatchCheck &c, long long nnz, bool has_sizes, int Ns,
+                                                      int Ms, long long p0_ld, bool has_p0) {
+    if (nnz == 0 && !has_sizes) return MISSLAP_BATCH_STATUS_NO_ENTRIES;
+    if (c.err & kErrColNegative) return MISSLAP_BATCH_STATUS_NEGATIVE_INDEX;
+    if (c.err & kErrRowsUnsorted) return MISSLAP_BATCH_STATUS_ROWS_UNSORTED;
+    // (from here on no index is negative and the rows ascend: last_row = max_row >= -1)
+    if (has_sizes && (c.n < 1 || (long long)c.n < (long long)c.last_row + 1)) return MISSLAP_BATCH_STATUS_BAD_SHAPE;
+    if (c.err & kErrNonFinite) return MISSLAP_BATCH_STATUS_INFINITE_VALUE;
+    if (c.n > Ns || sparse_batch_count(c.max_col) > Ms) return MISSLAP_BATCH_STATUS_TOO_LARGE;
+    if (has_p0 && sparse_batch_count(c.max_col) > p0_ld) return MISSLAP_BATCH_STATUS_PRICES_TOO_NARROW;
+    return MISSLAP_BATCH_STATUS_OK;
+}
+
+// The solve of the outside mode: the verdict from what the check pass left on the device, batch_solve on the
+// n x (m + n) problem, then the outputs in the caller's terms (batch_outside_outputs).  A condemned problem's workgroup
+// writes the defined outputs and leaves before any LDS state exists and before a row start, a loc or a val of its
+// problem is read.  Its record holds n_b, m_b + n_b and nnz_b + n_b where the verdict is one behind which they are
+// defined (3, 13, 14, 5, 6), and zeros otherwise.
+__global__ __launch_bounds__(1024) void k_sparse_outside_solve(SparseOutsideArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
+    const int b = blockIdx.x, tid = threadIdx.x, T = blockDim.x;
+    const SparseBatchCheck ck = a.d.chk[b];
+    const long long s = a.d.offsets[b];
+    const long long nnz = a.d.offsets[b + 1] - s;
+    const int Nmax = a.d.s.Ns;
+    const int own = sparse_outside_verdict(ck, nnz, a.sizes != nullptr, Nmax, a.Mmax, a.p0_ld, a.d.s.p0 != nullptr);
+    const int code = batch_verdict(own, false, -1, 0, ck.bad_price);
+    batch_publish_verdict(a.status, a.matching_size, b, code, -1);
+    double *po = a.prices ? a.prices + (size_t)b * (size_t)a.Mmax : nullptr;
+    double *oo = a.outside_prices ? a.outside_prices + (size_t)b * (size_t)Nmax : nullptr;
+    if (code != MISSLAP_BATCH_STATUS_OK) {
+        const bool counted = code == MISSLAP_BATCH_STATUS_INFINITE_VALUE || code == MISSLAP_BATCH_STATUS_TOO_LARGE ||
+                             code == MISSLAP_BATCH_STATUS_PRICES_TOO_NARROW ||
+                             code == MISSLAP_BATCH_STATUS_PRICE_NOT_FINITE || code == MISSLAP_BATCH_STATUS_PRICE_NEGATIVE;
+        const long long mc = (long long)sparse_batch_count(ck.max_col) + ck.n;
+        batch_condemn(a.d.s, counted ? ck.n : 0, counted ? (int)(mc < INT_MAX ? mc : INT_MAX) : 0,
+                      counted ? nnz + ck.n : 0);
+        batch_outside_condemn(po, a.Mmax, oo, Nmax, tid, T);
+        return;
+    }
+    BatchSolveArgs bs = a.d.s;
+    const int n = ck.n, m = ck.max_col < 0 ? 0 : ck.max_col + 1;
+    if (a.fast) batch_fast_eps(bs, n);
+    const double *O = a.outside + (a.outside_ld ? (size_t)b * (size_t)a.outside_ld : (size_t)b);
+    const SparseBatchRows<true> rows{a.d.loc, a.d.val, a.d.offsets, s, a.d.row_start + (size_t)b * ((size_t)Nmax + 1),
+                                     bs.maximize, m, n, {O, a.outside_ld ? 1 : 0}};
+    batch_solve(bs, rows, n, m + n, ck.absmax_bits);
+    batch_outside_outputs(s_raw, a.d.s, b, n, m, a.Mmax, Nmax, po, oo, tid, T);
 }
 
 }  // namespace misslap

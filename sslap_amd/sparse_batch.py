@@ -4,6 +4,11 @@ The batch form of `auction_solve(loc=, val=, size=)`: problem b of a packed (loc
 launch, and its result is exactly what `from_sparse(loc_b, val_b, size=sizes[b], ...).solve()` returns
 (csrc/kernels_batch_solve.hpp, csrc/kernels_sparse_batch.hpp).  The reference has no counterpart; it solves one
 problem per AuctionSolver.
+
+With `outside` every row also holds an outside option, so a row may stay unmatched (a partial assignment) and a row may
+have no entry at all: problem b is its packed entries plus one entry (i, m_b + i) per row i < n_b, stored last in its
+row, and its result is the reference's on that n_b x (m_b + n_b) problem (misslap_solve_sparse_batch_outside).
+`sparse_to_augmented` is the definition; it is the one `ell_to_packed(outside=)` gives for the ELL layout.
 """
 import ctypes as C
 
@@ -96,6 +101,46 @@ def _check_input(loc, val, offsets):
     return B, nnz, off, on_device
 
 
+def sparse_to_augmented(loc, val, offsets, sizes=None, outside=0.):
+    """numpy packed loc (nnz, 2) / val (nnz,) / offsets (B + 1,) -> [(loc_b int32, val_b float64, m_b, n_b)]: the
+    definition of auction_solve_sparse_batch(outside=).  n_b = sizes[b, 1] where sizes is given, else the last stored
+    row + 1; m_b = the largest real column + 1, 0 for a problem without an entry (sizes[b, 0] is not read).  The problem's
+    own entries are kept in stored order, duplicates of an (i, j) included, and every row i < n_b -- a row without any
+    other entry included -- gets one more entry (i, m_b + i), stored last in its row, whose value is the row's outside
+    value.  outside: a float, float64 (B,) or float64 (B, P) with P >= every n_b.  Problem b is then
+    auction_solve(loc=loc_b, val=val_b, size=(m_b + n_b, n_b), cardinality_check=False).  Rows must ascend."""
+    loc, val, off = np.asarray(loc), np.asarray(val, dtype=np.float64), np.asarray(offsets, dtype=np.int64)
+    if loc.ndim != 2 or loc.shape[1] != 2 or val.shape != (loc.shape[0],):
+        raise ValueError(f"loc must have shape (nnz, 2) and val (nnz,), got {loc.shape} and {val.shape}")
+    if off.ndim != 1 or off.shape[0] < 2 or off[0] != 0 or off[-1] != loc.shape[0] or (np.diff(off) < 0).any():
+        raise ValueError("offsets must have length B + 1, start at 0, end at nnz and not decrease")
+    B = off.shape[0] - 1
+    szs = None if sizes is None else np.asarray(sizes)
+    if szs is not None and szs.shape != (B, 2):
+        raise ValueError(f"sizes must have shape ({B}, 2), got {szs.shape}")
+    o = np.asarray(outside, dtype=np.float64)
+    if o.ndim > 2 or (o.ndim >= 1 and o.shape[0] != B):
+        raise ValueError(f"outside must be a float or have shape ({B},) or ({B}, P), got {o.shape}")
+    out = []
+    for b in range(B):
+        lb, vb = loc[off[b]:off[b + 1]].astype(np.int64), val[off[b]:off[b + 1]]
+        n = int(szs[b, 1]) if szs is not None else (int(lb[-1, 0]) + 1 if len(lb) else 0)
+        m = int(lb[:, 1].max()) + 1 if len(lb) else 0
+        if len(lb) and ((np.diff(lb[:, 0]) < 0).any() or lb[0, 0] < 0 or lb[-1, 0] >= n):
+            raise ValueError(f"problem {b}: rows must ascend within 0 .. n_b - 1 = {n - 1}")
+        if o.ndim == 2 and o.shape[1] < n:
+            raise ValueError(f"outside holds {o.shape[1]} rows per problem, problem {b} has {n}")
+        ob = np.broadcast_to(o if o.ndim == 0 else o[b] if o.ndim == 1 else o[b, :n], (n,))
+        # behind the last stored entry of row i: a stable sort by row, the outside entries after the stored ones
+        rows = np.concatenate([lb[:, 0], np.arange(n, dtype=np.int64)])
+        order = np.argsort(rows, kind="stable")
+        cols = np.concatenate([lb[:, 1], m + np.arange(n, dtype=np.int64)])[order]
+        vals = np.concatenate([vb, ob])[order]
+        out.append((np.ascontiguousarray(np.stack([rows[order], cols], axis=1), dtype=np.int32),
+                    np.ascontiguousarray(vals, dtype=np.float64), m, n))
+    return out
+
+
 def _check_sizes(sizes, B):
     if sizes is None:
         return None
@@ -105,8 +150,8 @@ def _check_sizes(sizes, B):
     return np.ascontiguousarray(s, dtype=np.int64)
 
 
-def auction_solve_sparse_batch(loc, val=None, offsets=None, problem="min", eps_start=0., max_iter=1000000, fast=False,
-                               sizes=None, cardinality_check=True, prices=None, errors="raise", dims=None):
+def auction_solve_sparse_batch(loc, val=None, offsets=None, problem="min", eps_start=0., max_iter=1000000, fast=None,
+                               sizes=None, cardinality_check=True, prices=None, errors="raise", dims=None, outside=None):
     """Solve B independent sparse problems in one call, one workgroup per problem.
 
     loc: int32 (nnz, 2) and val: float64 (nnz,), both numpy arrays or both contiguous tensors on the device (read in place,
@@ -144,10 +189,40 @@ def auction_solve_sparse_batch(loc, val=None, offsets=None, problem="min", eps_s
     (batch_meta_to_host(res) gives the default mode's meta dict).  With dims it waits for nothing and copies nothing
     back; without dims the maxima of loc are read back once before the call, the mode's only wait.  offsets stays a host
     array; sizes and prices may be host arrays (sent from pinned memory without a wait), prices also a device tensor.
+
+    outside: partial assignments (misslap_solve_sparse_batch_outside).  A finite float, float64 (B,) or float64 (B, P)
+    with P >= Nmax -- a numpy array or, with device input, a tensor on loc's device ((B,) contiguous; (B, P) with unit
+    stride along a row, so a slice of a wider buffer is taken in place): the outside value of every row, in the units of
+    val (problem="min": the cost of leaving row i unmatched; "max": the value of doing so).  It may be negative.  Problem
+    b is then its packed entries plus one entry (i, m_b + i) per row i < n_b, stored last in its row, with n_b =
+    sizes[b, 1] (without sizes the last stored row + 1) and m_b = the largest real column + 1 (sizes[b, 0] is not read);
+    its result is bit for bit auction_solve(loc=loc_b, val=val_b, size=(m_b + n_b, n_b), cardinality_check=False) on
+    sparse_to_augmented(loc, val, offsets, sizes, outside); with prices the solve starts from [p0[:m_b], zeros(n_b)].
+    A ROW WITHOUT ANY ENTRY IS LEGAL -- leading, in the middle, or trailing when sizes names it -- and so is a problem
+    without entries whose rows sizes names; graphs without a complete matching and n_b > m_b are solved.  The result is
+    the status-mode dict: sol[b, i] is the real column, or -1 where row i took its outside option (and beyond n_b, on a
+    condemned problem, or where max_iter cut the solve); prices stays (B, Mmax), the real columns; the new key
+    outside_prices is float64 (B, Nmax), the price of row i's outside object and 0 beyond n_b (+inf for a row without
+    any real entry: a one-entry row of the reference bids +inf).  meta is the augmented problem's record (n_rows = n_b,
+    n_cols = m_b + n_b, nnz = nnz_b + n_b).  matching_size is -1: no guard is launched and cardinality_check is not
+    consulted.  The checks, in their order: NO_ENTRIES (no entries and no sizes), NEGATIVE_INDEX, ROWS_UNSORTED,
+    BAD_SHAPE (sizes[b, 1] < max(1, last row + 1)), INFINITE_VALUE (a NaN or an infinity in val or in the outside value of
+    a row < min(n_b, Nmax)), TOO_LARGE (n_b > Nmax or m_b > Mmax), PRICES_TOO_NARROW, PRICE_NOT_FINITE, PRICE_NEGATIVE.
+    A condemned problem has sol -1, prices 0, outside_prices 0.  Both values of errors run the same stream-ordered call;
+    "raise" (the default) then raises ValueError("problem <b>: ...") for the first status that is not 0, and dims= is taken
+    with either.  Without dims, Nmax = max(largest row + 1, largest sizes[:, 1]) and Mmax = max(largest column + 1, 1), each
+    capped at MISSLAP_SPARSE_BATCH_MAX_DIM: the mode's single read-back with device input.  With device loc / val /
+    outside and dims the call enqueues two launches on the current stream, waits for nothing and reads nothing back; a
+    host outside travels from pinned memory as sizes and prices do.
+
+    fast=None (default) is False without outside (the call is what it always was) and with outside True, unless
+    eps_start > 0 was given (then False); an explicit fast= or eps_start= is passed through.  fast=True means
+    eps = 1 / n_b.  Why: the augmented problem is rectangular, where the reference's eps-scaling is not optimal in general
+    and a single phase from zero prices is (README "Rectangular problems").
     """
     if errors not in ("raise", "status"):
         raise ValueError(f"errors must be 'raise' or 'status', got {errors!r}")
-    if dims is not None and errors != "status":
+    if dims is not None and errors != "status" and outside is None:
         raise ValueError("dims is taken with errors='status' only")
     if isinstance(loc, (list, tuple)):
         if val is not None or offsets is not None:
@@ -159,6 +234,15 @@ def auction_solve_sparse_batch(loc, val=None, offsets=None, problem="min", eps_s
     e = float(eps_start)
     if e != e:
         raise ValueError("eps_start is NaN")
+    if outside is not None:
+        if fast is None:  # (resolved here: the library gets a plain flag)
+            fast = not e > 0
+        res = _solve_outside(loc, val, B, nnz, off, on_device, problem, e, max_iter, fast, szs, prices, dims, outside)
+        if errors == "raise":
+            from .dense_batch import raise_for_status
+            raise_for_status(res)
+        return res
+    fast = bool(fast)  # (None: False, the call is what it was)
     if errors == "status":
         return _solve_status(loc, val, B, nnz, off, on_device, problem, e, max_iter, fast, szs, cardinality_check, prices,
                              dims)
@@ -274,9 +358,139 @@ def _solve_status(loc, val, B, nnz, off, on_device, problem, e, max_iter, fast, 
                 stream=stream, keep=(work, loc, val, d_off, d_sizes, d_p), **common)
 
 
+def _check_outside(outside, B, on_device, dev):
+    """The outside values of a call, before Nmax is known: a finite float (broadcast to (B,) where the input lives), or
+    float64 (B,) / (B, P) on the host or (with device input) on loc's device, a row of it with unit stride.  Returns
+    (array or tensor, P or 0 for one value per problem, outside_ld)."""
+    if _is_device_tensor(outside):
+        import torch
+        if not on_device:
+            raise TypeError("outside on the device needs loc / val on the device")
+        if outside.dtype != torch.float64:
+            raise ValueError(f"outside must be float64, got {outside.dtype}")
+        if outside.dim() not in (1, 2) or int(outside.shape[0]) != B or (outside.dim() == 2 and int(outside.shape[1]) < 1):
+            raise ValueError(f"outside must have shape ({B},) or ({B}, P), got {tuple(outside.shape)}")
+        if outside.device != dev:
+            raise ValueError(f"outside is on {outside.device}, loc on {dev}")
+        if outside.dim() == 1:
+            if not outside.is_contiguous():
+                raise ValueError("a device outside tensor of shape (B,) must be contiguous (it is read in place)")
+            return outside, 0, 0
+        P = int(outside.shape[1])
+        ld = int(outside.stride(0)) if B > 1 else P
+        if (P > 1 and outside.stride(1) != 1) or ld < P:
+            raise ValueError("a device outside tensor of shape (B, P) must have unit stride along a row and rows that do "
+                             "not overlap (it is read in place)")
+        return outside, P, ld
+    if isinstance(outside, np.ndarray):
+        if outside.dtype != np.float64:
+            raise ValueError(f"outside must be float64, got {outside.dtype.name}")
+        if outside.ndim not in (1, 2) or outside.shape[0] != B or (outside.ndim == 2 and outside.shape[1] < 1):
+            raise ValueError(f"outside must have shape ({B},) or ({B}, P), got {outside.shape}")
+        o = np.ascontiguousarray(outside)
+        return o, (o.shape[1] if o.ndim == 2 else 0), (o.shape[1] if o.ndim == 2 else 0)
+    if isinstance(outside, (bool, str, bytes)) or not isinstance(outside, (int, float, np.integer, np.floating)):
+        raise TypeError("outside must be a float, a float64 numpy array or a float64 tensor on the device")
+    x = float(outside)
+    if not np.isfinite(x):
+        raise ValueError(f"outside must be finite, got {x!r}")
+    if on_device:
+        import torch
+        return torch.full((B,), x, dtype=torch.float64, device=dev), 0, 0
+    return np.full(B, x, dtype=np.float64), 0, 0
+
+
+def _solve_outside(loc, val, B, nnz, off, on_device, problem, e, max_iter, fast, szs, prices, dims, outside):
+    """outside= of auction_solve_sparse_batch (misslap_solve_sparse_batch_outside), in either mode."""
+    dev = loc.device if on_device else None
+    out_v, P, out_ld = _check_outside(outside, B, on_device, dev)
+    p = _status_prices(prices, B, on_device, loc)  # (a host array, or with device input possibly a device tensor)
+    if dims is not None:
+        Nmax, Mmax = _check_dims(dims)
+    else:  # (with device input this is the mode's one read-back)
+        max_row, max_col, _ = _maxima(loc, off, on_device, per_problem=False)
+        n_sized = int(szs[:, 1].max()) if szs is not None else 0
+        Nmax, Mmax = min(max(max_row + 1, n_sized, 1), MAX_DIM), min(max(max_col + 1, 1), MAX_DIM)
+    if P and P < Nmax:
+        raise ValueError(f"outside must have shape ({B},) or ({B}, P) with P >= Nmax = {Nmax}, got P = {P}")
+    opts = _solve_options(on_device, loc, problem, e, max_iter)
+    lib = _lib.load()
+    fast = 1 if fast else 0
+    common = dict(layout="sparse", dims=(Nmax, Mmax), sizes=szs, offsets=off, loc=loc,
+                  prices_ld=0 if p is None else int(p.shape[1]))
+    if not on_device:  # synchronous: the library uploads, uses its own scratch and waits once
+        lc, vc = np.ascontiguousarray(loc), np.ascontiguousarray(val)
+        sol, pout = np.empty((B, Nmax), dtype=np.int32), np.empty((B, Mmax), dtype=np.float64)
+        oout = np.empty((B, Nmax), dtype=np.float64)
+        status, msize = np.empty(B, dtype=np.int32), np.empty(B, dtype=np.int32)
+        metas, info = _new_meta(B)
+        _lib.check(lib.misslap_solve_sparse_batch_outside(
+            B, lc.ctypes.data, vc.ctypes.data, off.ctypes.data, None, None if szs is None else szs.ctypes.data, fast,
+            None if p is None else p.ctypes.data, common["prices_ld"], C.byref(opts), None, None, 0, Nmax, Mmax,
+            out_v.ctypes.data, out_ld, sol.ctypes.data, pout.ctypes.data, oout.ctypes.data, 0, status.ctypes.data,
+            msize.ctypes.data, C.cast(metas, C.c_void_p), C.byref(info)))
+        return dict(sol=sol, prices=pout, outside_prices=oout, status=status, matching_size=msize,
+                    meta=_decode_meta(metas, info), **common)
+    import torch
+    from .dense_batch import _meta_views
+
+    def send(a):  # a host array from pinned memory, without a wait (torch takes no read-only array: a copy then)
+        if a is None:
+            return None
+        return torch.from_numpy(a if a.flags.writeable else a.copy()).pin_memory().to(dev, non_blocking=True)
+    with torch.cuda.device(dev):  # (the allocations and copies below are made on the current stream of loc's device)
+        stream = torch.cuda.current_stream(dev)
+        d_off, d_sizes = send(off), send(szs)
+        d_p = send(p) if isinstance(p, np.ndarray) else p
+        d_out = send(out_v) if isinstance(out_v, np.ndarray) else out_v
+        nbytes = int(lib.misslap_sparse_batch_outside_workspace_bytes(B, Nmax, Mmax, 0 if p is None else 1))
+        work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        sol = torch.empty((B, Nmax), dtype=torch.int32, device=dev)
+        pout = torch.empty((B, Mmax), dtype=torch.float64, device=dev)
+        oout = torch.empty((B, Nmax), dtype=torch.float64, device=dev)
+        status = torch.empty(B, dtype=torch.int32, device=dev)
+        msize = torch.empty(B, dtype=torch.int32, device=dev)
+        rec = torch.empty((B, C.sizeof(_lib.DenseBatchMeta)), dtype=torch.uint8, device=dev)
+    info = _lib.DenseBatchInfo()
+    _lib.check(lib.misslap_solve_sparse_batch_outside(
+        B, loc.data_ptr(), val.data_ptr(), off.ctypes.data, d_off.data_ptr(), None if d_sizes is None else d_sizes.data_ptr(),
+        fast, None if d_p is None else d_p.data_ptr(), common["prices_ld"], C.byref(opts),
+        C.c_void_p(int(stream.cuda_stream)), work.data_ptr(), nbytes, Nmax, Mmax, d_out.data_ptr(), out_ld, sol.data_ptr(),
+        pout.data_ptr(), oout.data_ptr(), 1, status.data_ptr(), msize.data_ptr(), rec.data_ptr(), C.byref(info)))
+    # the workspace and the inputs stay referenced by the result: nothing of this call is recycled before it
+    return dict(sol=sol, prices=pout, outside_prices=oout, status=status, matching_size=msize, meta=_meta_views(rec),
+                records=rec, info=info, stream=stream, keep=(work, loc, val, d_off, d_sizes, d_p, d_out), **common)
+
+
+def _outside_error(res, b, code, n, m):
+    """The exception of problem b of an outside-mode result (n, m: the record's n_rows and n_cols, m counting the n outside
+    objects too)."""
+    Nmax, Mmax = res["dims"]
+    if m < _INT_MAX:
+        m -= n
+    if code == _lib.BATCH_STATUS_NO_ENTRIES:
+        text = "no entries (and no sizes to name its rows)"
+    elif code == _lib.BATCH_STATUS_NEGATIVE_INDEX:
+        text = "loc holds a negative row or column index"
+    elif code == _lib.BATCH_STATUS_BAD_SHAPE:
+        text = f"sizes[{b}, 1] = {int(res['sizes'][b, 1])}: at least 1 and at least the last stored row + 1"
+    elif code == _lib.BATCH_STATUS_INFINITE_VALUE:
+        text = "val holds a NaN or an infinity (in an entry or in the outside value of a row)"
+    elif code == _lib.BATCH_STATUS_TOO_LARGE:
+        if m >= _INT_MAX:
+            text = "column index too large (max + 1 must fit an int32)"
+        else:
+            text = f"{n} x {m} does not fit dims = ({Nmax}, {Mmax})"
+    else:
+        text = _STATUS_TEXT[code].format(N=n, n=n, m=m, card=-1, P=res["prices_ld"])
+    return ValueError(f"problem {b}: {text}")
+
+
 def _status_error(res, b, code, n, m, card):
     """The exception of problem b of a sparse status-mode result: what the default mode with cardinality_check=False
     raises for the same check (n, m: the record's n_rows and n_cols; card: its matching_size)."""
+    if "outside_prices" in res:
+        return _outside_error(res, b, code, n, m)
     if code == _lib.BATCH_STATUS_DIVISION_BY_ZERO:
         return ZeroDivisionError(f"problem {b}: division by zero")
     Nmax, Mmax = res["dims"]

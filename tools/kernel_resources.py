@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Register / LDS / spill numbers of every kernel of the library, from hipcc -Rpass-analysis=kernel-resource-usage
-(runs without a GPU).  usage: kernel_resources.py [substring ...] [-- extra hipcc flags]"""
+(runs without a GPU).  usage: kernel_resources.py [substring ...] [-- extra hipcc flags]
+The batch solves and their guards: `kernel_resources.py batch ell matching sparse_outside` (k_dense_* / k_sparse_batch_* /
+k_ell_* / k_matching_batch*, the outside modes k_dense_outside_* / k_ell_outside_* and k_sparse_outside_check / _solve)."""
 import os
 import re
 import subprocess
