@@ -39,7 +39,9 @@ extern "C" {
  *      misslap_solve_ell_batch, misslap_ell_batch_workspace_bytes, misslap_solve_ell_batch_outside,
  *      misslap_ell_batch_outside_workspace_bytes, misslap_solve_dense_batch_outside,
  *      misslap_dense_batch_outside_workspace_bytes (with MISSLAP_BATCH_STATUS_BAD_OUTSIDE, code 15),
- *      misslap_solve_sparse_batch_outside, misslap_sparse_batch_outside_workspace_bytes. */
+ *      misslap_solve_sparse_batch_outside, misslap_sparse_batch_outside_workspace_bytes,
+ *      misslap_solve_dense_batch_status_strided, misslap_solve_dense_batch_outside_strided,
+ *      misslap_matching_dense_batch_strided. */
 
 /* misslap_options.mat_dtype: the element type of a dense stack */
 #define MISSLAP_DTYPE_F64 0   /* double */
@@ -618,6 +620,42 @@ int misslap_solve_dense_batch_outside(int64_t B, int64_t N, int64_t M, const voi
  * aligned; -1 for B < 1 or N, M outside 1 .. MISSLAP_DENSE_BATCH_MAX_DIM.  Needs no GPU. */
 int64_t misslap_dense_batch_outside_workspace_bytes(int64_t B, int64_t N, int64_t M, int32_t has_prices);
 
+/* ---- the dense batch on a strided stack: a transposed view, a slice of a wider buffer, an expanded matrix, read where
+ * it lies.  misslap_solve_dense_batch_status_strided and misslap_solve_dense_batch_outside_strided are
+ * misslap_solve_dense_batch_status and misslap_solve_dense_batch_outside with three more arguments behind B, N, M: the
+ * strides of the stack in ELEMENTS of opt->mat_dtype.  mat points at the view's first element, and entry (i, j) of
+ * problem b is mat[b * stride_b + i * stride_n + j * stride_m]; shapes refer to the view.  Every other argument, both
+ * modes of the call (with and without a workspace), the workspace size (misslap_dense_batch_workspace_bytes /
+ * misslap_dense_batch_outside_workspace_bytes: strides do not change it) and every output are those of the contiguous
+ * call, and the result is bit for bit that call's on a compact copy of the view.
+ *   strides        each >= 0, and (B - 1) * stride_b + (N - 1) * stride_n + (M - 1) * stride_m must fit 62 bits: anything
+ *                  else is MISSLAP_ERR_INVALID, before a device is touched.  0 is allowed (stride_b = 0: one matrix solved
+ *                  B times, from different starting prices or outside values), and the strides need not be ordered
+ *                  (stride_n = 1: a transposed view).  Offsets are formed in 64 bits.  The strides of the contiguous stack
+ *                  (N * M, M, 1) take the contiguous call's kernels.
+ *   mat            a DEVICE pointer, aligned to its element only: opt->input_on_device must be set (MISSLAP_ERR_INVALID
+ *                  otherwise; a host stack is uploaded whole, so it is compact).  Only elements of the view are read --
+ *                  nothing beyond m_b in a row, no row >= n_b, nothing of the storage between the view's elements -- and
+ *                  nothing is written, copied or converted.
+ * The kernels are a family of their own with run-time strides (csrc/kernels_dense_batch.hpp); any layout is correct, and
+ * two are fast: stride_m == 1 (the lane map of the contiguous bid with stride_n as the row stride), and stride_n == 1,
+ * where rounds of many bidders bid one lane per person so that a load is coalesced across persons. */
+int misslap_solve_dense_batch_status_strided(int64_t B, int64_t N, int64_t M, int64_t stride_b, int64_t stride_n,
+                                             int64_t stride_m, const void *mat, const int32_t *shapes, int32_t fast,
+                                             const double *prices_in, int32_t cardinality_check,
+                                             const misslap_options *opt, void *stream, void *workspace,
+                                             int64_t workspace_bytes, int32_t *sol, double *prices_out,
+                                             int32_t out_on_device, int32_t *status, int32_t *matching_size,
+                                             misslap_dense_batch_meta *meta, misslap_dense_batch_info *info);
+int misslap_solve_dense_batch_outside_strided(int64_t B, int64_t N, int64_t M, int64_t stride_b, int64_t stride_n,
+                                              int64_t stride_m, const void *mat, const int32_t *shapes, int32_t fast,
+                                              const double *prices_in, const misslap_options *opt, void *stream,
+                                              void *workspace, int64_t workspace_bytes, const double *outside,
+                                              int64_t outside_ld, int32_t *sol, double *prices_out,
+                                              double *outside_prices_out, int32_t out_on_device, int32_t *status,
+                                              int32_t *matching_size, misslap_dense_batch_meta *meta,
+                                              misslap_dense_batch_info *info);
+
 /* ---- many small SPARSE problems in one call: the batch form of _from_sparse(loc, val, size=...) (auction_.pyx:575-617).
  * loc is int32[nnz][2] and val double[nnz]; problem b is the entries offsets[b] .. offsets[b + 1] (offsets: host
  * int64[B + 1], offsets[0] = 0, non-decreasing, offsets[B] = nnz), its row and column indices its own and 0-based, read
@@ -917,6 +955,15 @@ int misslap_matching_dense_batch(int64_t B, int64_t N, int64_t M, const double *
                                  const misslap_options *opt, int32_t *size, int32_t *n_rows, int32_t *n_cols,
                                  int32_t *left_pairings, int64_t left_ld, int32_t *right_pairings, int64_t right_ld,
                                  int32_t out_on_device, misslap_matching_batch_info *info);
+/* misslap_matching_dense_batch on a strided stack: entry (i, j) of graph b is mat[b * stride_b + i * stride_n +
+ * j * stride_m], strides in elements of opt->mat_dtype under the rules of misslap_solve_dense_batch_status_strided
+ * (>= 0, the extent within 62 bits, mat a device pointer with opt->input_on_device set).  Everything else, the pairings
+ * included, is misslap_matching_dense_batch on a compact copy of the view. */
+int misslap_matching_dense_batch_strided(int64_t B, int64_t N, int64_t M, int64_t stride_b, int64_t stride_n,
+                                         int64_t stride_m, const void *mat, const int32_t *shapes,
+                                         const misslap_options *opt, int32_t *size, int32_t *n_rows, int32_t *n_cols,
+                                         int32_t *left_pairings, int64_t left_ld, int32_t *right_pairings,
+                                         int64_t right_ld, int32_t out_on_device, misslap_matching_batch_info *info);
 
 const char *misslap_last_error(void);
 int misslap_abi_version(void);

@@ -40,9 +40,9 @@ def _mat_dtype_name(mat_dtype):
 
 
 def _check_stack(mats, mat_dtype="float64"):
-    """dtype / rank / layout of a (B, N, M) stack of mat_dtype (numpy array or device tensor); returns (B, N, M,
-    on_device, the MISSLAP_DTYPE_* code).  The stack must have exactly that dtype: nothing is converted.  The cap is the
-    caller's check."""
+    """dtype and rank of a (B, N, M) stack of mat_dtype (numpy array or device tensor); returns (B, N, M, on_device,
+    the MISSLAP_DTYPE_* code).  The stack must have exactly that dtype: nothing is converted.  A device tensor may have
+    any strides (_stack_strides).  The cap is the caller's check."""
     want = _mat_dtype_name(mat_dtype)
     if isinstance(mats, np.ndarray):
         on_device = False
@@ -61,14 +61,20 @@ def _check_stack(mats, mat_dtype="float64"):
             raise ValueError(f"mats must be float64, got {mats.dtype}")
         if mats.dtype != getattr(torch, want):
             raise ValueError(f"mats dtype mismatch: mat_dtype is {want}, the tensor is {mats.dtype}")
-        if not mats.is_contiguous():
-            raise ValueError("a device tensor must be contiguous (it is read in place)")
     else:
-        raise TypeError("mats must be a numpy array or a contiguous tensor on the device")
+        raise TypeError("mats must be a numpy array or a tensor on the device")
     B, N, M = (int(d) for d in mats.shape)
     if B < 1 or N < 1 or M < 1:
         raise ValueError(f"empty stack of shape {(B, N, M)}")
     return B, N, M, on_device, _MAT_DTYPES[want]
+
+
+def _stack_strides(mats, on_device):
+    """The element strides (sB, sN, sM) of a non-contiguous device stack, which the strided entry points read in place;
+    None for a contiguous tensor and for a numpy array (uploaded through np.ascontiguousarray): today's entry points."""
+    if not on_device or mats.is_contiguous():
+        return None
+    return tuple(int(x) for x in mats.stride())  # (torch has no negative strides; expand gives 0)
 
 
 def _check_shapes(shapes, B, N, M, what):

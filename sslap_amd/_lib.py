@@ -194,6 +194,13 @@ SYMBOLS = {
                                                     C.POINTER(Options), _VP, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP,
                                                     _VP, C.c_int32, _VP, _VP, _VP, C.POINTER(DenseBatchInfo)]),
     "misslap_dense_batch_outside_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64, C.c_int32]),
+    # the strided forms: the three strides (elements) behind B, N, M
+    "misslap_solve_dense_batch_status_strided": (C.c_int, [C.c_int64] * 6 + [_VP, _VP, C.c_int32, _VP, C.c_int32,
+                                                           C.POINTER(Options), _VP, _VP, C.c_int64, _VP, _VP, C.c_int32,
+                                                           _VP, _VP, _VP, C.POINTER(DenseBatchInfo)]),
+    "misslap_solve_dense_batch_outside_strided": (C.c_int, [C.c_int64] * 6 + [_VP, _VP, C.c_int32, _VP, C.POINTER(Options),
+                                                            _VP, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP, _VP, C.c_int32,
+                                                            _VP, _VP, _VP, C.POINTER(DenseBatchInfo)]),
     "misslap_solve_sparse_batch": (C.c_int, [C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int64, C.c_int32,
                                              C.POINTER(Options), _VP, C.c_int64, _VP, C.c_int64, C.c_int32,
                                              C.POINTER(DenseBatchMeta), C.POINTER(DenseBatchInfo)]),
@@ -220,6 +227,9 @@ SYMBOLS = {
     "misslap_matching_dense_batch": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, _VP, _VP, C.POINTER(Options), _VP, _VP,
                                                _VP, _VP, C.c_int64, _VP, C.c_int64, C.c_int32,
                                                C.POINTER(MatchingBatchInfo)]),
+    "misslap_matching_dense_batch_strided": (C.c_int, [C.c_int64] * 6 + [_VP, _VP, C.POINTER(Options), _VP, _VP, _VP, _VP,
+                                                       C.c_int64, _VP, C.c_int64, C.c_int32,
+                                                       C.POINTER(MatchingBatchInfo)]),
     "misslap_last_error": (C.c_char_p, []),
     "misslap_abi_version": (C.c_int, []),
 }

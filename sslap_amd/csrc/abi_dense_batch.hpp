@@ -64,6 +64,53 @@ int dense_batch_dims(int64_t B, int64_t N, int64_t M) {
     return MISSLAP_OK;
 }
 
+// The strides of a strided stack, in elements: element (b, i, j) of the view lies at mat[b * sB + i * sN + j * sM].
+// None may be negative, and the offset of the view's last element must fit 62 bits (it is formed in 64 bits on the
+// device, and scaled by the element size); made before any device is touched.  `who`: the entry point.
+int dense_strides_check(int64_t B, int64_t N, int64_t M, int64_t sB, int64_t sN, int64_t sM, const char *who) {
+    if (sB < 0 || sN < 0 || sM < 0)
+        return fail(MISSLAP_ERR_INVALID, "%s: strides (%lld, %lld, %lld): a stride must be >= 0 (elements)", who,
+                    (long long)sB, (long long)sN, (long long)sM);
+    const unsigned __int128 extent = (unsigned __int128)(B - 1) * (unsigned __int128)sB +
+                                     (unsigned __int128)(N - 1) * (unsigned __int128)sN +
+                                     (unsigned __int128)(M - 1) * (unsigned __int128)sM;
+    if (extent >> 62)
+        return fail(MISSLAP_ERR_INVALID,
+                    "%s: strides (%lld, %lld, %lld) of a %lld x %lld x %lld stack: the last element's offset does not fit "
+                    "62 bits", who, (long long)sB, (long long)sN, (long long)sM, (long long)B, (long long)N, (long long)M);
+    return MISSLAP_OK;
+}
+// the strides of the contiguous stack: such a call takes the contiguous kernels
+inline bool dense_strides_compact(int64_t N, int64_t M, int64_t sB, int64_t sN, int64_t sM) {
+    return sM == 1 && sN == M && sB == N * M;
+}
+// Rounds of at least this many bidders of a strided solve bid one lane per person where the stack's rows run along the
+// unit stride (DenseBatchRows::bid_lanes; DESIGN.md 4.19 has the measurement behind the value).
+// MISSLAP_STRIDED_LANE_MIN_K overrides it (tools/dense_strided.py: 0 = every round, a value above the cap = none).
+constexpr int kStridedLaneMinK = 64;
+inline DenseStrides dense_strides_arg(int64_t sB, int64_t sN, int64_t sM) {
+    int min_K = kStridedLaneMinK;
+    if (const char *e = std::getenv("MISSLAP_STRIDED_LANE_MIN_K")) min_K = std::atoi(e);  // (read per call)
+    return DenseStrides{(long long)sB, (long long)sN, (long long)sM, min_K};
+}
+
+// The layout of a call's stack: strides null (the contiguous entry points) or {sB, sN, sM} of a strided one (`who`).
+// *str becomes null for the contiguous kernels, else `store`, filled.  A strided stack lies on the device (a host
+// stack is uploaded whole, and is compact); all of this is checked before any device is touched.
+int dense_stack_layout(const char *who, const misslap_options &opt, int64_t B, int64_t N, int64_t M,
+                       const int64_t *strides, DenseStrides *store, const DenseStrides **str) {
+    *str = nullptr;
+    if (!strides) return MISSLAP_OK;
+    const int rc = dense_strides_check(B, N, M, strides[0], strides[1], strides[2], who);
+    if (rc) return rc;
+    if (!opt.input_on_device)
+        return fail(MISSLAP_ERR_INVALID, "%s: a strided stack is a device array: set input_on_device", who);
+    if (dense_strides_compact(N, M, strides[0], strides[1], strides[2])) return MISSLAP_OK;
+    *store = dense_strides_arg(strides[0], strides[1], strides[2]);
+    *str = store;
+    return MISSLAP_OK;
+}
+
 // a host shapes array (or null): every problem within the stack
 int dense_batch_host_shapes(const int32_t *shapes, int64_t B, int64_t N, int64_t M) {
     if (shapes)

@@ -1,5 +1,6 @@
 // abi_dense_batch_outside.hpp -- C ABI: the dense batch with an outside option per row, for partial assignments
-// (misslap_solve_dense_batch_outside, misslap_dense_batch_outside_workspace_bytes; include/misslap.h).  The options and
+// (misslap_solve_dense_batch_outside, its strided form misslap_solve_dense_batch_outside_strided,
+// misslap_dense_batch_outside_workspace_bytes; include/misslap.h).  The options and
 // the output conventions are those of misslap_solve_dense_batch_status (abi_dense_batch_status.hpp), the two modes of the
 // call are batch_stream_call's (abi_batch_stream.hpp); the kernels are the <T, true> instances of kernels_dense_batch.hpp.  Two launches, no guard; the verdict is formed in
 // k_dense_outside_solve, so nothing is read back between them.
@@ -17,6 +18,7 @@ inline BatchCarve dense_outside_carve(int64_t B, int64_t N, int64_t M, bool has_
 struct DenseOutsideCall {
     int64_t B, N, M;
     const void *d_mat;  // elements of opt.mat_dtype
+    const DenseStrides *str;  // the strides of a strided stack and its kernels, or null: the contiguous stack
     const int32_t *d_shapes;
     const double *d_p0;
     const double *d_outside;
@@ -44,11 +46,14 @@ int dense_outside_enqueue(hipStream_t st, const misslap_options &opt, const Dens
     k.outside_ld = c.outside_ld;
     k.aug = d_aug;
     dense_dtype_dispatch(opt.mat_dtype, [&](auto t) {
-        hipLaunchKernelGGL(k_dense_outside_check<decltype(t)>, dim3((unsigned)c.B), dim3(256), 0, st, k);
+        if (c.str)
+            hipLaunchKernelGGL((k_dense_strided_check<decltype(t), true>), dim3((unsigned)c.B), dim3(256), 0, st, k, *c.str);
+        else
+            hipLaunchKernelGGL(k_dense_outside_check<decltype(t)>, dim3((unsigned)c.B), dim3(256), 0, st, k);
     });
     HIP_TRY(hipGetLastError());
 
-    DenseOutsideArgs a{};
+    DenseStridedOutsideArgs a{};  // (its base is the contiguous kernels' argument)
     a.t.d.mat = c.d_mat;
     a.t.d.N = c.N;
     a.t.d.M = c.M;
@@ -65,8 +70,15 @@ int dense_outside_enqueue(hipStream_t st, const misslap_options &opt, const Dens
     // (the carve is N x (M + N): 77 824 B at the cap, above 64 KB from 683 x 683 on.  No prices array for batch_solve:
     // k_dense_outside_solve writes the real columns itself.)
     return dense_dtype_dispatch(opt.mat_dtype, [&](auto t) {
-        return batch_solve_launch(k_dense_outside_solve<decltype(t)>, a, a.t.d.s, opt, c.B, c.N, c.M + c.N, d.sol, c.N,
-                                  nullptr, 0, d_aug, c.M + c.N, d.meta, d.info, st);
+        using T = decltype(t);
+        if (c.str) {
+            a.str = *c.str;
+            return batch_solve_launch(k_dense_outside_solve<T, DenseStridedOutsideArgs>, a, a.t.d.s, opt, c.B, c.N,
+                                      c.M + c.N, d.sol, c.N, nullptr, 0, d_aug, c.M + c.N, d.meta, d.info, st);
+        }
+        DenseOutsideArgs &p = a;
+        return batch_solve_launch(k_dense_outside_solve<T>, p, p.t.d.s, opt, c.B, c.N, c.M + c.N, d.sol, c.N, nullptr, 0,
+                                  d_aug, c.M + c.N, d.meta, d.info, st);
     });
 }
 }  // namespace
@@ -76,17 +88,18 @@ MISSLAP_API int64_t misslap_dense_batch_outside_workspace_bytes(int64_t B, int64
     return (int64_t)dense_outside_carve(B, N, M, has_prices != 0).total;
 }
 
-MISSLAP_API int misslap_solve_dense_batch_outside(int64_t B, int64_t N, int64_t M, const void *mat, const int32_t *shapes,
-                                                  int32_t fast, const double *prices_in, const misslap_options *opt_in,
-                                                  void *stream, void *workspace, int64_t workspace_bytes,
-                                                  const double *outside, int64_t outside_ld, int32_t *sol,
-                                                  double *prices_out, double *outside_prices_out, int32_t out_on_device,
-                                                  int32_t *status, int32_t *matching_size, misslap_dense_batch_meta *meta,
-                                                  misslap_dense_batch_info *info) {
+namespace {
+// misslap_solve_dense_batch_outside (strides null) and misslap_solve_dense_batch_outside_strided (`who`)
+int dense_outside_call(const char *who, int64_t B, int64_t N, int64_t M, const void *mat, const int64_t *strides,
+                       const int32_t *shapes, int32_t fast, const double *prices_in, const misslap_options *opt_in,
+                       void *stream, void *workspace, int64_t workspace_bytes, const double *outside, int64_t outside_ld,
+                       int32_t *sol, double *prices_out, double *outside_prices_out, int32_t out_on_device,
+                       int32_t *status, int32_t *matching_size, misslap_dense_batch_meta *meta,
+                       misslap_dense_batch_info *info) {
     BatchStreamCall k;
     k.t_start = now_ms();
     misslap_options opt;
-    int rc = batch_options(opt_in, &opt, "misslap_solve_dense_batch_outside",
+    int rc = batch_options(opt_in, &opt, who,
                            "device, maximize, eps_start, max_iter, mat_dtype, input_on_device and input_stream", true);
     if (rc) return rc;
     if ((rc = dense_batch_dims(B, N, M))) return rc;
@@ -94,7 +107,9 @@ MISSLAP_API int misslap_solve_dense_batch_outside(int64_t B, int64_t N, int64_t 
     if (outside_ld != 0 && outside_ld < N)
         return fail(MISSLAP_ERR_INVALID, "outside_ld = %lld: 0 (one value per problem) or >= N = %lld",
                     (long long)outside_ld, (long long)N);
+    DenseStrides str_arg{};
     DenseOutsideCall c{};
+    if ((rc = dense_stack_layout(who, opt, B, N, M, strides, &str_arg, &c.str))) return rc;
     c.B = B;
     c.N = N;
     c.M = M;
@@ -136,4 +151,32 @@ MISSLAP_API int misslap_solve_dense_batch_outside(int64_t B, int64_t N, int64_t 
             return shapes ? upload(tmp, &c.d_shapes, shapes, (size_t)B * 2, st) : rc;
         },
         [&](hipStream_t st, void *ws, const BatchStreamOut &d) { return dense_outside_enqueue(st, opt, c, ws, d); });
+}
+}  // namespace
+
+MISSLAP_API int misslap_solve_dense_batch_outside(int64_t B, int64_t N, int64_t M, const void *mat, const int32_t *shapes,
+                                                  int32_t fast, const double *prices_in, const misslap_options *opt_in,
+                                                  void *stream, void *workspace, int64_t workspace_bytes,
+                                                  const double *outside, int64_t outside_ld, int32_t *sol,
+                                                  double *prices_out, double *outside_prices_out, int32_t out_on_device,
+                                                  int32_t *status, int32_t *matching_size, misslap_dense_batch_meta *meta,
+                                                  misslap_dense_batch_info *info) {
+    return dense_outside_call("misslap_solve_dense_batch_outside", B, N, M, mat, nullptr, shapes, fast, prices_in, opt_in,
+                              stream, workspace, workspace_bytes, outside, outside_ld, sol, prices_out, outside_prices_out,
+                              out_on_device, status, matching_size, meta, info);
+}
+
+MISSLAP_API int misslap_solve_dense_batch_outside_strided(int64_t B, int64_t N, int64_t M, int64_t stride_b, int64_t stride_n,
+                                                          int64_t stride_m, const void *mat, const int32_t *shapes,
+                                                          int32_t fast, const double *prices_in,
+                                                          const misslap_options *opt_in, void *stream, void *workspace,
+                                                          int64_t workspace_bytes, const double *outside,
+                                                          int64_t outside_ld, int32_t *sol, double *prices_out,
+                                                          double *outside_prices_out, int32_t out_on_device,
+                                                          int32_t *status, int32_t *matching_size,
+                                                          misslap_dense_batch_meta *meta, misslap_dense_batch_info *info) {
+    const int64_t strides[3] = {stride_b, stride_n, stride_m};
+    return dense_outside_call("misslap_solve_dense_batch_outside_strided", B, N, M, mat, strides, shapes, fast, prices_in,
+                              opt_in, stream, workspace, workspace_bytes, outside, outside_ld, sol, prices_out,
+                              outside_prices_out, out_on_device, status, matching_size, meta, info);
 }

@@ -1,18 +1,23 @@
 // abi_matching_batch.hpp -- C ABI: the reference's Hopcroft-Karp on many small graphs in one call, one workgroup per
-// graph (misslap_matching_batch / misslap_matching_dense_batch; the kernels are in kernels_matching_batch.hpp, the shared
+// graph (misslap_matching_batch / misslap_matching_dense_batch / misslap_matching_dense_batch_strided; the kernels are in kernels_matching_batch.hpp, the shared
 // host helpers in abi_batch_common.hpp).
 // (part of the single translation unit misslap.hip; included in the order given there, after abi_sparse_batch.hpp)
 #pragma once
 
 namespace {
 // Launch the matcher on a stream (LDS carve Ns x Ms; the > 64 KB opt-in is never needed: 48 KB at the cap).  mat_dtype:
-// the element type of a dense stack.
+// the element type of a dense stack; strided: a.sB / sN / sM are its strides (the matcher's strided source).
 template <bool kDense>
-int launch_matching_batch(hipStream_t st, int64_t B, const MatchBatchArgs &a, int32_t mat_dtype, size_t *lds_out) {
+int launch_matching_batch(hipStream_t st, int64_t B, const MatchBatchArgs &a, int32_t mat_dtype, size_t *lds_out,
+                          bool strided = false) {
     const size_t lds = matching_batch_lds_bytes(a.Ns, a.Ms, kDense);
     if constexpr (kDense)
         dense_dtype_dispatch(mat_dtype, [&](auto t) {
-            hipLaunchKernelGGL((k_matching_batch<MatchSrc::Dense, decltype(t)>), dim3((unsigned)B), dim3(kMatchBatchThreads), lds, st, a);
+            if (strided)
+                hipLaunchKernelGGL((k_matching_batch<MatchSrc::DenseStrided, decltype(t)>), dim3((unsigned)B),
+                                   dim3(kMatchBatchThreads), lds, st, a);
+            else
+                hipLaunchKernelGGL((k_matching_batch<MatchSrc::Dense, decltype(t)>), dim3((unsigned)B), dim3(kMatchBatchThreads), lds, st, a);
         });
     else
         hipLaunchKernelGGL(k_matching_batch<MatchSrc::Loc>, dim3((unsigned)B), dim3(kMatchBatchThreads), lds, st, a);
@@ -26,7 +31,7 @@ template <bool kDense>
 int matching_batch_run(hipStream_t st, DevScratch &tmp, int64_t B, MatchBatchArgs a, int32_t *size, int32_t *left,
                        int64_t left_ld, int32_t *right, int64_t right_ld, int32_t out_on_device,
                        misslap_matching_batch_info *info, double t_start, double t_checked,
-                       int32_t mat_dtype = MISSLAP_DTYPE_F64) {
+                       int32_t mat_dtype = MISSLAP_DTYPE_F64, bool strided = false) {
     int rc = 0;
     int *d_size = nullptr;
     if ((rc = tmp.alloc(&d_size, (size_t)B))) return rc;
@@ -43,7 +48,7 @@ int matching_batch_run(hipStream_t st, DevScratch &tmp, int64_t B, MatchBatchArg
     if ((rc = ev.create())) return rc;
     size_t lds = 0;
     HIP_TRY(hipEventRecord(ev.e[0], st));
-    if ((rc = launch_matching_batch<kDense>(st, B, a, mat_dtype, &lds))) return rc;
+    if ((rc = launch_matching_batch<kDense>(st, B, a, mat_dtype, &lds, strided))) return rc;
     HIP_TRY(hipEventRecord(ev.e[1], st));
     HIP_TRY(hipMemcpyAsync(size, d_size, sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToHost, st));
     if (!out_on_device) {
@@ -151,14 +156,15 @@ MISSLAP_API int misslap_matching_batch(int64_t B, const int32_t *loc, const int6
                                      info, t_start, t_checked);
 }
 
-MISSLAP_API int misslap_matching_dense_batch(int64_t B, int64_t N, int64_t M, const double *mat, const int32_t *shapes,
-                                             const misslap_options *opt_in, int32_t *size, int32_t *n_rows,
-                                             int32_t *n_cols, int32_t *left_pairings, int64_t left_ld,
-                                             int32_t *right_pairings, int64_t right_ld, int32_t out_on_device,
-                                             misslap_matching_batch_info *info) {
+namespace {
+// misslap_matching_dense_batch (strides null) and misslap_matching_dense_batch_strided (`who`)
+int matching_dense_batch_call(const char *who, int64_t B, int64_t N, int64_t M, const void *mat, const int64_t *strides,
+                              const int32_t *shapes, const misslap_options *opt_in, int32_t *size, int32_t *n_rows,
+                              int32_t *n_cols, int32_t *left_pairings, int64_t left_ld, int32_t *right_pairings,
+                              int64_t right_ld, int32_t out_on_device, misslap_matching_batch_info *info) {
     const double t_start = now_ms();
     misslap_options opt;
-    int rc = batch_options(opt_in, &opt, "misslap_matching_dense_batch",
+    int rc = batch_options(opt_in, &opt, who,
                            "device, mat_dtype, input_on_device and input_stream", true);
     if (rc) return rc;
     if ((rc = matching_batch_info_size(info))) return rc;
@@ -168,6 +174,9 @@ MISSLAP_API int misslap_matching_dense_batch(int64_t B, int64_t N, int64_t M, co
         return fail(MISSLAP_ERR_INVALID, "a %lld x %lld stack: N and M must be 1 .. 2^31 - 1", (long long)N, (long long)M);
     if ((left_pairings && left_ld < 1) || (right_pairings && right_ld < 1))
         return fail(MISSLAP_ERR_INVALID, "left_ld / right_ld must be >= 1");
+    DenseStrides str_arg{};
+    const DenseStrides *str = nullptr;
+    if ((rc = dense_stack_layout(who, opt, B, N, M, strides, &str_arg, &str))) return rc;
     // each graph is its slice (feasibility_.pyx:250-251)
     int Ns = 1, Ms = 1;
     for (int64_t b = 0; b < B; ++b) {
@@ -204,6 +213,32 @@ MISSLAP_API int misslap_matching_dense_batch(int64_t B, int64_t N, int64_t M, co
     a.shapes = d_shapes;
     a.Ns = Ns;
     a.Ms = Ms;
+    if (str) {
+        a.sB = str->sB;
+        a.sN = str->sN;
+        a.sM = str->sM;
+    }
     return matching_batch_run<true>(st, tmp, B, a, size, left_pairings, left_ld, right_pairings, right_ld, out_on_device,
-                                    info, t_start, now_ms(), opt.mat_dtype);
+                                    info, t_start, now_ms(), opt.mat_dtype, str != nullptr);
+}
+}  // namespace
+
+MISSLAP_API int misslap_matching_dense_batch(int64_t B, int64_t N, int64_t M, const double *mat, const int32_t *shapes,
+                                             const misslap_options *opt_in, int32_t *size, int32_t *n_rows,
+                                             int32_t *n_cols, int32_t *left_pairings, int64_t left_ld,
+                                             int32_t *right_pairings, int64_t right_ld, int32_t out_on_device,
+                                             misslap_matching_batch_info *info) {
+    return matching_dense_batch_call("misslap_matching_dense_batch", B, N, M, mat, nullptr, shapes, opt_in, size, n_rows,
+                                     n_cols, left_pairings, left_ld, right_pairings, right_ld, out_on_device, info);
+}
+
+MISSLAP_API int misslap_matching_dense_batch_strided(int64_t B, int64_t N, int64_t M, int64_t stride_b, int64_t stride_n,
+                                                     int64_t stride_m, const void *mat, const int32_t *shapes,
+                                                     const misslap_options *opt_in, int32_t *size, int32_t *n_rows,
+                                                     int32_t *n_cols, int32_t *left_pairings, int64_t left_ld,
+                                                     int32_t *right_pairings, int64_t right_ld, int32_t out_on_device,
+                                                     misslap_matching_batch_info *info) {
+    const int64_t strides[3] = {stride_b, stride_n, stride_m};
+    return matching_dense_batch_call("misslap_matching_dense_batch_strided", B, N, M, mat, strides, shapes, opt_in, size,
+                                     n_rows, n_cols, left_pairings, left_ld, right_pairings, right_ld, out_on_device, info);
 }

@@ -179,6 +179,15 @@ __device__ __forceinline__ void batch_outside_outputs(const unsigned char *s_raw
         for (int i = tid; i < N_ld; i += T) oo[i] = i < n ? price[m + i] : 0.0;
 }
 
+// Whether a row source has a second bid mapping for whole rounds, bid_lanes(U, K, price, eps, bid_key, bid_obj, bkey):
+// it makes the K bids of a round itself (keys, objects and the per-object maxima, as the BID step below leaves them) and
+// returns true, or does nothing and returns false.  Only the strided dense source has one (kernels_dense_batch.hpp);
+// for every other source the BID step compiles to what it was.
+template <class Rows>
+struct RowsBidLanes {
+    static constexpr bool value = false;
+};
+
 // eCE_satisfied(eps) (auction_.pyx:443-485, tol = 1e-7) on a state with everybody assigned; one wavefront per row.
 template <class Rows>
 __device__ __forceinline__ bool batch_ece(const Rows &rows, int n, const double *price, const int *p2o, float eps_f,
@@ -246,7 +255,9 @@ __device__ __forceinline__ void batch_solve(const BatchSolveArgs &a, const Rows 
 
     for (;;) {  // solve() (:271-292); leaves after at most max_iter rounds
         // ---- BID (:339-365)
-        for (int k = wave; k < K; k += nw) {
+        bool bid_done = false;
+        if constexpr (RowsBidLanes<Rows>::value) bid_done = rows.bid_lanes(U, K, price, eps, bid_key, bid_obj, bkey);
+        for (int k = wave; !bid_done && k < K; k += nw) {
             double costbest;
             int j;
             const Top2 r = rows.bid(U[k], price, costbest, j);

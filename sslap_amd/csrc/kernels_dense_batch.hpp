@@ -20,6 +20,15 @@
 // values into C = max |v| and the +inf flag, flags a negative or NaN one and never reports an empty row, and the solve
 // kernel rewrites the outputs behind batch_solve: an object >= m_b becomes -1 in sol, price[0 .. m_b) are the real
 // prices and price[m_b .. m_b + n_b) the outside prices.
+//
+// The strided family (misslap_solve_dense_batch_status_strided / _outside_strided; the instances on DenseStrided*Args
+// and k_dense_strided_check): the same check pass, row source and solve kernels on a stack whose element (b, i, j) lies
+// at mat[b * sB + i * sN + j * sM] for run-time strides >= 0 -- a transposed view, a slice of a wider buffer, an
+// expanded matrix (sB = 0).  Every entry plays the role it plays in the contiguous stack, so the results are those of
+// the compact copy bit for bit; offsets are formed in 64 bits and only elements of the view are read.  The contiguous
+// instances take no stride: theirs are compile-time (DenseColStride<false> is empty), and their code is what it was.
+// A strided row source also has a second bid mapping, bid_lanes below, for rounds of many bidders on a stack whose
+// rows run along the unit stride (sN == 1).
 #pragma once
 
 namespace misslap {
@@ -46,6 +55,25 @@ struct DenseBatchArgs {
     const DenseBatchCheck *chk;
 };
 
+// The element strides of a strided stack (all >= 0, the host has checked that the extent fits 62 bits), and the
+// smallest round that bids one lane per person (bid_lanes; INT_MAX: no round does).
+struct DenseStrides {
+    long long sB, sN, sM;
+    int lane_min_K;
+};
+
+// The column step of a row source: 1 at compile time in a contiguous stack, the stack's sM in a strided one.
+template <bool Str>
+struct DenseColStride {
+    __device__ __forceinline__ size_t at(int c) const { return (size_t)c; }
+};
+template <>
+struct DenseColStride<true> {
+    long long sM;
+    int lane_min_K;
+    __device__ __forceinline__ size_t at(int c) const { return (size_t)c * (size_t)sM; }
+};
+
 __device__ __forceinline__ void dense_batch_shape(const int *shapes, long long N, long long M, int b, int &n, int &m) {
     n = shapes ? shapes[2 * b] : (int)N;
     m = shapes ? shapes[2 * b + 1] : (int)M;
@@ -59,10 +87,12 @@ __device__ __forceinline__ void dense_batch_shape(const int *shapes, long long N
 // ov_ld == 0, else outside[b * ov_ld + i]; a negative one or a NaN raises bit 1 of has_inf instead), no row is empty,
 // and with starting prices the problem's augmented starting prices [p0[:m_b], zeros(n_b)] are staged at
 // aug[b * (M + N) ..] for batch_solve to load.
-template <class T, bool Out>
+// Str (the strided family): element (b, r, c) lies at mat[b * str.sB + r * str.sN + c * str.sM]; else str is not read.
+template <class T, bool Out, bool Str = false>
 __device__ __forceinline__ void dense_batch_check(const T *mat, long long N, long long M, const int *shapes,
                                                   const double *p0, DenseBatchCheck *out, int *shapes_out,
-                                                  const double *ov, long long ov_ld, double *aug) {
+                                                  const double *ov, long long ov_ld, double *aug,
+                                                  const DenseStrides &str = {}) {
     const int b = blockIdx.x, lane = lane_id(), wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
     int n, m;
     dense_batch_shape(shapes, N, M, b, n, m);
@@ -73,7 +103,9 @@ __device__ __forceinline__ void dense_batch_check(const T *mat, long long N, lon
             shapes_out[2 * b + 1] = m;
         }
     }
-    const T *A = mat + (size_t)b * (size_t)N * (size_t)M;
+    const T *A = mat + (Str ? (size_t)b * (size_t)str.sB : (size_t)b * (size_t)N * (size_t)M);
+    DenseColStride<Str> col{};
+    if constexpr (Str) col.sM = str.sM;
     __shared__ unsigned long long s_cnt, s_abs;
     __shared__ int s_empty, s_inf, s_mref, s_badp;
     if (threadIdx.x == 0) {
@@ -88,10 +120,10 @@ __device__ __forceinline__ void dense_batch_check(const T *mat, long long N, lon
     unsigned long long cnt = 0, am = 0;
     int inf = 0, mx = -1;
     for (int r = wave; r < n; r += nw) {
-        const T *row = A + (size_t)r * (size_t)M;
+        const T *row = A + (size_t)r * (size_t)(Str ? str.sN : M);
         int rc = 0;
         for (int c = lane; c < m; c += kWave) {
-            const T v = row[c];
+            const T v = row[col.at(c)];
             if (dense_entry_valid(v)) {
                 const unsigned long long bits =
                     (unsigned long long)__double_as_longlong(dense_widen(v)) & 0x7fffffffffffffffull;
@@ -167,6 +199,13 @@ __global__ __launch_bounds__(256) void k_dense_outside_check(DenseOutsideCheckAr
                                a.outside_ld, a.aug);
 }
 
+// the check pass of the strided family, in either mode (Out false: a.outside and a.aug are not read)
+template <class T, bool Out>
+__global__ __launch_bounds__(256) void k_dense_strided_check(DenseOutsideCheckArgs a, DenseStrides str) {
+    dense_batch_check<T, Out, true>(static_cast<const T *>(a.mat), a.N, a.M, a.shapes, a.p0, a.out, a.shapes_out,
+                                    a.outside, a.outside_ld, a.aug, str);
+}
+
 // The dense row source of batch_solve: problem b's slice A (row stride M) of n x m, its reference M and valid count.
 // The bid's staging array `vals` belongs to k_dense_batch_solve: declared in bid() it is promoted to a vector while bid()
 // is optimised on its own, and every staging step then zeroes the rest of it (measured: 3.8 % more kernel time at
@@ -177,7 +216,10 @@ __global__ __launch_bounds__(256) void k_dense_outside_check(DenseOutsideCheckAr
 // problem (m + n columns, n more entries).  Column m + i is above every real column, and lane (m + i) & 63 takes it AFTER
 // its own real columns, so every lane still scans in ascending column order and the winner's lane is r.g & 63 as before.
 // A chosen object j >= m is that entry: nothing of the slice is read for it.
-template <class T, bool Out = false>
+// Str (the strided family): M is the row stride sN and col holds the column stride sM; entry (i, c) lies at
+// A[i * M + c * sM].  The wavefront scan keeps its lane map (lane l holds columns l, l + 64, ...) whatever the strides
+// are, with loads of one element each: nothing wider than the element is assumed of the base or of a stride.
+template <class T, bool Out = false, bool Str = false>
 struct DenseBatchRows {
     const T *A;
     long long M;
@@ -185,30 +227,62 @@ struct DenseBatchRows {
     unsigned long long nvalid;
     T *vals;  // [kDenseBatchCols]
     BatchOutside<Out> out{};
+    DenseColStride<Str> col{};
 
     __device__ __forceinline__ Top2 bid(int i, const double *price, double &costbest, int &obj) const {
         const int lane = lane_id();
         const T *row = A + (size_t)i * (size_t)M;
-#pragma unroll
-        for (int q = 0; q < kDenseBatchCols; ++q) {
-            if (q * kWave >= m) break;
-            const int c = lane + q * kWave;
-            vals[q] = c < m ? row[c] : dense_hole<T>();
-        }
         Top2 x;
-        x.v = -__builtin_huge_val();
-        x.w = -__builtin_huge_val();
-        x.g = -1;
-        double cb = 0.0;
+        double cb;
+        if constexpr (!Str) {
 #pragma unroll
-        for (int q = 0; q < kDenseBatchCols; ++q) {
-            if (q * kWave >= m) break;
-            const int c = lane + q * kWave;
-            if (c < m && dense_entry_valid(vals[q])) {
-                const double v = dense_widen(vals[q]);
-                const double cost = maximize ? v : v * -1.0;  // :236-237
-                const double vi = cost - price[c];
-                if (top2_take(x, vi, c)) cb = cost;
+            for (int q = 0; q < kDenseBatchCols; ++q) {
+                if (q * kWave >= m) break;
+                const int c = lane + q * kWave;
+                vals[q] = c < m ? row[c] : dense_hole<T>();
+            }
+            x.v = -__builtin_huge_val();
+            x.w = -__builtin_huge_val();
+            x.g = -1;
+            cb = 0.0;
+#pragma unroll
+            for (int q = 0; q < kDenseBatchCols; ++q) {
+                if (q * kWave >= m) break;
+                const int c = lane + q * kWave;
+                if (c < m && dense_entry_valid(vals[q])) {
+                    const double v = dense_widen(vals[q]);
+                    const double cost = maximize ? v : v * -1.0;  // :236-237
+                    const double vi = cost - price[c];
+                    if (top2_take(x, vi, c)) cb = cost;
+                }
+            }
+        } else {
+            // a column stride other than 1 (a strided kernel gives sM == 1 to the contiguous row source): one pointer
+            // stepped from load to load, staged and scanned in two halves of 8 slots, in ascending order -- 16
+            // addresses next to 16 staged doubles do not fit the 128 registers of a 1024-thread workgroup
+            x.v = -__builtin_huge_val();
+            x.w = -__builtin_huge_val();
+            x.g = -1;
+            cb = 0.0;
+            const T *p = row + (size_t)lane * (size_t)col.sM;
+            const size_t step = (size_t)kWave * (size_t)col.sM;
+            constexpr int kHalf = kDenseBatchCols / 2;
+            for (int h = 0; h < kDenseBatchCols && h * kWave < m; h += kHalf) {
+#pragma unroll
+                for (int q = 0; q < kHalf; ++q) {
+                    vals[q] = lane + (h + q) * kWave < m ? *p : dense_hole<T>();
+                    p += step;
+                }
+#pragma unroll
+                for (int q = 0; q < kHalf; ++q) {
+                    const int c = lane + (h + q) * kWave;
+                    if (c < m && dense_entry_valid(vals[q])) {
+                        const double v = dense_widen(vals[q]);
+                        const double cost = maximize ? v : v * -1.0;
+                        const double vi = cost - price[c];
+                        if (top2_take(x, vi, c)) cb = cost;
+                    }
+                }
             }
         }
         if constexpr (Out) {
@@ -225,12 +299,63 @@ struct DenseBatchRows {
         return r;
     }
 
+    // The second bid mapping of a strided row source, for a whole round: one LANE per list position, 64 persons per
+    // wavefront.  On a stack whose rows run along the unit stride (M == sN == 1: a transposed view) a wavefront that
+    // scans one person's row touches 64 cache lines per load; here lane l scans the row of person U[k0 + l] in column
+    // order, so one load instruction reads column c of 64 persons, and in the first round of every eps-phase
+    // (U = 0 .. n - 1) those are 64 adjacent elements.  price[c] is one LDS address for the whole wavefront (a
+    // broadcast).  The scan is the reference's sequential one (:339-365) with its ">=" rule, so (v, w, g) and the
+    // winner's cost are those of bid(); eight loads are in flight per lane.  Returns false, having done nothing, for
+    // a round the wavefront scan serves better: fewer than lane_min_K bidders (one lane would run m dependent steps
+    // for one bidder) or another layout.  The branch is uniform.
+    __device__ __forceinline__ bool bid_lanes(const int *U, int K, const double *price, float eps,
+                                              unsigned long long *bid_key, int *bid_obj, unsigned long long *bkey) const {
+        static_assert(Str, "only a strided row source has the lane-per-person bid");
+        if (K < col.lane_min_K || M != 1) return false;
+        constexpr int kFly = 8;
+        for (int k = threadIdx.x; k < K; k += blockDim.x) {
+            const int i = U[k];
+            const T *row = A + (size_t)i * (size_t)M;
+            Top2 x;
+            x.v = -__builtin_huge_val();
+            x.w = -__builtin_huge_val();
+            x.g = -1;
+            double cb = 0.0;
+            for (int c0 = 0; c0 < m; c0 += kFly) {
+                T v8[kFly];
+#pragma unroll
+                for (int q = 0; q < kFly; ++q) v8[q] = c0 + q < m ? row[col.at(c0 + q)] : dense_hole<T>();
+#pragma unroll
+                for (int q = 0; q < kFly; ++q) {
+                    const int c = c0 + q;
+                    if (c < m && dense_entry_valid(v8[q])) {
+                        const double v = dense_widen(v8[q]);
+                        const double cost = maximize ? v : v * -1.0;  // :236-237
+                        const double vi = cost - price[c];
+                        if (top2_take(x, vi, c)) cb = cost;
+                    }
+                }
+            }
+            if constexpr (Out) {
+                const double v = out.value(i);
+                const double cost = maximize ? v : v * -1.0;
+                const double vi = cost - price[m + i];
+                if (top2_take(x, vi, m + i)) cb = cost;
+            }
+            const unsigned long long key = bid_to_key(cb - x.w + (double)eps);  // :360
+            bid_key[k] = key;
+            bid_obj[k] = x.g;
+            atomicMax(&bkey[x.g], key);
+        }
+        return true;
+    }
+
     // eCE_satisfied (auction_.pyx:443-485) for row i: choice_cost is the cost of column j, every valid column is tested
     __device__ __forceinline__ bool ece_bad(int i, int j, const double *price, double tol, double eps) const {
         const T *row = A + (size_t)i * (size_t)M;
         double vj;
-        if constexpr (Out) vj = j >= m ? out.value(i) : dense_widen(row[j]);
-        else vj = dense_widen(row[j]);
+        if constexpr (Out) vj = j >= m ? out.value(i) : dense_widen(row[col.at(j)]);
+        else vj = dense_widen(row[col.at(j)]);
         const double choice_cost = maximize ? vj : vj * -1.0;
         const double LHS = choice_cost - price[j] + tol;  // :475
         bool bad = false;
@@ -242,7 +367,7 @@ struct DenseBatchRows {
             }
         }
         for (int c = lane_id(); c < m; c += kWave) {
-            const T e = row[c];
+            const T e = row[col.at(c)];
             if (!dense_entry_valid(e)) continue;
             const double v = dense_widen(e);
             const double cost = maximize ? v : v * -1.0;
@@ -261,7 +386,7 @@ struct DenseBatchRows {
                     continue;
                 }
             }
-            selv[i] = j >= 0 ? dense_widen(A[(size_t)i * (size_t)M + j]) : 0.0;
+            selv[i] = j >= 0 ? dense_widen(A[(size_t)i * (size_t)M + col.at(j)]) : 0.0;
         }
     }
 
@@ -281,6 +406,11 @@ struct DenseBatchRows {
     __device__ __forceinline__ int64_t meta_nnz() const { return (int64_t)nvalid; }
 };
 
+template <class T, bool Out>
+struct RowsBidLanes<DenseBatchRows<T, Out, true>> {
+    static constexpr bool value = true;
+};
+
 template <class T>
 __global__ __launch_bounds__(1024) void k_dense_batch_solve(DenseBatchArgs a) {
     const int b = blockIdx.x;
@@ -296,11 +426,18 @@ __global__ __launch_bounds__(1024) void k_dense_batch_solve(DenseBatchArgs a) {
 // ---- status mode (misslap_solve_dense_batch_status): a verdict per problem instead of all or nothing
 
 struct DenseBatchStatusArgs {
+    static constexpr bool kStrided = false;
     DenseBatchArgs d;      // d.shapes: the check pass's sanitised shapes (never null)
     const int *card;       // [B] the guard's cardinalities, or null: no guard in this call
     int fast;              // eps_start = 1 / n_b of each problem (auction_.pyx:568-569)
     int *status;           // [B] MISSLAP_BATCH_STATUS_*
     int *matching_size;    // [B] or null: the guard's cardinality, -1 where it did not run
+};
+
+// ... and of the strided family: d.mat is the view's first element, d.N / d.M its extents
+struct DenseStridedStatusArgs : DenseBatchStatusArgs {
+    static constexpr bool kStrided = true;
+    DenseStrides str;
 };
 
 // The dense checks of a verdict, in first_error's order (abi_dense_batch.hpp); batch_verdict adds the shared rest.
@@ -314,9 +451,9 @@ __device__ __forceinline__ int dense_batch_verdict(const DenseBatchCheck &c, int
 
 // k_dense_batch_solve with the verdict formed here, from what the check pass and the guard left on the device.  A
 // condemned problem's workgroup writes the defined outputs and leaves before any LDS state exists; the others run the
-// same batch_solve on the same row source.
-template <class T>
-__global__ __launch_bounds__(1024) void k_dense_batch_solve_status(DenseBatchStatusArgs a) {
+// same batch_solve on the same row source.  Args: DenseBatchStatusArgs, or DenseStridedStatusArgs for the strided family.
+template <class T, class Args = DenseBatchStatusArgs>
+__global__ __launch_bounds__(1024) void k_dense_batch_solve_status(Args a) {
     const int b = blockIdx.x;
     const int n = a.d.shapes[2 * b], m = a.d.shapes[2 * b + 1];
     const DenseBatchCheck ck = a.d.chk[b];
@@ -330,21 +467,41 @@ __global__ __launch_bounds__(1024) void k_dense_batch_solve_status(DenseBatchSta
     BatchSolveArgs s = a.d.s;
     if (a.fast) batch_fast_eps(s, n);
     T vals[kDenseBatchCols];
-    const DenseBatchRows<T> rows{static_cast<const T *>(a.d.mat) + (size_t)b * (size_t)a.d.N * (size_t)a.d.M, a.d.M, m,
-                                 s.maximize, ck.mref, ck.nvalid, vals};
-    batch_solve(s, rows, n, m, ck.absmax_bits);
+    if constexpr (Args::kStrided) {
+        // a unit column stride is the contiguous row source with sN for its row stride (the same bid, instruction for
+        // instruction); any other takes the strided one.  The branch is uniform.
+        const T *A = static_cast<const T *>(a.d.mat) + (size_t)b * (size_t)a.str.sB;
+        if (a.str.sM == 1) {
+            const DenseBatchRows<T> rows{A, a.str.sN, m, s.maximize, ck.mref, ck.nvalid, vals};
+            batch_solve(s, rows, n, m, ck.absmax_bits);
+        } else {
+            const DenseBatchRows<T, false, true> rows{A, a.str.sN, m, s.maximize, ck.mref, ck.nvalid, vals, {},
+                                                      {a.str.sM, a.str.lane_min_K}};
+            batch_solve(s, rows, n, m, ck.absmax_bits);
+        }
+    } else {
+        const DenseBatchRows<T> rows{static_cast<const T *>(a.d.mat) + (size_t)b * (size_t)a.d.N * (size_t)a.d.M, a.d.M, m,
+                                     s.maximize, ck.mref, ck.nvalid, vals};
+        batch_solve(s, rows, n, m, ck.absmax_bits);
+    }
 }
 
 
 // ---- outside mode (misslap_solve_dense_batch_outside): an outside option per row, for partial assignments
 
 struct DenseOutsideArgs {
+    static constexpr bool kStrided = false;
     DenseBatchStatusArgs t;  // t.d.s: Ms = M + N (the carve), p0 / p0_ld the staged augmented prices, prices null;
                              // t.card null: no guard in this call
     const double *outside;   // [B] (outside_ld == 0) or [B][outside_ld]
     long long outside_ld;
     double *prices;          // [B][M] or null: the real columns
     double *outside_prices;  // [B][N] or null
+};
+
+struct DenseStridedOutsideArgs : DenseOutsideArgs {
+    static constexpr bool kStrided = true;
+    DenseStrides str;
 };
 
 // The checks of an outside verdict in their order; EMPTY_ROW, TOO_FEW_VALUES and INFEASIBLE cannot occur.
@@ -356,9 +513,9 @@ __device__ __forceinline__ int dense_outside_verdict(const DenseBatchCheck &c, i
 }
 
 // The solve of the outside mode: the verdict, batch_solve on the n x (m + n) problem, then the outputs in the caller's
-// terms (batch_outside_outputs).
-template <class T>
-__global__ __launch_bounds__(1024) void k_dense_outside_solve(DenseOutsideArgs a) {
+// terms (batch_outside_outputs).  Args: DenseOutsideArgs, or DenseStridedOutsideArgs for the strided family.
+template <class T, class Args = DenseOutsideArgs>
+__global__ __launch_bounds__(1024) void k_dense_outside_solve(Args a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
     const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
     const DenseBatchArgs &d = a.t.d;
@@ -378,15 +535,28 @@ __global__ __launch_bounds__(1024) void k_dense_outside_solve(DenseOutsideArgs a
     if (a.t.fast) batch_fast_eps(s, n);
     T vals[kDenseBatchCols];
     const double *O = a.outside + (a.outside_ld ? (size_t)b * (size_t)a.outside_ld : (size_t)b);
-    const DenseBatchRows<T, true> rows{static_cast<const T *>(d.mat) + (size_t)b * (size_t)d.N * (size_t)d.M,
-                                       d.M,
-                                       m,
-                                       s.maximize,
-                                       m + n,
-                                       ck.nvalid + (unsigned long long)n,
-                                       vals,
-                                       {O, a.outside_ld ? 1 : 0}};
-    batch_solve(s, rows, n, m + n, ck.absmax_bits);
+    if constexpr (Args::kStrided) {  // (as in k_dense_batch_solve_status)
+        const T *A = static_cast<const T *>(d.mat) + (size_t)b * (size_t)a.str.sB;
+        const unsigned long long nv = ck.nvalid + (unsigned long long)n;
+        if (a.str.sM == 1) {
+            const DenseBatchRows<T, true> rows{A, a.str.sN, m, s.maximize, m + n, nv, vals, {O, a.outside_ld ? 1 : 0}};
+            batch_solve(s, rows, n, m + n, ck.absmax_bits);
+        } else {
+            const DenseBatchRows<T, true, true> rows{A, a.str.sN, m, s.maximize, m + n, nv, vals, {O, a.outside_ld ? 1 : 0},
+                                                     {a.str.sM, a.str.lane_min_K}};
+            batch_solve(s, rows, n, m + n, ck.absmax_bits);
+        }
+    } else {
+        const DenseBatchRows<T, true> rows{static_cast<const T *>(d.mat) + (size_t)b * (size_t)d.N * (size_t)d.M,
+                                           d.M,
+                                           m,
+                                           s.maximize,
+                                           m + n,
+                                           ck.nvalid + (unsigned long long)n,
+                                           vals,
+                                           {O, a.outside_ld ? 1 : 0}};
+        batch_solve(s, rows, n, m + n, ck.absmax_bits);
+    }
     batch_outside_outputs(s_raw, d.s, b, n, m, M, N, po, oo, tid, nt);
 }
 

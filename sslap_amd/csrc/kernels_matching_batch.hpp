@@ -19,7 +19,9 @@
 // F16, Bf16: misslap_options.mat_dtype), entry iff v >= 0 by bit pattern in that type (dense_entry_valid: NaN is not an
 // entry, -0.0 and +inf are), or (c) the padded candidate lists of the ELL batch (kernels_ell_batch.hpp): the loc source
 // with implicit row bounds u * K .. (u + 1) * K and a unit-stride column read of index type E (int, long long), a
-// negative column being a hole that no step visits.  No value is ever widened here: only the pattern is read.
+// negative column being a hole that no step visits, or (d) a strided dense stack: source (b) with entry (b, i, j) at
+// mat[b * sB + i * sN + j * sM] for run-time strides >= 0 (the guard of the strided dense solves and
+// misslap_matching_dense_batch_strided).  No value is ever widened here: only the pattern is read.
 #pragma once
 
 namespace misslap {
@@ -28,7 +30,7 @@ constexpr int kMatchBatchMaxDim = MISSLAP_MATCHING_BATCH_MAX_DIM;
 constexpr int kMatchBatchThreads = 256;
 constexpr int kMatchInf = INT_MAX;  // the reference's inf of Dist
 constexpr int kMatchBatchMaxEntries = INT_MAX - 2 * kWave;  // entries of one graph
-enum class MatchSrc { Loc, Dense, Ell };  // where k_matching_batch reads its adjacency from
+enum class MatchSrc { Loc, Dense, Ell, DenseStrided };  // where k_matching_batch reads its adjacency from
 
 // per graph of a packed loc, from k_matching_batch_check
 struct MatchBatchCheck {
@@ -56,6 +58,7 @@ struct MatchBatchArgs {
     long long left_ld;
     int *right;                    // [B][right_ld] or null
     long long right_ld;
+    long long sB, sN, sM;          // source (d): the element strides of the stack (the other sources do not read them)
 };
 
 // Per graph: the maxima (n = max row + 1, m = max column + 1, feasibility_.pyx:245-246) and the first entry that
@@ -120,7 +123,8 @@ __device__ __forceinline__ void match_bfs_visit(int v, int L, const int *pair_v,
 
 template <MatchSrc kSrc, class E = double>
 __global__ __launch_bounds__(kMatchBatchThreads) void k_matching_batch(MatchBatchArgs a) {
-    constexpr bool kDense = kSrc == MatchSrc::Dense, kEll = kSrc == MatchSrc::Ell, kLoc = kSrc == MatchSrc::Loc;
+    constexpr bool kStrided = kSrc == MatchSrc::DenseStrided, kDense = kSrc == MatchSrc::Dense || kStrided;
+    constexpr bool kEll = kSrc == MatchSrc::Ell, kLoc = kSrc == MatchSrc::Loc;
     const int b = blockIdx.x, tid = threadIdx.x, T = blockDim.x, lane = lane_id(), wave = tid >> 6, nw = T >> 6;
     int n = 0, m = 0;
     long long s = 0;
@@ -129,7 +133,7 @@ __global__ __launch_bounds__(kMatchBatchThreads) void k_matching_batch(MatchBatc
     if (kDense) {
         n = a.shapes ? a.shapes[2 * b] : (int)a.N;
         m = a.shapes ? a.shapes[2 * b + 1] : (int)a.M;
-        A = static_cast<const E *>(a.mat) + (size_t)b * (size_t)a.N * (size_t)a.M;
+        A = static_cast<const E *>(a.mat) + (kStrided ? (size_t)b * (size_t)a.sB : (size_t)b * (size_t)a.N * (size_t)a.M);
     } else if (kEll) {
         // clean: n_b within the stack, no empty row, every column within the carve (none negative: those are holes)
         const EllBatchCheck c = a.echk[b];
@@ -181,6 +185,11 @@ __global__ __launch_bounds__(kMatchBatchThreads) void k_matching_batch(MatchBatc
     // the stored entries (ELL: the slots) of row u: g_begin(u) .. g_end(u)
     auto g_begin = [=](int u) { return kDense ? 0 : kEll ? u * ek : row_ptr[u]; };
     auto g_end = [=](int u) { return kDense ? m : kEll ? (u + 1) * ek : row_ptr[u + 1]; };
+    // a dense stack's entry (u, c), in 64 bits
+    const size_t row_stride = kStrided ? (size_t)a.sN : (size_t)a.M;
+    auto dense_at = [=](int u, int c) {
+        return A[(size_t)u * row_stride + (kStrided ? (size_t)c * (size_t)a.sM : (size_t)c)];
+    };
 
     for (int i = tid; i < n; i += T) pair_u[i] = -1;
     for (int j = tid; j < m; j += T) pair_v[j] = -1;
@@ -217,9 +226,9 @@ __global__ __launch_bounds__(kMatchBatchThreads) void k_matching_batch(MatchBatc
             bool found = false;
             if constexpr (kDense) {
                 for (int x = qs + wave; x < qe; x += nw) {
-                    const E *row = A + (size_t)queue[x] * (size_t)a.M;
+                    const int u = queue[x];
                     for (int c = lane; c < m; c += kWave)
-                        if (dense_entry_valid(row[c])) match_bfs_visit(c, L, pair_v, dist, queue, &s_tail, found);
+                        if (dense_entry_valid(dense_at(u, c))) match_bfs_visit(c, L, pair_v, dist, queue, &s_tail, found);
                 }
             } else if (lane_rows) {
                 for (int x = qs + tid; x < qe; x += T) {
@@ -269,7 +278,7 @@ __global__ __launch_bounds__(kMatchBatchThreads) void k_matching_batch(MatchBatc
                             const int pos = g + lane;
                             int cv = -1;
                             if (pos < g1) {
-                                if constexpr (kDense) cv = dense_entry_valid(A[(size_t)u * (size_t)a.M + pos]) ? pos : -1;
+                                if constexpr (kDense) cv = dense_entry_valid(dense_at(u, pos)) ? pos : -1;
                                 else cv = col_of(pos);
                             }
                             int cp = -1;

@@ -14,7 +14,8 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._batch import _check_shapes, _check_stack, _decode_meta, _is_device_tensor, _new_meta, _solve_options, _starting_prices
+from ._batch import (_check_shapes, _check_stack, _decode_meta, _is_device_tensor, _new_meta, _solve_options, _stack_strides,
+                     _starting_prices)
 
 MAX_DIM = _lib.DENSE_BATCH_MAX_DIM
 
@@ -66,8 +67,8 @@ def auction_solve_batch(mats, problem="min", eps_start=0., max_iter=1000000, fas
                         shapes=None, prices=None, errors="raise", mat_dtype="float64", outside=None):
     """Solve B independent dense problems in one call, one workgroup per problem.
 
-    mats: float64 (or mat_dtype, below) (B, N, M), a numpy array or a contiguous tensor on the device (read in place, ordered behind
-    torch.cuda.current_stream()); entries v >= 0 are edges, anything else (-1, NaN) is not.  shapes: optional int
+    mats: float64 (or mat_dtype, below) (B, N, M), a numpy array or a tensor on the device (read in place, whatever its
+    strides: see "strided stacks" below; ordered behind torch.cuda.current_stream()); entries v >= 0 are edges, anything else (-1, NaN) is not.  shapes: optional int
     (B, 2); problem b is then mats[b, :n_b, :m_b].  prices: optional float64 (B, M) starting prices (of the maximised
     problem) as AuctionSolver.resolve takes them.  N, M <= MISSLAP_DENSE_BATCH_MAX_DIM.
 
@@ -86,7 +87,20 @@ def auction_solve_batch(mats, problem="min", eps_start=0., max_iter=1000000, fas
     bit the float64 result on the widened stack (mats.astype(float64) / mats.double()).  An entry is valid iff it is
     >= 0 in its own type.  prices and every output keep their types.  numpy has no bfloat16, so a bfloat16 stack is a
     device tensor.  Only this call and hopcroft_solve_batch(mats=) take the keyword: auction_solve(mat=), from_matrix
-    and the sparse batch take float64, and a strided (non-contiguous) stack is not accepted.
+    and the sparse batch take float64.
+
+    Strided stacks: a device tensor of any non-negative element strides is read where it lies -- cost.transpose(1, 2)
+    (more rows than columns: the solver assigns every row and needs n <= m), a slice of a wider buffer
+    (buf[:, r0:r0 + N, c0:c0 + M], buf[::2], a padded leading dimension) or one.expand(B, N, M) (the same costs from B
+    starting prices or outside values; batch stride 0) -- in every mode, with shapes (which refer to the view), prices,
+    fast, outside and all four mat_dtypes, and in hopcroft_solve_batch(mats=).  The result is bit for bit that of the
+    same call on mats.contiguous(); nothing is copied or converted, only elements of the view are read, and the tensor's
+    storage is never written (misslap_solve_dense_batch_status_strided / _outside_strided).  A contiguous tensor takes
+    exactly the calls it always took, and a numpy array is uploaded through np.ascontiguousarray as before.  The default
+    mode's own call (all or nothing, with a host guard that reads the stack back) is not taught strides: for a strided
+    device stack errors="raise" runs the errors="status" call and then raise_for_status, which raises the default
+    mode's message for the first failing problem, and returns the status-mode dict (device tensors; meta through
+    batch_meta_to_host).
 
     raise_for_status(res) raises what the default mode would have raised.  With a device stack the call is
     stream-ordered: its kernels go onto torch.cuda.current_stream(mats.device), it waits for nothing, and sol, prices,
@@ -124,17 +138,20 @@ def auction_solve_batch(mats, problem="min", eps_start=0., max_iter=1000000, fas
     if errors not in ("raise", "status"):
         raise ValueError(f"errors must be 'raise' or 'status', got {errors!r}")
     B, N, M, on_device, dtype = _check_stack(mats, mat_dtype)
+    strides = _stack_strides(mats, on_device)
     if N > MAX_DIM or M > MAX_DIM:
         raise ValueError(f"problems of {N} x {M}: auction_solve_batch takes at most {MAX_DIM} x {MAX_DIM} "
                          f"(MISSLAP_DENSE_BATCH_MAX_DIM); solve larger problems with from_matrix / solve_batch")
     if outside is not None:
-        res = _solve_outside(mats, B, N, M, on_device, problem, eps_start, max_iter, fast, shapes, prices, dtype, outside)
+        res = _solve_outside(mats, B, N, M, on_device, problem, eps_start, max_iter, fast, shapes, prices, dtype, outside,
+                             strides)
         return raise_for_status(res) if errors == "raise" else res
     if fast is None:  # (resolved here: the library gets a plain flag)
         fast = False
-    if errors == "status":
-        return _solve_status(mats, B, N, M, on_device, problem, eps_start, max_iter, fast, cardinality_check, shapes,
-                             prices, dtype)
+    if errors == "status" or strides is not None:  # (the default mode's own call reads a contiguous stack only)
+        res = _solve_status(mats, B, N, M, on_device, problem, eps_start, max_iter, fast, cardinality_check, shapes,
+                            prices, dtype, strides)
+        return res if errors == "status" else raise_for_status(res)
     shp = _check_shapes(shapes, B, N, M, "problem")
     ns = shp[:, 0] if shp is not None else np.full(B, N, dtype=np.int32)
     e = float(eps_start)
@@ -174,9 +191,9 @@ def _eps(eps_start):
 
 
 def _solve_status(mats, B, N, M, on_device, problem, eps_start, max_iter, fast, cardinality_check, shapes, prices,
-                  dtype):
-    """errors="status" of auction_solve_batch (misslap_solve_dense_batch_status); the whole-call checks in the default
-    mode's order: shapes, eps_start, prices."""
+                  dtype, strides=None):
+    """errors="status" of auction_solve_batch (misslap_solve_dense_batch_status; with the strides of a non-contiguous
+    device stack its strided form); the whole-call checks in the default mode's order: shapes, eps_start, prices."""
     check = 1 if cardinality_check else 0
     if not on_device:  # synchronous: the library uploads, uses its own scratch and waits once
         shp = _check_shapes(shapes, B, N, M, "problem")
@@ -218,18 +235,22 @@ def _solve_status(mats, B, N, M, on_device, problem, eps_start, max_iter, fast, 
         msize = torch.empty(B, dtype=torch.int32, device=dev)
         rec = torch.empty((B, C.sizeof(_lib.DenseBatchMeta)), dtype=torch.uint8, device=dev)
     info = _lib.DenseBatchInfo()
-    _lib.check(lib.misslap_solve_dense_batch_status(
-        B, N, M, mats.data_ptr(), None if shp is None else shp.data_ptr(), 1 if fast else 0, p_ptr, check, C.byref(opts),
-        C.c_void_p(int(stream.cuda_stream)), work.data_ptr(), nbytes, sol.data_ptr(), pout.data_ptr(), 1, status.data_ptr(),
-        msize.data_ptr(), rec.data_ptr(), C.byref(info)))
+    rest = (mats.data_ptr(), None if shp is None else shp.data_ptr(), 1 if fast else 0, p_ptr, check, C.byref(opts),
+            C.c_void_p(int(stream.cuda_stream)), work.data_ptr(), nbytes, sol.data_ptr(), pout.data_ptr(), 1,
+            status.data_ptr(), msize.data_ptr(), rec.data_ptr(), C.byref(info))
+    if strides is None:
+        _lib.check(lib.misslap_solve_dense_batch_status(B, N, M, *rest))
+    else:
+        _lib.check(lib.misslap_solve_dense_batch_status_strided(B, N, M, *strides, *rest))
     # the workspace and the inputs stay referenced by the result: nothing of this call is recycled before it
     return dict(sol=sol, prices=pout, status=status, matching_size=msize, meta=_meta_views(rec), shapes=shp,
                 stack=(N, M), records=rec, info=info, stream=stream, keep=(work, mats, p))
 
 
-def _solve_outside(mats, B, N, M, on_device, problem, eps_start, max_iter, fast, shapes, prices, dtype, outside):
-    """auction_solve_batch(outside=) in either mode (misslap_solve_dense_batch_outside): the result dict of the status
-    mode plus outside_prices.  The whole-call checks in the status mode's order, then outside."""
+def _solve_outside(mats, B, N, M, on_device, problem, eps_start, max_iter, fast, shapes, prices, dtype, outside,
+                   strides=None):
+    """auction_solve_batch(outside=) in either mode (misslap_solve_dense_batch_outside; with the strides of a
+    non-contiguous device stack its strided form): the result dict of the status mode plus outside_prices.  The whole-call checks in the status mode's order, then outside."""
     from .ell_batch import _check_outside, _send
     if not on_device:  # synchronous: the library uploads, uses its own scratch and waits once
         shp = _check_shapes(shapes, B, N, M, "problem")
@@ -282,10 +303,13 @@ def _solve_outside(mats, B, N, M, on_device, problem, eps_start, max_iter, fast,
         msize = torch.empty(B, dtype=torch.int32, device=dev)
         rec = torch.empty((B, C.sizeof(_lib.DenseBatchMeta)), dtype=torch.uint8, device=dev)
     info = _lib.DenseBatchInfo()
-    _lib.check(lib.misslap_solve_dense_batch_outside(
-        B, N, M, mats.data_ptr(), None if shp is None else shp.data_ptr(), 1 if fast else 0, p_ptr, C.byref(opts),
-        C.c_void_p(int(stream.cuda_stream)), work.data_ptr(), nbytes, d_out.data_ptr(), out_ld, sol.data_ptr(),
-        pout.data_ptr(), oout.data_ptr(), 1, status.data_ptr(), msize.data_ptr(), rec.data_ptr(), C.byref(info)))
+    rest = (mats.data_ptr(), None if shp is None else shp.data_ptr(), 1 if fast else 0, p_ptr, C.byref(opts),
+            C.c_void_p(int(stream.cuda_stream)), work.data_ptr(), nbytes, d_out.data_ptr(), out_ld, sol.data_ptr(),
+            pout.data_ptr(), oout.data_ptr(), 1, status.data_ptr(), msize.data_ptr(), rec.data_ptr(), C.byref(info))
+    if strides is None:
+        _lib.check(lib.misslap_solve_dense_batch_outside(B, N, M, *rest))
+    else:
+        _lib.check(lib.misslap_solve_dense_batch_outside_strided(B, N, M, *strides, *rest))
     # the workspace and the inputs stay referenced by the result: nothing of this call is recycled before it
     return dict(sol=sol, prices=pout, outside_prices=oout, status=status, matching_size=msize, meta=_meta_views(rec),
                 shapes=shp, stack=(N, M), outside=d_out, records=rec, info=info, stream=stream, keep=(work, mats, p))

@@ -10,7 +10,8 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._batch import _check_offsets, _check_shapes, _check_stack, _is_device_tensor, _mat_dtype_name, _maxima, _options
+from ._batch import (_check_offsets, _check_shapes, _check_stack, _is_device_tensor, _mat_dtype_name, _maxima, _options,
+                     _stack_strides)
 
 MAX_DIM = _lib.MATCHING_BATCH_MAX_DIM
 
@@ -80,7 +81,9 @@ def hopcroft_solve_batch(loc=None, offsets=None, mats=None, shapes=None, mat_dty
           place, ordered behind torch.cuda.current_stream()); graph b is the entries offsets[b]:offsets[b + 1] (a host
           integer array of length B + 1), rows ascending, n_b = max row + 1 and m_b = max column + 1 of the graph.  Or a
           list of per-graph loc numpy arrays, with offsets None.
-    mats: a float64 (B, N, M) stack, numpy or a contiguous device tensor; graph b is mats[b, :n_b, :m_b] with
+    mats: a float64 (B, N, M) stack, numpy or a device tensor of any non-negative strides (a transposed view, a slice,
+          an expanded matrix: read where it lies, misslap_matching_dense_batch_strided; the pairings are those of
+          mats.contiguous()); graph b is mats[b, :n_b, :m_b] with
           (n_b, m_b) = shapes[b] (optional integer (B, 2); default N x M), edge (i, j) iff the entry is >= 0.
           mat_dtype ("float64", "float32", "float16", "bfloat16", or that numpy / torch dtype) names the stack's element
           type, which it must have exactly; the stack is read in place and the pairings are those of the widened stack.
@@ -134,8 +137,12 @@ def hopcroft_solve_batch(loc=None, offsets=None, mats=None, shapes=None, mat_dty
             Mmax, 1 if on_device else 0, C.byref(info))
     lib = _lib.load()
     if mats is not None:
-        _lib.check(lib.misslap_matching_dense_batch(B, N, M, C.c_void_p(src_ptr),
-                                                    None if shp is None else shp.ctypes.data, C.byref(opts), *outs))
+        strides = _stack_strides(mats, on_device)
+        ins = (C.c_void_p(src_ptr), None if shp is None else shp.ctypes.data, C.byref(opts))
+        if strides is None:
+            _lib.check(lib.misslap_matching_dense_batch(B, N, M, *ins, *outs))
+        else:
+            _lib.check(lib.misslap_matching_dense_batch_strided(B, N, M, *strides, *ins, *outs))
     else:
         _lib.check(lib.misslap_matching_batch(B, C.c_void_p(src_ptr), off.ctypes.data, C.byref(opts), *outs))
     return dict(size=size, left_pairings=left, right_pairings=right, n_rows=n_rows, n_cols=n_cols,
