@@ -1,7 +1,10 @@
-"""Plumbing shared by the one-workgroup-per-problem wrappers: dense_batch, sparse_batch and matching_batch.
+"""Plumbing shared by the one-workgroup-per-problem wrappers: dense_batch, sparse_batch, ell_batch and matching_batch.
 
-Argument checks that raise before the library is called, the options of the call and the decoding of its per-problem
-records.  The library is reached through `_lib.load()` at call time, never through a name bound here.
+Argument checks that raise before the library is called, the options of the call, the arrays of either side (`_empty`,
+`_ptr`, `_send`), the outputs and the argument tail of a status-mode call (`_StatusCall`), the decoding of its
+per-problem records, and what takes a status-mode result of any layout: batch_meta_to_host and raise_for_status.  The
+library is reached through `_lib.load()` at call time, never through a name bound here; torch is imported where a
+device tensor is at hand, never with the package.
 """
 import ctypes as C
 import os
@@ -14,6 +17,47 @@ from .auction_solve import _ENV_DEVICE, _cname
 
 def _is_device_tensor(x):
     return hasattr(x, "data_ptr") and getattr(x, "is_cuda", False)
+
+
+def _empty(shape, dtype, dev=None):
+    """An uninitialised array of a numpy dtype: a numpy array on the host (dev None), else a tensor on dev."""
+    if dev is None:
+        return np.empty(shape, dtype=dtype)
+    import torch
+    return torch.empty(shape, dtype=getattr(torch, np.dtype(dtype).name), device=dev)
+
+
+def _ptr(x):
+    """The address of a numpy array or of a tensor; None for None."""
+    if x is None:
+        return None
+    return x.ctypes.data if isinstance(x, np.ndarray) else x.data_ptr()
+
+
+def _contiguous(x):
+    """x as the library reads it, row after row: a numpy array or a tensor, the same object where it already is; None
+    for None."""
+    if x is None:
+        return None
+    return np.ascontiguousarray(x) if isinstance(x, np.ndarray) else x.contiguous()
+
+
+def _send(a, dev):
+    """A host array to dev from pinned memory, on the current stream of dev and without a wait (torch takes no
+    read-only array: a copy then).  None and a device tensor pass through, and so does everything with host input (dev
+    None)."""
+    if dev is None or not isinstance(a, np.ndarray):
+        return a
+    import torch
+    with torch.cuda.device(dev):
+        return torch.from_numpy(a if a.flags.writeable else a.copy()).pin_memory().to(dev, non_blocking=True)
+
+
+def _eps(eps_start):
+    e = float(eps_start)
+    if e != e:
+        raise ValueError("eps_start is NaN")
+    return e
 
 
 # mat_dtype: the element types a dense stack may have (MISSLAP_DTYPE_* of include/misslap.h)
@@ -89,6 +133,58 @@ def _check_shapes(shapes, B, N, M, what):
         b = int(np.flatnonzero(bad)[0])
         raise ValueError(f"{what} {b}: shape ({int(s[b, 0])}, {int(s[b, 1])}) outside 1 .. {N} x 1 .. {M}")
     return np.ascontiguousarray(s, dtype=np.int32)
+
+
+def _check_device_shapes(shp, B, dev):
+    """A device shapes tensor of a status-mode call: contiguous int32 (B, 2) on the stack's device.  Its values are the
+    library's to judge."""
+    import torch
+    if shp.dtype != torch.int32 or tuple(shp.shape) != (B, 2) or shp.device != dev or not shp.is_contiguous():
+        raise ValueError(f"a device shapes tensor must be contiguous int32 of shape ({B}, 2) on {dev}, got "
+                         f"{shp.dtype} {tuple(shp.shape)} on {shp.device}")
+    return shp
+
+
+def _scalar_outside(outside, B, dev, nonneg=False):
+    """One finite float as the outside value of every row: float64 (B,) where the input lives (a fill on dev, nothing
+    is sent).  nonneg: it must also be >= 0 (the dense batch, where a negative entry is an absent one)."""
+    if isinstance(outside, (bool, str, bytes)) or not isinstance(outside, (int, float, np.integer, np.floating)):
+        raise TypeError("outside must be a float, a float64 numpy array or a float64 tensor on the device")
+    x = float(outside)
+    if not np.isfinite(x):
+        raise ValueError(f"outside must be finite, got {x!r}")
+    if nonneg and not x >= 0:
+        raise ValueError(f"outside must be >= 0 (a negative entry of a dense matrix is an absent one), got {x!r}")
+    if dev is not None:
+        import torch
+        return torch.full((B,), x, dtype=torch.float64, device=dev)
+    return np.full(B, x, dtype=np.float64)
+
+
+def _check_outside(outside, B, N, dev, need="cols / vals", src="cols", nonneg=False):
+    """The outside values of a dense or an ELL call: a finite float (_scalar_outside), or float64 (B,) / (B, N) on the
+    host or (with device input, dev) contiguous on the input's device.  Returns (array or tensor, outside_ld); the
+    values are the library's to judge.  need / src: what the input is called in the texts."""
+    if _is_device_tensor(outside):
+        import torch
+        if dev is None:
+            raise TypeError(f"outside on the device needs {need} on the device")
+        if outside.dtype != torch.float64:
+            raise ValueError(f"outside must be float64, got {outside.dtype}")
+        if tuple(outside.shape) not in ((B,), (B, N)):
+            raise ValueError(f"outside must have shape ({B},) or ({B}, {N}), got {tuple(outside.shape)}")
+        if outside.device != dev:
+            raise ValueError(f"outside is on {outside.device}, {src} on {dev}")
+        if not outside.is_contiguous():
+            raise ValueError("a device outside tensor must be contiguous (it is read in place)")
+        return outside, (N if outside.dim() == 2 else 0)
+    if isinstance(outside, np.ndarray):
+        if outside.dtype != np.float64:
+            raise ValueError(f"outside must be float64, got {outside.dtype.name}")
+        if outside.shape not in ((B,), (B, N)):
+            raise ValueError(f"outside must have shape ({B},) or ({B}, {N}), got {outside.shape}")
+        return np.ascontiguousarray(outside), (N if outside.ndim == 2 else 0)
+    return _scalar_outside(outside, B, dev, nonneg), 0
 
 
 def _check_offsets(offsets, nnz, missing):
@@ -222,3 +318,109 @@ def _decode_meta(metas, info):
     meta["gpu"] = dict(threads=int(info.threads), lds_bytes=int(info.lds_bytes), check_ms=float(info.check_ms),
                        matching_ms=float(info.matching_ms), kernel_ms=float(info.solve_ms), wall_ms=float(info.wall_ms))
     return meta
+
+
+# the meta fields a status-mode call on the device returns as views of its record buffer
+_META_VIEWS = ("its", "nreductions", "eCE", "soln_found", "n_assigned", "obj_f64", "start_eps_f32", "final_eps_f32",
+               "n_rows", "n_cols", "nnz", "bids_made")
+
+
+def _meta_views(rec):
+    """The fields of a device buffer of misslap_dense_batch_meta records as column views, one tensor of length B each."""
+    import torch
+    kinds = {C.c_int32: torch.int32, C.c_int64: torch.int64, C.c_uint64: torch.int64, C.c_float: torch.float32,
+             C.c_double: torch.float64}
+    names = dict(start_eps_f32="start_eps", final_eps_f32="final_eps")
+    fields = dict(_lib.DenseBatchMeta._fields_)
+    out = {}
+    for key in _META_VIEWS:
+        f = names.get(key, key)
+        dt = kinds[fields[f]]
+        out[key] = rec.view(dt)[:, getattr(_lib.DenseBatchMeta, f).offset // C.sizeof(fields[f])]
+    return out
+
+
+class _StatusCall:
+    """The outputs of one "verdict per problem" call and the part of its argument list every such entry point shares
+    (batch_stream_call, csrc/abi_batch_stream.hpp):
+
+        head..., *way, [dims...], [outside, outside_ld], *outs
+
+    way = (opts, stream, workspace, workspace_bytes) and outs = (sol, prices_out, [outside_prices_out], out_on_device,
+    status, matching_size, meta, info).  sol is int32 (B, sol_w), prices float64 (B, prices_w), outside_prices float64
+    (B, outside_w) unless outside_w is None.  dev None is the synchronous call on host arrays: the library uploads, uses
+    its own scratch and waits once, and the records are _new_meta's.  On dev the call is ordered on the current stream
+    of dev: every output is a tensor allocated on that stream, the records a (B, sizeof record) uint8 tensor, and the
+    workspace has the bytes lib's `sizing` function names for sizing_args."""
+
+    def __init__(self, lib, opts, B, sol_w, prices_w, outside_w, dev, sizing, sizing_args):
+        self.dev, self.info = dev, _lib.DenseBatchInfo()
+
+        def outputs():
+            self.out = dict(sol=_empty((B, sol_w), np.int32, dev), prices=_empty((B, prices_w), np.float64, dev))
+            if outside_w is not None:
+                self.out["outside_prices"] = _empty((B, outside_w), np.float64, dev)
+            self.out.update(status=_empty(B, np.int32, dev), matching_size=_empty(B, np.int32, dev))
+        if dev is None:
+            outputs()
+            self.rec = _new_meta(B)[0]
+            way, meta = (None, None, 0), C.cast(self.rec, C.c_void_p)
+        else:
+            import torch
+            nbytes = int(getattr(lib, sizing)(*sizing_args))
+            with torch.cuda.device(dev):
+                self.stream = torch.cuda.current_stream(dev)
+                self.work = _empty(nbytes, np.uint8, dev)
+                outputs()
+                self.rec = _empty((B, C.sizeof(_lib.DenseBatchMeta)), np.uint8, dev)
+            way, meta = (C.c_void_p(int(self.stream.cuda_stream)), self.work.data_ptr(), nbytes), self.rec.data_ptr()
+        self.way = (C.byref(opts),) + way
+        arrays = [_ptr(x) for x in self.out.values()]
+        self.outs = (*arrays[:-2], 0 if dev is None else 1, *arrays[-2:], meta, C.byref(self.info))
+
+    def result(self, keep, **own):
+        """The result dict after the call: the outputs, meta and the layout's `own` keys; on a device also records, info,
+        stream and keep -- the workspace and `keep` (the inputs and what was sent for them) stay referenced by the result,
+        so nothing of this call is recycled before it."""
+        if self.dev is None:
+            return dict(self.out, meta=_decode_meta(self.rec, self.info), **own)
+        return dict(self.out, meta=_meta_views(self.rec), **own, records=self.rec, info=self.info, stream=self.stream,
+                    keep=(self.work, *keep))
+
+
+def batch_meta_to_host(res):
+    """The meta of a status-mode result as the default mode returns it: a dict of length-B numpy arrays with the
+    Python-rounded obj, start_eps and final_eps.  For a device result this waits for the call's stream once."""
+    if "records" not in res:
+        return res["meta"]
+    res["stream"].synchronize()
+    raw = res["records"].cpu().numpy()
+    metas = (_lib.DenseBatchMeta * raw.shape[0]).from_buffer_copy(raw.tobytes())
+    return _decode_meta(metas, res["info"])
+
+
+def _host(x):
+    return x if isinstance(x, np.ndarray) else x.cpu().numpy()
+
+
+# layout -> _status_error(res, b, code, n, m, card), the exception of problem b of a result of that layout (n, m: the
+# record's n_rows and n_cols; card: its matching_size).  Each layout's module enters its own when it is imported.
+_STATUS_ERRORS = {}
+
+
+def raise_for_status(res):
+    """Raise, for the first problem of a status-mode result whose status is not 0, the ValueError the default mode
+    raises for the same batch ("problem <b>: ..."); return res when every status is 0.  For a result of
+    auction_solve_sparse_batch: what its default mode raises with cardinality_check=False for that check, a
+    ZeroDivisionError for `fast` with N = 0 included.  For a result of auction_solve_ell_batch: the ValueError its own
+    default mode raises."""
+    if "stream" in res:
+        res["stream"].synchronize()
+    status = _host(res["status"])
+    bad = np.flatnonzero(status)
+    if bad.size == 0:
+        return res
+    b = int(bad[0])
+    raise _STATUS_ERRORS[res.get("layout", "dense")](
+        res, b, int(status[b]), int(_host(res["meta"]["n_rows"])[b]), int(_host(res["meta"]["n_cols"])[b]),
+        int(_host(res["matching_size"])[b]))

@@ -14,8 +14,9 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._batch import (_check_shapes, _check_stack, _decode_meta, _is_device_tensor, _new_meta, _solve_options, _stack_strides,
-                     _starting_prices)
+from ._batch import (_STATUS_ERRORS, _StatusCall, _check_device_shapes, _check_outside, _check_shapes, _check_stack,
+                     _decode_meta, _empty, _eps, _host, _is_device_tensor, _new_meta, _ptr, _send, _solve_options,
+                     _stack_strides, _starting_prices, batch_meta_to_host, raise_for_status)  # (the last two: also for import from here)
 
 MAX_DIM = _lib.DENSE_BATCH_MAX_DIM
 
@@ -33,9 +34,6 @@ _STATUS_TEXT = {
     _lib.BATCH_STATUS_BAD_OUTSIDE: "the outside value of row {row} is {value!r}: it must be >= 0 (a negative value or a NaN "
                                    "would be an absent entry)",
 }
-# the meta fields a status-mode call on the device returns as views of its record buffer
-_META_VIEWS = ("its", "nreductions", "eCE", "soln_found", "n_assigned", "obj_f64", "start_eps_f32", "final_eps_f32",
-               "n_rows", "n_cols", "nnz", "bids_made")
 
 
 def dense_to_augmented(mats, shapes=None, outside=0.):
@@ -154,226 +152,103 @@ def auction_solve_batch(mats, problem="min", eps_start=0., max_iter=1000000, fas
         return res if errors == "status" else raise_for_status(res)
     shp = _check_shapes(shapes, B, N, M, "problem")
     ns = shp[:, 0] if shp is not None else np.full(B, N, dtype=np.int32)
-    e = float(eps_start)
-    if e != e:
-        raise ValueError("eps_start is NaN")
-    p, p_ptr, _ = _starting_prices(prices, B, M, True, on_device, mats, "mats")
-    keep = [p]  # buffers that must live through the call
+    e = _eps(eps_start)
+    p, p_ptr, _ = _starting_prices(prices, B, M, True, on_device, mats, "mats")  # (p lives through the call)
     eps_b = None
     if fast:  # auction_.pyx:568-569: eps_start = 1 / N of each problem, as a C float
         eps_b = (1.0 / ns.astype(np.float64)).astype(np.float32)
     opts = _solve_options(on_device, mats, problem, e, max_iter, dtype)
-    if on_device:
-        import torch
-        sol = torch.empty((B, N), dtype=torch.int32, device=mats.device)
-        pout = torch.empty((B, M), dtype=torch.float64, device=mats.device)
-        sol_ptr, pout_ptr, mat_ptr = sol.data_ptr(), pout.data_ptr(), mats.data_ptr()
-    else:
-        mc = np.ascontiguousarray(mats)
-        keep.append(mc)
-        sol = np.empty((B, N), dtype=np.int32)
-        pout = np.empty((B, M), dtype=np.float64)
-        sol_ptr, pout_ptr, mat_ptr = sol.ctypes.data, pout.ctypes.data, mc.ctypes.data
+    dev = mats.device if on_device else None
+    mc = mats if on_device else np.ascontiguousarray(mats)
+    sol, pout = _empty((B, N), np.int32, dev), _empty((B, M), np.float64, dev)
     metas, info = _new_meta(B)
     _lib.check(_lib.load().misslap_solve_dense_batch(
-        B, N, M, C.c_void_p(mat_ptr), None if shp is None else shp.ctypes.data,
-        None if eps_b is None else eps_b.ctypes.data, None if p_ptr is None else C.c_void_p(p_ptr),
-        1 if cardinality_check else 0, C.byref(opts), C.c_void_p(sol_ptr), C.c_void_p(pout_ptr),
+        B, N, M, C.c_void_p(_ptr(mc)), _ptr(shp), _ptr(eps_b), None if p_ptr is None else C.c_void_p(p_ptr),
+        1 if cardinality_check else 0, C.byref(opts), C.c_void_p(_ptr(sol)), C.c_void_p(_ptr(pout)),
         1 if on_device else 0, metas, C.byref(info)))
     return dict(sol=sol, prices=pout, meta=_decode_meta(metas, info))
 
 
-def _eps(eps_start):
-    e = float(eps_start)
-    if e != e:
-        raise ValueError("eps_start is NaN")
-    return e
+def _shapes(shapes, B, N, M, dev):
+    """shapes of a status-mode call.  With a device stack (dev) a device tensor is read where it lies; a host array is
+    validated as in the default mode and then sent from pinned memory without a wait."""
+    if dev is not None and _is_device_tensor(shapes):
+        return _check_device_shapes(shapes, B, dev)
+    return _send(_check_shapes(shapes, B, N, M, "problem"), dev)
+
+
+def _prices(prices, B, M, mats, dev):
+    """Starting prices of a status-mode call, float64 (B, M), where the stack lives: a host array is checked (dtype and
+    shape) and with a device stack sent from pinned memory without a wait."""
+    if isinstance(prices, np.ndarray):
+        return _send(_starting_prices(prices, B, M, True, False, mats, "mats")[0], dev)
+    return _starting_prices(prices, B, M, True, dev is not None, mats, "mats")[0]
 
 
 def _solve_status(mats, B, N, M, on_device, problem, eps_start, max_iter, fast, cardinality_check, shapes, prices,
                   dtype, strides=None):
     """errors="status" of auction_solve_batch (misslap_solve_dense_batch_status; with the strides of a non-contiguous
     device stack its strided form); the whole-call checks in the default mode's order: shapes, eps_start, prices."""
+    dev = mats.device if on_device else None
     check = 1 if cardinality_check else 0
-    if not on_device:  # synchronous: the library uploads, uses its own scratch and waits once
-        shp = _check_shapes(shapes, B, N, M, "problem")
-        opts = _solve_options(False, mats, problem, _eps(eps_start), max_iter, dtype)
-        p, p_ptr, _ = _starting_prices(prices, B, M, True, False, mats, "mats")
-        mc = np.ascontiguousarray(mats)
-        sol, pout = np.empty((B, N), dtype=np.int32), np.empty((B, M), dtype=np.float64)
-        status, msize = np.empty(B, dtype=np.int32), np.empty(B, dtype=np.int32)
-        metas, info = _new_meta(B)
-        _lib.check(_lib.load().misslap_solve_dense_batch_status(
-            B, N, M, mc.ctypes.data, None if shp is None else shp.ctypes.data, 1 if fast else 0, p_ptr, check,
-            C.byref(opts), None, None, 0, sol.ctypes.data, pout.ctypes.data, 0, status.ctypes.data, msize.ctypes.data,
-            C.cast(metas, C.c_void_p), C.byref(info)))
-        return dict(sol=sol, prices=pout, status=status, matching_size=msize, meta=_decode_meta(metas, info),
-                    shapes=shp, stack=(N, M))
-    import torch
-    dev = mats.device
-    if shapes is None or _is_device_tensor(shapes):
-        shp = shapes
-        if shp is not None and (shp.dtype != torch.int32 or tuple(shp.shape) != (B, 2) or shp.device != dev or
-                                not shp.is_contiguous()):
-            raise ValueError(f"a device shapes tensor must be contiguous int32 of shape ({B}, 2) on {dev}, got "
-                             f"{shp.dtype} {tuple(shp.shape)} on {shp.device}")
-    else:  # a host array: validated as in the default mode, sent from pinned memory without a wait
-        shp = torch.from_numpy(_check_shapes(shapes, B, N, M, "problem")).pin_memory().to(dev, non_blocking=True)
-    opts = _solve_options(True, mats, problem, _eps(eps_start), max_iter, dtype)
-    if isinstance(prices, np.ndarray):
-        _starting_prices(prices, B, M, True, False, mats, "mats")  # (dtype and shape)
-        prices = torch.from_numpy(np.ascontiguousarray(prices)).pin_memory().to(dev, non_blocking=True)
-    p, p_ptr, _ = _starting_prices(prices, B, M, True, True, mats, "mats")
+    shp = _shapes(shapes, B, N, M, dev)
+    opts = _solve_options(on_device, mats, problem, _eps(eps_start), max_iter, dtype)
+    p = _prices(prices, B, M, mats, dev)
+    mc = mats if on_device else np.ascontiguousarray(mats)
     lib = _lib.load()
-    nbytes = int(lib.misslap_dense_batch_workspace_bytes(B, N, M, 0 if p is None else 1, check))
-    with torch.cuda.device(dev):  # (the allocations below are made on the current stream of the stack's device)
-        stream = torch.cuda.current_stream(dev)
-        work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        sol = torch.empty((B, N), dtype=torch.int32, device=dev)
-        pout = torch.empty((B, M), dtype=torch.float64, device=dev)
-        status = torch.empty(B, dtype=torch.int32, device=dev)
-        msize = torch.empty(B, dtype=torch.int32, device=dev)
-        rec = torch.empty((B, C.sizeof(_lib.DenseBatchMeta)), dtype=torch.uint8, device=dev)
-    info = _lib.DenseBatchInfo()
-    rest = (mats.data_ptr(), None if shp is None else shp.data_ptr(), 1 if fast else 0, p_ptr, check, C.byref(opts),
-            C.c_void_p(int(stream.cuda_stream)), work.data_ptr(), nbytes, sol.data_ptr(), pout.data_ptr(), 1,
-            status.data_ptr(), msize.data_ptr(), rec.data_ptr(), C.byref(info))
+    call = _StatusCall(lib, opts, B, N, M, None, dev, "misslap_dense_batch_workspace_bytes",
+                       (B, N, M, 0 if p is None else 1, check))
+    rest = (_ptr(mc), _ptr(shp), 1 if fast else 0, _ptr(p), check, *call.way, *call.outs)
     if strides is None:
         _lib.check(lib.misslap_solve_dense_batch_status(B, N, M, *rest))
     else:
         _lib.check(lib.misslap_solve_dense_batch_status_strided(B, N, M, *strides, *rest))
-    # the workspace and the inputs stay referenced by the result: nothing of this call is recycled before it
-    return dict(sol=sol, prices=pout, status=status, matching_size=msize, meta=_meta_views(rec), shapes=shp,
-                stack=(N, M), records=rec, info=info, stream=stream, keep=(work, mats, p))
+    return call.result((mats, shp, p), shapes=shp, stack=(N, M))
 
 
 def _solve_outside(mats, B, N, M, on_device, problem, eps_start, max_iter, fast, shapes, prices, dtype, outside,
                    strides=None):
     """auction_solve_batch(outside=) in either mode (misslap_solve_dense_batch_outside; with the strides of a
     non-contiguous device stack its strided form): the result dict of the status mode plus outside_prices.  The whole-call checks in the status mode's order, then outside."""
-    from .ell_batch import _check_outside, _send
-    if not on_device:  # synchronous: the library uploads, uses its own scratch and waits once
-        shp = _check_shapes(shapes, B, N, M, "problem")
-        e = _eps(eps_start)
-        p, p_ptr, _ = _starting_prices(prices, B, M, True, False, mats, "mats")
-        out_v, out_ld = _check_outside(outside, B, N, False, None, "mats", "mats", True)
-        if fast is None:
-            fast = not e > 0
-        opts = _solve_options(False, mats, problem, e, max_iter, dtype)
-        mc = np.ascontiguousarray(mats)
-        sol, pout = np.empty((B, N), dtype=np.int32), np.empty((B, M), dtype=np.float64)
-        oout = np.empty((B, N), dtype=np.float64)
-        status, msize = np.empty(B, dtype=np.int32), np.empty(B, dtype=np.int32)
-        metas, info = _new_meta(B)
-        _lib.check(_lib.load().misslap_solve_dense_batch_outside(
-            B, N, M, mc.ctypes.data, None if shp is None else shp.ctypes.data, 1 if fast else 0, p_ptr, C.byref(opts), None,
-            None, 0, out_v.ctypes.data, out_ld, sol.ctypes.data, pout.ctypes.data, oout.ctypes.data, 0, status.ctypes.data,
-            msize.ctypes.data, C.cast(metas, C.c_void_p), C.byref(info)))
-        return dict(sol=sol, prices=pout, outside_prices=oout, status=status, matching_size=msize,
-                    meta=_decode_meta(metas, info), shapes=shp, stack=(N, M), outside=out_v)
-    import torch
-    dev = mats.device
-    if shapes is None or _is_device_tensor(shapes):
-        shp = shapes
-        if shp is not None and (shp.dtype != torch.int32 or tuple(shp.shape) != (B, 2) or shp.device != dev or
-                                not shp.is_contiguous()):
-            raise ValueError(f"a device shapes tensor must be contiguous int32 of shape ({B}, 2) on {dev}, got "
-                             f"{shp.dtype} {tuple(shp.shape)} on {shp.device}")
-    else:  # a host array: validated as in the default mode, sent from pinned memory without a wait
-        shp = _send(_check_shapes(shapes, B, N, M, "problem"), dev)
+    dev = mats.device if on_device else None
+    shp = _shapes(shapes, B, N, M, dev)
     e = _eps(eps_start)
-    if isinstance(prices, np.ndarray):
-        _starting_prices(prices, B, M, True, False, mats, "mats")  # (dtype and shape)
-        prices = _send(np.ascontiguousarray(prices), dev)
-    p, p_ptr, _ = _starting_prices(prices, B, M, True, True, mats, "mats")
-    out_v, out_ld = _check_outside(outside, B, N, True, dev, "mats", "mats", True)
+    p = _prices(prices, B, M, mats, dev)
+    out_v, out_ld = _check_outside(outside, B, N, dev, "mats", "mats", True)
     if fast is None:
         fast = not e > 0
-    opts = _solve_options(True, mats, problem, e, max_iter, dtype)
+    opts = _solve_options(on_device, mats, problem, e, max_iter, dtype)
+    mc = mats if on_device else np.ascontiguousarray(mats)
+    d_out = _send(out_v, dev)
     lib = _lib.load()
-    nbytes = int(lib.misslap_dense_batch_outside_workspace_bytes(B, N, M, 0 if p is None else 1))
-    with torch.cuda.device(dev):  # (the allocations and copies below are made on the current stream of the stack's device)
-        stream = torch.cuda.current_stream(dev)
-        d_out = _send(out_v, dev)
-        work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        sol = torch.empty((B, N), dtype=torch.int32, device=dev)
-        pout = torch.empty((B, M), dtype=torch.float64, device=dev)
-        oout = torch.empty((B, N), dtype=torch.float64, device=dev)
-        status = torch.empty(B, dtype=torch.int32, device=dev)
-        msize = torch.empty(B, dtype=torch.int32, device=dev)
-        rec = torch.empty((B, C.sizeof(_lib.DenseBatchMeta)), dtype=torch.uint8, device=dev)
-    info = _lib.DenseBatchInfo()
-    rest = (mats.data_ptr(), None if shp is None else shp.data_ptr(), 1 if fast else 0, p_ptr, C.byref(opts),
-            C.c_void_p(int(stream.cuda_stream)), work.data_ptr(), nbytes, d_out.data_ptr(), out_ld, sol.data_ptr(),
-            pout.data_ptr(), oout.data_ptr(), 1, status.data_ptr(), msize.data_ptr(), rec.data_ptr(), C.byref(info))
+    call = _StatusCall(lib, opts, B, N, M, N, dev, "misslap_dense_batch_outside_workspace_bytes",
+                       (B, N, M, 0 if p is None else 1))
+    rest = (_ptr(mc), _ptr(shp), 1 if fast else 0, _ptr(p), *call.way, _ptr(d_out), out_ld, *call.outs)
     if strides is None:
         _lib.check(lib.misslap_solve_dense_batch_outside(B, N, M, *rest))
     else:
         _lib.check(lib.misslap_solve_dense_batch_outside_strided(B, N, M, *strides, *rest))
-    # the workspace and the inputs stay referenced by the result: nothing of this call is recycled before it
-    return dict(sol=sol, prices=pout, outside_prices=oout, status=status, matching_size=msize, meta=_meta_views(rec),
-                shapes=shp, stack=(N, M), outside=d_out, records=rec, info=info, stream=stream, keep=(work, mats, p))
+    return call.result((mats, shp, p, d_out), shapes=shp, stack=(N, M), outside=d_out)
 
 
-def _meta_views(rec):
-    """The fields of a device buffer of misslap_dense_batch_meta records as column views, one tensor of length B each."""
-    import torch
-    kinds = {C.c_int32: torch.int32, C.c_int64: torch.int64, C.c_uint64: torch.int64, C.c_float: torch.float32,
-             C.c_double: torch.float64}
-    names = dict(start_eps_f32="start_eps", final_eps_f32="final_eps")
-    fields = dict(_lib.DenseBatchMeta._fields_)
-    out = {}
-    for key in _META_VIEWS:
-        f = names.get(key, key)
-        dt = kinds[fields[f]]
-        out[key] = rec.view(dt)[:, getattr(_lib.DenseBatchMeta, f).offset // C.sizeof(fields[f])]
-    return out
-
-
-def batch_meta_to_host(res):
-    """The meta of a status-mode result as the default mode returns it: a dict of length-B numpy arrays with the
-    Python-rounded obj, start_eps and final_eps.  For a device result this waits for the call's stream once."""
-    if "records" not in res:
-        return res["meta"]
-    res["stream"].synchronize()
-    raw = res["records"].cpu().numpy()
-    metas = (_lib.DenseBatchMeta * raw.shape[0]).from_buffer_copy(raw.tobytes())
-    return _decode_meta(metas, res["info"])
-
-
-def raise_for_status(res):
-    """Raise, for the first problem of a status-mode result whose status is not 0, the ValueError the default mode
-    raises for the same batch ("problem <b>: ..."); return res when every status is 0.  For a result of
-    auction_solve_sparse_batch: what its default mode raises with cardinality_check=False for that check, a
-    ZeroDivisionError for `fast` with N = 0 included.  For a result of auction_solve_ell_batch: the ValueError its own
-    default mode raises."""
-    def host(x):
-        return x if isinstance(x, np.ndarray) else x.cpu().numpy()
-    if "stream" in res:
-        res["stream"].synchronize()
-    status = host(res["status"])
-    bad = np.flatnonzero(status)
-    if bad.size == 0:
-        return res
-    b = int(bad[0])
-    if res.get("layout") in ("sparse", "ell"):
-        if res["layout"] == "sparse":
-            from .sparse_batch import _status_error
-        else:
-            from .ell_batch import _status_error
-        raise _status_error(res, b, int(status[b]), int(host(res["meta"]["n_rows"])[b]),
-                            int(host(res["meta"]["n_cols"])[b]), int(host(res["matching_size"])[b]))
+def _status_error(res, b, code, n, m, card):
+    """The exception of problem b of a dense result: what the default mode raises for that slice (n: the record's
+    n_rows; card: its matching_size)."""
     N, M = res["stack"]
-    n, m, card = int(host(res["meta"]["n_rows"])[b]), 0, int(host(res["matching_size"])[b])
-    if status[b] == _lib.BATCH_STATUS_BAD_SHAPE:
-        n, m = (int(x) for x in host(res["shapes"])[b])
+    m = 0  # (only a bad shape names its columns)
+    if code == _lib.BATCH_STATUS_BAD_SHAPE:
+        n, m = (int(x) for x in _host(res["shapes"])[b])
     row, value = 0, 0.0
-    if status[b] == _lib.BATCH_STATUS_BAD_OUTSIDE:  # the first row < n_b whose outside value is no entry
-        o = host(res["outside"])[b]
+    if code == _lib.BATCH_STATUS_BAD_OUTSIDE:  # the first row < n_b whose outside value is no entry
+        o = _host(res["outside"])[b]
         o = np.broadcast_to(o, (n,)) if o.ndim == 0 else o[:n]
         row = int(np.flatnonzero(~(o >= 0))[0])
         value = float(o[row])
-    text = _STATUS_TEXT[int(status[b])].format(n=n, m=m, N=N, M=M, card=card, row=row, value=value)
-    if status[b] == _lib.BATCH_STATUS_INFINITE_VALUE and "outside_prices" in res:
+    text = _STATUS_TEXT[code].format(n=n, m=m, N=N, M=M, card=card, row=row, value=value)
+    if code == _lib.BATCH_STATUS_INFINITE_VALUE and "outside_prices" in res:
         text += " (in an entry or in the outside value of a row)"
-    raise ValueError(f"problem {b}: {text}")
+    return ValueError(f"problem {b}: {text}")
+
+
+_STATUS_ERRORS["dense"] = _status_error
+

@@ -10,12 +10,11 @@ With `outside` every row also holds an outside option, so a row may stay unmatch
 the packed problem plus one entry (i, m_b + i) per row, stored last in its row, and its result is the reference's on
 that n_b x (m_b + n_b) problem (misslap_solve_ell_batch_outside).
 """
-import ctypes as C
-
 import numpy as np
 
 from . import _lib
-from ._batch import _decode_meta, _is_device_tensor, _new_meta, _solve_options, _starting_prices
+from ._batch import (_STATUS_ERRORS, _StatusCall, _check_outside, _contiguous, _eps, _is_device_tensor, _ptr, _send,
+                     _solve_options, _starting_prices, raise_for_status)
 
 MAX_DIM = _lib.SPARSE_BATCH_MAX_DIM
 _INT_MAX = 2**31 - 1
@@ -121,43 +120,6 @@ def _check_rows(rows, B, on_device, dev):
     return np.ascontiguousarray(np.clip(r, -1, _INT_MAX), dtype=np.int32)  # (whatever is out of range stays so)
 
 
-def _check_outside(outside, B, N, on_device, dev, need="cols / vals", src="cols", nonneg=False):
-    """The outside values of a call: a finite float (broadcast to (B,) where the input lives, nothing read back), or
-    float64 (B,) / (B, N) on the host or (with device input) contiguous on the input's device.  Returns (array or tensor,
-    outside_ld); the values are the library's to judge.  need / src: what the input is called in the texts; nonneg: a
-    float must also be >= 0 (the dense batch, where a negative entry is an absent one)."""
-    if _is_device_tensor(outside):
-        import torch
-        if not on_device:
-            raise TypeError(f"outside on the device needs {need} on the device")
-        if outside.dtype != torch.float64:
-            raise ValueError(f"outside must be float64, got {outside.dtype}")
-        if tuple(outside.shape) not in ((B,), (B, N)):
-            raise ValueError(f"outside must have shape ({B},) or ({B}, {N}), got {tuple(outside.shape)}")
-        if outside.device != dev:
-            raise ValueError(f"outside is on {outside.device}, {src} on {dev}")
-        if not outside.is_contiguous():
-            raise ValueError("a device outside tensor must be contiguous (it is read in place)")
-        return outside, (N if outside.dim() == 2 else 0)
-    if isinstance(outside, np.ndarray):
-        if outside.dtype != np.float64:
-            raise ValueError(f"outside must be float64, got {outside.dtype.name}")
-        if outside.shape not in ((B,), (B, N)):
-            raise ValueError(f"outside must have shape ({B},) or ({B}, {N}), got {outside.shape}")
-        return np.ascontiguousarray(outside), (N if outside.ndim == 2 else 0)
-    if isinstance(outside, (bool, str, bytes)) or not isinstance(outside, (int, float, np.integer, np.floating)):
-        raise TypeError("outside must be a float, a float64 numpy array or a float64 tensor on the device")
-    x = float(outside)
-    if not np.isfinite(x):
-        raise ValueError(f"outside must be finite, got {x!r}")
-    if nonneg and not x >= 0:
-        raise ValueError(f"outside must be >= 0 (a negative entry of a dense matrix is an absent one), got {x!r}")
-    if on_device:
-        import torch
-        return torch.full((B,), x, dtype=torch.float64, device=dev), 0
-    return np.full(B, x, dtype=np.float64), 0
-
-
 def _check_n_cols(n_cols):
     try:
         ok = int(n_cols) == n_cols and 1 <= int(n_cols) <= MAX_DIM
@@ -222,9 +184,7 @@ def auction_solve_ell_batch(cols, vals, rows=None, n_cols=None, problem="min", e
     B, N, K, on_device, wide, dtype = _check_input(cols, vals)
     dev = cols.device if on_device else None
     rws = _check_rows(rows, B, on_device, dev)
-    e = float(eps_start)
-    if e != e:
-        raise ValueError("eps_start is NaN")
+    e = _eps(eps_start)
     if prices is not None:  # dtype and shape: float64 (B, P), any P >= 1; a device tensor only with device input
         _starting_prices(prices, B, 1, False, on_device and not isinstance(prices, np.ndarray), cols, "cols / vals")
         if _is_device_tensor(prices) and prices.device != dev:
@@ -234,113 +194,24 @@ def auction_solve_ell_batch(cols, vals, rows=None, n_cols=None, problem="min", e
     else:  # (with device input the call's one read-back, ordered behind the current stream like every read of cols)
         Mmax = min(max(int(cols.max()) + 1, 1), MAX_DIM)
     check = 1 if cardinality_check else 0
-    out_v, out_ld = (None, 0) if outside is None else _check_outside(outside, B, N, on_device, dev)
+    out_v, out_ld = (None, 0) if outside is None else _check_outside(outside, B, N, dev)
     if fast is None:  # (resolved here: the library gets a plain flag)
         fast = outside is not None and not e > 0
     opts = _solve_options(on_device, cols, problem, e, max_iter, dtype)
     lib = _lib.load()
-    common = dict(layout="ell", stack=(N, K), n_cols=Mmax, prices_ld=0 if prices is None else int(prices.shape[1]))
-    if outside is not None:
-        return _finish(_solve_outside(lib, opts, cols, vals, rws, prices, out_v, out_ld, 1 if fast else 0, B, N, K, Mmax,
-                                      on_device, wide, dev, common), errors)
-    if not on_device:  # synchronous: the library uploads, uses its own scratch and waits once
-        cc, vc = np.ascontiguousarray(cols), np.ascontiguousarray(vals)
-        p = None if prices is None else np.ascontiguousarray(prices)
-        sol, pout = np.empty((B, N), dtype=np.int32), np.empty((B, Mmax), dtype=np.float64)
-        status, msize = np.empty(B, dtype=np.int32), np.empty(B, dtype=np.int32)
-        metas, info = _new_meta(B)
-        _lib.check(lib.misslap_solve_ell_batch(
-            B, N, K, cc.ctypes.data, 1 if wide else 0, vc.ctypes.data, None if rws is None else rws.ctypes.data,
-            1 if fast else 0, None if p is None else p.ctypes.data, common["prices_ld"], check, C.byref(opts), None, None, 0,
-            Mmax, sol.ctypes.data, pout.ctypes.data, 0, status.ctypes.data, msize.ctypes.data, C.cast(metas, C.c_void_p),
-            C.byref(info)))
-        res = dict(sol=sol, prices=pout, status=status, matching_size=msize, meta=_decode_meta(metas, info), rows=rws,
-                   **common)
+    cc, vc = _contiguous(cols), _contiguous(vals)  # (device tensors are: they are read in place)
+    d_rows, d_out, d_p = _send(rws, dev), _send(out_v, dev), _send(_contiguous(prices), dev)
+    p_ld, has_p = (0, 0) if prices is None else (int(prices.shape[1]), 1)
+    head = (B, N, K, _ptr(cc), 1 if wide else 0, _ptr(vc), _ptr(d_rows), 1 if fast else 0, _ptr(d_p), p_ld)
+    if outside is None:
+        call = _StatusCall(lib, opts, B, N, Mmax, None, dev, "misslap_ell_batch_workspace_bytes", (B, N, K, has_p, check))
+        _lib.check(lib.misslap_solve_ell_batch(*head, check, *call.way, Mmax, *call.outs))
     else:
-        import torch
-        from .dense_batch import _meta_views
-
-        with torch.cuda.device(dev):  # (the allocations and copies below are made on the current stream of cols' device)
-            stream = torch.cuda.current_stream(dev)
-            d_rows = _send(rws, dev)
-            d_p = None if prices is None else _send(np.ascontiguousarray(prices) if isinstance(prices, np.ndarray)
-                                                    else prices.contiguous(), dev)
-            nbytes = int(lib.misslap_ell_batch_workspace_bytes(B, N, K, 0 if d_p is None else 1, check))
-            work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            sol = torch.empty((B, N), dtype=torch.int32, device=dev)
-            pout = torch.empty((B, Mmax), dtype=torch.float64, device=dev)
-            status = torch.empty(B, dtype=torch.int32, device=dev)
-            msize = torch.empty(B, dtype=torch.int32, device=dev)
-            rec = torch.empty((B, C.sizeof(_lib.DenseBatchMeta)), dtype=torch.uint8, device=dev)
-        info = _lib.DenseBatchInfo()
-        _lib.check(lib.misslap_solve_ell_batch(
-            B, N, K, cols.data_ptr(), 1 if wide else 0, vals.data_ptr(), None if d_rows is None else d_rows.data_ptr(),
-            1 if fast else 0, None if d_p is None else d_p.data_ptr(), common["prices_ld"], check, C.byref(opts),
-            C.c_void_p(int(stream.cuda_stream)), work.data_ptr(), nbytes, Mmax, sol.data_ptr(), pout.data_ptr(), 1,
-            status.data_ptr(), msize.data_ptr(), rec.data_ptr(), C.byref(info)))
-        # the workspace and the inputs stay referenced by the result: nothing of this call is recycled before it
-        res = dict(sol=sol, prices=pout, status=status, matching_size=msize, meta=_meta_views(rec), rows=d_rows, records=rec,
-                   info=info, stream=stream, keep=(work, cols, vals, d_rows, d_p), **common)
-    return _finish(res, errors)
-
-
-def _finish(res, errors):
-    if errors == "raise":
-        from .dense_batch import raise_for_status
-        raise_for_status(res)
-    return res
-
-
-def _send(a, dev):
-    """A host array to dev from pinned memory, without a wait (torch takes no read-only array: a copy then)."""
-    import torch
-    if not isinstance(a, np.ndarray):
-        return a
-    return torch.from_numpy(a if a.flags.writeable else a.copy()).pin_memory().to(dev, non_blocking=True)
-
-
-def _solve_outside(lib, opts, cols, vals, rws, prices, out_v, out_ld, fast, B, N, K, Mmax, on_device, wide, dev, common):
-    """The call of misslap_solve_ell_batch_outside, in either mode; the result dict of auction_solve_ell_batch plus
-    outside_prices."""
-    p_ld = common["prices_ld"]
-    if not on_device:  # synchronous: the library uploads, uses its own scratch and waits once
-        cc, vc = np.ascontiguousarray(cols), np.ascontiguousarray(vals)
-        p = None if prices is None else np.ascontiguousarray(prices)
-        sol, pout = np.empty((B, N), dtype=np.int32), np.empty((B, Mmax), dtype=np.float64)
-        oout = np.empty((B, N), dtype=np.float64)
-        status, msize = np.empty(B, dtype=np.int32), np.empty(B, dtype=np.int32)
-        metas, info = _new_meta(B)
-        _lib.check(lib.misslap_solve_ell_batch_outside(
-            B, N, K, cc.ctypes.data, 1 if wide else 0, vc.ctypes.data, None if rws is None else rws.ctypes.data, fast,
-            None if p is None else p.ctypes.data, p_ld, C.byref(opts), None, None, 0, Mmax, out_v.ctypes.data, out_ld,
-            sol.ctypes.data, pout.ctypes.data, oout.ctypes.data, 0, status.ctypes.data, msize.ctypes.data,
-            C.cast(metas, C.c_void_p), C.byref(info)))
-        return dict(sol=sol, prices=pout, outside_prices=oout, status=status, matching_size=msize,
-                    meta=_decode_meta(metas, info), rows=rws, **common)
-    import torch
-    from .dense_batch import _meta_views
-    with torch.cuda.device(dev):  # (the allocations and copies below are made on the current stream of cols' device)
-        stream = torch.cuda.current_stream(dev)
-        d_rows = _send(rws, dev)
-        d_out = _send(out_v, dev)
-        d_p = None if prices is None else _send(np.ascontiguousarray(prices) if isinstance(prices, np.ndarray)
-                                                else prices.contiguous(), dev)
-        nbytes = int(lib.misslap_ell_batch_outside_workspace_bytes(B, N, K, Mmax, 0 if d_p is None else 1))
-        work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        sol = torch.empty((B, N), dtype=torch.int32, device=dev)
-        pout = torch.empty((B, Mmax), dtype=torch.float64, device=dev)
-        oout = torch.empty((B, N), dtype=torch.float64, device=dev)
-        status = torch.empty(B, dtype=torch.int32, device=dev)
-        msize = torch.empty(B, dtype=torch.int32, device=dev)
-        rec = torch.empty((B, C.sizeof(_lib.DenseBatchMeta)), dtype=torch.uint8, device=dev)
-    info = _lib.DenseBatchInfo()
-    _lib.check(lib.misslap_solve_ell_batch_outside(
-        B, N, K, cols.data_ptr(), 1 if wide else 0, vals.data_ptr(), None if d_rows is None else d_rows.data_ptr(), fast,
-        None if d_p is None else d_p.data_ptr(), p_ld, C.byref(opts), C.c_void_p(int(stream.cuda_stream)),
-        work.data_ptr(), nbytes, Mmax, d_out.data_ptr(), out_ld, sol.data_ptr(), pout.data_ptr(), oout.data_ptr(), 1,
-        status.data_ptr(), msize.data_ptr(), rec.data_ptr(), C.byref(info)))
-    return dict(sol=sol, prices=pout, outside_prices=oout, status=status, matching_size=msize, meta=_meta_views(rec),
-                rows=d_rows, records=rec, info=info, stream=stream, keep=(work, cols, vals, d_rows, d_p, d_out), **common)
+        call = _StatusCall(lib, opts, B, N, Mmax, N, dev, "misslap_ell_batch_outside_workspace_bytes",
+                           (B, N, K, Mmax, has_p))
+        _lib.check(lib.misslap_solve_ell_batch_outside(*head, *call.way, Mmax, _ptr(d_out), out_ld, *call.outs))
+    res = call.result((cols, vals, d_rows, d_p, d_out), rows=d_rows, layout="ell", stack=(N, K), n_cols=Mmax, prices_ld=p_ld)
+    return raise_for_status(res) if errors == "raise" else res
 
 
 def _status_error(res, b, code, n, m, card):
@@ -361,3 +232,6 @@ def _status_error(res, b, code, n, m, card):
         also = " (in an entry or in the outside value of a row)" if "outside_prices" in res else ""
         text = _STATUS_TEXT[code].format(r=r, N=N, n=n, m=m, card=card, P=res["prices_ld"], also=also)
     return ValueError(f"problem {b}: {text}")
+
+
+_STATUS_ERRORS["ell"] = _status_error

@@ -10,8 +10,8 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._batch import (_check_offsets, _check_shapes, _check_stack, _is_device_tensor, _mat_dtype_name, _maxima, _options,
-                     _stack_strides)
+from ._batch import (_check_offsets, _check_shapes, _check_stack, _empty, _is_device_tensor, _mat_dtype_name, _maxima,
+                     _options, _ptr, _stack_strides)
 
 MAX_DIM = _lib.MATCHING_BATCH_MAX_DIM
 
@@ -121,30 +121,24 @@ def hopcroft_solve_batch(loc=None, offsets=None, mats=None, shapes=None, mat_dty
     size = np.empty(B, dtype=np.int32)
     n_rows = np.empty(B, dtype=np.int32)
     n_cols = np.empty(B, dtype=np.int32)
-    if on_device:
-        import torch
-        left = torch.empty((B, Nmax), dtype=torch.int32, device=src.device)
-        right = torch.empty((B, Mmax), dtype=torch.int32, device=src.device)
-        left_ptr, right_ptr, src_ptr = left.data_ptr(), right.data_ptr(), src.data_ptr()
-    else:
-        left = np.empty((B, Nmax), dtype=np.int32)
-        right = np.empty((B, Mmax), dtype=np.int32)
+    dev = src.device if on_device else None
+    left, right = _empty((B, Nmax), np.int32, dev), _empty((B, Mmax), np.int32, dev)
+    if not on_device:
         src = np.ascontiguousarray(src)
-        left_ptr, right_ptr, src_ptr = left.ctypes.data, right.ctypes.data, src.ctypes.data
     info = _lib.MatchingBatchInfo()
     info.struct_size = C.sizeof(_lib.MatchingBatchInfo)
-    outs = (size.ctypes.data, n_rows.ctypes.data, n_cols.ctypes.data, C.c_void_p(left_ptr), Nmax, C.c_void_p(right_ptr),
-            Mmax, 1 if on_device else 0, C.byref(info))
+    outs = (size.ctypes.data, n_rows.ctypes.data, n_cols.ctypes.data, C.c_void_p(_ptr(left)), Nmax,
+            C.c_void_p(_ptr(right)), Mmax, 1 if on_device else 0, C.byref(info))
     lib = _lib.load()
     if mats is not None:
         strides = _stack_strides(mats, on_device)
-        ins = (C.c_void_p(src_ptr), None if shp is None else shp.ctypes.data, C.byref(opts))
+        ins = (C.c_void_p(_ptr(src)), _ptr(shp), C.byref(opts))
         if strides is None:
             _lib.check(lib.misslap_matching_dense_batch(B, N, M, *ins, *outs))
         else:
             _lib.check(lib.misslap_matching_dense_batch_strided(B, N, M, *strides, *ins, *outs))
     else:
-        _lib.check(lib.misslap_matching_batch(B, C.c_void_p(src_ptr), off.ctypes.data, C.byref(opts), *outs))
+        _lib.check(lib.misslap_matching_batch(B, C.c_void_p(_ptr(src)), off.ctypes.data, C.byref(opts), *outs))
     return dict(size=size, left_pairings=left, right_pairings=right, n_rows=n_rows, n_cols=n_cols,
                 gpu=dict(threads=int(info.threads), lds_bytes=int(info.lds_bytes), check_ms=float(info.check_ms),
                          kernel_ms=float(info.kernel_ms), wall_ms=float(info.wall_ms)))

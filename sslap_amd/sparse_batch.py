@@ -15,8 +15,9 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._batch import (_check_offsets, _decode_meta, _is_device_tensor, _maxima, _new_meta, _solve_options,
-                     _starting_prices)
+from ._batch import (_STATUS_ERRORS, _StatusCall, _check_offsets, _contiguous, _decode_meta, _empty, _eps,
+                     _is_device_tensor, _maxima, _new_meta, _ptr, _scalar_outside, _send, _solve_options, _starting_prices,
+                     raise_for_status)
 from .auction_solve import _cname
 
 MAX_DIM = _lib.SPARSE_BATCH_MAX_DIM
@@ -231,17 +232,12 @@ def auction_solve_sparse_batch(loc, val=None, offsets=None, problem="min", eps_s
         loc, val, offsets = _pack(loc)
     B, nnz, off, on_device = _check_input(loc, val, offsets)
     szs = _check_sizes(sizes, B)
-    e = float(eps_start)
-    if e != e:
-        raise ValueError("eps_start is NaN")
+    e = _eps(eps_start)
     if outside is not None:
         if fast is None:  # (resolved here: the library gets a plain flag)
             fast = not e > 0
         res = _solve_outside(loc, val, B, nnz, off, on_device, problem, e, max_iter, fast, szs, prices, dims, outside)
-        if errors == "raise":
-            from .dense_batch import raise_for_status
-            raise_for_status(res)
-        return res
+        return raise_for_status(res) if errors == "raise" else res
     fast = bool(fast)  # (None: False, the call is what it was)
     if errors == "status":
         return _solve_status(loc, val, B, nnz, off, on_device, problem, e, max_iter, fast, szs, cardinality_check, prices,
@@ -249,10 +245,9 @@ def auction_solve_sparse_batch(loc, val=None, offsets=None, problem="min", eps_s
     max_row, max_col, rows = _maxima(loc, off, on_device, per_problem=fast and szs is None)
     Nmax = min(max(max_row + 1, 1), MAX_DIM)  # (a problem beyond the cap is rejected by the library, in its order)
     Mmax = min(max(max_col + 1, 1), MAX_DIM)
-    p, p_ptr, p_ld = _starting_prices(prices, B, Mmax, False, on_device, loc, "loc / val")
+    p, p_ptr, p_ld = _starting_prices(prices, B, Mmax, False, on_device, loc, "loc / val")  # (p lives through the call)
     if _is_device_tensor(prices) and prices.device != loc.device:
         raise ValueError(f"prices are on {prices.device}, loc on {loc.device}")
-    keep = [p]  # buffers that must live through the call
     eps_b = None
     if fast:  # auction_.pyx:614-615: eps_start = 1 / N of each problem (from_sparse's N: size[1], or the max row)
         N = szs[:, 1] if szs is not None else rows
@@ -263,23 +258,14 @@ def auction_solve_sparse_batch(loc, val=None, offsets=None, problem="min", eps_s
         Nf = np.where(nonempty, N, 1).astype(np.float64)
         eps_b = np.ascontiguousarray((1.0 / Nf).astype(np.float32))
     opts = _solve_options(on_device, loc, problem, e, max_iter)
-    if on_device:
-        import torch
-        sol = torch.empty((B, Nmax), dtype=torch.int32, device=loc.device)
-        pout = torch.empty((B, Mmax), dtype=torch.float64, device=loc.device)
-        sol_ptr, pout_ptr, loc_ptr, val_ptr = sol.data_ptr(), pout.data_ptr(), loc.data_ptr(), val.data_ptr()
-    else:
-        lc, vc = np.ascontiguousarray(loc), np.ascontiguousarray(val)
-        keep += [lc, vc]
-        sol = np.empty((B, Nmax), dtype=np.int32)
-        pout = np.empty((B, Mmax), dtype=np.float64)
-        sol_ptr, pout_ptr, loc_ptr, val_ptr = sol.ctypes.data, pout.ctypes.data, lc.ctypes.data, vc.ctypes.data
+    dev = loc.device if on_device else None
+    lc, vc = _contiguous(loc), _contiguous(val)  # (device tensors are: they are read in place)
+    sol, pout = _empty((B, Nmax), np.int32, dev), _empty((B, Mmax), np.float64, dev)
     metas, info = _new_meta(B)
     _lib.check(_lib.load().misslap_solve_sparse_batch(
-        B, C.c_void_p(loc_ptr), C.c_void_p(val_ptr), off.ctypes.data, None if szs is None else szs.ctypes.data,
-        None if eps_b is None else eps_b.ctypes.data, None if p_ptr is None else C.c_void_p(p_ptr), p_ld,
-        1 if cardinality_check else 0, C.byref(opts), C.c_void_p(sol_ptr), Nmax, C.c_void_p(pout_ptr), Mmax,
-        1 if on_device else 0, metas, C.byref(info)))
+        B, C.c_void_p(_ptr(lc)), C.c_void_p(_ptr(vc)), off.ctypes.data, _ptr(szs), _ptr(eps_b),
+        None if p_ptr is None else C.c_void_p(p_ptr), p_ld, 1 if cardinality_check else 0, C.byref(opts),
+        C.c_void_p(_ptr(sol)), Nmax, C.c_void_p(_ptr(pout)), Mmax, 1 if on_device else 0, metas, C.byref(info)))
     return dict(sol=sol, prices=pout, meta=_decode_meta(metas, info))
 
 
@@ -310,61 +296,49 @@ def _solve_status(loc, val, B, nnz, off, on_device, problem, e, max_iter, fast, 
     """errors="status" of auction_solve_sparse_batch (misslap_solve_sparse_batch_status)."""
     check = 1 if cardinality_check else 0
     p = _status_prices(prices, B, on_device, loc)  # (a host array, or with device input possibly a device tensor)
-    if dims is not None:
-        Nmax, Mmax = _check_dims(dims)
-    else:  # as the default mode sizes its outputs; with device input this is the mode's one read-back
-        max_row, max_col, _ = _maxima(loc, off, on_device, per_problem=False)
-        Nmax, Mmax = min(max(max_row + 1, 1), MAX_DIM), min(max(max_col + 1, 1), MAX_DIM)
+    Nmax, Mmax = _out_dims(dims, loc, off, on_device)
     opts = _solve_options(on_device, loc, problem, e, max_iter)
+    return _call(loc, val, B, nnz, off, on_device, opts, fast, szs, p, Nmax, Mmax, check)
+
+
+def _out_dims(dims, loc, off, on_device, n_sized=0):
+    """(Nmax, Mmax) of a status-mode call: dims, or as the default mode sizes its outputs (with device input this is the
+    mode's one read-back); n_sized: the most rows sizes names, where they count."""
+    if dims is not None:
+        return _check_dims(dims)
+    max_row, max_col, _ = _maxima(loc, off, on_device, per_problem=False)
+    return min(max(max_row + 1, n_sized, 1), MAX_DIM), min(max(max_col + 1, 1), MAX_DIM)
+
+
+def _call(loc, val, B, nnz, off, on_device, opts, fast, szs, p, Nmax, Mmax, check, out_v=None, out_ld=0):
+    """The call of misslap_solve_sparse_batch_status, or with outside values (out_v) of
+    misslap_solve_sparse_batch_outside, in either mode, and its result dict.  offsets is read on the host in both modes,
+    and with device input a second time on the device."""
+    dev = loc.device if on_device else None
     lib = _lib.load()
-    common = dict(layout="sparse", dims=(Nmax, Mmax), sizes=szs, offsets=off, loc=loc,
-                  prices_ld=0 if p is None else int(p.shape[1]))
-    if not on_device:  # synchronous: the library uploads, uses its own scratch and waits once
-        lc, vc = np.ascontiguousarray(loc), np.ascontiguousarray(val)
-        sol, pout = np.empty((B, Nmax), dtype=np.int32), np.empty((B, Mmax), dtype=np.float64)
-        status, msize = np.empty(B, dtype=np.int32), np.empty(B, dtype=np.int32)
-        metas, info = _new_meta(B)
-        _lib.check(lib.misslap_solve_sparse_batch_status(
-            B, lc.ctypes.data, vc.ctypes.data, off.ctypes.data, None, None if szs is None else szs.ctypes.data,
-            1 if fast else 0, None if p is None else p.ctypes.data, common["prices_ld"], check, C.byref(opts), None, None,
-            0, Nmax, Mmax, sol.ctypes.data, pout.ctypes.data, 0, status.ctypes.data, msize.ctypes.data,
-            C.cast(metas, C.c_void_p), C.byref(info)))
-        return dict(sol=sol, prices=pout, status=status, matching_size=msize, meta=_decode_meta(metas, info), **common)
-    import torch
-    from .dense_batch import _meta_views
-    dev = loc.device
-
-    def send(a):  # a host array from pinned memory, without a wait
-        return None if a is None else torch.from_numpy(a).pin_memory().to(dev, non_blocking=True)
-    with torch.cuda.device(dev):  # (the allocations and copies below are made on the current stream of loc's device)
-        stream = torch.cuda.current_stream(dev)
-        d_off, d_sizes = send(off), send(szs)
-        d_p = send(p) if isinstance(p, np.ndarray) else p
-        nbytes = int(lib.misslap_sparse_batch_workspace_bytes(B, nnz, 0 if p is None else 1, check))
-        work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        sol = torch.empty((B, Nmax), dtype=torch.int32, device=dev)
-        pout = torch.empty((B, Mmax), dtype=torch.float64, device=dev)
-        status = torch.empty(B, dtype=torch.int32, device=dev)
-        msize = torch.empty(B, dtype=torch.int32, device=dev)
-        rec = torch.empty((B, C.sizeof(_lib.DenseBatchMeta)), dtype=torch.uint8, device=dev)
-    info = _lib.DenseBatchInfo()
-    _lib.check(lib.misslap_solve_sparse_batch_status(
-        B, loc.data_ptr(), val.data_ptr(), off.ctypes.data, d_off.data_ptr(), None if d_sizes is None else d_sizes.data_ptr(),
-        1 if fast else 0, None if d_p is None else d_p.data_ptr(), common["prices_ld"], check, C.byref(opts),
-        C.c_void_p(int(stream.cuda_stream)), work.data_ptr(), nbytes, Nmax, Mmax, sol.data_ptr(), pout.data_ptr(), 1,
-        status.data_ptr(), msize.data_ptr(), rec.data_ptr(), C.byref(info)))
-    # the workspace and the inputs stay referenced by the result: nothing of this call is recycled before it
-    return dict(sol=sol, prices=pout, status=status, matching_size=msize, meta=_meta_views(rec), records=rec, info=info,
-                stream=stream, keep=(work, loc, val, d_off, d_sizes, d_p), **common)
+    lc, vc = _contiguous(loc), _contiguous(val)  # (device tensors are: they are read in place)
+    d_off = _send(off, dev) if on_device else None
+    d_sizes, d_p, d_out = _send(szs, dev), _send(p, dev), _send(out_v, dev)
+    p_ld, has_p = (0, 0) if p is None else (int(p.shape[1]), 1)
+    head = (B, _ptr(lc), _ptr(vc), off.ctypes.data, _ptr(d_off), _ptr(d_sizes), 1 if fast else 0, _ptr(d_p), p_ld)
+    if out_v is None:
+        call = _StatusCall(lib, opts, B, Nmax, Mmax, None, dev, "misslap_sparse_batch_workspace_bytes", (B, nnz, has_p, check))
+        _lib.check(lib.misslap_solve_sparse_batch_status(*head, check, *call.way, Nmax, Mmax, *call.outs))
+    else:
+        call = _StatusCall(lib, opts, B, Nmax, Mmax, Nmax, dev, "misslap_sparse_batch_outside_workspace_bytes",
+                           (B, Nmax, Mmax, has_p))
+        _lib.check(lib.misslap_solve_sparse_batch_outside(*head, *call.way, Nmax, Mmax, _ptr(d_out), out_ld, *call.outs))
+    return call.result((loc, val, d_off, d_sizes, d_p, d_out), layout="sparse", dims=(Nmax, Mmax), sizes=szs, offsets=off,
+                       loc=loc, prices_ld=p_ld)
 
 
-def _check_outside(outside, B, on_device, dev):
+def _check_outside(outside, B, dev):
     """The outside values of a call, before Nmax is known: a finite float (broadcast to (B,) where the input lives), or
     float64 (B,) / (B, P) on the host or (with device input) on loc's device, a row of it with unit stride.  Returns
     (array or tensor, P or 0 for one value per problem, outside_ld)."""
     if _is_device_tensor(outside):
         import torch
-        if not on_device:
+        if dev is None:
             raise TypeError("outside on the device needs loc / val on the device")
         if outside.dtype != torch.float64:
             raise ValueError(f"outside must be float64, got {outside.dtype}")
@@ -389,77 +363,19 @@ def _check_outside(outside, B, on_device, dev):
             raise ValueError(f"outside must have shape ({B},) or ({B}, P), got {outside.shape}")
         o = np.ascontiguousarray(outside)
         return o, (o.shape[1] if o.ndim == 2 else 0), (o.shape[1] if o.ndim == 2 else 0)
-    if isinstance(outside, (bool, str, bytes)) or not isinstance(outside, (int, float, np.integer, np.floating)):
-        raise TypeError("outside must be a float, a float64 numpy array or a float64 tensor on the device")
-    x = float(outside)
-    if not np.isfinite(x):
-        raise ValueError(f"outside must be finite, got {x!r}")
-    if on_device:
-        import torch
-        return torch.full((B,), x, dtype=torch.float64, device=dev), 0, 0
-    return np.full(B, x, dtype=np.float64), 0, 0
+    return _scalar_outside(outside, B, dev), 0, 0
 
 
 def _solve_outside(loc, val, B, nnz, off, on_device, problem, e, max_iter, fast, szs, prices, dims, outside):
     """outside= of auction_solve_sparse_batch (misslap_solve_sparse_batch_outside), in either mode."""
     dev = loc.device if on_device else None
-    out_v, P, out_ld = _check_outside(outside, B, on_device, dev)
+    out_v, P, out_ld = _check_outside(outside, B, dev)
     p = _status_prices(prices, B, on_device, loc)  # (a host array, or with device input possibly a device tensor)
-    if dims is not None:
-        Nmax, Mmax = _check_dims(dims)
-    else:  # (with device input this is the mode's one read-back)
-        max_row, max_col, _ = _maxima(loc, off, on_device, per_problem=False)
-        n_sized = int(szs[:, 1].max()) if szs is not None else 0
-        Nmax, Mmax = min(max(max_row + 1, n_sized, 1), MAX_DIM), min(max(max_col + 1, 1), MAX_DIM)
+    Nmax, Mmax = _out_dims(dims, loc, off, on_device, int(szs[:, 1].max()) if szs is not None else 0)
     if P and P < Nmax:
         raise ValueError(f"outside must have shape ({B},) or ({B}, P) with P >= Nmax = {Nmax}, got P = {P}")
     opts = _solve_options(on_device, loc, problem, e, max_iter)
-    lib = _lib.load()
-    fast = 1 if fast else 0
-    common = dict(layout="sparse", dims=(Nmax, Mmax), sizes=szs, offsets=off, loc=loc,
-                  prices_ld=0 if p is None else int(p.shape[1]))
-    if not on_device:  # synchronous: the library uploads, uses its own scratch and waits once
-        lc, vc = np.ascontiguousarray(loc), np.ascontiguousarray(val)
-        sol, pout = np.empty((B, Nmax), dtype=np.int32), np.empty((B, Mmax), dtype=np.float64)
-        oout = np.empty((B, Nmax), dtype=np.float64)
-        status, msize = np.empty(B, dtype=np.int32), np.empty(B, dtype=np.int32)
-        metas, info = _new_meta(B)
-        _lib.check(lib.misslap_solve_sparse_batch_outside(
-            B, lc.ctypes.data, vc.ctypes.data, off.ctypes.data, None, None if szs is None else szs.ctypes.data, fast,
-            None if p is None else p.ctypes.data, common["prices_ld"], C.byref(opts), None, None, 0, Nmax, Mmax,
-            out_v.ctypes.data, out_ld, sol.ctypes.data, pout.ctypes.data, oout.ctypes.data, 0, status.ctypes.data,
-            msize.ctypes.data, C.cast(metas, C.c_void_p), C.byref(info)))
-        return dict(sol=sol, prices=pout, outside_prices=oout, status=status, matching_size=msize,
-                    meta=_decode_meta(metas, info), **common)
-    import torch
-    from .dense_batch import _meta_views
-
-    def send(a):  # a host array from pinned memory, without a wait (torch takes no read-only array: a copy then)
-        if a is None:
-            return None
-        return torch.from_numpy(a if a.flags.writeable else a.copy()).pin_memory().to(dev, non_blocking=True)
-    with torch.cuda.device(dev):  # (the allocations and copies below are made on the current stream of loc's device)
-        stream = torch.cuda.current_stream(dev)
-        d_off, d_sizes = send(off), send(szs)
-        d_p = send(p) if isinstance(p, np.ndarray) else p
-        d_out = send(out_v) if isinstance(out_v, np.ndarray) else out_v
-        nbytes = int(lib.misslap_sparse_batch_outside_workspace_bytes(B, Nmax, Mmax, 0 if p is None else 1))
-        work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        sol = torch.empty((B, Nmax), dtype=torch.int32, device=dev)
-        pout = torch.empty((B, Mmax), dtype=torch.float64, device=dev)
-        oout = torch.empty((B, Nmax), dtype=torch.float64, device=dev)
-        status = torch.empty(B, dtype=torch.int32, device=dev)
-        msize = torch.empty(B, dtype=torch.int32, device=dev)
-        rec = torch.empty((B, C.sizeof(_lib.DenseBatchMeta)), dtype=torch.uint8, device=dev)
-    info = _lib.DenseBatchInfo()
-    _lib.check(lib.misslap_solve_sparse_batch_outside(
-        B, loc.data_ptr(), val.data_ptr(), off.ctypes.data, d_off.data_ptr(), None if d_sizes is None else d_sizes.data_ptr(),
-        fast, None if d_p is None else d_p.data_ptr(), common["prices_ld"], C.byref(opts),
-        C.c_void_p(int(stream.cuda_stream)), work.data_ptr(), nbytes, Nmax, Mmax, d_out.data_ptr(), out_ld, sol.data_ptr(),
-        pout.data_ptr(), oout.data_ptr(), 1, status.data_ptr(), msize.data_ptr(), rec.data_ptr(), C.byref(info)))
-    # the workspace and the inputs stay referenced by the result: nothing of this call is recycled before it
-    return dict(sol=sol, prices=pout, outside_prices=oout, status=status, matching_size=msize, meta=_meta_views(rec),
-                records=rec, info=info, stream=stream, keep=(work, loc, val, d_off, d_sizes, d_p, d_out), **common)
+    return _call(loc, val, B, nnz, off, on_device, opts, fast, szs, p, Nmax, Mmax, None, out_v, out_ld)
 
 
 def _outside_error(res, b, code, n, m):
@@ -509,3 +425,6 @@ def _status_error(res, b, code, n, m, card):
         N = int(res["sizes"][b, 1]) if res["sizes"] is not None else n - 1  # from_sparse's N (sic, :592 / :594)
         text = _STATUS_TEXT[code].format(N=N, n=n, m=m, card=card, P=res["prices_ld"])
     return ValueError(f"problem {b}: {text}")
+
+
+_STATUS_ERRORS["sparse"] = _status_error

@@ -1,12 +1,13 @@
-"""The call path the five "verdict per problem, stream-ordered" batch entry points share (batch_stream_call,
+"""The call path the six "verdict per problem, stream-ordered" batch entry points share (batch_stream_call,
 csrc/abi_batch_stream.hpp), where the Python front ends never go: a meta array of the shortest stride, optional outputs
 left out, the stream-ordered mode on a side stream against the library's own mode, and the workspace checks.
 
 Every case runs for misslap_solve_dense_batch_status, misslap_solve_dense_batch_outside,
-misslap_solve_sparse_batch_status, misslap_solve_ell_batch and misslap_solve_ell_batch_outside through ctypes, on three
-tiny problems (3 rows, 4 columns; problem 1 uses 2 rows) of small distinct integers; the sparse call takes the ELL
-call's problems as loc / val.  What is expected comes from the Python front end of the same entry point on the same
-input, which is tested against the oracle elsewhere.
+misslap_solve_sparse_batch_status, misslap_solve_sparse_batch_outside, misslap_solve_ell_batch and
+misslap_solve_ell_batch_outside through ctypes, on three tiny problems (3 rows, 4 columns; problem 1 uses 2 rows) of
+small distinct integers; the sparse calls take the ELL call's problems as loc / val.  What is expected comes from the
+Python front end of the same entry point on the same input, which is tested against the oracle elsewhere -- and which
+must give on device tensors, bit for bit, what it gives on the host arrays.
 """
 import ctypes as C
 import functools
@@ -14,7 +15,8 @@ import functools
 import numpy as np
 import pytest
 
-from sslap_amd import _lib, auction_solve_batch, auction_solve_ell_batch, auction_solve_sparse_batch, ell_to_packed
+from sslap_amd import (_lib, auction_solve_batch, auction_solve_ell_batch, auction_solve_sparse_batch, batch_meta_to_host,
+                       ell_to_packed)
 from tests._batch_shapes import bits
 
 B, N, M, K = 3, 3, 4, 3  # M: the dense stack's columns and the ELL / sparse calls' Mmax
@@ -36,32 +38,36 @@ VAL = np.ascontiguousarray(np.concatenate([v for _, v in _PACKED]), dtype=np.flo
 OFFSETS = np.concatenate([[0], np.cumsum([len(v) for _, v in _PACKED])]).astype(np.int64)
 NNZ = int(OFFSETS[-1])
 
-NAMES = ("dense_status", "dense_outside", "sparse_status", "ell", "ell_outside")
+NAMES = ("dense_status", "dense_outside", "sparse_status", "sparse_outside", "ell", "ell_outside")
 ENTRY = dict(dense_status="misslap_solve_dense_batch_status", dense_outside="misslap_solve_dense_batch_outside",
-             sparse_status="misslap_solve_sparse_batch_status", ell="misslap_solve_ell_batch",
-             ell_outside="misslap_solve_ell_batch_outside")
+             sparse_status="misslap_solve_sparse_batch_status", sparse_outside="misslap_solve_sparse_batch_outside",
+             ell="misslap_solve_ell_batch", ell_outside="misslap_solve_ell_batch_outside")
 SIZING = dict(dense_status=("misslap_dense_batch_workspace_bytes", (B, N, M, 0, 1)),
               dense_outside=("misslap_dense_batch_outside_workspace_bytes", (B, N, M, 0)),
               sparse_status=("misslap_sparse_batch_workspace_bytes", (B, NNZ, 0, 1)),
+              sparse_outside=("misslap_sparse_batch_outside_workspace_bytes", (B, N, M, 0)),
               ell=("misslap_ell_batch_workspace_bytes", (B, N, K, 0, 1)),
               ell_outside=("misslap_ell_batch_outside_workspace_bytes", (B, N, K, M, 0)))
 # the arrays a call reads with the input (on the host, or as device tensors in the stream-ordered mode); the sparse
-# call's offsets are read on the host in both modes, and a second time on the device with a workspace
+# calls' offsets are read on the host in both modes, and a second time on the device with a workspace
 INPUTS = dict(dense_status=dict(mat=MATS, shapes=SHAPES), dense_outside=dict(mat=MATS, shapes=SHAPES, outside=OUTSIDE),
-              sparse_status=dict(loc=LOC, val=VAL, offsets_dev=OFFSETS), ell=dict(cols=COLS, vals=VALS, rows=ROWS),
-              ell_outside=dict(cols=COLS, vals=VALS, rows=ROWS, outside=OUTSIDE))
+              sparse_status=dict(loc=LOC, val=VAL, offsets_dev=OFFSETS),
+              sparse_outside=dict(loc=LOC, val=VAL, offsets_dev=OFFSETS, outside=OUTSIDE),
+              ell=dict(cols=COLS, vals=VALS, rows=ROWS), ell_outside=dict(cols=COLS, vals=VALS, rows=ROWS, outside=OUTSIDE))
 
 
-def front_end(name):
-    """The status-mode result of the entry point's Python front end on the host input (fast, guard on where there is one)."""
-    if name == "dense_status":
-        return auction_solve_batch(MATS, fast=True, shapes=SHAPES, errors="status")
-    if name == "dense_outside":
-        return auction_solve_batch(MATS, fast=True, shapes=SHAPES, errors="status", outside=OUTSIDE)
-    if name == "sparse_status":
-        return auction_solve_sparse_batch(LOC, VAL, OFFSETS, fast=True, errors="status", dims=(N, M))
-    return auction_solve_ell_batch(COLS, VALS, rows=ROWS, n_cols=M, fast=True, errors="status",
-                                   outside=OUTSIDE if name == "ell_outside" else None)
+def front_end(name, a=None):
+    """The status-mode result of the entry point's Python front end (fast, guard on where there is one) on the host
+    input, or on `a`: INPUTS[name] as device tensors (the front end sends the sparse calls' offsets itself)."""
+    a = INPUTS[name] if a is None else a
+    kw = dict(fast=True, errors="status")
+    if "outside" in a:
+        kw["outside"] = a["outside"]
+    if name.startswith("dense"):
+        return auction_solve_batch(a["mat"], shapes=a["shapes"], **kw)
+    if name.startswith("sparse"):
+        return auction_solve_sparse_batch(a["loc"], a["val"], OFFSETS, dims=(N, M), **kw)
+    return auction_solve_ell_batch(a["cols"], a["vals"], rows=a["rows"], n_cols=M, **kw)
 
 
 def options(on_device):
@@ -94,6 +100,9 @@ def solve(lib, name, a, opts, stream, work, nwork, out, on_device):
     elif name == "sparse_status":
         args = (B, a["loc"], a["val"], OFFSETS.ctypes.data, a["offsets_dev"], None, 1, None, 0, 1) + way + (
             N, M, o["sol"], o["prices_out"]) + tail
+    elif name == "sparse_outside":
+        args = (B, a["loc"], a["val"], OFFSETS.ctypes.data, a["offsets_dev"], None, 1, None, 0) + way + (
+            N, M, a["outside"], N, o["sol"], o["prices_out"], o["outside_prices_out"]) + tail
     elif name == "ell":
         args = (B, N, K, a["cols"], 0, a["vals"], a["rows"], 1, None, 0, 1) + way + (M, o["sol"], o["prices_out"]) + tail
     else:
@@ -192,6 +201,29 @@ def test_stream_ordered_mode_is_the_host_mode_bit_for_bit(gpu_lib, name):
         assert np.array_equal(bits(out[key].cpu().numpy()), bits(host[key])), key
     assert (out["info"].threads, out["info"].lds_bytes) == (host["info"].threads, host["info"].lds_bytes)
     assert out["info"].threads == 256 and out["info"].wall_ms == 0  # nothing is waited for, nothing is timed
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", NAMES)
+def test_front_end_on_device_tensors_is_the_front_end_on_host_arrays(gpu_lib, name):
+    import torch
+    dev = torch.device("cuda", 0)
+    want = expected(name)
+    got = front_end(name, {k: torch.from_numpy(v).to(dev) for k, v in INPUTS[name].items() if k != "offsets_dev"})
+    assert set(got) == set(want) | {"records", "info", "stream", "keep"}
+    assert ("outside_prices" in want) == name.endswith("outside")
+    got_meta = batch_meta_to_host(got)  # (waits for the call's stream)
+    for key in ("sol", "status", "matching_size"):
+        assert got[key].is_cuda and np.array_equal(got[key].cpu().numpy(), want[key]), key
+    for key in ("prices", "outside_prices")[:2 if name.endswith("outside") else 1]:
+        assert got[key].is_cuda and np.array_equal(bits(got[key].cpu().numpy()), bits(want[key])), key
+    want_meta = batch_meta_to_host(want)
+    assert want_meta is want["meta"] and set(got_meta) == set(want_meta)
+    for key in set(want_meta) - {"timer", "gpu"}:  # length-B arrays, bit for bit
+        assert got_meta[key].dtype == want_meta[key].dtype and got_meta[key].tobytes() == want_meta[key].tobytes(), key
+    untimed = [k for k in want_meta["gpu"] if not k.endswith("_ms")]
+    assert untimed and set(got_meta["gpu"]) == set(want_meta["gpu"])
+    assert [got_meta["gpu"][k] for k in untimed] == [want_meta["gpu"][k] for k in untimed]
 
 
 @pytest.mark.parametrize("name", NAMES)
