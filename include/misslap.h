@@ -41,7 +41,8 @@ extern "C" {
  *      misslap_dense_batch_outside_workspace_bytes (with MISSLAP_BATCH_STATUS_BAD_OUTSIDE, code 15),
  *      misslap_solve_sparse_batch_outside, misslap_sparse_batch_outside_workspace_bytes,
  *      misslap_solve_dense_batch_status_strided, misslap_solve_dense_batch_outside_strided,
- *      misslap_matching_dense_batch_strided. */
+ *      misslap_matching_dense_batch_strided, misslap_solve_sparse_batch_status_view,
+ *      misslap_solve_sparse_batch_outside_view, misslap_sparse_batch_view_workspace_bytes. */
 
 /* misslap_options.mat_dtype: the element type of a dense stack */
 #define MISSLAP_DTYPE_F64 0   /* double */
@@ -818,6 +819,69 @@ int misslap_solve_sparse_batch_outside(int64_t B, const int32_t *loc, const doub
  * starts and, with has_prices, the staged starting prices of the augmented problems (B x (Mmax + Nmax) doubles), each
  * 256-byte aligned; -1 where B, Nmax or Mmax are out of range.  Needs no GPU. */
 int64_t misslap_sparse_batch_outside_workspace_bytes(int64_t B, int64_t Nmax, int64_t Mmax, int32_t has_prices);
+
+/* ---- the sparse batch on a VIEW of the packed arrays, as a device pipeline leaves them: int64 indices that are a slice
+ * of a wider buffer or a transposed view, float32 values, and offsets that only the device has seen.
+ * misslap_solve_sparse_batch_status_view and misslap_solve_sparse_batch_outside_view are
+ * misslap_solve_sparse_batch_status and misslap_solve_sparse_batch_outside with this head in place of (B, loc, val,
+ * offsets, offsets_dev, ...); no host offsets exist, nnz is an argument:
+ *   nnz            the packed entries of the call (0 .. 2^56).
+ *   loc, loc_int64, stride_e, stride_c   entry g of the packed arrays is row loc[g * stride_e], column
+ *                  loc[g * stride_e + stride_c], in ELEMENTS of the index type: int32, or int64 with loc_int64 != 0.
+ *                  Strides are >= 0 and (nnz - 1) * stride_e + stride_c must fit 62 bits: anything else is
+ *                  MISSLAP_ERR_INVALID, before a device is touched.  (2, 1) is the compact (nnz, 2) array, (3, 1) the
+ *                  [:, 1:] of an (nnz, 3) array, (1, nnz) the transposed (2, nnz) array.  Offsets are formed in 64 bits;
+ *                  loc needs only its element's alignment.
+ *   val            the value of entry g is val[g], contiguous, of opt->mat_dtype: MISSLAP_DTYPE_F64 or MISSLAP_DTYPE_F32
+ *                  (every other type is MISSLAP_ERR_INVALID).  A float32 value is widened to double as it is read, which
+ *                  is exact; C, eps, bids, prices, eCE and both objectives are the float64 arithmetic on the widened
+ *                  value, and prices, outside values and every output stay double.
+ *   offsets_dev    int64[B + 1] on the device.  Checked there, per problem: a problem whose slice is not
+ *                  0 <= offsets[b] <= offsets[b + 1] <= nnz, or holds 2^31 - 1 entries or more, gets
+ *                  MISSLAP_BATCH_STATUS_BAD_SHAPE (7) ahead of every other check; nothing of its loc / val is read and
+ *                  its outputs are the condemned ones with an all-zero record.  (7 cannot otherwise occur in the status
+ *                  call; in the outside call it already means "the extent of this problem is unusable".)
+ *                  offsets[0] != 0 or offsets[B] != nnz is no error: entries in no slice are never read.
+ * loc, val and offsets_dev are DEVICE pointers in both modes of the call and opt->input_on_device must be set
+ * (MISSLAP_ERR_INVALID otherwise); prices_in and outside live on the device with them.  With a workspace every pointer
+ * except opt and info is a device pointer, the launches go onto `stream`, and nothing is allocated, copied or waited
+ * for; without one the library uses its own stream and scratch, uploads a host sizes, and waits once at the end.
+ * Only elements of the view are read: nothing outside offsets[b] .. offsets[b + 1] of any problem, nothing of the
+ * storage between the view's elements; nothing is written.
+ * An int64 index outside the int32 range SATURATES to INT32_MIN / INT32_MAX before any check: a column at or above 2^31
+ * is MISSLAP_BATCH_STATUS_TOO_LARGE (and so is such a last row in the outside call; in the status call a row that far
+ * from its predecessor is a ROW_GAP, as INT32_MAX is in misslap_solve_sparse_batch_status), a value at or below -2^31 is
+ * NEGATIVE_INDEX whatever its low word is, and nothing is ever truncated into a valid index.
+ * Apart from the above every verdict, output, record and check order is that of misslap_solve_sparse_batch_status /
+ * _outside on a compact copy -- int32 (nnz, 2) indices, the values widened to double, the same offsets on the host -- bit
+ * for bit.  The guard of the status call cannot size its LDS carve from the largest problem: it is sized for
+ * min(nnz, MISSLAP_SPARSE_BATCH_MAX_DIM) rows, which still matches every clean graph within the cap.  The row starts live
+ * in a block of Nmax + 1 ints per problem in both calls, so a malformed slice cannot reach a healthy problem.
+ * The kernels are a family of their own (csrc/kernels_sparse_view.hpp): the contiguous calls keep theirs. */
+int misslap_solve_sparse_batch_status_view(int64_t B, int64_t nnz, const void *loc, int32_t loc_int64, int64_t stride_e,
+                                           int64_t stride_c, const void *val, const int64_t *offsets_dev,
+                                           const int64_t *sizes, int32_t fast, const double *prices_in, int64_t prices_ld,
+                                           int32_t cardinality_check, const misslap_options *opt, void *stream,
+                                           void *workspace, int64_t workspace_bytes, int64_t Nmax, int64_t Mmax,
+                                           int32_t *sol, double *prices_out, int32_t out_on_device, int32_t *status,
+                                           int32_t *matching_size, misslap_dense_batch_meta *meta,
+                                           misslap_dense_batch_info *info);
+/* (workspace: misslap_sparse_batch_outside_workspace_bytes -- its carve depends neither on nnz nor on strides) */
+int misslap_solve_sparse_batch_outside_view(int64_t B, int64_t nnz, const void *loc, int32_t loc_int64, int64_t stride_e,
+                                            int64_t stride_c, const void *val, const int64_t *offsets_dev,
+                                            const int64_t *sizes, int32_t fast, const double *prices_in,
+                                            int64_t prices_ld, const misslap_options *opt, void *stream, void *workspace,
+                                            int64_t workspace_bytes, int64_t Nmax, int64_t Mmax, const double *outside,
+                                            int64_t outside_ld, int32_t *sol, double *prices_out,
+                                            double *outside_prices_out, int32_t out_on_device, int32_t *status,
+                                            int32_t *matching_size, misslap_dense_batch_meta *meta,
+                                            misslap_dense_batch_info *info);
+/* Bytes of workspace a stream-ordered misslap_solve_sparse_batch_status_view needs: the check records, B x (Nmax + 1) row
+ * starts and, with cardinality_check, the cardinalities, each 256-byte aligned; -1 for B < 1, nnz < 0 or Nmax outside
+ * 1 .. MISSLAP_SPARSE_BATCH_MAX_DIM.  Needs no GPU.  nnz and has_prices are accepted for the day a layout depends on
+ * them: today's does not. */
+int64_t misslap_sparse_batch_view_workspace_bytes(int64_t B, int64_t nnz, int64_t Nmax, int32_t has_prices,
+                                                  int32_t cardinality_check);
 
 /* ---- the sparse batch from padded candidate lists (ELL), the layout a top-k, a gating step or a nearest-neighbour
  * search leaves on the device: cols[B][N][K] (int32, or int64 with cols_int64 != 0) and vals[B][N][K] (double, or float

@@ -205,6 +205,18 @@ def _check_offsets(offsets, nnz, missing):
     return off.shape[0] - 1, np.ascontiguousarray(off)
 
 
+def _check_device_offsets(offsets, dev):
+    """Offsets that a device pipeline left on the device: a contiguous int64 tensor of shape (B + 1,) on dev, the device
+    of loc / val.  Returns (B, the tensor).  Their values are the library's to judge, per problem: reading them here
+    would be a wait."""
+    import torch
+    if (offsets.dtype != torch.int64 or offsets.dim() != 1 or int(offsets.shape[0]) < 2 or offsets.device != dev or
+            not offsets.is_contiguous()):
+        raise ValueError(f"device offsets must be a contiguous int64 tensor of shape (B + 1,) with B >= 1 on {dev}, got "
+                         f"{offsets.dtype} {tuple(offsets.shape)} on {offsets.device}")
+    return int(offsets.shape[0]) - 1, offsets
+
+
 def _maxima(loc, offsets, on_device, per_problem):
     """(max row, max column) over all of loc, and per problem the max row (per_problem; empty problems: 0)."""
     B = offsets.shape[0] - 1

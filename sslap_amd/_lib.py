@@ -213,6 +213,17 @@ SYMBOLS = {
                                                      C.c_int64, _VP, _VP, _VP, C.c_int32, _VP, _VP, _VP,
                                                      C.POINTER(DenseBatchInfo)]),
     "misslap_sparse_batch_outside_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64, C.c_int32]),
+    # the view forms: (B, nnz, loc, loc_int64, stride_e, stride_c, val, offsets_dev) in place of (B, loc, val, offsets,
+    # offsets_dev)
+    "misslap_solve_sparse_batch_status_view": (C.c_int, [C.c_int64, C.c_int64, _VP, C.c_int32, C.c_int64, C.c_int64, _VP, _VP,
+                                                         _VP, C.c_int32, _VP, C.c_int64, C.c_int32, C.POINTER(Options), _VP,
+                                                         _VP, C.c_int64, C.c_int64, C.c_int64, _VP, _VP, C.c_int32, _VP, _VP,
+                                                         _VP, C.POINTER(DenseBatchInfo)]),
+    "misslap_solve_sparse_batch_outside_view": (C.c_int, [C.c_int64, C.c_int64, _VP, C.c_int32, C.c_int64, C.c_int64, _VP, _VP,
+                                                          _VP, C.c_int32, _VP, C.c_int64, C.POINTER(Options), _VP, _VP,
+                                                          C.c_int64, C.c_int64, C.c_int64, _VP, C.c_int64, _VP, _VP, _VP,
+                                                          C.c_int32, _VP, _VP, _VP, C.POINTER(DenseBatchInfo)]),
+    "misslap_sparse_batch_view_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
     "misslap_solve_ell_batch": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, _VP, C.c_int32, _VP, _VP, C.c_int32, _VP, C.c_int64,
                                           C.c_int32, C.POINTER(Options), _VP, _VP, C.c_int64, C.c_int64, _VP, _VP, C.c_int32,
                                           _VP, _VP, _VP, C.POINTER(DenseBatchInfo)]),

@@ -21,7 +21,10 @@
 // with implicit row bounds u * K .. (u + 1) * K and a unit-stride column read of index type E (int, long long), a
 // negative column being a hole that no step visits, or (d) a strided dense stack: source (b) with entry (b, i, j) at
 // mat[b * sB + i * sN + j * sM] for run-time strides >= 0 (the guard of the strided dense solves and
-// misslap_matching_dense_batch_strided).  No value is ever widened here: only the pattern is read.
+// misslap_matching_dense_batch_strided), or (e) a view of a packed loc (the guard of the sparse view solves,
+// kernels_sparse_view.hpp): source (a) with entry g of the packed arrays at row mat[g * sN], column mat[g * sN + sM], of
+// index type E (int, long long; an int64 index saturates into the int32 range as it is read), for graphs the view's
+// check pass found clean.  No value is ever widened here: only the pattern is read.
 #pragma once
 
 namespace misslap {
@@ -30,7 +33,7 @@ constexpr int kMatchBatchMaxDim = MISSLAP_MATCHING_BATCH_MAX_DIM;
 constexpr int kMatchBatchThreads = 256;
 constexpr int kMatchInf = INT_MAX;  // the reference's inf of Dist
 constexpr int kMatchBatchMaxEntries = INT_MAX - 2 * kWave;  // entries of one graph
-enum class MatchSrc { Loc, Dense, Ell, DenseStrided };  // where k_matching_batch reads its adjacency from
+enum class MatchSrc { Loc, Dense, Ell, DenseStrided, LocView };  // where k_matching_batch reads its adjacency from
 
 // per graph of a packed loc, from k_matching_batch_check
 struct MatchBatchCheck {
@@ -58,7 +61,8 @@ struct MatchBatchArgs {
     long long left_ld;
     int *right;                    // [B][right_ld] or null
     long long right_ld;
-    long long sB, sN, sM;          // source (d): the element strides of the stack (the other sources do not read them)
+    long long sB, sN, sM;          // source (d): the element strides of the stack; source (e): sN / sM the strides of an
+                                   // entry / of its column in `mat` (the other sources do not read them)
 };
 
 // Per graph: the maxima (n = max row + 1, m = max column + 1, feasibility_.pyx:245-246) and the first entry that
@@ -124,7 +128,8 @@ __device__ __forceinline__ void match_bfs_visit(int v, int L, const int *pair_v,
 template <MatchSrc kSrc, class E = double>
 __global__ __launch_bounds__(kMatchBatchThreads) void k_matching_batch(MatchBatchArgs a) {
     constexpr bool kStrided = kSrc == MatchSrc::DenseStrided, kDense = kSrc == MatchSrc::Dense || kStrided;
-    constexpr bool kEll = kSrc == MatchSrc::Ell, kLoc = kSrc == MatchSrc::Loc;
+    constexpr bool kEll = kSrc == MatchSrc::Ell, kView = kSrc == MatchSrc::LocView;
+    constexpr bool kLoc = kSrc == MatchSrc::Loc || kView;  // row starts in LDS, from a packed loc
     const int b = blockIdx.x, tid = threadIdx.x, T = blockDim.x, lane = lane_id(), wave = tid >> 6, nw = T >> 6;
     int n = 0, m = 0;
     long long s = 0;
@@ -142,6 +147,17 @@ __global__ __launch_bounds__(kMatchBatchThreads) void k_matching_batch(MatchBatc
         m = clean ? c.max_col + 1 : 0;
         nnz = (int)(a.N * a.M);  // slots, holes included (the host caps N * K at kMatchBatchMaxEntries)
         A = static_cast<const E *>(a.mat) + (size_t)b * (size_t)a.N * (size_t)a.M;
+    } else if (kView) {
+        // clean as below, and the slice itself usable (the view's offsets were never seen by the host)
+        const SparseBatchCheck c = a.schk[b];
+        const bool ok = !(c.err & kErrBadSlice);
+        s = ok ? a.offsets[b] : 0;
+        nnz = ok ? (int)(a.offsets[b + 1] - s) : 0;
+        const bool clean = nnz > 0 && !(c.err & (kErrColNegative | kErrRowsUnsorted | kErrRowGap)) &&
+                           c.last_row >= 0 && c.max_row == c.last_row;
+        n = clean ? sparse_batch_count(c.max_row) : 0;
+        m = clean ? sparse_batch_count(c.max_col) : 0;
+        A = static_cast<const E *>(a.mat);
     } else {
         s = a.offsets[b];
         nnz = (int)(a.offsets[b + 1] - s);
@@ -171,11 +187,24 @@ __global__ __launch_bounds__(kMatchBatchThreads) void k_matching_batch(MatchBatc
     int *row_ptr = pair_v + a.Ms;  // loc input only
     __shared__ int s_tail, s_found, s_cnt;
     // the graph's entries: row and column of local index k (64-bit offsets: 2k overflows an int above 2^30 entries)
-    const int *lc = kLoc ? a.loc + 2 * s : nullptr;
+    const int *lc = kLoc && !kView ? a.loc + 2 * s : nullptr;
     const int ek = kEll ? (int)a.M : 0;
-    auto row_of = [lc](int k) { return lc[2 * (long long)k]; };
+    auto view_at = [=](int k, long long at) {  // (source (e): entry s + k of the view, saturated into an int)
+        if constexpr (kView) {
+            const E v = A[(s + k) * a.sN + at];
+            return v < (E)INT_MIN ? INT_MIN : (v > (E)INT_MAX ? INT_MAX : (int)v);
+        } else {
+            return 0;
+        }
+    };
+    auto row_of = [=](int k) {
+        if constexpr (kView) return view_at(k, 0);
+        else return lc[2 * (long long)k];
+    };
     auto col_of = [=](int k) {  // (ELL: a hole reads as -1; a clean graph's columns are below Ms and narrow safely)
-        if constexpr (kEll) {
+        if constexpr (kView) {
+            return view_at(k, a.sM);
+        } else if constexpr (kEll) {
             const E c = A[k];
             return c < 0 ? -1 : (int)c;
         } else {

@@ -43,6 +43,7 @@
 #include "kernels_batch_solve.hpp"
 #include "kernels_dense_batch.hpp"
 #include "kernels_sparse_batch.hpp"
+#include "kernels_sparse_view.hpp"
 #include "kernels_ell_batch.hpp"
 #include "kernels_matching_batch.hpp"
 
@@ -520,3 +521,4 @@ MISSLAP_API int misslap_get_state(misslap_solver *h, double *prices, int32_t *un
 #include "abi_matching_batch.hpp"
 #include "abi_ell_batch.hpp"
 #include "abi_ell_batch_outside.hpp"
+#include "abi_sparse_view.hpp"

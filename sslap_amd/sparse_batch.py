@@ -15,13 +15,17 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._batch import (_STATUS_ERRORS, _StatusCall, _check_offsets, _contiguous, _decode_meta, _empty, _eps,
-                     _is_device_tensor, _maxima, _new_meta, _ptr, _scalar_outside, _send, _solve_options, _starting_prices,
-                     raise_for_status)
+from ._batch import (_STATUS_ERRORS, _StatusCall, _check_device_offsets, _check_offsets, _contiguous, _decode_meta,
+                     _empty, _eps, _host, _is_device_tensor, _maxima, _new_meta, _ptr, _scalar_outside, _send,
+                     _solve_options, _starting_prices, raise_for_status)
 from .auction_solve import _cname
 
 MAX_DIM = _lib.SPARSE_BATCH_MAX_DIM
 _INT_MAX = 2**31 - 1
+_DEVICE_OFFSETS_NEED_DIMS = ("offsets on the device need dims=(Nmax, Mmax): sizing the outputs from loc would read it "
+                             "back, and no wait may hide in this call")
+_DEVICE_OFFSETS_DEFAULT_MODE = ("offsets on the device are taken with errors='status' or with outside= (and dims=): the "
+                                "default mode reads offsets on the host")
 
 # what each status code of misslap_solve_sparse_batch_status says in the words of the default mode without its host
 # guard (abi_sparse_batch.hpp, abi_batch_common.hpp: reject_bad_prices)
@@ -66,7 +70,11 @@ def _pack(pairs):
 
 
 def _check_input(loc, val, offsets):
-    """dtype / shape / device of loc and val, offsets against them; returns (B, nnz, offsets int64, on_device)."""
+    """dtype / shape / device of loc and val, offsets against them; returns (B, nnz, offsets, on_device, view).  offsets:
+    int64 on the host, or the caller's device tensor.  view: None for what the contiguous entry points read -- numpy
+    arrays, or contiguous int32 / float64 tensors with host offsets -- else what the view entry points need to know:
+    dict(int64=, strides=(stride_e, stride_c), dtype=MISSLAP_DTYPE_*)."""
+    view = None
     if isinstance(loc, np.ndarray) and isinstance(val, np.ndarray):
         on_device = False
         if loc.ndim != 2 or loc.shape[1] != 2:
@@ -82,24 +90,30 @@ def _check_input(loc, val, offsets):
         on_device = True
         if loc.dim() != 2 or loc.shape[1] != 2:
             raise ValueError(f"loc must have shape (nnz, 2), got {tuple(loc.shape)}")
-        if loc.dtype != torch.int32:
-            raise ValueError(f"loc must be int32, got {loc.dtype}")
+        if loc.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"loc must be int32 or int64, got {loc.dtype}")
         if val.dim() != 1:
             raise ValueError(f"val must have 1 dimension, got {val.dim()}")
-        if val.dtype != torch.float64:
-            raise ValueError(f"val must be float64, got {val.dtype}")
-        if not loc.is_contiguous() or not val.is_contiguous():
-            raise ValueError("device tensors must be contiguous (they are read in place)")
+        if val.dtype not in (torch.float64, torch.float32):
+            raise ValueError(f"val must be float64 or float32, got {val.dtype}")
+        if not val.is_contiguous():
+            raise ValueError("a device val tensor must be contiguous (it is read in place; loc may have any strides)")
         if loc.device != val.device:
             raise ValueError(f"loc is on {loc.device}, val on {val.device}")
+        if loc.dtype != torch.int32 or val.dtype != torch.float64 or not loc.is_contiguous() or _is_device_tensor(offsets):
+            view = dict(int64=loc.dtype == torch.int64, strides=tuple(int(x) for x in loc.stride()),
+                        dtype=_lib.DTYPE_F32 if val.dtype == torch.float32 else _lib.DTYPE_F64)
     else:
         raise TypeError("loc and val must both be numpy arrays or both tensors on the device")
     nnz = int(loc.shape[0])
     if int(val.shape[0]) != nnz:
         raise ValueError(f"loc holds {nnz} entries, val {int(val.shape[0])}")
-    B, off = _check_offsets(offsets, nnz, "offsets is required with packed loc / val (a list of (loc, val) pairs needs "
-                                          "none)")
-    return B, nnz, off, on_device
+    if on_device and _is_device_tensor(offsets):
+        B, off = _check_device_offsets(offsets, loc.device)
+    else:
+        B, off = _check_offsets(offsets, nnz, "offsets is required with packed loc / val (a list of (loc, val) pairs "
+                                              "needs none)")
+    return B, nnz, off, on_device, view
 
 
 def sparse_to_augmented(loc, val, offsets, sizes=None, outside=0.):
@@ -142,9 +156,19 @@ def sparse_to_augmented(loc, val, offsets, sizes=None, outside=0.):
     return out
 
 
-def _check_sizes(sizes, B):
+def _check_sizes(sizes, B, dev=None):
+    """sizes as the call reads them: int64 (B, 2) on the host, or with device input (dev) possibly the caller's
+    contiguous int64 (B, 2) tensor on that device, whose values are the library's to judge."""
     if sizes is None:
         return None
+    if _is_device_tensor(sizes):
+        import torch
+        if dev is None:
+            raise TypeError("sizes on the device need loc / val on the device")
+        if sizes.dtype != torch.int64 or tuple(sizes.shape) != (B, 2) or sizes.device != dev or not sizes.is_contiguous():
+            raise ValueError(f"device sizes must be a contiguous int64 tensor of shape ({B}, 2) on {dev}, got {sizes.dtype} "
+                             f"{tuple(sizes.shape)} on {sizes.device}")
+        return sizes
     s = np.asarray(sizes)
     if s.shape != (B, 2) or not np.issubdtype(s.dtype, np.integer):
         raise ValueError(f"sizes must be an integer array of shape ({B}, 2), got {s.dtype} {s.shape}")
@@ -220,6 +244,31 @@ def auction_solve_sparse_batch(loc, val=None, offsets=None, problem="min", eps_s
     eps_start > 0 was given (then False); an explicit fast= or eps_start= is passed through.  fast=True means
     eps = 1 / n_b.  Why: the augmented problem is rectangular, where the reference's eps-scaling is not optimal in general
     and a single phase from zero prices is (README "Rectangular problems").
+
+    Views (device tensors only; misslap_solve_sparse_batch_status_view / _outside_view): what a device pipeline has is read
+    where it lies.  loc may be int32 or int64 of shape (nnz, 2) with ANY non-negative strides -- idx[:, 1:] of a
+    (nnz, 3) nonzero(), coo.indices()[1:].t() -- val float64 or float32 (1-d, contiguous; a float32 value is widened as it
+    is read, which is exact, and everything downstream and every output stays float64), offsets a host array as before
+    or a contiguous int64 (B + 1,) tensor on loc's device, sizes a host array or a contiguous int64 (B, 2) tensor there.
+    A contiguous int32 / float64 loc / val with host offsets takes the calls it always took; everything else takes the
+    view entry points, whose result is bit for bit that of the call on loc.to(int32).contiguous(), val.double(),
+    offsets.cpu().  Device offsets are never read on the host, so they need dims= (ValueError without: no wait may
+    hide in the call) and are taken with errors="status" and with outside= (the default mode reads offsets on the host:
+    TypeError); they are judged per problem on the device: a slice that is not 0 <= offsets[b] <= offsets[b + 1] <= nnz
+    (or holds 2^31 - 1 entries or more) gets status 7 (MISSLAP_BATCH_STATUS_BAD_SHAPE) ahead of every other check,
+    nothing of it is read, its outputs are the condemned ones with an all-zero record, and no other problem notices.
+    offsets[0] != 0 or offsets[B] != nnz is no error: entries in no slice are never read.  An int64 index outside the
+    int32 range saturates before any check: a column >= 2^31 is TOO_LARGE (so is a last row that large with outside=;
+    without, it is first of all a ROW_GAP, as INT32_MAX is in an int32 loc), a value <= -2^31 NEGATIVE_INDEX; nothing is
+    truncated into a valid index.  errors="raise" on a view runs the status call and then raise_for_status, which
+    returns the status-mode dict; raise_for_status copies device offsets / sizes back itself, after its synchronise.
+    Host numpy arrays keep every rule they had (int32 loc, float64 val, offsets from 0 to nnz).  The recipe:
+
+        idx = gate.nonzero()                                  # (nnz, 3) int64: b, i, j, sorted
+        off = torch.searchsorted(idx[:, 0].contiguous(), torch.arange(B + 1, device=idx.device))   # int64 (B + 1,)
+        res = auction_solve_sparse_batch(idx[:, 1:], cost[gate], off, dims=(N, M), outside=cost_limit, errors="status")
+
+    No wait, no copy of an entry: the only launches besides the library's are nonzero, the mask gather and searchsorted.
     """
     if errors not in ("raise", "status"):
         raise ValueError(f"errors must be 'raise' or 'status', got {errors!r}")
@@ -230,18 +279,26 @@ def auction_solve_sparse_batch(loc, val=None, offsets=None, problem="min", eps_s
             raise TypeError("a list of (loc, val) pairs takes no val / offsets; packed loc and val are numpy arrays or "
                             "device tensors")
         loc, val, offsets = _pack(loc)
-    B, nnz, off, on_device = _check_input(loc, val, offsets)
-    szs = _check_sizes(sizes, B)
+    B, nnz, off, on_device, view = _check_input(loc, val, offsets)
+    szs = _check_sizes(sizes, B, loc.device if on_device else None)
+    if _is_device_tensor(off):
+        if errors != "status" and outside is None:
+            raise TypeError(_DEVICE_OFFSETS_DEFAULT_MODE)
+        if dims is None:
+            raise ValueError(_DEVICE_OFFSETS_NEED_DIMS)
     e = _eps(eps_start)
     if outside is not None:
         if fast is None:  # (resolved here: the library gets a plain flag)
             fast = not e > 0
-        res = _solve_outside(loc, val, B, nnz, off, on_device, problem, e, max_iter, fast, szs, prices, dims, outside)
+        res = _solve_outside(loc, val, B, nnz, off, on_device, problem, e, max_iter, fast, szs, prices, dims, outside,
+                             view)
         return raise_for_status(res) if errors == "raise" else res
     fast = bool(fast)  # (None: False, the call is what it was)
-    if errors == "status":
-        return _solve_status(loc, val, B, nnz, off, on_device, problem, e, max_iter, fast, szs, cardinality_check, prices,
-                             dims)
+    if errors == "status" or view is not None or _is_device_tensor(szs):
+        # (the default mode's own call reads compact int32 / float64 arrays and host offsets / sizes only)
+        res = _solve_status(loc, val, B, nnz, off, on_device, problem, e, max_iter, fast, szs, cardinality_check, prices,
+                            dims, view)
+        return res if errors == "status" else raise_for_status(res)
     max_row, max_col, rows = _maxima(loc, off, on_device, per_problem=fast and szs is None)
     Nmax = min(max(max_row + 1, 1), MAX_DIM)  # (a problem beyond the cap is rejected by the library, in its order)
     Mmax = min(max(max_col + 1, 1), MAX_DIM)
@@ -292,13 +349,14 @@ def _status_prices(prices, B, on_device, loc):
     return p
 
 
-def _solve_status(loc, val, B, nnz, off, on_device, problem, e, max_iter, fast, szs, cardinality_check, prices, dims):
-    """errors="status" of auction_solve_sparse_batch (misslap_solve_sparse_batch_status)."""
+def _solve_status(loc, val, B, nnz, off, on_device, problem, e, max_iter, fast, szs, cardinality_check, prices, dims,
+                  view=None):
+    """errors="status" of auction_solve_sparse_batch (misslap_solve_sparse_batch_status, or its view form)."""
     check = 1 if cardinality_check else 0
     p = _status_prices(prices, B, on_device, loc)  # (a host array, or with device input possibly a device tensor)
     Nmax, Mmax = _out_dims(dims, loc, off, on_device)
-    opts = _solve_options(on_device, loc, problem, e, max_iter)
-    return _call(loc, val, B, nnz, off, on_device, opts, fast, szs, p, Nmax, Mmax, check)
+    opts = _solve_options(on_device, loc, problem, e, max_iter, _lib.DTYPE_F64 if view is None else view["dtype"])
+    return _call(loc, val, B, nnz, off, on_device, opts, fast, szs, p, Nmax, Mmax, check, view=view)
 
 
 def _out_dims(dims, loc, off, on_device, n_sized=0):
@@ -306,28 +364,46 @@ def _out_dims(dims, loc, off, on_device, n_sized=0):
     mode's one read-back); n_sized: the most rows sizes names, where they count."""
     if dims is not None:
         return _check_dims(dims)
+    if _is_device_tensor(off):
+        raise ValueError(_DEVICE_OFFSETS_NEED_DIMS)
     max_row, max_col, _ = _maxima(loc, off, on_device, per_problem=False)
     return min(max(max_row + 1, n_sized, 1), MAX_DIM), min(max(max_col + 1, 1), MAX_DIM)
 
 
-def _call(loc, val, B, nnz, off, on_device, opts, fast, szs, p, Nmax, Mmax, check, out_v=None, out_ld=0):
+def _view_head(B, nnz, loc, val, view, d_off):
+    """The arguments of a view entry point that stand where the contiguous ones have (B, loc, val, offsets,
+    offsets_dev): loc where it lies with its element strides, val, and the offsets on the device.  Nothing is copied."""
+    se, sc = view["strides"]
+    return (B, nnz, _ptr(loc), 1 if view["int64"] else 0, se, sc, _ptr(val), _ptr(d_off))
+
+
+def _call(loc, val, B, nnz, off, on_device, opts, fast, szs, p, Nmax, Mmax, check, out_v=None, out_ld=0, view=None):
     """The call of misslap_solve_sparse_batch_status, or with outside values (out_v) of
-    misslap_solve_sparse_batch_outside, in either mode, and its result dict.  offsets is read on the host in both modes,
-    and with device input a second time on the device."""
+    misslap_solve_sparse_batch_outside, in either mode, and its result dict.  There offsets is read on the host in both
+    modes, and with device input a second time on the device.  With a view (_check_input) the call is the entry point's
+    _view form: loc / val are read where they lie and offsets on the device only."""
     dev = loc.device if on_device else None
     lib = _lib.load()
-    lc, vc = _contiguous(loc), _contiguous(val)  # (device tensors are: they are read in place)
-    d_off = _send(off, dev) if on_device else None
+    d_off = _send(off, dev) if on_device else None  # (a device tensor passes through)
     d_sizes, d_p, d_out = _send(szs, dev), _send(p, dev), _send(out_v, dev)
     p_ld, has_p = (0, 0) if p is None else (int(p.shape[1]), 1)
-    head = (B, _ptr(lc), _ptr(vc), off.ctypes.data, _ptr(d_off), _ptr(d_sizes), 1 if fast else 0, _ptr(d_p), p_ld)
+    if view is None:
+        lc, vc = _contiguous(loc), _contiguous(val)  # (device tensors are: they are read in place)
+        head = (B, _ptr(lc), _ptr(vc), off.ctypes.data, _ptr(d_off), _ptr(d_sizes), 1 if fast else 0, _ptr(d_p), p_ld)
+        tag = ""
+    else:
+        head = (*_view_head(B, nnz, loc, val, view, d_off), _ptr(d_sizes), 1 if fast else 0, _ptr(d_p), p_ld)
+        tag = "_view"
     if out_v is None:
-        call = _StatusCall(lib, opts, B, Nmax, Mmax, None, dev, "misslap_sparse_batch_workspace_bytes", (B, nnz, has_p, check))
-        _lib.check(lib.misslap_solve_sparse_batch_status(*head, check, *call.way, Nmax, Mmax, *call.outs))
+        sizing = ("misslap_sparse_batch_workspace_bytes", (B, nnz, has_p, check)) if view is None else \
+                 ("misslap_sparse_batch_view_workspace_bytes", (B, nnz, Nmax, has_p, check))
+        call = _StatusCall(lib, opts, B, Nmax, Mmax, None, dev, *sizing)
+        _lib.check(getattr(lib, "misslap_solve_sparse_batch_status" + tag)(*head, check, *call.way, Nmax, Mmax, *call.outs))
     else:
         call = _StatusCall(lib, opts, B, Nmax, Mmax, Nmax, dev, "misslap_sparse_batch_outside_workspace_bytes",
                            (B, Nmax, Mmax, has_p))
-        _lib.check(lib.misslap_solve_sparse_batch_outside(*head, *call.way, Nmax, Mmax, _ptr(d_out), out_ld, *call.outs))
+        _lib.check(getattr(lib, "misslap_solve_sparse_batch_outside" + tag)(*head, *call.way, Nmax, Mmax, _ptr(d_out),
+                                                                            out_ld, *call.outs))
     return call.result((loc, val, d_off, d_sizes, d_p, d_out), layout="sparse", dims=(Nmax, Mmax), sizes=szs, offsets=off,
                        loc=loc, prices_ld=p_ld)
 
@@ -366,16 +442,28 @@ def _check_outside(outside, B, dev):
     return _scalar_outside(outside, B, dev), 0, 0
 
 
-def _solve_outside(loc, val, B, nnz, off, on_device, problem, e, max_iter, fast, szs, prices, dims, outside):
-    """outside= of auction_solve_sparse_batch (misslap_solve_sparse_batch_outside), in either mode."""
+def _solve_outside(loc, val, B, nnz, off, on_device, problem, e, max_iter, fast, szs, prices, dims, outside, view=None):
+    """outside= of auction_solve_sparse_batch (misslap_solve_sparse_batch_outside, or its view form), in either mode."""
     dev = loc.device if on_device else None
     out_v, P, out_ld = _check_outside(outside, B, dev)
     p = _status_prices(prices, B, on_device, loc)  # (a host array, or with device input possibly a device tensor)
-    Nmax, Mmax = _out_dims(dims, loc, off, on_device, int(szs[:, 1].max()) if szs is not None else 0)
+    # (sizes on the device without dims: read back with the maxima, the mode's one wait)
+    Nmax, Mmax = _out_dims(dims, loc, off, on_device, int(szs[:, 1].max()) if szs is not None and dims is None else 0)
     if P and P < Nmax:
         raise ValueError(f"outside must have shape ({B},) or ({B}, P) with P >= Nmax = {Nmax}, got P = {P}")
-    opts = _solve_options(on_device, loc, problem, e, max_iter)
-    return _call(loc, val, B, nnz, off, on_device, opts, fast, szs, p, Nmax, Mmax, None, out_v, out_ld)
+    opts = _solve_options(on_device, loc, problem, e, max_iter, _lib.DTYPE_F64 if view is None else view["dtype"])
+    return _call(loc, val, B, nnz, off, on_device, opts, fast, szs, p, Nmax, Mmax, None, out_v, out_ld, view=view)
+
+
+def _bad_slice(res, b):
+    """The text for an unusable offsets[b] .. offsets[b + 1] of a result, or None where the slice is usable (device offsets
+    are copied back here: the caller has synchronised)."""
+    off, nnz = _host(res["offsets"]), int(res["loc"].shape[0])
+    s, e = int(off[b]), int(off[b + 1])
+    if 0 <= s <= e <= nnz and e - s < _INT_MAX:
+        return None
+    return (f"offsets[{b}] .. offsets[{b + 1}] = {s} .. {e} is not a slice of the {nnz} packed entries "
+            f"(0 <= start <= end <= nnz, fewer than 2^31 - 1 entries)")
 
 
 def _outside_error(res, b, code, n, m):
@@ -388,8 +476,10 @@ def _outside_error(res, b, code, n, m):
         text = "no entries (and no sizes to name its rows)"
     elif code == _lib.BATCH_STATUS_NEGATIVE_INDEX:
         text = "loc holds a negative row or column index"
+    elif code == _lib.BATCH_STATUS_BAD_SHAPE and _bad_slice(res, b):
+        text = _bad_slice(res, b)
     elif code == _lib.BATCH_STATUS_BAD_SHAPE:
-        text = f"sizes[{b}, 1] = {int(res['sizes'][b, 1])}: at least 1 and at least the last stored row + 1"
+        text = f"sizes[{b}, 1] = {int(_host(res['sizes'])[b, 1])}: at least 1 and at least the last stored row + 1"
     elif code == _lib.BATCH_STATUS_INFINITE_VALUE:
         text = "val holds a NaN or an infinity (in an entry or in the outside value of a row)"
     elif code == _lib.BATCH_STATUS_TOO_LARGE:
@@ -410,8 +500,10 @@ def _status_error(res, b, code, n, m, card):
     if code == _lib.BATCH_STATUS_DIVISION_BY_ZERO:
         return ZeroDivisionError(f"problem {b}: division by zero")
     Nmax, Mmax = res["dims"]
-    if code == _lib.BATCH_STATUS_NEGATIVE_INDEX:
-        last_row = int(res["loc"][int(res["offsets"][b + 1]) - 1, 0])
+    if code == _lib.BATCH_STATUS_BAD_SHAPE:  # (the view calls only: device offsets, judged per problem)
+        text = _bad_slice(res, b) or "offsets name no usable slice"
+    elif code == _lib.BATCH_STATUS_NEGATIVE_INDEX:
+        last_row = int(res["loc"][int(_host(res["offsets"])[b + 1]) - 1, 0])
         text = "negative row index" if last_row < 0 else "loc holds a negative row or column index"
     elif code == _lib.BATCH_STATUS_TOO_LARGE:
         if m >= _INT_MAX:
@@ -422,7 +514,7 @@ def _status_error(res, b, code, n, m, card):
         else:
             text = f"{n} x {m} does not fit sol_ld = {Nmax} / prices_out_ld = {Mmax}"
     else:
-        N = int(res["sizes"][b, 1]) if res["sizes"] is not None else n - 1  # from_sparse's N (sic, :592 / :594)
+        N = int(_host(res["sizes"])[b, 1]) if res["sizes"] is not None else n - 1  # from_sparse's N (sic, :592 / :594)
         text = _STATUS_TEXT[code].format(N=N, n=n, m=m, card=card, P=res["prices_ld"])
     return ValueError(f"problem {b}: {text}")
 
