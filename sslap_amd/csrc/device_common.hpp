@@ -394,6 +394,16 @@ __device__ __forceinline__ int half_allmax_i32(int v) {
     const auto s = __builtin_amdgcn_permlane16_swap(v, v, false, false);
     return max((int)s[0], (int)s[1]);
 }
+__device__ __forceinline__ double half_allmax_f64(double v) {  // (two swaps, one per word, and one v_max_f64)
+    v = __builtin_fmax(v, dppf_f64<kDppXor1>(v));
+    v = __builtin_fmax(v, dppf_f64<kDppXor2>(v));
+    v = __builtin_fmax(v, dppf_f64<kDppHalfMirror>(v));
+    v = __builtin_fmax(v, dppf_f64<kDppMirror>(v));
+    const int lo = __double2loint(v), hi = __double2hiint(v);
+    const auto sl = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
+    const auto sh = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+    return __builtin_fmax(__hiloint2double((int)sh[0], (int)sl[0]), __hiloint2double((int)sh[1], (int)sl[1]));
+}
 
 // wave-uniform maximum over the 32-lane half H (a scalar): after the row_mirror step EVERY lane of a 16-lane row holds its
 // row's maximum, so two v_readlane and one s_max_i32 replace the row broadcast, its v_max and the wait states around them
@@ -559,12 +569,14 @@ __device__ __forceinline__ void cand_eval2_r(Slot &slot, const PriceRec r, const
     }
 }
 // The same for ONE person (lanes 0..31 hold its line, `cls` = the lane is one of them and its slot is a candidate
-// slot, i.e. 1 <= lane <= kCandMax): the chain of single-bidder rounds is half of all rounds at C3 and two thirds
+// slot, i.e. 1 <= lane <= kCandMax), in LANE-WISE form (cand_eval1_lane below: the tail's chain and team rounds;
+// tail_pair_mode carries its two-line copy): the chain of single-bidder rounds is half of all rounds at C3 and two thirds
 // at C5, and a round is bound by the length of this dependent instruction sequence, not by memory.  What needs the line
-// alone (tau, the row length, the lane's cost -- -inf where the lane holds no candidate) is formed while the record gather
-// is in flight; behind it: the subtraction, one 32-bit reduction of the high words, ballot, the winner's data, the request
-// of the next line (`early`), then the second-best pass and the bid.  (Requesting the next line from the ballot's first
-// lane BEFORE the uniqueness test, into a second slot variable, was measured slower: profiles/tail_winner_path.txt.)
+// alone (tau, the row length, the lane's cost -- -inf where the lane holds no candidate -- and a copy of the lane's column)
+// is formed while the record gather is in flight; behind it: the subtraction, one 32-bit reduction of the high words,
+// ballot, the winning object's owner, the request of the next line (`early`), then the second-best pass and the bid.
+// (Requesting the next line from the ballot's first lane BEFORE the uniqueness test, into a second slot variable, was
+// measured slower: profiles/tail_winner_path.txt.)
 // the lane's record gather of a one-person line evaluation (split off: a caller may issue the gather of the NEXT round's
 // line ahead of a barrier and evaluate it behind it, kernels_tail.hpp)
 template <class Slot, class Src>
@@ -572,54 +584,67 @@ __device__ __forceinline__ PriceRec cand_gather1(const Slot &slot, const bool cl
     return src.get(cls ? max(slot.x, 0) : 0);  // (an empty slot reads record 0 like a lane outside the line; the index is
                                                // known to be >= 0, so no sign extension stands in front of the gather)
 }
-template <class Slot, class Early, class S = NoStamp>
-__device__ __forceinline__ void cand_eval1_r(Slot &slot, const PriceRec r, const bool cls, const double eps, CandBid &out,
-                                             unsigned &bad_hi, Early &&early, const S &stamp = S());
-template <class Slot, class Src, class Early, class S = NoStamp>
-__device__ __forceinline__ void cand_eval1(Slot &slot, const bool cls, const Src &src, const double eps, CandBid &out,
-                                           unsigned &bad_hi, Early &&early, const S &stamp = S()) {
-    stamp(1);  // (diagnostic builds: drains the memory counters) the line has landed
-    const PriceRec r = cand_gather1(slot, cls, src);
-    stamp(2);  // the records have landed
-    cand_eval1_r(slot, r, cls, eps, out, bad_hi, early, stamp);
+// A copy of a lane-wise value, made HERE and in a register of its own.  The lane-wise rounds keep the lane's column beyond
+// the request of the next line; with this copy (one v_mov under the record gather, where the wavefront waits anyway) the
+// next line is loaded straight into `slot`'s registers.  Left to itself the compiler keeps the column where it is, loads
+// the line elsewhere and moves it -- behind a wait -- at the loop's back edge: measured 2 ms per C3 solve slower in the
+// K <= 2 instance and in the team instance each (profiles/tail_winning_lane.txt).
+__device__ __forceinline__ int copy_here(int x) {
+    int r;
+    asm volatile("v_mov_b32 %0, %1" : "=&v"(r) : "v"(x));
+    return r;
 }
-template <class Slot, class Early, class S>
-__device__ __forceinline__ void cand_eval1_r(Slot &slot, const PriceRec r, const bool cls, const double eps, CandBid &out,
-                                             unsigned &bad_hi, Early &&early, const S &stamp) {
+// After the record gather the lane that holds the winning candidate has the round's whole result in its own registers:
+// the object (its slot's column), the candidate's cost, its value and the object's owner.  So that lane forms the bid and
+// the hit test and stores / publishes the result itself; nothing is read out into scalars and moved back into lane 0,
+// and the bid never becomes a key.  The operations, their operands and their order are those of the two-person form
+// above (v = cost - price, the last stored slot among equal maxima, W counting multiplicity, bid = (cost - W) + eps, hit =
+// a winner exists and V > tau and W >= tau) -- only the lane that executes them differs.  Wave-uniform is what control flow
+// needs: `prev` (in front of the request of the next line: the ONLY value read out there), `pstart`, `hit`, `len`.
+struct LaneBid {
+    bool hit;          // wave-uniform: the line decided
+    bool mine;         // the lane holds the winning candidate (one lane; none when the line has no candidate)
+    double bid;        // (lanes `mine`) bbest
+    int obj;           // the lane's column: a copy of slot.x, which the next line overwrites
+    int prev, pstart;  // wave-uniform: the winning object's owner and the owner's row start
+    int len;           // wave-uniform: row length of the person
+};
+template <class Slot, class Early, class S = NoStamp>
+__device__ __forceinline__ void cand_eval1_lane(Slot &slot, const PriceRec r, const bool cls, const double eps,
+                                                LaneBid &out, unsigned &bad_hi, Early &&early, const S &stamp = S()) {
     const int lane = lane_id();
     const double ninf = -__builtin_huge_val();
     const bool is_cand = cls & (slot.x >= 0);
     const double cost = slot_cost_or_ninf(slot, is_cand);  // (everything that needs the line alone: under the gather)
     const double tau = readlane_f64(__hiloint2double(slot.y, slot.x), 0);
     out.len = __builtin_amdgcn_readlane(slot.x, kCandLanes - 1);
+    out.obj = copy_here(slot.x);
     const double v = cost - r.price;  // vi = cost - p[j]   (:350); -inf where the lane holds no candidate
     const int hi = __double2hiint(v);
     const int k = hi ^ ((hi >> 31) & 0x7fffffff);  // signed order of k == order of the doubles' high words
     const int km = half_max_i32_s<0>(k);
     const unsigned eq = (unsigned)(__ballot(k == km) & 0xffffffffull);  // (never 0: a lane of 0..31 holds the maximum)
-    double V;
     int G, sl;
     if (__popc(eq) == 1) {  // wave-uniform, the common case: the winner is known after one 32-bit reduction
         G = sl = __ffs((int)eq) - 1;
-        V = readlane_f64(v, G);
     } else {
-        V = readlane_f64(half_max_f64(v), 31);
+        const double V = readlane_f64(half_max_f64(v), 31);
         G = __builtin_amdgcn_readlane(half_max_i32((is_cand & (v == V)) ? lane : -1), 31);  // the LAST slot holding it
         sl = max(G, 0);  // (-1: no candidate at all)
     }
-    out.obj = __builtin_amdgcn_readlane(slot.x, sl);
     out.prev = __builtin_amdgcn_readlane(r.owner, sl);
-    out.pstart = __builtin_amdgcn_readlane(r.ostart, sl);
-    const double c1 = slot_cost_at(slot, sl);
-    early(out);  // `slot` is dead from here on
+    early(out.prev);  // `slot` is dead from here on
     stamp.light(3);
-    const double W = readlane_f64(half_max_f64(lane == G ? ninf : v), 31);  // second best, counting multiplicity
-    out.hit = (G >= 0) & (V > tau) & (W >= tau);
-    const double bid = (c1 - W) + eps;  // bbest = costbest - wi + eps   (:360)
+    out.mine = lane == G;
+    out.pstart = __builtin_amdgcn_readlane(r.ostart, sl);
+    const double W = readlane_f64(half_max_f64(out.mine ? ninf : v), 31);  // second best, counting multiplicity
+    out.bid = (cost - W) + eps;  // bbest = costbest - wi + eps   (:360), in the winner's lane
+    const bool hit = out.mine & (v > tau) & (W >= tau);
+    out.hit = __builtin_amdgcn_ballot_w64(hit) != 0ull;
     // a bid that breaks the bits-as-integer order of the keys (negative: sign bit; NaN): the running maximum of the high
-    // words of the bids that count, tested once when the kernel ends (bad_hi_is_error) -- two instructions per bid
-    bad_hi = max(bad_hi, out.hit ? (unsigned)__double2hiint(bid) : 0u);
-    out.key = bid_to_key(bid);
+    // words of the bids that count, kept per lane and tested over the wavefront once when the kernel ends
+    // (bad_hi_is_error) -- two instructions per bid
+    bad_hi = max(bad_hi, hit ? (unsigned)__double2hiint(out.bid) : 0u);
 }
 // (+inf = 0x7ff00000:00000000 is a legal bid; every NaN an operation produces and every negative value has a larger high word)
 __device__ __forceinline__ bool bad_hi_is_error(unsigned bad_hi) { return bad_hi > 0x7ff00000u; }

@@ -108,7 +108,7 @@ struct k_sync_from_rec {
 struct TailStats {
     unsigned long long edges, miss_edges, builds;
     unsigned bids, misses;
-    unsigned bad_hi;  // largest high word of a bid made from a line (cand_eval1_r; bad_hi_is_error)
+    unsigned bad_hi;  // largest high word of a bid made from a line, per LANE (cand_eval1_lane; bad_hi_is_error)
     int err;
     double hint;  // cand_build's search distance, carried from one build of this wavefront to the next
 };
@@ -250,17 +250,27 @@ __device__ __forceinline__ void tail_chain_mode(const TailArgs &a, const E &ed, 
     const NoStamp stamp;
 #endif
     for (;;) {
-        CandBid b;
-        b.hit = false;
+        LaneBid w = {};
         int sp = -2;  // the person whose line was requested early (-2: nothing requested)
-        if (E::kCand)
-            cand_eval1(slot, cls, src, eps, b, st.bad_hi, [&](const CandBid &w) {
-                sp = w.prev;
+        if (E::kCand) {
+            stamp(1);  // (diagnostic builds: drains the memory counters) the line has landed
+            const PriceRec g = cand_gather1(slot, cls, src);
+            stamp(2);  // the records have landed
+            cand_eval1_lane(slot, g, cls, eps, w, st.bad_hi, [&](int prev) {
+                sp = prev;
                 request(sp, 0);
             }, stamp);
+        }
         stamp.light(4);
-        if (!b.hit) {  // wave-uniform (rare behind the maintenance pass: the scan and the line's rebuild stay inside this
-                       // block -- what the rebuild needs must not be carried across the join with the common path)
+        // ASSIGN (:396-418) is one store by the lane that holds the winning candidate, from its own registers
+        bool store = w.mine;
+        double bid = w.bid;
+        int obj = w.obj, len = w.len;
+        int nprev = w.prev, npst = w.pstart;
+        if (!w.hit) {  // wave-uniform (rare behind the maintenance pass: the scan and the line's rebuild stay inside this
+                       // block -- what the rebuild needs must not be carried across the join with the common path); the
+                       // scan's result is wave-uniform and lane 0 stores it
+            CandBid b;
             CandBuildArgs bd;
             if (E::kCand) {
                 const typename E::Raw none[4] = {};
@@ -272,14 +282,26 @@ __device__ __forceinline__ void tail_chain_mode(const TailArgs &a, const E &ed, 
             st.misses += 1;
             st.miss_edges += (unsigned long long)b.len;
             if (bd.want && lines) tail_build(a, pi, bd, eps, st);
+            store = lane == 0;
+            bid = key_to_bid(b.key);
+            obj = b.obj;
+            len = b.len;
+            nprev = b.prev;
+            npst = b.pstart;
         }
         stamp.light(5);
-        st.edges += (unsigned long long)b.len;
+        st.edges += (unsigned long long)len;
         st.bids += 1;
         r += 1;
-        if (lane == 0) apply_winner(a, pi, ps, b.obj, b.prev, b.key);  // ASSIGN (:396-418)
-        pi = b.prev;  // the evicted owner inherits the slot (:409) and bids next; -1: everybody is assigned
-        ps = b.pstart;
+        if (store) {
+            PriceRec n;
+            n.price = bid;
+            n.owner = pi;
+            n.ostart = ps;
+            a.rec[(unsigned)obj] = n;  // (an object: >= 0, no sign extension)
+        }
+        pi = nprev;  // the evicted owner inherits the slot (:409) and bids next; -1: everybody is assigned
+        ps = npst;
         const bool done = pi < 0 || r >= rmax;
         if (!done && sp != pi) request(pi, ps);  // (a scanned row decided differently from its line)
         stamp.light(6);
@@ -393,6 +415,14 @@ __device__ __forceinline__ void tail_solo_mode(const TailArgs &a, const E &ed, i
     }
 }
 
+// lane-wise values that a round forms under its record gather: the empty statement defines them at this point of the
+// program, so the compiler cannot sink the instructions that form them into the instruction-bound part of the round
+__device__ __forceinline__ void pin_here(int &a, int &b, int &c, double &d) {
+    int lo = __double2loint(d), hi = __double2hiint(d);
+    asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(lo), "+v"(hi));
+    d = __hiloint2double(hi, lo);
+}
+
 // ---- pair mode: K == 2, handles with lines ---------------------------------------------------------------------------
 // Wavefront 0 alone, in the form of the chain round: person A's line in lanes 0..31, person B's in lanes 32..63, ONE line
 // load, ONE record gather and ONE evaluation serve both bids; no LDS, no barrier.  Per half the chain's "winner first"
@@ -402,11 +432,16 @@ __device__ __forceinline__ void tail_solo_mode(const TailArgs &a, const E &ed, i
 // Both bids use the prices of the previous round: this round's records are stored after both bids are formed, and the
 // next gather follows those stores in program order (the wavefront's memory path is in order), so nothing gathered
 // ahead has to be patched.  A clean round -- two different objects, both owned: 99.9 % -- needs no RESOLVE: both
-// bidders win, each slot passes to the owner its bidder evicts (:409), and both records go out as ONE store on lanes 0
-// and 32.  Any other round runs RESOLVE (:375-385, strict ">": the earlier list position keeps an object on equal
+// bidders win, each slot passes to the owner its bidder evicts (:409), and both records go out as ONE store by the two
+// winning lanes.  Any other round runs RESOLVE (:375-385, strict ">": the earlier list position keeps an object on equal
 // bids), ASSIGN (:396-418) and push_all_left on two slots (:137-162) as tail_solo_mode does.  A line that does not
 // decide is answered by a full scan of the row, and the line is rebuilt, inside the miss block.  When K falls to 1 the
 // wavefront goes on in tail_chain_mode.
+// The evaluation is lane-wise (device_common.hpp: cand_eval1_lane, here for both halves in the same instructions): the
+// lane that holds its half's winning candidate forms the bid and the hit test against its half's tau and stores
+// {bid, its half's bidder, that bidder's row start} at its own column.  No per-half scalar is formed on the clean path:
+// wave-uniform are the two owners (read out in front of the request), "both lines decided" (one ballot), the two objects
+// of the clean test and the next row starts.
 template <class E>
 __device__ __forceinline__ void tail_pair_mode(const TailArgs &a, const E &ed, int *sU, int *sStart, int &K,
                                                long long &nits, const long long max_iter, const double eps,
@@ -439,109 +474,139 @@ __device__ __forceinline__ void tail_pair_mode(const TailArgs &a, const E &ed, i
     while (K == 2) {  // (wave-uniform: the loop ends by `break`)
         stamp(1);
         const PriceRec g = cand_gather1(slot, cls, src);
-        // both line evaluations (cand_eval1_r per half).  Under the gather: what needs the lines alone
+        // both line evaluations in the lane-wise form of cand_eval1_lane, both halves in the same instructions.  Under the
+        // gather: what needs the lines and the bidders alone, for the lane's half
         const bool is_cand = cls & (slot.x >= 0);
         const double cost = slot_cost_or_ninf(slot, is_cand);
-        CandBid b[2];
-        double tau[2], c1[2];
+        int obj = copy_here(slot.x);  // (the next lines overwrite `slot`)
+        double tau[2];
+        int len[2];
 #pragma unroll
         for (int X = 0; X < 2; ++X) {
             tau[X] = readlane_f64(__hiloint2double(slot.y, slot.x), kCandLanes * X);
-            b[X].len = __builtin_amdgcn_readlane(slot.x, kCandLanes * X + kCandLanes - 1);
+            len[X] = __builtin_amdgcn_readlane(slot.x, kCandLanes * X + kCandLanes - 1);
         }
+        double tauL = upper ? tau[1] : tau[0];
+        int piL = upper ? pi[1] : pi[0], psL = upper ? ps[1] : ps[0];
+        pin_here(obj, piL, psL, tauL);  // (formed HERE, where the wavefront waits anyway, not where they are first used)
         stamp(2);
         const double v = cost - g.price;  // vi = cost - p[j]   (:350); -inf where the lane holds no candidate
         const int hw = __double2hiint(v);
         const int k = hw ^ ((hw >> 31) & 0x7fffffff);  // signed order of k == order of the doubles' high words
-        const unsigned long long eq = __ballot(k == half_allmax_i32(k));
+        const bool top = k == half_allmax_i32(k);
+        const unsigned long long eq = __ballot(top);
         const unsigned eq0 = (unsigned)eq, eq1 = (unsigned)(eq >> 32);
-        int G[2];  // winning lane of each half (-1: no candidate)
-        double V[2];
+        int sl[2];  // winning lane of each half (the half's lane 0: no candidate)
+        bool mine;  // the lane holds its half's winning candidate
         if ((int)(__popc(eq0) == 1) & (int)(__popc(eq1) == 1)) {  // wave-uniform, the common case
-            G[0] = __ffs((int)eq0) - 1;
-            G[1] = __ffs((int)eq1) + (kCandLanes - 1);
-            V[0] = readlane_f64(v, G[0]);
-            V[1] = readlane_f64(v, G[1]);
+            sl[0] = __ffs((int)eq0) - 1;
+            sl[1] = __ffs((int)eq1) + (kCandLanes - 1);
+            mine = top;
         } else {  // a tie on the high word: the exact passes (for both halves, in the same instructions)
             const double vm = half_max_f64(v);
-            V[0] = readlane_f64(vm, kCandLanes - 1);
-            V[1] = readlane_f64(vm, kWave - 1);
-            const int gm = half_max_i32((is_cand & (v == (upper ? V[1] : V[0]))) ? lane : -1);  // the LAST slot holding it
-            G[0] = __builtin_amdgcn_readlane(gm, kCandLanes - 1);
-            G[1] = __builtin_amdgcn_readlane(gm, kWave - 1);
+            const double V0 = readlane_f64(vm, kCandLanes - 1), V1 = readlane_f64(vm, kWave - 1);
+            const int gm = half_max_i32((is_cand & (v == (upper ? V1 : V0))) ? lane : -1);  // the LAST slot holding it
+            const int G0 = __builtin_amdgcn_readlane(gm, kCandLanes - 1), G1 = __builtin_amdgcn_readlane(gm, kWave - 1);
+            mine = lane == (upper ? G1 : G0);  // (-1: no candidate, no lane)
+            sl[0] = max(G0, 0);
+            sl[1] = max(G1, kCandLanes);
         }
-#pragma unroll
-        for (int X = 0; X < 2; ++X) {
-            const int sl = max(G[X], kCandLanes * X);
-            b[X].obj = __builtin_amdgcn_readlane(slot.x, sl);
-            b[X].prev = __builtin_amdgcn_readlane(g.owner, sl);
-            b[X].pstart = __builtin_amdgcn_readlane(g.ostart, sl);
-            c1[X] = slot_cost_at(slot, sl);
-        }
-        const int sp0 = b[0].prev, sp1 = b[1].prev;  // the persons whose lines are requested early
+        // in front of the request only the two owners are read out: the persons whose lines are requested early
+        const int sp0 = __builtin_amdgcn_readlane(g.owner, sl[0]), sp1 = __builtin_amdgcn_readlane(g.owner, sl[1]);
         request(sp0, sp1);  // `slot` is dead from here on
         stamp.light(3);
-        const double wm = half_max_f64(((lane == G[0]) | (lane == G[1])) ? ninf : v);  // second best, counting multiplicity
-        const double W[2] = {readlane_f64(wm, kCandLanes - 1), readlane_f64(wm, kWave - 1)};
+        const double W = half_allmax_f64(mine ? ninf : v);  // second best of the lane's half, counting multiplicity
+        double bid = (cost - W) + eps;                      // bbest = costbest - wi + eps   (:360), in the winners' lanes
+        const bool hit = mine & (v > tauL) & (W >= tauL);
+        st.bad_hi = max(st.bad_hi, hit ? (unsigned)__double2hiint(bid) : 0u);  // (per lane, see cand_eval1_lane)
+        const unsigned long long hm = __builtin_amdgcn_ballot_w64(hit);  // (at most one lane per half)
+        // wave-uniform is what control flow needs: the clean test's two objects (the owners are already held) and the next
+        // row starts
+        int o[2], prev[2] = {sp0, sp1}, pst[2];
 #pragma unroll
         for (int X = 0; X < 2; ++X) {
-            b[X].hit = (G[X] >= 0) & (V[X] > tau[X]) & (W[X] >= tau[X]);
-            const double bid = (c1[X] - W[X]) + eps;  // bbest = costbest - wi + eps   (:360)
-            st.bad_hi = max(st.bad_hi, b[X].hit ? (unsigned)__double2hiint(bid) : 0u);  // (see cand_eval1_r)
-            b[X].key = bid_to_key(bid);
+            o[X] = __builtin_amdgcn_readlane(obj, sl[X]);
+            pst[X] = __builtin_amdgcn_readlane(g.ostart, sl[X]);
         }
+        bool store = mine;  // the lanes that hold a half's result {object, bid}: ASSIGN is one store by them
         stamp.light(4);
+        if (__popcll(hm) != 2) {  // wave-uniform (rare behind the maintenance pass): a line did not decide.  The scan and
+                                  // the line's rebuild stay inside this block; a scan's result is wave-uniform, so from
+                                  // here on lanes 0 and 32 hold the halves' results
+            CandBid b[2];
 #pragma unroll
-        for (int X = 0; X < 2; ++X) {
-            if (!b[X].hit) {  // wave-uniform (rare behind the maintenance pass: the scan and the line's rebuild stay inside
-                              // this block -- what the rebuild needs must not be carried across the join with the common path)
-                CandBuildArgs bd;
-                const typename E::Raw none[4] = {};
-                const int e = a.row_ptr[pi[X] + 1];
-                wave_bid_full<E, RecSource, true, false>(ed, src, ps[X], e, none, eps, b[X], bd, st.err);
-                st.misses += 1;
-                st.miss_edges += (unsigned long long)b[X].len;
-                if (bd.want) tail_build(a, pi[X], bd, eps, st);
-            }
-        }
-        stamp.light(5);
-        st.edges += (unsigned long long)(b[0].len + b[1].len);
-        st.bids += 2;
-        r += 1;
-        if ((b[0].obj != b[1].obj) & (b[0].prev >= 0) & (b[1].prev >= 0)) {  // wave-uniform
-            // CLEAN: both bidders win (:375-385 has nothing to resolve); ASSIGN (:396-418) of both as one store on
-            // lanes 0 and 32; each slot passes to the owner its bidder evicts (:409)
-            if (l32 == 0) {
-                PriceRec w;
-                w.price = key_to_bid(upper ? b[1].key : b[0].key);
-                w.owner = upper ? pi[1] : pi[0];
-                w.ostart = upper ? ps[1] : ps[0];
-                a.rec[upper ? b[1].obj : b[0].obj] = w;
+            for (int X = 0; X < 2; ++X) {
+                b[X].hit = (unsigned)(hm >> (kCandLanes * X)) != 0u;
+                b[X].key = bid_to_key(readlane_f64(bid, sl[X]));
+                b[X].obj = o[X];
+                b[X].prev = prev[X];
+                b[X].pstart = pst[X];
+                b[X].len = len[X];
             }
 #pragma unroll
             for (int X = 0; X < 2; ++X) {
-                pi[X] = b[X].prev;
-                ps[X] = b[X].pstart;
+                if (!b[X].hit) {
+                    CandBuildArgs bd;
+                    const typename E::Raw none[4] = {};
+                    const int e = a.row_ptr[pi[X] + 1];
+                    wave_bid_full<E, RecSource, true, false>(ed, src, ps[X], e, none, eps, b[X], bd, st.err);
+                    st.misses += 1;
+                    st.miss_edges += (unsigned long long)b[X].len;
+                    if (bd.want) tail_build(a, pi[X], bd, eps, st);
+                }
+                o[X] = b[X].obj;
+                prev[X] = b[X].prev;
+                pst[X] = b[X].pstart;
+                len[X] = b[X].len;
+                sl[X] = kCandLanes * X;
+            }
+            store = l32 == 0;
+            bid = key_to_bid(upper ? b[1].key : b[0].key);
+            obj = upper ? b[1].obj : b[0].obj;
+        }
+        stamp.light(5);
+        st.edges += (unsigned long long)(len[0] + len[1]);
+        st.bids += 2;
+        r += 1;
+        if ((int)(o[0] != o[1]) & (int)(prev[0] >= 0) & (int)(prev[1] >= 0)) {  // wave-uniform
+            // CLEAN: both bidders win (:375-385 has nothing to resolve); ASSIGN (:396-418) of both as ONE store by the two
+            // lanes that hold the results, straight from their registers; each slot passes to the owner its bidder evicts
+            // (:409)
+            if (store) {
+                PriceRec n;
+                n.price = bid;
+                n.owner = piL;
+                n.ostart = psL;
+                a.rec[(unsigned)obj] = n;  // (an object: >= 0, no sign extension)
+            }
+#pragma unroll
+            for (int X = 0; X < 2; ++X) {
+                pi[X] = prev[X];
+                ps[X] = pst[X];
             }
         } else {
-            // RESOLVE (:375-385): strict ">" -- the earlier list position keeps an object on equal bids
+            // RESOLVE (:375-385): strict ">" -- the earlier list position keeps an object on equal bids.  The keys are read
+            // out of the lanes here, where they are needed
             bool win0 = true, win1 = true;
-            if (b[0].obj == b[1].obj) {
-                if (b[1].key > b[0].key) win0 = false;
+            if (o[0] == o[1]) {
+                if (bid_to_key(readlane_f64(bid, sl[1])) > bid_to_key(readlane_f64(bid, sl[0]))) win0 = false;
                 else win1 = false;
             }
             // ASSIGN (:396-418): a winner's slot goes to the evicted owner (or becomes a hole), a loser stays
-            if (lane == 0) {
-                if (win0) apply_winner(a, pi[0], ps[0], b[0].obj, b[0].prev, b[0].key);
-                if (win1) apply_winner(a, pi[1], ps[1], b[1].obj, b[1].prev, b[1].key);
+            if (store & (upper ? win1 : win0)) {
+                PriceRec n;
+                n.price = bid;
+                n.owner = piL;
+                n.ostart = psL;
+                a.rec[(unsigned)obj] = n;
             }
             if (win0) {
-                pi[0] = b[0].prev;
-                ps[0] = b[0].pstart;
+                pi[0] = prev[0];
+                ps[0] = pst[0];
             }
             if (win1) {
-                pi[1] = b[1].prev;
-                ps[1] = b[1].pstart;
+                pi[1] = prev[1];
+                ps[1] = pst[1];
             }
             // push_all_left (:137-162) on two slots
             if (pi[0] == -1 && pi[1] != -1) {
@@ -842,8 +907,7 @@ __device__ __forceinline__ bool tail_team1_pipe(const TailArgs &a, const E &ed, 
             return true;
         }
         int sp = -2;  // the person whose line was requested early (-2: nothing requested)
-        CandBid b;
-        b.hit = false;
+        LaneBid w = {};
         stamp.light(0);
         // BID for my slot (auction_.pyx:339-365).  The gather follows the previous round's stores in program order.
         if (!have_g) grec = cand_gather1(slot, cls, src);
@@ -851,11 +915,19 @@ __device__ __forceinline__ bool tail_team1_pipe(const TailArgs &a, const E &ed, 
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         stamp.light(1);
 #endif
-        cand_eval1_r(slot, grec, cls, eps, b, st.bad_hi, [&](const CandBid &w) {
-            sp = w.prev;
+        cand_eval1_lane(slot, grec, cls, eps, w, st.bad_hi, [&](int prev) {
+            sp = prev;
             request(sp);  // the owner my bidder evicts if it wins
         });
-        if (!b.hit) {  // (rare behind the maintenance pass: the scan and the line's rebuild stay inside this block)
+        // The lane that holds the winning candidate publishes the bid and exchanges the clean test's tag, from the
+        // registers it already holds: {bid, bidder, bidder's row start} and {object, its owner, the owner's row start}
+        bool publish = w.mine;
+        double bid = w.bid;
+        int obj = w.obj, own = grec.owner, ost = grec.ostart, len = w.len;
+        int nprev = w.prev, npst = w.pstart;  // my slot's next occupant if my bidder wins: the owner it evicts
+        if (!w.hit) {  // wave-uniform (rare behind the maintenance pass: the scan and the line's rebuild stay inside this
+                       // block); the scan's result is wave-uniform and lane 0 publishes it
+            CandBid b;
             CandBuildArgs bd;
             const typename E::Raw none[4] = {};
             const int e = a.row_ptr[pi + 1 + lane_zero()];
@@ -863,19 +935,25 @@ __device__ __forceinline__ bool tail_team1_pipe(const TailArgs &a, const E &ed, 
             st.misses += 1;
             st.miss_edges += (unsigned long long)b.len;
             if (bd.want) tail_build(a, pi, bd, eps, st);
+            publish = lane == 0;
+            bid = key_to_bid(b.key);
+            obj = b.obj;
+            own = nprev = b.prev;
+            ost = npst = b.pstart;
+            len = b.len;
         }
-        st.edges += (unsigned long long)b.len;
+        st.edges += (unsigned long long)len;
         st.bids += 1;
         stamp.light(2);
-        if (lane == 0) {
-            const int old = atomicExch(&L.tab[pipe_hash(b.obj)], r);
+        if (publish) {
+            const int old = atomicExch(&L.tab[pipe_hash(obj)], r);
             PriceRec mine;
-            mine.price = key_to_bid(b.key);
+            mine.price = bid;
             mine.owner = pi;
             mine.ostart = ps;
             L.slot[par][n0].rec = mine;
-            L.slot[par][n0].aux = make_int4(b.obj, b.prev, b.pstart, 0);
-            if (old == r || b.prev < 0) L.dirty[par] = r;
+            L.slot[par][n0].aux = make_int4(obj, own, ost, 0);
+            if (old == r || own < 0) L.dirty[par] = r;
         }
         stamp.light(3);
         tail_barrier_lds();  // the bids are in LDS and every gather of the round has landed
@@ -895,7 +973,7 @@ __device__ __forceinline__ bool tail_team1_pipe(const TailArgs &a, const E &ed, 
                 // publish, the barrier and these reads
                 // (the next gather is issued right here, behind the stores and inside the block that has waited for the line:
                 // at the loop's back edge the compiler would put a wait for EVERYTHING in front of it, the stores included)
-                have_g = sp == b.prev;  // (wave-uniform; false only behind a scanned row that decided differently from its line)
+                have_g = sp == nprev;  // (wave-uniform; false only behind a scanned row that decided differently from its line)
                 if (have_g) {
                     touch_slot(slot);
                     if (lane < K) a.rec[lobj] = lrec;
@@ -903,8 +981,8 @@ __device__ __forceinline__ bool tail_team1_pipe(const TailArgs &a, const E &ed, 
                 } else {
                     if (lane < K) a.rec[lobj] = lrec;
                 }
-                pi = b.prev;
-                ps = b.pstart;
+                pi = nprev;
+                ps = npst;
             } else {
                 // RESOLVE / ASSIGN / push_all_left in full, on lanes = slots
                 have_g = false;
@@ -1052,7 +1130,8 @@ struct k_tail {
             md[3 + m] += __builtin_amdgcn_s_memrealtime();
             md[m] += (unsigned long long)nits;
         };
-        auto flush_stats = [&]() {  // a wavefront's statistics, once, when it leaves the kernel
+        auto flush_stats = [&]() {  // a wavefront's statistics, once, when it leaves the kernel (whole wavefronts call)
+            const bool bad_bid = __any(bad_hi_is_error(st.bad_hi));  // (the lane-wise rounds keep the maximum per lane)
             if (lane == 0) {
                 if (st.bids) {
                     const unsigned long long hits = (unsigned long long)(st.bids - st.misses), hit_edges = st.edges - st.miss_edges;
@@ -1068,7 +1147,7 @@ struct k_tail {
                     atomicAdd(&ctl->dbg[14], st.builds);
                     atomicAdd(&ctl->dbg[15], hit_edges);
                 }
-                if (bad_hi_is_error(st.bad_hi)) st.err |= kErrNegativeBid;
+                if (bad_bid) st.err |= kErrNegativeBid;
                 if (st.err) atomicOr(&ctl->err, st.err);
             }
         };
