@@ -111,8 +111,14 @@ MISSLAP_API int misslap_solve_sparse_batch(int64_t B, const int32_t *loc, const 
         return rc;
 
     // ---- check pass: every problem before any is solved
-    hipLaunchKernelGGL(k_sparse_batch_check, dim3((unsigned)B), dim3(256), 0, st, d_loc, d_val, d_off, d_p0,
-                       (long long)prices_ld, d_rs, d_chk);
+    SparseCheckArgs<SparsePacked> k{};
+    k.w = SparsePacked{d_loc, d_val};
+    k.offsets = d_off;
+    k.p0 = d_p0;
+    k.p0_ld = prices_ld;
+    k.row_start = d_rs;
+    k.out = d_chk;
+    hipLaunchKernelGGL((k_sparse_batch_check<SparsePacked, false>), dim3((unsigned)B), dim3(256), 0, st, k);
     HIP_TRY(hipGetLastError());
     // The matching guard on the device, behind the check pass and read back with it, for every problem whose graph the
     // check pass finds clean (rows ascending from 0 without a gap, no negative index) and within the cap: card[b] >= 0.
@@ -255,12 +261,11 @@ MISSLAP_API int misslap_solve_sparse_batch(int64_t B, const int32_t *loc, const 
     }
 
     // ---- the solve: one launch, one workgroup per problem
-    SparseBatchArgs a{};
+    SparseBatchArgs<SparsePacked> a{};
     a.s.eps_b = d_eps;
     a.s.p0 = d_p0;
     a.s.p0_ld = prices_ld;
-    a.loc = d_loc;
-    a.val = d_val;
+    a.w = SparsePacked{d_loc, d_val};
     a.offsets = d_off;
     a.row_start = d_rs;
     a.chk = d_chk;

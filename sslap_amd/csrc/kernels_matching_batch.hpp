@@ -22,9 +22,9 @@
 // negative column being a hole that no step visits, or (d) a strided dense stack: source (b) with entry (b, i, j) at
 // mat[b * sB + i * sN + j * sM] for run-time strides >= 0 (the guard of the strided dense solves and
 // misslap_matching_dense_batch_strided), or (e) a view of a packed loc (the guard of the sparse view solves,
-// kernels_sparse_view.hpp): source (a) with entry g of the packed arrays at row mat[g * sN], column mat[g * sN + sM], of
-// index type E (int, long long; an int64 index saturates into the int32 range as it is read), for graphs the view's
-// check pass found clean.  No value is ever widened here: only the pattern is read.
+// SparseView of kernels_sparse_batch.hpp): source (a) with entry g of the packed arrays at row mat[g * sN], column
+// mat[g * sN + sM], of index type E (int, long long; an int64 index saturates into the int32 range as it is read), for
+// graphs the view's check pass found clean.  No value is ever widened here: only the pattern is read.
 #pragma once
 
 namespace misslap {

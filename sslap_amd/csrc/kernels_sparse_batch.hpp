@@ -1,6 +1,28 @@
 // kernels_sparse_batch.hpp -- many small SPARSE problems, one workgroup per problem for its whole solve
 // (misslap_solve_sparse_batch, include/misslap.h; the host side is abi_sparse_batch.hpp), and the same solve with a
-// verdict per problem (misslap_solve_sparse_batch_status; abi_sparse_batch_status.hpp).
+// verdict per problem, on the packed arrays or on a view of them (misslap_solve_sparse_batch_status / _outside and their
+// _view forms; abi_sparse_batch_status.hpp).
+//
+// ONE kernel family -- the check pass, the row source of batch_solve and the two solve kernels -- templated on an entry
+// source Src, which says how entry g is read (row(g), col(g), value(g)) and whether the host has checked the offsets
+// (Src::kHostOffsets).  Two sources:
+//   SparsePacked      loc [nnz][2] int32 and val [nnz] float64, read as loc[2 * g], loc[2 * g + 1], val[g]; the host
+//                     has validated the offsets (sparse_batch_offsets, abi_sparse_batch.hpp).
+//   SparseView<I, V>  what a device pipeline left behind: int32 or int64 indices with run-time strides, float64 or
+//                     float32 values, and offsets that only the device has seen.  What that changes:
+//     ACCESS   entry g is row loc[g * se], column loc[g * se + sc], value val[g]; offsets are formed in 64 bits.  An
+//              int64 index outside the int32 range SATURATES to INT_MIN / INT_MAX as it is read, before any check sees
+//              it: a value at or below -2^31 is a negative index whatever its low word is, one at or above 2^31 is
+//              beyond every carve, and nothing is ever truncated into a valid index.  A float32 value is widened to
+//              double as it is read (exact); everything downstream is the float64 arithmetic of the packed source.
+//     OFFSETS  nobody checked them on the host (!kHostOffsets).  A problem whose slice is not
+//              0 <= offsets[b] <= offsets[b + 1] <= nnz, or holds 2^31 - 1 entries or more, gets kErrBadSlice from the
+//              check pass before anything of loc / val is read; the solve kernels turn that into
+//              MISSLAP_BATCH_STATUS_BAD_SHAPE ahead of every other check, and the guard skips the problem.
+//     ROW STARTS  in a block of Ns + 1 ints per problem in both modes (with host-checked offsets the plain mode keeps
+//              them at offsets[b] + b of an nnz + B array, which races between problems once the offsets are not
+//              monotone); every index written is clamped to the block.  sparse_row_starts is the one place that knows.
+// Apart from that every verdict, output and record is the same for both sources, bit for bit.
 //
 // The round loop is batch_solve (kernels_batch_solve.hpp); this file has the check pass and the sparse row source.
 // What differs from the dense source is where a row comes from.  Problem b is the entries offsets[b] .. offsets[b + 1]
@@ -16,10 +38,9 @@
 //   get_obj  every stored entry whose column is p2o[i] is added, in row order and stored order (:508-521): a
 //            duplicate of the chosen entry counts once per copy.
 //
-// The outside mode (misslap_solve_sparse_batch_outside; the <true> instances below; the host side is
-// abi_sparse_batch_outside.hpp): row i of problem b also holds one virtual entry (i, m_b + i), stored LAST in its row,
-// whose value is the row's outside value -- a private object that only row i can bid for, so a row may stay unmatched
-// and a row may have no stored entry at all.  n_b is sizes[b][1] (without sizes the last stored row + 1), m_b the
+// The outside mode (misslap_solve_sparse_batch_outside; the Out instances below): row i of problem b also holds one
+// virtual entry (i, m_b + i), stored LAST in its row, whose value is the row's outside value -- a private object that
+// only row i can bid for, so a row may stay unmatched and a row may have no stored entry at all.  n_b is sizes[b][1] (without sizes the last stored row + 1), m_b the
 // largest real column + 1; the problem solved is the n_b x (m_b + n_b) packed problem, the round loop is batch_solve
 // unchanged on a carve of Mmax + Nmax objects.  The row starts live in a block of Nmax + 1 ints per problem (n_b may
 // exceed nnz_b, so the plain mode's nnz_b + 1 slots do not fit) and a row gap is legal: the check pass fills the starts
@@ -43,34 +64,112 @@ struct SparseBatchCheck {
     int n;          // the outside mode: n_b = sizes[b][1] clamped to -1 .. INT_MAX, without sizes last_row + 1; else 0
 };
 
+constexpr int kErrBadSlice = 1 << 12;  // SparseBatchCheck::err without host-checked offsets: the slice is unusable
+
+// The packed arrays as misslap_solve_sparse_batch and its status / outside forms take them.
+struct SparsePacked {
+    static constexpr bool kHostOffsets = true;
+    const int *loc;     // [nnz][2]
+    const double *val;  // [nnz]
+
+    __device__ __forceinline__ int row(long long g) const { return loc[2 * g]; }
+    __device__ __forceinline__ int col(long long g) const { return loc[2 * g + 1]; }
+    __device__ __forceinline__ double value(long long g) const { return val[g]; }
+};
+
+// The packed arrays as the caller's view presents them.
+template <class I, class V>
+struct SparseView {
+    static constexpr bool kHostOffsets = false;
+    const I *loc;      // entry g: row loc[g * se], column loc[g * se + sc]
+    const V *val;      // [nnz], contiguous
+    long long se, sc;  // >= 0, in elements of I
+
+    __device__ __forceinline__ static int narrow(I v) {
+        if constexpr (sizeof(I) == 8)
+            return v < (I)INT_MIN ? INT_MIN : (v > (I)INT_MAX ? INT_MAX : (int)v);
+        else
+            return v;
+    }
+    __device__ __forceinline__ int row(long long g) const { return narrow(loc[g * se]); }
+    __device__ __forceinline__ int col(long long g) const { return narrow(loc[g * se + sc]); }
+    __device__ __forceinline__ double value(long long g) const { return (double)val[g]; }
+};
+
+// Whether offsets[b] .. offsets[b + 1] = s .. e is a slice of the nnz packed entries that a problem can be
+__device__ __forceinline__ bool sparse_view_slice_ok(long long s, long long e, long long nnz) {
+    return s >= 0 && s <= e && e <= nnz && e - s < (long long)INT_MAX;
+}
+
+// Where the row starts (local indices) of problem b, whose entries begin at s, live in row_start.  Plain mode with
+// host-checked offsets: nnz_b + 1 slots at s + b of an nnz + B array (monotone offsets keep the problems apart).
+// Otherwise -- the outside mode, where n_b may exceed nnz_b, and offsets nobody checked -- a block of Ns + 1 ints.
+template <class Src, bool Out, class T>
+__device__ __forceinline__ T *sparse_row_starts(T *row_start, long long s, int b, int Ns) {
+    if constexpr (Src::kHostOffsets && !Out) return row_start + s + b;
+    else return row_start + (size_t)b * ((size_t)Ns + 1);
+}
+
+template <class Src>
 struct SparseBatchArgs {
-    BatchSolveArgs s;             // Ns / Ms: the batch's largest n_b / n_cols
-    const int *loc;               // [nnz][2]
-    const double *val;            // [nnz]
+    BatchSolveArgs s;             // Ns / Ms: the largest n_b / n_cols (the LDS carve; status modes: the caller's bound)
+    Src w;
     const long long *offsets;     // [B + 1]
-    const int *row_start;         // [nnz + B]: problem b's row starts (local indices) at offsets[b] + b
+    const int *row_start;         // where sparse_row_starts finds problem b's
     const SparseBatchCheck *chk;  // [B]
+};
+
+template <class Src>
+struct SparseCheckArgs {
+    Src w;
+    const long long *offsets, *sizes;  // sizes: [B][2] or null (read in the outside mode only)
+    const double *p0;
+    long long p0_ld;
+    int *row_start;  // where sparse_row_starts finds problem b's
+    SparseBatchCheck *out;
+    const double *outside;  // the outside mode: [B] (outside_ld == 0) or [B][outside_ld], outside_ld >= Nmax
+    long long outside_ld;
+    double *aug;            // the outside mode: [B][aug_ld] or null (no starting prices)
+    long long aug_ld;       // Mmax + Nmax
+    int Nmax, Mmax;         // the bounds on the rows and on the real columns (no row-start block, not in the outside
+                            // mode: unread)
+    long long nnz;          // the packed entries of the whole call (read without host-checked offsets only)
 };
 
 // Check pass, one workgroup per problem: the checks of AuctionSolver.__init__ (k_ingest_rows / k_ingest_vals with the
 // same rules), the maxima of from_sparse (:594-595) and of the guard (n_true, m_true), C = max |v|, the starting prices,
-// and the row starts.  A row start is written only where the rows seen so far are gap-free (r <= local index), so a
-// malformed problem never writes outside its own nnz_b + 1 slots.
-// Out (the outside mode): rs is the problem's own block of Ns + 1 row starts.  The thread that sees the row change
-// rp -> r at local index k fills rs[rp + 1 .. r] = k (the rows rp + 1 .. r - 1 are empty), thread 0 fills
+// and the row starts rs[0 .. rs_hi], which the calling kernel places (sparse_row_starts).  Without host-checked offsets
+// a problem with an unusable slice leaves only its record.  Plain mode: a row start is written only where the rows seen
+// so far are gap-free (r <= local index) and within rs_hi, so a malformed problem never writes outside its own slots.
+// Out (the outside mode): rs is the problem's own block of Ns + 1 row starts (rs_hi = Ns).  The thread that sees the row
+// change rp -> r at local index k fills rs[rp + 1 .. r] = k (the rows rp + 1 .. r - 1 are empty), thread 0 fills
 // rs[last_row + 1 .. n_b] = nnz_b; every index written is clamped to 0 .. Ns, so a malformed or oversized problem stays
-// within its block.  No row gap is reported.  The outside values of the rows < min(n_b, Ns) (ov: outside[b] with
-// ov_ld == 0, else outside[b * ov_ld + i]; ov_ld >= Ns) count as an entry's value does, and with starting prices the
-// augmented start [p0[:m_b], zeros(n_b)] is staged at aug[b * aug_ld ..] (aug_ld = Ms + Ns) -- only where the verdict
-// can still be 0 (no error, 1 <= n_b <= Ns, m_b <= Ms and m_b <= p0_ld, so m_b + n_b <= aug_ld).
-template <bool Out>
-__device__ __forceinline__ void sparse_batch_check(const int *loc, const double *val, const long long *offsets,
-                                                   const double *p0, long long p0_ld, int *rs, SparseBatchCheck *out,
-                                                   const long long *sizes, const double *ov, long long ov_ld,
-                                                   double *aug, long long aug_ld, int Ns, int Ms) {
+// within its block.  No row gap is reported.  The outside values of the rows < min(n_b, Ns) (outside[b] with
+// outside_ld == 0, else outside[b * outside_ld + i]; outside_ld >= Ns) count as an entry's value does, and with starting
+// prices the augmented start [p0[:m_b], zeros(n_b)] is staged at aug[b * aug_ld ..] (aug_ld = Ms + Ns) -- only where the
+// verdict can still be 0 (no error, 1 <= n_b <= Ns, m_b <= Ms and m_b <= p0_ld, so m_b + n_b <= aug_ld).
+template <class Src, bool Out>
+__device__ __forceinline__ void sparse_batch_check(const SparseCheckArgs<Src> &a, int *rs, int rs_hi) {
+    const Src &w = a.w;
+    const double *p0 = a.p0;
+    const long long p0_ld = a.p0_ld;
+    const int Ns = a.Nmax, Ms = a.Mmax;  // (read in the outside mode only)
     const int b = blockIdx.x;
-    const long long s = offsets[b], e = offsets[b + 1];
-    const int nnz = (int)(e - s);  // (the host rejects problems of 2^31 - 1 entries or more)
+    const long long s = a.offsets[b], e = a.offsets[b + 1];
+    if constexpr (!Src::kHostOffsets) {
+        if (!sparse_view_slice_ok(s, e, a.nnz)) {  // (uniform)
+            if (threadIdx.x == 0) {
+                SparseBatchCheck c{};
+                c.max_row = INT_MIN;
+                c.max_col = INT_MIN;
+                c.last_row = -1;
+                c.err = kErrBadSlice;
+                a.out[b] = c;
+            }
+            return;
+        }
+    }
+    const int nnz = (int)(e - s);  // (fewer than 2^31 - 1 entries: the host's check of the offsets, or the slice test)
     __shared__ unsigned long long s_abs;
     __shared__ int s_err, s_maxr, s_maxc, s_badp;
     if (threadIdx.x == 0) {
@@ -81,13 +180,15 @@ __device__ __forceinline__ void sparse_batch_check(const int *loc, const double 
         s_badp = 0;
     }
     __syncthreads();
-    const int last_row = nnz > 0 ? loc[2 * (e - 1)] : -1;
+    const int last_row = nnz > 0 ? w.row(e - 1) : -1;
     int err = 0, mr = INT_MIN, mc = INT_MIN;
     unsigned long long am = 0ull;
     int n = 0;  // the outside mode's n_b
     if constexpr (Out) {
-        if (sizes) {
-            const long long v = sizes[2 * b + 1];
+        const double *ov = a.outside;
+        const long long ov_ld = a.outside_ld;
+        if (a.sizes) {
+            const long long v = a.sizes[2 * b + 1];
             n = (int)(v < -1 ? -1 : (v > INT_MAX ? INT_MAX : v));
         } else {
             n = last_row < 0 ? 0 : (last_row == INT_MAX ? INT_MAX : last_row + 1);
@@ -103,25 +204,25 @@ __device__ __forceinline__ void sparse_batch_check(const int *loc, const double 
     }
     for (int k = threadIdx.x; k < nnz; k += blockDim.x) {
         const long long g = s + k;
-        const int r = loc[2 * g], c = loc[2 * g + 1];
+        const int r = w.row(g), c = w.col(g);
         mr = r > mr ? r : mr;
         mc = c > mc ? c : mc;
-        const unsigned long long bits = (unsigned long long)__double_as_longlong(val[g]) & 0x7fffffffffffffffull;
+        const unsigned long long bits = (unsigned long long)__double_as_longlong(w.value(g)) & 0x7fffffffffffffffull;
         if (bits >= 0x7ff0000000000000ull) err |= kErrNonFinite;
         am = bits > am ? bits : am;
         if (r < 0 || c < 0) {
             err |= kErrColNegative;
             continue;
         }
-        const int rp = k ? loc[2 * (g - 1)] : -1;
+        const int rp = k ? w.row(g - 1) : -1;
         if (r < rp) err |= kErrRowsUnsorted;
         else if (r > rp) {
             if constexpr (Out) {
-                const int hi = r < Ns ? r : Ns;
+                const int hi = r < rs_hi ? r : rs_hi;
                 for (int i = rp < 0 ? 0 : rp + 1; i <= hi; ++i) rs[i] = k;
             } else {
                 if (r != rp + 1 || r > last_row) err |= kErrRowGap;
-                else if (r <= k) rs[r] = k;  // (r > k implies a gap earlier in the problem)
+                else if (r <= k && r <= rs_hi) rs[r] = k;  // (r > k implies a gap earlier in the problem)
             }
         }
     }
@@ -130,27 +231,24 @@ __device__ __forceinline__ void sparse_batch_check(const int *loc, const double 
     if (mc != INT_MIN) atomicMax(&s_maxc, mc);
     if (am) atomicMax(&s_abs, am);
     __syncthreads();
+    // m_b = n_cols (0 without an entry; only meaningful without errors), in 64 bits: a column may be INT_MAX
+    const long long m = s_maxc < 0 ? 0 : (long long)s_maxc + 1;
+    if (p0 && s_err == 0 && m > 0)
+        batch_check_prices(p0 + (size_t)b * (size_t)p0_ld, (int)(m < p0_ld ? m : p0_ld), &s_badp);
     if constexpr (Out) {
-        const long long m = s_maxc < 0 ? 0 : (long long)s_maxc + 1;  // m_b (0 without an entry)
-        if (p0 && s_err == 0 && m > 0)
-            batch_check_prices(p0 + (size_t)b * (size_t)p0_ld, (int)(m < p0_ld ? m : p0_ld), &s_badp);
         if (p0 && s_err == 0 && n >= 1 && n <= Ns && m <= (long long)Ms && m <= p0_ld) {
             const double *src = p0 + (size_t)b * (size_t)p0_ld;
-            double *dst = aug + (size_t)b * (size_t)aug_ld;
+            double *dst = a.aug + (size_t)b * (size_t)a.aug_ld;
             for (int j = threadIdx.x; j < (int)m + n; j += blockDim.x) dst[j] = j < (int)m ? src[j] : 0.0;
         }
-    } else {
-        const int m = s_maxc + 1;  // n_cols (only meaningful without errors)
-        if (p0 && s_err == 0 && m > 0)  // (the host rejects m > p0_ld)
-            batch_check_prices(p0 + (size_t)b * (size_t)p0_ld, (long long)m < p0_ld ? m : (int)p0_ld, &s_badp);
     }
     __syncthreads();
     if (threadIdx.x == 0) {
         if constexpr (Out) {
-            const int hi = n < Ns ? n : Ns;
-            for (int i = last_row < 0 ? 0 : (last_row < Ns ? last_row + 1 : Ns + 1); i <= hi; ++i) rs[i] = nnz;
+            const int hi = n < rs_hi ? n : rs_hi;
+            for (int i = last_row < 0 ? 0 : (last_row < rs_hi ? last_row + 1 : rs_hi + 1); i <= hi; ++i) rs[i] = nnz;
         } else {
-            if (last_row >= 0 && last_row < nnz) rs[last_row + 1] = nnz;  // :47
+            if (last_row >= 0 && last_row < nnz && last_row < rs_hi) rs[last_row + 1] = nnz;  // :47
         }
         SparseBatchCheck c;
         c.absmax_bits = s_abs;
@@ -160,36 +258,17 @@ __device__ __forceinline__ void sparse_batch_check(const int *loc, const double 
         c.err = s_err;
         c.bad_price = s_badp;
         c.n = n;
-        out[b] = c;
+        a.out[b] = c;
     }
 }
 
-__global__ __launch_bounds__(256) void k_sparse_batch_check(const int *loc, const double *val, const long long *offsets,
-                                                            const double *p0, long long p0_ld, int *row_start,
-                                                            SparseBatchCheck *out) {
-    sparse_batch_check<false>(loc, val, offsets, p0, p0_ld, row_start + offsets[blockIdx.x] + blockIdx.x, out, nullptr,
-                              nullptr, 0, nullptr, 0, 0, 0);
-}
-
-struct SparseOutsideCheckArgs {
-    const int *loc;
-    const double *val;
-    const long long *offsets, *sizes;  // sizes: [B][2] or null
-    const double *p0;
-    long long p0_ld;
-    int *row_start;  // [B][Nmax + 1]
-    SparseBatchCheck *out;
-    const double *outside;  // [B] (outside_ld == 0) or [B][outside_ld], outside_ld >= Nmax
-    long long outside_ld;
-    double *aug;            // [B][aug_ld] or null (no starting prices)
-    long long aug_ld;       // Mmax + Nmax
-    int Nmax, Mmax;         // the bounds on the rows and on the real columns
-};
-
-__global__ __launch_bounds__(256) void k_sparse_outside_check(SparseOutsideCheckArgs a) {
-    sparse_batch_check<true>(a.loc, a.val, a.offsets, a.p0, a.p0_ld,
-                             a.row_start + (size_t)blockIdx.x * ((size_t)a.Nmax + 1), a.out, a.sizes, a.outside,
-                             a.outside_ld, a.aug, a.aug_ld, a.Nmax, a.Mmax);
+// The check kernel of every sparse call.  It places the problem's row starts: rs[0 .. hi] may be written.
+template <class Src, bool Out>
+__global__ __launch_bounds__(256) void k_sparse_batch_check(SparseCheckArgs<Src> a) {
+    const int b = blockIdx.x;
+    const long long s = a.offsets[b];
+    const int hi = Src::kHostOffsets && !Out ? (int)(a.offsets[b + 1] - s) : a.Nmax;  // (nnz_b + 1 slots, or the block)
+    sparse_batch_check<Src, Out>(a, sparse_row_starts<Src, Out>(a.row_start, s, b, a.Nmax), hi);
 }
 
 // The sparse row source of batch_solve: problem b's entries from global index s, row i at s + rs[i] .. s + rs[i + 1].
@@ -198,10 +277,9 @@ __global__ __launch_bounds__(256) void k_sparse_outside_check(SparseOutsideCheck
 // lane still scans in ascending stored order, the virtual entry wins ">=" ties as the last stored entry must, and the
 // winner's lane is r.g & 63 as before.  A row of len = 0 is a one-entry row: its second best is -inf and it bids +inf.
 // A chosen object j >= m is that entry: nothing of loc / val is read for it.
-template <bool Out = false>
+template <class Src, bool Out>
 struct SparseBatchRows {
-    const int *loc;
-    const double *val;
+    Src w;
     const long long *offsets;
     long long s;
     const int *rs;
@@ -221,8 +299,8 @@ struct SparseBatchRows {
         double cb = 0.0;
         int cj = 0;
         for (int q = lane; q < len; q += kWave) {
-            const int c = loc[2 * (g0 + q) + 1];
-            const double v = val[g0 + q];
+            const int c = w.col(g0 + q);
+            const double v = w.value(g0 + q);
             const double cost = maximize ? v : v * -1.0;  // :236-237
             const double vi = cost - price[c];
             if (vi >= x.v) {  // :351 (the first entry is always taken: vi >= -inf for every non-NaN vi)
@@ -260,11 +338,11 @@ struct SparseBatchRows {
         const int len = rs[i + 1] - rs[i];
         int last = -1;  // the last stored index of column j (:462-467)
         for (int q = lane; q < len; q += kWave)
-            if (loc[2 * (g0 + q) + 1] == j) last = q;
+            if (w.col(g0 + q) == j) last = q;
         last = wave_max_i32(last);
         double vj;
-        if constexpr (Out) vj = j >= m ? out.value(i) : val[g0 + (last < 0 ? 0 : last)];  // (j < m: stored, last >= 0)
-        else vj = val[g0 + last];
+        if constexpr (Out) vj = j >= m ? out.value(i) : w.value(g0 + (last < 0 ? 0 : last));  // (j < m: stored, last >= 0)
+        else vj = w.value(g0 + last);
         const double choice_cost = maximize ? vj : vj * -1.0;
         const double LHS = choice_cost - price[j] + tol;  // :475
         bool bad = false;
@@ -276,9 +354,9 @@ struct SparseBatchRows {
             }
         }
         for (int q = lane; q < len; q += kWave) {
-            const double v = val[g0 + q];
+            const double v = w.value(g0 + q);
             const double cost = maximize ? v : v * -1.0;
-            if (LHS < (cost - price[loc[2 * (g0 + q) + 1]]) - eps) bad = true;  // :482
+            if (LHS < (cost - price[w.col(g0 + q)]) - eps) bad = true;  // :482
         }
         return bad;
     }
@@ -303,7 +381,7 @@ struct SparseBatchRows {
             const int len = rs[i + 1] - rs[i];
             int cnt = 0, at = -1;
             for (int q = lane; q < len; q += kWave)
-                if (loc[2 * (g0 + q) + 1] == j) {
+                if (w.col(g0 + q) == j) {
                     ++cnt;
                     at = q;
                 }
@@ -311,7 +389,7 @@ struct SparseBatchRows {
             at = wave_max_i32(at);
             if (lane == 0) {
                 nsel[i] = cnt;
-                selv[i] = val[g0 + at];
+                selv[i] = w.value(g0 + at);
             }
         }
     }
@@ -331,8 +409,9 @@ struct SparseBatchRows {
             const long long g0 = s + rs[i];
             const int len = rs[i + 1] - rs[i];
             for (int q = 0; q < len; ++q)
-                if (loc[2 * (g0 + q) + 1] == j) {
-                    const double v = maximize ? val[g0 + q] : val[g0 + q] * -1.0;
+                if (w.col(g0 + q) == j) {
+                    const double x = w.value(g0 + q);
+                    const double v = maximize ? x : x * -1.0;
                     if (maximize) obj += v;
                     else obj -= v;
                 }
@@ -347,18 +426,21 @@ struct SparseBatchRows {
     }
 };
 
-__global__ __launch_bounds__(1024) void k_sparse_batch_solve(SparseBatchArgs a) {
+// the all-or-nothing call (misslap_solve_sparse_batch): the host has read the check records and found every problem fit
+__global__ __launch_bounds__(1024) void k_sparse_batch_solve(SparseBatchArgs<SparsePacked> a) {
     const int b = blockIdx.x;
     const SparseBatchCheck ck = a.chk[b];
     const long long s = a.offsets[b];
-    const SparseBatchRows<> rows{a.loc, a.val, a.offsets, s, a.row_start + s + b, a.s.maximize, 0, 0, {}};
+    const SparseBatchRows<SparsePacked, false> rows{
+        a.w, a.offsets, s, sparse_row_starts<SparsePacked, false>(a.row_start, s, b, a.s.Ns), a.s.maximize, 0, 0, {}};
     batch_solve(a.s, rows, ck.last_row + 1, ck.max_col + 1, ck.absmax_bits);
 }
 
-// ---- status mode (misslap_solve_sparse_batch_status): a verdict per problem instead of all or nothing
+// ---- status mode (misslap_solve_sparse_batch_status, _status_view): a verdict per problem instead of all or nothing
 
-struct SparseBatchStatusArgs {
-    SparseBatchArgs d;       // d.s.Ns / Ms = sol_ld / prices_ld: the caller's bound on every problem (dims), the LDS carve
+template <class Src>
+struct SparseStatusArgs {
+    SparseBatchArgs<Src> d;  // d.s.Ns / Ms = sol_ld / prices_ld: the caller's bound on every problem (dims), the LDS carve
     const long long *sizes;  // [B][2] or null: from_sparse's `size` of each problem (N = sizes[b][1], auction_.pyx:592)
     const int *card;         // [B] the guard's cardinalities (-1: not matched), or null: no guard in this call
     int fast;                // eps_start = 1 / N of each problem (:614-615)
@@ -392,10 +474,19 @@ __device__ __forceinline__ int sparse_batch_verdict(const SparseBatchCheck &c, l
 // k_sparse_batch_solve with the verdict formed here, from what the check pass and the guard left on the device.  A
 // condemned problem's workgroup writes the defined outputs and leaves before any LDS state exists and before anything of
 // loc, val or the row starts is read: an index beyond the carve never reaches the price array.  The others run the same
-// batch_solve on the same row source.
-__global__ __launch_bounds__(1024) void k_sparse_batch_solve_status(SparseBatchStatusArgs a) {
+// batch_solve on the same row source.  Without host-checked offsets an unusable slice is BAD_SHAPE before anything
+// else: its offsets are not read again and its record is all zeros.
+template <class Src>
+__global__ __launch_bounds__(1024) void k_sparse_batch_solve_status(SparseStatusArgs<Src> a) {
     const int b = blockIdx.x;
     const SparseBatchCheck ck = a.d.chk[b];
+    if constexpr (!Src::kHostOffsets) {
+        if (ck.err & kErrBadSlice) {
+            batch_publish_verdict(a.status, a.matching_size, b, MISSLAP_BATCH_STATUS_BAD_SHAPE, -1);
+            batch_condemn(a.d.s, 0, 0, 0);
+            return;
+        }
+    }
     const long long s = a.d.offsets[b];
     const long long nnz = a.d.offsets[b + 1] - s;
     const long long N = a.sizes ? a.sizes[2 * b + 1] : (long long)ck.max_row;  // sic, :592 / :594
@@ -409,15 +500,17 @@ __global__ __launch_bounds__(1024) void k_sparse_batch_solve_status(SparseBatchS
     }
     BatchSolveArgs bs = a.d.s;
     if (a.fast) batch_fast_eps(bs, (double)N);
-    const SparseBatchRows<> rows{a.d.loc, a.d.val, a.d.offsets, s, a.d.row_start + s + b, bs.maximize, 0, 0, {}};
+    const SparseBatchRows<Src, false> rows{
+        a.d.w, a.d.offsets, s, sparse_row_starts<Src, false>(a.d.row_start, s, b, a.d.s.Ns), bs.maximize, 0, 0, {}};
     batch_solve(bs, rows, ck.last_row + 1, ck.max_col + 1, ck.absmax_bits);
 }
 
-// ---- outside mode (misslap_solve_sparse_batch_outside): an outside option per row, for partial assignments
+// ---- outside mode (misslap_solve_sparse_batch_outside, _outside_view): an outside option per row, for partial assignments
 
+template <class Src>
 struct SparseOutsideArgs {
-    SparseBatchArgs d;       // d.s.Ns / Ms = Nmax / Mmax + Nmax (the carve), d.s.p0 / p0_ld the staged augmented prices,
-                             // d.s.prices null, d.row_start [B][Nmax + 1]
+    SparseBatchArgs<Src> d;  // d.s.Ns / Ms = Nmax / Mmax + Nmax (the carve), d.s.p0 / p0_ld the staged augmented prices,
+                             // d.s.prices null
     const long long *sizes;  // [B][2] or null: n_b = sizes[b][1] (sizes[b][0] is not read)
     int fast;                // eps_start = 1 / n_b of each problem
     int *status;             // [B] MISSLAP_BATCH_STATUS_*
@@ -450,19 +543,29 @@ __device__ __forceinline__ int sparse_outside_verdict(const SparseBatchCheck &c,
 // n x (m + n) problem, then the outputs in the caller's terms (batch_outside_outputs).  A condemned problem's workgroup
 // writes the defined outputs and leaves before any LDS state exists and before a row start, a loc or a val of its
 // problem is read.  Its record holds n_b, m_b + n_b and nnz_b + n_b where the verdict is one behind which they are
-// defined (3, 13, 14, 5, 6), and zeros otherwise.
-__global__ __launch_bounds__(1024) void k_sparse_outside_solve(SparseOutsideArgs a) {
+// defined (3, 13, 14, 5, 6), and zeros otherwise.  Without host-checked offsets an unusable slice is BAD_SHAPE before
+// anything else, as in the status solve.
+template <class Src>
+__global__ __launch_bounds__(1024) void k_sparse_outside_solve(SparseOutsideArgs<Src> a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
     const int b = blockIdx.x, tid = threadIdx.x, T = blockDim.x;
     const SparseBatchCheck ck = a.d.chk[b];
+    const int Nmax = a.d.s.Ns;
+    double *po = a.prices ? a.prices + (size_t)b * (size_t)a.Mmax : nullptr;
+    double *oo = a.outside_prices ? a.outside_prices + (size_t)b * (size_t)Nmax : nullptr;
+    if constexpr (!Src::kHostOffsets) {
+        if (ck.err & kErrBadSlice) {
+            batch_publish_verdict(a.status, a.matching_size, b, MISSLAP_BATCH_STATUS_BAD_SHAPE, -1);
+            batch_condemn(a.d.s, 0, 0, 0);
+            batch_outside_condemn(po, a.Mmax, oo, Nmax, tid, T);
+            return;
+        }
+    }
     const long long s = a.d.offsets[b];
     const long long nnz = a.d.offsets[b + 1] - s;
-    const int Nmax = a.d.s.Ns;
     const int own = sparse_outside_verdict(ck, nnz, a.sizes != nullptr, Nmax, a.Mmax, a.p0_ld, a.d.s.p0 != nullptr);
     const int code = batch_verdict(own, false, -1, 0, ck.bad_price);
     batch_publish_verdict(a.status, a.matching_size, b, code, -1);
-    double *po = a.prices ? a.prices + (size_t)b * (size_t)a.Mmax : nullptr;
-    double *oo = a.outside_prices ? a.outside_prices + (size_t)b * (size_t)Nmax : nullptr;
     if (code != MISSLAP_BATCH_STATUS_OK) {
         const bool counted = code == MISSLAP_BATCH_STATUS_INFINITE_VALUE || code == MISSLAP_BATCH_STATUS_TOO_LARGE ||
                              code == MISSLAP_BATCH_STATUS_PRICES_TOO_NARROW ||
@@ -477,8 +580,9 @@ __global__ __launch_bounds__(1024) void k_sparse_outside_solve(SparseOutsideArgs
     const int n = ck.n, m = ck.max_col < 0 ? 0 : ck.max_col + 1;
     if (a.fast) batch_fast_eps(bs, n);
     const double *O = a.outside + (a.outside_ld ? (size_t)b * (size_t)a.outside_ld : (size_t)b);
-    const SparseBatchRows<true> rows{a.d.loc, a.d.val, a.d.offsets, s, a.d.row_start + (size_t)b * ((size_t)Nmax + 1),
-                                     bs.maximize, m, n, {O, a.outside_ld ? 1 : 0}};
+    const SparseBatchRows<Src, true> rows{
+        a.d.w, a.d.offsets, s, sparse_row_starts<Src, true>(a.d.row_start, s, b, Nmax), bs.maximize, m, n,
+        {O, a.outside_ld ? 1 : 0}};
     batch_solve(bs, rows, n, m + n, ck.absmax_bits);
     batch_outside_outputs(s_raw, a.d.s, b, n, m, a.Mmax, Nmax, po, oo, tid, T);
 }

@@ -43,7 +43,6 @@
 #include "kernels_batch_solve.hpp"
 #include "kernels_dense_batch.hpp"
 #include "kernels_sparse_batch.hpp"
-#include "kernels_sparse_view.hpp"
 #include "kernels_ell_batch.hpp"
 #include "kernels_matching_batch.hpp"
 
@@ -516,9 +515,7 @@ MISSLAP_API int misslap_get_state(misslap_solver *h, double *prices, int32_t *un
 #include "abi_dense_batch_status.hpp"
 #include "abi_dense_batch_outside.hpp"
 #include "abi_sparse_batch.hpp"
-#include "abi_sparse_batch_status.hpp"
-#include "abi_sparse_batch_outside.hpp"
 #include "abi_matching_batch.hpp"
 #include "abi_ell_batch.hpp"
 #include "abi_ell_batch_outside.hpp"
-#include "abi_sparse_view.hpp"
+#include "abi_sparse_batch_status.hpp"
