@@ -42,13 +42,17 @@ extern "C" {
  *      misslap_solve_sparse_batch_outside, misslap_sparse_batch_outside_workspace_bytes,
  *      misslap_solve_dense_batch_status_strided, misslap_solve_dense_batch_outside_strided,
  *      misslap_matching_dense_batch_strided, misslap_solve_sparse_batch_status_view,
- *      misslap_solve_sparse_batch_outside_view, misslap_sparse_batch_view_workspace_bytes. */
+ *      misslap_solve_sparse_batch_outside_view, misslap_sparse_batch_view_workspace_bytes,
+ *      MISSLAP_DENSE_ENTRIES_FINITE in misslap_options.mat_dtype (no new entry point). */
 
 /* misslap_options.mat_dtype: the element type of a dense stack */
 #define MISSLAP_DTYPE_F64 0   /* double */
 #define MISSLAP_DTYPE_F32 1   /* float */
 #define MISSLAP_DTYPE_F16 2   /* IEEE binary16 */
 #define MISSLAP_DTYPE_BF16 3  /* bfloat16: the upper 16 bits of a float */
+/* OR-ed into mat_dtype: the entry rule of a dense stack of signed costs (misslap_solve_dense_batch_status has the text).
+ * The valid values of mat_dtype are 0 .. 3 and 0x100 .. 0x103; any other bit pattern is MISSLAP_ERR_INVALID. */
+#define MISSLAP_DENSE_ENTRIES_FINITE 0x100
 
 #define MISSLAP_OK 0
 #define MISSLAP_ERR_INVALID 1    /* malformed arguments / input contract violated */
@@ -552,7 +556,19 @@ int misslap_solve_dense_batch(int64_t B, int64_t N, int64_t M, const double *mat
  *   meta           required with a workspace; else as for misslap_solve_dense_batch.
  *   info           may be NULL; threads and lds_bytes are set (without a workspace wall_ms too), the other times are 0.
  * Only what is wrong with the whole call is an error: B, N, M, a NULL mat / sol / status, the options, a workspace that
- * is too small or misaligned. */
+ * is too small or misaligned.
+ *
+ * Signed costs: opt->mat_dtype = MISSLAP_DTYPE_* | MISSLAP_DENSE_ENTRIES_FINITE.  An element is then an entry iff it is
+ * not a NaN in its own type: negative values, -0.0 and subnormals are entries, and NaN is the one way to say "no
+ * edge".  An entry of +inf or -inf gives MISSLAP_BATCH_STATUS_INFINITE_VALUE.  Everything else is unchanged: n_cols is
+ * the largest column with an entry plus 1, C = max |v| over the entries, the checks and their order, shapes, fast,
+ * prices_in, both modes of the call, and the workspace size.  The result of a problem with status 0 is the reference's
+ * sparse solver on its entries in row-major order.  The flag is taken by this call,
+ * misslap_solve_dense_batch_outside (an outside value may then be any finite double: a NaN in a row < n_b is
+ * MISSLAP_BATCH_STATUS_BAD_OUTSIDE, an infinity MISSLAP_BATCH_STATUS_INFINITE_VALUE), both _strided forms,
+ * misslap_matching_dense_batch and misslap_matching_dense_batch_strided (an edge iff not a NaN; also the rule of this
+ * call's guard).  A contiguous stack in this mode is read by the kernels of the strided family with its natural
+ * strides.  misslap_solve_dense_batch itself does not take the flag (MISSLAP_ERR_INVALID): use this call. */
 #define MISSLAP_BATCH_STATUS_OK 0                /* solved */
 #define MISSLAP_BATCH_STATUS_TOO_FEW_VALUES 1    /* fewer valid values than rows */
 #define MISSLAP_BATCH_STATUS_EMPTY_ROW 2         /* a row without a valid entry */
@@ -988,6 +1004,8 @@ int64_t misslap_ell_batch_outside_workspace_bytes(int64_t B, int64_t N, int64_t 
  *                                 entry (i, j) iff mat[b][i][j] >= 0 (:256-262; NaN is not an entry, -0.0 and +inf are).
  *                                 The element type of mat is opt->mat_dtype, as for misslap_solve_dense_batch (the
  *                                 parameter keeps its declared type; the pairings are those of the widened stack).
+ *                                 With MISSLAP_DENSE_ENTRIES_FINITE OR-ed into opt->mat_dtype: entry (i, j) iff
+ *                                 mat[b][i][j] is not a NaN (negative values and both infinities are entries).
  *   opt            device, input_on_device (loc / mat are device pointers) and input_stream, as for the batch solves;
  *                  mat_dtype for misslap_matching_dense_batch; maximize, eps_start and max_iter are ignored, every
  *                  other field must be 0.

@@ -83,6 +83,17 @@ def _mat_dtype_name(mat_dtype):
     return name
 
 
+_ENTRIES = ("nonneg", "finite")
+
+
+def _entries_flag(entries):
+    """The entries= keyword of the dense calls as the bits it adds to mat_dtype: "nonneg" (v >= 0 is an entry, today's
+    rule) adds none, "finite" (every element that is not a NaN is one) adds MISSLAP_DENSE_ENTRIES_FINITE."""
+    if not isinstance(entries, str) or entries not in _ENTRIES:
+        raise ValueError(f"entries must be 'nonneg' or 'finite', got {entries!r}")
+    return _lib.DENSE_ENTRIES_FINITE if entries == "finite" else 0
+
+
 def _check_stack(mats, mat_dtype="float64"):
     """dtype and rank of a (B, N, M) stack of mat_dtype (numpy array or device tensor); returns (B, N, M, on_device,
     the MISSLAP_DTYPE_* code).  The stack must have exactly that dtype: nothing is converted.  A device tensor may have

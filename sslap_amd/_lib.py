@@ -12,6 +12,8 @@ MISSLAP_OK, ERR_INVALID, ERR_HIP, ERR_NO_DEVICE, ERR_STATE = 0, 1, 2, 3, 4
 
 # misslap_options.mat_dtype: the element type of a dense stack
 DTYPE_F64, DTYPE_F32, DTYPE_F16, DTYPE_BF16 = range(4)
+# OR-ed into mat_dtype: an element of a dense stack is an entry iff it is not a NaN (MISSLAP_DENSE_ENTRIES_FINITE)
+DENSE_ENTRIES_FINITE = 0x100
 
 
 class _DtypeOrReserved(C.Union):

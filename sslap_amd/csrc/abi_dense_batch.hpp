@@ -16,6 +16,14 @@ inline bool dense_entry_valid_host(T v) {  // float, F16, Bf16: by bit pattern i
     return dense_entry_valid(v);
 }
 
+// The entry rule a call's options ask for: true for MISSLAP_DENSE_ENTRIES_FINITE, and opt->mat_dtype is left as the
+// element type alone (normalise_options has checked the word), which is what every later reader of it expects.
+inline bool dense_take_entries_finite(misslap_options *opt) {
+    const bool finite = (opt->mat_dtype & MISSLAP_DENSE_ENTRIES_FINITE) != 0;
+    opt->mat_dtype &= ~(int32_t)MISSLAP_DENSE_ENTRIES_FINITE;
+    return finite;
+}
+
 // f(T{}) with T the element type mat_dtype names (normalise_options has checked the range)
 template <class F>
 auto dense_dtype_dispatch(int32_t mat_dtype, F &&f) {
@@ -97,15 +105,23 @@ inline DenseStrides dense_strides_arg(int64_t sB, int64_t sN, int64_t sM) {
 // The layout of a call's stack: strides null (the contiguous entry points) or {sB, sN, sM} of a strided one (`who`).
 // *str becomes null for the contiguous kernels, else `store`, filled.  A strided stack lies on the device (a host
 // stack is uploaded whole, and is compact); all of this is checked before any device is touched.
+// finite: the call's kernels are the finite-mode instances, which exist in the strided family only, so *str is never
+// null: a contiguous stack (of either kind of entry point) gets its natural strides (N * M, M, 1).
 int dense_stack_layout(const char *who, const misslap_options &opt, int64_t B, int64_t N, int64_t M,
-                       const int64_t *strides, DenseStrides *store, const DenseStrides **str) {
+                       const int64_t *strides, DenseStrides *store, const DenseStrides **str, bool finite = false) {
     *str = nullptr;
-    if (!strides) return MISSLAP_OK;
+    if (!strides) {
+        if (finite) {
+            *store = dense_strides_arg(N * M, M, 1);
+            *str = store;
+        }
+        return MISSLAP_OK;
+    }
     const int rc = dense_strides_check(B, N, M, strides[0], strides[1], strides[2], who);
     if (rc) return rc;
     if (!opt.input_on_device)
         return fail(MISSLAP_ERR_INVALID, "%s: a strided stack is a device array: set input_on_device", who);
-    if (dense_strides_compact(N, M, strides[0], strides[1], strides[2])) return MISSLAP_OK;
+    if (!finite && dense_strides_compact(N, M, strides[0], strides[1], strides[2])) return MISSLAP_OK;
     *store = dense_strides_arg(strides[0], strides[1], strides[2]);
     *str = store;
     return MISSLAP_OK;
@@ -132,6 +148,10 @@ MISSLAP_API int misslap_solve_dense_batch(int64_t B, int64_t N, int64_t M, const
     int rc = batch_options(opt_in, &opt, "misslap_solve_dense_batch",
                            "device, maximize, eps_start, max_iter, mat_dtype, input_on_device and input_stream", true);
     if (rc) return rc;
+    if (dense_take_entries_finite(&opt))  // (this call has a host guard and kernels of its own: not taught the mode)
+        return fail(MISSLAP_ERR_INVALID,
+                    "misslap_solve_dense_batch does not take MISSLAP_DENSE_ENTRIES_FINITE in mat_dtype: call "
+                    "misslap_solve_dense_batch_status");
     if (!mat || !sol) return fail(MISSLAP_ERR_INVALID, "null mat / sol");
     if ((rc = dense_batch_dims(B, N, M))) return rc;
     int32_t stride = 0;

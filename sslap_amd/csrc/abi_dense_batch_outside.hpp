@@ -19,6 +19,7 @@ struct DenseOutsideCall {
     int64_t B, N, M;
     const void *d_mat;  // elements of opt.mat_dtype
     const DenseStrides *str;  // the strides of a strided stack and its kernels, or null: the contiguous stack
+    bool finite;  // MISSLAP_DENSE_ENTRIES_FINITE: the finite-mode instances of the strided family (str is not null)
     const int32_t *d_shapes;
     const double *d_p0;
     const double *d_outside;
@@ -46,14 +47,16 @@ int dense_outside_enqueue(hipStream_t st, const misslap_options &opt, const Dens
     k.outside_ld = c.outside_ld;
     k.aug = d_aug;
     dense_dtype_dispatch(opt.mat_dtype, [&](auto t) {
-        if (c.str)
+        if (c.finite)
+            hipLaunchKernelGGL((k_dense_finite_check<decltype(t), true>), dim3((unsigned)c.B), dim3(256), 0, st, k, *c.str);
+        else if (c.str)
             hipLaunchKernelGGL((k_dense_strided_check<decltype(t), true>), dim3((unsigned)c.B), dim3(256), 0, st, k, *c.str);
         else
             hipLaunchKernelGGL(k_dense_outside_check<decltype(t)>, dim3((unsigned)c.B), dim3(256), 0, st, k);
     });
     HIP_TRY(hipGetLastError());
 
-    DenseStridedOutsideArgs a{};  // (its base is the contiguous kernels' argument)
+    DenseFiniteOutsideArgs a{};  // (its bases are the strided and the contiguous kernels' arguments)
     a.t.d.mat = c.d_mat;
     a.t.d.N = c.N;
     a.t.d.M = c.M;
@@ -71,9 +74,13 @@ int dense_outside_enqueue(hipStream_t st, const misslap_options &opt, const Dens
     // k_dense_outside_solve writes the real columns itself.)
     return dense_dtype_dispatch(opt.mat_dtype, [&](auto t) {
         using T = decltype(t);
+        if (c.str) a.str = *c.str;
+        if (c.finite)
+            return batch_solve_launch(k_dense_outside_solve<T, DenseFiniteOutsideArgs>, a, a.t.d.s, opt, c.B, c.N,
+                                      c.M + c.N, d.sol, c.N, nullptr, 0, d_aug, c.M + c.N, d.meta, d.info, st);
         if (c.str) {
-            a.str = *c.str;
-            return batch_solve_launch(k_dense_outside_solve<T, DenseStridedOutsideArgs>, a, a.t.d.s, opt, c.B, c.N,
+            DenseStridedOutsideArgs &s = a;
+            return batch_solve_launch(k_dense_outside_solve<T, DenseStridedOutsideArgs>, s, s.t.d.s, opt, c.B, c.N,
                                       c.M + c.N, d.sol, c.N, nullptr, 0, d_aug, c.M + c.N, d.meta, d.info, st);
         }
         DenseOutsideArgs &p = a;
@@ -102,6 +109,7 @@ int dense_outside_call(const char *who, int64_t B, int64_t N, int64_t M, const v
     int rc = batch_options(opt_in, &opt, who,
                            "device, maximize, eps_start, max_iter, mat_dtype, input_on_device and input_stream", true);
     if (rc) return rc;
+    const bool finite = dense_take_entries_finite(&opt);
     if ((rc = dense_batch_dims(B, N, M))) return rc;
     if (!mat || !sol || !status || !outside) return fail(MISSLAP_ERR_INVALID, "null mat / sol / status / outside");
     if (outside_ld != 0 && outside_ld < N)
@@ -109,7 +117,8 @@ int dense_outside_call(const char *who, int64_t B, int64_t N, int64_t M, const v
                     (long long)outside_ld, (long long)N);
     DenseStrides str_arg{};
     DenseOutsideCall c{};
-    if ((rc = dense_stack_layout(who, opt, B, N, M, strides, &str_arg, &c.str))) return rc;
+    if ((rc = dense_stack_layout(who, opt, B, N, M, strides, &str_arg, &c.str, finite))) return rc;
+    c.finite = finite;
     c.B = B;
     c.N = N;
     c.M = M;

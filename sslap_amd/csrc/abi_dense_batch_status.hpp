@@ -16,9 +16,10 @@ inline BatchCarve dense_status_carve(int64_t B, bool guard) {
 // The three launches of a call on st: the check pass, the guard, the solve with its verdict.  Every pointer is a device
 // pointer (d_mat: elements of opt.mat_dtype).  str: the strides of a strided stack (the strided family of
 // kernels_dense_batch.hpp and the matcher's strided source), or null: the contiguous stack and its kernels.
+// finite (MISSLAP_DENSE_ENTRIES_FINITE; str is then never null): the finite-mode instances of that family.
 int dense_batch_status_enqueue(hipStream_t st, const misslap_options &opt, int64_t B, int64_t N, int64_t M,
                                const void *d_mat, const DenseStrides *str, const int32_t *d_shapes, int32_t fast,
-                               const double *d_p0, bool guard, void *ws, const BatchStreamOut &d) {
+                               const double *d_p0, bool guard, void *ws, const BatchStreamOut &d, bool finite) {
     const BatchCarve carve = dense_status_carve(B, guard);
     DenseBatchCheck *d_chk = carve.at<DenseBatchCheck>(ws, 0);
     int *d_san = carve.at<int>(ws, 1);
@@ -35,7 +36,10 @@ int dense_batch_status_enqueue(hipStream_t st, const misslap_options &opt, int64
             k.p0 = d_p0;
             k.out = d_chk;
             k.shapes_out = d_san;
-            hipLaunchKernelGGL((k_dense_strided_check<T, false>), dim3((unsigned)B), dim3(256), 0, st, k, *str);
+            if (finite)
+                hipLaunchKernelGGL((k_dense_finite_check<T, false>), dim3((unsigned)B), dim3(256), 0, st, k, *str);
+            else
+                hipLaunchKernelGGL((k_dense_strided_check<T, false>), dim3((unsigned)B), dim3(256), 0, st, k, *str);
         } else {
             hipLaunchKernelGGL(k_dense_batch_check<T>, dim3((unsigned)B), dim3(256), 0, st, static_cast<const T *>(d_mat),
                                (long long)N, (long long)M, d_shapes, d_p0, d_chk, d_san);
@@ -58,7 +62,10 @@ int dense_batch_status_enqueue(hipStream_t st, const misslap_options &opt, int64
         }
         dense_dtype_dispatch(opt.mat_dtype, [&](auto t) {
             const size_t lds = matching_batch_lds_bytes(N, M, true);
-            if (str)
+            if (finite)
+                hipLaunchKernelGGL((k_matching_batch<MatchSrc::DenseStridedFinite, decltype(t)>), dim3((unsigned)B),
+                                   dim3(kMatchBatchThreads), lds, st, g);
+            else if (str)
                 hipLaunchKernelGGL((k_matching_batch<MatchSrc::DenseStrided, decltype(t)>), dim3((unsigned)B),
                                    dim3(kMatchBatchThreads), lds, st, g);
             else
@@ -67,7 +74,7 @@ int dense_batch_status_enqueue(hipStream_t st, const misslap_options &opt, int64
         });
         HIP_TRY(hipGetLastError());
     }
-    DenseStridedStatusArgs a{};  // (its base is the contiguous kernels' argument)
+    DenseFiniteStatusArgs a{};  // (its bases are the strided and the contiguous kernels' arguments)
     a.d.mat = d_mat;
     a.d.N = N;
     a.d.M = M;
@@ -79,9 +86,13 @@ int dense_batch_status_enqueue(hipStream_t st, const misslap_options &opt, int64
     a.matching_size = d.matching_size;
     return dense_dtype_dispatch(opt.mat_dtype, [&](auto t) {
         using T = decltype(t);
+        if (str) a.str = *str;
+        if (finite)
+            return batch_solve_launch(k_dense_batch_solve_status<T, DenseFiniteStatusArgs>, a, a.d.s, opt, B, N, M, d.sol,
+                                      N, d.prices, M, d_p0, M, d.meta, d.info, st);
         if (str) {
-            a.str = *str;
-            return batch_solve_launch(k_dense_batch_solve_status<T, DenseStridedStatusArgs>, a, a.d.s, opt, B, N, M, d.sol,
+            DenseStridedStatusArgs &s = a;
+            return batch_solve_launch(k_dense_batch_solve_status<T, DenseStridedStatusArgs>, s, s.d.s, opt, B, N, M, d.sol,
                                       N, d.prices, M, d_p0, M, d.meta, d.info, st);
         }
         DenseBatchStatusArgs &c = a;
@@ -102,11 +113,12 @@ int dense_batch_status_call(const char *who, int64_t B, int64_t N, int64_t M, co
     int rc = batch_options(opt_in, &opt, who,
                            "device, maximize, eps_start, max_iter, mat_dtype, input_on_device and input_stream", true);
     if (rc) return rc;
+    const bool finite = dense_take_entries_finite(&opt);
     if (!mat || !sol || !status) return fail(MISSLAP_ERR_INVALID, "null mat / sol / status");
     if ((rc = dense_batch_dims(B, N, M))) return rc;
     DenseStrides str_arg{};
     const DenseStrides *str = nullptr;
-    if ((rc = dense_stack_layout(who, opt, B, N, M, strides, &str_arg, &str))) return rc;
+    if ((rc = dense_stack_layout(who, opt, B, N, M, strides, &str_arg, &str, finite))) return rc;
     const bool guard = cardinality_check != 0;
     const size_t cells = (size_t)B * (size_t)N * (size_t)M, pcells = (size_t)B * (size_t)M;
     k.B = B;
@@ -139,7 +151,7 @@ int dense_batch_status_call(const char *who, int64_t B, int64_t N, int64_t M, co
             return shapes ? upload(tmp, &d_shapes, shapes, (size_t)B * 2, st) : rc;
         },
         [&](hipStream_t st, void *ws, const BatchStreamOut &d) {
-            return dense_batch_status_enqueue(st, opt, B, N, M, d_mat, str, d_shapes, fast, d_p0, guard, ws, d);
+            return dense_batch_status_enqueue(st, opt, B, N, M, d_mat, str, d_shapes, fast, d_p0, guard, ws, d, finite);
         });
 }
 }  // namespace

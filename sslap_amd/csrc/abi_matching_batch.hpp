@@ -6,14 +6,18 @@
 
 namespace {
 // Launch the matcher on a stream (LDS carve Ns x Ms; the > 64 KB opt-in is never needed: 48 KB at the cap).  mat_dtype:
-// the element type of a dense stack; strided: a.sB / sN / sM are its strides (the matcher's strided source).
+// the element type of a dense stack; strided: a.sB / sN / sM are its strides (the matcher's strided source); finite
+// (MISSLAP_DENSE_ENTRIES_FINITE, always strided): that source with "not a NaN" for its edge test.
 template <bool kDense>
 int launch_matching_batch(hipStream_t st, int64_t B, const MatchBatchArgs &a, int32_t mat_dtype, size_t *lds_out,
-                          bool strided = false) {
+                          bool strided = false, bool finite = false) {
     const size_t lds = matching_batch_lds_bytes(a.Ns, a.Ms, kDense);
     if constexpr (kDense)
         dense_dtype_dispatch(mat_dtype, [&](auto t) {
-            if (strided)
+            if (finite)
+                hipLaunchKernelGGL((k_matching_batch<MatchSrc::DenseStridedFinite, decltype(t)>), dim3((unsigned)B),
+                                   dim3(kMatchBatchThreads), lds, st, a);
+            else if (strided)
                 hipLaunchKernelGGL((k_matching_batch<MatchSrc::DenseStrided, decltype(t)>), dim3((unsigned)B),
                                    dim3(kMatchBatchThreads), lds, st, a);
             else
@@ -31,7 +35,7 @@ template <bool kDense>
 int matching_batch_run(hipStream_t st, DevScratch &tmp, int64_t B, MatchBatchArgs a, int32_t *size, int32_t *left,
                        int64_t left_ld, int32_t *right, int64_t right_ld, int32_t out_on_device,
                        misslap_matching_batch_info *info, double t_start, double t_checked,
-                       int32_t mat_dtype = MISSLAP_DTYPE_F64, bool strided = false) {
+                       int32_t mat_dtype = MISSLAP_DTYPE_F64, bool strided = false, bool finite = false) {
     int rc = 0;
     int *d_size = nullptr;
     if ((rc = tmp.alloc(&d_size, (size_t)B))) return rc;
@@ -48,7 +52,7 @@ int matching_batch_run(hipStream_t st, DevScratch &tmp, int64_t B, MatchBatchArg
     if ((rc = ev.create())) return rc;
     size_t lds = 0;
     HIP_TRY(hipEventRecord(ev.e[0], st));
-    if ((rc = launch_matching_batch<kDense>(st, B, a, mat_dtype, &lds, strided))) return rc;
+    if ((rc = launch_matching_batch<kDense>(st, B, a, mat_dtype, &lds, strided, finite))) return rc;
     HIP_TRY(hipEventRecord(ev.e[1], st));
     HIP_TRY(hipMemcpyAsync(size, d_size, sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToHost, st));
     if (!out_on_device) {
@@ -167,6 +171,7 @@ int matching_dense_batch_call(const char *who, int64_t B, int64_t N, int64_t M, 
     int rc = batch_options(opt_in, &opt, who,
                            "device, mat_dtype, input_on_device and input_stream", true);
     if (rc) return rc;
+    const bool finite = dense_take_entries_finite(&opt);
     if ((rc = matching_batch_info_size(info))) return rc;
     if (!mat || !size || !n_rows || !n_cols) return fail(MISSLAP_ERR_INVALID, "null mat / size / n_rows / n_cols");
     if (B < 1 || B > 0x7fffffff) return fail(MISSLAP_ERR_INVALID, "B = %lld: 1 .. 2^31 - 1 graphs", (long long)B);
@@ -176,7 +181,7 @@ int matching_dense_batch_call(const char *who, int64_t B, int64_t N, int64_t M, 
         return fail(MISSLAP_ERR_INVALID, "left_ld / right_ld must be >= 1");
     DenseStrides str_arg{};
     const DenseStrides *str = nullptr;
-    if ((rc = dense_stack_layout(who, opt, B, N, M, strides, &str_arg, &str))) return rc;
+    if ((rc = dense_stack_layout(who, opt, B, N, M, strides, &str_arg, &str, finite))) return rc;
     // each graph is its slice (feasibility_.pyx:250-251)
     int Ns = 1, Ms = 1;
     for (int64_t b = 0; b < B; ++b) {
@@ -219,7 +224,7 @@ int matching_dense_batch_call(const char *who, int64_t B, int64_t N, int64_t M, 
         a.sM = str->sM;
     }
     return matching_batch_run<true>(st, tmp, B, a, size, left_pairings, left_ld, right_pairings, right_ld, out_on_device,
-                                    info, t_start, now_ms(), opt.mat_dtype, str != nullptr);
+                                    info, t_start, now_ms(), opt.mat_dtype, str != nullptr, finite);
 }
 }  // namespace
 

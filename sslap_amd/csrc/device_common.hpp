@@ -190,6 +190,23 @@ __host__ __device__ __forceinline__ bool dense_entry_valid(float v) {
 }
 __host__ __device__ __forceinline__ bool dense_entry_valid(F16 v) { return v.bits <= 0x7c00 || v.bits == 0x8000; }
 __host__ __device__ __forceinline__ bool dense_entry_valid(Bf16 v) { return v.bits <= 0x7f80 || v.bits == 0x8000; }
+// "not a NaN" in the element's own type, the entry rule of a finite-mode stack (MISSLAP_DENSE_ENTRIES_FINITE: signed
+// costs, NaN alone says "no edge"): every finite value of either sign, -0.0 and the subnormals, and both infinities,
+// which the check pass then reports.  A NaN with its sign bit set is a NaN.
+__host__ __device__ __forceinline__ bool dense_entry_not_nan(double v) {
+    return (__builtin_bit_cast(unsigned long long, v) & 0x7fffffffffffffffull) <= 0x7ff0000000000000ull;
+}
+__host__ __device__ __forceinline__ bool dense_entry_not_nan(float v) {
+    return (__builtin_bit_cast(unsigned, v) & 0x7fffffffu) <= 0x7f800000u;
+}
+__host__ __device__ __forceinline__ bool dense_entry_not_nan(F16 v) { return (v.bits & 0x7fff) <= 0x7c00; }
+__host__ __device__ __forceinline__ bool dense_entry_not_nan(Bf16 v) { return (v.bits & 0x7fff) <= 0x7f80; }
+// the entry test of a dense stack under the compile-time rule Fin: "not a NaN", else the reference's "v >= 0"
+template <bool Fin, class T>
+__device__ __forceinline__ bool dense_entry_is(T v) {
+    if constexpr (Fin) return dense_entry_not_nan(v);
+    else return dense_entry_valid(v);
+}
 // The value as a double.  Every step is exact, subnormals included: binary16 -> float -> double, and a bfloat16 is the
 // float with its bits in the upper half (the code object keeps denormals: no flush-to-zero flag in build.FLAGS).
 __device__ __forceinline__ double dense_widen(double v) { return v; }

@@ -548,8 +548,12 @@ int normalise_options(const misslap_options *in, misslap_options *out, int *abi)
         *abi = 2;
     }
     out->struct_size = (int32_t)sizeof(misslap_options);
-    if (out->mat_dtype < MISSLAP_DTYPE_F64 || out->mat_dtype > MISSLAP_DTYPE_BF16)
-        return fail(MISSLAP_ERR_INVALID, "mat_dtype %d: 0 (float64), 1 (float32), 2 (float16) or 3 (bfloat16)", out->mat_dtype);
+    // (MISSLAP_DENSE_ENTRIES_FINITE may ride on the type: 0x100 .. 0x103; who takes the flag is the entry point's check)
+    const int32_t elem = out->mat_dtype & ~(int32_t)MISSLAP_DENSE_ENTRIES_FINITE;
+    if (elem < MISSLAP_DTYPE_F64 || elem > MISSLAP_DTYPE_BF16)
+        return fail(MISSLAP_ERR_INVALID,
+                    "mat_dtype %d: 0 (float64), 1 (float32), 2 (float16) or 3 (bfloat16), alone or OR-ed with "
+                    "MISSLAP_DENSE_ENTRIES_FINITE (0x100)", out->mat_dtype);
     if (out->cand_mode < 0 || out->cand_mode > 2) return fail(MISSLAP_ERR_INVALID, "cand_mode %d: 0, 1 or 2", out->cand_mode);
     if (out->cand_refresh_min < 0 || out->cand_refresh_min > 32)
         return fail(MISSLAP_ERR_INVALID, "cand_refresh_min %d: 0 .. 32", out->cand_refresh_min);

@@ -29,6 +29,12 @@
 // instances take no stride: theirs are compile-time (DenseColStride<false> is empty), and their code is what it was.
 // A strided row source also has a second bid mapping, bid_lanes below, for rounds of many bidders on a stack whose
 // rows run along the unit stride (sN == 1).
+//
+// Finite mode (MISSLAP_DENSE_ENTRIES_FINITE in misslap_options.mat_dtype; the instances on DenseFinite*Args and
+// k_dense_finite_check): signed cost stacks.  An element is an entry iff it is not a NaN in its own type, so negative
+// values, -0.0 and subnormals are entries and NaN alone says "no edge"; an entry of either infinity condemns the
+// problem.  One compile-time flag (Fin) on everything that asks "is this an entry", default off; it is instantiated in
+// the strided family only, and a contiguous stack in this mode runs these kernels with its natural strides.
 #pragma once
 
 namespace misslap {
@@ -41,8 +47,9 @@ struct DenseBatchCheck {
     unsigned long long nvalid;       // valid entries of the slice
     unsigned long long absmax_bits;  // max |v| over them, as bits (non-negative doubles order like their bit patterns)
     int empty_row;                   // first row without a valid entry (INT_MAX: none)
-    int has_inf;                     // bit 0: a valid entry is +inf (outside mode: or the outside value of a row < n);
-                                     // bit 1 (outside mode only): the outside value of a row < n is negative or a NaN
+    int has_inf;                     // bit 0: a valid entry is +inf (outside mode: or the outside value of a row < n;
+                                     // finite mode: or -inf); bit 1 (outside mode only): the outside value of a row < n
+                                     // is no entry (negative or a NaN; finite mode: a NaN)
     int mref;                        // max valid column + 1 (auction_.pyx:209-212)
     int bad_price;                   // starting prices: bit 0 NaN / infinity, bit 1 sign bit set
 };
@@ -88,7 +95,9 @@ __device__ __forceinline__ void dense_batch_shape(const int *shapes, long long N
 // and with starting prices the problem's augmented starting prices [p0[:m_b], zeros(n_b)] are staged at
 // aug[b * (M + N) ..] for batch_solve to load.
 // Str (the strided family): element (b, r, c) lies at mat[b * str.sB + r * str.sN + c * str.sM]; else str is not read.
-template <class T, bool Out, bool Str = false>
+// Fin (finite mode, below): an element is an entry iff it is not a NaN; max |v| and the infinity flag mask the sign, so
+// -inf is caught as +inf is; an outside value is an entry under the same rule (a NaN raises bit 1, either infinity bit 0).
+template <class T, bool Out, bool Str = false, bool Fin = false>
 __device__ __forceinline__ void dense_batch_check(const T *mat, long long N, long long M, const int *shapes,
                                                   const double *p0, DenseBatchCheck *out, int *shapes_out,
                                                   const double *ov, long long ov_ld, double *aug,
@@ -124,7 +133,7 @@ __device__ __forceinline__ void dense_batch_check(const T *mat, long long N, lon
         int rc = 0;
         for (int c = lane; c < m; c += kWave) {
             const T v = row[col.at(c)];
-            if (dense_entry_valid(v)) {
+            if (dense_entry_is<Fin>(v)) {
                 const unsigned long long bits =
                     (unsigned long long)__double_as_longlong(dense_widen(v)) & 0x7fffffffffffffffull;
                 ++rc;
@@ -137,7 +146,7 @@ __device__ __forceinline__ void dense_batch_check(const T *mat, long long N, lon
         if constexpr (Out) {
             if (lane == 0) {
                 const double o = ov[ov_ld ? (size_t)b * (size_t)ov_ld + (size_t)r : (size_t)b];
-                if (dense_entry_valid(o)) {
+                if (dense_entry_is<Fin>(o)) {
                     const unsigned long long bits = (unsigned long long)__double_as_longlong(o) & 0x7fffffffffffffffull;
                     am = bits > am ? bits : am;
                     inf |= bits == 0x7ff0000000000000ull;
@@ -206,6 +215,13 @@ __global__ __launch_bounds__(256) void k_dense_strided_check(DenseOutsideCheckAr
                                     a.outside, a.outside_ld, a.aug, str);
 }
 
+// ... and of a finite-mode call (a kernel of its own name: k_dense_strided_check's instances are what they were)
+template <class T, bool Out>
+__global__ __launch_bounds__(256) void k_dense_finite_check(DenseOutsideCheckArgs a, DenseStrides str) {
+    dense_batch_check<T, Out, true, true>(static_cast<const T *>(a.mat), a.N, a.M, a.shapes, a.p0, a.out, a.shapes_out,
+                                          a.outside, a.outside_ld, a.aug, str);
+}
+
 // The dense row source of batch_solve: problem b's slice A (row stride M) of n x m, its reference M and valid count.
 // The bid's staging array `vals` belongs to k_dense_batch_solve: declared in bid() it is promoted to a vector while bid()
 // is optimised on its own, and every staging step then zeroes the rest of it (measured: 3.8 % more kernel time at
@@ -219,7 +235,10 @@ __global__ __launch_bounds__(256) void k_dense_strided_check(DenseOutsideCheckAr
 // Str (the strided family): M is the row stride sN and col holds the column stride sM; entry (i, c) lies at
 // A[i * M + c * sM].  The wavefront scan keeps its lane map (lane l holds columns l, l + 64, ...) whatever the strides
 // are, with loads of one element each: nothing wider than the element is assumed of the base or of a stride.
-template <class T, bool Out = false, bool Str = false>
+// Fin (finite mode): the entry test of the three bid mappings and of the eCE walk is "not a NaN" (dense_entry_is); a
+// staging slot beyond the row still holds dense_hole, which is an entry under this rule, and is still never tested:
+// every scan asks c < m first.  Resolved at compile time: the <.., false> instances are the code they were.
+template <class T, bool Out = false, bool Str = false, bool Fin = false>
 struct DenseBatchRows {
     const T *A;
     long long M;
@@ -249,7 +268,7 @@ struct DenseBatchRows {
             for (int q = 0; q < kDenseBatchCols; ++q) {
                 if (q * kWave >= m) break;
                 const int c = lane + q * kWave;
-                if (c < m && dense_entry_valid(vals[q])) {
+                if (c < m && dense_entry_is<Fin>(vals[q])) {
                     const double v = dense_widen(vals[q]);
                     const double cost = maximize ? v : v * -1.0;  // :236-237
                     const double vi = cost - price[c];
@@ -276,7 +295,7 @@ struct DenseBatchRows {
 #pragma unroll
                 for (int q = 0; q < kHalf; ++q) {
                     const int c = lane + (h + q) * kWave;
-                    if (c < m && dense_entry_valid(vals[q])) {
+                    if (c < m && dense_entry_is<Fin>(vals[q])) {
                         const double v = dense_widen(vals[q]);
                         const double cost = maximize ? v : v * -1.0;
                         const double vi = cost - price[c];
@@ -328,7 +347,7 @@ struct DenseBatchRows {
 #pragma unroll
                 for (int q = 0; q < kFly; ++q) {
                     const int c = c0 + q;
-                    if (c < m && dense_entry_valid(v8[q])) {
+                    if (c < m && dense_entry_is<Fin>(v8[q])) {
                         const double v = dense_widen(v8[q]);
                         const double cost = maximize ? v : v * -1.0;  // :236-237
                         const double vi = cost - price[c];
@@ -368,7 +387,7 @@ struct DenseBatchRows {
         }
         for (int c = lane_id(); c < m; c += kWave) {
             const T e = row[col.at(c)];
-            if (!dense_entry_valid(e)) continue;
+            if (!dense_entry_is<Fin>(e)) continue;
             const double v = dense_widen(e);
             const double cost = maximize ? v : v * -1.0;
             if (LHS < (cost - price[c]) - eps) bad = true;  // :482
@@ -406,8 +425,8 @@ struct DenseBatchRows {
     __device__ __forceinline__ int64_t meta_nnz() const { return (int64_t)nvalid; }
 };
 
-template <class T, bool Out>
-struct RowsBidLanes<DenseBatchRows<T, Out, true>> {
+template <class T, bool Out, bool Fin>
+struct RowsBidLanes<DenseBatchRows<T, Out, true, Fin>> {
     static constexpr bool value = true;
 };
 
@@ -427,6 +446,7 @@ __global__ __launch_bounds__(1024) void k_dense_batch_solve(DenseBatchArgs a) {
 
 struct DenseBatchStatusArgs {
     static constexpr bool kStrided = false;
+    static constexpr bool kFinite = false;  // the entry rule of the kernel's instance (finite mode: below)
     DenseBatchArgs d;      // d.shapes: the check pass's sanitised shapes (never null)
     const int *card;       // [B] the guard's cardinalities, or null: no guard in this call
     int fast;              // eps_start = 1 / n_b of each problem (auction_.pyx:568-569)
@@ -438,6 +458,12 @@ struct DenseBatchStatusArgs {
 struct DenseStridedStatusArgs : DenseBatchStatusArgs {
     static constexpr bool kStrided = true;
     DenseStrides str;
+};
+
+// ... and of a finite-mode call (MISSLAP_DENSE_ENTRIES_FINITE): the strided family with "not a NaN" for its entry test.
+// A contiguous stack comes here with its natural strides (N * M, M, 1).
+struct DenseFiniteStatusArgs : DenseStridedStatusArgs {
+    static constexpr bool kFinite = true;
 };
 
 // The dense checks of a verdict, in first_error's order (abi_dense_batch.hpp); batch_verdict adds the shared rest.
@@ -470,13 +496,14 @@ __global__ __launch_bounds__(1024) void k_dense_batch_solve_status(Args a) {
     if constexpr (Args::kStrided) {
         // a unit column stride is the contiguous row source with sN for its row stride (the same bid, instruction for
         // instruction); any other takes the strided one.  The branch is uniform.
+        constexpr bool kFin = Args::kFinite;
         const T *A = static_cast<const T *>(a.d.mat) + (size_t)b * (size_t)a.str.sB;
         if (a.str.sM == 1) {
-            const DenseBatchRows<T> rows{A, a.str.sN, m, s.maximize, ck.mref, ck.nvalid, vals};
+            const DenseBatchRows<T, false, false, kFin> rows{A, a.str.sN, m, s.maximize, ck.mref, ck.nvalid, vals};
             batch_solve(s, rows, n, m, ck.absmax_bits);
         } else {
-            const DenseBatchRows<T, false, true> rows{A, a.str.sN, m, s.maximize, ck.mref, ck.nvalid, vals, {},
-                                                      {a.str.sM, a.str.lane_min_K}};
+            const DenseBatchRows<T, false, true, kFin> rows{A, a.str.sN, m, s.maximize, ck.mref, ck.nvalid, vals, {},
+                                                            {a.str.sM, a.str.lane_min_K}};
             batch_solve(s, rows, n, m, ck.absmax_bits);
         }
     } else {
@@ -491,6 +518,7 @@ __global__ __launch_bounds__(1024) void k_dense_batch_solve_status(Args a) {
 
 struct DenseOutsideArgs {
     static constexpr bool kStrided = false;
+    static constexpr bool kFinite = false;
     DenseBatchStatusArgs t;  // t.d.s: Ms = M + N (the carve), p0 / p0_ld the staged augmented prices, prices null;
                              // t.card null: no guard in this call
     const double *outside;   // [B] (outside_ld == 0) or [B][outside_ld]
@@ -502,6 +530,10 @@ struct DenseOutsideArgs {
 struct DenseStridedOutsideArgs : DenseOutsideArgs {
     static constexpr bool kStrided = true;
     DenseStrides str;
+};
+
+struct DenseFiniteOutsideArgs : DenseStridedOutsideArgs {  // (finite mode, as DenseFiniteStatusArgs)
+    static constexpr bool kFinite = true;
 };
 
 // The checks of an outside verdict in their order; EMPTY_ROW, TOO_FEW_VALUES and INFEASIBLE cannot occur.
@@ -536,14 +568,16 @@ __global__ __launch_bounds__(1024) void k_dense_outside_solve(Args a) {
     T vals[kDenseBatchCols];
     const double *O = a.outside + (a.outside_ld ? (size_t)b * (size_t)a.outside_ld : (size_t)b);
     if constexpr (Args::kStrided) {  // (as in k_dense_batch_solve_status)
+        constexpr bool kFin = Args::kFinite;
         const T *A = static_cast<const T *>(d.mat) + (size_t)b * (size_t)a.str.sB;
         const unsigned long long nv = ck.nvalid + (unsigned long long)n;
         if (a.str.sM == 1) {
-            const DenseBatchRows<T, true> rows{A, a.str.sN, m, s.maximize, m + n, nv, vals, {O, a.outside_ld ? 1 : 0}};
+            const DenseBatchRows<T, true, false, kFin> rows{A, a.str.sN, m, s.maximize, m + n, nv, vals,
+                                                            {O, a.outside_ld ? 1 : 0}};
             batch_solve(s, rows, n, m + n, ck.absmax_bits);
         } else {
-            const DenseBatchRows<T, true, true> rows{A, a.str.sN, m, s.maximize, m + n, nv, vals, {O, a.outside_ld ? 1 : 0},
-                                                     {a.str.sM, a.str.lane_min_K}};
+            const DenseBatchRows<T, true, true, kFin> rows{A, a.str.sN, m, s.maximize, m + n, nv, vals,
+                                                           {O, a.outside_ld ? 1 : 0}, {a.str.sM, a.str.lane_min_K}};
             batch_solve(s, rows, n, m + n, ck.absmax_bits);
         }
     } else {

@@ -21,7 +21,8 @@
 // with implicit row bounds u * K .. (u + 1) * K and a unit-stride column read of index type E (int, long long), a
 // negative column being a hole that no step visits, or (d) a strided dense stack: source (b) with entry (b, i, j) at
 // mat[b * sB + i * sN + j * sM] for run-time strides >= 0 (the guard of the strided dense solves and
-// misslap_matching_dense_batch_strided), or (e) a view of a packed loc (the guard of the sparse view solves,
+// misslap_matching_dense_batch_strided; with MISSLAP_DENSE_ENTRIES_FINITE an entry iff the element is not a NaN, the
+// rule of a finite-mode solve and of its guard), or (e) a view of a packed loc (the guard of the sparse view solves,
 // SparseView of kernels_sparse_batch.hpp): source (a) with entry g of the packed arrays at row mat[g * sN], column
 // mat[g * sN + sM], of index type E (int, long long; an int64 index saturates into the int32 range as it is read), for
 // graphs the view's check pass found clean.  No value is ever widened here: only the pattern is read.
@@ -33,7 +34,8 @@ constexpr int kMatchBatchMaxDim = MISSLAP_MATCHING_BATCH_MAX_DIM;
 constexpr int kMatchBatchThreads = 256;
 constexpr int kMatchInf = INT_MAX;  // the reference's inf of Dist
 constexpr int kMatchBatchMaxEntries = INT_MAX - 2 * kWave;  // entries of one graph
-enum class MatchSrc { Loc, Dense, Ell, DenseStrided, LocView };  // where k_matching_batch reads its adjacency from
+// where k_matching_batch reads its adjacency from (DenseStridedFinite: source (d) with the finite-mode entry rule)
+enum class MatchSrc { Loc, Dense, Ell, DenseStrided, LocView, DenseStridedFinite };
 
 // per graph of a packed loc, from k_matching_batch_check
 struct MatchBatchCheck {
@@ -127,7 +129,8 @@ __device__ __forceinline__ void match_bfs_visit(int v, int L, const int *pair_v,
 
 template <MatchSrc kSrc, class E = double>
 __global__ __launch_bounds__(kMatchBatchThreads) void k_matching_batch(MatchBatchArgs a) {
-    constexpr bool kStrided = kSrc == MatchSrc::DenseStrided, kDense = kSrc == MatchSrc::Dense || kStrided;
+    constexpr bool kFinite = kSrc == MatchSrc::DenseStridedFinite;  // an edge iff the element is not a NaN
+    constexpr bool kStrided = kSrc == MatchSrc::DenseStrided || kFinite, kDense = kSrc == MatchSrc::Dense || kStrided;
     constexpr bool kEll = kSrc == MatchSrc::Ell, kView = kSrc == MatchSrc::LocView;
     constexpr bool kLoc = kSrc == MatchSrc::Loc || kView;  // row starts in LDS, from a packed loc
     const int b = blockIdx.x, tid = threadIdx.x, T = blockDim.x, lane = lane_id(), wave = tid >> 6, nw = T >> 6;
@@ -257,7 +260,7 @@ __global__ __launch_bounds__(kMatchBatchThreads) void k_matching_batch(MatchBatc
                 for (int x = qs + wave; x < qe; x += nw) {
                     const int u = queue[x];
                     for (int c = lane; c < m; c += kWave)
-                        if (dense_entry_valid(dense_at(u, c))) match_bfs_visit(c, L, pair_v, dist, queue, &s_tail, found);
+                        if (dense_entry_is<kFinite>(dense_at(u, c))) match_bfs_visit(c, L, pair_v, dist, queue, &s_tail, found);
                 }
             } else if (lane_rows) {
                 for (int x = qs + tid; x < qe; x += T) {
@@ -307,7 +310,7 @@ __global__ __launch_bounds__(kMatchBatchThreads) void k_matching_batch(MatchBatc
                             const int pos = g + lane;
                             int cv = -1;
                             if (pos < g1) {
-                                if constexpr (kDense) cv = dense_entry_valid(dense_at(u, pos)) ? pos : -1;
+                                if constexpr (kDense) cv = dense_entry_is<kFinite>(dense_at(u, pos)) ? pos : -1;
                                 else cv = col_of(pos);
                             }
                             int cp = -1;

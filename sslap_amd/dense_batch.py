@@ -15,7 +15,7 @@ import numpy as np
 
 from . import _lib
 from ._batch import (_STATUS_ERRORS, _StatusCall, _check_device_shapes, _check_outside, _check_shapes, _check_stack,
-                     _decode_meta, _empty, _eps, _host, _is_device_tensor, _new_meta, _ptr, _send, _solve_options,
+                     _decode_meta, _empty, _entries_flag, _eps, _host, _is_device_tensor, _new_meta, _ptr, _send, _solve_options,
                      _stack_strides, _starting_prices, batch_meta_to_host, raise_for_status)  # (the last two: also for import from here)
 
 MAX_DIM = _lib.DENSE_BATCH_MAX_DIM
@@ -61,8 +61,35 @@ def dense_to_augmented(mats, shapes=None, outside=0.):
     return out
 
 
+def dense_to_packed(mats, shapes=None, entries="nonneg"):
+    """(B, N, M) stack -> [(loc_b int32 (k, 2), val_b float64 (k,))]: the entries of mats[b, :n_b, :m_b] in row-major
+    order, widened to float64 -- the definition of auction_solve_batch(entries=).  entries="nonneg": v >= 0 is an entry
+    (-0.0 and +inf included; a negative value or a NaN is not), what from_matrix keeps.  entries="finite": every element
+    that is not a NaN is one, so negative values, -0.0, subnormals and both infinities are.  With entries="finite"
+    problem b of the batch is auction_solve(loc=loc_b, val=val_b, ..., cardinality_check=False) on that pair (with fast,
+    eps = 1 / n_b as ever), and hopcroft_solve_batch(mats=, entries="finite") is hopcroft_solve(loc=loc_b).  mats: a numpy
+    array of any float type or a tensor; shapes: optional integer (B, 2)."""
+    _entries_flag(entries)
+    if hasattr(mats, "cpu"):
+        mats = mats.double().cpu().numpy()
+    mats = np.asarray(mats)
+    if mats.ndim != 3:
+        raise ValueError(f"mats must have 3 dimensions (B, N, M), got {mats.ndim}")
+    B, N, M = mats.shape
+    shp = np.tile([N, M], (B, 1)) if shapes is None else np.asarray(shapes.cpu() if hasattr(shapes, "cpu") else shapes)
+    out = []
+    for b in range(B):
+        n, m = (max(int(x), 0) for x in shp[b])
+        v = mats[b, :n, :m].astype(np.float64)
+        with np.errstate(invalid="ignore"):
+            keep = ~np.isnan(v) if entries == "finite" else v >= 0
+        ii, jj = np.nonzero(keep)  # (row-major)
+        out.append((np.ascontiguousarray(np.stack([ii, jj], axis=1).astype(np.int32)), np.ascontiguousarray(v[ii, jj])))
+    return out
+
+
 def auction_solve_batch(mats, problem="min", eps_start=0., max_iter=1000000, fast=None, cardinality_check=True,
-                        shapes=None, prices=None, errors="raise", mat_dtype="float64", outside=None):
+                        shapes=None, prices=None, errors="raise", mat_dtype="float64", outside=None, entries="nonneg"):
     """Solve B independent dense problems in one call, one workgroup per problem.
 
     mats: float64 (or mat_dtype, below) (B, N, M), a numpy array or a tensor on the device (read in place, whatever its
@@ -126,6 +153,20 @@ def auction_solve_batch(mats, problem="min", eps_start=0., max_iter=1000000, fas
     without a complete matching and n_b > m_b are solved; the guard is not launched whatever cardinality_check says and
     matching_size is -1.  The values of rows >= n_b are never read.
 
+    entries: "nonneg" (default) is the rule above, v >= 0, and the call takes exactly the path it always took.
+    entries="finite" is for signed costs (a matcher's -prob + L1 - GIoU, a tracker's log-likelihood ratio), read in
+    place without a shift by the minimum: an element is an entry iff it is not a NaN in its own type, so negative values,
+    -0.0 and subnormals are entries and NaN is the one way to say "no edge" (cost.masked_fill(~gate, float("nan"))).
+    An entry of +inf or -inf gives MISSLAP_BATCH_STATUS_INFINITE_VALUE.  Everything else is unchanged: n_cols is the
+    largest column with an entry plus 1, C = max |v|, the checks and their order, shapes, prices, fast, eps_start,
+    max_iter, problem, mat_dtype, strides, outside.  A problem with status 0 is bit for bit
+    auction_solve(loc=loc_b, val=val_b, ..., cardinality_check=False) on dense_to_packed(mats, shapes, "finite")[b] (fast:
+    eps = 1 / n_b).  With outside, an outside value may be any finite float64 (a NaN gives BAD_OUTSIDE, an infinity
+    INFINITE_VALUE) and problem b is sparse_to_augmented of the packed problem: one entry (i, m_b + i) more per row,
+    stored last in its row.  errors="raise" runs the status call and then raise_for_status, as for a strided stack, and
+    returns the status-mode dict.  A contiguous stack in this mode is read by the kernels of the strided family with its
+    natural strides (misslap_options.mat_dtype | MISSLAP_DENSE_ENTRIES_FINITE).
+
     fast=None (default) is False without outside (the call is what it always was) and with outside True, unless
     eps_start > 0 was given (then False); an explicit fast= or eps_start= is passed through as it is.  Why: the augmented
     problem is rectangular (n rows, m + n columns).  A single phase (fast=True, or 0 < eps_start <= 1 / n) from zero prices
@@ -135,7 +176,9 @@ def auction_solve_batch(mats, problem="min", eps_start=0., max_iter=1000000, fas
     """
     if errors not in ("raise", "status"):
         raise ValueError(f"errors must be 'raise' or 'status', got {errors!r}")
+    flag = _entries_flag(entries)
     B, N, M, on_device, dtype = _check_stack(mats, mat_dtype)
+    dtype |= flag  # (the option word carries the rule: the element type OR-ed with MISSLAP_DENSE_ENTRIES_FINITE)
     strides = _stack_strides(mats, on_device)
     if N > MAX_DIM or M > MAX_DIM:
         raise ValueError(f"problems of {N} x {M}: auction_solve_batch takes at most {MAX_DIM} x {MAX_DIM} "
@@ -146,7 +189,8 @@ def auction_solve_batch(mats, problem="min", eps_start=0., max_iter=1000000, fas
         return raise_for_status(res) if errors == "raise" else res
     if fast is None:  # (resolved here: the library gets a plain flag)
         fast = False
-    if errors == "status" or strides is not None:  # (the default mode's own call reads a contiguous stack only)
+    # (the default mode's own call reads a contiguous stack under the "nonneg" rule only)
+    if errors == "status" or strides is not None or flag:
         res = _solve_status(mats, B, N, M, on_device, problem, eps_start, max_iter, fast, cardinality_check, shapes,
                             prices, dtype, strides)
         return res if errors == "status" else raise_for_status(res)
@@ -214,7 +258,8 @@ def _solve_outside(mats, B, N, M, on_device, problem, eps_start, max_iter, fast,
     shp = _shapes(shapes, B, N, M, dev)
     e = _eps(eps_start)
     p = _prices(prices, B, M, mats, dev)
-    out_v, out_ld = _check_outside(outside, B, N, dev, "mats", "mats", True)
+    finite = bool(dtype & _lib.DENSE_ENTRIES_FINITE)  # (then an outside value may have either sign)
+    out_v, out_ld = _check_outside(outside, B, N, dev, "mats", "mats", not finite)
     if fast is None:
         fast = not e > 0
     opts = _solve_options(on_device, mats, problem, e, max_iter, dtype)
@@ -228,7 +273,8 @@ def _solve_outside(mats, B, N, M, on_device, problem, eps_start, max_iter, fast,
         _lib.check(lib.misslap_solve_dense_batch_outside(B, N, M, *rest))
     else:
         _lib.check(lib.misslap_solve_dense_batch_outside_strided(B, N, M, *strides, *rest))
-    return call.result((mats, shp, p, d_out), shapes=shp, stack=(N, M), outside=d_out)
+    own = dict(entries="finite") if finite else {}  # (raise_for_status words a bad outside value by the rule)
+    return call.result((mats, shp, p, d_out), shapes=shp, stack=(N, M), outside=d_out, **own)
 
 
 def _status_error(res, b, code, n, m, card):
@@ -242,8 +288,13 @@ def _status_error(res, b, code, n, m, card):
     if code == _lib.BATCH_STATUS_BAD_OUTSIDE:  # the first row < n_b whose outside value is no entry
         o = _host(res["outside"])[b]
         o = np.broadcast_to(o, (n,)) if o.ndim == 0 else o[:n]
-        row = int(np.flatnonzero(~(o >= 0))[0])
+        finite = res.get("entries") == "finite"
+        with np.errstate(invalid="ignore"):
+            row = int(np.flatnonzero(np.isnan(o) if finite else ~(o >= 0))[0])
         value = float(o[row])
+        if finite:  # (the one outside value this rule refuses)
+            return ValueError(f"problem {b}: the outside value of row {row} is {value!r}: it must not be a NaN (a NaN "
+                              "would be an absent entry)")
     text = _STATUS_TEXT[code].format(n=n, m=m, N=N, M=M, card=card, row=row, value=value)
     if code == _lib.BATCH_STATUS_INFINITE_VALUE and "outside_prices" in res:
         text += " (in an entry or in the outside value of a row)"

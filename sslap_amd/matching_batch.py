@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._batch import (_check_offsets, _check_shapes, _check_stack, _empty, _is_device_tensor, _mat_dtype_name, _maxima,
+from ._batch import (_check_offsets, _check_shapes, _check_stack, _empty, _entries_flag, _is_device_tensor, _mat_dtype_name, _maxima,
                      _options, _ptr, _stack_strides)
 
 MAX_DIM = _lib.MATCHING_BATCH_MAX_DIM
@@ -73,7 +73,7 @@ def _check_mats(mats, shapes, mat_dtype):
     return B, N, M, s, on_device, dtype
 
 
-def hopcroft_solve_batch(loc=None, offsets=None, mats=None, shapes=None, mat_dtype="float64"):
+def hopcroft_solve_batch(loc=None, offsets=None, mats=None, shapes=None, mat_dtype="float64", entries="nonneg"):
     """Maximum matching of B small bipartite graphs in one call, one workgroup per graph.
 
     Exactly ONE of
@@ -87,6 +87,9 @@ def hopcroft_solve_batch(loc=None, offsets=None, mats=None, shapes=None, mat_dty
           (n_b, m_b) = shapes[b] (optional integer (B, 2); default N x M), edge (i, j) iff the entry is >= 0.
           mat_dtype ("float64", "float32", "float16", "bfloat16", or that numpy / torch dtype) names the stack's element
           type, which it must have exactly; the stack is read in place and the pairings are those of the widened stack.
+          entries="finite" (default "nonneg", the rule above): edge (i, j) iff the entry is not a NaN, the rule of
+          auction_solve_batch(entries="finite"); the pairings are those of hopcroft_solve(loc=loc_b) on the graph
+          dense_to_packed(mats, shapes, "finite") gives.
     A graph has at most MISSLAP_MATCHING_BATCH_MAX_DIM rows and columns.
 
     Returns dict(size=int32 (B,), left_pairings=int32 (B, Nmax), right_pairings=int32 (B, Mmax), n_rows, n_cols);
@@ -96,6 +99,7 @@ def hopcroft_solve_batch(loc=None, offsets=None, mats=None, shapes=None, mat_dty
     """
     if (loc is None) == (mats is None):
         raise ValueError("exactly one of loc and mats must be given")
+    flag = _entries_flag(entries)
     if mats is not None:
         if offsets is not None:
             raise TypeError("offsets goes with loc, not with mats")
@@ -108,6 +112,8 @@ def hopcroft_solve_batch(loc=None, offsets=None, mats=None, shapes=None, mat_dty
             raise TypeError("shapes goes with mats, not with loc")
         if _mat_dtype_name(mat_dtype) != "float64":
             raise TypeError("mat_dtype goes with mats, not with loc")
+        if flag:
+            raise TypeError("entries goes with mats, not with loc")
         if isinstance(loc, (list, tuple)):
             if offsets is not None:
                 raise TypeError("a list of per-graph loc arrays takes no offsets")
@@ -117,7 +123,7 @@ def hopcroft_solve_batch(loc=None, offsets=None, mats=None, shapes=None, mat_dty
         Nmax = min(max(max_row + 1, 1), MAX_DIM)  # (a graph beyond the cap is rejected by the library, in its order)
         Mmax = min(max(max_col + 1, 1), MAX_DIM)
         src = loc
-    opts = _options(on_device, src) if mats is None else _options(on_device, src, mat_dtype=dtype)
+    opts = _options(on_device, src) if mats is None else _options(on_device, src, mat_dtype=dtype | flag)
     size = np.empty(B, dtype=np.int32)
     n_rows = np.empty(B, dtype=np.int32)
     n_cols = np.empty(B, dtype=np.int32)
