@@ -1,6 +1,6 @@
 // abi_batch_stream.hpp -- the one call path of the six "verdict per problem, stream-ordered" batch entry points:
 // misslap_solve_dense_batch_status (abi_dense_batch_status.hpp), misslap_solve_dense_batch_outside
-// (abi_dense_batch_outside.hpp), misslap_solve_sparse_batch_status (abi_sparse_batch_status.hpp),
+// (abi_dense_batch_status.hpp), misslap_solve_sparse_batch_status (abi_sparse_batch_status.hpp),
 // misslap_solve_sparse_batch_outside (abi_sparse_batch_status.hpp), misslap_solve_ell_batch (abi_ell_batch.hpp) and
 // misslap_solve_ell_batch_outside (abi_ell_batch_outside.hpp).  An entry point checks its own
 // arguments, describes the call in a BatchStreamCall and supplies three steps; batch_stream_call runs them in either of

@@ -103,10 +103,10 @@ inline DenseStrides dense_strides_arg(int64_t sB, int64_t sN, int64_t sM) {
 }
 
 // The layout of a call's stack: strides null (the contiguous entry points) or {sB, sN, sM} of a strided one (`who`).
-// *str becomes null for the contiguous kernels, else `store`, filled.  A strided stack lies on the device (a host
+// *str becomes null for DenseContig, else `store`, filled: a view.  A strided stack lies on the device (a host
 // stack is uploaded whole, and is compact); all of this is checked before any device is touched.
-// finite: the call's kernels are the finite-mode instances, which exist in the strided family only, so *str is never
-// null: a contiguous stack (of either kind of entry point) gets its natural strides (N * M, M, 1).
+// finite: the call's kernels are those of DenseView<true>, so *str is never null: a contiguous stack (of either kind
+// of entry point) gets its natural strides (N * M, M, 1).
 int dense_stack_layout(const char *who, const misslap_options &opt, int64_t B, int64_t N, int64_t M,
                        const int64_t *strides, DenseStrides *store, const DenseStrides **str, bool finite = false) {
     *str = nullptr;
@@ -125,6 +125,33 @@ int dense_stack_layout(const char *who, const misslap_options &opt, int64_t B, i
     *store = dense_strides_arg(strides[0], strides[1], strides[2]);
     *str = store;
     return MISSLAP_OK;
+}
+
+// body(T{}, lay) with T the element type mat_dtype names and lay the layout dense_stack_layout chose: DenseContig
+// (str null), DenseView<false>{*str} or, finite, DenseView<true>{*str}.  Every launch of a dense kernel on a call's
+// stack comes through here, and nothing else knows how many layouts there are.
+template <class F>
+auto dense_dispatch(int32_t mat_dtype, const DenseStrides *str, bool finite, F &&body) {
+    return dense_dtype_dispatch(mat_dtype, [&](auto t) {
+        if (finite) return body(t, DenseView<true>{*str});
+        if (str) return body(t, DenseView<false>{*str});
+        return body(t, DenseContig{});
+    });
+}
+
+// The matcher on a dense stack of element type T and layout lay (g: everything but the strides; lds: its carve):
+// the one place that maps a layout to the matcher's source.
+template <class T, class Lay>
+void dense_guard_launch(hipStream_t st, int64_t B, MatchBatchArgs g, const Lay &lay, size_t lds) {
+    constexpr MatchSrc kSrc = !Lay::kView    ? MatchSrc::Dense
+                              : Lay::kFinite ? MatchSrc::DenseStridedFinite
+                                             : MatchSrc::DenseStrided;
+    if constexpr (Lay::kView) {
+        g.sB = lay.str.sB;
+        g.sN = lay.str.sN;
+        g.sM = lay.str.sM;
+    }
+    hipLaunchKernelGGL((k_matching_batch<kSrc, T>), dim3((unsigned)B), dim3(kMatchBatchThreads), lds, st, g);
 }
 
 // a host shapes array (or null): every problem within the stack
@@ -175,10 +202,15 @@ MISSLAP_API int misslap_solve_dense_batch(int64_t B, int64_t N, int64_t M, const
         return rc;
 
     // ---- validation: every problem before any is solved
+    DenseCheckArgs<DenseContig> k{};  // (shapes_out null: the shapes are checked above)
+    k.mat = d_mat;
+    k.N = N;
+    k.M = M;
+    k.shapes = d_shapes;
+    k.p0 = d_p0;
+    k.out = d_chk;
     dense_dtype_dispatch(opt.mat_dtype, [&](auto t) {
-        using T = decltype(t);
-        hipLaunchKernelGGL(k_dense_batch_check<T>, dim3((unsigned)B), dim3(256), 0, st, static_cast<const T *>(d_mat),
-                           (long long)N, (long long)M, d_shapes, d_p0, d_chk, (int *)nullptr);
+        hipLaunchKernelGGL((k_dense_batch_check<decltype(t), DenseContig, false>), dim3((unsigned)B), dim3(256), 0, st, k);
     });
     HIP_TRY(hipGetLastError());
     // the matching guard of every problem on the device, behind the validation pass and read back with it
@@ -199,8 +231,7 @@ MISSLAP_API int misslap_solve_dense_batch(int64_t B, int64_t N, int64_t M, const
         if ((rc = gev.create())) return rc;
         HIP_TRY(hipEventRecord(gev.e[0], st));
         dense_dtype_dispatch(opt.mat_dtype, [&](auto t) {
-            hipLaunchKernelGGL((k_matching_batch<MatchSrc::Dense, decltype(t)>), dim3((unsigned)B), dim3(kMatchBatchThreads),
-                               matching_batch_lds_bytes(N, M, true), st, g);
+            dense_guard_launch<decltype(t)>(st, B, g, DenseContig{}, matching_batch_lds_bytes(N, M, true));
         });
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(gev.e[1], st));

@@ -5,37 +5,13 @@
 #pragma once
 
 namespace {
-// Launch the matcher on a stream (LDS carve Ns x Ms; the > 64 KB opt-in is never needed: 48 KB at the cap).  mat_dtype:
-// the element type of a dense stack; strided: a.sB / sN / sM are its strides (the matcher's strided source); finite
-// (MISSLAP_DENSE_ENTRIES_FINITE, always strided): that source with "not a NaN" for its edge test.
-template <bool kDense>
-int launch_matching_batch(hipStream_t st, int64_t B, const MatchBatchArgs &a, int32_t mat_dtype, size_t *lds_out,
-                          bool strided = false, bool finite = false) {
-    const size_t lds = matching_batch_lds_bytes(a.Ns, a.Ms, kDense);
-    if constexpr (kDense)
-        dense_dtype_dispatch(mat_dtype, [&](auto t) {
-            if (finite)
-                hipLaunchKernelGGL((k_matching_batch<MatchSrc::DenseStridedFinite, decltype(t)>), dim3((unsigned)B),
-                                   dim3(kMatchBatchThreads), lds, st, a);
-            else if (strided)
-                hipLaunchKernelGGL((k_matching_batch<MatchSrc::DenseStrided, decltype(t)>), dim3((unsigned)B),
-                                   dim3(kMatchBatchThreads), lds, st, a);
-            else
-                hipLaunchKernelGGL((k_matching_batch<MatchSrc::Dense, decltype(t)>), dim3((unsigned)B), dim3(kMatchBatchThreads), lds, st, a);
-        });
-    else
-        hipLaunchKernelGGL(k_matching_batch<MatchSrc::Loc>, dim3((unsigned)B), dim3(kMatchBatchThreads), lds, st, a);
-    HIP_TRY(hipGetLastError());
-    if (lds_out) *lds_out = lds;
-    return MISSLAP_OK;
-}
-
 // The part both entry points share once every graph is accepted: the launch, the outputs, the info.
-template <bool kDense>
+// launch(a, lds) starts the matcher of the caller's source on st with an LDS carve of lds bytes (Ns x Ms; the > 64 KB
+// opt-in is never needed: 48 KB at the cap).
+template <bool kDense, class Launch>
 int matching_batch_run(hipStream_t st, DevScratch &tmp, int64_t B, MatchBatchArgs a, int32_t *size, int32_t *left,
                        int64_t left_ld, int32_t *right, int64_t right_ld, int32_t out_on_device,
-                       misslap_matching_batch_info *info, double t_start, double t_checked,
-                       int32_t mat_dtype = MISSLAP_DTYPE_F64, bool strided = false, bool finite = false) {
+                       misslap_matching_batch_info *info, double t_start, double t_checked, const Launch &launch) {
     int rc = 0;
     int *d_size = nullptr;
     if ((rc = tmp.alloc(&d_size, (size_t)B))) return rc;
@@ -50,9 +26,10 @@ int matching_batch_run(hipStream_t st, DevScratch &tmp, int64_t B, MatchBatchArg
     }
     EventPair ev;
     if ((rc = ev.create())) return rc;
-    size_t lds = 0;
+    const size_t lds = matching_batch_lds_bytes(a.Ns, a.Ms, kDense);
     HIP_TRY(hipEventRecord(ev.e[0], st));
-    if ((rc = launch_matching_batch<kDense>(st, B, a, mat_dtype, &lds, strided, finite))) return rc;
+    launch(a, lds);
+    HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(ev.e[1], st));
     HIP_TRY(hipMemcpyAsync(size, d_size, sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToHost, st));
     if (!out_on_device) {
@@ -157,7 +134,10 @@ MISSLAP_API int misslap_matching_batch(int64_t B, const int32_t *loc, const int6
     a.Ns = Ns;
     a.Ms = Ms;
     return matching_batch_run<false>(st, tmp, B, a, size, left_pairings, left_ld, right_pairings, right_ld, out_on_device,
-                                     info, t_start, t_checked);
+                                     info, t_start, t_checked, [&](const MatchBatchArgs &g, size_t lds) {
+                                         hipLaunchKernelGGL(k_matching_batch<MatchSrc::Loc>, dim3((unsigned)B),
+                                                            dim3(kMatchBatchThreads), lds, st, g);
+                                     });
 }
 
 namespace {
@@ -218,13 +198,12 @@ int matching_dense_batch_call(const char *who, int64_t B, int64_t N, int64_t M, 
     a.shapes = d_shapes;
     a.Ns = Ns;
     a.Ms = Ms;
-    if (str) {
-        a.sB = str->sB;
-        a.sN = str->sN;
-        a.sM = str->sM;
-    }
     return matching_batch_run<true>(st, tmp, B, a, size, left_pairings, left_ld, right_pairings, right_ld, out_on_device,
-                                    info, t_start, now_ms(), opt.mat_dtype, str != nullptr, finite);
+                                    info, t_start, now_ms(), [&](const MatchBatchArgs &g, size_t lds) {
+                                        dense_dispatch(opt.mat_dtype, str, finite, [&](auto t, auto lay) {
+                                            dense_guard_launch<decltype(t)>(st, B, g, lay, lds);
+                                        });
+                                    });
 }
 }  // namespace
 

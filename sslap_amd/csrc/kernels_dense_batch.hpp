@@ -1,40 +1,42 @@
 // kernels_dense_batch.hpp -- many small dense problems, one workgroup per problem for its whole solve
-// (misslap_solve_dense_batch, include/misslap.h; the host side is abi_dense_batch.hpp).
+// (misslap_solve_dense_batch and the stream-ordered calls with a verdict per problem, include/misslap.h; the host side
+// is abi_dense_batch.hpp and abi_dense_batch_status.hpp).
 //
-// The round loop is batch_solve (kernels_batch_solve.hpp); this file has the check pass and the dense row source.
-// Values are read from the caller's dense rows (row stride = the stack's M) in global memory, where a small problem
-// stays in L2.  The rows have the caller's element type T (double, float, F16, Bf16: misslap_options.mat_dtype); the
-// three kernels that read them are templates on T, every value is widened to double where it is used (dense_widen,
-// exact), and batch_solve only ever sees doubles:
+// The round loop is batch_solve (kernels_batch_solve.hpp); this file has the check pass, the dense row source and the
+// solve kernels, each once: k_dense_batch_check<T, Lay, Out>, DenseBatchRows<T, Lay, Out>, k_dense_batch_solve<T>,
+// k_dense_batch_solve_status<T, Lay> and k_dense_outside_solve<T, Lay>.  Values are read from the caller's stack in
+// global memory, where a small problem stays in L2:
 //   BID      lanes scan the row in column order (lane l holds columns l, l + 64, ...), staged in registers with up to
 //            kDenseBatchCols loads in flight; the object is the winning column r.g.
 //   eCE      every column is stored once, so choice_cost -- never reset per row in the reference -- is the cost of the
 //            row's own column.
 //   get_obj  the selected values are gathered into LDS, then one lane adds them in row order.
 //
-// The outside mode (misslap_solve_dense_batch_outside; the <T, true> instances below): row i of problem b also holds one
-// virtual entry (i, m_b + i) whose value is the row's outside value -- a private object that only row i can bid for, so
-// a row may stay unmatched.  The problem solved is the dense n_b x (m_b + n_b) matrix hstack([slice, D_b]) with D_b the
-// outside values on its diagonal and -1 elsewhere; the round loop is batch_solve unchanged, on a carve of M + N objects.
-// The row source presents the virtual entry (column m_b + i, above every real column), the check pass folds the outside
-// values into C = max |v| and the +inf flag, flags a negative or NaN one and never reports an empty row, and the solve
-// kernel rewrites the outputs behind batch_solve: an object >= m_b becomes -1 in sol, price[0 .. m_b) are the real
-// prices and price[m_b .. m_b + n_b) the outside prices.
+// Element type T (double, float, F16, Bf16: misslap_options.mat_dtype).  The rows are read in the caller's type, every
+// value is widened to double where it is used (dense_widen, exact), and batch_solve only ever sees doubles.
 //
-// The strided family (misslap_solve_dense_batch_status_strided / _outside_strided; the instances on DenseStrided*Args
-// and k_dense_strided_check): the same check pass, row source and solve kernels on a stack whose element (b, i, j) lies
+// Layout Lay: where element (b, i, j) lies.  DenseContig is the compact stack: problem stride N * M, row stride M and
+// column step 1, all known at compile time, so it holds nothing.  DenseView<Fin> holds DenseStrides: the element lies
 // at mat[b * sB + i * sN + j * sM] for run-time strides >= 0 -- a transposed view, a slice of a wider buffer, an
-// expanded matrix (sB = 0).  Every entry plays the role it plays in the contiguous stack, so the results are those of
-// the compact copy bit for bit; offsets are formed in 64 bits and only elements of the view are read.  The contiguous
-// instances take no stride: theirs are compile-time (DenseColStride<false> is empty), and their code is what it was.
-// A strided row source also has a second bid mapping, bid_lanes below, for rounds of many bidders on a stack whose
-// rows run along the unit stride (sN == 1).
+// expanded matrix (sB = 0).  Every entry plays the role it plays in the compact copy, so the results are those of the
+// copy bit for bit; offsets are formed in 64 bits, loads are one element each, and only elements of the view are read.
+// A view whose rows run along the unit stride (sN == 1) also has a second bid mapping, bid_lanes below, for rounds of
+// many bidders.
 //
-// Finite mode (MISSLAP_DENSE_ENTRIES_FINITE in misslap_options.mat_dtype; the instances on DenseFinite*Args and
-// k_dense_finite_check): signed cost stacks.  An element is an entry iff it is not a NaN in its own type, so negative
-// values, -0.0 and subnormals are entries and NaN alone says "no edge"; an entry of either infinity condemns the
-// problem.  One compile-time flag (Fin) on everything that asks "is this an entry", default off; it is instantiated in
-// the strided family only, and a contiguous stack in this mode runs these kernels with its natural strides.
+// Entry rule, the layout's second fact.  DenseContig and DenseView<false> take the reference's "v >= 0".
+// DenseView<true> (MISSLAP_DENSE_ENTRIES_FINITE in misslap_options.mat_dtype) is a signed cost stack: an element is an
+// entry iff it is not a NaN in its own type, so negative values, -0.0 and subnormals are entries and NaN alone says
+// "no edge"; an entry of either infinity condemns the problem.  A compact stack under this rule is a view with its
+// natural strides (N * M, M, 1).
+//
+// Outside mode Out (misslap_solve_dense_batch_outside): row i of problem b also holds one virtual entry (i, m_b + i)
+// whose value is the row's outside value -- a private object that only row i can bid for, so a row may stay unmatched.
+// The problem solved is the dense n_b x (m_b + n_b) matrix hstack([slice, D_b]) with D_b the outside values on its
+// diagonal and no entry elsewhere; the round loop is batch_solve unchanged, on a carve of M + N objects.  The row source
+// presents the virtual entry (column m_b + i, above every real column), the check pass folds the outside values into
+// C = max |v| and the +inf flag, flags one that is no entry and never reports an empty row, and the solve kernel
+// rewrites the outputs behind batch_solve: an object >= m_b becomes -1 in sol, price[0 .. m_b) are the real prices and
+// price[m_b .. m_b + n_b) the outside prices.
 #pragma once
 
 namespace misslap {
@@ -57,28 +59,41 @@ struct DenseBatchCheck {
 struct DenseBatchArgs {
     BatchSolveArgs s;         // p0_ld = prices_ld = M, sol_ld = Ns = N, Ms = M
     const void *mat;          // elements of the kernel's T
-    long long N, M;           // the stack: row stride M, problem stride N * M, in elements
+    long long N, M;           // the extents of the stack (DenseContig: row stride M, problem stride N * M, in elements)
     const int *shapes;        // [B][2] (n_b, m_b) or null
     const DenseBatchCheck *chk;
 };
 
-// The element strides of a strided stack (all >= 0, the host has checked that the extent fits 62 bits), and the
-// smallest round that bids one lane per person (bid_lanes; INT_MAX: no round does).
+// The element strides of a view (all >= 0, the host has checked that the extent fits 62 bits), and the smallest round
+// that bids one lane per person (bid_lanes; INT_MAX: no round does).
 struct DenseStrides {
     long long sB, sN, sM;
     int lane_min_K;
 };
 
-// The column step of a row source: 1 at compile time in a contiguous stack, the stack's sM in a strided one.
-template <bool Str>
-struct DenseColStride {
-    __device__ __forceinline__ size_t at(int c) const { return (size_t)c; }
+// A layout: where problem b, its row i and the row's column c lie, in elements, and which elements are entries.
+// It is all the contiguous, strided and finite kernels differ in.
+struct DenseContig {
+    static constexpr bool kView = false, kUnitCol = true, kFinite = false;
+    __device__ __forceinline__ size_t problem(int b, long long N, long long M) const {
+        return (size_t)b * (size_t)N * (size_t)M;
+    }
+    __device__ __forceinline__ long long row_stride(long long M) const { return M; }
+    __device__ __forceinline__ size_t col(int c) const { return (size_t)c; }
 };
-template <>
-struct DenseColStride<true> {
-    long long sM;
-    int lane_min_K;
-    __device__ __forceinline__ size_t at(int c) const { return (size_t)c * (size_t)sM; }
+// Fin: the entry rule is "not a NaN".  Unit: sM == 1 is known where the code is compiled -- the solve kernels branch
+// on it once per workgroup (MISSLAP_DENSE_BATCH_RUN) and the row source then steps its columns as DenseContig does.
+template <bool Fin, bool Unit = false>
+struct DenseView {
+    static constexpr bool kView = true, kUnitCol = Unit, kFinite = Fin;
+    DenseStrides str;
+    __device__ __forceinline__ size_t problem(int b, long long, long long) const { return (size_t)b * (size_t)str.sB; }
+    __device__ __forceinline__ long long row_stride(long long) const { return str.sN; }
+    __device__ __forceinline__ size_t col(int c) const {
+        if constexpr (Unit) return (size_t)c;
+        else return (size_t)c * (size_t)str.sM;
+    }
+    __device__ __forceinline__ DenseView<Fin, true> unit() const { return {str}; }
 };
 
 __device__ __forceinline__ void dense_batch_shape(const int *shapes, long long N, long long M, int b, int &n, int &m) {
@@ -89,32 +104,42 @@ __device__ __forceinline__ void dense_batch_shape(const int *shapes, long long N
 // Validation, one workgroup per problem: valid count, empty rows, +inf, C = max |v|, the reference's M, prices.
 // With shapes_out (status mode: `shapes` may be a caller's device array that no host has seen) a shape outside
 // 1 .. N x 1 .. M becomes (0, 0), nothing of that problem is read, and the shape every later kernel uses is written
-// to shapes_out[b]: the guard and the solve read those, never the caller's.
-// Out (the outside mode): the outside value of every row < n_b counts as an entry's value does (ov: outside[b] with
-// ov_ld == 0, else outside[b * ov_ld + i]; a negative one or a NaN raises bit 1 of has_inf instead), no row is empty,
-// and with starting prices the problem's augmented starting prices [p0[:m_b], zeros(n_b)] are staged at
-// aug[b * (M + N) ..] for batch_solve to load.
-// Str (the strided family): element (b, r, c) lies at mat[b * str.sB + r * str.sN + c * str.sM]; else str is not read.
-// Fin (finite mode, below): an element is an entry iff it is not a NaN; max |v| and the infinity flag mask the sign, so
-// -inf is caught as +inf is; an outside value is an entry under the same rule (a NaN raises bit 1, either infinity bit 0).
-template <class T, bool Out, bool Str = false, bool Fin = false>
-__device__ __forceinline__ void dense_batch_check(const T *mat, long long N, long long M, const int *shapes,
-                                                  const double *p0, DenseBatchCheck *out, int *shapes_out,
-                                                  const double *ov, long long ov_ld, double *aug,
-                                                  const DenseStrides &str = {}) {
+// to shapes_out[b]: the guard and the solve read those, never the caller's.  The all-or-nothing call, whose host has
+// checked the shapes, passes null.
+// Out (the outside mode): the outside value of every row < n_b counts as an entry's value does (outside[b] with
+// outside_ld == 0, else outside[b * outside_ld + i]; one that is no entry raises bit 1 of has_inf instead), no row is
+// empty, and with starting prices the problem's augmented starting prices [p0[:m_b], zeros(n_b)] are staged at
+// aug[b * (M + N) ..] for batch_solve to load.  Otherwise outside and aug are not read.
+// Under the finite rule max |v| and the infinity flag mask the sign, so -inf is caught as +inf is; an outside value is
+// an entry under the layout's rule too (a NaN raises bit 1, either infinity bit 0).
+template <class Lay>
+struct DenseCheckArgs {
+    const void *mat;        // elements of the kernel's T
+    long long N, M;
+    const int *shapes;      // [B][2] or null
+    const double *p0;       // [B][M] or null
+    DenseBatchCheck *out;   // [B]
+    int *shapes_out;        // [B][2]: the sanitised shapes, or null
+    const double *outside;  // [B] (outside_ld == 0) or [B][outside_ld]
+    long long outside_ld;
+    double *aug;            // [B][M + N] or null (no starting prices)
+    [[no_unique_address]] Lay lay;
+};
+
+template <class T, class Lay, bool Out>
+__device__ __forceinline__ void dense_batch_check(const DenseCheckArgs<Lay> &a) {
+    const long long N = a.N, M = a.M;
     const int b = blockIdx.x, lane = lane_id(), wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
     int n, m;
-    dense_batch_shape(shapes, N, M, b, n, m);
-    if (shapes_out) {
+    dense_batch_shape(a.shapes, N, M, b, n, m);
+    if (int *shapes_out = a.shapes_out) {
         if (n < 1 || n > N || m < 1 || m > M) n = m = 0;
         if (threadIdx.x == 0) {
             shapes_out[2 * b] = n;
             shapes_out[2 * b + 1] = m;
         }
     }
-    const T *A = mat + (Str ? (size_t)b * (size_t)str.sB : (size_t)b * (size_t)N * (size_t)M);
-    DenseColStride<Str> col{};
-    if constexpr (Str) col.sM = str.sM;
+    const T *A = static_cast<const T *>(a.mat) + a.lay.problem(b, N, M);
     __shared__ unsigned long long s_cnt, s_abs;
     __shared__ int s_empty, s_inf, s_mref, s_badp;
     if (threadIdx.x == 0) {
@@ -129,11 +154,11 @@ __device__ __forceinline__ void dense_batch_check(const T *mat, long long N, lon
     unsigned long long cnt = 0, am = 0;
     int inf = 0, mx = -1;
     for (int r = wave; r < n; r += nw) {
-        const T *row = A + (size_t)r * (size_t)(Str ? str.sN : M);
+        const T *row = A + (size_t)r * (size_t)a.lay.row_stride(M);
         int rc = 0;
         for (int c = lane; c < m; c += kWave) {
-            const T v = row[col.at(c)];
-            if (dense_entry_is<Fin>(v)) {
+            const T v = row[a.lay.col(c)];
+            if (dense_entry_is<Lay::kFinite>(v)) {
                 const unsigned long long bits =
                     (unsigned long long)__double_as_longlong(dense_widen(v)) & 0x7fffffffffffffffull;
                 ++rc;
@@ -145,8 +170,8 @@ __device__ __forceinline__ void dense_batch_check(const T *mat, long long N, lon
         for (int off = 32; off >= 1; off >>= 1) rc += __shfl_xor(rc, off);
         if constexpr (Out) {
             if (lane == 0) {
-                const double o = ov[ov_ld ? (size_t)b * (size_t)ov_ld + (size_t)r : (size_t)b];
-                if (dense_entry_is<Fin>(o)) {
+                const double o = a.outside[a.outside_ld ? (size_t)b * (size_t)a.outside_ld + (size_t)r : (size_t)b];
+                if (dense_entry_is<Lay::kFinite>(o)) {
                     const unsigned long long bits = (unsigned long long)__double_as_longlong(o) & 0x7fffffffffffffffull;
                     am = bits > am ? bits : am;
                     inf |= bits == 0x7ff0000000000000ull;
@@ -163,11 +188,11 @@ __device__ __forceinline__ void dense_batch_check(const T *mat, long long N, lon
     if (am) atomicMax(&s_abs, am);
     if (inf) atomicOr(&s_inf, Out ? inf : 1);
     if (mx >= 0) atomicMax(&s_mref, mx + 1);
-    if (p0) batch_check_prices(p0 + (size_t)b * (size_t)M, m, &s_badp);
+    if (a.p0) batch_check_prices(a.p0 + (size_t)b * (size_t)M, m, &s_badp);
     if constexpr (Out) {
-        if (p0) {
-            const double *src = p0 + (size_t)b * (size_t)M;
-            double *dst = aug + (size_t)b * (size_t)(M + N);
+        if (a.p0) {
+            const double *src = a.p0 + (size_t)b * (size_t)M;
+            double *dst = a.aug + (size_t)b * (size_t)(M + N);
             for (int j = threadIdx.x; j < m + n; j += blockDim.x) dst[j] = j < m ? src[j] : 0.0;
         }
     }
@@ -180,50 +205,20 @@ __device__ __forceinline__ void dense_batch_check(const T *mat, long long N, lon
         r.has_inf = s_inf;
         r.mref = s_mref;
         r.bad_price = s_badp;
-        out[b] = r;
+        a.out[b] = r;
     }
 }
 
-template <class T>
-__global__ __launch_bounds__(256) void k_dense_batch_check(const T *mat, long long N, long long M, const int *shapes,
-                                                           const double *p0, DenseBatchCheck *out, int *shapes_out) {
-    dense_batch_check<T, false>(mat, N, M, shapes, p0, out, shapes_out, nullptr, 0, nullptr);
+// (the body stays a function of its own: written into the kernel, the double instances of DenseView<true> take another
+// register allocation)
+template <class T, class Lay, bool Out>
+__global__ __launch_bounds__(256) void k_dense_batch_check(DenseCheckArgs<Lay> a) {
+    dense_batch_check<T, Lay, Out>(a);
 }
 
-struct DenseOutsideCheckArgs {
-    const void *mat;        // elements of the kernel's T
-    long long N, M;
-    const int *shapes;      // [B][2] or null
-    const double *p0;       // [B][M] or null
-    DenseBatchCheck *out;   // [B]
-    int *shapes_out;        // [B][2]: the sanitised shapes (never null)
-    const double *outside;  // [B] (outside_ld == 0) or [B][outside_ld]
-    long long outside_ld;
-    double *aug;            // [B][M + N] or null (no starting prices)
-};
-
-template <class T>
-__global__ __launch_bounds__(256) void k_dense_outside_check(DenseOutsideCheckArgs a) {
-    dense_batch_check<T, true>(static_cast<const T *>(a.mat), a.N, a.M, a.shapes, a.p0, a.out, a.shapes_out, a.outside,
-                               a.outside_ld, a.aug);
-}
-
-// the check pass of the strided family, in either mode (Out false: a.outside and a.aug are not read)
-template <class T, bool Out>
-__global__ __launch_bounds__(256) void k_dense_strided_check(DenseOutsideCheckArgs a, DenseStrides str) {
-    dense_batch_check<T, Out, true>(static_cast<const T *>(a.mat), a.N, a.M, a.shapes, a.p0, a.out, a.shapes_out,
-                                    a.outside, a.outside_ld, a.aug, str);
-}
-
-// ... and of a finite-mode call (a kernel of its own name: k_dense_strided_check's instances are what they were)
-template <class T, bool Out>
-__global__ __launch_bounds__(256) void k_dense_finite_check(DenseOutsideCheckArgs a, DenseStrides str) {
-    dense_batch_check<T, Out, true, true>(static_cast<const T *>(a.mat), a.N, a.M, a.shapes, a.p0, a.out, a.shapes_out,
-                                          a.outside, a.outside_ld, a.aug, str);
-}
-
-// The dense row source of batch_solve: problem b's slice A (row stride M) of n x m, its reference M and valid count.
-// The bid's staging array `vals` belongs to k_dense_batch_solve: declared in bid() it is promoted to a vector while bid()
+// The dense row source of batch_solve: problem b's slice A of n x m, its reference M and valid count.  Entry (i, c)
+// lies at A[i * M + lay.col(c)], M being the layout's row stride (MISSLAP_DENSE_BATCH_RUN fills both in).
+// The bid's staging array `vals` belongs to the solve kernel: declared in bid() it is promoted to a vector while bid()
 // is optimised on its own, and every staging step then zeroes the rest of it (measured: 3.8 % more kernel time at
 // 64 x 1000).  Declared in the kernel, it becomes 16 register pairs as in a hand-inlined scan.  The row is staged in its
 // own type T -- 16 registers for float and for the 16-bit types, one element per lane per load with the same
@@ -232,28 +227,33 @@ __global__ __launch_bounds__(256) void k_dense_finite_check(DenseOutsideCheckArg
 // problem (m + n columns, n more entries).  Column m + i is above every real column, and lane (m + i) & 63 takes it AFTER
 // its own real columns, so every lane still scans in ascending column order and the winner's lane is r.g & 63 as before.
 // A chosen object j >= m is that entry: nothing of the slice is read for it.
-// Str (the strided family): M is the row stride sN and col holds the column stride sM; entry (i, c) lies at
-// A[i * M + c * sM].  The wavefront scan keeps its lane map (lane l holds columns l, l + 64, ...) whatever the strides
-// are, with loads of one element each: nothing wider than the element is assumed of the base or of a stride.
-// Fin (finite mode): the entry test of the three bid mappings and of the eCE walk is "not a NaN" (dense_entry_is); a
-// staging slot beyond the row still holds dense_hole, which is an entry under this rule, and is still never tested:
-// every scan asks c < m first.  Resolved at compile time: the <.., false> instances are the code they were.
-template <class T, bool Out = false, bool Str = false, bool Fin = false>
+// The wavefront scan keeps its lane map (lane l holds columns l, l + 64, ...) whatever the strides are, with loads of
+// one element each: nothing wider than the element is assumed of the base or of a stride.
+// Under the finite rule a staging slot beyond the row still holds dense_hole, which is then an entry, and is still
+// never tested: every scan asks c < m first.
+template <class T, class Lay, bool Out>
 struct DenseBatchRows {
     const T *A;
     long long M;
     int m, maximize, mref;
     unsigned long long nvalid;
     T *vals;  // [kDenseBatchCols]
-    BatchOutside<Out> out{};
-    DenseColStride<Str> col{};
+    BatchOutside<Out> out;
+    [[no_unique_address]] Lay lay;
+
+    // one candidate of a scan: value v of object c, against the best two so far
+    __device__ __forceinline__ void take(Top2 &x, double &cb, double v, int c, const double *price) const {
+        const double cost = maximize ? v : v * -1.0;  // :236-237
+        const double vi = cost - price[c];
+        if (top2_take(x, vi, c)) cb = cost;
+    }
 
     __device__ __forceinline__ Top2 bid(int i, const double *price, double &costbest, int &obj) const {
         const int lane = lane_id();
         const T *row = A + (size_t)i * (size_t)M;
         Top2 x;
         double cb;
-        if constexpr (!Str) {
+        if constexpr (Lay::kUnitCol) {
 #pragma unroll
             for (int q = 0; q < kDenseBatchCols; ++q) {
                 if (q * kWave >= m) break;
@@ -268,23 +268,18 @@ struct DenseBatchRows {
             for (int q = 0; q < kDenseBatchCols; ++q) {
                 if (q * kWave >= m) break;
                 const int c = lane + q * kWave;
-                if (c < m && dense_entry_is<Fin>(vals[q])) {
-                    const double v = dense_widen(vals[q]);
-                    const double cost = maximize ? v : v * -1.0;  // :236-237
-                    const double vi = cost - price[c];
-                    if (top2_take(x, vi, c)) cb = cost;
-                }
+                if (c < m && dense_entry_is<Lay::kFinite>(vals[q])) take(x, cb, dense_widen(vals[q]), c, price);
             }
         } else {
-            // a column stride other than 1 (a strided kernel gives sM == 1 to the contiguous row source): one pointer
-            // stepped from load to load, staged and scanned in two halves of 8 slots, in ascending order -- 16
-            // addresses next to 16 staged doubles do not fit the 128 registers of a 1024-thread workgroup
+            // a column stride other than 1 (a view's sM == 1 takes the scan above): one pointer stepped from load to
+            // load, staged and scanned in two halves of 8 slots, in ascending order -- 16 addresses next to 16 staged
+            // doubles do not fit the 128 registers of a 1024-thread workgroup
             x.v = -__builtin_huge_val();
             x.w = -__builtin_huge_val();
             x.g = -1;
             cb = 0.0;
-            const T *p = row + (size_t)lane * (size_t)col.sM;
-            const size_t step = (size_t)kWave * (size_t)col.sM;
+            const T *p = row + (size_t)lane * (size_t)lay.str.sM;
+            const size_t step = (size_t)kWave * (size_t)lay.str.sM;
             constexpr int kHalf = kDenseBatchCols / 2;
             for (int h = 0; h < kDenseBatchCols && h * kWave < m; h += kHalf) {
 #pragma unroll
@@ -295,22 +290,12 @@ struct DenseBatchRows {
 #pragma unroll
                 for (int q = 0; q < kHalf; ++q) {
                     const int c = lane + (h + q) * kWave;
-                    if (c < m && dense_entry_is<Fin>(vals[q])) {
-                        const double v = dense_widen(vals[q]);
-                        const double cost = maximize ? v : v * -1.0;
-                        const double vi = cost - price[c];
-                        if (top2_take(x, vi, c)) cb = cost;
-                    }
+                    if (c < m && dense_entry_is<Lay::kFinite>(vals[q])) take(x, cb, dense_widen(vals[q]), c, price);
                 }
             }
         }
         if constexpr (Out) {
-            if (lane == ((m + i) & (kWave - 1))) {
-                const double v = out.value(i);
-                const double cost = maximize ? v : v * -1.0;
-                const double vi = cost - price[m + i];
-                if (top2_take(x, vi, m + i)) cb = cost;
-            }
+            if (lane == ((m + i) & (kWave - 1))) take(x, cb, out.value(i), m + i, price);
         }
         const Top2 r = top2_wave_reduce(x);
         costbest = readlane_f64(cb, r.g & (kWave - 1));  // the lane that holds column r.g
@@ -318,7 +303,7 @@ struct DenseBatchRows {
         return r;
     }
 
-    // The second bid mapping of a strided row source, for a whole round: one LANE per list position, 64 persons per
+    // The second bid mapping of a view's row source, for a whole round: one LANE per list position, 64 persons per
     // wavefront.  On a stack whose rows run along the unit stride (M == sN == 1: a transposed view) a wavefront that
     // scans one person's row touches 64 cache lines per load; here lane l scans the row of person U[k0 + l] in column
     // order, so one load instruction reads column c of 64 persons, and in the first round of every eps-phase
@@ -329,8 +314,8 @@ struct DenseBatchRows {
     // for one bidder) or another layout.  The branch is uniform.
     __device__ __forceinline__ bool bid_lanes(const int *U, int K, const double *price, float eps,
                                               unsigned long long *bid_key, int *bid_obj, unsigned long long *bkey) const {
-        static_assert(Str, "only a strided row source has the lane-per-person bid");
-        if (K < col.lane_min_K || M != 1) return false;
+        static_assert(Lay::kView && !Lay::kUnitCol, "only a view's row source has the lane-per-person bid");
+        if (K < lay.str.lane_min_K || M != 1) return false;
         constexpr int kFly = 8;
         for (int k = threadIdx.x; k < K; k += blockDim.x) {
             const int i = U[k];
@@ -343,24 +328,14 @@ struct DenseBatchRows {
             for (int c0 = 0; c0 < m; c0 += kFly) {
                 T v8[kFly];
 #pragma unroll
-                for (int q = 0; q < kFly; ++q) v8[q] = c0 + q < m ? row[col.at(c0 + q)] : dense_hole<T>();
+                for (int q = 0; q < kFly; ++q) v8[q] = c0 + q < m ? row[lay.col(c0 + q)] : dense_hole<T>();
 #pragma unroll
                 for (int q = 0; q < kFly; ++q) {
                     const int c = c0 + q;
-                    if (c < m && dense_entry_is<Fin>(v8[q])) {
-                        const double v = dense_widen(v8[q]);
-                        const double cost = maximize ? v : v * -1.0;  // :236-237
-                        const double vi = cost - price[c];
-                        if (top2_take(x, vi, c)) cb = cost;
-                    }
+                    if (c < m && dense_entry_is<Lay::kFinite>(v8[q])) take(x, cb, dense_widen(v8[q]), c, price);
                 }
             }
-            if constexpr (Out) {
-                const double v = out.value(i);
-                const double cost = maximize ? v : v * -1.0;
-                const double vi = cost - price[m + i];
-                if (top2_take(x, vi, m + i)) cb = cost;
-            }
+            if constexpr (Out) take(x, cb, out.value(i), m + i, price);
             const unsigned long long key = bid_to_key(cb - x.w + (double)eps);  // :360
             bid_key[k] = key;
             bid_obj[k] = x.g;
@@ -373,8 +348,8 @@ struct DenseBatchRows {
     __device__ __forceinline__ bool ece_bad(int i, int j, const double *price, double tol, double eps) const {
         const T *row = A + (size_t)i * (size_t)M;
         double vj;
-        if constexpr (Out) vj = j >= m ? out.value(i) : dense_widen(row[col.at(j)]);
-        else vj = dense_widen(row[col.at(j)]);
+        if constexpr (Out) vj = j >= m ? out.value(i) : dense_widen(row[lay.col(j)]);
+        else vj = dense_widen(row[lay.col(j)]);
         const double choice_cost = maximize ? vj : vj * -1.0;
         const double LHS = choice_cost - price[j] + tol;  // :475
         bool bad = false;
@@ -386,8 +361,8 @@ struct DenseBatchRows {
             }
         }
         for (int c = lane_id(); c < m; c += kWave) {
-            const T e = row[col.at(c)];
-            if (!dense_entry_is<Fin>(e)) continue;
+            const T e = row[lay.col(c)];
+            if (!dense_entry_is<Lay::kFinite>(e)) continue;
             const double v = dense_widen(e);
             const double cost = maximize ? v : v * -1.0;
             if (LHS < (cost - price[c]) - eps) bad = true;  // :482
@@ -405,7 +380,7 @@ struct DenseBatchRows {
                     continue;
                 }
             }
-            selv[i] = j >= 0 ? dense_widen(A[(size_t)i * (size_t)M + col.at(j)]) : 0.0;
+            selv[i] = j >= 0 ? dense_widen(A[(size_t)i * (size_t)M + lay.col(j)]) : 0.0;
         }
     }
 
@@ -425,45 +400,69 @@ struct DenseBatchRows {
     __device__ __forceinline__ int64_t meta_nnz() const { return (int64_t)nvalid; }
 };
 
-template <class T, bool Out, bool Fin>
-struct RowsBidLanes<DenseBatchRows<T, Out, true, Fin>> {
+template <class T, bool Fin, bool Out>
+struct RowsBidLanes<DenseBatchRows<T, DenseView<Fin>, Out>> {
     static constexpr bool value = true;
 };
 
-template <class T>
+// batch_solve on the accepted problem b (n x m) of a kernel's stack, written once: the one place that forms the
+// problem's base pointer and row stride from the layout `lay`, builds the row source and holds a view's branch.
+// d: the kernel's DenseBatchArgs, s: its BatchSolveArgs, vals: its staging array, out: a BatchOutside<Out> (the
+// outside mode counts the augmented problem: m + n columns, n more entries).  A view with a unit column stride takes
+// the scan of the contiguous row source with sN for its row stride (the same bid, instruction for instruction); any
+// other takes the two-half scan.  That branch is uniform, and a view's kernel holds both solves.
+// A macro, because the sequence has to be compiled as part of the kernel that declares `vals`.  A callee is optimised
+// on its own before it is inlined: one that builds the row source around a `vals` it only has a pointer to forwards
+// the staged values past the array (all 34 solve instances then move, by 2 VGPRs at double); one that declares `vals`
+// itself leaves the contiguous instances alone but the view instances allocate their scalar registers anew; and even a
+// function that only returns the row source moves the contiguous instances by a register.
+#define MISSLAP_DENSE_BATCH_RUN(T, Lay, Out, d, lay, s, b, n, m, ck, vals, out)                                           \
+    do {                                                                                                                  \
+        const T *A = static_cast<const T *>(d.mat) + lay.problem(b, d.N, d.M);                                            \
+        const unsigned long long nv = Out ? ck.nvalid + (unsigned long long)n : ck.nvalid;                                \
+        if constexpr (Lay::kView) {                                                                                       \
+            if (lay.str.sM == 1) {                                                                                        \
+                const DenseBatchRows<T, DenseView<Lay::kFinite, true>, Out> rows{                                         \
+                    A, lay.row_stride(d.M), m, s.maximize, Out ? m + n : ck.mref, nv, vals, out, lay.unit()};             \
+                batch_solve(s, rows, n, Out ? m + n : m, ck.absmax_bits);                                                 \
+            } else {                                                                                                      \
+                const DenseBatchRows<T, Lay, Out> rows{                                                                   \
+                    A, lay.row_stride(d.M), m, s.maximize, Out ? m + n : ck.mref, nv, vals, out, lay};                    \
+                batch_solve(s, rows, n, Out ? m + n : m, ck.absmax_bits);                                                 \
+            }                                                                                                             \
+        } else {                                                                                                          \
+            const DenseBatchRows<T, Lay, Out> rows{                                                                       \
+                A, lay.row_stride(d.M), m, s.maximize, Out ? m + n : ck.mref, nv, vals, out, lay};                        \
+            batch_solve(s, rows, n, Out ? m + n : m, ck.absmax_bits);                                                     \
+        }                                                                                                                 \
+    } while (0)
+
+template <class T, class Lay = DenseContig>
 __global__ __launch_bounds__(1024) void k_dense_batch_solve(DenseBatchArgs a) {
     const int b = blockIdx.x;
     int n, m;
     dense_batch_shape(a.shapes, a.N, a.M, b, n, m);
     const DenseBatchCheck ck = a.chk[b];
     T vals[kDenseBatchCols];
-    const DenseBatchRows<T> rows{static_cast<const T *>(a.mat) + (size_t)b * (size_t)a.N * (size_t)a.M, a.M, m, a.s.maximize,
-                                 ck.mref, ck.nvalid, vals};
-    batch_solve(a.s, rows, n, m, ck.absmax_bits);
+    const Lay lay{};
+    MISSLAP_DENSE_BATCH_RUN(T, Lay, false, a, lay, a.s, b, n, m, ck, vals, BatchOutside<false>{});
 }
 
 // ---- status mode (misslap_solve_dense_batch_status): a verdict per problem instead of all or nothing
 
-struct DenseBatchStatusArgs {
-    static constexpr bool kStrided = false;
-    static constexpr bool kFinite = false;  // the entry rule of the kernel's instance (finite mode: below)
-    DenseBatchArgs d;      // d.shapes: the check pass's sanitised shapes (never null)
+// what the two solves with a verdict share
+struct DenseVerdictArgs {
+    DenseBatchArgs d;      // d.shapes: the check pass's sanitised shapes (never null); d.mat: the stack's first element
     const int *card;       // [B] the guard's cardinalities, or null: no guard in this call
     int fast;              // eps_start = 1 / n_b of each problem (auction_.pyx:568-569)
     int *status;           // [B] MISSLAP_BATCH_STATUS_*
     int *matching_size;    // [B] or null: the guard's cardinality, -1 where it did not run
 };
 
-// ... and of the strided family: d.mat is the view's first element, d.N / d.M its extents
-struct DenseStridedStatusArgs : DenseBatchStatusArgs {
-    static constexpr bool kStrided = true;
-    DenseStrides str;
-};
-
-// ... and of a finite-mode call (MISSLAP_DENSE_ENTRIES_FINITE): the strided family with "not a NaN" for its entry test.
-// A contiguous stack comes here with its natural strides (N * M, M, 1).
-struct DenseFiniteStatusArgs : DenseStridedStatusArgs {
-    static constexpr bool kFinite = true;
+template <class Lay>
+struct DenseStatusArgs {
+    DenseVerdictArgs t;
+    [[no_unique_address]] Lay lay;
 };
 
 // The dense checks of a verdict, in first_error's order (abi_dense_batch.hpp); batch_verdict adds the shared rest.
@@ -477,63 +476,37 @@ __device__ __forceinline__ int dense_batch_verdict(const DenseBatchCheck &c, int
 
 // k_dense_batch_solve with the verdict formed here, from what the check pass and the guard left on the device.  A
 // condemned problem's workgroup writes the defined outputs and leaves before any LDS state exists; the others run the
-// same batch_solve on the same row source.  Args: DenseBatchStatusArgs, or DenseStridedStatusArgs for the strided family.
-template <class T, class Args = DenseBatchStatusArgs>
-__global__ __launch_bounds__(1024) void k_dense_batch_solve_status(Args a) {
+// same batch_solve on the same row source.
+template <class T, class Lay>
+__global__ __launch_bounds__(1024) void k_dense_batch_solve_status(DenseStatusArgs<Lay> a) {
     const int b = blockIdx.x;
-    const int n = a.d.shapes[2 * b], m = a.d.shapes[2 * b + 1];
-    const DenseBatchCheck ck = a.d.chk[b];
-    const int card = a.card && n >= 1 ? a.card[b] : -1;
-    const int code = batch_verdict(dense_batch_verdict(ck, n), a.card != nullptr, card, n, ck.bad_price);
-    batch_publish_verdict(a.status, a.matching_size, b, code, card);
+    const DenseBatchArgs &d = a.t.d;
+    const int n = d.shapes[2 * b], m = d.shapes[2 * b + 1];
+    const DenseBatchCheck ck = d.chk[b];
+    const int card = a.t.card && n >= 1 ? a.t.card[b] : -1;
+    const int code = batch_verdict(dense_batch_verdict(ck, n), a.t.card != nullptr, card, n, ck.bad_price);
+    batch_publish_verdict(a.t.status, a.t.matching_size, b, code, card);
     if (code != MISSLAP_BATCH_STATUS_OK) {
-        batch_condemn(a.d.s, n, ck.mref, (long long)ck.nvalid);
+        batch_condemn(d.s, n, ck.mref, (long long)ck.nvalid);
         return;
     }
-    BatchSolveArgs s = a.d.s;
-    if (a.fast) batch_fast_eps(s, n);
+    BatchSolveArgs s = d.s;
+    if (a.t.fast) batch_fast_eps(s, n);
     T vals[kDenseBatchCols];
-    if constexpr (Args::kStrided) {
-        // a unit column stride is the contiguous row source with sN for its row stride (the same bid, instruction for
-        // instruction); any other takes the strided one.  The branch is uniform.
-        constexpr bool kFin = Args::kFinite;
-        const T *A = static_cast<const T *>(a.d.mat) + (size_t)b * (size_t)a.str.sB;
-        if (a.str.sM == 1) {
-            const DenseBatchRows<T, false, false, kFin> rows{A, a.str.sN, m, s.maximize, ck.mref, ck.nvalid, vals};
-            batch_solve(s, rows, n, m, ck.absmax_bits);
-        } else {
-            const DenseBatchRows<T, false, true, kFin> rows{A, a.str.sN, m, s.maximize, ck.mref, ck.nvalid, vals, {},
-                                                            {a.str.sM, a.str.lane_min_K}};
-            batch_solve(s, rows, n, m, ck.absmax_bits);
-        }
-    } else {
-        const DenseBatchRows<T> rows{static_cast<const T *>(a.d.mat) + (size_t)b * (size_t)a.d.N * (size_t)a.d.M, a.d.M, m,
-                                     s.maximize, ck.mref, ck.nvalid, vals};
-        batch_solve(s, rows, n, m, ck.absmax_bits);
-    }
+    MISSLAP_DENSE_BATCH_RUN(T, Lay, false, d, a.lay, s, b, n, m, ck, vals, BatchOutside<false>{});
 }
-
 
 // ---- outside mode (misslap_solve_dense_batch_outside): an outside option per row, for partial assignments
 
+template <class Lay>
 struct DenseOutsideArgs {
-    static constexpr bool kStrided = false;
-    static constexpr bool kFinite = false;
-    DenseBatchStatusArgs t;  // t.d.s: Ms = M + N (the carve), p0 / p0_ld the staged augmented prices, prices null;
+    DenseVerdictArgs t;      // t.d.s: Ms = M + N (the carve), p0 / p0_ld the staged augmented prices, prices null;
                              // t.card null: no guard in this call
     const double *outside;   // [B] (outside_ld == 0) or [B][outside_ld]
     long long outside_ld;
     double *prices;          // [B][M] or null: the real columns
     double *outside_prices;  // [B][N] or null
-};
-
-struct DenseStridedOutsideArgs : DenseOutsideArgs {
-    static constexpr bool kStrided = true;
-    DenseStrides str;
-};
-
-struct DenseFiniteOutsideArgs : DenseStridedOutsideArgs {  // (finite mode, as DenseFiniteStatusArgs)
-    static constexpr bool kFinite = true;
+    [[no_unique_address]] Lay lay;
 };
 
 // The checks of an outside verdict in their order; EMPTY_ROW, TOO_FEW_VALUES and INFEASIBLE cannot occur.
@@ -545,9 +518,9 @@ __device__ __forceinline__ int dense_outside_verdict(const DenseBatchCheck &c, i
 }
 
 // The solve of the outside mode: the verdict, batch_solve on the n x (m + n) problem, then the outputs in the caller's
-// terms (batch_outside_outputs).  Args: DenseOutsideArgs, or DenseStridedOutsideArgs for the strided family.
-template <class T, class Args = DenseOutsideArgs>
-__global__ __launch_bounds__(1024) void k_dense_outside_solve(Args a) {
+// terms (batch_outside_outputs).
+template <class T, class Lay>
+__global__ __launch_bounds__(1024) void k_dense_outside_solve(DenseOutsideArgs<Lay> a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
     const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
     const DenseBatchArgs &d = a.t.d;
@@ -567,30 +540,7 @@ __global__ __launch_bounds__(1024) void k_dense_outside_solve(Args a) {
     if (a.t.fast) batch_fast_eps(s, n);
     T vals[kDenseBatchCols];
     const double *O = a.outside + (a.outside_ld ? (size_t)b * (size_t)a.outside_ld : (size_t)b);
-    if constexpr (Args::kStrided) {  // (as in k_dense_batch_solve_status)
-        constexpr bool kFin = Args::kFinite;
-        const T *A = static_cast<const T *>(d.mat) + (size_t)b * (size_t)a.str.sB;
-        const unsigned long long nv = ck.nvalid + (unsigned long long)n;
-        if (a.str.sM == 1) {
-            const DenseBatchRows<T, true, false, kFin> rows{A, a.str.sN, m, s.maximize, m + n, nv, vals,
-                                                            {O, a.outside_ld ? 1 : 0}};
-            batch_solve(s, rows, n, m + n, ck.absmax_bits);
-        } else {
-            const DenseBatchRows<T, true, true, kFin> rows{A, a.str.sN, m, s.maximize, m + n, nv, vals,
-                                                           {O, a.outside_ld ? 1 : 0}, {a.str.sM, a.str.lane_min_K}};
-            batch_solve(s, rows, n, m + n, ck.absmax_bits);
-        }
-    } else {
-        const DenseBatchRows<T, true> rows{static_cast<const T *>(d.mat) + (size_t)b * (size_t)d.N * (size_t)d.M,
-                                           d.M,
-                                           m,
-                                           s.maximize,
-                                           m + n,
-                                           ck.nvalid + (unsigned long long)n,
-                                           vals,
-                                           {O, a.outside_ld ? 1 : 0}};
-        batch_solve(s, rows, n, m + n, ck.absmax_bits);
-    }
+    MISSLAP_DENSE_BATCH_RUN(T, Lay, true, d, a.lay, s, b, n, m, ck, vals, (BatchOutside<true>{O, a.outside_ld ? 1 : 0}));
     batch_outside_outputs(s_raw, d.s, b, n, m, M, N, po, oo, tid, nt);
 }
 

@@ -513,7 +513,6 @@ MISSLAP_API int misslap_get_state(misslap_solver *h, double *prices, int32_t *un
 #include "abi_batch_stream.hpp"
 #include "abi_dense_batch.hpp"
 #include "abi_dense_batch_status.hpp"
-#include "abi_dense_batch_outside.hpp"
 #include "abi_sparse_batch.hpp"
 #include "abi_matching_batch.hpp"
 #include "abi_ell_batch.hpp"

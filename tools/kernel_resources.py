@@ -2,10 +2,12 @@
 """Register / LDS / spill numbers of every kernel of the library, from hipcc -Rpass-analysis=kernel-resource-usage
 (runs without a GPU).  usage: kernel_resources.py [substring ...] [-- extra hipcc flags]
 The batch solves and their guards: `kernel_resources.py batch ell matching sparse_outside` (k_dense_* / k_sparse_batch_* /
-k_ell_* / k_matching_batch*, the outside modes k_dense_outside_* / k_ell_outside_* and k_sparse_outside_solve<Src>; the
-sparse check pass of both modes is k_sparse_batch_check<Src, Out>, Src being SparsePacked or SparseView<I, V>).
+k_ell_* / k_matching_batch*, the outside modes k_dense_outside_solve<T, Lay> / k_ell_outside_* and
+k_sparse_outside_solve<Src>; the check pass of both modes is k_dense_batch_check<T, Lay, Out>, Lay being DenseContig or
+DenseView<Fin>, and k_sparse_batch_check<Src, Out>, Src being SparsePacked or SparseView<I, V>).
 With --code-size the device code is compiled once more on its own and every line ends in code=<bytes>, the size of the
-kernel's symbol in the gfx950 code object (the comparison of DESIGN 4.20)."""
+kernel's symbol in the gfx950 code object (the comparisons of DESIGN 4.20 and 4.21:
+`kernel_resources.py --code-size dense matching_batch`)."""
 import os
 import re
 import subprocess
