@@ -663,6 +663,57 @@ __device__ __forceinline__ void cand_eval1_lane(Slot &slot, const PriceRec r, co
     // (bad_hi_is_error) -- two instructions per bid
     bad_hi = max(bad_hi, hit ? (unsigned)__double2hiint(out.bid) : 0u);
 }
+// The lane-wise form for TWO lines behind one cand_gather2 (the tail's block rounds): lanes 0..31 hold the line of one list
+// slot, lanes 32..63 that of the next (act0 / act1 = the half holds a person at all, wave-uniform; no lane of an inactive
+// half becomes `mine`).  Every lane works for its own half: v = cost - price, the winner = the last stored slot among equal
+// maxima, W counting multiplicity in every lane of the half (half_allmax_f64), tau of the lane's half, bid = (cost - W) +
+// eps and hit = mine & v > tau & W >= tau -- cand_eval2_r's operations on the same operands in the same order, executed by
+// the lane that holds the winning candidate, and the bid does not become a key and back.  That lane also holds the rest of
+// the round's result in its own registers: the object is its column, the object's owner and the owner's row start are its
+// gathered record.  "Winner first" as in the pair round: one 32-bit reduction of the values' high words, one ballot; the
+// exact 64-bit passes only when an active half has no single maximum on the high word (a tie, or no candidate at all).
+// (The straight-line lane-wise form -- always the exact passes, no branch -- was measured 9 ms per C3 solve slower in the
+// block instance, slower than the scalar form it replaces: profiles/tail_block_lane.txt.)
+// Wave-uniform is what control flow and the statistics need: the ballot of `hit` and the two row lengths.
+struct LaneBid2 {
+    bool mine;              // the lane holds its half's winning candidate (at most one lane per half)
+    bool hit;               // ... and its half's line decided
+    double bid;             // (lanes `mine`) bbest
+    unsigned long long hm;  // wave-uniform: ballot of `hit`
+    int len[2];             // wave-uniform: row lengths of the two persons (an inactive half's is undefined)
+};
+template <class Slot>
+__device__ __forceinline__ void cand_eval2_lane(const Slot &slot, const PriceRec r, const bool act0, const bool act1,
+                                                const double eps, LaneBid2 &out, unsigned &bad_hi) {
+    const int lane = lane_id(), l32 = lane & (kCandLanes - 1);
+    const bool upper = lane >= kCandLanes;
+    const double ninf = -__builtin_huge_val();
+    const bool active = upper ? act1 : act0;
+    const bool is_cand = active & (l32 >= 1) & (l32 <= kCandMax) & (slot.x >= 0);
+    const double cost = slot_cost_or_ninf(slot, is_cand);  // (everything that needs the lines alone: under the gather)
+    const double tau0 = readlane_f64(__hiloint2double(slot.y, slot.x), 0);
+    const double tau1 = readlane_f64(__hiloint2double(slot.y, slot.x), kCandLanes);
+    const double tau = upper ? tau1 : tau0;
+    out.len[0] = __builtin_amdgcn_readlane(slot.x, kCandLanes - 1);
+    out.len[1] = __builtin_amdgcn_readlane(slot.x, 2 * kCandLanes - 1);
+    const double v = cost - r.price;  // vi = cost - p[j]   (:350); -inf where the lane holds no candidate
+    const int hw = __double2hiint(v);
+    const int k = hw ^ ((hw >> 31) & 0x7fffffff);  // signed order of k == order of the doubles' high words
+    const bool top = k == half_allmax_i32(k);
+    const unsigned long long eq = __ballot(top);
+    // (a half without a candidate is all -inf: 32 equal lanes; an inactive one needs no winner)
+    if ((int)(__popc((unsigned)eq) == 1) & ((int)(__popc((unsigned)(eq >> 32)) == 1) | (int)!act1)) {  // wave-uniform
+        out.mine = top & active;
+    } else {  // the exact passes, for both halves in the same instructions
+        const double V = half_allmax_f64(v);
+        out.mine = lane == half_allmax_i32((is_cand & (v == V)) ? lane : -1);  // the LAST slot holding it (-1: no lane)
+    }
+    const double W = half_allmax_f64(out.mine ? ninf : v);  // second best of the lane's half, counting multiplicity
+    out.bid = (cost - W) + eps;                              // bbest = costbest - wi + eps   (:360), in the winners' lanes
+    out.hit = out.mine & (v > tau) & (W >= tau);
+    bad_hi = max(bad_hi, out.hit ? (unsigned)__double2hiint(out.bid) : 0u);  // (per lane, see cand_eval1_lane)
+    out.hm = __builtin_amdgcn_ballot_w64(out.hit);
+}
 // (+inf = 0x7ff00000:00000000 is a legal bid; every NaN an operation produces and every negative value has a larger high word)
 __device__ __forceinline__ bool bad_hi_is_error(unsigned bad_hi) { return bad_hi > 0x7ff00000u; }
 struct NoEarly {

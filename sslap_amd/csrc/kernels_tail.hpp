@@ -1116,7 +1116,9 @@ struct k_tail {
         if (t == 0) sMissCnt = 0;
         __syncthreads();
 
-        // per-mode accounting (always on: two s_memrealtime reads per mode entry, 100 MHz ticks), Ctl::dbg:
+        // per-mode accounting (always on: two s_memrealtime reads per mode entry -- block mode: per ROUND; bracketing a whole
+        // run of block rounds instead was measured 1.3 ms per C3 solve slower, profiles/tail_block_lane.txt --, 100 MHz
+        // ticks), Ctl::dbg:
         //   [0..2] rounds in chain + solo / team / block mode, [3..5] ticks
         unsigned long long md[6] = {0, 0, 0, 0, 0, 0};
 #ifdef MISSLAP_TAIL_STAMP_BLOCK
@@ -1216,12 +1218,13 @@ struct k_tail {
                 // (sixteen wavefronts -- four per SIMD -- hide the two latencies by themselves: measured per block round
                 // 3.51 us with one sweep in flight, 3.69 with two, 3.96 with three, 4.06 with four)
                 constexpr int kBlockDepth = kBlockOnly ? 1 : 3;
+                const int wv = __builtin_amdgcn_readfirstlane(wave);  // (a scalar: the tests on a wavefront's slots are branches)
                 for (int base = 0; base < K; base += kBlockDepth * 2 * nwaves) {
                     typename E::Slot sl[kBlockDepth];
                     PriceRec rr[kBlockDepth];
 #pragma unroll
                     for (int c = 0; c < kBlockDepth; ++c) {
-                        const int nme = base + c * 2 * nwaves + 2 * wave + (lane >> 5);
+                        const int nme = base + c * 2 * nwaves + 2 * wv + (lane >> 5);
                         const int pme = nme < K ? sU[min(nme, kTailMax - 1)] : -1;
                         sl[c] = cand_no_line<typename E::Slot>();
                         if (E::kCand && a.cand != nullptr) sl[c] = line_of<E>(a, pme, lane & (kCandLanes - 1));
@@ -1229,38 +1232,57 @@ struct k_tail {
                     bstamp(1);
 #pragma unroll
                     for (int c = 0; c < kBlockDepth; ++c) {
-                        const int n0 = base + c * 2 * nwaves + 2 * wave;
+                        const int n0 = base + c * 2 * nwaves + 2 * wv;
                         if (E::kCand) rr[c] = cand_gather2(sl[c], n0 < K, n0 + 1 < K, src);
                     }
                     bstamp(2);
 #pragma unroll
                     for (int c = 0; c < kBlockDepth; ++c) {
-                        const int n0 = base + c * 2 * nwaves + 2 * wave;
+                        const int n0 = base + c * 2 * nwaves + 2 * wv;
                         if (n0 >= K) continue;  // wave-uniform
-                        CandBid b[2];
-                        b[0].hit = b[1].hit = false;
-                        if (E::kCand) cand_eval2_r(sl[c], rr[c], n0 < K, n0 + 1 < K, eps, b, st.err, NoEarly());
-#pragma unroll
-                        for (int X = 0; X < 2; ++X) {
-                            const int n = n0 + X;
-                            if (n >= K) continue;  // wave-uniform
-                            if (b[X].hit) {
-                                if (lane == 0) {
-                                    sKey[n] = b[X].key;
-                                    sObj[n] = b[X].obj;
-                                    // owner at the start of the round == what the assignment phase reads (:401): the
-                                    // record of obj is only rewritten by this round's winner of obj, after every bid
-                                    // has been made.
-                                    sPrev[n] = b[X].prev;
-                                    sPst[n] = b[X].pstart;
-                                }
-                                st.edges += (unsigned long long)b[X].len;
+                        // lane-wise (device_common.hpp: cand_eval2_lane): the lane that holds a half's winning candidate
+                        // forms the bid and the hit test and publishes the slot's result from its own registers -- its
+                        // column, and the owner and the owner's row start of its gathered record -- both halves in the
+                        // same LDS instructions
+                        LaneBid2 w;
+                        w.hit = false;
+                        w.hm = 0ull;
+                        w.len[0] = w.len[1] = 0;
+                        if (E::kCand) cand_eval2_lane(sl[c], rr[c], true, n0 + 1 < K, eps, w, st.bad_hi);
+                        if (w.hit) {
+                            const int n = n0 + (lane >> 5);
+                            sKey[n] = bid_to_key(w.bid);
+                            sObj[n] = sl[c].x;
+                            // owner at the start of the round == what the assignment phase reads (:401): the record of
+                            // obj is only rewritten by this round's winner of obj, after every bid has been made.
+                            sPrev[n] = rr[c].owner;
+                            sPst[n] = rr[c].ostart;
+                        }
+                        if (__popcll(w.hm) == 2) {  // wave-uniform (at most one lane per half): both lines decided
+                            st.edges += (unsigned long long)(w.len[0] + w.len[1]);
+                            st.bids += 2;
+                        } else {  // a line did not decide (its slot is queued for the scan pass), or the last pair of an
+                                  // odd K: its second half holds nobody
+                            const bool h0 = (unsigned)w.hm != 0u, h1 = (unsigned)(w.hm >> 32) != 0u;
+                            if (h0) {
+                                st.edges += (unsigned long long)w.len[0];
                                 st.bids += 1;
                             } else if (lane == 0) {
-                                sList[atomicAdd(&sMissCnt, 1)] = n;
+                                sList[atomicAdd(&sMissCnt, 1)] = n0;
+                            }
+                            if (n0 + 1 < K) {
+                                if (h1) {
+                                    st.edges += (unsigned long long)w.len[1];
+                                    st.bids += 1;
+                                } else if (lane == 0) {
+                                    sList[atomicAdd(&sMissCnt, 1)] = n0 + 1;
+                                }
                             }
                         }
                     }
+#ifdef MISSLAP_TAIL_STAMP_BLOCK
+                    bstamp.light(3);  // (a sweep's evaluation is billed to [8], not to the next sweep's "lines landed")
+#endif
                 }
                 __syncthreads();
                 bstamp(3);
