@@ -1,9 +1,8 @@
 // abi_batch_stream.hpp -- the one call path of the six "verdict per problem, stream-ordered" batch entry points:
 // misslap_solve_dense_batch_status (abi_dense_batch_status.hpp), misslap_solve_dense_batch_outside
 // (abi_dense_batch_status.hpp), misslap_solve_sparse_batch_status (abi_sparse_batch_status.hpp),
-// misslap_solve_sparse_batch_outside (abi_sparse_batch_status.hpp), misslap_solve_ell_batch (abi_ell_batch.hpp) and
-// misslap_solve_ell_batch_outside (abi_ell_batch_outside.hpp).  An entry point checks its own
-// arguments, describes the call in a BatchStreamCall and supplies three steps; batch_stream_call runs them in either of
+// misslap_solve_sparse_batch_outside (abi_sparse_batch_status.hpp), misslap_solve_ell_batch and
+// misslap_solve_ell_batch_outside (abi_ell_batch.hpp).  An entry point checks its own arguments, describes the call in a BatchStreamCall and supplies three steps; batch_stream_call runs them in either of
 // the two modes of include/misslap.h:
 //   with a workspace   every array is on the device: the launches go onto the caller's stream, nothing is allocated,
 //                      copied or waited for;

@@ -1,17 +1,24 @@
 // abi_ell_batch.hpp -- C ABI: the batch solve from padded candidate lists, cols / vals of shape (B, N, K), with a verdict
-// per problem and in stream order (misslap_solve_ell_batch, misslap_ell_batch_workspace_bytes; include/misslap.h).  The
-// two modes of the call are batch_stream_call's (abi_batch_stream.hpp); the kernels are in kernels_ell_batch.hpp, the
-// guard is the third source of k_matching_batch (kernels_matching_batch.hpp).  The verdict is formed in
-// k_ell_batch_solve, so nothing is read back between the launches.  What the call shares with
-// misslap_solve_ell_batch_outside (abi_ell_batch_outside.hpp) is here too: the argument checks, the dispatch, EllCall
-// and the uploads.
+// per problem and in stream order (include/misslap.h):
+//   misslap_solve_ell_batch, misslap_ell_batch_workspace_bytes
+//   misslap_solve_ell_batch_outside, misslap_ell_batch_outside_workspace_bytes    ... with an outside option per row
+// Both calls are described by one EllCall, filled by ell_describe, and enqueued by ell_enqueue: the check pass, the guard
+// (the plain mode only; the third source of k_matching_batch, kernels_matching_batch.hpp) and the solve, whose kernels
+// are in kernels_ell_batch.hpp.  The verdict is formed in the solve kernel, so nothing is read back between the
+// launches; the two modes of a call are batch_stream_call's (abi_batch_stream.hpp).
 // (part of the single translation unit misslap.hip; included in the order given there, after abi_matching_batch.hpp)
 #pragma once
 
 namespace {
-// The workspace of one call: the check records and the guard's cardinalities.
+// The workspace of a plain call: the check records and the guard's cardinalities.
 inline BatchCarve ell_carve(int64_t B, bool guard) {
     return batch_carve({sizeof(EllBatchCheck) * (size_t)B, guard ? sizeof(int) * (size_t)B : 0});
+}
+
+// The workspace of an outside call: the check records, and with starting prices the staged [p0[:m_b], zeros(n_b)] of
+// every problem at a leading dimension of Mmax + N.
+inline BatchCarve ell_outside_carve(int64_t B, int64_t N, int64_t Mmax, bool has_prices) {
+    return batch_carve({sizeof(EllBatchCheck) * (size_t)B, has_prices ? sizeof(double) * (size_t)B * (size_t)(Mmax + N) : 0});
 }
 
 // B, N and K of a call: 0, or the reason they are not taken
@@ -43,18 +50,53 @@ auto ell_dispatch(int32_t cols_int64, int32_t mat_dtype, F &&f) {
     return mat_dtype == MISSLAP_DTYPE_F32 ? f(int{}, float{}) : f(int{}, double{});
 }
 
+// One ELL call.  Every pointer is a device pointer by the time the call is enqueued.
 struct EllCall {
     int64_t B, N, K, Mmax, prices_ld;
     const void *d_cols, *d_vals;
     int32_t cols_int64;
     const int32_t *d_rows;
-    const double *d_p0;
+    const double *d_p0, *d_outside;  // d_outside: the outside mode only
+    int64_t outside_ld;
     int32_t fast;
-    bool guard;
+    bool guard;  // (the outside mode: never)
 };
 
-// Without a workspace and with host inputs: c's cols, vals, rows and starting prices, which the entry point set to the
-// caller's arrays, replaced by copies on the device.
+// What both entry points put into the call and its description once their checks have passed.  The outside call adds
+// its values, its second price array and its own carve.
+void ell_describe(EllCall &c, BatchStreamCall &k, int64_t B, int64_t N, int64_t K, const void *cols, int32_t cols_int64,
+                  const void *vals, const int32_t *rows, int32_t fast, const double *prices_in, int64_t prices_ld,
+                  void *stream, void *workspace, int64_t workspace_bytes, int64_t Mmax, int32_t *sol, double *prices_out,
+                  int32_t out_on_device, int32_t *status, int32_t *matching_size, misslap_dense_batch_meta *meta,
+                  misslap_dense_batch_info *info) {
+    c.B = B;
+    c.N = N;
+    c.K = K;
+    c.Mmax = Mmax;
+    c.prices_ld = prices_in ? prices_ld : 0;
+    c.cols_int64 = cols_int64 ? 1 : 0;
+    c.fast = fast;
+    c.d_cols = cols;
+    c.d_vals = vals;
+    c.d_rows = rows;
+    c.d_p0 = prices_in;
+    k.B = B;
+    k.out.sol = sol;
+    k.out.sol_cells = (size_t)B * (size_t)N;
+    k.out.status = status;
+    k.out.matching_size = matching_size;
+    k.out.prices = prices_out;
+    k.out.prices_cells = (size_t)B * (size_t)Mmax;
+    k.out.meta = meta;
+    k.out.info = info;
+    k.out_on_device = out_on_device;
+    k.stream = stream;
+    k.workspace = workspace;
+    k.workspace_bytes = workspace_bytes;
+}
+
+// Without a workspace and with host inputs: c's cols, vals, rows, starting prices and outside values, which the entry
+// point set to the caller's arrays, replaced by copies on the device.
 int ell_upload(DevScratch &tmp, hipStream_t st, const misslap_options &opt, EllCall &c) {
     const size_t slots = (size_t)c.B * (size_t)c.N * (size_t)c.K;
     const char *dc = nullptr, *dv = nullptr;
@@ -66,25 +108,38 @@ int ell_upload(DevScratch &tmp, hipStream_t st, const misslap_options &opt, EllC
         return rc;
     c.d_cols = dc;
     c.d_vals = dv;
-    return MISSLAP_OK;
+    if (!c.d_outside) return MISSLAP_OK;
+    return upload(tmp, &c.d_outside, c.d_outside, c.outside_ld ? (size_t)c.B * (size_t)c.outside_ld : (size_t)c.B, st);
 }
 
-// The three launches of a call on st: the check pass, the guard, the solve with its verdict.  Every pointer is a device
-// pointer.
-int ell_batch_enqueue(hipStream_t st, const misslap_options &opt, const EllCall &c, void *ws, const BatchStreamOut &d) {
-    const BatchCarve carve = ell_carve(c.B, c.guard);
+// The launches of a call on st: the check pass, in the plain mode the guard, the solve with its verdict.
+template <bool Out>
+int ell_enqueue(hipStream_t st, const misslap_options &opt, const EllCall &c, void *ws, const BatchStreamOut &d) {
+    const BatchCarve carve = Out ? ell_outside_carve(c.B, c.N, c.Mmax, c.d_p0 != nullptr) : ell_carve(c.B, c.guard);
     EllBatchCheck *d_chk = carve.at<EllBatchCheck>(ws, 0);
-    int *d_card = c.guard ? carve.at<int>(ws, 1) : nullptr;
+    int *d_card = !Out && c.guard ? carve.at<int>(ws, 1) : nullptr;
+    double *d_aug = Out && c.d_p0 ? carve.at<double>(ws, 1) : nullptr;
+    const long long aug_ld = (long long)(c.Mmax + c.N);
 
+    EllCheckArgs k{};
+    k.cols = c.d_cols;
+    k.vals = c.d_vals;
+    k.N = c.N;
+    k.K = c.K;
+    k.rows = c.d_rows;
+    k.p0 = c.d_p0;
+    k.p0_ld = c.prices_ld;
+    k.out = d_chk;
+    k.outside = c.d_outside;
+    k.outside_ld = c.outside_ld;
+    k.aug = d_aug;
+    k.aug_ld = aug_ld;
+    k.Ms = (int)c.Mmax;
     ell_dispatch(c.cols_int64, opt.mat_dtype, [&](auto i, auto v) {
-        using I = decltype(i);
-        using V = decltype(v);
-        hipLaunchKernelGGL((k_ell_batch_check<I, V>), dim3((unsigned)c.B), dim3(256), 0, st,
-                           static_cast<const I *>(c.d_cols), static_cast<const V *>(c.d_vals), (long long)c.N,
-                           (long long)c.K, c.d_rows, c.d_p0, (long long)c.prices_ld, d_chk);
+        hipLaunchKernelGGL((k_ell_batch_check<decltype(i), decltype(v), Out>), dim3((unsigned)c.B), dim3(256), 0, st, k);
     });
     HIP_TRY(hipGetLastError());
-    if (c.guard) {  // every problem the check pass found clean, on the device (no row starts in the carve)
+    if (d_card) {  // every problem the check pass found clean, on the device (no row starts in the carve)
         MatchBatchArgs g{};
         g.mat = c.d_cols;
         g.N = c.N;
@@ -102,19 +157,35 @@ int ell_batch_enqueue(hipStream_t st, const misslap_options &opt, const EllCall 
                                st, g);
         HIP_TRY(hipGetLastError());
     }
-    EllBatchArgs a{};
-    a.cols = c.d_cols;
-    a.vals = c.d_vals;
-    a.N = c.N;
-    a.K = c.K;
-    a.chk = d_chk;
-    a.card = d_card;
-    a.fast = c.fast ? 1 : 0;
-    a.status = d.status;
-    a.matching_size = d.matching_size;
+    EllBatchArgs e{};
+    e.cols = c.d_cols;
+    e.vals = c.d_vals;
+    e.N = c.N;
+    e.K = c.K;
+    e.chk = d_chk;
+    e.card = d_card;
+    e.fast = c.fast ? 1 : 0;
+    e.status = d.status;
+    e.matching_size = d.matching_size;
     return ell_dispatch(c.cols_int64, opt.mat_dtype, [&](auto i, auto v) {
-        return batch_solve_launch(k_ell_batch_solve<decltype(i), decltype(v)>, a, a.s, opt, c.B, c.N, c.Mmax, d.sol, c.N,
-                                  d.prices, c.Mmax, c.d_p0, c.prices_ld, d.meta, d.info, st);
+        if constexpr (Out) {
+            EllOutsideArgs a{};
+            a.e = e;
+            a.outside = c.d_outside;
+            a.outside_ld = c.outside_ld;
+            a.prices = d.prices;
+            a.outside_prices = d.outside_prices;
+            a.Mmax = (int)c.Mmax;
+            a.p0_ld = c.prices_ld;
+            // (the carve is N x (Mmax + N).  No prices array for batch_solve: k_ell_outside_solve writes the real
+            // columns itself.)
+            return batch_solve_launch(k_ell_outside_solve<decltype(i), decltype(v)>, a, a.e.s, opt, c.B, c.N,
+                                      c.Mmax + c.N, d.sol, c.N, nullptr, 0, d_aug, aug_ld, d.meta, d.info, st);
+        } else {
+            EllBatchArgs a = e;
+            return batch_solve_launch(k_ell_batch_solve<decltype(i), decltype(v)>, a, a.s, opt, c.B, c.N, c.Mmax, d.sol,
+                                      c.N, d.prices, c.Mmax, c.d_p0, c.prices_ld, d.meta, d.info, st);
+        }
     });
 }
 }  // namespace
@@ -124,6 +195,12 @@ MISSLAP_API int64_t misslap_ell_batch_workspace_bytes(int64_t B, int64_t N, int6
     (void)has_prices;
     if (ell_batch_dims(B, N, K)) return -1;
     return (int64_t)ell_carve(B, cardinality_check != 0).total;
+}
+
+MISSLAP_API int64_t misslap_ell_batch_outside_workspace_bytes(int64_t B, int64_t N, int64_t K, int64_t Mmax,
+                                                              int32_t has_prices) {
+    if (ell_batch_dims(B, N, K) || Mmax < 1 || Mmax > kSparseBatchMaxDim) return -1;
+    return (int64_t)ell_outside_carve(B, N, Mmax, has_prices != 0).total;
 }
 
 MISSLAP_API int misslap_solve_ell_batch(int64_t B, int64_t N, int64_t K, const void *cols, int32_t cols_int64,
@@ -142,35 +219,48 @@ MISSLAP_API int misslap_solve_ell_batch(int64_t B, int64_t N, int64_t K, const v
     if (!cols || !vals || !sol || !status) return fail(MISSLAP_ERR_INVALID, "null cols / vals / sol / status");
     if (prices_in && prices_ld < 1) return fail(MISSLAP_ERR_INVALID, "prices_ld must be >= 1");
     EllCall c{};
-    c.B = B;
-    c.N = N;
-    c.K = K;
-    c.Mmax = Mmax;
-    c.prices_ld = prices_in ? prices_ld : 0;
-    c.cols_int64 = cols_int64 ? 1 : 0;
-    c.fast = fast;
+    ell_describe(c, k, B, N, K, cols, cols_int64, vals, rows, fast, prices_in, prices_ld, stream, workspace,
+                 workspace_bytes, Mmax, sol, prices_out, out_on_device, status, matching_size, meta, info);
     c.guard = cardinality_check != 0;
-    c.d_cols = cols;
-    c.d_vals = vals;
-    c.d_rows = rows;
-    c.d_p0 = prices_in;
-    k.B = B;
-    k.out.sol = sol;
-    k.out.sol_cells = (size_t)B * (size_t)N;
-    k.out.status = status;
-    k.out.matching_size = matching_size;
-    k.out.prices = prices_out;
-    k.out.prices_cells = (size_t)B * (size_t)Mmax;
-    k.out.meta = meta;
-    k.out.info = info;
-    k.out_on_device = out_on_device;
-    k.stream = stream;
-    k.workspace = workspace;
-    k.workspace_bytes = workspace_bytes;
     k.carve_total = ell_carve(B, c.guard).total;
     k.sizing = "misslap_ell_batch_workspace_bytes";
     return batch_stream_call(
         opt, k, batch_no_host_check,
         [&](DevScratch &tmp, hipStream_t st) { return opt.input_on_device ? MISSLAP_OK : ell_upload(tmp, st, opt, c); },
-        [&](hipStream_t st, void *ws, const BatchStreamOut &d) { return ell_batch_enqueue(st, opt, c, ws, d); });
+        [&](hipStream_t st, void *ws, const BatchStreamOut &d) { return ell_enqueue<false>(st, opt, c, ws, d); });
+}
+
+MISSLAP_API int misslap_solve_ell_batch_outside(int64_t B, int64_t N, int64_t K, const void *cols, int32_t cols_int64,
+                                                const void *vals, const int32_t *rows, int32_t fast,
+                                                const double *prices_in, int64_t prices_ld, const misslap_options *opt_in,
+                                                void *stream, void *workspace, int64_t workspace_bytes, int64_t Mmax,
+                                                const double *outside, int64_t outside_ld, int32_t *sol,
+                                                double *prices_out, double *outside_prices_out, int32_t out_on_device,
+                                                int32_t *status, int32_t *matching_size, misslap_dense_batch_meta *meta,
+                                                misslap_dense_batch_info *info) {
+    BatchStreamCall k;
+    k.t_start = now_ms();
+    misslap_options opt;
+    int rc = batch_options(opt_in, &opt, "misslap_solve_ell_batch_outside",
+                           "device, maximize, eps_start, max_iter, mat_dtype, input_on_device and input_stream", true);
+    if (rc || (rc = ell_batch_shape_checks("misslap_solve_ell_batch_outside", opt, B, N, K, Mmax))) return rc;
+    if (!cols || !vals || !sol || !status || !outside)
+        return fail(MISSLAP_ERR_INVALID, "null cols / vals / sol / status / outside");
+    if (outside_ld != 0 && outside_ld < N)
+        return fail(MISSLAP_ERR_INVALID, "outside_ld = %lld: 0 (one value per problem) or >= N = %lld",
+                    (long long)outside_ld, (long long)N);
+    if (prices_in && prices_ld < 1) return fail(MISSLAP_ERR_INVALID, "prices_ld must be >= 1");
+    EllCall c{};
+    ell_describe(c, k, B, N, K, cols, cols_int64, vals, rows, fast, prices_in, prices_ld, stream, workspace,
+                 workspace_bytes, Mmax, sol, prices_out, out_on_device, status, matching_size, meta, info);
+    c.d_outside = outside;
+    c.outside_ld = outside_ld;
+    k.out.outside_prices = outside_prices_out;
+    k.out.outside_cells = (size_t)B * (size_t)N;
+    k.carve_total = ell_outside_carve(B, N, Mmax, prices_in != nullptr).total;
+    k.sizing = "misslap_ell_batch_outside_workspace_bytes";
+    return batch_stream_call(
+        opt, k, batch_no_host_check,
+        [&](DevScratch &tmp, hipStream_t st) { return opt.input_on_device ? MISSLAP_OK : ell_upload(tmp, st, opt, c); },
+        [&](hipStream_t st, void *ws, const BatchStreamOut &d) { return ell_enqueue<true>(st, opt, c, ws, d); });
 }

@@ -12,7 +12,7 @@
 // kernels_sparse_batch.hpp through sparse_dispatch, which names the call's entry source.  The verdict is formed in the
 // solve kernel, so nothing is read back between the launches; the two modes of a call are batch_stream_call's
 // (abi_batch_stream.hpp).
-// (part of the single translation unit misslap.hip; included in the order given there, after abi_ell_batch_outside.hpp)
+// (part of the single translation unit misslap.hip; included in the order given there, after abi_ell_batch.hpp)
 #pragma once
 
 namespace {

@@ -25,7 +25,8 @@
 // After the round: terminate() (:308-309), and at the end of a phase eps *= theta or stop (:275-292), with the eCE test
 // of :443-485 at target eps = 1 / N.
 //
-// A row source (DenseBatchRows, SparseBatchRows) supplies what differs between the two layouts:
+// A row source supplies what differs between the layouts.  There are two: DenseBatchRows (kernels_dense_batch.hpp) and
+// the list row source ListBatchRows below, which SparseBatchRows and EllBatchRows name with their run accessors:
 //   bid(i, price, cb, obj)          the wavefront's reduced Top2 of row i, the winner's cost (all lanes) and its object
 //   ece_bad(i, j, price, tol, eps)  this lane's part of the eCE row test of row i assigned to object j
 //   gather(p2o, n, selv, nsel)      the objective's per-row gather into LDS (after the last barrier of the loop)
@@ -150,6 +151,185 @@ struct BatchOutside<true> {
     const double *O;
     int stride;
     __device__ __forceinline__ double value(int i) const { return O[i * stride]; }
+};
+
+// The list row source of batch_solve, for every layout whose row is a run of (column, value) entries in stored order:
+// the sparse batch's packed arrays and views, and the ELL batch's padded candidate lists.  A run accessor Acc states
+// what differs between them:
+//   start(i), len(i)     where row i's run begins (in the accessor's own index width) and how many slots it has
+//   col(g), value(g)     entry g's column and value, in their stored types; the value is widened where it is used
+//                        (dense_widen, exact), the column is compared in its own width and narrowed only once it is
+//                        known to be an entry, so an int64 column is never narrowed before it is tested
+//   kHoles               whether a negative column is a hole: skipped before anything is done with its column (it never
+//                        indexes price[]), and its value is never interpreted
+//   count()              the problem's entries, for the meta record
+// Everything else is here once: the stored order the reference's AuctionSolver walks (flat_j / val after
+// cumulative_idxs, auction_.pyx:33-48, :202-233), the tie key and the outside entry.
+//   BID      lane l holds the row's slots l, l + 64, ... (rows of any length), the tie key is the slot index:
+//            top2_wave_reduce keeps the reference's ">=" rule (the last stored maximum wins, :351) and counts a repeated
+//            maximum -- a duplicate (i, j) entry included -- into the second best as the sequential scan does (:353).
+//            Dropping holes keeps the order of the entries and the key is only ever compared, so the slot index serves
+//            as the stored index.
+//   eCE      choice_cost is the value at the LAST slot of row i whose column is p2o[i] (the loop of :462-467 overwrites
+//            it on every match), then every entry is tested against it (:475-485).
+//   get_obj  every entry whose column is p2o[i] is added, in row order and slot order (:508-521): a duplicate of the
+//            chosen entry counts once per copy.
+// Out: the row's virtual last entry (i, m + i) with the row's outside value.  Its tie key is len, above every slot, and
+// lane len & 63 takes it AFTER its own slots (slot len would be that lane's next one), so every lane still scans in
+// ascending stored order, the virtual entry wins ">=" ties as the last stored entry must, and the winner's lane is
+// r.g & 63 as before.  A row of len = 0 is a one-entry row: its second best is -inf and it bids +inf.  A chosen object
+// j >= m is that entry: nothing of the run is read for it.
+template <class Acc, bool Out>
+struct ListBatchRows {
+    using Col = typename Acc::Col;  // the column's stored width
+    Acc a;
+    int maximize;
+    int m;  // the real columns (read in the outside mode only)
+    BatchOutside<Out> out;
+
+    // the row in stored order, lane l at slots l, l + 64, ...; the tie key is the slot index
+    __device__ __forceinline__ Top2 bid(int i, const double *price, double &costbest, int &obj) const {
+        const int lane = lane_id();
+        const auto g0 = a.start(i);
+        const int len = a.len(i);
+        Top2 x;
+        x.v = -__builtin_huge_val();
+        x.w = -__builtin_huge_val();
+        x.g = -1;
+        double cb = 0.0;
+        int cj = 0;
+        for (int q = lane; q < len; q += kWave) {
+            const Col c = a.col(g0 + q);
+            const auto e = a.value(g0 + q);
+            if constexpr (Acc::kHoles)
+                if (c < 0) continue;
+            const double v = dense_widen(e);
+            const double cost = maximize ? v : v * -1.0;  // :236-237
+            const double vi = cost - price[(int)c];
+            // (top2_take, spelled out: through the helper the sparse instances number the running state's registers in
+            // another order, and here every solve instance is the code it was before the sources were folded)
+            if (vi >= x.v) {
+                x.w = x.v;
+                x.v = vi;
+                x.g = q;
+                cb = cost;
+                cj = (int)c;
+            } else if (vi > x.w) {
+                x.w = vi;
+            }
+        }
+        if constexpr (Out) {
+            if (lane == (len & (kWave - 1))) {
+                const double v = out.value(i);
+                const double cost = maximize ? v : v * -1.0;
+                const double vi = cost - price[m + i];
+                if (top2_take(x, vi, len)) {
+                    cb = cost;
+                    cj = m + i;
+                }
+            }
+        }
+        const Top2 r = top2_wave_reduce(x);
+        const int gl = r.g & (kWave - 1);  // the lane that holds slot r.g
+        costbest = readlane_f64(cb, gl);
+        obj = __builtin_amdgcn_readlane(cj, gl);
+        return r;
+    }
+
+    // eCE_satisfied (auction_.pyx:443-485) for row i: choice_cost from the last slot of column j (j >= 0: never a hole)
+    __device__ __forceinline__ bool ece_bad(int i, int j, const double *price, double tol, double eps) const {
+        const int lane = lane_id();
+        const auto g0 = a.start(i);
+        const int len = a.len(i);
+        int last = -1;  // :462-467
+        for (int q = lane; q < len; q += kWave)
+            if (a.col(g0 + q) == (Col)j) last = q;
+        last = wave_max_i32(last);
+        double vj;
+        if constexpr (Out) vj = j >= m ? out.value(i) : dense_widen(a.value(g0 + (last < 0 ? 0 : last)));  // (j < m: stored)
+        else vj = dense_widen(a.value(g0 + last));
+        const double choice_cost = maximize ? vj : vj * -1.0;
+        const double LHS = choice_cost - price[j] + tol;  // :475
+        bool bad = false;
+        if constexpr (Out) {
+            if (lane == 0) {
+                const double v = out.value(i);
+                const double cost = maximize ? v : v * -1.0;
+                if (LHS < (cost - price[m + i]) - eps) bad = true;
+            }
+        }
+        for (int q = lane; q < len; q += kWave) {
+            const Col c = a.col(g0 + q);
+            if constexpr (Acc::kHoles)
+                if (c < 0) continue;
+            const double v = dense_widen(a.value(g0 + q));
+            const double cost = maximize ? v : v * -1.0;
+            if (LHS < (cost - price[(int)c]) - eps) bad = true;  // :482
+        }
+        return bad;
+    }
+
+    // get_obj (:489-523) over EVERY entry of the chosen column: a wavefront per row gathers the row's one matching value;
+    // a row with several matches (a repeated column) is marked (nsel[i] > 1) and re-walked by the summing lane.
+    __device__ __forceinline__ void gather(const int *p2o, int n, double *selv, int *nsel) const {
+        const int lane = lane_id(), wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+        for (int i = wave; i < n; i += nw) {
+            const int j = p2o[i];
+            if (j < 0) continue;
+            if constexpr (Out) {
+                if (j >= m) {  // the row's outside entry: exactly one match
+                    if (lane == 0) {
+                        nsel[i] = 1;
+                        selv[i] = out.value(i);
+                    }
+                    continue;
+                }
+            }
+            const auto g0 = a.start(i);
+            const int len = a.len(i);
+            int cnt = 0, at = -1;
+            for (int q = lane; q < len; q += kWave)
+                if (a.col(g0 + q) == (Col)j) {
+                    ++cnt;
+                    at = q;
+                }
+            for (int off = 32; off >= 1; off >>= 1) cnt += __shfl_xor(cnt, off);
+            at = wave_max_i32(at);
+            if (lane == 0) {
+                nsel[i] = cnt;
+                selv[i] = dense_widen(a.value(g0 + at));
+            }
+        }
+    }
+
+    // a double sum in row order, within a row in slot order
+    __device__ __forceinline__ double objective(const int *p2o, int n, const double *selv, const int *nsel) const {
+        double obj = 0;
+        for (int i = 0; i < n; ++i) {
+            const int j = p2o[i];
+            if (j == -1) continue;
+            if (nsel[i] == 1) {
+                const double v = maximize ? selv[i] : selv[i] * -1.0;
+                if (maximize) obj += v;
+                else obj -= v;
+                continue;
+            }
+            const auto g0 = a.start(i);
+            const int len = a.len(i);
+            for (int q = 0; q < len; ++q)
+                if (a.col(g0 + q) == (Col)j) {
+                    const double e = dense_widen(a.value(g0 + q));
+                    const double v = maximize ? e : e * -1.0;
+                    if (maximize) obj += v;
+                    else obj -= v;
+                }
+        }
+        return obj;
+    }
+
+    // (m_: batch_solve's object count, in the outside mode m + n)
+    __device__ __forceinline__ int meta_cols(int m_) const { return m_; }
+    __device__ __forceinline__ int64_t meta_nnz() const { return a.count(); }
 };
 
 // The price outputs of an outside call (po: [M_ld] the real columns, oo: [N_ld] the outside objects, either may be null)

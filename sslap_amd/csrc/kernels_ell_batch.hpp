@@ -1,19 +1,15 @@
 // kernels_ell_batch.hpp -- many small sparse problems given as padded candidate lists (ELL), one workgroup per problem
-// for its whole solve (misslap_solve_ell_batch, include/misslap.h; the host side is abi_ell_batch.hpp, for the outside
-// mode abi_ell_batch_outside.hpp).
+// for its whole solve (misslap_solve_ell_batch, include/misslap.h; the host side of both modes is abi_ell_batch.hpp).
 //
-// The round loop is batch_solve (kernels_batch_solve.hpp); this file has the check pass, the ELL row source and the
-// solve with its verdict.  The input is what a top-k, a gating step or a nearest-neighbour search leaves on the device:
-// cols[B][N][K] (int32 or int64: the kernels' I) and vals[B][N][K] (double or float: V, widened where it is used by
-// dense_widen, exact).  Problem b is rows 0 .. n_b - 1 of its slice; slot (i, k) is an entry iff cols[b][i][k] >= 0, a
+// The round loop is batch_solve and the row source is its list row source (ListBatchRows, kernels_batch_solve.hpp);
+// this file has the check pass, the runs that the row source walks (EllRuns) and the solve with its verdict.  The input
+// is what a top-k, a gating step or a nearest-neighbour search leaves on the device: cols[B][N][K] (int32 or int64: the
+// kernels' I) and vals[B][N][K] (double or float: V, widened where it is used by dense_widen, exact).  Problem b is rows 0 .. n_b - 1 of its slice; slot (i, k) is an entry iff cols[b][i][k] >= 0, a
 // negative column is a hole in any position and the value stored in a hole is never interpreted.  The result is that of
 // the packed problem with the holes dropped (rows in order, within a row in slot order) under
 // from_sparse(loc_b, val_b, size=(m_b, n_b)): dropping holes keeps the order of the entries, and the bid's tie key is
-// only ever compared (top2_wave_reduce), so the slot index k serves as the stored index.
-//   BID      one wavefront per unassigned list position; lane l holds slots l, l + 64, ... of the row, both loads
-//            unit-stride.  A hole is skipped before anything is done with its column: it never indexes price[].
-//   eCE      choice_cost is the value at the LAST slot of row i whose column is p2o[i]; every entry is tested against it.
-//   get_obj  every entry whose column is p2o[i] is added, in row order and slot order.
+// only ever compared (top2_wave_reduce), so the slot index k serves as the stored index.  In the bid lane l holds slots
+// l, l + 64, ... of the row, so both loads are unit-stride.
 //
 // The outside mode (misslap_solve_ell_batch_outside; the <.., true> instances below): row i of problem b also holds one
 // virtual entry (i, m_b + i), stored LAST in its row, whose value is the row's outside value -- a private object that
@@ -50,19 +46,36 @@ struct EllBatchArgs {
     int *matching_size;        // [B] or null
 };
 
+// What the check pass takes.  The plain mode leaves the outside fields unread.
+struct EllCheckArgs {
+    const void *cols, *vals;
+    long long N, K;
+    const int *rows;
+    const double *p0;
+    long long p0_ld;
+    EllBatchCheck *out;
+    const double *outside;  // [B] (outside_ld == 0) or [B][outside_ld]
+    long long outside_ld;
+    double *aug;            // [B][aug_ld] or null (no starting prices)
+    long long aug_ld;       // Mmax + N
+    int Ms;                 // Mmax: the bound on the real columns
+};
+
 // Check pass, one workgroup per problem, a wavefront per row: the entries per row and in all, the first empty row, the
 // largest column (compared in the index's own width: an int64 column at or above 2^31 is too large, not wrapped), NaN /
 // infinity and C = max |v| among the entries only, and the starting prices of the problem's columns.
-// Out (the outside mode): the outside value of every row < n_b counts as an entry's value does (ov: outside[b] with
-// ov_ld == 0, else outside[b * ov_ld + i]), no row is empty, and with starting prices the problem's augmented starting
-// prices [p0[:m_b], zeros(n_b)] are staged at aug[b * aug_ld ..] (aug_ld = Ms + N) for batch_solve to load -- only where
-// the real columns fit both Ms and p0_ld, i.e. where the verdict can still be 0 (m_b + n_b <= aug_ld then).
+// Out (the outside mode): the outside value of every row < n_b counts as an entry's value does (outside[b] with
+// outside_ld == 0, else outside[b * outside_ld + i]), no row is empty, and with starting prices the problem's augmented
+// starting prices [p0[:m_b], zeros(n_b)] are staged at aug[b * aug_ld ..] (aug_ld = Ms + N) for batch_solve to load --
+// only where the real columns fit both Ms and p0_ld, i.e. where the verdict can still be 0 (m_b + n_b <= aug_ld then).
 template <class I, class V, bool Out>
-__device__ __forceinline__ void ell_batch_check(const I *cols, const V *vals, long long N, long long K, const int *rows,
-                                                const double *p0, long long p0_ld, EllBatchCheck *out, const double *ov,
-                                                long long ov_ld, double *aug, long long aug_ld, int Ms) {
+__global__ __launch_bounds__(256) void k_ell_batch_check(EllCheckArgs a) {
+    const I *cols = static_cast<const I *>(a.cols);
+    const V *vals = static_cast<const V *>(a.vals);
+    const long long N = a.N, K = a.K;
+    const double *p0 = a.p0;
     const int b = blockIdx.x, lane = lane_id(), wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    int n = rows ? rows[b] : (int)N;
+    int n = a.rows ? a.rows[b] : (int)N;
     if (n < 1 || n > N) n = 0;
     const size_t base = (size_t)b * (size_t)N * (size_t)K;
     __shared__ unsigned long long s_cnt, s_abs;
@@ -95,9 +108,9 @@ __device__ __forceinline__ void ell_batch_check(const I *cols, const V *vals, lo
         for (int off = 32; off >= 1; off >>= 1) rc += __shfl_xor(rc, off);
         if constexpr (Out) {
             if (lane == 0) {
+                const size_t at = a.outside_ld ? (size_t)b * (size_t)a.outside_ld + (size_t)r : (size_t)b;
                 const unsigned long long bits =
-                    (unsigned long long)__double_as_longlong(ov[ov_ld ? (size_t)b * (size_t)ov_ld + (size_t)r : (size_t)b]) &
-                    0x7fffffffffffffffull;
+                    (unsigned long long)__double_as_longlong(a.outside[at]) & 0x7fffffffffffffffull;
                 am = bits > am ? bits : am;
                 bad |= bits >= 0x7ff0000000000000ull;
             }
@@ -113,13 +126,13 @@ __device__ __forceinline__ void ell_batch_check(const I *cols, const V *vals, lo
     __syncthreads();
     if (p0 && s_maxc >= 0) {
         const long long m = (long long)s_maxc + 1;
-        batch_check_prices(p0 + (size_t)b * (size_t)p0_ld, (int)(m < p0_ld ? m : p0_ld), &s_badp);
+        batch_check_prices(p0 + (size_t)b * (size_t)a.p0_ld, (int)(m < a.p0_ld ? m : a.p0_ld), &s_badp);
     }
     if constexpr (Out) {
         const long long m = (long long)s_maxc + 1;
-        if (p0 && m <= (long long)Ms && m <= p0_ld) {
-            const double *src = p0 + (size_t)b * (size_t)p0_ld;
-            double *dst = aug + (size_t)b * (size_t)aug_ld;
+        if (p0 && m <= (long long)a.Ms && m <= a.p0_ld) {
+            const double *src = p0 + (size_t)b * (size_t)a.p0_ld;
+            double *dst = a.aug + (size_t)b * (size_t)a.aug_ld;
             for (int j = threadIdx.x; j < (int)m + n; j += blockDim.x) dst[j] = j < (int)m ? src[j] : 0.0;
         }
     }
@@ -134,182 +147,32 @@ __device__ __forceinline__ void ell_batch_check(const I *cols, const V *vals, lo
         r.nonfinite = s_bad;
         r.bad_price = s_badp;
         r.pad = 0;
-        out[b] = r;
+        a.out[b] = r;
     }
 }
 
+// The runs of the ELL row source (ListBatchRows, kernels_batch_solve.hpp): problem b's slices C / A (at
+// (size_t)b * N * K, formed in 64 bits), row i the K slots from i * K of them (an int: the host caps N * K at
+// INT_MAX - 128), a negative column a hole.  Every valid column is below the carve's Ms once the verdict is 0, so an
+// int64 column narrows safely once it is known to be an entry.
 template <class I, class V>
-__global__ __launch_bounds__(256) void k_ell_batch_check(const I *cols, const V *vals, long long N, long long K,
-                                                         const int *rows, const double *p0, long long p0_ld,
-                                                         EllBatchCheck *out) {
-    ell_batch_check<I, V, false>(cols, vals, N, K, rows, p0, p0_ld, out, nullptr, 0, nullptr, 0, 0);
-}
-
-struct EllOutsideCheckArgs {
-    const void *cols, *vals;
-    long long N, K;
-    const int *rows;
-    const double *p0;
-    long long p0_ld;
-    EllBatchCheck *out;
-    const double *outside;  // [B] (outside_ld == 0) or [B][outside_ld]
-    long long outside_ld;
-    double *aug;            // [B][aug_ld] or null (no starting prices)
-    long long aug_ld;       // Mmax + N
-    int Ms;                 // Mmax: the bound on the real columns
-};
-
-template <class I, class V>
-__global__ __launch_bounds__(256) void k_ell_outside_check(EllOutsideCheckArgs a) {
-    ell_batch_check<I, V, true>(static_cast<const I *>(a.cols), static_cast<const V *>(a.vals), a.N, a.K, a.rows, a.p0,
-                                a.p0_ld, a.out, a.outside, a.outside_ld, a.aug, a.aug_ld, a.Ms);
-}
-
-// The ELL row source of batch_solve: problem b's slices C / A (at (size_t)b * N * K, formed in 64 bits), row i at slot
-// i * K of them (an int: the host caps N * K at INT_MAX - 128).  Every valid column is below the carve's Ms once the
-// verdict is 0, so an int64 column narrows safely.
-// Out: the row's virtual last entry (i, m + i) with the row's outside value.  Its tie key is K, above every slot, and
-// lane K & 63 takes it AFTER its own slots (slot K would be that lane's next one), so every lane still scans in
-// ascending stored order and the winner's lane is r.g & 63 as before.  A chosen object j >= m is that entry.
-template <class I, class V, bool Out = false>
-struct EllBatchRows {
+struct EllRuns {
+    using Col = I;
+    static constexpr bool kHoles = true;
     const I *C;
     const V *A;
-    int K, maximize;
-    unsigned long long nvalid;
-    int m;  // the real columns (read in the outside mode only)
-    BatchOutside<Out> out;
+    int K;
+    unsigned long long nvalid;  // the entries of the problem, in the outside mode with its n virtual ones
 
-    // the row in slot order, lane l at slots l, l + 64, ...; the tie key is the slot index
-    __device__ __forceinline__ Top2 bid(int i, const double *price, double &costbest, int &obj) const {
-        const int lane = lane_id();
-        const int g0 = i * K;
-        Top2 x;
-        x.v = -__builtin_huge_val();
-        x.w = -__builtin_huge_val();
-        x.g = -1;
-        double cb = 0.0;
-        int cj = 0;
-        for (int q = lane; q < K; q += kWave) {
-            const I c = C[g0 + q];
-            const V e = A[g0 + q];
-            if (c < 0) continue;  // a hole: its column never reaches price[], its value is not interpreted
-            const double v = dense_widen(e);
-            const double cost = maximize ? v : v * -1.0;  // :236-237
-            const double vi = cost - price[(int)c];
-            if (top2_take(x, vi, q)) {
-                cb = cost;
-                cj = (int)c;
-            }
-        }
-        if constexpr (Out) {
-            if (lane == (K & (kWave - 1))) {
-                const double v = out.value(i);
-                const double cost = maximize ? v : v * -1.0;
-                const double vi = cost - price[m + i];
-                if (top2_take(x, vi, K)) {
-                    cb = cost;
-                    cj = m + i;
-                }
-            }
-        }
-        const Top2 r = top2_wave_reduce(x);
-        const int gl = r.g & (kWave - 1);  // the lane that holds slot r.g
-        costbest = readlane_f64(cb, gl);
-        obj = __builtin_amdgcn_readlane(cj, gl);
-        return r;
-    }
-
-    // eCE_satisfied (auction_.pyx:443-485) for row i: choice_cost from the last slot of column j (j >= 0: never a hole)
-    __device__ __forceinline__ bool ece_bad(int i, int j, const double *price, double tol, double eps) const {
-        const int lane = lane_id();
-        const int g0 = i * K;
-        int last = -1;  // :462-467
-        for (int q = lane; q < K; q += kWave)
-            if (C[g0 + q] == (I)j) last = q;
-        last = wave_max_i32(last);
-        double vj;
-        if constexpr (Out) vj = j >= m ? out.value(i) : dense_widen(A[g0 + (last < 0 ? 0 : last)]);
-        else vj = dense_widen(A[g0 + last]);
-        const double choice_cost = maximize ? vj : vj * -1.0;
-        const double LHS = choice_cost - price[j] + tol;  // :475
-        bool bad = false;
-        if constexpr (Out) {
-            if (lane == 0) {
-                const double v = out.value(i);
-                const double cost = maximize ? v : v * -1.0;
-                if (LHS < (cost - price[m + i]) - eps) bad = true;
-            }
-        }
-        for (int q = lane; q < K; q += kWave) {
-            const I c = C[g0 + q];
-            if (c < 0) continue;
-            const double v = dense_widen(A[g0 + q]);
-            const double cost = maximize ? v : v * -1.0;
-            if (LHS < (cost - price[(int)c]) - eps) bad = true;  // :482
-        }
-        return bad;
-    }
-
-    // get_obj (:489-523) over EVERY entry of the chosen column: a wavefront per row gathers the row's one matching value;
-    // a row with several matches (a repeated column) is marked (nsel[i] > 1) and re-walked by the summing lane.
-    __device__ __forceinline__ void gather(const int *p2o, int n, double *selv, int *nsel) const {
-        const int lane = lane_id(), wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-        for (int i = wave; i < n; i += nw) {
-            const int j = p2o[i];
-            if (j < 0) continue;
-            if constexpr (Out) {
-                if (j >= m) {  // the row's outside entry: exactly one match
-                    if (lane == 0) {
-                        nsel[i] = 1;
-                        selv[i] = out.value(i);
-                    }
-                    continue;
-                }
-            }
-            const int g0 = i * K;
-            int cnt = 0, at = -1;
-            for (int q = lane; q < K; q += kWave)
-                if (C[g0 + q] == (I)j) {
-                    ++cnt;
-                    at = q;
-                }
-            for (int off = 32; off >= 1; off >>= 1) cnt += __shfl_xor(cnt, off);
-            at = wave_max_i32(at);
-            if (lane == 0) {
-                nsel[i] = cnt;
-                selv[i] = dense_widen(A[g0 + at]);
-            }
-        }
-    }
-
-    // a double sum in row order, within a row in slot order
-    __device__ __forceinline__ double objective(const int *p2o, int n, const double *selv, const int *nsel) const {
-        double obj = 0;
-        for (int i = 0; i < n; ++i) {
-            const int j = p2o[i];
-            if (j == -1) continue;
-            if (nsel[i] == 1) {
-                const double v = maximize ? selv[i] : selv[i] * -1.0;
-                if (maximize) obj += v;
-                else obj -= v;
-                continue;
-            }
-            const int g0 = i * K;
-            for (int q = 0; q < K; ++q)
-                if (C[g0 + q] == (I)j) {
-                    const double e = dense_widen(A[g0 + q]);
-                    const double v = maximize ? e : e * -1.0;
-                    if (maximize) obj += v;
-                    else obj -= v;
-                }
-        }
-        return obj;
-    }
-
-    __device__ __forceinline__ int meta_cols(int m) const { return m; }
-    __device__ __forceinline__ int64_t meta_nnz() const { return (int64_t)nvalid; }
+    __device__ __forceinline__ int start(int i) const { return i * K; }
+    __device__ __forceinline__ int len(int) const { return K; }
+    __device__ __forceinline__ I col(int g) const { return C[g]; }
+    __device__ __forceinline__ V value(int g) const { return A[g]; }
+    __device__ __forceinline__ int64_t count() const { return (int64_t)nvalid; }
 };
+
+template <class I, class V, bool Out = false>
+using EllBatchRows = ListBatchRows<EllRuns<I, V>, Out>;
 
 // The ELL checks of a verdict ahead of the guard and the starting prices, in their order (include/misslap.h);
 // batch_verdict adds those two.
@@ -345,7 +208,7 @@ __global__ __launch_bounds__(1024) void k_ell_batch_solve(EllBatchArgs a) {
     // (the two slice pointers as opaque scalars: left to itself the compiler also keeps base * sizeof(I) and
     // base * sizeof(V) alive for the objective's scalar re-walk, and those four registers are the ones that spill)
     asm volatile("" : "+s"(C), "+s"(A));
-    const EllBatchRows<I, V> rows{C, A, (int)a.K, bs.maximize, ck.nvalid, ck.max_col + 1, {}};
+    const EllBatchRows<I, V> rows{{C, A, (int)a.K, ck.nvalid}, bs.maximize, ck.max_col + 1, {}};
     batch_solve(bs, rows, ck.n, ck.max_col + 1, ck.absmax_bits);
 }
 
@@ -387,7 +250,7 @@ __global__ __launch_bounds__(1024) void k_ell_outside_solve(EllOutsideArgs a) {
     asm volatile("" : "+s"(C), "+s"(A));
     const int n = ck.n, m = ck.max_col + 1;
     const double *O = a.outside + (a.outside_ld ? (size_t)b * (size_t)a.outside_ld : (size_t)b);
-    const EllBatchRows<I, V, true> rows{C, A, (int)a.e.K, bs.maximize, ck.nvalid + (unsigned long long)n, m,
+    const EllBatchRows<I, V, true> rows{{C, A, (int)a.e.K, ck.nvalid + (unsigned long long)n}, bs.maximize, m,
                                         {O, a.outside_ld ? 1 : 0}};
     batch_solve(bs, rows, n, m + n, ck.absmax_bits);
     batch_outside_outputs(s_raw, a.e.s, b, n, m, a.Mmax, N, po, oo, tid, T);

@@ -24,19 +24,10 @@
 //              monotone); every index written is clamped to the block.  sparse_row_starts is the one place that knows.
 // Apart from that every verdict, output and record is the same for both sources, bit for bit.
 //
-// The round loop is batch_solve (kernels_batch_solve.hpp); this file has the check pass and the sparse row source.
-// What differs from the dense source is where a row comes from.  Problem b is the entries offsets[b] .. offsets[b + 1]
-// of the caller's loc / val, in their STORED order -- the order the reference's AuctionSolver walks them (flat_j / val
-// after cumulative_idxs, auction_.pyx:33-48, :202-233) -- and row i of it is the run row_start[i] .. row_start[i + 1]
-// that the check pass found.  So:
-//   BID      one wavefront per unassigned list position; lane l holds the row's stored indices l, l + 64, ... (rows of
-//            any length), the tie key is the stored index: top2_wave_reduce keeps the reference's ">=" rule (the last
-//            stored maximum wins, :351) and counts a repeated maximum -- a duplicate (i, j) entry included -- into the
-//            second best as the sequential scan does (:353).  The object is col[start + g].
-//   eCE      choice_cost is the value at the LAST stored entry of row i whose column is p2o[i] (the loop of :462-467
-//            overwrites it on every match), then every stored entry is tested against it (:475-485).
-//   get_obj  every stored entry whose column is p2o[i] is added, in row order and stored order (:508-521): a
-//            duplicate of the chosen entry counts once per copy.
+// The round loop is batch_solve and the row source is its list row source (ListBatchRows, kernels_batch_solve.hpp, which
+// has the rules of the bid, the eCE test and the objective); this file has the check pass and the runs that the row
+// source walks (SparseRuns).  Problem b is the entries offsets[b] .. offsets[b + 1] of the caller's loc / val, in their
+// STORED order, and row i of it is the run row_start[i] .. row_start[i + 1] that the check pass found.
 //
 // The outside mode (misslap_solve_sparse_batch_outside; the Out instances below): row i of problem b also holds one
 // virtual entry (i, m_b + i), stored LAST in its row, whose value is the row's outside value -- a private object that
@@ -271,160 +262,28 @@ __global__ __launch_bounds__(256) void k_sparse_batch_check(SparseCheckArgs<Src>
     sparse_batch_check<Src, Out>(a, sparse_row_starts<Src, Out>(a.row_start, s, b, a.Nmax), hi);
 }
 
-// The sparse row source of batch_solve: problem b's entries from global index s, row i at s + rs[i] .. s + rs[i + 1].
-// Out: the row's virtual last entry (i, m + i) with the row's outside value.  Its tie key is len, above every stored
-// index, and lane len & 63 takes it AFTER its own stored indices (index len would be that lane's next one), so every
-// lane still scans in ascending stored order, the virtual entry wins ">=" ties as the last stored entry must, and the
-// winner's lane is r.g & 63 as before.  A row of len = 0 is a one-entry row: its second best is -inf and it bids +inf.
-// A chosen object j >= m is that entry: nothing of loc / val is read for it.
-template <class Src, bool Out>
-struct SparseBatchRows {
+// The runs of the sparse row source (ListBatchRows, kernels_batch_solve.hpp): problem b's entries from global index s,
+// row i the run s + rs[i] .. s + rs[i + 1] that the check pass found, every stored entry an entry (no holes).  It
+// serves both entry sources.  n: the rows whose virtual entries the outside mode counts into the meta record, else 0.
+template <class Src>
+struct SparseRuns {
+    using Col = int;
+    static constexpr bool kHoles = false;
     Src w;
     const long long *offsets;
     long long s;
     const int *rs;
-    int maximize;
-    int m, n;  // the real columns and the rows (read in the outside mode only)
-    BatchOutside<Out> out;
+    int n;
 
-    // the row in stored order, lane l at stored indices l, l + 64, ...; the tie key is the stored index
-    __device__ __forceinline__ Top2 bid(int i, const double *price, double &costbest, int &obj) const {
-        const int lane = lane_id();
-        const long long g0 = s + rs[i];
-        const int len = rs[i + 1] - rs[i];
-        Top2 x;
-        x.v = -__builtin_huge_val();
-        x.w = -__builtin_huge_val();
-        x.g = -1;
-        double cb = 0.0;
-        int cj = 0;
-        for (int q = lane; q < len; q += kWave) {
-            const int c = w.col(g0 + q);
-            const double v = w.value(g0 + q);
-            const double cost = maximize ? v : v * -1.0;  // :236-237
-            const double vi = cost - price[c];
-            if (vi >= x.v) {  // :351 (the first entry is always taken: vi >= -inf for every non-NaN vi)
-                x.w = x.v;
-                x.v = vi;
-                x.g = q;
-                cb = cost;
-                cj = c;
-            } else if (vi > x.w) {
-                x.w = vi;
-            }
-        }
-        if constexpr (Out) {
-            if (lane == (len & (kWave - 1))) {
-                const double v = out.value(i);
-                const double cost = maximize ? v : v * -1.0;
-                const double vi = cost - price[m + i];
-                if (top2_take(x, vi, len)) {
-                    cb = cost;
-                    cj = m + i;
-                }
-            }
-        }
-        const Top2 r = top2_wave_reduce(x);
-        const int gl = r.g & (kWave - 1);  // the lane that holds stored index r.g
-        costbest = readlane_f64(cb, gl);
-        obj = __builtin_amdgcn_readlane(cj, gl);
-        return r;
-    }
-
-    // eCE_satisfied (auction_.pyx:443-485) for row i: choice_cost from the last stored entry of column j
-    __device__ __forceinline__ bool ece_bad(int i, int j, const double *price, double tol, double eps) const {
-        const int lane = lane_id();
-        const long long g0 = s + rs[i];
-        const int len = rs[i + 1] - rs[i];
-        int last = -1;  // the last stored index of column j (:462-467)
-        for (int q = lane; q < len; q += kWave)
-            if (w.col(g0 + q) == j) last = q;
-        last = wave_max_i32(last);
-        double vj;
-        if constexpr (Out) vj = j >= m ? out.value(i) : w.value(g0 + (last < 0 ? 0 : last));  // (j < m: stored, last >= 0)
-        else vj = w.value(g0 + last);
-        const double choice_cost = maximize ? vj : vj * -1.0;
-        const double LHS = choice_cost - price[j] + tol;  // :475
-        bool bad = false;
-        if constexpr (Out) {
-            if (lane == 0) {
-                const double v = out.value(i);
-                const double cost = maximize ? v : v * -1.0;
-                if (LHS < (cost - price[m + i]) - eps) bad = true;
-            }
-        }
-        for (int q = lane; q < len; q += kWave) {
-            const double v = w.value(g0 + q);
-            const double cost = maximize ? v : v * -1.0;
-            if (LHS < (cost - price[w.col(g0 + q)]) - eps) bad = true;  // :482
-        }
-        return bad;
-    }
-
-    // get_obj (:489-523) over EVERY entry of the chosen column: a wavefront per row gathers the row's one matching value;
-    // a row with several matches (duplicate entries) is marked (nsel[i] > 1) and re-walked by the summing lane.
-    __device__ __forceinline__ void gather(const int *p2o, int n, double *selv, int *nsel) const {
-        const int lane = lane_id(), wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-        for (int i = wave; i < n; i += nw) {
-            const int j = p2o[i];
-            if (j < 0) continue;
-            if constexpr (Out) {
-                if (j >= m) {  // the row's outside entry: exactly one match
-                    if (lane == 0) {
-                        nsel[i] = 1;
-                        selv[i] = out.value(i);
-                    }
-                    continue;
-                }
-            }
-            const long long g0 = s + rs[i];
-            const int len = rs[i + 1] - rs[i];
-            int cnt = 0, at = -1;
-            for (int q = lane; q < len; q += kWave)
-                if (w.col(g0 + q) == j) {
-                    ++cnt;
-                    at = q;
-                }
-            for (int off = 32; off >= 1; off >>= 1) cnt += __shfl_xor(cnt, off);
-            at = wave_max_i32(at);
-            if (lane == 0) {
-                nsel[i] = cnt;
-                selv[i] = w.value(g0 + at);
-            }
-        }
-    }
-
-    // a double sum in row order, within a row in stored order
-    __device__ __forceinline__ double objective(const int *p2o, int n, const double *selv, const int *nsel) const {
-        double obj = 0;
-        for (int i = 0; i < n; ++i) {
-            const int j = p2o[i];
-            if (j == -1) continue;
-            if (nsel[i] == 1) {
-                const double v = maximize ? selv[i] : selv[i] * -1.0;
-                if (maximize) obj += v;
-                else obj -= v;
-                continue;
-            }
-            const long long g0 = s + rs[i];
-            const int len = rs[i + 1] - rs[i];
-            for (int q = 0; q < len; ++q)
-                if (w.col(g0 + q) == j) {
-                    const double x = w.value(g0 + q);
-                    const double v = maximize ? x : x * -1.0;
-                    if (maximize) obj += v;
-                    else obj -= v;
-                }
-        }
-        return obj;
-    }
-
-    // (m_: batch_solve's object count, in the outside mode m + n)
-    __device__ __forceinline__ int meta_cols(int m_) const { return m_; }
-    __device__ __forceinline__ int64_t meta_nnz() const {
-        return (int64_t)(offsets[blockIdx.x + 1] - s) + (Out ? (int64_t)n : 0);
-    }
+    __device__ __forceinline__ long long start(int i) const { return s + rs[i]; }
+    __device__ __forceinline__ int len(int i) const { return rs[i + 1] - rs[i]; }
+    __device__ __forceinline__ int col(long long g) const { return w.col(g); }
+    __device__ __forceinline__ double value(long long g) const { return w.value(g); }
+    __device__ __forceinline__ int64_t count() const { return (int64_t)(offsets[blockIdx.x + 1] - s) + (int64_t)n; }
 };
+
+template <class Src, bool Out>
+using SparseBatchRows = ListBatchRows<SparseRuns<Src>, Out>;
 
 // the all-or-nothing call (misslap_solve_sparse_batch): the host has read the check records and found every problem fit
 __global__ __launch_bounds__(1024) void k_sparse_batch_solve(SparseBatchArgs<SparsePacked> a) {
@@ -432,7 +291,7 @@ __global__ __launch_bounds__(1024) void k_sparse_batch_solve(SparseBatchArgs<Spa
     const SparseBatchCheck ck = a.chk[b];
     const long long s = a.offsets[b];
     const SparseBatchRows<SparsePacked, false> rows{
-        a.w, a.offsets, s, sparse_row_starts<SparsePacked, false>(a.row_start, s, b, a.s.Ns), a.s.maximize, 0, 0, {}};
+        {a.w, a.offsets, s, sparse_row_starts<SparsePacked, false>(a.row_start, s, b, a.s.Ns), 0}, a.s.maximize, 0, {}};
     batch_solve(a.s, rows, ck.last_row + 1, ck.max_col + 1, ck.absmax_bits);
 }
 
@@ -501,7 +360,7 @@ __global__ __launch_bounds__(1024) void k_sparse_batch_solve_status(SparseStatus
     BatchSolveArgs bs = a.d.s;
     if (a.fast) batch_fast_eps(bs, (double)N);
     const SparseBatchRows<Src, false> rows{
-        a.d.w, a.d.offsets, s, sparse_row_starts<Src, false>(a.d.row_start, s, b, a.d.s.Ns), bs.maximize, 0, 0, {}};
+        {a.d.w, a.d.offsets, s, sparse_row_starts<Src, false>(a.d.row_start, s, b, a.d.s.Ns), 0}, bs.maximize, 0, {}};
     batch_solve(bs, rows, ck.last_row + 1, ck.max_col + 1, ck.absmax_bits);
 }
 
@@ -581,7 +440,7 @@ __global__ __launch_bounds__(1024) void k_sparse_outside_solve(SparseOutsideArgs
     if (a.fast) batch_fast_eps(bs, n);
     const double *O = a.outside + (a.outside_ld ? (size_t)b * (size_t)a.outside_ld : (size_t)b);
     const SparseBatchRows<Src, true> rows{
-        a.d.w, a.d.offsets, s, sparse_row_starts<Src, true>(a.d.row_start, s, b, Nmax), bs.maximize, m, n,
+        {a.d.w, a.d.offsets, s, sparse_row_starts<Src, true>(a.d.row_start, s, b, Nmax), n}, bs.maximize, m,
         {O, a.outside_ld ? 1 : 0}};
     batch_solve(bs, rows, n, m + n, ck.absmax_bits);
     batch_outside_outputs(s_raw, a.d.s, b, n, m, a.Mmax, Nmax, po, oo, tid, T);

@@ -516,5 +516,4 @@ MISSLAP_API int misslap_get_state(misslap_solver *h, double *prices, int32_t *un
 #include "abi_sparse_batch.hpp"
 #include "abi_matching_batch.hpp"
 #include "abi_ell_batch.hpp"
-#include "abi_ell_batch_outside.hpp"
 #include "abi_sparse_batch_status.hpp"

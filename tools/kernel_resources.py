@@ -2,12 +2,13 @@
 """Register / LDS / spill numbers of every kernel of the library, from hipcc -Rpass-analysis=kernel-resource-usage
 (runs without a GPU).  usage: kernel_resources.py [substring ...] [-- extra hipcc flags]
 The batch solves and their guards: `kernel_resources.py batch ell matching sparse_outside` (k_dense_* / k_sparse_batch_* /
-k_ell_* / k_matching_batch*, the outside modes k_dense_outside_solve<T, Lay> / k_ell_outside_* and
+k_ell_* / k_matching_batch*, the outside modes k_dense_outside_solve<T, Lay> / k_ell_outside_solve<I, V> and
 k_sparse_outside_solve<Src>; the check pass of both modes is k_dense_batch_check<T, Lay, Out>, Lay being DenseContig or
-DenseView<Fin>, and k_sparse_batch_check<Src, Out>, Src being SparsePacked or SparseView<I, V>).
+DenseView<Fin>, k_sparse_batch_check<Src, Out>, Src being SparsePacked or SparseView<I, V>, and
+k_ell_batch_check<I, V, Out>).
 With --code-size the device code is compiled once more on its own and every line ends in code=<bytes>, the size of the
-kernel's symbol in the gfx950 code object (the comparisons of DESIGN 4.20 and 4.21:
-`kernel_resources.py --code-size dense matching_batch`)."""
+kernel's symbol in the gfx950 code object (the comparisons of DESIGN 4.20, 4.21 and 4.22:
+`kernel_resources.py --code-size dense matching_batch`, `kernel_resources.py --code-size ell sparse matching_batch`)."""
 import os
 import re
 import subprocess
