@@ -168,7 +168,8 @@ typedef struct misslap_meta {
                                     never read from memory */
     double tail_stats[12];       /* tail kernel accounting: [0..2] rounds in chain+solo / team / block mode, [3..5] their
                                     duration in 10-ns ticks, [6] bids, [7] bids answered by candidate lines, [8] line
-                                    (re)builds, [9] edges of the rows those lines answered, [10..11] reserved */
+                                    (re)builds, [9] edges of the rows those lines answered, [10] block rounds finished on
+                                    the clean path (no object bid on twice, none unowned), [11] reserved */
     /* validity of the returned assignment, reduced on the device so that `sol` is the only O(N) copy-out (the flags
      * the reference's benchmark harness forms on the host, benchmarking.py:56-64, with size = n_rows and numpy's
      * wrap-around for sol = -1):

@@ -230,6 +230,7 @@ class AuctionSolver:
         g["tail_modes"] = {name: dict(rounds=int(d[k]), ms=round(d[3 + k] * 1e-5, 3),
                                       us_per_round=round(d[3 + k] * 1e-2 / d[k], 3) if d[k] else None)
                            for k, name in enumerate(("solo", "team", "block"))}
+        g["tail_modes"]["block"]["clean_rounds"] = int(d[10])
         g["tail_cand"] = dict(bids=int(d[6]), hits=int(d[7]), builds=int(d[8]))
         g["tail_cand_edges"] = int(d[9])
         g["tail_raw"] = d[:6]  # (diagnostic MISSLAP_TAIL_STAMP builds: cycles per segment of a solo round)

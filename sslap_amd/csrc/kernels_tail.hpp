@@ -18,7 +18,9 @@
 // A round is a serial chain of dependent instructions per wavefront, so what makes it shorter is wavefronts: three
 // instances of k_tail by role, launched back to back once per phase (K only falls: block -> team -> solo):
 //   block (K > 16;  1024 threads): two list slots per wavefront and sweep (one per 32-lane half, one gather serves
-//         both), misses queued and scanned in a second pass, wavefront 0 resolves (LDS hash table above 64 bidders);
+//         both), misses queued and scanned in a second pass; a clean round (no object bid on twice, none unowned: the
+//         test runs in front of the barrier) is finished by the threads = slots, any other by wavefront 0 (LDS hash table
+//         above 64 bidders);
 //   team  (3 <= K <= 16; 1024 threads): wavefront w serves slot w alone; ONE LDS-only barrier per round, every
 //         serving wavefront finishes the round for the whole list on lanes = slots;
 //   pair / chain (K <= 2; 64 threads): one wavefront, no barrier, no LDS; K = 2: both bidders' lines in the two
@@ -1050,6 +1052,55 @@ __device__ __forceinline__ bool tail_team1_pipe(const TailArgs &a, const E &ed, 
     return false;
 }
 
+// ---- the clean test of a block round (17 <= K <= 192 bidders at the default threshold) -------------------------------
+// As in the team rounds, almost every block round is clean -- no object bid on twice, no unowned object won (C3: 93 % of
+// the block rounds, profiles/tail_block_clean.txt) -- and then every bidder wins, every slot passes to the owner its bidder
+// evicts (:409) and the list keeps its length and order: nothing is left to RESOLVE (:375-385) or to push left (:137-162).
+// The test runs IN FRONT of the barriers, by the lanes that publish a slot.  A table of one-probe tags (the team rounds'
+// kPipeTab) cannot serve 192 bidders: 192 objects fall on 192 different tags of a table of T entries with probability
+// exp(-192 * 191 / 2T), i.e. 67 % false positives at T = 16384 (64 KB), 11 % at K = 64.  The table below is therefore EXACT:
+// an entry is {round tag, object} as one 64-bit key, inserted with one LDS atomic maximum at the object's hash.  Tags
+// only grow, so an entry of an earlier round is smaller than every key of this one: the maximum replaces it and returns it
+// -- the slot was free, one LDS operation, the common case.  Meeting the own key = the object has been bid on in this
+// round.  Meeting another key of this round (two objects, one hash: 9 % of the inserts at K = 192, 0.8 % at K = 17): the
+// slot keeps the larger of the two keys and the lane carries the smaller one to the next slot (an ordered open-addressing
+// table: the slots between an object's hash and its key hold larger keys of this round, and entries only grow within a
+// round, so a second bid on the object walks the same slots and meets the key -- or a lane that carries it meets the
+// second bid's).  No round resets anything.  A walk that has not ended after kCleanProbes slots reports "bid on twice",
+// which only sends the round through the exact path.
+// The table lives in hKey, the key array of the exact path's own hash table (64 < K): both are empty at zero, the exact
+// path empties the array before it inserts and leaves it empty.  A table of its own (32 KB more) takes the workgroup's
+// LDS beyond 64 KB, where an address no longer fits the LDS instructions' offset field and every array costs an address
+// register: the 1024-thread instances then spill (16 .. 60 bytes of scratch per lane).
+constexpr int kCleanTab = kHashSize;
+constexpr int kCleanProbes = 8;
+static_assert(2 * kCleanTab == kPipeTab, "clean_hash: pipe_hash's top 11 bits");
+__device__ __forceinline__ int clean_hash(int obj) { return pipe_hash(obj) >> 1; }
+// The thread's slot index, formed HERE: the LDS addresses of a block of slot-indexed accesses are then computed inside the
+// block, from one register and the arrays' offsets.  Left to itself the compiler forms one address register per array ahead of
+// the round loop and keeps them all for the whole kernel, which the 1024-thread instances (128 VGPRs) pay with spills.
+__device__ __forceinline__ int slot_index_here(int t) {
+    asm volatile("" : "+v"(t));
+    return t;
+}
+// LDS reads issued together are waited for HERE, together (the two values stand for their group: the LDS returns in order),
+// so that a branch behind them costs no second LDS latency
+__device__ __forceinline__ void lds_landed_here(int &a, int &b) { asm volatile("" : "+v"(a), "+v"(b)); }
+// true: `obj` has been bid on before in the round `tag` (or the walk was cut short)
+__device__ __forceinline__ bool clean_insert(unsigned long long *tab, unsigned tag, int obj) {
+    const unsigned long long first = (unsigned long long)tag << 32;
+    unsigned long long cur = first | (unsigned long long)(unsigned)obj;
+    int h = clean_hash(obj);
+    for (int probe = 0; probe < kCleanProbes; ++probe) {
+        const unsigned long long old = atomicMax(&tab[h], cur);
+        if (old < first) return false;                              // an entry of an earlier round: the slot was free
+        if (old == cur || (unsigned)(old >> 32) != tag) return true;  // (a larger tag: the 32-bit round count has wrapped)
+        cur = min(old, cur);  // two objects, one hash: the smaller key moves on
+        h = (h + 1) & (kCleanTab - 1);
+    }
+    return true;
+}
+
 // kThreads = kTailMax (512): every mode.  kThreads = 1024 ("block only"): the rounds with more than kTeamMax bidders
 // with SIXTEEN wavefronts -- half the sweeps per wavefront in pass A, which is where a block round spends its time --
 // and nothing else: the solo / team code needs more than the 128 registers a 1024-thread workgroup leaves a
@@ -1078,6 +1129,9 @@ struct k_tail {
         __shared__ unsigned long long hKey[kHashSize];
         __shared__ int hPos[kHashSize];
         __shared__ int sCnt[3][kThreads / kWave];
+        unsigned long long *const cTab = hKey;  // block rounds: the clean table (clean_insert)
+        __shared__ unsigned sHit[kTailMax];  // tag of the last block round in which pass A published the slot (a line hit)
+        __shared__ unsigned sDirty;  // tag of the last block round that needs the exact RESOLVE / ASSIGN / push_all_left
         __shared__ int sK, sMissCnt;
         __shared__ long long sNits;
 
@@ -1101,12 +1155,15 @@ struct k_tail {
             sU[n] = (n < K) ? a.U[n] : -1;
             sStart[n] = (n < K) ? a.row_ptr[sU[n]] : 0;
         }
+        if (!kDuoOnly && !kTeamOnly)
+            for (int n = t; n < kTailMax; n += kThreads) sHit[n] = 0u;  // (round tags are >= 1)
         if (!kDuoOnly)
             for (int h = t; h < kHashSize; h += kThreads) {
                 hObj[h] = -1;
                 hKey[h] = 0ull;
                 hPos[h] = kPosNone;
             }
+        if (!kDuoOnly && !kTeamOnly && t == 0) sDirty = 0u;  // (round tags are >= 1; hKey = the clean table is empty at zero)
         const double eps = (double)a.eps;
         TailStats st;
         st.edges = st.miss_edges = st.builds = 0ull;
@@ -1153,6 +1210,28 @@ struct k_tail {
                 if (st.err) atomicOr(&ctl->err, st.err);
             }
         };
+        // block rounds: the round's tag in cTab / sDirty, and -- sixteen wavefronts, handles with lines -- per covered sweep
+        // the line of the person who takes the sweep's slot of the lane's half if its bidder wins (`enp`; -2: none requested).
+        // kEarlySweeps: how many sweeps of a round are covered; 0, 1, 2 and all 6 were measured (profiles/tail_block_clean.txt).
+        // MISSLAP_TAIL_BLOCK_EARLY_SWEEPS is the build switch of that A/B, like the MISSLAP_TAIL_STAMP_* ones
+        // (tools/build_ab.sh es2 "-DMISSLAP_TAIL_BLOCK_EARLY_SWEEPS=2"); above 1 the 12 B/edge k_batched_ptr instance spills.
+#ifndef MISSLAP_TAIL_BLOCK_EARLY_SWEEPS
+#define MISSLAP_TAIL_BLOCK_EARLY_SWEEPS 1
+#endif
+        constexpr int kEarlySweeps = (kBlockOnly && E::kCand) ? MISSLAP_TAIL_BLOCK_EARLY_SWEEPS : 0;
+        constexpr bool kEarly = kEarlySweeps > 0;
+        constexpr int kEarlyN = kEarly ? kEarlySweeps : 1;
+        unsigned rtag = 0u;
+        unsigned long long nclean = 0ull;  // clean block rounds of this launch -> Ctl::dbg[6] (tail_stats[10])
+        typename E::Slot el[kEarlyN];  // (set where block rounds exist: the other instances stay what they were, instruction for instruction)
+        int enp[kEarlyN];
+        if (!kDuoOnly && !kTeamOnly) {
+#pragma unroll
+            for (int q = 0; q < kEarlyN; ++q) {
+                el[q] = cand_no_line<typename E::Slot>();
+                enp[q] = -2;
+            }
+        }
         for (;;) {
             if (kBlockOnly && K <= kTeamMax) break;  // the next kernel takes over
             if (kDuoOnly) {
@@ -1199,12 +1278,24 @@ struct k_tail {
             }
             // ---- block mode, BID in two passes.  Pass A: the lines, two list slots per wavefront (one per 32-lane
             // half, one gather serves both); a hit goes straight to LDS, a miss is queued.  Pass B: the queued persons,
-            // one wavefront each, by a full scan of their rows (+ line rebuild).
+            // one wavefront each, by a full scan of their rows (+ line rebuild).  Between the passes the thread that holds a
+            // published slot enters its object into the clean table (a scanned slot's: its scanner) and raises sDirty for a
+            // second bid on it or an unowned object (clean_insert).
+            // Behind the two passes ONE broadcast LDS read decides: a clean round is finished by the threads = slots
+            // (ASSIGN of every bidder, the slot passes to the evicted owner; K and the order stay), every other round by
+            // the exact RESOLVE / ASSIGN / push_all_left below.
+            // In a clean round slot n's next bidder is the owner in the publishing lane's gathered record, and slot n
+            // stays with its wavefront: the first sweep's next lines are requested when the winners are known (kEarly)
+            // and are in flight across the LDS-only barriers of both passes, the finish and the closing barrier.  The next
+            // round takes such a line only where it belongs to the person its slot then holds -- whatever the round turned
+            // out to be; that person did not bid in this round (it owned an object), so no scan pass rebuilt its line.
             mode_begin(2);
+            rtag += 1u;
 #ifdef MISSLAP_TAIL_STAMP_BLOCK
-            // diagnostic build: cycles of wavefront 0 per segment of a block round -> Ctl::dbg[6..11]: [6] lines landed,
-            // [7] records landed, [8] evaluated + barrier, [9] scan pass + barrier, [10] resolve / assign / compaction,
-            // [11] closing barrier
+            // diagnostic build: cycles of wavefront 0 per segment of a block round -> Ctl::dbg[6..11]: [6] lines landed
+            // (the first sweep's: a requested line only has to finish landing), [7] records landed, [8] evaluated +
+            // barrier, [9] clean test + scan pass + barrier, [10] a clean round: the dirty word and the winners' record
+            // stores; any other: resolve / assign / compaction, [11] closing barrier
             unsigned long long sprev_b = __builtin_amdgcn_s_memtime();
             const CycleStamp bstamp{bacc, &sprev_b, wave == 0};
 #else
@@ -1227,7 +1318,20 @@ struct k_tail {
                         const int nme = base + c * 2 * nwaves + 2 * wv + (lane >> 5);
                         const int pme = nme < K ? sU[min(nme, kTailMax - 1)] : -1;
                         sl[c] = cand_no_line<typename E::Slot>();
-                        if (E::kCand && a.cand != nullptr) sl[c] = line_of<E>(a, pme, lane & (kCandLanes - 1));
+                        if (E::kCand && a.cand != nullptr) {
+                            if (kEarly && c == 0 && base < kEarlySweeps * 2 * nwaves) {  // (wave-uniform) the line requested in the round before
+                                int ep = -2;
+#pragma unroll
+                                for (int q = 0; q < kEarlyN; ++q)
+                                    if (base == q * 2 * nwaves) {  // (wave-uniform)
+                                        sl[c] = el[q];
+                                        ep = enp[q];
+                                    }
+                                if (pme != ep) sl[c] = line_of<E>(a, pme, lane & (kCandLanes - 1));
+                            } else {
+                                sl[c] = line_of<E>(a, pme, lane & (kCandLanes - 1));
+                            }
+                        }
                     }
                     bstamp(1);
 #pragma unroll
@@ -1249,6 +1353,21 @@ struct k_tail {
                         w.hm = 0ull;
                         w.len[0] = w.len[1] = 0;
                         if (E::kCand) cand_eval2_lane(sl[c], rr[c], true, n0 + 1 < K, eps, w, st.bad_hi);
+                        if (kEarly && c == 0 && base < kEarlySweeps * 2 * nwaves) {  // (wave-uniform) the next lines of my two slots
+                            int o = -2;
+                            const bool both = a.cand != nullptr && __popcll(w.hm) == 2;
+                            if (both) {
+                                const int o0 = __builtin_amdgcn_readlane(rr[c].owner, __ffs((int)(unsigned)w.hm) - 1);
+                                const int o1 = __builtin_amdgcn_readlane(rr[c].owner, __ffs((int)(unsigned)(w.hm >> 32)) + (kCandLanes - 1));
+                                o = lane < kCandLanes ? o0 : o1;
+                            }
+#pragma unroll
+                            for (int q = 0; q < kEarlyN; ++q)
+                                if (base == q * 2 * nwaves) {  // (wave-uniform)
+                                    if (both) el[q] = line_of<E>(a, o, lane & (kCandLanes - 1));
+                                    enp[q] = o >= 0 ? o : -2;  // (an unowned object: the chain ends, the slot goes to nobody)
+                                }
+                        }
                         if (w.hit) {
                             const int n = n0 + (lane >> 5);
                             sKey[n] = bid_to_key(w.bid);
@@ -1257,6 +1376,7 @@ struct k_tail {
                             // obj is only rewritten by this round's winner of obj, after every bid has been made.
                             sPrev[n] = rr[c].owner;
                             sPst[n] = rr[c].ostart;
+                            sHit[n] = rtag;  // (the scan pass never writes it: the slot's clean test is thread n's)
                         }
                         if (__popcll(w.hm) == 2) {  // wave-uniform (at most one lane per half): both lines decided
                             st.edges += (unsigned long long)(w.len[0] + w.len[1]);
@@ -1284,8 +1404,23 @@ struct k_tail {
                     bstamp.light(3);  // (a sweep's evaluation is billed to [8], not to the next sweep's "lines landed")
 #endif
                 }
-                __syncthreads();
+                // (kEarly: LDS-only barriers around the scan pass, so that the requested lines stay in flight.  Pass A
+                // stores nothing to memory; the scan pass stores rebuilt lines, which nobody reads before the closing
+                // barrier; and every record gather of the round has landed before its wavefront published the bid.)
+                if (kEarly) tail_barrier_lds();
+                else __syncthreads();
                 bstamp(3);
+                // the clean test of the slots that pass A published, by the threads = slots (three wavefronts at K = 192,
+                // next to the scan pass: inside the sweeps it would cost every wavefront a divergent loop per sweep, and
+                // the registers of one -- the 1024-thread instances then spill); a scanned slot's is its scanner's
+                // (the three LDS reads are issued together: one LDS latency in front of the insert, not three)
+                if (t < K) {
+                    const int ts = slot_index_here(t);
+                    const unsigned hit_t = sHit[ts];
+                    int obj_t = sObj[ts], prev_t = sPrev[ts];
+                    lds_landed_here(obj_t, prev_t);
+                    if (hit_t == rtag && (clean_insert(cTab, rtag, obj_t) || prev_t < 0)) sDirty = rtag;
+                }
                 const int nmiss = sMissCnt;
                 for (int m = wave; m < nmiss; m += nwaves) {
                     const int n = __builtin_amdgcn_readfirstlane(sList[m]);
@@ -1308,17 +1443,41 @@ struct k_tail {
                     st.bids += 1;
                     st.misses += 1;
                     if (ba.want) tail_build(a, i, ba, eps, st);
+                    // the scanned slot's clean test (behind the rebuild: what the rebuild holds in registers is dead here)
+                    if (lane == 0 && (clean_insert(cTab, rtag, bm.obj) || bm.prev < 0)) sDirty = rtag;
                 }
             }
-            __syncthreads();
+            if (kEarly) tail_barrier_lds();
+            else __syncthreads();
             bstamp(4);
 
-            if (K <= kWave) {
+            // the dirty word (one broadcast LDS read) and, in the same LDS latency, what the clean finish of slot t needs
+            const int dirty = (int)sDirty;
+            const int tf = slot_index_here(min(t, kTailMax - 1));
+            int fu = -1, fs = 0, fo = 0, fp = 0, fq = 0;
+            unsigned long long fk = 0ull;
+            if (t < K) {  // (the wavefronts without a slot read the dirty word alone)
+                fu = sU[tf], fs = sStart[tf], fo = sObj[tf], fp = sPrev[tf], fq = sPst[tf];
+                fk = sKey[tf];
+                lds_landed_here(fu, fs);
+            }
+            const bool clean = (unsigned)__builtin_amdgcn_readfirstlane(dirty) != rtag;
+            if (clean) {
+                // ---- clean round: every bidder wins (:375-385 has nothing to resolve); ASSIGN (:396-418) of slot t by
+                // thread t, the slot passes to the owner its bidder evicts (:409); K and the list's order stay ----------
+                if (t < K) {
+                    sU[tf] = apply_winner(a, fu, fs, fo, fp, fk);
+                    sStart[tf] = fq;
+                }
+                if (t == 0) sMissCnt = 0;
+                nclean += 1ull;
+            } else if (K <= kWave) {
                 // ---- fast path: the whole rest of the round in wavefront 0, no LDS atomics ------------
                 if (wave == 0) {
                     const bool act = lane < K;
-                    const unsigned long long key = act ? sKey[lane] : 0ull;
-                    const int obj = act ? sObj[lane] : (-2 - lane);
+                    const int ln = slot_index_here(lane);
+                    const unsigned long long key = act ? sKey[ln] : 0ull;
+                    const int obj = act ? sObj[ln] : (-2 - lane);
                     // RESOLVE (:375-385).  Two bidders on one object are the exception: every bidder inserts its object
                     // into the (empty) LDS hash table with one compare-and-swap; only if some insert meets its own object
                     // -- a contested object -- is the all-pairs loop run.  The table is emptied again right away.
@@ -1351,11 +1510,11 @@ struct k_tail {
                             }
                         }
                     }
-                    int u = act ? sU[lane] : -1;
-                    int sx = act ? sStart[lane] : 0;  // row start travelling with the slot's person
+                    int u = act ? sU[ln] : -1;
+                    int sx = act ? sStart[ln] : 0;  // row start travelling with the slot's person
                     if (act && !lose) {
-                        u = apply_winner(a, u, sx, obj, sPrev[lane], key);
-                        sx = sPst[lane];
+                        u = apply_winner(a, u, sx, obj, sPrev[ln], key);
+                        sx = sPst[ln];
                     }
                     // push_all_left with ballots
                     const unsigned long long kmask = (K >= 64) ? ~0ull : ((1ull << K) - 1ull);
@@ -1365,8 +1524,8 @@ struct k_tail {
                     const unsigned long long hl = holes & lmask;            // empty slots left of K'
                     if (hl == 0ull) {  // wave-uniform: nothing to move (no hole, or only holes at the end)
                         if (act) {
-                            sU[lane] = (lane < Kn) ? u : -1;
-                            sStart[lane] = sx;
+                            sU[ln] = (lane < Kn) ? u : -1;
+                            sStart[ln] = sx;
                         }
                     } else {
                         const unsigned long long mv = ~holes & ~lmask & kmask;  // persons right of K'
@@ -1381,10 +1540,10 @@ struct k_tail {
                             sStart[dst] = sx;
                         }
                         if (act) {
-                            if (lane >= Kn) sU[lane] = -1;
+                            if (lane >= Kn) sU[ln] = -1;
                             else if (!is_hl) {
-                                sU[lane] = u;
-                                sStart[lane] = sx;
+                                sU[ln] = u;
+                                sStart[ln] = sx;
                             }
                         }
                     }
@@ -1395,12 +1554,15 @@ struct k_tail {
                 }
             } else {
                 // ---- general path (64 < K <= 512): LDS hash table keyed by object ---------------------
+                for (int h = t; h < kHashSize; h += kThreads) hKey[h] = 0ull;  // (it has held the clean table)
+                __syncthreads();
                 const bool act = t < K;
+                const int tn = slot_index_here(t);
                 unsigned long long key = 0ull;
                 int obj = -1, h = 0;
                 if (act) {
-                    key = sKey[t];
-                    obj = sObj[t];
+                    key = sKey[tn];
+                    obj = sObj[tn];
                     h = (int)(((unsigned)obj * 2654435761u) >> 21) & (kHashSize - 1);
                     for (;;) {
                         const int old = atomicCAS(&hObj[h], -1, obj);
@@ -1419,11 +1581,11 @@ struct k_tail {
                     hKey[h] = 0ull;
                     hPos[h] = kPosNone;
                 }
-                int u = act ? sU[t] : -1;
-                int sx = act ? sStart[t] : 0;
+                int u = act ? sU[tn] : -1;
+                int sx = act ? sStart[tn] : 0;
                 if (win) {
-                    u = apply_winner(a, u, sx, obj, sPrev[t], key);
-                    sx = sPst[t];
+                    u = apply_winner(a, u, sx, obj, sPrev[tn], key);
+                    sx = sPst[tn];
                 }
                 const bool hole = act && u == -1;
                 const unsigned long long bh = __ballot(hole);
@@ -1452,10 +1614,10 @@ struct k_tail {
                     sStart[sList[pm]] = sx;
                 }
                 if (act) {
-                    if (t >= Kn) sU[t] = -1;
+                    if (t >= Kn) sU[tn] = -1;
                     else if (!is_hl) {
-                        sU[t] = u;
-                        sStart[t] = sx;
+                        sU[tn] = u;
+                        sStart[tn] = sx;
                     }
                 }
                 if (t == 0) {
@@ -1466,7 +1628,7 @@ struct k_tail {
             bstamp(5);
             __syncthreads();
             bstamp(6);
-            K = sK;
+            if (!clean) K = sK;
             nits += 1;
             mode_end(2);
             if (K == 0 || nits >= max_iter) break;
@@ -1476,6 +1638,10 @@ struct k_tail {
 #ifdef MISSLAP_TAIL_STAMP_BLOCK
         if (t == 0)
             for (int k = 1; k <= 6; ++k) ctl->dbg[5 + k] += bacc[k];
+#endif
+#if !defined(MISSLAP_TAIL_STAMP) && !defined(MISSLAP_TAIL_STAMP_SOLO) && !defined(MISSLAP_TAIL_STAMP_DUO) && \
+    !defined(MISSLAP_TAIL_STAMP_TEAM) && !defined(MISSLAP_TAIL_STAMP_BLOCK) && !defined(MISSLAP_TILED_STAMP)
+        if (!kDuoOnly && !kTeamOnly && t == 0) ctl->dbg[6] += nclean;  // (the stamped builds use the slot for a segment)
 #endif
 
         for (int n = t; n < K0; n += kThreads) a.U[n] = sU[n];

@@ -385,9 +385,11 @@ MISSLAP_API int misslap_finish(misslap_solver *h, int32_t *person_to_object_out,
     meta->shard_edges = c.shard_edges;
     for (int k = 0; k < 6; ++k) meta->tail_stats[k] = (double)c.dbg[k];  // tail: rounds / 10-ns ticks per mode
     for (int k = 0; k < 4; ++k) meta->tail_stats[6 + k] = (double)c.dbg[12 + k];  // bids, line hits, builds, hit edges
+    meta->tail_stats[10] = (double)c.dbg[6];  // block rounds finished on the clean path (the stamped builds: not counted)
 #if defined(MISSLAP_TAIL_STAMP) || defined(MISSLAP_TAIL_STAMP_SOLO) || defined(MISSLAP_TAIL_STAMP_TEAM) || \
     defined(MISSLAP_TAIL_STAMP_BLOCK) || defined(MISSLAP_TILED_STAMP) || defined(MISSLAP_TAIL_STAMP_DUO)
     for (int k = 0; k < 6; ++k) meta->tail_stats[k] = (double)c.dbg[6 + k];  // diagnostic build: solo-round segments (cycles)
+    meta->tail_stats[10] = 0.0;
 #endif
     meta->cand_hits = c.cand_hits;
     meta->cand_edges = c.cand_edges;

@@ -17,7 +17,7 @@ tm = d["tail_modes"]
 names = {"chain": ["wait for the line", "record gather", "winner known + next line requested", "rest of the evaluation", "full scan of a missed person", "store / re-request"],
          "duo": ["wait for the lines", "record gather", "both winners known + next lines requested", "rest of the evaluation", "full scans of missed persons", "resolve / stores / re-request"],
          "team": ["wait for the line + record gather", "evaluation of my slot up to the bid", "publish", "barrier", "LDS reads landed", "dirty word / wait for the next line / stores / next gather issued / loop"],
-         "block": ["lines landed", "records landed", "evaluation + barrier", "scan pass + barrier", "resolve / assign / compaction (wavefront 0)", "closing barrier"]}[m]
+         "block": ["lines landed", "records landed", "evaluation + barrier", "clean test + scan pass + barrier", "clean: dirty word + record stores; else resolve / assign / compaction (wavefront 0)", "closing barrier"]}[m]
 # rounds the stamped code ran: chain = K = 1 rounds are not counted separately by the kernel: use the simulator's histogram share
 print(f"{sys.argv[3]} {m}: solve {d['solve_ms']} ms, sha {d['sol_sha256']}, tail modes {json.dumps(tm)}")
 print("   cycles (wavefront 0, summed over the solve): " + "; ".join(f"{n}: {int(x)}" for n, x in zip(names, r) if n != "-"), "| total", int(sum(r)))
