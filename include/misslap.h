@@ -43,7 +43,8 @@ extern "C" {
  *      misslap_solve_dense_batch_status_strided, misslap_solve_dense_batch_outside_strided,
  *      misslap_matching_dense_batch_strided, misslap_solve_sparse_batch_status_view,
  *      misslap_solve_sparse_batch_outside_view, misslap_sparse_batch_view_workspace_bytes,
- *      MISSLAP_DENSE_ENTRIES_FINITE in misslap_options.mat_dtype (no new entry point). */
+ *      MISSLAP_DENSE_ENTRIES_FINITE in misslap_options.mat_dtype (no new entry point),
+ *      misslap_dense_batch_reverse_finish. */
 
 /* misslap_options.mat_dtype: the element type of a dense stack */
 #define MISSLAP_DTYPE_F64 0   /* double */
@@ -673,6 +674,39 @@ int misslap_solve_dense_batch_outside_strided(int64_t B, int64_t N, int64_t M, i
                                               double *outside_prices_out, int32_t out_on_device, int32_t *status,
                                               int32_t *matching_size, misslap_dense_batch_meta *meta,
                                               misslap_dense_batch_info *info);
+
+/* ---- the reverse-auction finish of a dense batch solve: rectangular problems made optimal from any starting prices.
+ * A forward auction on n_b rows and more than n_b objects (m_b > n_b, and every outside problem) is optimal only as a
+ * single phase from zero prices; from other prices, or with eps-scaling, it ends with eps-CS but with abandoned objects
+ * priced above the objects in use.  This call runs, behind a stream-ordered misslap_solve_dense_batch_status[_strided]
+ * or misslap_solve_dense_batch_outside[_strided] and on that solve's device outputs, the modified reverse auction with a
+ * fixed lambda (Bertsekas, Network Optimization, 7.2) on every problem with status[b] == 0 and meta[b].n_assigned ==
+ * n_b: lambda = the smallest price of an assigned object, and every unassigned object priced above lambda either takes
+ * the row that values it most or drops to lambda.  Afterwards the assignment satisfies eps-CS at meta[b].final_eps and no
+ * unassigned object is priced above lambda: it is optimal within n_b * final_eps.  The arithmetic is float64 and stated,
+ * operation for operation, by sslap_amd.dense_reverse_finish; csrc/kernels_dense_batch.hpp has the kernel.
+ *   B, N, M, stride_*, mat   the stack as misslap_solve_dense_batch_status_strided takes it: a contiguous stack passes
+ *                  (N * M, M, 1).  Element type and entry rule from opt->mat_dtype (| MISSLAP_DENSE_ENTRIES_FINITE).
+ *   shapes         the solve's device shapes, or NULL.  status[b] is read first and nothing else of a problem whose status
+ *                  is not 0 is read or written, so a bad device shape is never used.
+ *   outside, outside_ld   the solve's outside values (device), or NULL for a solve without them; outside_prices likewise.
+ *   opt            device, maximize, mat_dtype; max_iter is the finish's own budget of iterations per problem;
+ *                  input_on_device must be set.  Every pointer except opt is a device pointer.
+ *   stream         the launch goes onto it: one launch, one workgroup per problem; nothing is allocated, copied or waited
+ *                  for, and no workspace is needed.
+ *   status, sol, prices, outside_prices, meta   the solve's outputs.  sol, prices and outside_prices of a finished
+ *                  problem are rewritten from the final state (an outside object is -1 in sol), meta[b].obj_f64 and
+ *                  obj_f32 are recomputed in the reference's row order and meta[b].eCE at target_eps = 1 / n_b; every other
+ *                  field of meta[b] stays the forward solve's.
+ *   reverse_its    int64[B]: the iterations made (0 for a square problem), -1 where the finish did not run
+ *   reverse_left   int32[B]: the unassigned objects still priced above lambda -- 0 unless max_iter cut the finish --, -1
+ *                  where it did not run (status != 0, or max_iter cut the forward solve before every row was assigned:
+ *                  nothing of that problem is touched). */
+int misslap_dense_batch_reverse_finish(int64_t B, int64_t N, int64_t M, int64_t stride_b, int64_t stride_n, int64_t stride_m,
+                                       const void *mat, const int32_t *shapes, const double *outside, int64_t outside_ld,
+                                       const misslap_options *opt, void *stream, const int32_t *status, int32_t *sol,
+                                       double *prices, double *outside_prices, misslap_dense_batch_meta *meta,
+                                       int64_t *reverse_its, int32_t *reverse_left);
 
 /* ---- many small SPARSE problems in one call: the batch form of _from_sparse(loc, val, size=...) (auction_.pyx:575-617).
  * loc is int32[nnz][2] and val double[nnz]; problem b is the entries offsets[b] .. offsets[b + 1] (offsets: host

@@ -203,6 +203,9 @@ SYMBOLS = {
     "misslap_solve_dense_batch_outside_strided": (C.c_int, [C.c_int64] * 6 + [_VP, _VP, C.c_int32, _VP, C.POINTER(Options),
                                                             _VP, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP, _VP, C.c_int32,
                                                             _VP, _VP, _VP, C.POINTER(DenseBatchInfo)]),
+    # (B, N, M, strides, mat, shapes, outside, outside_ld, opt, stream, status, sol, prices, outside_prices, meta, its, left)
+    "misslap_dense_batch_reverse_finish": (C.c_int, [C.c_int64] * 6 + [_VP, _VP, _VP, C.c_int64, C.POINTER(Options), _VP,
+                                                     _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "misslap_solve_sparse_batch": (C.c_int, [C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int64, C.c_int32,
                                              C.POINTER(Options), _VP, C.c_int64, _VP, C.c_int64, C.c_int32,
                                              C.POINTER(DenseBatchMeta), C.POINTER(DenseBatchInfo)]),

@@ -4,6 +4,7 @@
 //   misslap_solve_dense_batch_status_strided                                          ... as a strided view
 //   misslap_solve_dense_batch_outside, misslap_dense_batch_outside_workspace_bytes    with an outside option per row
 //   misslap_solve_dense_batch_outside_strided                                         ... as a strided view
+//   misslap_dense_batch_reverse_finish                                                one more launch behind any of them
 // The options, the shape checks and the launch geometry are those of misslap_solve_dense_batch (abi_dense_batch.hpp,
 // abi_batch_common.hpp), the two modes of a call are batch_stream_call's (abi_batch_stream.hpp).  Every call is
 // described by one DenseCall; the sequence of launches is written once per mode (dense_batch_status_enqueue,
@@ -239,7 +240,72 @@ int dense_outside_call(const char *who, int64_t B, int64_t N, int64_t M, const v
         [&](DevScratch &tmp, hipStream_t st) { return dense_call_upload(tmp, st, opt, c); },
         [&](hipStream_t st, void *ws, const BatchStreamOut &d) { return dense_outside_enqueue(st, opt, c, ws, d); });
 }
+
+// The one launch of misslap_dense_batch_reverse_finish on st: k_dense_reverse_finish<T, DenseView<finite>, outside>.
+template <class T, bool Fin>
+void dense_finish_launch(hipStream_t st, int64_t B, int64_t Mo, DenseFinishArgs<DenseView<Fin>> a, bool out) {
+    const size_t lds = dense_finish_lds_bytes(a.N, Mo);
+    if (out)
+        hipLaunchKernelGGL((k_dense_reverse_finish<T, DenseView<Fin>, true>), dim3((unsigned)B), dim3(kDenseFinishThreads),
+                           lds, st, a);
+    else
+        hipLaunchKernelGGL((k_dense_reverse_finish<T, DenseView<Fin>, false>), dim3((unsigned)B),
+                           dim3(kDenseFinishThreads), lds, st, a);
+}
 }  // namespace
+
+MISSLAP_API int misslap_dense_batch_reverse_finish(int64_t B, int64_t N, int64_t M, int64_t stride_b, int64_t stride_n,
+                                                   int64_t stride_m, const void *mat, const int32_t *shapes,
+                                                   const double *outside, int64_t outside_ld,
+                                                   const misslap_options *opt_in, void *stream, const int32_t *status,
+                                                   int32_t *sol, double *prices, double *outside_prices,
+                                                   misslap_dense_batch_meta *meta, int64_t *reverse_its,
+                                                   int32_t *reverse_left) {
+    const char *who = "misslap_dense_batch_reverse_finish";
+    misslap_options opt;
+    int rc = batch_options(opt_in, &opt, who, "device, maximize, max_iter, mat_dtype and input_on_device", true);
+    if (rc) return rc;
+    const bool finite = dense_take_entries_finite(&opt);
+    if (!opt.input_on_device) return fail(MISSLAP_ERR_INVALID, "%s: every array is on the device: set input_on_device", who);
+    if (!mat || !status || !sol || !prices || !meta || !reverse_its || !reverse_left)
+        return fail(MISSLAP_ERR_INVALID, "null mat / status / sol / prices / meta / reverse_its / reverse_left");
+    if ((rc = dense_batch_dims(B, N, M))) return rc;
+    if ((outside != nullptr) != (outside_prices != nullptr))
+        return fail(MISSLAP_ERR_INVALID, "%s: outside and outside_prices go together (the outputs of the outside solve)", who);
+    if (outside && outside_ld != 0 && outside_ld < N)
+        return fail(MISSLAP_ERR_INVALID, "outside_ld = %lld: 0 (one value per problem) or >= N = %lld",
+                    (long long)outside_ld, (long long)N);
+    if ((rc = dense_strides_check(B, N, M, stride_b, stride_n, stride_m, who))) return rc;
+    if ((rc = batch_set_device(opt))) return rc;
+    const DenseStrides str{(long long)stride_b, (long long)stride_n, (long long)stride_m, 0x7fffffff};
+    dense_dtype_dispatch(opt.mat_dtype, [&](auto t) {
+        auto fill = [&](auto lay) {
+            DenseFinishArgs<decltype(lay)> a{};
+            a.mat = mat;
+            a.N = N;
+            a.M = M;
+            a.shapes = shapes;
+            a.outside = outside;
+            a.outside_ld = outside_ld;
+            a.maximize = opt.maximize ? 1 : 0;
+            a.max_iter = opt.max_iter;
+            a.status = status;
+            a.sol = sol;
+            a.prices = prices;
+            a.outside_prices = outside_prices;
+            a.meta = meta;
+            a.its = reinterpret_cast<long long *>(reverse_its);
+            a.left = reverse_left;
+            a.lay = lay;
+            return a;
+        };
+        const int64_t Mo = outside ? M + N : M;
+        if (finite) dense_finish_launch<decltype(t), true>((hipStream_t)stream, B, Mo, fill(DenseView<true>{str}), outside != nullptr);
+        else dense_finish_launch<decltype(t), false>((hipStream_t)stream, B, Mo, fill(DenseView<false>{str}), outside != nullptr);
+    });
+    HIP_TRY(hipGetLastError());
+    return MISSLAP_OK;
+}
 
 MISSLAP_API int64_t misslap_dense_batch_workspace_bytes(int64_t B, int64_t N, int64_t M, int32_t has_prices,
                                                         int32_t cardinality_check) {

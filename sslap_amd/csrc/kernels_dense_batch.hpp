@@ -4,7 +4,8 @@
 //
 // The round loop is batch_solve (kernels_batch_solve.hpp); this file has the check pass, the dense row source and the
 // solve kernels, each once: k_dense_batch_check<T, Lay, Out>, DenseBatchRows<T, Lay, Out>, k_dense_batch_solve<T>,
-// k_dense_batch_solve_status<T, Lay> and k_dense_outside_solve<T, Lay>.  Values are read from the caller's stack in
+// k_dense_batch_solve_status<T, Lay> and k_dense_outside_solve<T, Lay>; behind them, as a launch of its own, the reverse
+// finish k_dense_reverse_finish<T, Lay, Out> (at the end of the file).  Values are read from the caller's stack in
 // global memory, where a small problem stays in L2:
 //   BID      lanes scan the row in column order (lane l holds columns l, l + 64, ...), staged in registers with up to
 //            kDenseBatchCols loads in flight; the object is the winning column r.g.
@@ -542,6 +543,304 @@ __global__ __launch_bounds__(1024) void k_dense_outside_solve(DenseOutsideArgs<L
     const double *O = a.outside + (a.outside_ld ? (size_t)b * (size_t)a.outside_ld : (size_t)b);
     MISSLAP_DENSE_BATCH_RUN(T, Lay, true, d, a.lay, s, b, n, m, ck, vals, (BatchOutside<true>{O, a.outside_ld ? 1 : 0}));
     batch_outside_outputs(s_raw, d.s, b, n, m, M, N, po, oo, tid, nt);
+}
+
+// ---- reverse finish (misslap_dense_batch_reverse_finish): the reverse-auction clean-up behind a forward solve
+//
+// A forward auction on a rectangular problem (n rows, more than n objects) that did not start from zero prices ends
+// with eps-CS and, in general, far from the optimum: objects that were bid up and then abandoned keep prices above
+// those of the objects in use.  The modified reverse auction with a fixed lambda (Bertsekas, Network Optimization, 7.2)
+// repairs exactly that: lambda = the smallest price of an assigned object, and every unassigned object priced above it
+// either takes the row that values it most (at a price that keeps eps-CS) or drops to lambda.  Afterwards eps-CS still
+// holds at the solve's final eps and no unassigned object is priced above lambda: optimal within n * eps.
+//
+// One workgroup per problem, its own launch behind the solve's, reading the solve's outputs: status first (a problem
+// whose status is not 0 is not touched, so a caller's bad device shape is never read), then meta.n_assigned (a solve
+// cut by max_iter is not touched either).  State in LDS, carved for the stack's N rows and Mo = M (+ N outside) objects:
+// p[Mo], pi[N] (the rows' profits a_ij - p_j), o2p[Mo], p2o[N]: 12 Mo + 12 N bytes, 36 864 at 1024 x 1024 with outside.
+//
+// The loop is serial by definition (sslap_amd.dense_reverse_finish is its statement in numpy; the two agree operation
+// for operation in float64) and each iteration is a chain of dependent latencies: pick j, read column j of the n rows
+// (strided global loads), reduce the rows' top two of a_ij - pi_i, update a few scalars.  It runs on wavefront 0 ALONE:
+// lane l holds rows l, l + 64, ... (up to 16 loads in flight, issued back to back under one latency), the top two are
+// reduced with lane shuffles so that every lane ends with the same (beta, row, omega) and takes the same branch, and
+// lane 0 stores the few changed cells.  Nothing in the iteration crosses a wavefront, so there is no LDS exchange and no
+// workgroup barrier in it: LDS operations of one wavefront complete in order, and a wavefront-scope fence keeps the
+// compiler from moving them.  The other three wavefronts wait at the one barrier behind the loop; they load the state
+// before it and share the eCE test (n rows x m columns) and the outputs after it.
+constexpr int kDenseFinishThreads = 256;
+constexpr int kDenseFinishRows = kDenseBatchMaxDim / kWave;  // rows per lane in a column scan
+
+template <class Lay>
+struct DenseFinishArgs {
+    const void *mat;         // elements of the kernel's T
+    long long N, M;          // the extents of the stack
+    const int *shapes;       // [B][2] or null
+    const double *outside;   // [B] (outside_ld == 0) or [B][outside_ld]; read when Out
+    long long outside_ld;
+    int maximize;
+    long long max_iter;      // the finish's own budget of iterations
+    const int *status;       // [B] the solve's verdicts
+    int *sol;                // [B][N]
+    double *prices;          // [B][M]
+    double *outside_prices;  // [B][N]; read and written when Out
+    misslap_dense_batch_meta *meta;  // [B]
+    long long *its;          // [B] iterations made, -1: not run
+    int *left;               // [B] unassigned objects still priced above lambda (0 unless the budget cut), -1: not run
+    [[no_unique_address]] Lay lay;
+};
+
+__host__ __device__ constexpr size_t dense_finish_lds_bytes(long long N, long long Mo) {
+    return (size_t)Mo * (8 + 4) + (size_t)N * (8 + 4);
+}
+
+// LDS stores of this wavefront before, its LDS loads behind: in order (one wavefront's LDS operations complete in the
+// order they were issued; the fences bind the compiler)
+__device__ __forceinline__ void dense_finish_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+template <class T, class Lay, bool Out>
+__global__ __launch_bounds__(kDenseFinishThreads) void k_dense_reverse_finish(DenseFinishArgs<Lay> a) {
+    static_assert(Lay::kView, "the finish reads every stack as a view (a compact one has its natural strides)");
+    extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
+    __shared__ double s_min[kDenseFinishThreads / kWave];
+    __shared__ int s_bad;
+    const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x, lane = lane_id(), wave = tid >> 6, nw = nt >> 6;
+    const int N = (int)a.N, M = (int)a.M;
+    int n, m;
+    dense_batch_shape(a.shapes, a.N, a.M, b, n, m);
+    const bool run = a.status[b] == MISSLAP_BATCH_STATUS_OK && n >= 1 && n <= N && m >= 1 && m <= M &&
+                     a.meta[b].n_assigned == (int64_t)n;
+    if (!run) {  // (uniform: nothing of the problem is read or written)
+        if (tid == 0) {
+            a.its[b] = -1;
+            a.left[b] = -1;
+        }
+        return;
+    }
+    const int mo = Out ? m + n : m;
+    const int Mo = Out ? M + N : M;
+    double *p = reinterpret_cast<double *>(s_raw);  // [Mo]
+    double *pi = p + Mo;                            // [N]
+    int *o2p = reinterpret_cast<int *>(pi + N);     // [Mo]
+    int *p2o = o2p + Mo;                            // [N]
+    const T *A = static_cast<const T *>(a.mat) + a.lay.problem(b, a.N, a.M);
+    const size_t sN = (size_t)a.lay.row_stride(a.M);
+    const double *O = nullptr;
+    int ostride = 0;
+    if constexpr (Out) {
+        O = a.outside + (a.outside_ld ? (size_t)b * (size_t)a.outside_ld : (size_t)b);
+        ostride = a.outside_ld ? 1 : 0;
+    }
+    const int maximize = a.maximize;
+    int *sol = a.sol + (size_t)b * (size_t)N;
+    double *po = a.prices + (size_t)b * (size_t)M;
+    double *oo = Out ? a.outside_prices + (size_t)b * (size_t)N : nullptr;
+    // the maximised value of entry (i, j) of the augmented problem (an entry: the caller knows)
+    auto value = [&](int i, int j) -> double {
+        double v;
+        if (Out && j >= m) v = O[i * ostride];
+        else v = dense_widen(A[(size_t)i * sN + a.lay.col(j)]);
+        return maximize ? v : v * -1.0;
+    };
+
+    // ---- set-up: p, o2p, p2o, pi and lambda
+    if (tid == 0) s_bad = 0;
+    for (int j = tid; j < mo; j += nt) {
+        p[j] = j < m ? po[j] : oo[j - m];
+        o2p[j] = -1;
+    }
+    __syncthreads();
+    double lmin = __builtin_huge_val();
+    for (int i = tid; i < n; i += nt) {
+        int j = sol[i];
+        if (Out && j == -1) j = m + i;
+        if (j < 0 || j >= m + (Out ? n : 0) || (j >= m && j != m + i)) {  // (not a solve's output: leave it alone)
+            atomicOr(&s_bad, 1);
+            j = Out ? m + i : 0;
+        }
+        p2o[i] = j;
+        o2p[j] = i;
+        const double pj = p[j];
+        pi[i] = value(i, j) - pj;
+        lmin = pj < lmin ? pj : lmin;
+    }
+    for (int off = 32; off >= 1; off >>= 1) {
+        const double o = __shfl_xor(lmin, off);
+        lmin = o < lmin ? o : lmin;
+    }
+    if (lane == 0) s_min[wave] = lmin;
+    __syncthreads();
+    if (s_bad) {
+        if (tid == 0) {
+            a.its[b] = -1;
+            a.left[b] = -1;
+        }
+        return;
+    }
+    double lam = s_min[0];
+    for (int w = 1; w < nw; ++w) lam = s_min[w] < lam ? s_min[w] : lam;
+    const double eps = (double)a.meta[b].final_eps;
+
+    // ---- the loop, on wavefront 0
+    if (wave == 0) {
+        const double ninf = -__builtin_huge_val();
+        long long its = 0;
+        int left = 0, cursor = 0, next = -1;
+        for (;;) {
+            int j = -1;
+            if (next >= 0) {
+                j = next;
+                next = -1;
+            } else {
+                for (int base = cursor; base < mo; base += kWave) {
+                    const int c = base + lane;
+                    const bool hit = c < mo && o2p[c] == -1 && p[c] > lam;
+                    const unsigned long long bm = __ballot(hit);
+                    if (bm) {
+                        j = base + __ffsll((long long)bm) - 1;
+                        break;
+                    }
+                }
+                if (j < 0) break;  // left = 0
+                cursor = j + 1;
+            }
+            if (its >= a.max_iter) {  // the budget: what is left, j included
+                for (int base = 0; base < mo; base += kWave) {
+                    const int c = base + lane;
+                    left += __popcll(__ballot(c < mo && o2p[c] == -1 && p[c] > lam));
+                }
+                break;
+            }
+            ++its;
+            // column j over the rows, ascending within a lane: the top two of w = a_ij - pi_i, strict ">"
+            double bw = ninf, ow = ninf, ba = 0.0;
+            int bi = -1;
+            if (!Out || j < m) {
+                const T *col = A + a.lay.col(j);
+                T v[kDenseFinishRows];
+#pragma unroll
+                for (int q = 0; q < kDenseFinishRows; ++q) {
+                    if (q * kWave >= n) break;
+                    const int i = lane + q * kWave;
+                    v[q] = i < n ? col[(size_t)i * sN] : dense_hole<T>();
+                }
+#pragma unroll
+                for (int q = 0; q < kDenseFinishRows; ++q) {
+                    if (q * kWave >= n) break;
+                    const int i = lane + q * kWave;
+                    if (i < n && dense_entry_is<Lay::kFinite>(v[q])) {
+                        const double e = dense_widen(v[q]);
+                        const double av = maximize ? e : e * -1.0;
+                        const double w = av - pi[i];
+                        if (w > bw) {
+                            ow = bw;
+                            bw = w;
+                            bi = i;
+                            ba = av;
+                        } else if (w > ow) {
+                            ow = w;
+                        }
+                    }
+                }
+            } else if (lane == 0) {  // an outside object: the one entry of its row
+                const int i = j - m;
+                const double av = value(i, j);
+                const double w = av - pi[i];
+                if (w > bw) {
+                    bw = w;
+                    bi = i;
+                    ba = av;
+                }
+            }
+            // across lanes: the larger w, the smaller row on a tie (a lane without an entry holds row -1 = UINT_MAX);
+            // the second is the largest of the two seconds and the smaller of the two bests.  Symmetric, so after the
+            // butterfly every lane holds the same result.
+            for (int off = 32; off >= 1; off >>= 1) {
+                const double xb = __shfl_xor(bw, off), xo = __shfl_xor(ow, off), xa = __shfl_xor(ba, off);
+                const int xi = __shfl_xor(bi, off);
+                const bool take = xb > bw || (xb == bw && (unsigned)xi < (unsigned)bi);
+                const double lo = take ? bw : xb;
+                const double o2 = xo > ow ? xo : ow;
+                ow = lo > o2 ? lo : o2;
+                if (take) {
+                    bw = xb;
+                    bi = xi;
+                    ba = xa;
+                }
+            }
+            if (bi < 0 || lam >= bw - eps) {
+                if (lane == 0) p[j] = lam;
+            } else {
+                const double t = ow - eps;
+                const double pj = t > lam ? t : lam;
+                const int jo = p2o[bi];
+                const double pjo = p[jo];
+                if (lane == 0) {
+                    p[j] = pj;
+                    pi[bi] = ba - pj;
+                    o2p[jo] = -1;
+                    o2p[j] = bi;
+                    p2o[bi] = j;
+                }
+                if (pjo > lam) next = jo;
+            }
+            dense_finish_wave_sync();
+        }
+        if (lane == 0) {
+            a.its[b] = its;
+            a.left[b] = left;
+        }
+    }
+    if (tid == 0) s_bad = 0;  // (from here on: the eCE flag)
+    __syncthreads();
+
+    // ---- the outputs in the caller's terms, the chosen values (into pi, which the loop is done with), eCE at target eps
+    for (int i = tid; i < n; i += nt) sol[i] = p2o[i] < m ? p2o[i] : -1;
+    for (int j = tid; j < m; j += nt) po[j] = p[j];
+    if constexpr (Out)
+        for (int i = tid; i < n; i += nt) oo[i] = p[m + i];
+    double *selv = pi;
+    const double tol = 1e-7, teps = (double)(float)(1.0 / (double)n);
+    for (int i = wave; i < n; i += nw) {  // eCE_satisfied (auction_.pyx:443-485), as batch_ece makes it
+        const int j = p2o[i];
+        double vj;
+        if (Out && j >= m) vj = O[i * ostride];
+        else vj = dense_widen(A[(size_t)i * sN + a.lay.col(j)]);
+        const double choice_cost = maximize ? vj : vj * -1.0;
+        const double LHS = choice_cost - p[j] + tol;
+        bool bad = false;
+        if constexpr (Out) {
+            if (lane == 0 && LHS < (value(i, m + i) - p[m + i]) - teps) bad = true;
+        }
+        const T *row = A + (size_t)i * sN;
+        for (int c = lane; c < m; c += kWave) {
+            const T e = row[a.lay.col(c)];
+            if (!dense_entry_is<Lay::kFinite>(e)) continue;
+            const double v = dense_widen(e);
+            const double cost = maximize ? v : v * -1.0;
+            if (LHS < (cost - p[c]) - teps) bad = true;
+        }
+        if (__ballot(bad) && lane == 0) s_bad = 1;
+        __builtin_amdgcn_wave_barrier();
+        if (lane == 0) selv[i] = vj;
+    }
+    __syncthreads();
+    if (tid == 0) {  // get_obj (:489-523) in row order
+        double obj = 0;
+        for (int i = 0; i < n; ++i) {
+            const double val = maximize ? selv[i] : selv[i] * -1.0;
+            if (maximize) obj += val;
+            else obj -= val;
+        }
+        misslap_dense_batch_meta &r = a.meta[b];
+        r.obj_f64 = obj;
+        r.obj_f32 = (float)obj;
+        r.eCE = s_bad ? 0 : 1;
+    }
 }
 
 }  // namespace misslap

@@ -8,12 +8,18 @@ csrc/kernels_dense_batch.hpp).
 With `outside` every row also holds an outside option, so a row may stay unmatched (a partial assignment): problem b is
 the dense matrix `dense_to_augmented` returns, its slice plus an n_b x n_b block with the outside values on the diagonal
 and -1 elsewhere, and its result is the reference's on that n_b x (m_b + n_b) matrix (misslap_solve_dense_batch_outside).
+
+With `finish="reverse"` every solved problem gets the reverse-auction clean-up behind its forward solve, which makes a
+rectangular solve optimal from any starting prices (misslap_dense_batch_reverse_finish); `dense_reverse_finish` is its
+definition in numpy.
 """
 import ctypes as C
+import os
 
 import numpy as np
 
 from . import _lib
+from .auction_solve import _ENV_DEVICE
 from ._batch import (_STATUS_ERRORS, _StatusCall, _check_device_shapes, _check_outside, _check_shapes, _check_stack,
                      _decode_meta, _empty, _entries_flag, _eps, _host, _is_device_tensor, _new_meta, _ptr, _send, _solve_options,
                      _stack_strides, _starting_prices, batch_meta_to_host, raise_for_status)  # (the last two: also for import from here)
@@ -88,8 +94,157 @@ def dense_to_packed(mats, shapes=None, entries="nonneg"):
     return out
 
 
+def _reverse_finish_one(a, valid, p, p2o, eps, max_iter, trace=None):
+    """The reverse finish of one problem, in place: a, valid (n, mo) the maximised values and which of them are entries;
+    p (mo,) the prices; p2o (n,) the assignment, every row assigned; eps the forward solve's final eps.  Returns
+    (its, left).  Every operation is a float64 one, in the order csrc/kernels_dense_batch.hpp makes them.  trace: a list
+    that receives (j, i*, freed object, whether j was the object freed last) per iteration (-1: none)."""
+    n, mo = a.shape
+    o2p = np.full(mo, -1, dtype=np.int64)
+    o2p[p2o] = np.arange(n)
+    lam = p[p2o].min()
+    with np.errstate(invalid="ignore"):
+        pi = a[np.arange(n), p2o] - p[p2o]
+    cursor, nxt, its = 0, -1, 0
+    ninf = -np.inf
+    while True:
+        chained = nxt >= 0
+        if chained:
+            j, nxt = nxt, -1
+        else:
+            open_ = np.flatnonzero((o2p[cursor:] == -1) & (p[cursor:] > lam))
+            if open_.size == 0:
+                return its, 0
+            j = cursor + int(open_[0])
+            cursor = j + 1
+        if its >= max_iter:
+            return its, int(np.count_nonzero((o2p == -1) & (p > lam)))
+        its += 1
+        beta, omega, istar = ninf, ninf, -1
+        rows = np.flatnonzero(valid[:, j])
+        if rows.size:
+            w = a[rows, j] - pi[rows]
+            k = int(np.argmax(w))  # (the first maximum: the smallest row wins a tie)
+            if w[k] > ninf:
+                beta, istar = w[k], int(rows[k])
+                if rows.size > 1:
+                    omega = np.delete(w, k).max()  # (a second row at beta counts: omega == beta)
+        if istar < 0 or lam >= beta - eps:
+            p[j] = lam
+            if trace is not None:
+                trace.append((j, -1, -1, chained))
+            continue
+        t = omega - eps
+        p[j] = t if t > lam else lam
+        pi[istar] = a[istar, j] - p[j]
+        jo = int(p2o[istar])
+        o2p[jo], o2p[j], p2o[istar] = -1, istar, j
+        if p[jo] > lam:
+            nxt = jo
+        if trace is not None:
+            trace.append((j, istar, jo, chained))
+
+
+def dense_reverse_finish(mats, sol, prices, final_eps, problem="min", shapes=None, outside=None, outside_prices=None,
+                         entries="nonneg", max_iter=1000000, run=None, trace=None):
+    """The reverse-auction finish of auction_solve_batch(finish="reverse"), stated in numpy: its definition.
+
+    Takes the outputs of a forward solve -- sol int (B, N), prices float64 (B, M), with `outside` also outside_prices
+    float64 (B, N), and final_eps (B,): meta["final_eps_f32"], widened to float64 -- on the stack `mats` (a numpy array of
+    any float type or a tensor, as dense_to_packed takes it) under the same problem, shapes, outside and entries, and
+    runs on every problem b with run[b] the modified reverse auction with a fixed lambda (Bertsekas, Network
+    Optimization, 7.2).  run: bool (B,), what the call uses: status == 0 and n_assigned == n_rows; by default every
+    problem whose rows all hold an object.
+
+    One problem: a[i][j] is the maximised value of entry (i, j) -- the element widened to float64, times -1.0 for
+    problem="min" -- over the m_b real objects and, with outside, the object m_b + i of each row (its one entry is
+    (i, outside value of row i)); p the prices over the same objects; p2o the augmented assignment (a row on its outside
+    option holds m_b + i).  lambda = min_i p[p2o[i]], pi[i] = a[i][p2o[i]] - p[p2o[i]], cursor = 0.  Then, until no
+    unassigned object with p > lambda is left (left = 0) or max_iter iterations were made (left = their number):
+    j is the object the last iteration freed if that is still priced above lambda, else the first such object at or
+    behind the cursor (cursor = j + 1); over the rows i that have entry (i, j), in ascending i, w = a[i][j] - pi[i], beta
+    the largest (the smallest i wins a tie), omega the second largest (-inf without one); without an entry, or when
+    lambda >= beta - eps, p[j] = lambda; otherwise p[j] = max(lambda, omega - eps), pi[i*] = a[i*][j] - p[j], and row i*
+    moves to j, freeing its object.
+
+    Returns dict(sol, prices, [outside_prices], obj_f64, obj_f32, eCE, reverse=dict(its=int64 (B,), left=int32 (B,)), ran):
+    copies of the inputs rewritten where the finish ran (an outside object is -1 in sol), the objective summed in row
+    order as the solve sums it, eCE at target_eps = float32(1 / n_b) with the solve's tolerance 1e-7; its = left = -1 and
+    obj_f64 = NaN where it did not run (ran[b] False): nothing of such a problem changes.  Afterwards every row holds an
+    object within eps of its best net value, and every unassigned object is priced at or below lambda: the assignment is
+    optimal within n_b * eps, whatever prices the forward solve started from.  trace: an optional list that receives,
+    per iteration, (b, j, i* or -1, the object i* left or -1, whether j was the object freed by the iteration before)."""
+    flag = _entries_flag(entries)
+    if hasattr(mats, "cpu"):
+        mats = mats.double().cpu().numpy()
+    mats = np.asarray(mats)
+    if mats.ndim != 3:
+        raise ValueError(f"mats must have 3 dimensions (B, N, M), got {mats.ndim}")
+    B, N, M = mats.shape
+    shp = np.tile([N, M], (B, 1)) if shapes is None else np.asarray(_host(shapes))
+    sol = np.array(_host(sol), dtype=np.int32).reshape(B, N)
+    prices = np.array(_host(prices), dtype=np.float64).reshape(B, M)
+    eps_b = np.asarray(_host(final_eps)).astype(np.float64).reshape(B)
+    maximize = problem != "min"
+    o = None
+    if outside is not None:
+        o = np.asarray(_host(outside) if hasattr(outside, "cpu") else outside, dtype=np.float64)
+        if o.shape not in ((), (B,), (B, N)):
+            raise ValueError(f"outside must be a float or have shape ({B},) or ({B}, {N}), got {o.shape}")
+        o = np.broadcast_to(o if o.ndim != 1 else o[:, None], (B, N))
+        if outside_prices is None:
+            raise ValueError("with outside, the solve's outside_prices are needed")
+        outside_prices = np.array(_host(outside_prices), dtype=np.float64).reshape(B, N)
+    out = dict(sol=sol, prices=prices)
+    if o is not None:
+        out["outside_prices"] = outside_prices
+    its, left = np.full(B, -1, dtype=np.int64), np.full(B, -1, dtype=np.int32)
+    obj64, ece, ran = np.full(B, np.nan), np.zeros(B, dtype=np.int64), np.zeros(B, dtype=bool)
+    run = None if run is None else np.asarray(run.cpu() if hasattr(run, "cpu") else run).astype(bool).reshape(B)
+    for b in range(B):
+        n, m = (int(x) for x in shp[b])
+        if not (1 <= n <= N and 1 <= m <= M):
+            continue
+        p2o = sol[b, :n].astype(np.int64)
+        if o is not None:
+            p2o = np.where(p2o < 0, m + np.arange(n), p2o)
+        if (p2o < 0).any() or (run is not None and not run[b]):
+            continue
+        v = mats[b, :n, :m].astype(np.float64)
+        with np.errstate(invalid="ignore"):
+            valid = ~np.isnan(v) if flag else v >= 0
+        p = prices[b, :m].copy()
+        if o is not None:
+            d = np.zeros((n, n))
+            d[np.arange(n), np.arange(n)] = o[b, :n]
+            v, valid, p = np.hstack([v, d]), np.hstack([valid, np.eye(n, dtype=bool)]), np.concatenate([p, outside_prices[b, :n]])
+        a = v if maximize else v * -1.0
+        with np.errstate(invalid="ignore"):
+            steps = None if trace is None else []
+            its[b], left[b] = _reverse_finish_one(a, valid, p, p2o, eps_b[b], int(max_iter), steps)
+            if trace is not None:
+                trace.extend((b,) + t for t in steps)
+            ran[b] = True
+            sol[b, :n] = np.where(p2o < m, p2o, -1)
+            prices[b, :m] = p[:m]
+            if o is not None:
+                outside_prices[b, :n] = p[m:]
+            # eCE_satisfied at target_eps (auction_.pyx:443-485) and get_obj (:489-523), as the solve makes them
+            teps = float(np.float32(1.0 / np.float64(n)))
+            lhs = a[np.arange(n), p2o] - p[p2o] + 1e-7
+            ece[b] = 0 if (valid & (lhs[:, None] < (a - p[None, :]) - teps)).any() else 1
+            obj = 0.0
+            for i in range(n):
+                val = float(a[i, p2o[i]])
+                obj = obj + val if maximize else obj - val
+        obj64[b] = obj
+    out.update(obj_f64=obj64, obj_f32=obj64.astype(np.float32), eCE=ece, reverse=dict(its=its, left=left), ran=ran)
+    return out
+
+
 def auction_solve_batch(mats, problem="min", eps_start=0., max_iter=1000000, fast=None, cardinality_check=True,
-                        shapes=None, prices=None, errors="raise", mat_dtype="float64", outside=None, entries="nonneg"):
+                        shapes=None, prices=None, errors="raise", mat_dtype="float64", outside=None, entries="nonneg",
+                        finish=None):
     """Solve B independent dense problems in one call, one workgroup per problem.
 
     mats: float64 (or mat_dtype, below) (B, N, M), a numpy array or a tensor on the device (read in place, whatever its
@@ -173,9 +328,35 @@ def auction_solve_batch(mats, problem="min", eps_start=0., max_iter=1000000, fas
     is optimal within n * eps.  The reference's eps-scaling (fast=False, eps_start=0) keeps prices between phases and has no
     reverse phase: it gives the reference's answer on the augmented problem, which is NOT the optimum in general.  The
     same holds for every rectangular problem (n < m) of the batch solves.
+
+    finish: None (default) is the call described so far, in every respect.  finish="reverse" is for rectangular problems
+    (n_b < m_b, and every outside problem) that do NOT start from zero prices -- a tracker or a matcher that passes the
+    last frame's prices= -- or that run the reference's eps-scaling: the forward auction then ends with eps-CS but, in
+    general, far from the optimum, because objects that were bid up and abandoned keep prices above those of the objects
+    in use; status 0 and eCE = 1 do not show it.  Every solved problem (status 0, every row assigned) then gets the
+    reverse-auction clean-up behind its forward solve (misslap_dense_batch_reverse_finish: one more launch on the same
+    stream, one workgroup per problem, waiting for nothing): lambda = the smallest price of an assigned object, and every
+    unassigned object priced above lambda takes the row that values it most or drops to lambda.  Afterwards the
+    assignment still satisfies eps-CS at the solve's final eps and no unassigned object is priced above lambda: optimal
+    within n_b * final_eps from any starting prices and with any fast / eps_start.  The result is exactly
+    dense_reverse_finish (its docstring is the definition) applied to the outputs of the same call with finish=None:
+    sol, prices and outside_prices are rewritten, meta obj / obj_f64 and eCE recomputed, every other meta field stays the
+    forward solve's, and the result gains reverse=dict(its=int64 (B,), left=int32 (B,)): the iterations made (0 for a
+    square problem) and the unassigned objects still priced above lambda (0 unless max_iter, which is also the finish's
+    own budget, cut it); both -1 where the finish did not run -- status != 0, or max_iter cut the forward solve -- and
+    nothing of such a problem is touched.  It combines with every other keyword and with strided views; both errors=
+    modes run the status call, then the finish ("raise": then raise_for_status) and return the status-mode dict.  A numpy
+    stack is uploaded once, takes the device route and comes back as numpy arrays (meta as batch_meta_to_host gives it).
+    Cold solves should keep fast=True from zero prices: that needs no finish, and behind the reference's eps-scaling the
+    finish has far more to repair than a cold single phase has to do.  Any other value raises ValueError.
     """
     if errors not in ("raise", "status"):
         raise ValueError(f"errors must be 'raise' or 'status', got {errors!r}")
+    if finish is not None:
+        if not isinstance(finish, str) or finish != "reverse":
+            raise ValueError(f"finish must be None or 'reverse', got {finish!r}")
+        return _solve_with_finish(mats, problem, eps_start, max_iter, fast, cardinality_check, shapes, prices, errors,
+                                  mat_dtype, outside, entries)
     flag = _entries_flag(entries)
     B, N, M, on_device, dtype = _check_stack(mats, mat_dtype)
     dtype |= flag  # (the option word carries the rule: the element type OR-ed with MISSLAP_DENSE_ENTRIES_FINITE)
@@ -275,6 +456,48 @@ def _solve_outside(mats, B, N, M, on_device, problem, eps_start, max_iter, fast,
         _lib.check(lib.misslap_solve_dense_batch_outside_strided(B, N, M, *strides, *rest))
     own = dict(entries="finite") if finite else {}  # (raise_for_status words a bad outside value by the rule)
     return call.result((mats, shp, p, d_out), shapes=shp, stack=(N, M), outside=d_out, **own)
+
+
+def _reverse_finish_launch(stack, res, problem, max_iter, dtype):
+    """misslap_dense_batch_reverse_finish on the device result `res` of a status-mode call on the device stack `stack`
+    (dtype: its option word), on the call's stream: res's outputs are rewritten in place and res gains `reverse`."""
+    import torch
+    B, N, M = (int(d) for d in stack.shape)
+    dev = stack.device
+    opts = _solve_options(True, stack, problem, 0.0, max_iter, dtype)
+    with torch.cuda.device(dev):
+        its, left = _empty(B, np.int64, dev), _empty(B, np.int32, dev)
+    d_out = res.get("outside") if "outside_prices" in res else None
+    _lib.check(_lib.load().misslap_dense_batch_reverse_finish(
+        B, N, M, *(int(x) for x in stack.stride()), C.c_void_p(_ptr(stack)), _ptr(res["shapes"]), _ptr(d_out),
+        0 if d_out is None or d_out.dim() == 1 else N, C.byref(opts), C.c_void_p(int(res["stream"].cuda_stream)),
+        _ptr(res["status"]), _ptr(res["sol"]), _ptr(res["prices"]), _ptr(res.get("outside_prices")), _ptr(res["records"]),
+        _ptr(its), _ptr(left)))
+    res["reverse"] = dict(its=its, left=left)
+    return its, left
+
+
+def _solve_with_finish(mats, problem, eps_start, max_iter, fast, cardinality_check, shapes, prices, errors, mat_dtype,
+                       outside, entries):
+    """auction_solve_batch(finish="reverse"): the status-mode call of a device stack, then the reverse finish on its
+    outputs -- one more launch on the call's stream (misslap_dense_batch_reverse_finish), nothing is waited for.  A numpy
+    stack is uploaded once and its result brought back as numpy arrays."""
+    flag = _entries_flag(entries)
+    B, N, M, on_device, dtype = _check_stack(mats, mat_dtype)
+    stack = mats
+    if not on_device:
+        import torch
+        dev = torch.device("cuda", int(os.environ.get(_ENV_DEVICE, 0)))
+        stack = torch.from_numpy(np.ascontiguousarray(mats)).to(dev)
+    res = auction_solve_batch(stack, problem, eps_start, max_iter, fast, cardinality_check, shapes, prices, "status",
+                              mat_dtype, outside, entries)
+    its, left = _reverse_finish_launch(stack, res, problem, max_iter, dtype | flag)
+    if not on_device:
+        meta = batch_meta_to_host(res)  # (waits for the call's stream once)
+        res = {k: v for k, v in res.items() if k not in ("records", "info", "stream", "keep")}
+        res = {k: _host(v) if _is_device_tensor(v) else v for k, v in res.items()}
+        res.update(meta=meta, reverse=dict(its=_host(its), left=_host(left)))
+    return raise_for_status(res) if errors == "raise" else res
 
 
 def _status_error(res, b, code, n, m, card):
