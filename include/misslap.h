@@ -190,8 +190,10 @@ typedef struct misslap_meta {
     int32_t phases_with_lines;   /* eps-phases of the solve that ran WITH candidate lines (all of them unless eps fell below
                                     the rounding error of a price update on the way: see misslap_create) */
     int32_t eps_phases;          /* eps-phases of the solve (nreductions + 1 when it ran to its end) */
-    int32_t filter_undecided;    /* reserved, always -1 (the counter of round 5's opt-in fp32-tile filter scans, which were
-                                    measured slower than the exact scans and removed in round 6; the slot keeps the layout) */
+    int32_t filter_undecided;    /* full scans of the wave-per-row kernel that its fp32 filter could not decide (ties and
+                                    near-ties among a row's three best values: answered by the exact scan), saturating;
+                                    -1 where this solve ran without the filter: the handle has none, or the current values
+                                    or starting prices are outside its range (up to round 6 the slot was always -1) */
 } misslap_meta;
 
 /* Snapshot of the round state (tests / multi-GPU driver). */

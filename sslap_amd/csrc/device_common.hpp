@@ -77,6 +77,7 @@ struct Ctl {
     unsigned long long dbg[16]; // tail accounting: [0..2] rounds per mode, [3..5] 10-ns ticks, [12..15] bids / line hits /
                                 // builds / hit edges; [6..11] cycles per segment in -DMISSLAP_TAIL_STAMP* builds
     unsigned long long val_cnt[4]; // k_validity: distinct owned objects, sol < 0, sol >= n_rows, invalid selected entries
+    unsigned long long filter_undecided;  // full scans through the fp32 filter that went to the exact scan (wave_bid_filter)
 };
 
 // ---- live status ---------------------------------------------------------------------------------
@@ -237,6 +238,14 @@ __device__ __forceinline__ bool bid_is_bad(double bid) {
     const unsigned long long b = (unsigned long long)__double_as_longlong(bid);
     return b > 0x7ff0000000000000ull;
 }
+
+// A value as the handle stores it (create and update_values): negated for 'min' (auction_.pyx:236-237), and a zero always
+// as +0.0.  The solve orders a row's values  cost - p  by the high words of their bits ("winner first": cand_eval1_lane,
+// cand_eval2_lane, wave_bid_full, the pair rounds), where -0.0 sits one below +0.0 although the two are equal values and a
+// tie between them belongs to the later stored index like every tie.  cost - p is -0.0 only for a cost of -0.0 at a price
+// of +0.0 (prices are never -0.0), so with zeros stored as +0.0 no value is ever -0.0; every bid (costbest - w) + eps and
+// every price is the same number with the same bits either way.
+__device__ __forceinline__ double stored_cost(double v, int flip) { return flip ? 0.0 - v : v + 0.0; }
 
 __device__ __forceinline__ double shfl_xor_f64(double v, int off) {
     int lo = __double2loint(v), hi = __double2hiint(v);
@@ -962,10 +971,12 @@ __device__ __forceinline__ void wave_bid_lean(const E &ed, const Src &src, const
 //     row's two best edges, strictly: the bid is formed from their exact values (two fp64 gathers), best = the larger,
 //     the later stored index among equals (:351), w = the other (:357), bid = (cost - w) + eps (:360).
 //     otherwise (ties or near-ties at the top, rows of fewer than two finite values): the exact scan (wave_bid_lean).
-// `two_delta` = 2 delta as fp32 (+inf disables the filter for rows that have a finite third value).
+// `two_delta` = 2 delta as fp32 (+inf disables the filter for rows that have a finite third value).  `undecided` counts
+// the rows that went to the exact scan (wave-uniform; misslap_meta.filter_undecided).
 template <class E>
 __device__ __forceinline__ void wave_bid_filter(const E &ed, const double *price, const float *p32, const float two_delta,
-                                                const int s, const int e, const double eps, CandBid &out, int &err) {
+                                                const int s, const int e, const double eps, CandBid &out, int &err,
+                                                int &undecided) {
     const int lane = lane_id();
     const float ninf = -__builtin_huge_valf();
     float t1 = ninf, t2 = ninf, t3 = ninf;  // the lane's three largest a, and stored index / column / cost of the first two
@@ -1014,6 +1025,7 @@ __device__ __forceinline__ void wave_bid_filter(const E &ed, const double *price
     const float M3 = wave_max_f32(c3);
     const bool decided = (M2 > ninf) && ((M3 == ninf) || (M2 - M3 > two_delta));  // wave-uniform
     if (!decided) {
+        undecided += 1;
         wave_bid_lean(ed, PriceSource{price}, s, e, eps, out, err);
         return;
     }

@@ -77,12 +77,12 @@ __global__ __launch_bounds__(256) void k_ingest_vals(const double *val, long lon
     }
 }
 
-// flat_j copy (:229) + sign flip for 'min' (:236-237) into the streaming layout.
+// flat_j copy (:229) + sign flip for 'min' (:236-237) into the streaming layout (stored_cost: zeros as +0.0).
 __global__ __launch_bounds__(256) void k_build_edges_f32(const int *loc, const double *val, long long nnz, int flip,
                                                          int2 *edges) {
     const long long stride = (long long)gridDim.x * blockDim.x;
     for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < nnz; g += stride) {
-        const double v = flip ? val[g] * -1 : val[g];
+        const double v = stored_cost(val[g], flip);
         edges[g] = make_int2(loc[2 * g + 1], __float_as_int((float)v));
     }
 }
@@ -91,7 +91,7 @@ __global__ __launch_bounds__(256) void k_build_edges_f64(const int *loc, const d
     const long long stride = (long long)gridDim.x * blockDim.x;
     for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < nnz; g += stride) {
         col[g] = loc[2 * g + 1];
-        v64[g] = flip ? val[g] * -1 : val[g];
+        v64[g] = stored_cost(val[g], flip);
     }
 }
 
@@ -145,6 +145,7 @@ __global__ __launch_bounds__(256) void k_init_state(Ctl *ctl, double *price, Pri
         ctl->cand_edges = 0;
         ctl->tail_edges = 0;
         ctl->shard_edges = 0;
+        ctl->filter_undecided = 0;
         ctl->obj_abs = 0.0;
         ctl->obj_minexp = 1 << 20;
         ctl->n_need = 0;

@@ -64,6 +64,7 @@ struct RoundArgs {
 };
 constexpr int kStatEdges = 0, kStatBids = 1, kStatHits = 2, kStatHitEdges = 3, kStatShardEdges = 4, kStatLaunchEdges = 5,
               kStatLaunchHitEdges = 6,  // of kStatLaunchEdges: rows a candidate line answered (counted, never read)
+              kStatUndecided = 7,       // scans through the fp32 filter that fell back to the exact scan
               kStatWords = 8;
 
 __device__ __forceinline__ bool round_live(const Ctl *c, int thr) {
@@ -123,6 +124,7 @@ struct SrcOf<RecSource> {
 struct BidTally {
     unsigned long long edges = 0, hit_edges = 0;
     int nb = 0, nh = 0, err = 0;
+    int nu = 0;  // of the scans through the fp32 filter: undecided ones (wave_bid_filter)
 };
 // hand-over of bids between the workgroups of ONE launch (k_round_fused): device-scope relaxed atomics are performed
 // at the level all XCDs share (the XCDs' L2s are not coherent with each other, and a device-scope fence would write
@@ -168,7 +170,7 @@ __device__ __forceinline__ void bid_positions(const RoundArgs &a, const E &ed, i
                 // 2 delta = 2^-21 (max |cost| + max price): see wave_bid_filter; an infinite price (one-entry rows bid
                 // +inf) makes it infinite, which sends every row with a finite third value to the exact scan
                 const float two_delta = 0x1p-21f * (a.cmax + __int_as_float(*a.pmax_bits));
-                wave_bid_filter(ed, a.price, a.price32, two_delta, s, e, eps, b[0], tl.err);
+                wave_bid_filter(ed, a.price, a.price32, two_delta, s, e, eps, b[0], tl.err, tl.nu);
             } else {
                 wave_bid_lean(ed, src, s, e, eps, b[0], tl.err);
             }
@@ -201,23 +203,25 @@ template <int kWaves>
 __device__ __forceinline__ void tally_flush(const RoundArgs &a, const BidTally &tl, int K) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     __shared__ unsigned long long s_edges[kWaves], s_hedges[kWaves];
-    __shared__ int s_nb[kWaves], s_nh[kWaves];
+    __shared__ int s_nb[kWaves], s_nh[kWaves], s_nu[kWaves];
     if (lane == 0) {
         s_edges[wave] = tl.edges;
         s_hedges[wave] = tl.hit_edges;
         s_nb[wave] = tl.nb;
         s_nh[wave] = tl.nh;
+        s_nu[wave] = tl.nu;
         if (tl.err) atomicOr(&a.ctl->err, tl.err);
     }
     __syncthreads();
     if (threadIdx.x == 0) {
         unsigned long long te = 0, the = 0;
-        int tb = 0, th = 0;
+        int tb = 0, th = 0, tu = 0;
         for (int w = 0; w < kWaves; ++w) {
             te += s_edges[w];
             the += s_hedges[w];
             tb += s_nb[w];
             th += s_nh[w];
+            tu += s_nu[w];
         }
         if (tb) {
             unsigned long long *st = a.wg_stats + (size_t)kStatWords * blockIdx.x;
@@ -233,6 +237,8 @@ __device__ __forceinline__ void tally_flush(const RoundArgs &a, const BidTally &
                 st[kStatHitEdges] += the;
             }
         }
+        // (of its own: not tied to the bid count above)
+        if (tu) a.wg_stats[(size_t)kStatWords * blockIdx.x + kStatUndecided] += (unsigned long long)tu;
     }
 }
 
@@ -540,7 +546,7 @@ __device__ __forceinline__ unsigned long long block_sum_u64(unsigned long long v
 }
 __global__ __launch_bounds__(1024) void k_collect_stats(Ctl *ctl, unsigned long long *wg_stats, int n_slots) {
     __shared__ unsigned long long s_w[16];
-    unsigned long long v[5] = {0, 0, 0, 0, 0};
+    unsigned long long v[5] = {0, 0, 0, 0, 0}, vu = 0;
     for (int k = threadIdx.x; k < n_slots; k += 1024) {
         unsigned long long *st = wg_stats + (size_t)kStatWords * k;
 #pragma unroll
@@ -548,10 +554,14 @@ __global__ __launch_bounds__(1024) void k_collect_stats(Ctl *ctl, unsigned long 
             v[q] += st[q];
             st[q] = 0ull;
         }
+        vu += st[kStatUndecided];
+        st[kStatUndecided] = 0ull;
     }
     unsigned long long t[5];
     for (int q = 0; q < 5; ++q) t[q] = block_sum_u64(v[q], s_w);
+    const unsigned long long tu = block_sum_u64(vu, s_w);
     if (threadIdx.x == 0) {
+        ctl->filter_undecided += tu;
         ctl->edges += t[kStatEdges];
         ctl->bids += t[kStatBids];
         ctl->cand_hits += t[kStatHits];

@@ -59,7 +59,7 @@ __global__ __launch_bounds__(256) void k_update_check(E ed, const double *val, l
     int err = 0;
     const long long stride = (long long)gridDim.x * blockDim.x;
     for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < nnz; g += stride) {
-        const double v = flip ? val[g] * -1 : val[g];
+        const double v = stored_cost(val[g], flip);
         const unsigned long long b = (unsigned long long)__double_as_longlong(v) & 0x7fffffffffffffffull;
         if (b >= 0x7ff0000000000000ull) {
             err |= kErrNonFinite;
@@ -83,14 +83,14 @@ __global__ __launch_bounds__(256) void k_update_check(E ed, const double *val, l
 __global__ __launch_bounds__(256) void k_update_edges_f32(const double *val, long long nnz, int flip, int2 *edges) {
     const long long stride = (long long)gridDim.x * blockDim.x;
     for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < nnz; g += stride) {
-        const double v = flip ? val[g] * -1 : val[g];
+        const double v = stored_cost(val[g], flip);
         edges[g].y = __float_as_int((float)v);
     }
 }
 __global__ __launch_bounds__(256) void k_update_edges_f64(const double *val, long long nnz, int flip, double *v64) {
     const long long stride = (long long)gridDim.x * blockDim.x;
     for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < nnz; g += stride)
-        v64[g] = flip ? val[g] * -1 : val[g];
+        v64[g] = stored_cost(val[g], flip);
 }
 
 // Phase 2, tile-major copy: the values of every (person, tile) segment rewritten from the (already updated) row-major

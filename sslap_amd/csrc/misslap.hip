@@ -397,7 +397,9 @@ MISSLAP_API int misslap_finish(misslap_solver *h, int32_t *person_to_object_out,
     meta->tiled_format = h->tiled_ok ? h->tiled_fmt : 0;
     meta->phases_with_lines = h->phases_with_lines;
     meta->eps_phases = h->phases_run;
-    meta->filter_undecided = -1;  // (reserved: the slot of round 5's fp32-tile filter scans, removed in round 6)
+    // full scans through the fp32 filter of the wave-per-row kernel that went to the exact scan; -1: this solve had no
+    // filter (no mirror at create, or set_filter found max_abs / the starting prices outside its range)
+    meta->filter_undecided = h->price32 ? (int32_t)std::min<unsigned long long>(c.filter_undecided, 0x7fffffffull) : -1;
     if (h->profile && h->prof_used) {
         std::vector<unsigned long long> le(2 * (size_t)h->launch_idx);
         if (h->launch_idx)
