@@ -475,11 +475,10 @@ int launch_tail(misslap_solver *h) {
     // rows the long-row builder takes (it runs right behind the pass over all lines, on the list that pass leaves)
     const int long_max = !(lines && h->line_maintenance && h->long_rows) ? 0 : (h->max_row_len <= 256 * kLongPer ? 256 : 512) * kLongPer;
     const int min_alive_long = kLongRowMinAlive;
-    // every line checked at today's prices (kernels_round.hpp); then the rounds with more than kTeamMax bidders, with
-    // sixteen wavefronts (kernels_tail.hpp); then -- lines only -- the rounds with 3..kTeamMax bidders, one list slot
-    // per wavefront; then the rest: with lines the one-wavefront pair / chain instance, without them the 512-thread
-    // instance that holds every mode
-    // (inside a batch all three instances are launched whatever K: an instance that finds K outside its range returns
+    // every line checked at today's prices (kernels_round.hpp); then the tail's kernels by role (kernels_tail.hpp):
+    // k_tail_block for the rounds with more than kTeamMax bidders; then, with lines, k_tail_team for 3..kTeamMax bidders
+    // and k_tail_pair for the rest; without lines k_tail_nolines, which runs every mode
+    // (inside a batch all three kernels are launched whatever K: a kernel that finds K outside its range returns
     // at once, and the problems of a group then issue the same sequence of kernels, i.e. share every launch)
     const bool in_batch = h->batch != nullptr;
     if (in_batch) h->batch->hold_next = true;  // ... and the sequence waits for the other problems of the group (host_batch.hpp)
@@ -492,10 +491,10 @@ int launch_tail(misslap_solver *h) {
             if (h->max_row_len <= 256 * kLongPer) launch<k_refresh_long<E, 256>>(h, dim3(blocks_for(h->n_rows, 1)), round_args(h), ed);
             else launch<k_refresh_long<E, 512>>(h, dim3(blocks_for(h->n_rows, 1)), round_args(h), ed);
         }
-        if (h->K_ub > kTeamMax || in_batch) launch<k_tail<E, 2 * kTailMax>>(h, dim3(1), a, ed);
-        if ((h->K_ub > 2 || in_batch) && lines) launch<k_tail<E, 2 * kTailMax, true>>(h, dim3(1), a, ed);
-        if (lines) launch<k_tail<E, kWave>>(h, dim3(1), a, ed);
-        else launch<k_tail<E, kTailMax>>(h, dim3(1), a, ed);
+        if (h->K_ub > kTeamMax || in_batch) launch<k_tail_block<E>>(h, dim3(1), a, ed);
+        if ((h->K_ub > 2 || in_batch) && lines) launch<k_tail_team<E>>(h, dim3(1), a, ed);
+        if (lines) launch<k_tail_pair<E>>(h, dim3(1), a, ed);
+        else launch<k_tail_nolines<E>>(h, dim3(1), a, ed);
     };
     if (h->f32) tail(e32);
     else tail(e64);

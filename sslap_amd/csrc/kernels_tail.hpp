@@ -15,20 +15,21 @@
 // 30-wide record gather instead of the whole row and ~200 gathers; the dependent chain of a round is
 // line -> records -> 32-lane reduction -> next line.
 //
-// A round is a serial chain of dependent instructions per wavefront, so what makes it shorter is wavefronts: three
-// instances of k_tail by role, launched back to back once per phase (K only falls: block -> team -> solo):
-//   block (K > 16;  1024 threads): two list slots per wavefront and sweep (one per 32-lane half, one gather serves
-//         both), misses queued and scanned in a second pass; a clean round (no object bid on twice, none unowned: the
-//         test runs in front of the barrier) is finished by the threads = slots, any other by wavefront 0 (LDS hash table
-//         above 64 bidders);
-//   team  (3 <= K <= 16; 1024 threads): wavefront w serves slot w alone; ONE LDS-only barrier per round, every
+// A round is a serial chain of dependent instructions per wavefront, so what makes it shorter is wavefronts: one
+// kernel per role (at the end of this file; a mode is a function above them), launched back to back once per phase (K
+// only falls), each with the registers and the LDS of its role alone -- all roles in one kernel: 185 VGPRs, spills:
+//   k_tail_block (K > 16;  1024 threads): two list slots per wavefront and sweep (one per 32-lane half, one gather
+//         serves both), misses queued and scanned in a second pass; a clean round (no object bid on twice, none unowned:
+//         the test runs in front of the barrier) is finished by the threads = slots, any other by wavefront 0 (LDS hash
+//         table above 64 bidders);
+//   k_tail_team (3 <= K <= 16; 1024 threads): wavefront w serves slot w alone; ONE LDS-only barrier per round, every
 //         serving wavefront finishes the round for the whole list on lanes = slots;
-//   pair / chain (K <= 2; 64 threads): one wavefront, no barrier, no LDS; K = 2: both bidders' lines in the two
-//         32-lane halves, one evaluation for both (tail_pair_mode); K = 1: the chain.  (Solo mode -- the older form of
-//         the same idea -- is what the layout without lines uses for K = 2.)
-// The 512-thread instance still holds every mode (two slots per wavefront in team mode): a handle whose lines are
-// switched off runs in it alone (plus the block instance).  Both edge layouts keep lines; in the 12 B/edge layout a
-// slot's cost comes from a parallel line of fp64 costs (device_common.hpp: Slot64).
+//   k_tail_pair (K <= 2; 64 threads): one wavefront, no barrier, no LDS but the two list slots; K = 2: both bidders'
+//         lines in the two 32-lane halves, one evaluation for both (tail_pair_mode); K = 1: the chain;
+//   k_tail_nolines (512 threads), for a handle whose lines are switched off, behind k_tail_block: every mode (team
+//         mode with two slots per wavefront, solo mode -- the older form of the pair round -- for K = 2).
+// Both edge layouts keep lines; in the 12 B/edge layout a slot's cost comes from a parallel line of fp64 costs
+// (device_common.hpp: Slot64).
 //
 // Visibility: records / lines are written and re-read by this one workgroup only (same CU, same
 // vector L1, barriers between phases); the CSR is read-only.  No other workgroup runs.
@@ -48,7 +49,7 @@ struct TailArgs {
     int2 *cand;     // candidate lines (nullptr: none)
     double *cand64; // ... their fp64 costs (12 B/edge layout only, nullptr otherwise)
     int thr;
-    int round_budget;  // > 0: a kernel instance returns to the host after so many rounds (the host then refreshes the
+    int round_budget;  // > 0: a kernel returns to the host after so many rounds (the host then refreshes the
                        // lines of long rows, which the kernels cannot rebuild in place, and launches again); 0 = no limit
     float eps;
 };
@@ -173,6 +174,73 @@ __device__ __forceinline__ void tail_build(const TailArgs &a, int person, const 
     st.builds += 1;
 }
 
+// ---- the exact paths that several modes share; no clean round of any mode runs one of them ----------------------------
+// (left as they are: bid_two's scan, which rebuilds the line of a first miss in front of a second, and the block round's
+// push_all_left, which serves 64 slots through LDS)
+// A line did not decide: the bid by a full scan of the person's row [start, row_end), counted as a miss.  `bd` is what
+// the rebuild of the line needs (tail_build); when that runs is the caller's business.
+template <class E>
+__device__ __forceinline__ void tail_scan(const TailArgs &a, const E &ed, int start, int row_end, double eps, CandBid &b,
+                                          CandBuildArgs &bd, TailStats &st) {
+    const typename E::Raw none[4] = {};
+    wave_bid_full<E, RecSource, true, false>(ed, RecSource{a.rec}, start, row_end, none, eps, b, bd, st.err);
+    st.misses += 1;
+    st.miss_edges += (unsigned long long)b.len;
+}
+// RESOLVE (:375-385) on lanes = slots, all pairs via readlane: true where the lane's bid loses its object (strict ">":
+// the earlier list position keeps an object on equal bids)
+__device__ __forceinline__ bool lanes_lose(int obj, unsigned long long key, int K, int lane) {
+    bool lose = false;
+    for (int m = 0; m < K; ++m) {
+        const int om = __builtin_amdgcn_readlane(obj, m);
+        const bool same = (om == obj) && (m != lane);
+        if (__any(same)) {  // wave-uniform
+            const unsigned long long km = readlane_u64(key, m);
+            lose |= same && (km > key || (km == key && m < lane));
+        }
+    }
+    return lose;
+}
+// push_all_left (:137-162) on lanes = slots, K <= 63: lane l holds slot l's person `u` (-1: a hole) and its row start;
+// the k-th hole left of K' takes the k-th person right of it.  Returns K'.
+__device__ __forceinline__ int lanes_push_left(int &u, int &sx, bool act, int K, int lane) {
+    const unsigned long long kmask = (1ull << K) - 1ull;
+    const unsigned long long holes = __ballot(act && u == -1) & kmask;
+    const int Kn = K - __popcll(holes);
+    const unsigned long long lmask = (1ull << Kn) - 1ull;
+    unsigned long long hl = holes & lmask;            // empty slots left of K'
+    unsigned long long mv = ~holes & ~lmask & kmask;  // persons right of K'
+    while (hl) {  // wave-uniform
+        const int hk = __ffsll((long long)hl) - 1, mk = __ffsll((long long)mv) - 1;
+        const int mu = __builtin_amdgcn_readlane(u, mk), ms = __builtin_amdgcn_readlane(sx, mk);
+        if (lane == hk) {
+            u = mu;
+            sx = ms;
+        }
+        hl &= hl - 1;
+        mv &= mv - 1;
+    }
+    return Kn;
+}
+// RESOLVE (:375-385) on two slots that bid on ONE object: strict ">" -- the earlier list position keeps it on equal bids
+__device__ __forceinline__ void two_resolve(unsigned long long key0, unsigned long long key1, bool &win0, bool &win1) {
+    if (key1 > key0) win0 = false;
+    else win1 = false;
+}
+// ... behind ASSIGN (:396-418): a winner's slot goes to the evicted owner (:409) or becomes a hole (:412), a loser
+// stays; push_all_left (:137-162) on two slots.  Returns K.
+__device__ __forceinline__ int two_pass_on(int (&pi)[2], int (&ps)[2], bool win0, bool win1, const int (&prev)[2],
+                                           const int (&pst)[2]) {
+    if (win0) pi[0] = prev[0], ps[0] = pst[0];
+    if (win1) pi[1] = prev[1], ps[1] = pst[1];
+    if (pi[0] == -1 && pi[1] != -1) pi[0] = pi[1], ps[0] = ps[1], pi[1] = -1;
+    return (pi[0] != -1) + (pi[1] != -1);
+}
+// ... and, when a two-slot mode ends, the two slots go back to the list
+__device__ __forceinline__ void two_hand_back(int *sU, int *sStart, const int (&pi)[2], const int (&ps)[2]) {
+    if (lane_id() == 0) sU[0] = pi[0], sU[1] = pi[1], sStart[0] = ps[0], sStart[1] = ps[1];
+}
+
 // The bids of the wavefront's two persons (auction_.pyx:339-365): both lines by one gather, then a full scan for
 // every person whose line did not decide.  `early(b)` is cand_eval2's hook (the winners' owners are known).  The
 // rebuild of the (last) scanned person's line is left to the caller (bd / bd_person), who first publishes the bids
@@ -275,14 +343,12 @@ __device__ __forceinline__ void tail_chain_mode(const TailArgs &a, const E &ed, 
             CandBid b;
             CandBuildArgs bd;
             if (E::kCand) {
-                const typename E::Raw none[4] = {};
-                const int e = a.row_ptr[pi + 1];
-                wave_bid_full<E, RecSource, true, false>(ed, src, ps, e, none, eps, b, bd, st.err);
+                tail_scan(a, ed, ps, a.row_ptr[pi + 1], eps, b, bd, st);
             } else {
                 wave_bid_full<E, RecSource, true, true>(ed, src, ps, ev, row, eps, b, bd, st.err);
+                st.misses += 1;
+                st.miss_edges += (unsigned long long)b.len;
             }
-            st.misses += 1;
-            st.miss_edges += (unsigned long long)b.len;
             if (bd.want && lines) tail_build(a, pi, bd, eps, st);
             store = lane == 0;
             bid = key_to_bid(b.key);
@@ -339,11 +405,7 @@ __device__ __forceinline__ void tail_solo_mode(const TailArgs &a, const E &ed, i
     ps[1] = K > 1 ? __builtin_amdgcn_readfirstlane(sStart[1]) : 0;
     if (K == 1) {
         tail_chain_mode(a, ed, pi[0], ps[0], K, nits, max_iter, eps, st);
-        if (lane == 0) {
-            sU[0] = pi[0];
-            sU[1] = -1;
-            sStart[0] = ps[0];
-        }
+        two_hand_back(sU, sStart, pi, ps);
         return;
     }
     TwoFetch<E> tf;
@@ -370,32 +432,14 @@ __device__ __forceinline__ void tail_solo_mode(const TailArgs &a, const E &ed, i
         }, stamp);
         stamp.light(5);  // full scans of missed persons done
         nits += 1;
-        // RESOLVE (:375-385): strict ">" -- the earlier list position keeps an object on equal bids
+        // RESOLVE (:375-385), ASSIGN (:396-418) by lane 0, then the slots pass on
         bool win0 = true, win1 = pi[1] >= 0;
-        if (win1 && b[0].obj == b[1].obj) {
-            if (b[1].key > b[0].key) win0 = false;
-            else win1 = false;
-        }
-        // ASSIGN (:396-418): a winner's slot goes to the evicted owner (or becomes a hole), a loser stays
+        if (win1 && b[0].obj == b[1].obj) two_resolve(b[0].key, b[1].key, win0, win1);
         if (lane == 0) {
             if (win0) apply_winner(a, pi[0], ps[0], b[0].obj, b[0].prev, b[0].key);
             if (win1) apply_winner(a, pi[1], ps[1], b[1].obj, b[1].prev, b[1].key);
         }
-        if (win0) {
-            pi[0] = b[0].prev;
-            ps[0] = b[0].pstart;
-        }
-        if (win1) {
-            pi[1] = b[1].prev;
-            ps[1] = b[1].pstart;
-        }
-        // push_all_left (:137-162) on two slots
-        if (pi[0] == -1 && pi[1] != -1) {
-            pi[0] = pi[1];
-            ps[0] = ps[1];
-            pi[1] = -1;
-        }
-        K = (pi[0] != -1) + (pi[1] != -1);
+        K = two_pass_on(pi, ps, win0, win1, {b[0].prev, b[1].prev}, {b[0].pstart, b[1].pstart});
         const bool done = K <= 1 || nits >= max_iter;
         // the early request assumed "both bidders win, nobody moves"; otherwise (a scanned row, a lost bid, the
         // end of a chain) request again
@@ -409,12 +453,7 @@ __device__ __forceinline__ void tail_solo_mode(const TailArgs &a, const E &ed, i
     if (lane == 0)
         for (int k = 1; k <= 6; ++k) a.ctl->dbg[5 + k] += sacc[k];
 #endif
-    if (lane == 0) {
-        sU[0] = pi[0];
-        sU[1] = pi[1];
-        sStart[0] = ps[0];
-        sStart[1] = ps[1];
-    }
+    two_hand_back(sU, sStart, pi, ps);
 }
 
 // lane-wise values that a round forms under its record gather: the empty statement defines them at this point of the
@@ -549,11 +588,7 @@ __device__ __forceinline__ void tail_pair_mode(const TailArgs &a, const E &ed, i
             for (int X = 0; X < 2; ++X) {
                 if (!b[X].hit) {
                     CandBuildArgs bd;
-                    const typename E::Raw none[4] = {};
-                    const int e = a.row_ptr[pi[X] + 1];
-                    wave_bid_full<E, RecSource, true, false>(ed, src, ps[X], e, none, eps, b[X], bd, st.err);
-                    st.misses += 1;
-                    st.miss_edges += (unsigned long long)b[X].len;
+                    tail_scan(a, ed, ps[X], a.row_ptr[pi[X] + 1], eps, b[X], bd, st);
                     if (bd.want) tail_build(a, pi[X], bd, eps, st);
                 }
                 o[X] = b[X].obj;
@@ -590,11 +625,9 @@ __device__ __forceinline__ void tail_pair_mode(const TailArgs &a, const E &ed, i
             // RESOLVE (:375-385): strict ">" -- the earlier list position keeps an object on equal bids.  The keys are read
             // out of the lanes here, where they are needed
             bool win0 = true, win1 = true;
-            if (o[0] == o[1]) {
-                if (bid_to_key(readlane_f64(bid, sl[1])) > bid_to_key(readlane_f64(bid, sl[0]))) win0 = false;
-                else win1 = false;
-            }
-            // ASSIGN (:396-418): a winner's slot goes to the evicted owner (or becomes a hole), a loser stays
+            if (o[0] == o[1])
+                two_resolve(bid_to_key(readlane_f64(bid, sl[0])), bid_to_key(readlane_f64(bid, sl[1])), win0, win1);
+            // ASSIGN (:396-418) stays lane-wise: the winners' lanes store from their own registers
             if (store & (upper ? win1 : win0)) {
                 PriceRec n;
                 n.price = bid;
@@ -602,21 +635,7 @@ __device__ __forceinline__ void tail_pair_mode(const TailArgs &a, const E &ed, i
                 n.ostart = psL;
                 a.rec[(unsigned)obj] = n;
             }
-            if (win0) {
-                pi[0] = prev[0];
-                ps[0] = pst[0];
-            }
-            if (win1) {
-                pi[1] = prev[1];
-                ps[1] = pst[1];
-            }
-            // push_all_left (:137-162) on two slots
-            if (pi[0] == -1 && pi[1] != -1) {
-                pi[0] = pi[1];
-                ps[0] = ps[1];
-                pi[1] = -1;
-            }
-            K = (pi[0] != -1) + (pi[1] != -1);
+            K = two_pass_on(pi, ps, win0, win1, prev, pst);
         }
         const bool done = K <= 1 || r >= rmax;
         // the early request assumed "both bidders win, nobody moves"; otherwise (a scanned row that decided differently
@@ -631,12 +650,7 @@ __device__ __forceinline__ void tail_pair_mode(const TailArgs &a, const E &ed, i
         for (int k = 1; k <= 6; ++k) a.ctl->dbg[5 + k] += sacc[k];
 #endif
     if (K == 1 && nits < max_iter) tail_chain_mode(a, ed, pi[0], ps[0], K, nits, max_iter, eps, st);
-    if (lane == 0) {
-        sU[0] = pi[0];
-        sU[1] = pi[1];
-        sStart[0] = ps[0];
-        sStart[1] = ps[1];
-    }
+    two_hand_back(sU, sStart, pi, ps);
 }
 
 // ---- team mode: 3 <= K <= 16 -----------------------------------------------------------------------------------
@@ -757,36 +771,11 @@ __device__ __forceinline__ void tail_team_mode(const TailArgs &a, const E &ed, i
                 }
             } else {
                 // RESOLVE / ASSIGN / push_all_left in full, on lanes = slots
-                bool lose = false;
-                for (int m = 0; m < K; ++m) {  // :375-385, all pairs via readlane
-                    const int om = __builtin_amdgcn_readlane(lobj, m);
-                    const bool same = (om == lobj) && (m != lane);
-                    if (__any(same)) {  // wave-uniform
-                        const unsigned long long km = readlane_u64(lkey, m);
-                        lose |= same && (km > lkey || (km == lkey && m < lane));
-                    }
-                }
-                const bool won = act && !lose;
+                const bool won = act && !lanes_lose(lobj, lkey, K, lane);
                 if (won && n0 < K) apply_winner(a, u, sx, lobj, lprev, lkey);  // :396-418 (serving wavefronts only)
                 u = won ? lprev : u;  // the evicted owner inherits the slot (:409) / hole (:412) / a loser stays
                 sx = won ? lpst : sx;
-                const unsigned long long kmask = (1ull << K) - 1ull;
-                const unsigned long long holes = __ballot(act && u == -1) & kmask;
-                const int Kn = K - __popcll(holes);
-                const unsigned long long lmask = (1ull << Kn) - 1ull;
-                unsigned long long hl = holes & lmask;            // empty slots left of K'
-                unsigned long long mv = ~holes & ~lmask & kmask;  // persons right of K'
-                while (hl) {  // wave-uniform: k-th hole <- k-th mover (:137-162)
-                    const int hk = __ffsll((long long)hl) - 1, mk = __ffsll((long long)mv) - 1;
-                    const int mu = __builtin_amdgcn_readlane(u, mk), ms = __builtin_amdgcn_readlane(sx, mk);
-                    if (lane == hk) {
-                        u = mu;
-                        sx = ms;
-                    }
-                    hl &= hl - 1;
-                    mv &= mv - 1;
-                }
-                K = Kn;
+                K = lanes_push_left(u, sx, act, K, lane);
 #pragma unroll
                 for (int X = 0; X < 2; ++X) {
                     pi[X] = n0 + X < K ? __builtin_amdgcn_readlane(u, min(n0 + X, kWave - 1)) : -1;
@@ -875,8 +864,8 @@ __device__ __forceinline__ bool tail_team1_pipe(const TailArgs &a, const E &ed, 
     const RecSource src{a.rec};
     const bool cls = (lane >= 1) & (lane <= kCandMax);
     const int n0 = wave;  // my slot
-    int pi = n0 < K ? __builtin_amdgcn_readfirstlane(sU[min(n0, kTailMax - 1)]) : -1;
-    int ps = n0 < K ? __builtin_amdgcn_readfirstlane(sStart[min(n0, kTailMax - 1)]) : 0;
+    int pi = n0 < K ? __builtin_amdgcn_readfirstlane(sU[min(n0, kTeamMax - 1)]) : -1;  // (the list has kTeamMax slots)
+    int ps = n0 < K ? __builtin_amdgcn_readfirstlane(sStart[min(n0, kTeamMax - 1)]) : 0;
     for (int h = threadIdx.x; h < kPipeTab; h += blockDim.x) L.tab[h] = -1;  // (round numbers are >= 0)
     if (threadIdx.x < 2) L.dirty[threadIdx.x] = -1;
     typename E::Slot slot = cand_no_line<typename E::Slot>();
@@ -931,11 +920,7 @@ __device__ __forceinline__ bool tail_team1_pipe(const TailArgs &a, const E &ed, 
                        // block); the scan's result is wave-uniform and lane 0 publishes it
             CandBid b;
             CandBuildArgs bd;
-            const typename E::Raw none[4] = {};
-            const int e = a.row_ptr[pi + 1 + lane_zero()];
-            wave_bid_full<E, RecSource, true, false>(ed, src, ps, e, none, eps, b, bd, st.err);
-            st.misses += 1;
-            st.miss_edges += (unsigned long long)b.len;
+            tail_scan(a, ed, ps, a.row_ptr[pi + 1 + lane_zero()], eps, b, bd, st);
             if (bd.want) tail_build(a, pi, bd, eps, st);
             publish = lane == 0;
             bid = key_to_bid(b.key);
@@ -995,36 +980,11 @@ __device__ __forceinline__ bool tail_team1_pipe(const TailArgs &a, const E &ed, 
                 const int lprev = act ? laux.y : 0, lpst = act ? laux.z : 0;
                 int u = act ? lrec.owner : -1;  // the list: lane l holds slot l
                 int sx = act ? lrec.ostart : 0;
-                bool lose = false;
-                for (int m = 0; m < K; ++m) {  // :375-385, all pairs via readlane
-                    const int om = __builtin_amdgcn_readlane(lo, m);
-                    const bool same = (om == lo) && (m != lane);
-                    if (__any(same)) {  // wave-uniform
-                        const unsigned long long km = readlane_u64(lkey, m);
-                        lose |= same && (km > lkey || (km == lkey && m < lane));
-                    }
-                }
-                const bool won = act && !lose;
+                const bool won = act && !lanes_lose(lo, lkey, K, lane);
                 if (won) apply_winner(a, u, sx, lo, lprev, lkey);  // :396-418
                 u = won ? lprev : u;  // the evicted owner inherits the slot (:409) / hole (:412) / a loser stays
                 sx = won ? lpst : sx;
-                const unsigned long long kmask = (1ull << K) - 1ull;
-                const unsigned long long holes = __ballot(act && u == -1) & kmask;
-                const int Kn = K - __popcll(holes);
-                const unsigned long long lmask = (1ull << Kn) - 1ull;
-                unsigned long long hl = holes & lmask;            // empty slots left of K'
-                unsigned long long mv = ~holes & ~lmask & kmask;  // persons right of K'
-                while (hl) {  // wave-uniform: k-th hole <- k-th mover (:137-162)
-                    const int hk = __ffsll((long long)hl) - 1, mk = __ffsll((long long)mv) - 1;
-                    const int mu = __builtin_amdgcn_readlane(u, mk), ms = __builtin_amdgcn_readlane(sx, mk);
-                    if (lane == hk) {
-                        u = mu;
-                        sx = ms;
-                    }
-                    hl &= hl - 1;
-                    mv &= mv - 1;
-                }
-                K = Kn;
+                K = lanes_push_left(u, sx, act, K, lane);
                 pi = n0 < K ? __builtin_amdgcn_readlane(u, min(n0, kWave - 1)) : -1;
                 ps = n0 < K ? __builtin_amdgcn_readlane(sx, min(n0, kWave - 1)) : 0;
             }
@@ -1071,14 +1031,14 @@ __device__ __forceinline__ bool tail_team1_pipe(const TailArgs &a, const E &ed, 
 // The table lives in hKey, the key array of the exact path's own hash table (64 < K): both are empty at zero, the exact
 // path empties the array before it inserts and leaves it empty.  A table of its own (32 KB more) takes the workgroup's
 // LDS beyond 64 KB, where an address no longer fits the LDS instructions' offset field and every array costs an address
-// register: the 1024-thread instances then spill (16 .. 60 bytes of scratch per lane).
+// register: the 1024-thread kernels then spill (16 .. 60 bytes of scratch per lane).
 constexpr int kCleanTab = kHashSize;
 constexpr int kCleanProbes = 8;
 static_assert(2 * kCleanTab == kPipeTab, "clean_hash: pipe_hash's top 11 bits");
 __device__ __forceinline__ int clean_hash(int obj) { return pipe_hash(obj) >> 1; }
 // The thread's slot index, formed HERE: the LDS addresses of a block of slot-indexed accesses are then computed inside the
 // block, from one register and the arrays' offsets.  Left to itself the compiler forms one address register per array ahead of
-// the round loop and keeps them all for the whole kernel, which the 1024-thread instances (128 VGPRs) pay with spills.
+// the round loop and keeps them all for the whole kernel, which the 1024-thread kernels (128 VGPRs) pay with spills.
 __device__ __forceinline__ int slot_index_here(int t) {
     asm volatile("" : "+v"(t));
     return t;
@@ -1101,182 +1061,156 @@ __device__ __forceinline__ bool clean_insert(unsigned long long *tab, unsigned t
     return true;
 }
 
-// kThreads = kTailMax (512): every mode.  kThreads = 1024 ("block only"): the rounds with more than kTeamMax bidders
-// with SIXTEEN wavefronts -- half the sweeps per wavefront in pass A, which is where a block round spends its time --
-// and nothing else: the solo / team code needs more than the 128 registers a 1024-thread workgroup leaves a
-// wavefront.  The host launches it ahead of the 512-thread kernel, which then finds K <= kTeamMax.
-// kTeamOnly (1024 threads as well): the rounds with 3..kTeamMax bidders, one slot per wavefront (tail_team1_pipe).
-// kThreads = 64 ("pair / chain only", handles with lines): the rounds with K <= 2 and nothing else, on one wavefront
-// (tail_pair_mode, then tail_chain_mode); the instance that carries every mode needs 185 VGPRs and spills 14 SGPRs,
-// each spill a v_writelane / v_readlane pair inside a chain that is bound by its instruction count.
-template <class E, int kThreads, bool kTeamOnly = false>
-struct k_tail {
-    MISSLAP_KERNEL(kThreads)
-    static __device__ __forceinline__ void run(TailArgs a, E ed) {
-        static_assert(!kTeamOnly || (kThreads == 2 * kTailMax && kThreads / kWave == kTeamMax), "one slot per wavefront");
-        constexpr bool kBlockOnly = kThreads > kTailMax && !kTeamOnly;
-        constexpr bool kDuoOnly = kThreads == kWave;
-        static_assert(!kDuoOnly || !kTeamOnly, "roles are exclusive");
-        __shared__ int sU[kTailMax];
-        __shared__ unsigned long long sKey[kTailMax];
-        __shared__ int sObj[kTailMax];
-        __shared__ int sPrev[kTailMax];
-        __shared__ int sStart[kTailMax];  // row start of the person in slot n, kept next to sU: evicted owners bring
-                                          // theirs with the price record, so no row_ptr load precedes a row fetch
-        __shared__ int sPst[kTailMax];    // row start of the owner of the object slot n bid on
-        __shared__ int sList[kTailMax];
-        __shared__ int hObj[kHashSize];
-        __shared__ unsigned long long hKey[kHashSize];
-        __shared__ int hPos[kHashSize];
-        __shared__ int sCnt[3][kThreads / kWave];
-        unsigned long long *const cTab = hKey;  // block rounds: the clean table (clean_insert)
-        __shared__ unsigned sHit[kTailMax];  // tag of the last block round in which pass A published the slot (a line hit)
-        __shared__ unsigned sDirty;  // tag of the last block round that needs the exact RESOLVE / ASSIGN / push_all_left
-        __shared__ int sK, sMissCnt;
-        __shared__ long long sNits;
+// ---- what every tail kernel does at its start and at its end -------------------------------------------------------------
+// what a kernel carries from tail_begin to tail_end
+struct TailRun {
+    int K, K0;
+    long long nits, nits0, max_iter;
+    double eps;
+    TailStats st;
+    // per-mode accounting (always on: two s_memrealtime reads per mode entry -- block mode: per ROUND; bracketing a whole
+    // run of block rounds instead was measured 1.3 ms per C3 solve slower, profiles/tail_block_lane.txt --, 100 MHz
+    // ticks), Ctl::dbg:
+    //   [0..2] rounds in chain + pair + solo / team / block mode, [3..5] ticks
+    unsigned long long md[6];
+    __device__ __forceinline__ void mode_begin(int m) {
+        md[3 + m] -= __builtin_amdgcn_s_memrealtime();
+        md[m] -= (unsigned long long)nits;
+    }
+    __device__ __forceinline__ void mode_end(int m) {
+        md[3 + m] += __builtin_amdgcn_s_memrealtime();
+        md[m] += (unsigned long long)nits;
+    }
+};
 
-        Ctl *ctl = a.ctl;
-        const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-        constexpr int nwaves = kThreads / kWave;
-        int K = ctl->K;
-        long long nits = ctl->nits;
-        const long long max_iter =
-            a.round_budget > 0 ? min(ctl->max_iter, nits + (long long)(kBlockOnly ? max(a.round_budget / 4, 1) : a.round_budget))
-                               : ctl->max_iter;  // (block rounds have the most bidders, i.e. spend the most lines)
-        if (K == 0 || K > a.thr || nits >= max_iter) return;  // uniform
-        if (kBlockOnly && K <= kTeamMax) return;
-        if (kTeamOnly && (K <= 2 || K > kTeamMax)) return;
-        if (kDuoOnly && (K > 2 || !E::kCand || a.cand == nullptr)) return;
-        // (budgeted launches: an instance that ran out of rounds leaves K to the NEXT launch's instance of the right role)
-        if (!kBlockOnly && !kTeamOnly && a.round_budget > 0 && K > 2 && E::kCand && a.cand != nullptr) return;
-        const int K0 = K;
-        const long long nits0 = nits;
-        for (int n = t; n < kTailMax; n += kThreads) {
-            sU[n] = (n < K) ? a.U[n] : -1;
-            sStart[n] = (n < K) ? a.row_ptr[sU[n]] : 0;
+// a wavefront's statistics, once, when it leaves the kernel (whole wavefronts call)
+__device__ __forceinline__ void tail_flush_stats(Ctl *ctl, TailStats &st) {
+    const bool bad_bid = __any(bad_hi_is_error(st.bad_hi));  // (the lane-wise rounds keep the maximum per lane)
+    if ((threadIdx.x & 63) == 0) {
+        if (st.bids) {
+            const unsigned long long hits = (unsigned long long)(st.bids - st.misses), hit_edges = st.edges - st.miss_edges;
+            atomicAdd(&ctl->edges, st.edges);
+            atomicAdd(&ctl->tail_edges, st.edges);
+            atomicAdd(&ctl->bids, (unsigned long long)st.bids);
+            if (hits) {
+                atomicAdd(&ctl->cand_hits, hits);
+                atomicAdd(&ctl->cand_edges, hit_edges);
+            }
+            atomicAdd(&ctl->dbg[12], (unsigned long long)st.bids);  // the tail's own totals: bids, line hits, line builds
+            atomicAdd(&ctl->dbg[13], hits);
+            atomicAdd(&ctl->dbg[14], st.builds);
+            atomicAdd(&ctl->dbg[15], hit_edges);
         }
-        if (!kDuoOnly && !kTeamOnly)
-            for (int n = t; n < kTailMax; n += kThreads) sHit[n] = 0u;  // (round tags are >= 1)
-        if (!kDuoOnly)
-            for (int h = t; h < kHashSize; h += kThreads) {
-                hObj[h] = -1;
-                hKey[h] = 0ull;
-                hPos[h] = kPosNone;
-            }
-        if (!kDuoOnly && !kTeamOnly && t == 0) sDirty = 0u;  // (round tags are >= 1; hKey = the clean table is empty at zero)
-        const double eps = (double)a.eps;
-        TailStats st;
-        st.edges = st.miss_edges = st.builds = 0ull;
-        st.bids = st.misses = st.bad_hi = 0u;
-        st.err = 0;
-        st.hint = 0.0;
-        if (t == 0) sMissCnt = 0;
-        __syncthreads();
+        if (bad_bid) st.err |= kErrNegativeBid;
+        if (st.err) atomicOr(&ctl->err, st.err);
+    }
+}
 
-        // per-mode accounting (always on: two s_memrealtime reads per mode entry -- block mode: per ROUND; bracketing a whole
-        // run of block rounds instead was measured 1.3 ms per C3 solve slower, profiles/tail_block_lane.txt --, 100 MHz
-        // ticks), Ctl::dbg:
-        //   [0..2] rounds in chain + solo / team / block mode, [3..5] ticks
-        unsigned long long md[6] = {0, 0, 0, 0, 0, 0};
-#ifdef MISSLAP_TAIL_STAMP_BLOCK
-        unsigned long long bacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#endif
-        auto mode_begin = [&](int m) {
-            md[3 + m] -= __builtin_amdgcn_s_memrealtime();
-            md[m] -= (unsigned long long)nits;
-        };
-        auto mode_end = [&](int m) {
-            md[3 + m] += __builtin_amdgcn_s_memrealtime();
-            md[m] += (unsigned long long)nits;
-        };
-        auto flush_stats = [&]() {  // a wavefront's statistics, once, when it leaves the kernel (whole wavefronts call)
-            const bool bad_bid = __any(bad_hi_is_error(st.bad_hi));  // (the lane-wise rounds keep the maximum per lane)
-            if (lane == 0) {
-                if (st.bids) {
-                    const unsigned long long hits = (unsigned long long)(st.bids - st.misses), hit_edges = st.edges - st.miss_edges;
-                    atomicAdd(&ctl->edges, st.edges);
-                    atomicAdd(&ctl->tail_edges, st.edges);
-                    atomicAdd(&ctl->bids, (unsigned long long)st.bids);
-                    if (hits) {
-                        atomicAdd(&ctl->cand_hits, hits);
-                        atomicAdd(&ctl->cand_edges, hit_edges);
-                    }
-                    atomicAdd(&ctl->dbg[12], (unsigned long long)st.bids);  // the tail's own totals: bids, line hits, line builds
-                    atomicAdd(&ctl->dbg[13], hits);
-                    atomicAdd(&ctl->dbg[14], st.builds);
-                    atomicAdd(&ctl->dbg[15], hit_edges);
-                }
-                if (bad_bid) st.err |= kErrNegativeBid;
-                if (st.err) atomicOr(&ctl->err, st.err);
-            }
-        };
-        // block rounds: the round's tag in cTab / sDirty, and -- sixteen wavefronts, handles with lines -- per covered sweep
-        // the line of the person who takes the sweep's slot of the lane's half if its bidder wins (`enp`; -2: none requested).
-        // kEarlySweeps: how many sweeps of a round are covered; 0, 1, 2 and all 6 were measured (profiles/tail_block_clean.txt).
-        // MISSLAP_TAIL_BLOCK_EARLY_SWEEPS is the build switch of that A/B, like the MISSLAP_TAIL_STAMP_* ones
-        // (tools/build_ab.sh es2 "-DMISSLAP_TAIL_BLOCK_EARLY_SWEEPS=2"); above 1 the 12 B/edge k_batched_ptr instance spills.
+// The start: K / nits, the launch's last round (`budget` > 0: so many rounds from here; 0: no limit), the entry tests
+// -- false: these rounds are not this kernel's, return at once; inside a batch every kernel is launched whatever K is,
+// and under a budget a kernel that ran out of rounds leaves K to the NEXT launch's kernel of the right role --, the list
+// into sU / sStart[0, slots), the statistics zeroed.  The caller sets its own LDS and closes with the barrier.
+__device__ __forceinline__ bool tail_begin(const TailArgs &a, int budget, int k_lo, int k_hi, int *sU, int *sStart,
+                                           int slots, int threads, TailRun &r) {
+    const Ctl *ctl = a.ctl;
+    r.K = ctl->K;
+    r.nits = ctl->nits;
+    r.max_iter = budget > 0 ? min(ctl->max_iter, r.nits + (long long)budget) : ctl->max_iter;
+    if (r.K == 0 || r.K > a.thr || r.nits >= r.max_iter) return false;  // uniform
+    if (r.K < k_lo || r.K > k_hi) return false;                          // another kernel's rounds
+    r.K0 = r.K;
+    r.nits0 = r.nits;
+    for (int n = threadIdx.x; n < slots; n += threads) {
+        sU[n] = (n < r.K) ? a.U[n] : -1;
+        sStart[n] = (n < r.K) ? a.row_ptr[sU[n]] : 0;
+    }
+    r.eps = (double)a.eps;
+    r.st = TailStats{};  // (all zero)
+    for (int k = 0; k < 6; ++k) r.md[k] = 0ull;
+    return true;
+}
+
+// The end (every thread that is still here): the mode counters, the list back to U[0, K0), the statistics, K / nits
+__device__ __forceinline__ void tail_end(const TailArgs &a, const int *sU, int threads, TailRun &r) {
+    Ctl *ctl = a.ctl;
+    const int t = threadIdx.x;
+    if (t == 0)
+        for (int k = 0; k < 6; ++k) ctl->dbg[k] += r.md[k];
+    for (int n = t; n < r.K0; n += threads) a.U[n] = sU[n];
+    tail_flush_stats(ctl, r.st);
+    if (t == 0) {
+        ctl->K = r.K;
+        ctl->nits = r.nits;
+        ctl->tail_rounds += r.nits - r.nits0;
+    }
+}
+
+// ---- block mode: K > kTeamMax ------------------------------------------------------------------------------------------
+// MISSLAP_TAIL_BLOCK_EARLY_SWEEPS is the build switch of the early-sweep A/B, like the MISSLAP_TAIL_STAMP_* ones
+// (tools/build_ab.sh es2 "-DMISSLAP_TAIL_BLOCK_EARLY_SWEEPS=2"); above 1 the 12 B/edge k_batched_ptr kernel spills.
 #ifndef MISSLAP_TAIL_BLOCK_EARLY_SWEEPS
 #define MISSLAP_TAIL_BLOCK_EARLY_SWEEPS 1
 #endif
-        constexpr int kEarlySweeps = (kBlockOnly && E::kCand) ? MISSLAP_TAIL_BLOCK_EARLY_SWEEPS : 0;
-        constexpr bool kEarly = kEarlySweeps > 0;
-        constexpr int kEarlyN = kEarly ? kEarlySweeps : 1;
+constexpr int kEarlySweeps = MISSLAP_TAIL_BLOCK_EARLY_SWEEPS;  // 0, 1, 2 and all 6 were measured (profiles/tail_block_clean.txt)
+constexpr int kEarlyN = kEarlySweeps > 0 ? kEarlySweeps : 1;
+
+// Block rounds until K <= kTeamMax (the next mode takes over), K == 0 or max_iter, on the list sU / sStart[kTailMax].
+// kThreads = 1024: SIXTEEN wavefronts -- half the sweeps per wavefront in pass A, which is where a block round spends its
+// time; 512: eight, with three sweeps in flight together.  `early_sweeps` (a constant at both call sites): for how many
+// sweeps of a round the next lines are requested early; k_tail_block: kEarlySweeps, k_tail_nolines: 0.
+// The mode's LDS is declared here, as in the team modes: the two kernels that run block rounds carry it and nobody else
+// (a struct like those kernels: the round below stands as it stood in k_tail::run).
+template <class E, int kThreads>
+struct tail_block_mode {
+    static __device__ __forceinline__ void run(const TailArgs &a, const E &ed, int *sU, int *sStart, TailRun &r,
+                                               const int early_sweeps) {
+        __shared__ unsigned long long sKey[kTailMax];  // per list slot: the bid's key, its object, the object's owner and
+        __shared__ int sObj[kTailMax];                 // that owner's row start
+        __shared__ int sPrev[kTailMax];
+        __shared__ int sPst[kTailMax];
+        __shared__ int sList[kTailMax];  // the slots queued for the scan pass; the exact paths' list of holes
+        __shared__ int hObj[kHashSize];  // the exact paths' hash table (64 < K), keyed by object
+        __shared__ unsigned long long hKey[kHashSize];
+        __shared__ int hPos[kHashSize];
+        __shared__ int sCnt[3][kThreads / kWave];
+        __shared__ unsigned sHit[kTailMax];  // tag of the last block round in which pass A published the slot (a line hit)
+        __shared__ unsigned sDirty;  // tag of the last block round that needs the exact RESOLVE / ASSIGN / push_all_left
+        __shared__ int sK, sMissCnt;
+        unsigned long long *const cTab = hKey;  // the clean table (clean_insert)
+        const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+        constexpr int nwaves = kThreads / kWave;
+        int &K = r.K;
+        long long &nits = r.nits;
+        const long long max_iter = r.max_iter;
+        const double eps = r.eps;
+        TailStats &st = r.st;
+        // emptied once per launch: no round resets anything it leaves empty
+        for (int n = t; n < kTailMax; n += kThreads) sHit[n] = 0u;  // (round tags are >= 1)
+        for (int h = t; h < kHashSize; h += kThreads) {
+            hObj[h] = -1;
+            hKey[h] = 0ull;
+            hPos[h] = kPosNone;
+        }
+        if (t == 0) sDirty = 0u, sMissCnt = 0;  // (round tags are >= 1; hKey = the clean table is empty at zero)
+        __syncthreads();
+#ifdef MISSLAP_TAIL_STAMP_BLOCK
+        unsigned long long bacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#endif
+        // the round's tag in cTab / sDirty, and -- sixteen wavefronts, handles with lines -- per covered sweep the line of
+        // the person who takes the sweep's slot of the lane's half if its bidder wins (`enp`; -2: none requested)
+        const bool early = early_sweeps > 0;
         unsigned rtag = 0u;
         unsigned long long nclean = 0ull;  // clean block rounds of this launch -> Ctl::dbg[6] (tail_stats[10])
-        typename E::Slot el[kEarlyN];  // (set where block rounds exist: the other instances stay what they were, instruction for instruction)
+        typename E::Slot el[kEarlyN];
         int enp[kEarlyN];
-        if (!kDuoOnly && !kTeamOnly) {
 #pragma unroll
-            for (int q = 0; q < kEarlyN; ++q) {
-                el[q] = cand_no_line<typename E::Slot>();
-                enp[q] = -2;
-            }
+        for (int q = 0; q < kEarlyN; ++q) {
+            el[q] = cand_no_line<typename E::Slot>();
+            enp[q] = -2;
         }
         for (;;) {
-            if (kBlockOnly && K <= kTeamMax) break;  // the next kernel takes over
-            if (kDuoOnly) {
-                // ---- K <= 2, lines: wavefront 0 alone, pair rounds while two bidders are left, then the chain
-                mode_begin(0);
-                tail_pair_mode(a, ed, sU, sStart, K, nits, max_iter, eps, st);
-                mode_end(0);
-                break;  // K == 0 or nits == max_iter
-            }
-            if (kTeamOnly) {
-                if (K > 2 && nits < max_iter) {
-                    mode_begin(1);
-                    if (tail_team1_pipe(a, ed, sU, sStart, K, nits, max_iter, eps, st)) {  // (this wavefront's slot fell away)
-                        flush_stats();
-                        return;
-                    }
-                    mode_end(1);
-                }
-                break;
-            }
-            if (!kBlockOnly && K <= 2) {
-                // ---- solo mode: wavefront 0 runs the rest of the phase alone, see tail_solo_mode
-                if (wave == 0) {
-                    mode_begin(0);
-                    tail_solo_mode(a, ed, sU, sStart, K, nits, max_iter, eps, st);
-                    mode_end(0);
-                    if (lane == 0) {
-                        sK = K;
-                        sNits = nits;
-                    }
-                }
-                __syncthreads();
-                K = sK;
-                nits = sNits;
-                break;  // K == 0 or nits == max_iter
-            }
-            if (!kBlockOnly && K <= kTeamMax) {
-                // ---- team mode: every wavefront, until K <= 2 (or max_iter), see tail_team_mode
-                mode_begin(1);
-                tail_team_mode(a, ed, sU, sStart, K, nits, max_iter, eps, st);
-                mode_end(1);
-                if (K == 0 || nits >= max_iter) break;
-                continue;
-            }
-            // ---- block mode, BID in two passes.  Pass A: the lines, two list slots per wavefront (one per 32-lane
+            if (K <= kTeamMax) break;  // the next mode takes over
+            // ---- BID in two passes.  Pass A: the lines, two list slots per wavefront (one per 32-lane
             // half, one gather serves both); a hit goes straight to LDS, a miss is queued.  Pass B: the queued persons,
             // one wavefront each, by a full scan of their rows (+ line rebuild).  Between the passes the thread that holds a
             // published slot enters its object into the clean table (a scanned slot's: its scanner) and raises sDirty for a
@@ -1285,11 +1219,11 @@ struct k_tail {
             // (ASSIGN of every bidder, the slot passes to the evicted owner; K and the order stay), every other round by
             // the exact RESOLVE / ASSIGN / push_all_left below.
             // In a clean round slot n's next bidder is the owner in the publishing lane's gathered record, and slot n
-            // stays with its wavefront: the first sweep's next lines are requested when the winners are known (kEarly)
+            // stays with its wavefront: the first sweep's next lines are requested when the winners are known (early)
             // and are in flight across the LDS-only barriers of both passes, the finish and the closing barrier.  The next
             // round takes such a line only where it belongs to the person its slot then holds -- whatever the round turned
             // out to be; that person did not bid in this round (it owned an object), so no scan pass rebuilt its line.
-            mode_begin(2);
+            r.mode_begin(2);
             rtag += 1u;
 #ifdef MISSLAP_TAIL_STAMP_BLOCK
             // diagnostic build: cycles of wavefront 0 per segment of a block round -> Ctl::dbg[6..11]: [6] lines landed
@@ -1308,7 +1242,7 @@ struct k_tail {
                 // other -- the two memory latencies are paid once per group of sweeps, not once per sweep
                 // (sixteen wavefronts -- four per SIMD -- hide the two latencies by themselves: measured per block round
                 // 3.51 us with one sweep in flight, 3.69 with two, 3.96 with three, 4.06 with four)
-                constexpr int kBlockDepth = kBlockOnly ? 1 : 3;
+                constexpr int kBlockDepth = kThreads > kTailMax ? 1 : 3;
                 const int wv = __builtin_amdgcn_readfirstlane(wave);  // (a scalar: the tests on a wavefront's slots are branches)
                 for (int base = 0; base < K; base += kBlockDepth * 2 * nwaves) {
                     typename E::Slot sl[kBlockDepth];
@@ -1319,7 +1253,7 @@ struct k_tail {
                         const int pme = nme < K ? sU[min(nme, kTailMax - 1)] : -1;
                         sl[c] = cand_no_line<typename E::Slot>();
                         if (E::kCand && a.cand != nullptr) {
-                            if (kEarly && c == 0 && base < kEarlySweeps * 2 * nwaves) {  // (wave-uniform) the line requested in the round before
+                            if (early && c == 0 && base < early_sweeps * 2 * nwaves) {  // (wave-uniform) the line requested in the round before
                                 int ep = -2;
 #pragma unroll
                                 for (int q = 0; q < kEarlyN; ++q)
@@ -1353,7 +1287,7 @@ struct k_tail {
                         w.hm = 0ull;
                         w.len[0] = w.len[1] = 0;
                         if (E::kCand) cand_eval2_lane(sl[c], rr[c], true, n0 + 1 < K, eps, w, st.bad_hi);
-                        if (kEarly && c == 0 && base < kEarlySweeps * 2 * nwaves) {  // (wave-uniform) the next lines of my two slots
+                        if (early && c == 0 && base < early_sweeps * 2 * nwaves) {  // (wave-uniform) the next lines of my two slots
                             int o = -2;
                             const bool both = a.cand != nullptr && __popcll(w.hm) == 2;
                             if (both) {
@@ -1404,15 +1338,15 @@ struct k_tail {
                     bstamp.light(3);  // (a sweep's evaluation is billed to [8], not to the next sweep's "lines landed")
 #endif
                 }
-                // (kEarly: LDS-only barriers around the scan pass, so that the requested lines stay in flight.  Pass A
+                // (early: LDS-only barriers around the scan pass, so that the requested lines stay in flight.  Pass A
                 // stores nothing to memory; the scan pass stores rebuilt lines, which nobody reads before the closing
                 // barrier; and every record gather of the round has landed before its wavefront published the bid.)
-                if (kEarly) tail_barrier_lds();
+                if (early) tail_barrier_lds();
                 else __syncthreads();
                 bstamp(3);
                 // the clean test of the slots that pass A published, by the threads = slots (three wavefronts at K = 192,
                 // next to the scan pass: inside the sweeps it would cost every wavefront a divergent loop per sweep, and
-                // the registers of one -- the 1024-thread instances then spill); a scanned slot's is its scanner's
+                // the registers of one -- the 1024-thread kernels then spill); a scanned slot's is its scanner's
                 // (the three LDS reads are issued together: one LDS latency in front of the insert, not three)
                 if (t < K) {
                     const int ts = slot_index_here(t);
@@ -1426,11 +1360,9 @@ struct k_tail {
                     const int n = __builtin_amdgcn_readfirstlane(sList[m]);
                     const int i = __builtin_amdgcn_readfirstlane(sU[n]);
                     const int s0 = __builtin_amdgcn_readfirstlane(sStart[n]);
-                    const typename E::Raw none[4] = {};
-                    const int ev = a.row_ptr[i + 1 + lane_zero()];
                     CandBid bm;
                     CandBuildArgs ba;
-                    wave_bid_full<E, RecSource, true, false>(ed, src, s0, ev, none, eps, bm, ba, st.err);
+                    tail_scan(a, ed, s0, a.row_ptr[i + 1 + lane_zero()], eps, bm, ba, st);
                     ba.want = ba.want && a.cand != nullptr;
                     if (lane == 0) {
                         sKey[n] = bm.key;
@@ -1439,15 +1371,13 @@ struct k_tail {
                         sPst[n] = bm.pstart;
                     }
                     st.edges += (unsigned long long)bm.len;
-                    st.miss_edges += (unsigned long long)bm.len;
                     st.bids += 1;
-                    st.misses += 1;
                     if (ba.want) tail_build(a, i, ba, eps, st);
                     // the scanned slot's clean test (behind the rebuild: what the rebuild holds in registers is dead here)
                     if (lane == 0 && (clean_insert(cTab, rtag, bm.obj) || bm.prev < 0)) sDirty = rtag;
                 }
             }
-            if (kEarly) tail_barrier_lds();
+            if (early) tail_barrier_lds();
             else __syncthreads();
             bstamp(4);
 
@@ -1481,7 +1411,6 @@ struct k_tail {
                     // RESOLVE (:375-385).  Two bidders on one object are the exception: every bidder inserts its object
                     // into the (empty) LDS hash table with one compare-and-swap; only if some insert meets its own object
                     // -- a contested object -- is the all-pairs loop run.  The table is emptied again right away.
-                    bool lose = false;
                     int hs = 0;
                     bool dup = false;
                     if (act) {
@@ -1500,16 +1429,7 @@ struct k_tail {
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                     __builtin_amdgcn_wave_barrier();
                     if (act && !dup) hObj[hs] = -1;
-                    if (contested) {
-                        for (int m = 0; m < K; ++m) {  // all pairs via readlane
-                            const int om = __builtin_amdgcn_readlane(obj, m);
-                            const bool same = (om == obj) && (m != lane);
-                            if (__any(same)) {  // wave-uniform
-                                const unsigned long long km = readlane_u64(key, m);
-                                lose |= same && (km > key || (km == key && m < lane));
-                            }
-                        }
-                    }
+                    const bool lose = contested && lanes_lose(obj, key, K, lane);
                     int u = act ? sU[ln] : -1;
                     int sx = act ? sStart[ln] : 0;  // row start travelling with the slot's person
                     if (act && !lose) {
@@ -1630,29 +1550,108 @@ struct k_tail {
             bstamp(6);
             if (!clean) K = sK;
             nits += 1;
-            mode_end(2);
+            r.mode_end(2);
             if (K == 0 || nits >= max_iter) break;
         }
-        if (t == 0)
-            for (int k = 0; k < 6; ++k) ctl->dbg[k] += md[k];
 #ifdef MISSLAP_TAIL_STAMP_BLOCK
         if (t == 0)
-            for (int k = 1; k <= 6; ++k) ctl->dbg[5 + k] += bacc[k];
+            for (int k = 1; k <= 6; ++k) a.ctl->dbg[5 + k] += bacc[k];
 #endif
 #if !defined(MISSLAP_TAIL_STAMP) && !defined(MISSLAP_TAIL_STAMP_SOLO) && !defined(MISSLAP_TAIL_STAMP_DUO) && \
     !defined(MISSLAP_TAIL_STAMP_TEAM) && !defined(MISSLAP_TAIL_STAMP_BLOCK) && !defined(MISSLAP_TILED_STAMP)
-        if (!kDuoOnly && !kTeamOnly && t == 0) ctl->dbg[6] += nclean;  // (the stamped builds use the slot for a segment)
+        if (t == 0) a.ctl->dbg[6] += nclean;  // (the stamped builds use the slot for a segment)
 #endif
-
-        for (int n = t; n < K0; n += kThreads) a.U[n] = sU[n];
-        flush_stats();
-        if (t == 0) {
-            ctl->K = K;
-            ctl->nits = nits;
-            ctl->tail_rounds += nits - nits0;
-        }
     }
 };
 
+// ---- the four kernels: entry tests and list (tail_begin), the role's LDS, its modes, tail_end ------------------------------
+// K > kTeamMax.  Block rounds have the most bidders, i.e. spend the most lines: a quarter of a launch's round budget.
+template <class E>
+struct k_tail_block {
+    MISSLAP_KERNEL(2 * kTailMax)
+    static __device__ __forceinline__ void run(TailArgs a, E ed) {
+        __shared__ int sU[kTailMax];
+        __shared__ int sStart[kTailMax];  // row start of the person in slot n, kept next to sU: evicted owners bring
+                                          // theirs with the price record, so no row_ptr load precedes a row fetch
+        TailRun r;
+        const int budget = a.round_budget > 0 ? max(a.round_budget / 4, 1) : 0;
+        if (!tail_begin(a, budget, kTeamMax + 1, kTailMax, sU, sStart, kTailMax, kBlock, r)) return;
+        tail_block_mode<E, kBlock>::run(a, ed, sU, sStart, r, E::kCand ? kEarlySweeps : 0);  // (opens with a barrier)
+        tail_end(a, sU, kBlock, r);
+    }
+};
+
+// 3 <= K <= kTeamMax, handles with lines: one list slot per wavefront
+template <class E>
+struct k_tail_team {
+    MISSLAP_KERNEL(2 * kTailMax)
+    static_assert(kBlock / kWave == kTeamMax, "one slot per wavefront");
+    static __device__ __forceinline__ void run(TailArgs a, E ed) {
+        __shared__ int sU[kTeamMax];
+        __shared__ int sStart[kTeamMax];
+        TailRun r;
+        if (!tail_begin(a, a.round_budget, 3, kTeamMax, sU, sStart, kTeamMax, kBlock, r)) return;
+        __syncthreads();
+        r.mode_begin(1);
+        if (tail_team1_pipe(a, ed, sU, sStart, r.K, r.nits, r.max_iter, r.eps, r.st)) {
+            tail_flush_stats(a.ctl, r.st);  // this wavefront's slot fell away: it ends here, with its statistics
+            return;
+        }
+        r.mode_end(1);
+        tail_end(a, sU, kBlock, r);
+    }
+};
+
+// K <= 2, handles with lines: one wavefront, pair rounds while two bidders are left, then the chain
+template <class E>
+struct k_tail_pair {
+    MISSLAP_KERNEL(kWave)
+    static __device__ __forceinline__ void run(TailArgs a, E ed) {
+        __shared__ int sU[2];
+        __shared__ int sStart[2];
+        TailRun r;
+        if (!E::kCand || a.cand == nullptr) return;  // no lines: k_tail_nolines' rounds
+        if (!tail_begin(a, a.round_budget, 1, 2, sU, sStart, 2, kBlock, r)) return;
+        __syncthreads();
+        r.mode_begin(0);
+        tail_pair_mode(a, ed, sU, sStart, r.K, r.nits, r.max_iter, r.eps, r.st);
+        r.mode_end(0);  // K == 0 or nits == max_iter
+        tail_end(a, sU, kBlock, r);
+    }
+};
+
+// Every K, for a handle whose lines are switched off (launched for no other): block -> team -> solo / chain.  The team
+// and solo modes of this kernel need more than the 128 registers a 1024-thread workgroup leaves a wavefront.
+template <class E>
+struct k_tail_nolines {
+    MISSLAP_KERNEL(kTailMax)
+    static __device__ __forceinline__ void run(TailArgs a, E ed) {
+        __shared__ int sU[kTailMax];
+        __shared__ int sStart[kTailMax];
+        __shared__ int sK;
+        __shared__ long long sNits;
+        TailRun r;
+        if (!tail_begin(a, a.round_budget, 1, kTailMax, sU, sStart, kTailMax, kBlock, r)) return;
+        __syncthreads();
+        if (r.K > kTeamMax) tail_block_mode<E, kBlock>::run(a, ed, sU, sStart, r, 0);
+        if (r.K > 2 && r.nits < r.max_iter) {  // every wavefront, until K <= 2 (or max_iter)
+            r.mode_begin(1);
+            tail_team_mode(a, ed, sU, sStart, r.K, r.nits, r.max_iter, r.eps, r.st);
+            r.mode_end(1);
+        }
+        if (r.K > 0 && r.nits < r.max_iter) {  // K <= 2: wavefront 0 runs the rest of the phase alone
+            if (threadIdx.x < kWave) {
+                r.mode_begin(0);
+                tail_solo_mode(a, ed, sU, sStart, r.K, r.nits, r.max_iter, r.eps, r.st);
+                r.mode_end(0);
+                if (threadIdx.x == 0) sK = r.K, sNits = r.nits;
+            }
+            __syncthreads();
+            r.K = sK;
+            r.nits = sNits;
+        }
+        tail_end(a, sU, kBlock, r);
+    }
+};
 
 }  // namespace misslap

@@ -17,9 +17,9 @@ from sslap_amd import AuctionSolver, from_sparse
 
 pytestmark = pytest.mark.gpu
 
-# (input, solver options).  cand: default / 2 = lines without the maintenance pass (more misses) / False = no lines (the
-# 512-thread instance takes every tail mode, default threshold 40); tail_threshold 16: the small round hands straight to
-# team, 512: the block instance and its hash table serve 193..512; tiled_min_k=1, engine=1: the tile engine on the grid
+# (input, solver options).  cand: default / 2 = lines without the maintenance pass (more misses) / False = no lines
+# (k_tail_nolines takes every tail mode, default threshold 40); tail_threshold 16: the small round hands straight to
+# team, 512: k_tail_block and its hash table serve 193..512; tiled_min_k=1, engine=1: the tile engine on the grid
 # side of the 2048 hand-off.
 VARIANTS = [
     ("f32max", {}), ("f32max", dict(cand=2)), ("f32max", dict(cand=False)), ("f32max", dict(tail_threshold=16)),

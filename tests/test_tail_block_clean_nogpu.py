@@ -96,11 +96,16 @@ def test_tail_kernels_fit_their_registers(built_lib, tmp_path):
     subprocess.check_call([os.path.join(llvm, "clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + fat,
                            "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + elf])
     notes = subprocess.run([os.path.join(llvm, "llvm-readelf"), "--notes", elf], capture_output=True, text=True, check=True).stdout
-    kernels = [k for k in re.split(r"\n  - \.agpr_count:", notes) if re.search(r"\.name:\s+\S*6k_tailI", k)]
-    assert len(kernels) >= 24  # 2 layouts x 4 instances x (entry, k_batched, k_batched_ptr)
+    roles = ("12k_tail_blockI", "11k_tail_teamI", "11k_tail_pairI", "14k_tail_nolinesI")
+    kernels = [k for k in re.split(r"\n  - \.agpr_count:", notes) if re.search(r"\.name:\s+\S*\d+k_tail_\w+I", k)]
+    assert len(kernels) >= 24  # 2 layouts x 4 kernels x (entry, k_batched, k_batched_ptr)
     field = lambda k, name: int(re.search(r"\.%s:\s+(\d+)" % name, k).group(1))
-    for k in kernels:
-        name = re.search(r"\.name:\s+(\S+)", k).group(1)
+    names = [re.search(r"\.name:\s+(\S+)", k).group(1) for k in kernels]
+    for role in roles:  # each kernel for both layouts, by itself and in both batched wrappers
+        for layout in ("8EdgesF32E", "8EdgesF64E"):
+            for wrapper in ("_ZN7misslap%s", "_ZN7misslap9k_batchedINS_%s", "_ZN7misslap13k_batched_ptrINS_%s"):
+                assert any(n.startswith(wrapper % role + "NS_" + layout) for n in names), (role, layout, wrapper)
+    for k, name in zip(kernels, names):
         assert field(k, "private_segment_fixed_size") == 0 and field(k, "vgpr_spill_count") == 0, name
         if field(k, "max_flat_workgroup_size") == 1024:
             assert field(k, "vgpr_count") <= 128, name
