@@ -1,14 +1,17 @@
 #!/usr/bin/env python3
 """Randomized parity run of the SHARDED solve on one GPU: W rank threads (sslap_amd.dist.ThreadGroup / Comm.in_process:
 the library's own loop and exchange calls, buffers reduced on the host), random instances and option mixes; every
-rank's assignment, round count and prices against the oracle.  usage: fuzz_sharded.py [first_seed] [count]"""
+rank's assignment, meta and final state against the oracle; a mismatch names the first field of the state that differs
+(tests/_round_modes.py: state_diff).  usage: fuzz_sharded.py [first_seed] [count]"""
 import os
 import sys
 import threading
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden"))
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
 import numpy as np
 import cases
+import _round_modes as rm
 from oracle import oracle as orc
 from sslap_amd import from_sparse, synth
 from sslap_amd.dist import Comm, ThreadGroup, solve_sharded
@@ -48,10 +51,12 @@ for seed in range(first, first + count):
             comm = Comm.in_process(rank, group)
             s = from_sparse(loc, val.copy(), shard=(rank, world), **kw, **gpu)
             sol = solve_sharded(s, comm)
-            sg = s.state()
-            res[rank] = (np.array_equal(sol, osol) and all(s.meta[k] == o.meta[k] for k in cases.META_KEYS)
-                         and np.array_equal(sg["p"].view(np.uint64), so["p"].view(np.uint64)),
-                         int(s.gpu.get("sharded_rounds", 0)))
+            diff = rm.state_diff(s.state(), so)  # None, or the first differing field
+            if diff is None and not np.array_equal(sol, osol):
+                diff = "returned assignment"
+            if diff is None:
+                diff = next(("meta " + k for k in cases.META_KEYS if s.meta[k] != o.meta[k]), None)
+            res[rank] = (diff is None, int(s.gpu.get("sharded_rounds", 0)), diff)
         except Exception as e:  # noqa: BLE001
             errs.append((rank, repr(e)))
             group.abort()
@@ -63,7 +68,7 @@ for seed in range(first, first + count):
     ok = not errs and len(res) == world and all(v[0] for v in res.values())
     if not ok:
         bad += 1
-        print("MISMATCH", seed, world, n, m, density * m, ints, kw, gpu, errs[:2], {k: v for k, v in res.items()}, flush=True)
+        print("MISMATCH", seed, world, n, m, density * m, ints, kw, gpu, errs[:2], {k: v[2] for k, v in sorted(res.items())}, flush=True)
     elif seed % 10 == 0:
         print("ok", seed, "W", world, n, m, "its", o.meta["its"], "sharded rounds", res[0][1], flush=True)
 print(f"done {count} sharded solves, {bad} mismatches")
