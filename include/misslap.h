@@ -701,9 +701,15 @@ int misslap_solve_dense_batch_outside_strided(int64_t B, int64_t N, int64_t M, i
  *                  obj_f32 are recomputed in the reference's row order and meta[b].eCE at target_eps = 1 / n_b; every other
  *                  field of meta[b] stays the forward solve's.
  *   reverse_its    int64[B]: the iterations made (0 for a square problem), -1 where the finish did not run
- *   reverse_left   int32[B]: the unassigned objects still priced above lambda -- 0 unless max_iter cut the finish --, -1
- *                  where it did not run (status != 0, or max_iter cut the forward solve before every row was assigned:
- *                  nothing of that problem is touched). */
+ *   reverse_left   int32[B]: the unassigned objects still priced above lambda -- 0 unless max_iter cut the finish or a
+ *                  stalled iteration ended it --, -1 where it did not run (status != 0, or max_iter cut the forward
+ *                  solve before every row was assigned: nothing of that problem is touched).
+ *                  A stalled iteration: the move found would not raise the moving row's profit, a[i*][j] - p_j > pi[i*]
+ *                  is false for p_j = max(lambda, omega - eps).  In exact arithmetic every move raises it by at least
+ *                  eps; it happens only where eps is lost to rounding, outside max(|a|, |p|) * 2^-52 < final_eps.  The
+ *                  iteration is counted, nothing is written, and the finish ends with reverse_left > 0 (the object of
+ *                  that iteration included): outside that range the finish promises nothing and a caller reads
+ *                  reverse_left, since status stays 0 and eCE may be 1. */
 int misslap_dense_batch_reverse_finish(int64_t B, int64_t N, int64_t M, int64_t stride_b, int64_t stride_n, int64_t stride_m,
                                        const void *mat, const int32_t *shapes, const double *outside, int64_t outside_ld,
                                        const misslap_options *opt, void *stream, const int32_t *status, int32_t *sol,

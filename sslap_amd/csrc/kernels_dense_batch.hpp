@@ -553,6 +553,9 @@ __global__ __launch_bounds__(1024) void k_dense_outside_solve(DenseOutsideArgs<L
 // repairs exactly that: lambda = the smallest price of an assigned object, and every unassigned object priced above it
 // either takes the row that values it most (at a price that keeps eps-CS) or drops to lambda.  Afterwards eps-CS still
 // holds at the solve's final eps and no unassigned object is priced above lambda: optimal within n * eps.
+// Every move raises the moving row's profit by at least eps, which ends the loop; where eps is lost to rounding
+// (outside max(|a|, |p|) * 2^-52 < eps) a move can leave it unchanged, so an iteration whose move would not raise it
+// ends the finish with left > 0 (the stall rule of sslap_amd.dense_reverse_finish).
 //
 // One workgroup per problem, its own launch behind the solve's, reading the solve's outputs: status first (a problem
 // whose status is not 0 is not touched, so a caller's bad device shape is never read), then meta.n_assigned (a solve
@@ -777,6 +780,14 @@ __global__ __launch_bounds__(kDenseFinishThreads) void k_dense_reverse_finish(De
             } else {
                 const double t = ow - eps;
                 const double pj = t > lam ? t : lam;
+                if (!(ba - pj > pi[bi])) {  // a stall (uniform): eps is lost to rounding, the move would not raise the
+                                            // row's profit.  Nothing is written; what is left, j included
+                    for (int base = 0; base < mo; base += kWave) {
+                        const int c = base + lane;
+                        left += __popcll(__ballot(c < mo && o2p[c] == -1 && p[c] > lam));
+                    }
+                    break;
+                }
                 const int jo = p2o[bi];
                 const double pjo = p[jo];
                 if (lane == 0) {

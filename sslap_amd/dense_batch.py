@@ -98,7 +98,8 @@ def _reverse_finish_one(a, valid, p, p2o, eps, max_iter, trace=None):
     """The reverse finish of one problem, in place: a, valid (n, mo) the maximised values and which of them are entries;
     p (mo,) the prices; p2o (n,) the assignment, every row assigned; eps the forward solve's final eps.  Returns
     (its, left).  Every operation is a float64 one, in the order csrc/kernels_dense_batch.hpp makes them.  trace: a list
-    that receives (j, i*, freed object, whether j was the object freed last) per iteration (-1: none)."""
+    that receives (j, i*, freed object, whether j was the object freed last) per iteration (-1: none; a stalled
+    iteration, which ends the finish, has a row and no freed object)."""
     n, mo = a.shape
     o2p = np.full(mo, -1, dtype=np.int64)
     o2p[p2o] = np.arange(n)
@@ -135,7 +136,12 @@ def _reverse_finish_one(a, valid, p, p2o, eps, max_iter, trace=None):
                 trace.append((j, -1, -1, chained))
             continue
         t = omega - eps
-        p[j] = t if t > lam else lam
+        pj = t if t > lam else lam
+        if not (a[istar, j] - pj > pi[istar]):  # a stall: eps is lost to rounding, the move would not raise the profit
+            if trace is not None:
+                trace.append((j, istar, -1, chained))
+            return its, int(np.count_nonzero((o2p == -1) & (p > lam)))
+        p[j] = pj
         pi[istar] = a[istar, j] - p[j]
         jo = int(p2o[istar])
         o2p[jo], o2p[j], p2o[istar] = -1, istar, j
@@ -164,8 +170,15 @@ def dense_reverse_finish(mats, sol, prices, final_eps, problem="min", shapes=Non
     j is the object the last iteration freed if that is still priced above lambda, else the first such object at or
     behind the cursor (cursor = j + 1); over the rows i that have entry (i, j), in ascending i, w = a[i][j] - pi[i], beta
     the largest (the smallest i wins a tie), omega the second largest (-inf without one); without an entry, or when
-    lambda >= beta - eps, p[j] = lambda; otherwise p[j] = max(lambda, omega - eps), pi[i*] = a[i*][j] - p[j], and row i*
-    moves to j, freeing its object.
+    lambda >= beta - eps, p[j] = lambda; otherwise pj = max(lambda, omega - eps) and, if a[i*][j] - pj > pi[i*],
+    p[j] = pj, pi[i*] = a[i*][j] - p[j], and row i* moves to j, freeing its object.
+
+    The stall rule: if a[i*][j] - pj > pi[i*] is false the finish ends there.  The iteration is counted in its, no cell
+    changes, and left is the number of unassigned objects priced above lambda, j included (the budget's formula).  In
+    exact arithmetic every move raises the moving row's profit by at least eps, which is why the loop ends; where eps is
+    below one ulp of the profits a move can leave the profit unchanged, and two objects would hand one row back and
+    forth until max_iter.  Inside max(|a|, |p|) * 2**-52 < eps no iteration stalls; outside it the finish promises
+    nothing: status stays 0 and eCE may be 1, so a caller reads left.
 
     Returns dict(sol, prices, [outside_prices], obj_f64, obj_f32, eCE, reverse=dict(its=int64 (B,), left=int32 (B,)), ran):
     copies of the inputs rewritten where the finish ran (an outside object is -1 in sol), the objective summed in row
@@ -173,7 +186,8 @@ def dense_reverse_finish(mats, sol, prices, final_eps, problem="min", shapes=Non
     obj_f64 = NaN where it did not run (ran[b] False): nothing of such a problem changes.  Afterwards every row holds an
     object within eps of its best net value, and every unassigned object is priced at or below lambda: the assignment is
     optimal within n_b * eps, whatever prices the forward solve started from.  trace: an optional list that receives,
-    per iteration, (b, j, i* or -1, the object i* left or -1, whether j was the object freed by the iteration before)."""
+    per iteration, (b, j, i* or -1, the object i* left or -1, whether j was the object freed by the iteration before); a
+    stalled iteration is the one entry with a row and no freed object."""
     flag = _entries_flag(entries)
     if hasattr(mats, "cpu"):
         mats = mats.double().cpu().numpy()
@@ -238,7 +252,9 @@ def dense_reverse_finish(mats, sol, prices, final_eps, problem="min", shapes=Non
                 val = float(a[i, p2o[i]])
                 obj = obj + val if maximize else obj - val
         obj64[b] = obj
-    out.update(obj_f64=obj64, obj_f32=obj64.astype(np.float32), eCE=ece, reverse=dict(its=its, left=left), ran=ran)
+    with np.errstate(over="ignore"):  # (an objective beyond float32 is +-inf there, as the kernel's cast gives it)
+        obj32 = obj64.astype(np.float32)
+    out.update(obj_f64=obj64, obj_f32=obj32, eCE=ece, reverse=dict(its=its, left=left), ran=ran)
     return out
 
 
@@ -343,7 +359,9 @@ def auction_solve_batch(mats, problem="min", eps_start=0., max_iter=1000000, fas
     sol, prices and outside_prices are rewritten, meta obj / obj_f64 and eCE recomputed, every other meta field stays the
     forward solve's, and the result gains reverse=dict(its=int64 (B,), left=int32 (B,)): the iterations made (0 for a
     square problem) and the unassigned objects still priced above lambda (0 unless max_iter, which is also the finish's
-    own budget, cut it); both -1 where the finish did not run -- status != 0, or max_iter cut the forward solve -- and
+    own budget, cut it, or a stalled iteration ended it: where eps is lost to rounding, outside
+    max(|a|, |p|) * 2**-52 < final_eps, a move may not raise the moving row's profit; the finish then ends with left > 0
+    while status stays 0 and eCE may be 1, so read left -- dense_reverse_finish has the rule); both -1 where the finish did not run -- status != 0, or max_iter cut the forward solve -- and
     nothing of such a problem is touched.  It combines with every other keyword and with strided views; both errors=
     modes run the status call, then the finish ("raise": then raise_for_status) and return the status-mode dict.  A numpy
     stack is uploaded once, takes the device route and comes back as numpy arrays (meta as batch_meta_to_host gives it).
