@@ -44,7 +44,8 @@ extern "C" {
  *      misslap_matching_dense_batch_strided, misslap_solve_sparse_batch_status_view,
  *      misslap_solve_sparse_batch_outside_view, misslap_sparse_batch_view_workspace_bytes,
  *      MISSLAP_DENSE_ENTRIES_FINITE in misslap_options.mat_dtype (no new entry point),
- *      misslap_dense_batch_reverse_finish. */
+ *      misslap_dense_batch_reverse_finish, misslap_sparse_batch_reverse_finish, misslap_ell_batch_reverse_finish,
+ *      misslap_list_batch_finish_workspace_bytes. */
 
 /* misslap_options.mat_dtype: the element type of a dense stack */
 #define MISSLAP_DTYPE_F64 0   /* double */
@@ -1032,6 +1033,56 @@ int misslap_solve_ell_batch_outside(int64_t B, int64_t N, int64_t K, const void 
  * staged starting prices of the augmented problems (B x (Mmax + N) doubles), each 256-byte aligned; -1 where B, N, K or
  * Mmax are out of range.  Needs no GPU. */
 int64_t misslap_ell_batch_outside_workspace_bytes(int64_t B, int64_t N, int64_t K, int64_t Mmax, int32_t has_prices);
+
+/* ---- the reverse-auction finish of a list batch solve: what misslap_dense_batch_reverse_finish is for the dense batch,
+ * behind a stream-ordered misslap_solve_sparse_batch_status / _outside (or their _view forms) or misslap_solve_ell_batch /
+ * _outside, on that solve's device outputs.  Every outside problem is rectangular, and a list solve that starts from
+ * prices_in other than zero ends with eps-CS but, in general, far from the optimum; this call repairs every problem with
+ * status[b] == 0 and meta[b].n_assigned == meta[b].n_rows as the dense finish does: lambda = the smallest price of an
+ * assigned object, every unassigned object priced above lambda takes the row that values it most or drops to lambda,
+ * and afterwards the assignment is optimal within n_b * meta[b].final_eps (for problems without duplicates of an
+ * (i, j); with duplicates the largest maximised value among them is the entry).  sslap_amd.sparse_reverse_finish states
+ * it in numpy; csrc/kernels_list_finish.hpp has the kernel, which first builds a column index of each problem in
+ * `workspace`, so that an iteration costs the length of its column.  n_b and m_b are taken from the record.
+ *   misslap_sparse_batch_reverse_finish
+ *     B, nnz, loc, loc_int64, stride_e, stride_c, val, offsets_dev   the entries as misslap_solve_sparse_batch_outside_view
+ *                  takes them; packed int32 [nnz][2] / float64 arrays pass loc_int64 = 0 and strides (2, 1).  offsets_dev
+ *                  is the device copy of the offsets; the slices of the problems with status 0 must not overlap (a host
+ *                  offsets array never does).
+ *   misslap_ell_batch_reverse_finish
+ *     B, N, K, cols, cols_int64, vals   the stack as misslap_solve_ell_batch takes it.  Nmax must be N.
+ *   outside, outside_ld   the solve's outside values (device), or NULL for a solve without them; outside_prices likewise.
+ *   opt            device, maximize, mat_dtype (the value type: MISSLAP_DTYPE_F64 / _F32); max_iter is the finish's own
+ *                  budget of iterations per problem; input_on_device must be set.  Every pointer except opt is a device
+ *                  pointer.
+ *   stream         the launch goes onto it: one launch, one workgroup per problem; nothing is allocated, copied or waited
+ *                  for.
+ *   workspace, workspace_bytes   at least misslap_list_batch_finish_workspace_bytes(entries) bytes on the device,
+ *                  entries = nnz for the sparse call and B * N * K for the ELL call; its contents are the call's own.
+ *   Nmax, Mmax     the solve's bounds: sol is [B][Nmax], prices [B][Mmax], outside_prices [B][Nmax].
+ *   status, sol, prices, outside_prices, meta   the solve's outputs, rewritten as misslap_dense_batch_reverse_finish
+ *                  rewrites them; meta[b].obj_f64 / obj_f32 and meta[b].eCE are recomputed as the list solve makes them
+ *                  (the last stored entry of the chosen column is the choice; every stored copy of it counts into the
+ *                  objective), every other field stays the forward solve's.
+ *   reverse_its, reverse_left   int64[B] / int32[B], as for the dense call: -1 where the finish did not run (status != 0,
+ *                  max_iter cut the forward solve, or sol is not a solve's output), and nothing of such a problem is
+ *                  touched; reverse_left > 0 where the budget or a stalled iteration ended the finish.
+ * Argument errors are MISSLAP_ERR_INVALID before a device is touched. */
+int misslap_sparse_batch_reverse_finish(int64_t B, int64_t nnz, const void *loc, int32_t loc_int64, int64_t stride_e,
+                                        int64_t stride_c, const void *val, const int64_t *offsets_dev,
+                                        const double *outside, int64_t outside_ld, const misslap_options *opt,
+                                        void *stream, void *workspace, int64_t workspace_bytes, int64_t Nmax, int64_t Mmax,
+                                        const int32_t *status, int32_t *sol, double *prices, double *outside_prices,
+                                        misslap_dense_batch_meta *meta, int64_t *reverse_its, int32_t *reverse_left);
+int misslap_ell_batch_reverse_finish(int64_t B, int64_t N, int64_t K, const void *cols, int32_t cols_int64,
+                                     const void *vals, const double *outside, int64_t outside_ld,
+                                     const misslap_options *opt, void *stream, void *workspace, int64_t workspace_bytes,
+                                     int64_t Nmax, int64_t Mmax, const int32_t *status, int32_t *sol, double *prices,
+                                     double *outside_prices, misslap_dense_batch_meta *meta, int64_t *reverse_its,
+                                     int32_t *reverse_left);
+/* Bytes of workspace either finish needs for `entries` entries (12 per entry, in two 256-byte aligned parts); -1 where
+ * entries is negative or above 2^56.  Needs no GPU. */
+int64_t misslap_list_batch_finish_workspace_bytes(int64_t entries);
 
 /* ---- the matching of many small graphs in one call: the batch form of misslap_hopcroft_karp / sslap.hopcroft_solve
  * (feasibility_.pyx:227-283).  Each graph is matched by ONE workgroup of ONE launch, its state in LDS

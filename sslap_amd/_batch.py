@@ -426,6 +426,41 @@ def _host(x):
     return x if isinstance(x, np.ndarray) else x.cpu().numpy()
 
 
+def _list_finish_launch(res, name, head, entries, src, problem, max_iter, dtype, Nmax, Mmax, d_out):
+    """misslap_sparse_batch_reverse_finish / misslap_ell_batch_reverse_finish (`name`) on the device result `res` of a
+    status-mode list call, on the call's stream: head is the entry point's description of the input (src: one of its
+    tensors), entries what its column index holds, dtype the value type, d_out the call's outside values on the device
+    or None.  res's outputs are rewritten in place; res gains `reverse` and keeps the index's workspace alive."""
+    import torch
+    dev, B = src.device, int(res["status"].shape[0])
+    lib = _lib.load()
+    opts = _solve_options(True, src, problem, 0.0, max_iter, dtype)
+    nbytes = int(lib.misslap_list_batch_finish_workspace_bytes(entries))
+    with torch.cuda.device(dev), torch.cuda.stream(res["stream"]):
+        work, its, left = _empty(nbytes, np.uint8, dev), _empty(B, np.int64, dev), _empty(B, np.int32, dev)
+    out_ld = 0
+    if d_out is not None and d_out.dim() == 2:
+        out_ld = int(d_out.stride(0)) if B > 1 else int(d_out.shape[1])
+    _lib.check(getattr(lib, name)(
+        *head, _ptr(d_out), out_ld, C.byref(opts), C.c_void_p(int(res["stream"].cuda_stream)), _ptr(work), nbytes, Nmax, Mmax,
+        _ptr(res["status"]), _ptr(res["sol"]), _ptr(res["prices"]), _ptr(res.get("outside_prices")), _ptr(res["records"]),
+        _ptr(its), _ptr(left)))
+    res["keep"] = (*res["keep"], work)
+    res["reverse"] = dict(its=its, left=left)
+    return its, left
+
+
+def _finished_to_host(res):
+    """The device result of a finished call on uploaded numpy input as numpy arrays, meta as batch_meta_to_host gives it
+    (which waits for the call's stream once)."""
+    meta = batch_meta_to_host(res)
+    rev = res["reverse"]
+    res = {k: v for k, v in res.items() if k not in ("records", "info", "stream", "keep", "reverse")}
+    res = {k: _host(v) if _is_device_tensor(v) else v for k, v in res.items()}
+    res.update(meta=meta, reverse=dict(its=_host(rev["its"]), left=_host(rev["left"])))
+    return res
+
+
 # layout -> _status_error(res, b, code, n, m, card), the exception of problem b of a result of that layout (n, m: the
 # record's n_rows and n_cols; card: its matching_size).  Each layout's module enters its own when it is imported.
 _STATUS_ERRORS = {}

@@ -238,6 +238,15 @@ SYMBOLS = {
                                                   C.c_int64, _VP, _VP, _VP, C.c_int32, _VP, _VP, _VP,
                                                   C.POINTER(DenseBatchInfo)]),
     "misslap_ell_batch_outside_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32]),
+    # the list finishes: (the view / the stack, outside, outside_ld, opt, stream, workspace, workspace_bytes, Nmax, Mmax,
+    # status, sol, prices, outside_prices, meta, its, left)
+    "misslap_sparse_batch_reverse_finish": (C.c_int, [C.c_int64, C.c_int64, _VP, C.c_int32, C.c_int64, C.c_int64, _VP, _VP,
+                                                      _VP, C.c_int64, C.POINTER(Options), _VP, _VP, C.c_int64, C.c_int64,
+                                                      C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "misslap_ell_batch_reverse_finish": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, _VP, C.c_int32, _VP, _VP, C.c_int64,
+                                                   C.POINTER(Options), _VP, _VP, C.c_int64, C.c_int64, C.c_int64, _VP, _VP,
+                                                   _VP, _VP, _VP, _VP, _VP]),
+    "misslap_list_batch_finish_workspace_bytes": (C.c_int64, [C.c_int64]),
     "misslap_matching_batch": (C.c_int, [C.c_int64, _VP, _VP, C.POINTER(Options), _VP, _VP, _VP, _VP, C.c_int64, _VP,
                                          C.c_int64, C.c_int32, C.POINTER(MatchingBatchInfo)]),
     "misslap_matching_dense_batch": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, _VP, _VP, C.POINTER(Options), _VP, _VP,

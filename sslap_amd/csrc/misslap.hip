@@ -521,3 +521,6 @@ MISSLAP_API int misslap_get_state(misslap_solver *h, double *prices, int32_t *un
 #include "abi_matching_batch.hpp"
 #include "abi_ell_batch.hpp"
 #include "abi_sparse_batch_status.hpp"
+// (behind everything else: no kernel above is instantiated or scheduled differently for it)
+#include "kernels_list_finish.hpp"
+#include "abi_list_finish.hpp"

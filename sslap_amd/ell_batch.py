@@ -13,8 +13,8 @@ that n_b x (m_b + n_b) problem (misslap_solve_ell_batch_outside).
 import numpy as np
 
 from . import _lib
-from ._batch import (_STATUS_ERRORS, _StatusCall, _check_outside, _contiguous, _eps, _is_device_tensor, _ptr, _send,
-                     _solve_options, _starting_prices, raise_for_status)
+from ._batch import (_STATUS_ERRORS, _StatusCall, _check_outside, _contiguous, _eps, _finished_to_host, _is_device_tensor,
+                     _list_finish_launch, _ptr, _send, _solve_options, _starting_prices, raise_for_status)
 
 MAX_DIM = _lib.SPARSE_BATCH_MAX_DIM
 _INT_MAX = 2**31 - 1
@@ -131,7 +131,7 @@ def _check_n_cols(n_cols):
 
 
 def auction_solve_ell_batch(cols, vals, rows=None, n_cols=None, problem="min", eps_start=0., max_iter=1000000, fast=None,
-                            cardinality_check=True, prices=None, errors="raise", outside=None):
+                            cardinality_check=True, prices=None, errors="raise", outside=None, finish=None):
     """Solve B independent sparse problems given as padded candidate lists, one workgroup per problem.
 
     cols: int32 or int64 (B, N, K) and vals: float64 or float32 of the same shape, both numpy arrays or both contiguous
@@ -178,9 +178,36 @@ def auction_solve_ell_batch(cols, vals, rows=None, n_cols=None, problem="min", e
     is optimal within n * eps.  The reference's eps-scaling (fast=False, eps_start=0) keeps prices between phases and has no
     reverse phase: it gives the reference's answer on the augmented problem, which is NOT the optimum in general.  The
     same holds for every rectangular problem (n < m) of the batch solves.
+
+    finish: None (default) is the call described so far, in every respect.  finish="reverse" is for rectangular problems
+    (n_b < m_b, and every outside problem) that do NOT start from zero prices -- a tracker or a matcher that passes the
+    last frame's prices= -- or that run the reference's eps-scaling: the forward auction then ends with eps-CS but, in
+    general, far from the optimum, because objects that were bid up and abandoned keep prices above those of the objects
+    in use; status 0 and eCE = 1 do not show it.  Every solved problem (status 0, every row assigned) then gets the
+    reverse-auction clean-up behind its forward solve (misslap_ell_batch_reverse_finish: one more launch on the same
+    stream, one workgroup per problem, waiting for nothing; it first builds a column index of each problem in a
+    workspace that the result keeps alive).  Afterwards the assignment still satisfies eps-CS at the solve's final eps
+    and no unassigned object is priced above lambda, the smallest price of an assigned object: optimal within
+    n_b * final_eps from any starting prices and with any fast / eps_start (for problems without duplicates of an (i, j);
+    with duplicates the largest value among them is the entry).  The result is exactly sparse_reverse_finish (its
+    docstring is the definition) on ell_to_packed(cols, vals, rows) and the outputs of the same call with finish=None:
+    sol, prices and outside_prices are rewritten, meta obj / obj_f64 and eCE recomputed, every other meta field stays the
+    forward solve's, and the result gains reverse=dict(its=int64 (B,), left=int32 (B,)): the iterations made and the
+    unassigned objects still priced above lambda (0 unless max_iter, which is also the finish's own budget, cut it, or a
+    stalled iteration ended it: where eps is lost to rounding, outside max(|a|, |p|) * 2**-52 < final_eps, the finish
+    ends with left > 0 while status stays 0 and eCE may be 1, so read left -- dense_reverse_finish has the rule); both
+    -1 where the finish did not run -- status != 0, or max_iter cut the forward solve -- and nothing of such a problem
+    is touched.  It combines with every other keyword; device input with n_cols= waits for nothing.  Numpy input is
+    uploaded once, takes the device route and comes back as numpy arrays (meta as batch_meta_to_host gives it).  Cold
+    solves should keep fast=True from zero prices: that needs no finish.  Any other value raises ValueError.
     """
     if errors not in ("raise", "status"):
         raise ValueError(f"errors must be 'raise' or 'status', got {errors!r}")
+    if finish is not None:
+        if not isinstance(finish, str) or finish != "reverse":
+            raise ValueError(f"finish must be None or 'reverse', got {finish!r}")
+        return _solve_with_finish(cols, vals, rows, n_cols, problem, eps_start, max_iter, fast, cardinality_check, prices,
+                                  errors, outside)
     B, N, K, on_device, wide, dtype = _check_input(cols, vals)
     dev = cols.device if on_device else None
     rws = _check_rows(rows, B, on_device, dev)
@@ -211,6 +238,41 @@ def auction_solve_ell_batch(cols, vals, rows=None, n_cols=None, problem="min", e
                            (B, N, K, Mmax, has_p))
         _lib.check(lib.misslap_solve_ell_batch_outside(*head, *call.way, Mmax, _ptr(d_out), out_ld, *call.outs))
     res = call.result((cols, vals, d_rows, d_p, d_out), rows=d_rows, layout="ell", stack=(N, K), n_cols=Mmax, prices_ld=p_ld)
+    return raise_for_status(res) if errors == "raise" else res
+
+
+def _reverse_finish_launch(res, problem, max_iter):
+    """misslap_ell_batch_reverse_finish on the device result `res` of a call on device input, on the call's stream, with
+    max_iter as the finish's budget: res's outputs are rewritten in place and res gains `reverse`."""
+    _, cols, vals, _, _, d_out = res["keep"][:6]
+    import torch
+    B, (N, K) = int(cols.shape[0]), res["stack"]
+    dtype = _lib.DTYPE_F32 if vals.dtype == torch.float32 else _lib.DTYPE_F64
+    head = (B, N, K, _ptr(cols), 1 if cols.dtype == torch.int64 else 0, _ptr(vals))
+    return _list_finish_launch(res, "misslap_ell_batch_reverse_finish", head, B * N * K, cols, problem, max_iter, dtype, N,
+                               res["n_cols"], d_out if "outside_prices" in res else None)
+
+
+def _solve_with_finish(cols, vals, rows, n_cols, problem, eps_start, max_iter, fast, cardinality_check, prices, errors,
+                       outside):
+    """auction_solve_ell_batch(finish="reverse"): the call on device input, then the reverse finish on its outputs -- one
+    more launch on the call's stream (misslap_ell_batch_reverse_finish), nothing is waited for.  Numpy arrays are
+    uploaded once and their result brought back as numpy arrays."""
+    on_device = _check_input(cols, vals)[3]
+    if not on_device:
+        import os
+
+        import torch
+
+        from .auction_solve import _ENV_DEVICE
+        dev = torch.device("cuda", int(os.environ.get(_ENV_DEVICE, 0)))
+        cols = torch.from_numpy(np.ascontiguousarray(cols)).to(dev)
+        vals = torch.from_numpy(np.ascontiguousarray(vals)).to(dev)
+    res = auction_solve_ell_batch(cols, vals, rows, n_cols, problem, eps_start, max_iter, fast, cardinality_check, prices,
+                                  "status", outside)
+    _reverse_finish_launch(res, problem, max_iter)
+    if not on_device:
+        res = _finished_to_host(res)
     return raise_for_status(res) if errors == "raise" else res
 
 

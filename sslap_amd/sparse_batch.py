@@ -16,8 +16,8 @@ import numpy as np
 
 from . import _lib
 from ._batch import (_STATUS_ERRORS, _StatusCall, _check_device_offsets, _check_offsets, _contiguous, _decode_meta,
-                     _empty, _eps, _host, _is_device_tensor, _maxima, _new_meta, _ptr, _scalar_outside, _send,
-                     _solve_options, _starting_prices, raise_for_status)
+                     _empty, _eps, _finished_to_host, _host, _is_device_tensor, _list_finish_launch, _maxima, _new_meta, _ptr,
+                     _scalar_outside, _send, _solve_options, _starting_prices, raise_for_status)
 from .auction_solve import _cname
 
 MAX_DIM = _lib.SPARSE_BATCH_MAX_DIM
@@ -156,6 +156,141 @@ def sparse_to_augmented(loc, val, offsets, sizes=None, outside=0.):
     return out
 
 
+def _np(x):
+    """A tensor as a numpy array on the host; everything else (an array, a list, a float) as it is."""
+    return x.cpu().numpy() if hasattr(x, "cpu") else x
+
+
+def sparse_reverse_finish(loc, val, offsets, sol, prices, final_eps, shapes, problem="min", outside=None,
+                          outside_prices=None, max_iter=1000000, run=None, trace=None):
+    """The reverse-auction finish of auction_solve_sparse_batch / auction_solve_ell_batch(finish="reverse"), stated in
+    numpy: its definition.
+
+    Takes the outputs of a forward solve -- sol int (B, Nmax), prices float64 (B, Mmax), with `outside` also
+    outside_prices float64 (B, Nmax), and final_eps (B,): meta["final_eps_f32"] -- on the packed problems loc (nnz, 2) /
+    val (nnz,) / offsets (B + 1,) under the same problem and outside, or on a list of per-problem (loc_b, val_b) pairs
+    with val and offsets None (an ELL stack goes through ell_to_packed(cols, vals, rows), without its outside keyword).
+    shapes: int (B, 2), row b = (n_b, m_b): the rows and the REAL columns of problem b, from the solve's records: n_rows,
+    and n_cols (minus n_rows with outside).
+
+    The iteration is dense_reverse_finish's, not restated here: problem b becomes its dense image (a, valid) over the m_b
+    real objects and, with outside, the n_b outside objects (object m_b + i has the one entry of row i), and the loop
+    that serves the dense batch runs on it -- the same cursor / chained-object choice, strict ">", the smallest row
+    winning a tie for beta, omega counting a second row at beta, the stall rule and the budget.  So the image decides and
+    the stored order of a row does not.  Duplicates of an (i, j) are legal in the list families: the image holds the
+    largest maximised value among them.  The finish's promise (eps-CS at the solve's final eps, no unassigned object
+    priced above lambda, optimal within n_b * eps) is stated for problems without duplicates; with them this function is
+    still the definition and the GPU matches it.
+
+    Behind the loop eCE and the objective are recomputed as the list solve makes them: for row i on object j the choice
+    is the LAST stored entry of column j in the row and every stored entry is tested against it (target_eps =
+    float32(1 / n_b), tolerance 1e-7); the objective adds EVERY stored entry of the chosen column, in row order and
+    within a row in stored order.
+
+    Returns dict(sol, prices, [outside_prices], obj_f64, obj_f32, eCE, reverse=dict(its=int64 (B,), left=int32 (B,)), ran)
+    with dense_reverse_finish's conventions: copies of the inputs rewritten where the finish ran (a row on its outside
+    option is -1 in sol); its = left = -1 and obj_f64 = NaN where it did not run -- run[b] false (what the call uses:
+    status == 0 and n_assigned == n_rows; by default every problem whose rows all hold an object), or a sol that is not
+    a solve's output (a row without an object, an object that is not an entry of its row, two rows on one object) --
+    and nothing of such a problem changes.  trace: an optional list that receives, per iteration, (b, j, i* or -1, the
+    object i* left or -1, whether j was the object freed by the iteration before)."""
+    from .dense_batch import _reverse_finish_one
+    if isinstance(loc, (list, tuple)):
+        if val is not None or offsets is not None:
+            raise TypeError("a list of (loc, val) pairs takes no val / offsets")
+        loc, val, offsets = _pack(loc)
+    loc, val = np.asarray(_np(loc)), np.asarray(_np(val), dtype=np.float64)
+    off = np.asarray(_np(offsets), dtype=np.int64)
+    if loc.ndim != 2 or loc.shape[1] != 2 or val.shape != (loc.shape[0],):
+        raise ValueError(f"loc must have shape (nnz, 2) and val (nnz,), got {loc.shape} and {val.shape}")
+    if off.ndim != 1 or off.shape[0] < 2:
+        raise ValueError("offsets must have length B + 1")
+    B = off.shape[0] - 1
+    shp = np.asarray(_np(shapes))
+    if shp.shape != (B, 2):
+        raise ValueError(f"shapes must have shape ({B}, 2), got {shp.shape}")
+    sol = np.array(_np(sol), dtype=np.int32)
+    prices = np.array(_np(prices), dtype=np.float64)
+    if sol.ndim != 2 or sol.shape[0] != B or prices.ndim != 2 or prices.shape[0] != B:
+        raise ValueError(f"sol and prices must have shape ({B}, Nmax) and ({B}, Mmax), got {sol.shape} and {prices.shape}")
+    Nmax, Mmax = sol.shape[1], prices.shape[1]
+    eps_b = np.asarray(_np(final_eps)).astype(np.float64).reshape(B)
+    maximize = problem != "min"
+    o = None
+    if outside is not None:
+        o = np.asarray(_np(outside), dtype=np.float64)
+        if o.ndim > 2 or (o.ndim >= 1 and o.shape[0] != B) or (o.ndim == 2 and o.shape[1] < Nmax):
+            raise ValueError(f"outside must be a float or have shape ({B},) or ({B}, P) with P >= {Nmax}, got {o.shape}")
+        o = np.broadcast_to(o if o.ndim != 1 else o[:, None], (B, max(Nmax, o.shape[1] if o.ndim == 2 else 0)))
+        if outside_prices is None:
+            raise ValueError("with outside, the solve's outside_prices are needed")
+        outside_prices = np.array(_np(outside_prices), dtype=np.float64).reshape(B, Nmax)
+    out = dict(sol=sol, prices=prices)
+    if o is not None:
+        out["outside_prices"] = outside_prices
+    its, left = np.full(B, -1, dtype=np.int64), np.full(B, -1, dtype=np.int32)
+    obj64, ece, ran = np.full(B, np.nan), np.zeros(B, dtype=np.int64), np.zeros(B, dtype=bool)
+    run = None if run is None else np.asarray(_np(run)).astype(bool).reshape(B)
+    for b in range(B):
+        n, m = (int(x) for x in shp[b])
+        if not (1 <= n <= Nmax and (0 if o is not None else 1) <= m <= Mmax) or (run is not None and not run[b]):
+            continue
+        ii, jj = loc[off[b]:off[b + 1], 0].astype(np.int64), loc[off[b]:off[b + 1], 1].astype(np.int64)
+        x = val[off[b]:off[b + 1]] if maximize else val[off[b]:off[b + 1]] * -1.0  # the maximised values, in stored order
+        if ((ii < 0) | (ii >= n) | (jj < 0) | (jj >= m)).any():
+            continue
+        mo = m + n if o is not None else m
+        # the dense image: per (i, j) the largest maximised value among its stored copies
+        a, valid = np.full((n, mo), -np.inf), np.zeros((n, mo), dtype=bool)
+        np.maximum.at(a, (ii, jj), x)
+        valid[ii, jj] = True
+        a[~valid] = 0.0
+        p = prices[b, :m].copy()
+        rows = np.arange(n)
+        if o is not None:
+            ox = o[b, :n] if maximize else o[b, :n] * -1.0
+            a[rows, m + rows], valid[rows, m + rows] = ox, True
+            p = np.concatenate([p, outside_prices[b, :n]])
+        p2o = sol[b, :n].astype(np.int64)
+        if o is not None:
+            p2o = np.where(p2o == -1, m + rows, p2o)
+        if ((p2o < 0) | (p2o >= mo)).any() or not valid[rows, p2o].all() or np.unique(p2o).size != n:
+            continue
+        with np.errstate(invalid="ignore"):
+            steps = None if trace is None else []
+            its[b], left[b] = _reverse_finish_one(a, valid, p, p2o, eps_b[b], int(max_iter), steps)
+            if trace is not None:
+                trace.extend((b,) + t for t in steps)
+            ran[b] = True
+            sol[b, :n] = np.where(p2o < m, p2o, -1)
+            prices[b, :m] = p[:m]
+            if o is not None:
+                outside_prices[b, :n] = p[m:]
+            # eCE_satisfied at target_eps (auction_.pyx:443-485) and get_obj (:489-523) over the stored entries
+            teps = float(np.float32(1.0 / np.float64(n)))
+            hit = jj == p2o[ii]
+            choice = a[rows, p2o].copy()  # (a row on its outside object: that one entry)
+            for k in np.flatnonzero(hit):  # :462-467: the last stored match stays
+                choice[ii[k]] = x[k]
+            lhs = choice - p[p2o] + 1e-7
+            bad = (lhs[ii] < (x - p[jj]) - teps).any()
+            if o is not None:
+                bad = bad or (lhs < (ox - p[m + rows]) - teps).any()
+            ece[b] = 0 if bad else 1
+            on_out = rows[p2o >= m]
+            who = np.concatenate([ii[hit], on_out])
+            what = np.concatenate([x[hit], a[on_out, p2o[on_out]]])
+            obj = 0.0
+            for k in np.argsort(who, kind="stable"):  # row order, within a row stored order
+                v = float(what[k])
+                obj = obj + v if maximize else obj - v
+        obj64[b] = obj
+    with np.errstate(over="ignore"):  # (an objective beyond float32 is +-inf there, as the kernel's cast gives it)
+        obj32 = obj64.astype(np.float32)
+    out.update(obj_f64=obj64, obj_f32=obj32, eCE=ece, reverse=dict(its=its, left=left), ran=ran)
+    return out
+
+
 def _check_sizes(sizes, B, dev=None):
     """sizes as the call reads them: int64 (B, 2) on the host, or with device input (dev) possibly the caller's
     contiguous int64 (B, 2) tensor on that device, whose values are the library's to judge."""
@@ -176,7 +311,8 @@ def _check_sizes(sizes, B, dev=None):
 
 
 def auction_solve_sparse_batch(loc, val=None, offsets=None, problem="min", eps_start=0., max_iter=1000000, fast=None,
-                               sizes=None, cardinality_check=True, prices=None, errors="raise", dims=None, outside=None):
+                               sizes=None, cardinality_check=True, prices=None, errors="raise", dims=None, outside=None,
+                               finish=None):
     """Solve B independent sparse problems in one call, one workgroup per problem.
 
     loc: int32 (nnz, 2) and val: float64 (nnz,), both numpy arrays or both contiguous tensors on the device (read in place,
@@ -269,9 +405,39 @@ def auction_solve_sparse_batch(loc, val=None, offsets=None, problem="min", eps_s
         res = auction_solve_sparse_batch(idx[:, 1:], cost[gate], off, dims=(N, M), outside=cost_limit, errors="status")
 
     No wait, no copy of an entry: the only launches besides the library's are nonzero, the mask gather and searchsorted.
+
+    finish: None (default) is the call described so far, in every respect.  finish="reverse" is for rectangular problems
+    (n_b < m_b, and every outside problem) that do NOT start from zero prices -- a tracker or a matcher that passes the
+    last frame's prices= -- or that run the reference's eps-scaling: the forward auction then ends with eps-CS but, in
+    general, far from the optimum, because objects that were bid up and abandoned keep prices above those of the objects
+    in use; status 0 and eCE = 1 do not show it.  Every solved problem (status 0, every row assigned) then gets the
+    reverse-auction clean-up behind its forward solve (misslap_sparse_batch_reverse_finish: one more launch on the same
+    stream, one workgroup per problem, waiting for nothing; it first builds a column index of each problem in a
+    workspace that the result keeps alive): lambda = the smallest price of an assigned object, and every unassigned
+    object priced above lambda takes the row that values it most or drops to lambda.  Afterwards the assignment still
+    satisfies eps-CS at the solve's final eps and no unassigned object is priced above lambda: optimal within
+    n_b * final_eps from any starting prices and with any fast / eps_start (for problems without duplicates of an (i, j);
+    with duplicates the largest value among them is the entry).  The result is exactly sparse_reverse_finish (its
+    docstring is the definition) applied to the outputs of the same call with finish=None: sol, prices and outside_prices
+    are rewritten, meta obj / obj_f64 and eCE recomputed, every other meta field stays the forward solve's, and the result
+    gains reverse=dict(its=int64 (B,), left=int32 (B,)): the iterations made and the unassigned objects still priced
+    above lambda (0 unless max_iter, which is also the finish's own budget, cut it, or a stalled iteration ended it:
+    where eps is lost to rounding, outside max(|a|, |p|) * 2**-52 < final_eps, the finish ends with left > 0 while status
+    stays 0 and eCE may be 1, so read left -- dense_reverse_finish has the rule); both -1 where the finish did not run --
+    status != 0, or max_iter cut the forward solve -- and nothing of such a problem is touched.  It combines with every
+    other keyword and with views; both errors= modes run the status call, then the finish ("raise": then
+    raise_for_status) and return the status-mode dict.  Device input with dims= waits for nothing.  Numpy input, and a
+    list of pairs, is uploaded once, takes the device route and comes back as numpy arrays (meta as batch_meta_to_host
+    gives it).  Cold solves should keep fast=True from zero prices: that needs no finish.  Any other value raises
+    ValueError.
     """
     if errors not in ("raise", "status"):
         raise ValueError(f"errors must be 'raise' or 'status', got {errors!r}")
+    if finish is not None:
+        if not isinstance(finish, str) or finish != "reverse":
+            raise ValueError(f"finish must be None or 'reverse', got {finish!r}")
+        return _solve_with_finish(loc, val, offsets, problem, eps_start, max_iter, fast, sizes, cardinality_check, prices,
+                                  errors, dims, outside)
     if dims is not None and errors != "status" and outside is None:
         raise ValueError("dims is taken with errors='status' only")
     if isinstance(loc, (list, tuple)):
@@ -453,6 +619,47 @@ def _solve_outside(loc, val, B, nnz, off, on_device, problem, e, max_iter, fast,
         raise ValueError(f"outside must have shape ({B},) or ({B}, P) with P >= Nmax = {Nmax}, got P = {P}")
     opts = _solve_options(on_device, loc, problem, e, max_iter, _lib.DTYPE_F64 if view is None else view["dtype"])
     return _call(loc, val, B, nnz, off, on_device, opts, fast, szs, p, Nmax, Mmax, None, out_v, out_ld, view=view)
+
+
+def _reverse_finish_launch(res, problem, max_iter):
+    """misslap_sparse_batch_reverse_finish on the device result `res` of a status-mode call, on the call's stream, with
+    max_iter as the finish's budget: res's outputs are rewritten in place and res gains `reverse`.  The entries are read
+    as a view -- packed arrays with their natural strides -- and the offsets are the device copy the call made."""
+    _, loc, val, d_off, _, _, d_out = res["keep"][:7]
+    import torch
+    nnz, (Nmax, Mmax) = int(loc.shape[0]), res["dims"]
+    dtype = _lib.DTYPE_F32 if val.dtype == torch.float32 else _lib.DTYPE_F64
+    head = (int(res["status"].shape[0]), nnz, _ptr(loc), 1 if loc.dtype == torch.int64 else 0,
+            *(int(x) for x in loc.stride()), _ptr(val), _ptr(d_off))
+    return _list_finish_launch(res, "misslap_sparse_batch_reverse_finish", head, nnz, loc, problem, max_iter, dtype, Nmax,
+                               Mmax, d_out if "outside_prices" in res else None)
+
+
+def _solve_with_finish(loc, val, offsets, problem, eps_start, max_iter, fast, sizes, cardinality_check, prices, errors,
+                       dims, outside):
+    """auction_solve_sparse_batch(finish="reverse"): the status-mode call on device input, then the reverse finish on its
+    outputs -- one more launch on the call's stream (misslap_sparse_batch_reverse_finish), nothing is waited for.  Numpy
+    arrays and a list of pairs are uploaded once and their result brought back as numpy arrays."""
+    if isinstance(loc, (list, tuple)):
+        if val is not None or offsets is not None:
+            raise TypeError("a list of (loc, val) pairs takes no val / offsets; packed loc and val are numpy arrays or "
+                            "device tensors")
+        loc, val, offsets = _pack(loc)
+    on_device = _check_input(loc, val, offsets)[3]
+    if not on_device:
+        import os
+
+        import torch
+
+        from .auction_solve import _ENV_DEVICE
+        dev = torch.device("cuda", int(os.environ.get(_ENV_DEVICE, 0)))
+        loc, val = torch.from_numpy(np.ascontiguousarray(loc)).to(dev), torch.from_numpy(np.ascontiguousarray(val)).to(dev)
+    res = auction_solve_sparse_batch(loc, val, offsets, problem, eps_start, max_iter, fast, sizes, cardinality_check, prices,
+                                     "status", dims, outside)
+    _reverse_finish_launch(res, problem, max_iter)
+    if not on_device:
+        res = _finished_to_host(res)
+    return raise_for_status(res) if errors == "raise" else res
 
 
 def _bad_slice(res, b):
