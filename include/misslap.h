@@ -45,7 +45,8 @@ extern "C" {
  *      misslap_solve_sparse_batch_outside_view, misslap_sparse_batch_view_workspace_bytes,
  *      MISSLAP_DENSE_ENTRIES_FINITE in misslap_options.mat_dtype (no new entry point),
  *      misslap_dense_batch_reverse_finish, misslap_sparse_batch_reverse_finish, misslap_ell_batch_reverse_finish,
- *      misslap_list_batch_finish_workspace_bytes. */
+ *      misslap_list_batch_finish_workspace_bytes, misslap_solve_points_batch,
+ *      misslap_points_batch_workspace_bytes. */
 
 /* misslap_options.mat_dtype: the element type of a dense stack */
 #define MISSLAP_DTYPE_F64 0   /* double */
@@ -1083,6 +1084,44 @@ int misslap_ell_batch_reverse_finish(int64_t B, int64_t N, int64_t K, const void
 /* Bytes of workspace either finish needs for `entries` entries (12 per entry, in two 256-byte aligned parts); -1 where
  * entries is negative or above 2^56.  Needs no GPU. */
 int64_t misslap_list_batch_finish_workspace_bytes(int64_t entries);
+
+/* ---- the dense batch from two point sets: costs from coordinates, the distance stack never stored.
+ * x holds B sets of N points and y B sets of M points of D coordinates each, of the type misslap_options.mat_dtype names
+ * (MISSLAP_DTYPE_F64 or MISSLAP_DTYPE_F32 only).  Coordinate k of point i of problem b lies at
+ * x[b * x_stride_b + i * x_stride_n + k * x_stride_d] (y alike), strides in elements and >= 0; the offset of a view's
+ * last element must fit 62 bits.  Problem b has shape (n_b, m_b) = shapes[b] (NULL: N x M) and the costs
+ *     c[i][j] = s_(D-1),  d_k = x[i][k] - y[j][k],  s_0 = d_0 * d_0,  s_k = s_(k-1) + d_k * d_k
+ * on the coordinates widened to double (exact): 3 D - 1 separately rounded IEEE double operations in this order, nothing
+ * fused or reassociated (sslap_amd.points_to_dense is the definition).  The kernels form every cost they need from the
+ * coordinates by exactly this chain (csrc/kernels_points_batch.hpp), and a problem with status 0 is bit for bit -- sol,
+ * prices, outside_prices and every field of meta -- the dense call on that float64 stack:
+ * misslap_solve_dense_batch_status with cardinality_check = 0 where outside is NULL, else
+ * misslap_solve_dense_batch_outside, whose outside / outside_ld, fast, prices_in, opt fields, output arrays and two
+ * modes (with a workspace of misslap_points_batch_workspace_bytes every pointer except opt and info is a device pointer
+ * and the call allocates, copies and waits for nothing: two launches on `stream`; without one the library uploads compact
+ * host arrays -- strides (N * D, D, 1) and (M * D, D, 1) --, checks host shapes and synchronises once) apply unchanged.
+ * meta.n_cols is m_b (m_b + n_b with outside), meta.nnz n_b * m_b (+ n_b).
+ * The verdicts of a problem, in their order: MISSLAP_BATCH_STATUS_BAD_SHAPE (a shape outside 1 .. N x 1 .. M: nothing of
+ * the problem is read), with outside MISSLAP_BATCH_STATUS_BAD_OUTSIDE (a negative or NaN outside value of a row < n_b),
+ * MISSLAP_BATCH_STATUS_INFINITE_VALUE (some cost with i < n_b, j < m_b is not finite -- a NaN or infinite coordinate, an
+ * overflow -- or an outside value is +inf), without outside MISSLAP_BATCH_STATUS_INFEASIBLE (n_b > m_b: every pair is an
+ * edge, so no matcher is launched), MISSLAP_BATCH_STATUS_PRICE_NOT_FINITE, MISSLAP_BATCH_STATUS_PRICE_NEGATIVE.
+ * matching_size[b] is min(n_b, m_b) for a good shape without outside, else -1.  A condemned problem has sol -1, prices 0
+ * and a meta of the three counts and zeros.  Argument errors are MISSLAP_ERR_INVALID before a device is touched. */
+#define MISSLAP_POINTS_BATCH_MAX_DIM 2048
+#define MISSLAP_POINTS_BATCH_MAX_COORDS 8
+int misslap_solve_points_batch(int64_t B, int64_t N, int64_t M, int64_t D,
+                               const void *x, int64_t x_stride_b, int64_t x_stride_n, int64_t x_stride_d,
+                               const void *y, int64_t y_stride_b, int64_t y_stride_m, int64_t y_stride_d,
+                               const int32_t *shapes, int32_t fast, const double *prices_in, const misslap_options *opt,
+                               void *stream, void *workspace, int64_t workspace_bytes, const double *outside,
+                               int64_t outside_ld, int32_t *sol, double *prices_out, double *outside_prices_out,
+                               int32_t out_on_device, int32_t *status, int32_t *matching_size,
+                               misslap_dense_batch_meta *meta, misslap_dense_batch_info *info);
+/* Bytes of workspace a stream-ordered misslap_solve_points_batch needs: the check records, the sanitised shapes and, with
+ * has_prices and has_outside, the staged starting prices; -1 where B < 1 or N / M are outside
+ * 1 .. MISSLAP_POINTS_BATCH_MAX_DIM.  Needs no GPU. */
+int64_t misslap_points_batch_workspace_bytes(int64_t B, int64_t N, int64_t M, int32_t has_prices, int32_t has_outside);
 
 /* ---- the matching of many small graphs in one call: the batch form of misslap_hopcroft_karp / sslap.hopcroft_solve
  * (feasibility_.pyx:227-283).  Each graph is matched by ONE workgroup of ONE launch, its state in LDS

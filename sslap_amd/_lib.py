@@ -94,6 +94,8 @@ class MatchingBatchInfo(C.Structure):
 DENSE_BATCH_MAX_DIM = 1024  # MISSLAP_DENSE_BATCH_MAX_DIM
 SPARSE_BATCH_MAX_DIM = 2048  # MISSLAP_SPARSE_BATCH_MAX_DIM
 MATCHING_BATCH_MAX_DIM = 2048  # MISSLAP_MATCHING_BATCH_MAX_DIM
+POINTS_BATCH_MAX_DIM = 2048  # MISSLAP_POINTS_BATCH_MAX_DIM
+POINTS_BATCH_MAX_COORDS = 8  # MISSLAP_POINTS_BATCH_MAX_COORDS
 # MISSLAP_BATCH_STATUS_*: the verdict of one problem of misslap_solve_dense_batch_status
 (BATCH_STATUS_OK, BATCH_STATUS_TOO_FEW_VALUES, BATCH_STATUS_EMPTY_ROW, BATCH_STATUS_INFINITE_VALUE,
  BATCH_STATUS_INFEASIBLE, BATCH_STATUS_PRICE_NOT_FINITE, BATCH_STATUS_PRICE_NEGATIVE, BATCH_STATUS_BAD_SHAPE) = range(8)
@@ -247,6 +249,12 @@ SYMBOLS = {
                                                    C.POINTER(Options), _VP, _VP, C.c_int64, C.c_int64, C.c_int64, _VP, _VP,
                                                    _VP, _VP, _VP, _VP, _VP]),
     "misslap_list_batch_finish_workspace_bytes": (C.c_int64, [C.c_int64]),
+    # (B, N, M, D, x, x strides, y, y strides, shapes, fast, prices_in, opt, stream, workspace, workspace_bytes, outside,
+    # outside_ld, sol, prices_out, outside_prices_out, out_on_device, status, matching_size, meta, info)
+    "misslap_solve_points_batch": (C.c_int, [C.c_int64] * 4 + [_VP] + [C.c_int64] * 3 + [_VP] + [C.c_int64] * 3 +
+                                   [_VP, C.c_int32, _VP, C.POINTER(Options), _VP, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP,
+                                    _VP, C.c_int32, _VP, _VP, _VP, C.POINTER(DenseBatchInfo)]),
+    "misslap_points_batch_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
     "misslap_matching_batch": (C.c_int, [C.c_int64, _VP, _VP, C.POINTER(Options), _VP, _VP, _VP, _VP, C.c_int64, _VP,
                                          C.c_int64, C.c_int32, C.POINTER(MatchingBatchInfo)]),
     "misslap_matching_dense_batch": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, _VP, _VP, C.POINTER(Options), _VP, _VP,

@@ -524,3 +524,5 @@ MISSLAP_API int misslap_get_state(misslap_solver *h, double *prices, int32_t *un
 // (behind everything else: no kernel above is instantiated or scheduled differently for it)
 #include "kernels_list_finish.hpp"
 #include "abi_list_finish.hpp"
+#include "kernels_points_batch.hpp"
+#include "abi_points_batch.hpp"
