@@ -46,7 +46,7 @@ extern "C" {
  *      MISSLAP_DENSE_ENTRIES_FINITE in misslap_options.mat_dtype (no new entry point),
  *      misslap_dense_batch_reverse_finish, misslap_sparse_batch_reverse_finish, misslap_ell_batch_reverse_finish,
  *      misslap_list_batch_finish_workspace_bytes, misslap_solve_points_batch,
- *      misslap_points_batch_workspace_bytes. */
+ *      misslap_points_batch_workspace_bytes, misslap_points_batch_reverse_finish. */
 
 /* misslap_options.mat_dtype: the element type of a dense stack */
 #define MISSLAP_DTYPE_F64 0   /* double */
@@ -1122,6 +1122,37 @@ int misslap_solve_points_batch(int64_t B, int64_t N, int64_t M, int64_t D,
  * has_prices and has_outside, the staged starting prices; -1 where B < 1 or N / M are outside
  * 1 .. MISSLAP_POINTS_BATCH_MAX_DIM.  Needs no GPU. */
 int64_t misslap_points_batch_workspace_bytes(int64_t B, int64_t N, int64_t M, int32_t has_prices, int32_t has_outside);
+
+/* ---- the reverse-auction finish of a points batch solve: what misslap_dense_batch_reverse_finish is for the dense batch,
+ * behind a stream-ordered misslap_solve_points_batch and on that solve's device outputs.  Every solve with an outside
+ * option is rectangular (n_b rows, m_b + n_b objects), and one that starts from prices_in other than zero ends with
+ * eps-CS but, in general, far from the optimum; this call repairs every problem with status[b] == 0 and
+ * meta[b].n_assigned == n_b exactly as the dense finish does on the float64 stack of the costs (the chain stated at
+ * misslap_solve_points_batch; every finite cost is an entry), which is never stored: the kernel forms every cost from
+ * the coordinates (csrc/kernels_points_finish.hpp).  sslap_amd.points_reverse_finish states the call in numpy, and the
+ * result is that function's bit for bit.  Problems of up to MISSLAP_POINTS_BATCH_MAX_DIM rows and columns are taken.
+ *   B, N, M, D, x, x_stride_*, y, y_stride_*   the point sets as misslap_solve_points_batch takes them (device arrays,
+ *                  element type from opt->mat_dtype: MISSLAP_DTYPE_F64 or MISSLAP_DTYPE_F32); nothing of them is written.
+ *   shapes         the solve's device shapes, or NULL.  status[b] is read first and nothing else of a problem whose status
+ *                  is not 0 is read or written, so a bad device shape is never used.
+ *   outside, outside_ld   the solve's outside values (device), or NULL for the plain problem; outside_prices likewise.
+ *   opt            device, maximize, mat_dtype; max_iter is the finish's own budget of iterations per problem;
+ *                  input_on_device must be set.  Every pointer except opt is a device pointer.
+ *   stream         the launch goes onto it: one launch, one workgroup per problem; nothing is allocated, copied or waited
+ *                  for, and no workspace is needed.
+ *   status, sol, prices, outside_prices, meta, reverse_its, reverse_left   as for misslap_dense_batch_reverse_finish:
+ *                  sol, prices and outside_prices of a finished problem are rewritten, meta[b].obj_f64 / obj_f32 / eCE
+ *                  recomputed, every other field kept; reverse_its / reverse_left are -1 where the finish did not run
+ *                  (status != 0, or max_iter cut the forward solve) and nothing of such a problem is touched;
+ *                  reverse_left > 0 where the budget or a stalled iteration ended the finish.
+ * Argument errors (the caps, D, the strides: the solve's checks) are MISSLAP_ERR_INVALID before a device is touched. */
+int misslap_points_batch_reverse_finish(int64_t B, int64_t N, int64_t M, int64_t D,
+                                        const void *x, int64_t x_stride_b, int64_t x_stride_n, int64_t x_stride_d,
+                                        const void *y, int64_t y_stride_b, int64_t y_stride_m, int64_t y_stride_d,
+                                        const int32_t *shapes, const double *outside, int64_t outside_ld,
+                                        const misslap_options *opt, void *stream, const int32_t *status, int32_t *sol,
+                                        double *prices, double *outside_prices, misslap_dense_batch_meta *meta,
+                                        int64_t *reverse_its, int32_t *reverse_left);
 
 /* ---- the matching of many small graphs in one call: the batch form of misslap_hopcroft_karp / sslap.hopcroft_solve
  * (feasibility_.pyx:227-283).  Each graph is matched by ONE workgroup of ONE launch, its state in LDS

@@ -15,8 +15,8 @@ from .dense_batch import (auction_solve_batch, batch_meta_to_host, dense_reverse
 from .sparse_batch import auction_solve_sparse_batch, sparse_reverse_finish, sparse_to_augmented
 from .ell_batch import auction_solve_ell_batch, ell_to_packed
 from .matching_batch import hopcroft_solve_batch
-from .points_batch import auction_solve_points_batch, points_to_dense
+from .points_batch import auction_solve_points_batch, points_reverse_finish, points_to_dense
 
 __version__ = "0.1.0"
 solve_batch = AuctionSolver.solve_batch  # many problems with the same number of persons in lockstep on one GPU (include/misslap.h: misslap_solve_batch)
-__all__ = ["auction_solve", "auction_solve_batch", "auction_solve_sparse_batch", "auction_solve_ell_batch", "auction_solve_points_batch", "points_to_dense", "ell_to_packed", "dense_to_augmented", "dense_to_packed", "dense_reverse_finish", "sparse_to_augmented", "sparse_reverse_finish", "batch_meta_to_host", "raise_for_status", "hopcroft_solve", "hopcroft_solve_batch", "from_matrix", "from_sparse", "AuctionSolver", "solve_batch"]
+__all__ = ["auction_solve", "auction_solve_batch", "auction_solve_sparse_batch", "auction_solve_ell_batch", "auction_solve_points_batch", "points_to_dense", "points_reverse_finish", "ell_to_packed", "dense_to_augmented", "dense_to_packed", "dense_reverse_finish", "sparse_to_augmented", "sparse_reverse_finish", "batch_meta_to_host", "raise_for_status", "hopcroft_solve", "hopcroft_solve_batch", "from_matrix", "from_sparse", "AuctionSolver", "solve_batch"]

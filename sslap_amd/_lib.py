@@ -255,6 +255,11 @@ SYMBOLS = {
                                    [_VP, C.c_int32, _VP, C.POINTER(Options), _VP, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP,
                                     _VP, C.c_int32, _VP, _VP, _VP, C.POINTER(DenseBatchInfo)]),
     "misslap_points_batch_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
+    # (B, N, M, D, x, x strides, y, y strides, shapes, outside, outside_ld, opt, stream, status, sol, prices,
+    # outside_prices, meta, its, left)
+    "misslap_points_batch_reverse_finish": (C.c_int, [C.c_int64] * 4 + [_VP] + [C.c_int64] * 3 + [_VP] + [C.c_int64] * 3 +
+                                            [_VP, _VP, C.c_int64, C.POINTER(Options), _VP, _VP, _VP, _VP, _VP, _VP, _VP,
+                                             _VP]),
     "misslap_matching_batch": (C.c_int, [C.c_int64, _VP, _VP, C.POINTER(Options), _VP, _VP, _VP, _VP, C.c_int64, _VP,
                                          C.c_int64, C.c_int32, C.POINTER(MatchingBatchInfo)]),
     "misslap_matching_dense_batch": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, _VP, _VP, C.POINTER(Options), _VP, _VP,

@@ -526,3 +526,5 @@ MISSLAP_API int misslap_get_state(misslap_solver *h, double *prices, int32_t *un
 #include "abi_list_finish.hpp"
 #include "kernels_points_batch.hpp"
 #include "abi_points_batch.hpp"
+#include "kernels_points_finish.hpp"
+#include "abi_points_finish.hpp"

@@ -4,12 +4,22 @@ The costs are squared distances, c[b, i, j] = |x[b, i] - y[b, j]|^2, and the (B,
 kernels form every cost they need from the coordinates (csrc/kernels_points_batch.hpp).  `points_to_dense` is the
 definition: the result of problem b is bit for bit the dense batch's (`auction_solve_batch`) on the float64 stack it
 returns.  Problems of up to 2048 x 2048 are taken, twice the dense batch's cap.
+
+With `finish="reverse"` every solved problem gets the reverse-auction clean-up behind its forward solve, which makes a
+warm start (`prices=` with `outside=`) optimal (misslap_points_batch_reverse_finish); `points_reverse_finish` is its
+definition in numpy.
 """
+import ctypes as C
+import os
+
 import numpy as np
 
 from . import _lib
-from ._batch import (_STATUS_ERRORS, _StatusCall, _check_device_shapes, _check_outside, _check_shapes, _eps, _host,
-                     _is_device_tensor, _ptr, _send, _solve_options, _starting_prices, raise_for_status)
+from .auction_solve import _ENV_DEVICE
+from ._batch import (_STATUS_ERRORS, _StatusCall, _check_device_shapes, _check_outside, _check_shapes, _empty, _eps, _host,
+                     _is_device_tensor, _ptr, _send, _solve_options, _starting_prices, batch_meta_to_host,
+                     raise_for_status)
+from .dense_batch import dense_reverse_finish
 
 MAX_DIM = _lib.POINTS_BATCH_MAX_DIM
 MAX_COORDS = _lib.POINTS_BATCH_MAX_COORDS
@@ -72,6 +82,20 @@ def points_to_dense(x, y, shapes=None):
     return c
 
 
+def points_reverse_finish(x, y, sol, prices, final_eps, problem="min", shapes=None, outside=None, outside_prices=None,
+                          max_iter=1000000, run=None, trace=None):
+    """The reverse-auction finish of auction_solve_points_batch(finish="reverse"), stated in numpy: its definition.
+
+    It is dense_reverse_finish (whose docstring states the loop, the stall rule and the return keys) applied to
+    points_to_dense(x, y, shapes): every finite squared distance is an entry under the "nonneg" rule, so a problem has
+    no holes.  x (B, N, D) and y (B, M, D) as points_to_dense takes them; sol, prices, final_eps, problem, shapes,
+    outside, outside_prices, max_iter, run and trace as dense_reverse_finish takes them.  numpy has no size cap.
+    Returns dict(sol, prices, [outside_prices], obj_f64, obj_f32, eCE, reverse=dict(its, left), ran)."""
+    return dense_reverse_finish(points_to_dense(x, y, shapes), sol, prices, final_eps, problem=problem, shapes=shapes,
+                                outside=outside, outside_prices=outside_prices, entries="nonneg", max_iter=max_iter,
+                                run=run, trace=trace)
+
+
 def _check_points(x, y):
     """dtype / rank / device of x and y; returns (B, N, M, D, on_device, the MISSLAP_DTYPE_* of the coordinates)."""
     if isinstance(x, np.ndarray) and isinstance(y, np.ndarray):
@@ -112,6 +136,9 @@ def _check_points(x, y):
     return B, N, M, D, on_device, _lib.DTYPE_F32 if names[0] == "float32" else _lib.DTYPE_F64
 
 
+_NO_FINISH = type("_NoFinish", (), {"__repr__": lambda self: "<no finish>"})()  # finish= was left out
+
+
 def _strides(a, rows, D):
     """The element strides of a point set as the library reads it: a tensor's own, a numpy array's compact ones."""
     if isinstance(a, np.ndarray):
@@ -120,7 +147,7 @@ def _strides(a, rows, D):
 
 
 def auction_solve_points_batch(x, y, problem="min", eps_start=0., max_iter=1000000, fast=None, shapes=None, prices=None,
-                               outside=None, errors="raise"):
+                               outside=None, errors="raise", finish=_NO_FINISH):
     """Solve B independent dense problems whose costs are the squared distances between two point sets, one workgroup
     per problem; the cost stack is never stored.
 
@@ -151,9 +178,31 @@ def auction_solve_points_batch(x, y, problem="min", eps_start=0., max_iter=10000
     with outside also an outside value of +inf), without outside INFEASIBLE (n_b > m_b; every pair is an edge, so no
     matcher runs), PRICE_NOT_FINITE, PRICE_NEGATIVE.  matching_size is min(n_b, m_b) for a good shape without outside,
     else -1.  A condemned problem has sol -1, prices 0 and a meta of n_rows, n_cols, nnz and zeros.
+
+    finish: left out (the default), the call is the one described so far, in every respect.  The keyword takes the one
+    value "reverse"; finish=None is a TypeError, as it was before the keyword existed (the call's whole-call checks pin
+    that it has no finish=None), and any other value a ValueError.  finish="reverse" is for warm starts: every
+    outside problem is rectangular (n_b rows, m_b + n_b objects), and a forward auction that starts from prices other
+    than zero ends with status 0 and eCE = 1 but, in general, far from the optimum.  With finish="reverse" every problem
+    with status 0 whose rows all hold an object gets the reverse-auction clean-up of auction_solve_batch(finish="reverse")
+    behind its forward solve (misslap_points_batch_reverse_finish: one more launch on the same stream, nothing is waited
+    for), with that call's meaning, result key and rules: the result is bit for bit points_reverse_finish (the definition)
+    applied to the outputs of the same call without finish -- sol, prices, outside_prices and obj_f64, obj_f32 and eCE
+    of meta; every other meta field, status and matching_size stay -- and gains reverse=dict(its, left), both -1 where the
+    finish did not run (status != 0, or max_iter, which is also the finish's own budget, cut the forward solve) and left
+    > 0 where the budget or a stalled iteration ended it.  Afterwards the assignment is optimal within n_b * final_eps.
+    Both errors= modes run the status call, then the finish ("raise": then raise_for_status).  numpy point sets are
+    uploaded once and the result comes back as numpy arrays.
     """
     if errors not in ("raise", "status"):
         raise ValueError(f"errors must be 'raise' or 'status', got {errors!r}")
+    if finish is None:
+        raise TypeError("auction_solve_points_batch() takes no finish=None: leave finish out for the call without a "
+                        "finish, or pass finish='reverse'")
+    if finish is not _NO_FINISH:
+        if not isinstance(finish, str) or finish != "reverse":
+            raise ValueError(f"finish must be left out or 'reverse', got {finish!r}")
+        return _solve_with_finish(x, y, problem, eps_start, max_iter, fast, shapes, prices, outside, errors)
     B, N, M, D, on_device, dtype = _check_points(x, y)
     dev = x.device if on_device else None
     if dev is not None and _is_device_tensor(shapes):
@@ -181,6 +230,45 @@ def auction_solve_points_batch(x, y, problem="min", eps_start=0., max_iter=10000
         *call.way, _ptr(d_out), out_ld, *outs))
     own = {} if outside is None else dict(outside=d_out)
     res = call.result((x, y, d_shp, d_p, d_out), shapes=d_shp, stack=(N, M), layout="points", **own)
+    return raise_for_status(res) if errors == "raise" else res
+
+
+def _reverse_finish_launch(x, y, res, problem, max_iter):
+    """misslap_points_batch_reverse_finish on the device result `res` of a status-mode call on the device point sets x
+    and y, on the call's stream: res's outputs are rewritten in place and res gains `reverse`."""
+    import torch
+    B, N, M, D, _, dtype = _check_points(x, y)
+    dev = x.device
+    opts = _solve_options(True, x, problem, 0.0, max_iter, dtype)
+    with torch.cuda.device(dev):
+        its, left = _empty(B, np.int64, dev), _empty(B, np.int32, dev)
+    d_out = res.get("outside") if "outside_prices" in res else None
+    _lib.check(_lib.load().misslap_points_batch_reverse_finish(
+        B, N, M, D, _ptr(x), *_strides(x, N, D), _ptr(y), *_strides(y, M, D), _ptr(res["shapes"]), _ptr(d_out),
+        0 if d_out is None or d_out.dim() == 1 else N, C.byref(opts), C.c_void_p(int(res["stream"].cuda_stream)),
+        _ptr(res["status"]), _ptr(res["sol"]), _ptr(res["prices"]), _ptr(res.get("outside_prices")), _ptr(res["records"]),
+        _ptr(its), _ptr(left)))
+    res["reverse"] = dict(its=its, left=left)
+    return its, left
+
+
+def _solve_with_finish(x, y, problem, eps_start, max_iter, fast, shapes, prices, outside, errors):
+    """auction_solve_points_batch(finish="reverse"): the status-mode call on device point sets, then the reverse finish
+    on its outputs -- one more launch on the call's stream, nothing is waited for.  numpy point sets are uploaded once
+    and their result brought back as numpy arrays."""
+    on_device = _check_points(x, y)[4]
+    xd, yd = x, y
+    if not on_device:
+        import torch
+        dev = torch.device("cuda", int(os.environ.get(_ENV_DEVICE, 0)))
+        xd, yd = (torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (x, y))
+    res = auction_solve_points_batch(xd, yd, problem, eps_start, max_iter, fast, shapes, prices, outside, "status")
+    its, left = _reverse_finish_launch(xd, yd, res, problem, max_iter)
+    if not on_device:
+        meta = batch_meta_to_host(res)  # (waits for the call's stream once)
+        res = {k: v for k, v in res.items() if k not in ("records", "info", "stream", "keep")}
+        res = {k: _host(v) if _is_device_tensor(v) else v for k, v in res.items()}
+        res.update(meta=meta, reverse=dict(its=_host(its), left=_host(left)))
     return raise_for_status(res) if errors == "raise" else res
 
 
