@@ -46,7 +46,8 @@ extern "C" {
  *      MISSLAP_DENSE_ENTRIES_FINITE in misslap_options.mat_dtype (no new entry point),
  *      misslap_dense_batch_reverse_finish, misslap_sparse_batch_reverse_finish, misslap_ell_batch_reverse_finish,
  *      misslap_list_batch_finish_workspace_bytes, misslap_solve_points_batch,
- *      misslap_points_batch_workspace_bytes, misslap_points_batch_reverse_finish. */
+ *      misslap_points_batch_workspace_bytes, misslap_points_batch_reverse_finish,
+ *      misslap_points_batch_candidates. */
 
 /* misslap_options.mat_dtype: the element type of a dense stack */
 #define MISSLAP_DTYPE_F64 0   /* double */
@@ -1153,6 +1154,42 @@ int misslap_points_batch_reverse_finish(int64_t B, int64_t N, int64_t M, int64_t
                                         const misslap_options *opt, void *stream, const int32_t *status, int32_t *sol,
                                         double *prices, double *outside_prices, misslap_dense_batch_meta *meta,
                                         int64_t *reverse_its, int32_t *reverse_left);
+
+/* ---- candidate lists from two point sets: per row the (at most) K nearest columns under a per-row limit, in the padded
+ * (B, N, K) layout misslap_solve_ell_batch and misslap_solve_ell_batch_outside read in place.  The (B, N, M) stack of the
+ * costs is never stored: one launch forms every cost once, by the chain stated at misslap_solve_points_batch
+ * (csrc/kernels_points_candidates.hpp).  sslap_amd.points_to_ell states the call in numpy, and the four outputs are that
+ * function's bit for bit.  With c[i][j] the cost of (i, j) and (n_b, m_b) the shape of problem b:
+ *   rows[b]        n_b for a shape inside 1 .. N x 1 .. M (shapes NULL: N), else 0 -- which misslap_solve_ell_batch
+ *                  reports as MISSLAP_BATCH_STATUS_BAD_SHAPE -- and every slot of such a problem is a hole.
+ *   candidates     of row i < n_b: the columns j < m_b whose cost is not finite (a NaN or an infinite coordinate, an
+ *                  overflow) or is <= the row's limit under the IEEE comparison (a limit of -0.0 admits a cost of +0.0, a
+ *                  NaN limit admits no finite cost; limit NULL admits every column).
+ *   counts[b][i]   the number of candidates, before any truncation; 0 for a row >= n_b.
+ *   cols, vals     int32 / double [B][N][K].  The candidates of row i in ascending column order from slot 0, the value
+ *                  of a cost that is not finite stored as +inf (so the ELL call condemns exactly the problems
+ *                  misslap_solve_points_batch condemns, with MISSLAP_BATCH_STATUS_INFINITE_VALUE); every later slot
+ *                  holds cols -1, vals 0.0.  Where counts[b][i] > K the K smallest by (cost, column) are kept, the
+ *                  non-finite ones first, by column.
+ *   B, N, M, D, x, x_stride_*, y, y_stride_*   the point sets as misslap_solve_points_batch takes them (device arrays,
+ *                  element type from opt->mat_dtype: MISSLAP_DTYPE_F64 or MISSLAP_DTYPE_F32); only elements of the two
+ *                  views are read and nothing of them is written.
+ *   K              1 .. MISSLAP_POINTS_CANDIDATES_MAX_K.
+ *   shapes         device int32[B][2], or NULL.
+ *   limit, limit_ld   device doubles: NULL for no limit; limit_ld == 0: limit[b] is the limit of every row of problem
+ *                  b; else limit[b * limit_ld + i] with limit_ld >= N.  Its sign and finiteness are judged per row, as
+ *                  stated above.
+ *   opt            device, mat_dtype; input_on_device must be set.  Every pointer except opt is a device pointer.
+ *   stream         the launch goes onto it: one launch, a wavefront per row; nothing is allocated, copied, waited for or
+ *                  read back, and no workspace is needed.
+ * Argument errors (the caps, D, the strides: the solve's checks; K) are MISSLAP_ERR_INVALID before a device is touched. */
+#define MISSLAP_POINTS_CANDIDATES_MAX_K 64
+int misslap_points_batch_candidates(int64_t B, int64_t N, int64_t M, int64_t D,
+                                    const void *x, int64_t x_stride_b, int64_t x_stride_n, int64_t x_stride_d,
+                                    const void *y, int64_t y_stride_b, int64_t y_stride_m, int64_t y_stride_d,
+                                    int64_t K, const int32_t *shapes, const double *limit, int64_t limit_ld,
+                                    const misslap_options *opt, void *stream, int32_t *cols, double *vals,
+                                    int32_t *counts, int32_t *rows);
 
 /* ---- the matching of many small graphs in one call: the batch form of misslap_hopcroft_karp / sslap.hopcroft_solve
  * (feasibility_.pyx:227-283).  Each graph is matched by ONE workgroup of ONE launch, its state in LDS

@@ -96,6 +96,7 @@ SPARSE_BATCH_MAX_DIM = 2048  # MISSLAP_SPARSE_BATCH_MAX_DIM
 MATCHING_BATCH_MAX_DIM = 2048  # MISSLAP_MATCHING_BATCH_MAX_DIM
 POINTS_BATCH_MAX_DIM = 2048  # MISSLAP_POINTS_BATCH_MAX_DIM
 POINTS_BATCH_MAX_COORDS = 8  # MISSLAP_POINTS_BATCH_MAX_COORDS
+POINTS_CANDIDATES_MAX_K = 64  # MISSLAP_POINTS_CANDIDATES_MAX_K
 # MISSLAP_BATCH_STATUS_*: the verdict of one problem of misslap_solve_dense_batch_status
 (BATCH_STATUS_OK, BATCH_STATUS_TOO_FEW_VALUES, BATCH_STATUS_EMPTY_ROW, BATCH_STATUS_INFINITE_VALUE,
  BATCH_STATUS_INFEASIBLE, BATCH_STATUS_PRICE_NOT_FINITE, BATCH_STATUS_PRICE_NEGATIVE, BATCH_STATUS_BAD_SHAPE) = range(8)
@@ -260,6 +261,9 @@ SYMBOLS = {
     "misslap_points_batch_reverse_finish": (C.c_int, [C.c_int64] * 4 + [_VP] + [C.c_int64] * 3 + [_VP] + [C.c_int64] * 3 +
                                             [_VP, _VP, C.c_int64, C.POINTER(Options), _VP, _VP, _VP, _VP, _VP, _VP, _VP,
                                              _VP]),
+    # (B, N, M, D, x, x strides, y, y strides, K, shapes, limit, limit_ld, opt, stream, cols, vals, counts, rows)
+    "misslap_points_batch_candidates": (C.c_int, [C.c_int64] * 4 + [_VP] + [C.c_int64] * 3 + [_VP] + [C.c_int64] * 3 +
+                                        [C.c_int64, _VP, _VP, C.c_int64, C.POINTER(Options), _VP, _VP, _VP, _VP, _VP]),
     "misslap_matching_batch": (C.c_int, [C.c_int64, _VP, _VP, C.POINTER(Options), _VP, _VP, _VP, _VP, C.c_int64, _VP,
                                          C.c_int64, C.c_int32, C.POINTER(MatchingBatchInfo)]),
     "misslap_matching_dense_batch": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, _VP, _VP, C.POINTER(Options), _VP, _VP,

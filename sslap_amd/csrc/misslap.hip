@@ -528,3 +528,5 @@ MISSLAP_API int misslap_get_state(misslap_solver *h, double *prices, int32_t *un
 #include "abi_points_batch.hpp"
 #include "kernels_points_finish.hpp"
 #include "abi_points_finish.hpp"
+#include "kernels_points_candidates.hpp"
+#include "abi_points_candidates.hpp"

@@ -8,6 +8,11 @@ returns.  Problems of up to 2048 x 2048 are taken, twice the dense batch's cap.
 With `finish="reverse"` every solved problem gets the reverse-auction clean-up behind its forward solve, which makes a
 warm start (`prices=` with `outside=`) optimal (misslap_points_batch_reverse_finish); `points_reverse_finish` is its
 definition in numpy.
+
+`points_candidates` turns the two point sets into padded candidate lists -- per row the (at most) K nearest columns
+under a per-row limit, in the (B, N, K) layout `auction_solve_ell_batch` reads in place -- without storing the stack
+(misslap_points_batch_candidates); `points_to_ell` is its definition in numpy.  With `candidates=K` the points call
+runs that builder and the ELL solve back to back on the caller's stream.
 """
 import ctypes as C
 import os
@@ -17,12 +22,14 @@ import numpy as np
 from . import _lib
 from .auction_solve import _ENV_DEVICE
 from ._batch import (_STATUS_ERRORS, _StatusCall, _check_device_shapes, _check_outside, _check_shapes, _empty, _eps, _host,
-                     _is_device_tensor, _ptr, _send, _solve_options, _starting_prices, batch_meta_to_host,
+                     _is_device_tensor, _options, _ptr, _send, _solve_options, _starting_prices, batch_meta_to_host,
                      raise_for_status)
 from .dense_batch import dense_reverse_finish
+from .ell_batch import auction_solve_ell_batch
 
 MAX_DIM = _lib.POINTS_BATCH_MAX_DIM
 MAX_COORDS = _lib.POINTS_BATCH_MAX_COORDS
+MAX_CANDIDATES = _lib.POINTS_CANDIDATES_MAX_K
 
 _STATUS_TEXT = {
     _lib.BATCH_STATUS_BAD_SHAPE: "shape ({n}, {m}) outside 1 .. {N} x 1 .. {M}",
@@ -96,6 +103,89 @@ def points_reverse_finish(x, y, sol, prices, final_eps, problem="min", shapes=No
                                 run=run, trace=trace)
 
 
+def _check_k(k):
+    """k of points_to_ell / points_candidates / candidates=: an integer in 1 .. MISSLAP_POINTS_CANDIDATES_MAX_K."""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+        raise TypeError(f"the number of candidates per row must be an integer, got {k!r}")
+    if not 1 <= int(k) <= MAX_CANDIDATES:
+        raise ValueError(f"the number of candidates per row must be in 1 .. {MAX_CANDIDATES} "
+                         f"(MISSLAP_POINTS_CANDIDATES_MAX_K), got {int(k)}")
+    return int(k)
+
+
+def points_to_ell(x, y, k, shapes=None, limit=None):
+    """x (B, N, D) and y (B, M, D) as points_to_dense takes them, k in 1 .. 64 -> dict(cols int32 (B, N, k), vals float64
+    (B, N, k), counts int32 (B, N), rows int32 (B,)): per row the (at most) k nearest columns under the row's limit, as
+    padded candidate lists in the layout auction_solve_ell_batch reads.  The definition of points_candidates and of
+    auction_solve_points_batch(candidates=k): the GPU's four arrays are these bit for bit.
+
+    limit: None, a float, float64 (B,) (one value per problem) or float64 (B, N) (one per row).
+    With c = points_to_dense(x, y, shapes) -- the chain of 3 D - 1 separately rounded float64 operations -- and
+    (n_b, m_b) = shapes[b] (without shapes: (N, M)):
+
+    Shapes      rows[b] = n_b for a shape inside 1 .. N x 1 .. M.  For any other shape rows[b] = 0, which
+                auction_solve_ell_batch reports as BAD_SHAPE, and every slot of the problem is a hole.
+    Candidates  for row i < n_b, column j < m_b is a candidate iff c[b, i, j] is not finite, or
+                c[b, i, j] <= limit[b, i].  The comparison is IEEE: a limit of -0.0 admits a cost of +0.0, a NaN limit
+                admits no finite cost, a limit of +inf every one; limit=None admits everything.  counts[b, i] is the
+                number of candidates, before any truncation, and 0 for rows >= n_b.
+    Non-finite  a cost that is not finite (a NaN or an infinite coordinate, or an overflow) is always a candidate, sorts
+                ahead of every finite one and is stored as +inf (no NaN payload has to agree, and the ELL call then
+                condemns exactly the problems the points call condemns, with INFINITE_VALUE).
+    Truncation  where counts[b, i] > k the k smallest candidates by (cost, column) are kept, the non-finite ones first,
+                by column.
+    Order       the kept candidates are stored in ascending column order in slots 0 .., and every later slot holds
+                cols = -1, vals = 0.0.  In column order an untruncated row is exactly the row gate.nonzero() would give
+                the sparse batch."""
+    k = _check_k(k)
+    c = points_to_dense(x, y)  # (the shape is applied below: beyond it nothing is a candidate, +inf or not)
+    B, N, M = c.shape
+    if shapes is None:
+        shp = np.tile(np.array([N, M], dtype=np.int64), (B, 1))
+    else:
+        shp = np.asarray(shapes.cpu() if hasattr(shapes, "cpu") else shapes).astype(np.int64)
+        if shp.shape != (B, 2):
+            raise ValueError(f"shapes must have shape ({B}, 2), got {shp.shape}")
+    if limit is None:
+        lim = None
+    else:
+        lim = np.asarray(limit.cpu() if hasattr(limit, "cpu") else limit, dtype=np.float64)
+        if lim.shape not in ((), (B,), (B, N)):
+            raise ValueError(f"limit must be a float or have shape ({B},) or ({B}, {N}), got {lim.shape}")
+        lim = np.broadcast_to(lim if lim.ndim != 1 else lim[:, None], (B, N))
+    cols = np.full((B, N, k), -1, dtype=np.int32)
+    vals = np.zeros((B, N, k), dtype=np.float64)
+    counts = np.zeros((B, N), dtype=np.int32)
+    rows = np.zeros(B, dtype=np.int32)
+    far = np.iinfo(np.int64).max
+    for b in range(B):
+        n, m = int(shp[b, 0]), int(shp[b, 1])
+        if not (1 <= n <= N and 1 <= m <= M):
+            continue
+        rows[b] = n
+        cost = c[b, :n, :m]
+        finite = np.isfinite(cost)
+        if lim is None:
+            cand = np.ones((n, m), dtype=bool)
+        else:
+            with np.errstate(invalid="ignore"):
+                cand = ~finite | (cost <= lim[b, :n, None])
+        counts[b, :n] = cand.sum(axis=1)
+        # the order (non-finite first, then cost, then column): a stable sort of the row on -inf / the cost, with what is
+        # no candidate at +inf (no candidate's sort value is +inf)
+        value = np.where(cand, np.where(finite, cost, -np.inf), np.inf)
+        order = np.argsort(value, axis=1, kind="stable")[:, :k]
+        kept = np.arange(order.shape[1])[None, :] < np.minimum(counts[b, :n], k)[:, None]
+        kept_cols = np.sort(np.where(kept, order, far), axis=1)  # ascending columns, what was not kept behind them
+        w = kept_cols.shape[1]
+        here = kept_cols < far
+        at = np.where(here, kept_cols, 0)
+        stored = np.where(finite, cost, np.inf)
+        cols[b, :n, :w] = np.where(here, at, -1)
+        vals[b, :n, :w] = np.where(here, np.take_along_axis(stored, at, axis=1), 0.0)
+    return dict(cols=cols, vals=vals, counts=counts, rows=rows)
+
+
 def _check_points(x, y):
     """dtype / rank / device of x and y; returns (B, N, M, D, on_device, the MISSLAP_DTYPE_* of the coordinates)."""
     if isinstance(x, np.ndarray) and isinstance(y, np.ndarray):
@@ -147,7 +237,7 @@ def _strides(a, rows, D):
 
 
 def auction_solve_points_batch(x, y, problem="min", eps_start=0., max_iter=1000000, fast=None, shapes=None, prices=None,
-                               outside=None, errors="raise", finish=_NO_FINISH):
+                               outside=None, errors="raise", finish=_NO_FINISH, candidates=None):
     """Solve B independent dense problems whose costs are the squared distances between two point sets, one workgroup
     per problem; the cost stack is never stored.
 
@@ -193,6 +283,23 @@ def auction_solve_points_batch(x, y, problem="min", eps_start=0., max_iter=10000
     > 0 where the budget or a stalled iteration ended it.  Afterwards the assignment is optimal within n_b * final_eps.
     Both errors= modes run the status call, then the finish ("raise": then raise_for_status).  numpy point sets are
     uploaded once and the result comes back as numpy arrays.
+
+    candidates: left out (None, the default), the call is the one described so far, in every respect.  candidates=K
+    (1 .. MISSLAP_POINTS_CANDIDATES_MAX_K = 64) takes the list route: points_candidates(x, y, K, shapes, limit=outside)
+    builds per row the (at most) K nearest columns under the row's outside value -- outside is the radius gate; without
+    outside there is no limit -- and auction_solve_ell_batch(cols, vals, rows=rows, n_cols=M, outside=outside,
+    prices=prices, problem="min", eps_start=..., max_iter=..., fast=..., finish=..., errors="status") solves the lists,
+    back to back on the same stream; with device input nothing is waited for.  The result is the ELL call's dict
+    (layout="ell"; outside, prices, fast and finish have that call's rules -- a scalar outside must be finite, prices are
+    (B, P), finish left out is its finish=None) and gains candidates=dict(cols, vals, counts, rows), the builder's output,
+    and truncated, int32 (B,): the rows of problem b with counts > K.  Problem b is bit for bit -- status, sol, prices,
+    outside_prices, meta, reverse -- problem b of that ELL call on points_to_ell(x, y, K, shapes, limit=outside), the
+    definition.  With outside and truncated[b] == 0 its optimum is the optimum of the full points problem: a pair dearer
+    than the row's outside value is never in an optimal assignment.  Where truncated[b] > 0 some in-gate pairs were
+    dropped and the optimum of the lists may be worse: raise K.  A NaN or infinite coordinate gives INFINITE_VALUE for its
+    problem, a bad device shape BAD_SHAPE.  problem="max" with candidates is a ValueError: the lists are the NEAREST
+    columns.  errors="raise" applies raise_for_status behind the solve (the ELL call's texts).  numpy point sets are
+    uploaded once and the result comes back as numpy arrays.
     """
     if errors not in ("raise", "status"):
         raise ValueError(f"errors must be 'raise' or 'status', got {errors!r}")
@@ -202,6 +309,10 @@ def auction_solve_points_batch(x, y, problem="min", eps_start=0., max_iter=10000
     if finish is not _NO_FINISH:
         if not isinstance(finish, str) or finish != "reverse":
             raise ValueError(f"finish must be left out or 'reverse', got {finish!r}")
+    if candidates is not None:
+        return _solve_from_candidates(x, y, candidates, problem, eps_start, max_iter, fast, shapes, prices, outside, errors,
+                                      None if finish is _NO_FINISH else finish)
+    if finish is not _NO_FINISH:
         return _solve_with_finish(x, y, problem, eps_start, max_iter, fast, shapes, prices, outside, errors)
     B, N, M, D, on_device, dtype = _check_points(x, y)
     dev = x.device if on_device else None
@@ -269,6 +380,117 @@ def _solve_with_finish(x, y, problem, eps_start, max_iter, fast, shapes, prices,
         res = {k: v for k, v in res.items() if k not in ("records", "info", "stream", "keep")}
         res = {k: _host(v) if _is_device_tensor(v) else v for k, v in res.items()}
         res.update(meta=meta, reverse=dict(its=_host(its), left=_host(left)))
+    return raise_for_status(res) if errors == "raise" else res
+
+
+def _check_limit(limit, B, N, dev):
+    """The limit of points_candidates: None, a float (any: its sign and finiteness are the kernel's business), or
+    float64 (B,) / (B, N) on the host or (with device input, dev) contiguous on the input's device, under the rules of
+    _check_outside.  Returns (array or tensor or None, limit_ld)."""
+    if limit is None:
+        return None, 0
+    if _is_device_tensor(limit) or isinstance(limit, np.ndarray):
+        try:
+            return _check_outside(limit, B, N, dev, "x / y", "x")
+        except (TypeError, ValueError) as e:
+            raise type(e)(str(e).replace("outside", "limit")) from None
+    if isinstance(limit, (bool, str, bytes)) or not isinstance(limit, (int, float, np.integer, np.floating)):
+        raise TypeError("limit must be a float, a float64 numpy array or a float64 tensor on the device")
+    if dev is not None:
+        import torch
+        return torch.full((B,), float(limit), dtype=torch.float64, device=dev), 0
+    return np.full(B, float(limit), dtype=np.float64), 0
+
+
+def _candidates_launch(x, y, k, d_shp, d_lim, lim_ld):
+    """misslap_points_batch_candidates on device point sets, on the current stream of their device: d_shp / d_lim are
+    device tensors or None.  Returns dict(cols, vals, counts, rows) of device tensors; nothing is waited for."""
+    import torch
+    B, N, M, D, _, dtype = _check_points(x, y)
+    dev = x.device
+    opts = _options(True, x, mat_dtype=dtype)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev)
+        out = dict(cols=_empty((B, N, k), np.int32, dev), vals=_empty((B, N, k), np.float64, dev),
+                   counts=_empty((B, N), np.int32, dev), rows=_empty(B, np.int32, dev))
+    _lib.check(lib.misslap_points_batch_candidates(
+        B, N, M, D, _ptr(x), *_strides(x, N, D), _ptr(y), *_strides(y, M, D), k, _ptr(d_shp), _ptr(d_lim), lim_ld,
+        C.byref(opts), C.c_void_p(int(stream.cuda_stream)), *(_ptr(v) for v in out.values())))
+    return out
+
+
+def _candidates_input(x, y, shapes):
+    """The whole-call checks of the two list calls on x, y and shapes.  Returns (B, N, M, on_device, shapes as the
+    launch takes them: the device tensor, a checked int32 host array or None)."""
+    B, N, M, _, on_device, _ = _check_points(x, y)
+    if _is_device_tensor(shapes):
+        if not on_device:
+            raise TypeError("shapes on the device need x / y on the device")
+        shp = _check_device_shapes(shapes, B, x.device)
+    else:
+        shp = _check_shapes(shapes, B, N, M, "problem")
+    return B, N, M, on_device, shp
+
+
+def _upload_points(x, y):
+    import torch
+    dev = torch.device("cuda", int(os.environ.get(_ENV_DEVICE, 0)))
+    return tuple(torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (x, y))
+
+
+def points_candidates(x, y, k, shapes=None, limit=None):
+    """Per row the (at most) k nearest points of y under the row's limit, as padded candidate lists: a batched, gated
+    nearest-neighbour search on the squared distances of auction_solve_points_batch, and the lists
+    auction_solve_ell_batch reads in place.  The (B, N, M) stack is never stored (misslap_points_batch_candidates: one
+    launch, a wavefront per row).
+
+    x (B, N, D), y (B, M, D) and shapes as auction_solve_points_batch takes them (device tensors of any non-negative
+    strides are read where they lie); k in 1 .. MISSLAP_POINTS_CANDIDATES_MAX_K (64); limit: None, a float, or float64
+    (B,) / (B, N) -- a numpy array or, with device input, a contiguous tensor on the same device.  Its sign and
+    finiteness are judged per row: -0.0 admits a cost of +0.0, a negative value or a NaN no finite cost, +inf every one.
+    Returns dict(cols int32 (B, N, k), vals float64 (B, N, k), counts int32 (B, N), rows int32 (B,)), bit for bit
+    points_to_ell(x, y, k, shapes, limit), whose docstring is the definition: candidates in ascending column order,
+    holes (cols -1, vals 0.0) behind them, counts before truncation, rows[b] = 0 for a bad device shape, a cost that is
+    not finite stored as +inf.  Device tensors give device tensors, ordered on torch.cuda.current_stream(x.device), and
+    nothing is waited for; numpy point sets are uploaded once and the result comes back as numpy arrays."""
+    k = _check_k(k)
+    B, N, _, on_device, shp = _candidates_input(x, y, shapes)
+    lim, lim_ld = _check_limit(limit, B, N, x.device if on_device else None)
+    xd, yd = (x, y) if on_device else _upload_points(x, y)
+    out = _candidates_launch(xd, yd, k, _send(shp, xd.device), _send(lim, xd.device), lim_ld)
+    return out if on_device else {key: _host(v) for key, v in out.items()}
+
+
+def _solve_from_candidates(x, y, candidates, problem, eps_start, max_iter, fast, shapes, prices, outside, errors, finish):
+    """auction_solve_points_batch(candidates=K): the builder with the outside values as its limit, then the ELL call on
+    its lists, both on the current stream of the point sets' device; nothing is waited for with device input."""
+    if problem != "min":
+        raise ValueError(f"candidates needs problem='min', got {problem!r}: the lists hold the NEAREST columns")
+    k = _check_k(candidates)
+    B, N, M, on_device, shp = _candidates_input(x, y, shapes)
+    _eps(eps_start)
+    if not on_device and (_is_device_tensor(prices) or _is_device_tensor(outside)):
+        raise TypeError(f"{'prices' if _is_device_tensor(prices) else 'outside'} on the device need x / y on the device")
+    if outside is not None and not on_device:
+        _check_outside(outside, B, N, None, "x / y", "x")  # (dtype, shape and a finite scalar, ahead of the upload)
+    xd, yd = (x, y) if on_device else _upload_points(x, y)
+    dev = xd.device
+    out_v, out_ld = (None, 0) if outside is None else _check_outside(outside, B, N, dev, "x / y", "x")
+    d_out = _send(out_v, dev)
+    cand = _candidates_launch(xd, yd, k, _send(shp, dev), d_out, out_ld)
+    res = auction_solve_ell_batch(cand["cols"], cand["vals"], rows=cand["rows"], n_cols=M, problem="min",
+                                  eps_start=eps_start, max_iter=max_iter, fast=fast, prices=prices, errors="status",
+                                  outside=d_out, finish=finish)
+    import torch
+    res["candidates"] = cand
+    res["truncated"] = (cand["counts"] > k).sum(dim=1, dtype=torch.int32)
+    if not on_device:
+        meta = batch_meta_to_host(res)  # (waits for the call's stream once)
+        res = {key: v for key, v in res.items() if key not in ("records", "info", "stream", "keep")}
+        res = {key: {q: _host(t) for q, t in v.items()} if key in ("candidates", "reverse") else v for key, v in res.items()}
+        res = {key: _host(v) if _is_device_tensor(v) else v for key, v in res.items()}
+        res["meta"] = meta
     return raise_for_status(res) if errors == "raise" else res
 
 
