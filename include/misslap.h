@@ -47,7 +47,8 @@ extern "C" {
  *      misslap_dense_batch_reverse_finish, misslap_sparse_batch_reverse_finish, misslap_ell_batch_reverse_finish,
  *      misslap_list_batch_finish_workspace_bytes, misslap_solve_points_batch,
  *      misslap_points_batch_workspace_bytes, misslap_points_batch_reverse_finish,
- *      misslap_points_batch_candidates. */
+ *      misslap_points_batch_candidates, misslap_solve_points_batch_whitened,
+ *      misslap_points_batch_candidates_whitened (with MISSLAP_POINTS_BATCH_MAX_WHITEN_COORDS). */
 
 /* misslap_options.mat_dtype: the element type of a dense stack */
 #define MISSLAP_DTYPE_F64 0   /* double */
@@ -1190,6 +1191,51 @@ int misslap_points_batch_candidates(int64_t B, int64_t N, int64_t M, int64_t D,
                                     int64_t K, const int32_t *shapes, const double *limit, int64_t limit_ld,
                                     const misslap_options *opt, void *stream, int32_t *cols, double *vals,
                                     int32_t *counts, int32_t *rows);
+
+/* ---- the points batch with a whitening matrix per row: Mahalanobis costs.  misslap_solve_points_batch_whitened is
+ * misslap_solve_points_batch and misslap_points_batch_candidates_whitened is misslap_points_batch_candidates, each with
+ * the five arguments w, w_stride_b, w_stride_n, w_stride_k, w_stride_l behind the y strides, and every other argument,
+ * output, verdict, mode and workspace (misslap_points_batch_workspace_bytes) is that call's.  w holds a lower-triangular
+ * D x D matrix W[b][i] for every row, of the element type opt->mat_dtype names like x and y: element (k, l) of row i of
+ * problem b lies at w[b * w_stride_b + i * w_stride_n + k * w_stride_k + l * w_stride_l], strides in elements and >= 0
+ * (w_stride_n == 0: one matrix per problem; w_stride_b == w_stride_n == 0: one for the call); the offset of the view's
+ * last element must fit 62 bits.  A host array (the solve without a workspace and without input_on_device) is compact:
+ * strides (N * D * D, D * D, D, 1); a strided w is a device array.  The cost is
+ *     c[i][j] = | W[i] (x[i] - y[j]) |^2:
+ *     d_l = x[i][l] - y[j][l]                                          l = 0 .. D - 1
+ *     z_k = W[k][0] * d_0;  z_k = z_k + W[k][l] * d_l  for l = 1 .. k   k = 0 .. D - 1
+ *     s_0 = z_0 * z_0;  s_k = s_(k-1) + z_k * z_k;  c = s_(D-1)
+ * on everything widened to double (exact): D^2 + 3 D - 1 separately rounded IEEE double operations in this order, nothing
+ * fused or reassociated (sslap_amd.points_to_dense(whiten=) is the definition; csrc/kernels_points_whiten.hpp).  Only the
+ * elements W[b][i][k][l] with l <= k < D and i < n_b are ever read: the upper triangle and the rows beyond the shape may
+ * hold anything.  With a covariance S_i = L L^T (Cholesky) and W_i = L^-1 the cost is the Mahalanobis distance
+ * d^T S_i^-1 d, and outside / limit are in its units: the chi-square gate.  A cost is a sum of squares, never negative
+ * and never -0.0, so a problem with status 0 is bit for bit the dense call on the float64 stack of these costs, as for the
+ * plain call.  A cost is not finite iff an intermediate of the chain is not finite -- a NaN or an infinite coordinate or
+ * matrix element that is read, an overflow, or, from finite inputs, two products that overflow to +inf and -inf, whose
+ * sum is a NaN --: MISSLAP_BATCH_STATUS_INFINITE_VALUE for the solve, a candidate stored as +inf for the builder.
+ * D is 1 .. MISSLAP_POINTS_BATCH_MAX_WHITEN_COORDS (a row's triangle is held in registers); a larger D, w == NULL (the
+ * plain entry points are the calls without a matrix), a negative stride or a host w that is not compact are
+ * MISSLAP_ERR_INVALID before a device is touched.  misslap_points_batch_reverse_finish takes no matrix: the list route
+ * (the whitened candidates, then misslap_solve_ell_batch_outside and misslap_ell_batch_reverse_finish) has a finish. */
+#define MISSLAP_POINTS_BATCH_MAX_WHITEN_COORDS 4
+int misslap_solve_points_batch_whitened(int64_t B, int64_t N, int64_t M, int64_t D,
+                                        const void *x, int64_t x_stride_b, int64_t x_stride_n, int64_t x_stride_d,
+                                        const void *y, int64_t y_stride_b, int64_t y_stride_m, int64_t y_stride_d,
+                                        const void *w, int64_t w_stride_b, int64_t w_stride_n, int64_t w_stride_k,
+                                        int64_t w_stride_l, const int32_t *shapes, int32_t fast, const double *prices_in,
+                                        const misslap_options *opt, void *stream, void *workspace, int64_t workspace_bytes,
+                                        const double *outside, int64_t outside_ld, int32_t *sol, double *prices_out,
+                                        double *outside_prices_out, int32_t out_on_device, int32_t *status,
+                                        int32_t *matching_size, misslap_dense_batch_meta *meta,
+                                        misslap_dense_batch_info *info);
+int misslap_points_batch_candidates_whitened(int64_t B, int64_t N, int64_t M, int64_t D,
+                                             const void *x, int64_t x_stride_b, int64_t x_stride_n, int64_t x_stride_d,
+                                             const void *y, int64_t y_stride_b, int64_t y_stride_m, int64_t y_stride_d,
+                                             const void *w, int64_t w_stride_b, int64_t w_stride_n, int64_t w_stride_k,
+                                             int64_t w_stride_l, int64_t K, const int32_t *shapes, const double *limit,
+                                             int64_t limit_ld, const misslap_options *opt, void *stream, int32_t *cols,
+                                             double *vals, int32_t *counts, int32_t *rows);
 
 /* ---- the matching of many small graphs in one call: the batch form of misslap_hopcroft_karp / sslap.hopcroft_solve
  * (feasibility_.pyx:227-283).  Each graph is matched by ONE workgroup of ONE launch, its state in LDS

@@ -97,6 +97,7 @@ MATCHING_BATCH_MAX_DIM = 2048  # MISSLAP_MATCHING_BATCH_MAX_DIM
 POINTS_BATCH_MAX_DIM = 2048  # MISSLAP_POINTS_BATCH_MAX_DIM
 POINTS_BATCH_MAX_COORDS = 8  # MISSLAP_POINTS_BATCH_MAX_COORDS
 POINTS_CANDIDATES_MAX_K = 64  # MISSLAP_POINTS_CANDIDATES_MAX_K
+POINTS_BATCH_MAX_WHITEN_COORDS = 4  # MISSLAP_POINTS_BATCH_MAX_WHITEN_COORDS
 # MISSLAP_BATCH_STATUS_*: the verdict of one problem of misslap_solve_dense_batch_status
 (BATCH_STATUS_OK, BATCH_STATUS_TOO_FEW_VALUES, BATCH_STATUS_EMPTY_ROW, BATCH_STATUS_INFINITE_VALUE,
  BATCH_STATUS_INFEASIBLE, BATCH_STATUS_PRICE_NOT_FINITE, BATCH_STATUS_PRICE_NEGATIVE, BATCH_STATUS_BAD_SHAPE) = range(8)
@@ -264,6 +265,15 @@ SYMBOLS = {
     # (B, N, M, D, x, x strides, y, y strides, K, shapes, limit, limit_ld, opt, stream, cols, vals, counts, rows)
     "misslap_points_batch_candidates": (C.c_int, [C.c_int64] * 4 + [_VP] + [C.c_int64] * 3 + [_VP] + [C.c_int64] * 3 +
                                         [C.c_int64, _VP, _VP, C.c_int64, C.POINTER(Options), _VP, _VP, _VP, _VP, _VP]),
+    # (the two calls above with w and its four strides behind the y strides)
+    "misslap_solve_points_batch_whitened": (C.c_int, [C.c_int64] * 4 + [_VP] + [C.c_int64] * 3 + [_VP] + [C.c_int64] * 3 +
+                                            [_VP] + [C.c_int64] * 4 +
+                                            [_VP, C.c_int32, _VP, C.POINTER(Options), _VP, _VP, C.c_int64, _VP, C.c_int64,
+                                             _VP, _VP, _VP, C.c_int32, _VP, _VP, _VP, C.POINTER(DenseBatchInfo)]),
+    "misslap_points_batch_candidates_whitened": (C.c_int, [C.c_int64] * 4 + [_VP] + [C.c_int64] * 3 + [_VP] +
+                                                 [C.c_int64] * 3 + [_VP] + [C.c_int64] * 4 +
+                                                 [C.c_int64, _VP, _VP, C.c_int64, C.POINTER(Options), _VP, _VP, _VP, _VP,
+                                                  _VP]),
     "misslap_matching_batch": (C.c_int, [C.c_int64, _VP, _VP, C.POINTER(Options), _VP, _VP, _VP, _VP, C.c_int64, _VP,
                                          C.c_int64, C.c_int32, C.POINTER(MatchingBatchInfo)]),
     "misslap_matching_dense_batch": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, _VP, _VP, C.POINTER(Options), _VP, _VP,

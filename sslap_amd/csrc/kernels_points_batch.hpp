@@ -34,6 +34,13 @@ struct PointsView {
     long long sB, sP, sD;
 };
 
+// the whitening matrices of a call (kernels_points_whiten.hpp): the first element and the element strides of problem,
+// row, matrix row and matrix column; p null: the call has none
+struct WhitenView {
+    const void *p;
+    long long sB, sN, sK, sL;
+};
+
 // per problem, from the check pass
 struct PointsBatchCheck {
     unsigned long long absmax_bits;  // the largest cost (and outside value of a row < n), as bits

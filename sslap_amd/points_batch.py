@@ -13,6 +13,10 @@ definition in numpy.
 under a per-row limit, in the (B, N, K) layout `auction_solve_ell_batch` reads in place -- without storing the stack
 (misslap_points_batch_candidates); `points_to_ell` is its definition in numpy.  With `candidates=K` the points call
 runs that builder and the ELL solve back to back on the caller's stream.
+
+`whiten=W` on the two definitions, the builder and the solve gives every row a lower-triangular matrix and the
+Mahalanobis cost c[b, i, j] = |W[b, i] (x[b, i] - y[b, j])|^2 (misslap_solve_points_batch_whitened,
+misslap_points_batch_candidates_whitened; csrc/kernels_points_whiten.hpp); `points_to_dense(..., whiten=W)` states it.
 """
 import ctypes as C
 import os
@@ -30,6 +34,7 @@ from .ell_batch import auction_solve_ell_batch
 MAX_DIM = _lib.POINTS_BATCH_MAX_DIM
 MAX_COORDS = _lib.POINTS_BATCH_MAX_COORDS
 MAX_CANDIDATES = _lib.POINTS_CANDIDATES_MAX_K
+MAX_WHITEN_COORDS = _lib.POINTS_BATCH_MAX_WHITEN_COORDS
 
 _STATUS_TEXT = {
     _lib.BATCH_STATUS_BAD_SHAPE: "shape ({n}, {m}) outside 1 .. {N} x 1 .. {M}",
@@ -43,7 +48,71 @@ _STATUS_TEXT = {
 }
 
 
-def points_to_dense(x, y, shapes=None):
+def _np(a):
+    return np.asarray(a.cpu().numpy() if hasattr(a, "cpu") else a)
+
+
+def _lower_triangles(whiten, x, shp):
+    """whiten (B, N, D, D) of x's dtype -> float64 (B, N, D, D) holding W[b, i, k, l] for l <= k and i < shp[b, 0] (all
+    rows without shp) and 0.0 everywhere else: exactly the elements the definition reads, and no other."""
+    w = _np(whiten)
+    B, N, D = x.shape
+    if w.ndim != 4:
+        raise ValueError(f"whiten must have 4 dimensions (B, N, D, D), got {w.ndim}")
+    if w.dtype != x.dtype:
+        raise ValueError(f"whiten must have the dtype of x and y, {x.dtype.name}, got {w.dtype.name}")
+    if w.shape != (B, N, D, D):
+        raise ValueError(f"whiten must have shape {(B, N, D, D)}, got {w.shape}")
+    if D > MAX_WHITEN_COORDS:
+        raise ValueError(f"points of {D} coordinates with whiten: at most {MAX_WHITEN_COORDS} "
+                         f"(MISSLAP_POINTS_BATCH_MAX_WHITEN_COORDS)")
+    rows = np.full(B, N) if shp is None else np.clip(np.asarray(shp)[:, 0].astype(np.int64), 0, N)
+    keep = (np.arange(N)[None, :] < rows[:, None])[:, :, None, None] & np.tril(np.ones((D, D), dtype=bool))[None, None]
+    out = np.zeros((B, N, D, D), dtype=np.float64)
+    np.copyto(out, w, where=keep, casting="same_kind")
+    return out
+
+
+def _points_xy(x, y):
+    """x and y of the two definitions as numpy arrays, checked."""
+    x, y = _np(x), _np(y)
+    if x.ndim != 3 or y.ndim != 3:
+        raise ValueError(f"x and y must have 3 dimensions (B, N, D) and (B, M, D), got {x.ndim} and {y.ndim}")
+    if x.dtype != y.dtype or x.dtype not in (np.float32, np.float64):
+        raise ValueError(f"x and y must both be float32 or both float64, got {x.dtype.name} and {y.dtype.name}")
+    if x.shape[0] != y.shape[0] or x.shape[2] != y.shape[2] or x.shape[2] < 1:
+        raise ValueError(f"x {x.shape} and y {y.shape} must share B and D >= 1")
+    return x, y
+
+
+def _points_costs(x, y, whiten, shp):
+    """The float64 (B, N, M) costs of points_to_dense before the shapes are applied (shp: only which rows of whiten are
+    read).  x and y: from _points_xy."""
+    D = x.shape[2]
+    xw, yw = x.astype(np.float64), y.astype(np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        if whiten is None:
+            d = xw[:, :, None, 0] - yw[:, None, :, 0]
+            c = d * d
+            for k in range(1, D):
+                d = xw[:, :, None, k] - yw[:, None, :, k]
+                q = d * d
+                c = c + q
+        else:
+            ww = _lower_triangles(whiten, x, shp)
+            d = [xw[:, :, None, l] - yw[:, None, :, l] for l in range(D)]
+            c = None
+            for k in range(D):
+                z = ww[:, :, None, k, 0] * d[0]
+                for l in range(1, k + 1):
+                    q = ww[:, :, None, k, l] * d[l]
+                    z = z + q
+                q = z * z
+                c = q if k == 0 else c + q
+    return np.ascontiguousarray(c)
+
+
+def points_to_dense(x, y, shapes=None, whiten=None):
     """x (B, N, D) and y (B, M, D), float32 or float64, numpy arrays or tensors -> the float64 (B, N, M) cost stack of
     squared distances: the definition of auction_solve_points_batch.
 
@@ -60,28 +129,28 @@ def points_to_dense(x, y, shapes=None):
     Problem b of auction_solve_points_batch(x, y, shapes=shapes, ...) with status 0 is bit for bit problem b of
     auction_solve_batch(points_to_dense(x, y, shapes), shapes=shapes, ..., errors="status", cardinality_check=False),
     or, with outside, of auction_solve_batch(points_to_dense(x, y, shapes), shapes=shapes, outside=outside, ...,
-    errors="status")."""
-    x = np.asarray(x.cpu().numpy() if hasattr(x, "cpu") else x)
-    y = np.asarray(y.cpu().numpy() if hasattr(y, "cpu") else y)
-    if x.ndim != 3 or y.ndim != 3:
-        raise ValueError(f"x and y must have 3 dimensions (B, N, D) and (B, M, D), got {x.ndim} and {y.ndim}")
-    if x.dtype != y.dtype or x.dtype not in (np.float32, np.float64):
-        raise ValueError(f"x and y must both be float32 or both float64, got {x.dtype.name} and {y.dtype.name}")
-    if x.shape[0] != y.shape[0] or x.shape[2] != y.shape[2] or x.shape[2] < 1:
-        raise ValueError(f"x {x.shape} and y {y.shape} must share B and D >= 1")
-    B, N, D = x.shape
-    M = y.shape[1]
-    xw, yw = x.astype(np.float64), y.astype(np.float64)
-    with np.errstate(invalid="ignore", over="ignore"):
-        d = xw[:, :, None, 0] - yw[:, None, :, 0]
-        c = d * d
-        for k in range(1, D):
-            d = xw[:, :, None, k] - yw[:, None, :, k]
-            q = d * d
-            c = c + q
-    c = np.ascontiguousarray(c)
+    errors="status").
+
+    whiten: None (the default: everything above), or W of shape (B, N, D, D) and the dtype of x and y, a numpy array or
+    a tensor, with D <= MISSLAP_POINTS_BATCH_MAX_WHITEN_COORDS (4): W[b, i] is a lower-triangular matrix for row i and
+    the cost is the Mahalanobis form c[b, i, j] = |W[b, i] (x[b, i] - y[b, j])|^2.  With everything widened to float64:
+
+        d_l    = xw[b, i, l] - yw[b, j, l]                  l = 0 .. D - 1
+        z_k    = W[k][0] * d_0;  z_k = z_k + W[k][l] * d_l   for l = 1 .. k, in this order;  k = 0 .. D - 1
+        s_0    = z_0 * z_0;      s_k = s_(k-1) + z_k * z_k
+        c[b, i, j] = s_(D-1)
+
+    D^2 + 3 D - 1 separately rounded float64 operations, nothing fused or reassociated.  Only W[b, i, k, l] with l <= k
+    and i < n_b is ever read: the upper triangle and the rows beyond the shape may hold anything, NaN included.  A cost
+    is a sum of squares, never negative and never -0.0, and it is not finite iff an intermediate of the chain is not
+    finite: a NaN or infinite coordinate or matrix element that is read, an overflow, or -- unlike the plain chain, and
+    from finite inputs -- two products that overflow to +inf and -inf, whose sum is a NaN.  With S = L L^T the innovation
+    covariance of a track and W = L^-1, c is the Mahalanobis distance d^T S^-1 d."""
+    x, y = _points_xy(x, y)
+    shp = None if shapes is None else np.asarray(shapes.cpu() if hasattr(shapes, "cpu") else shapes)
+    c = _points_costs(x, y, whiten, shp)
+    B = c.shape[0]
     if shapes is not None:
-        shp = np.asarray(shapes.cpu() if hasattr(shapes, "cpu") else shapes)
         for b in range(B):
             n, m = (max(int(v), 0) for v in shp[b])
             c[b, n:, :] = np.inf
@@ -113,7 +182,7 @@ def _check_k(k):
     return int(k)
 
 
-def points_to_ell(x, y, k, shapes=None, limit=None):
+def points_to_ell(x, y, k, shapes=None, limit=None, whiten=None):
     """x (B, N, D) and y (B, M, D) as points_to_dense takes them, k in 1 .. 64 -> dict(cols int32 (B, N, k), vals float64
     (B, N, k), counts int32 (B, N), rows int32 (B,)): per row the (at most) k nearest columns under the row's limit, as
     padded candidate lists in the layout auction_solve_ell_batch reads.  The definition of points_candidates and of
@@ -136,16 +205,21 @@ def points_to_ell(x, y, k, shapes=None, limit=None):
                 by column.
     Order       the kept candidates are stored in ascending column order in slots 0 .., and every later slot holds
                 cols = -1, vals = 0.0.  In column order an untruncated row is exactly the row gate.nonzero() would give
-                the sparse batch."""
+                the sparse batch.
+    whiten      None, or W (B, N, D, D) as points_to_dense takes it: c is then points_to_dense(x, y, shapes, whiten=W),
+                the limit is in the units of that cost, and everything above holds as it stands."""
     k = _check_k(k)
-    c = points_to_dense(x, y)  # (the shape is applied below: beyond it nothing is a candidate, +inf or not)
-    B, N, M = c.shape
-    if shapes is None:
-        shp = np.tile(np.array([N, M], dtype=np.int64), (B, 1))
-    else:
+    x, y = _points_xy(x, y)
+    shp = None
+    if shapes is not None:
         shp = np.asarray(shapes.cpu() if hasattr(shapes, "cpu") else shapes).astype(np.int64)
-        if shp.shape != (B, 2):
-            raise ValueError(f"shapes must have shape ({B}, 2), got {shp.shape}")
+        if shp.shape != (x.shape[0], 2):
+            raise ValueError(f"shapes must have shape ({x.shape[0]}, 2), got {shp.shape}")
+    # (the shape is applied below: beyond it nothing is a candidate, +inf or not)
+    c = _points_costs(x, y, whiten, shp)
+    B, N, M = c.shape
+    if shp is None:
+        shp = np.tile(np.array([N, M], dtype=np.int64), (B, 1))
     if limit is None:
         lim = None
     else:
@@ -226,6 +300,42 @@ def _check_points(x, y):
     return B, N, M, D, on_device, _lib.DTYPE_F32 if names[0] == "float32" else _lib.DTYPE_F64
 
 
+def _check_whiten(whiten, x, B, N, D, on_device):
+    """whiten of the GPU calls against the checked x: a numpy array with numpy point sets, a tensor on x's device with
+    device point sets; shape (B, N, D, D), x's dtype, D within the whitened cap, strides >= 0."""
+    if on_device:
+        if not _is_device_tensor(whiten):
+            raise TypeError("whiten must be a tensor on the device of x / y (x and y are device tensors)")
+        name, ndim = str(whiten.dtype).split(".")[-1], whiten.dim()
+        xname = str(x.dtype).split(".")[-1]
+    else:
+        if not isinstance(whiten, np.ndarray):
+            raise TypeError("whiten must be a numpy array (x and y are numpy arrays)")
+        name, ndim, xname = whiten.dtype.name, whiten.ndim, x.dtype.name
+    if ndim != 4:
+        raise ValueError(f"whiten must have 4 dimensions (B, N, D, D), got {ndim}")
+    if name != xname:
+        raise ValueError(f"whiten must have the dtype of x and y, {xname}, got {name}")
+    if D > MAX_WHITEN_COORDS:
+        raise ValueError(f"points of {D} coordinates with whiten: at most {MAX_WHITEN_COORDS} "
+                         f"(MISSLAP_POINTS_BATCH_MAX_WHITEN_COORDS)")
+    shape = tuple(int(v) for v in whiten.shape)
+    if shape != (B, N, D, D):
+        raise ValueError(f"whiten must have shape {(B, N, D, D)}, got {shape}")
+    if on_device:
+        if whiten.device != x.device:
+            raise ValueError(f"whiten is on {whiten.device}, x on {x.device}")
+        if min(int(s) for s in whiten.stride()) < 0:
+            raise ValueError(f"whiten has strides {tuple(whiten.stride())}: a stride must be >= 0")
+
+
+def _whiten_strides(w, N, D):
+    """The element strides of the matrices as the library reads them: a tensor's own, a numpy array's compact ones."""
+    if isinstance(w, np.ndarray):
+        return N * D * D, D * D, D, 1
+    return tuple(int(s) for s in w.stride())
+
+
 _NO_FINISH = type("_NoFinish", (), {"__repr__": lambda self: "<no finish>"})()  # finish= was left out
 
 
@@ -237,7 +347,7 @@ def _strides(a, rows, D):
 
 
 def auction_solve_points_batch(x, y, problem="min", eps_start=0., max_iter=1000000, fast=None, shapes=None, prices=None,
-                               outside=None, errors="raise", finish=_NO_FINISH, candidates=None):
+                               outside=None, errors="raise", finish=_NO_FINISH, candidates=None, whiten=None):
     """Solve B independent dense problems whose costs are the squared distances between two point sets, one workgroup
     per problem; the cost stack is never stored.
 
@@ -300,6 +410,21 @@ def auction_solve_points_batch(x, y, problem="min", eps_start=0., max_iter=10000
     problem, a bad device shape BAD_SHAPE.  problem="max" with candidates is a ValueError: the lists are the NEAREST
     columns.  errors="raise" applies raise_for_status behind the solve (the ELL call's texts).  numpy point sets are
     uploaded once and the result comes back as numpy arrays.
+
+    whiten: left out (None, the default), the call is the one described so far, in every respect.  whiten=W gives every
+    row its own metric: W has shape (B, N, D, D) and the dtype of x and y, with D <= MISSLAP_POINTS_BATCH_MAX_WHITEN_COORDS
+    (4), W[b, i] is a lower-triangular matrix and the cost is c[b, i, j] = |W[b, i] (x[b, i] - y[b, j])|^2, the chain of
+    points_to_dense(x, y, shapes, whiten=W), which replaces points_to_dense(x, y, shapes) in every statement above
+    (misslap_solve_points_batch_whitened).  For a Kalman tracker with innovation covariances S: L = cholesky(S),
+    W = solve_triangular(L, eye(D), upper=False) gives the Mahalanobis distance d^T S^-1 d, and outside is its chi-square
+    gate.  W is a numpy array with numpy point sets and a tensor on the same device with device point sets; a device view
+    of any non-negative strides is read where it lies and never written -- cov[1:B + 1, 1:N + 1, :D, :D] of a larger
+    buffer, W.expand(B, N, D, D) of one matrix per problem (B, 1, D, D) or of one for the call (1, 1, D, D).  Only the
+    lower triangle of the rows i < n_b is read; the rest may hold anything.  INFINITE_VALUE then also covers a NaN or an
+    infinite matrix element that is read, and finite inputs whose products overflow to +inf and -inf (their sum is a NaN).
+    candidates=K with whiten runs the whitened builder (points_candidates(..., whiten=W)) and the ELL call unchanged, so
+    prices= and finish="reverse" are available on that route.  finish="reverse" with whiten and without candidates is a
+    ValueError: the points finish kernel takes no matrix.
     """
     if errors not in ("raise", "status"):
         raise ValueError(f"errors must be 'raise' or 'status', got {errors!r}")
@@ -311,10 +436,15 @@ def auction_solve_points_batch(x, y, problem="min", eps_start=0., max_iter=10000
             raise ValueError(f"finish must be left out or 'reverse', got {finish!r}")
     if candidates is not None:
         return _solve_from_candidates(x, y, candidates, problem, eps_start, max_iter, fast, shapes, prices, outside, errors,
-                                      None if finish is _NO_FINISH else finish)
+                                      None if finish is _NO_FINISH else finish, whiten)
+    if finish is not _NO_FINISH and whiten is not None:
+        raise ValueError("finish='reverse' with whiten needs candidates=K: the points finish takes no matrix, the list "
+                         "route (candidates=K, whiten=W, finish='reverse') runs the ELL finish on the whitened lists")
     if finish is not _NO_FINISH:
         return _solve_with_finish(x, y, problem, eps_start, max_iter, fast, shapes, prices, outside, errors)
     B, N, M, D, on_device, dtype = _check_points(x, y)
+    if whiten is not None:
+        _check_whiten(whiten, x, B, N, D, on_device)
     dev = x.device if on_device else None
     if dev is not None and _is_device_tensor(shapes):
         shp = _check_device_shapes(shapes, B, dev)
@@ -336,11 +466,19 @@ def auction_solve_points_batch(x, y, problem="min", eps_start=0., max_iter=10000
     call = _StatusCall(lib, opts, B, N, M, None if outside is None else N, dev, "misslap_points_batch_workspace_bytes",
                        (B, N, M, 0 if p is None else 1, 0 if outside is None else 1))
     outs = call.outs if outside is not None else (*call.outs[:2], None, *call.outs[2:])
-    _lib.check(lib.misslap_solve_points_batch(
-        B, N, M, D, _ptr(xc), *_strides(xc, N, D), _ptr(yc), *_strides(yc, M, D), _ptr(d_shp), 1 if fast else 0, _ptr(d_p),
-        *call.way, _ptr(d_out), out_ld, *outs))
+    if whiten is None:
+        _lib.check(lib.misslap_solve_points_batch(
+            B, N, M, D, _ptr(xc), *_strides(xc, N, D), _ptr(yc), *_strides(yc, M, D), _ptr(d_shp), 1 if fast else 0,
+            _ptr(d_p), *call.way, _ptr(d_out), out_ld, *outs))
+    else:
+        wc = whiten if on_device else np.ascontiguousarray(whiten)
+        _lib.check(lib.misslap_solve_points_batch_whitened(
+            B, N, M, D, _ptr(xc), *_strides(xc, N, D), _ptr(yc), *_strides(yc, M, D), _ptr(wc), *_whiten_strides(wc, N, D),
+            _ptr(d_shp), 1 if fast else 0, _ptr(d_p), *call.way, _ptr(d_out), out_ld, *outs))
     own = {} if outside is None else dict(outside=d_out)
-    res = call.result((x, y, d_shp, d_p, d_out), shapes=d_shp, stack=(N, M), layout="points", **own)
+    if whiten is not None:
+        own["whitened"] = True
+    res = call.result((x, y, whiten, d_shp, d_p, d_out), shapes=d_shp, stack=(N, M), layout="points", **own)
     return raise_for_status(res) if errors == "raise" else res
 
 
@@ -402,9 +540,9 @@ def _check_limit(limit, B, N, dev):
     return np.full(B, float(limit), dtype=np.float64), 0
 
 
-def _candidates_launch(x, y, k, d_shp, d_lim, lim_ld):
-    """misslap_points_batch_candidates on device point sets, on the current stream of their device: d_shp / d_lim are
-    device tensors or None.  Returns dict(cols, vals, counts, rows) of device tensors; nothing is waited for."""
+def _candidates_launch(x, y, k, d_shp, d_lim, lim_ld, w=None):
+    """misslap_points_batch_candidates (w, a checked device tensor: misslap_points_batch_candidates_whitened) on device
+    point sets, on the current stream of their device: d_shp / d_lim are device tensors or None.  Returns dict(cols, vals, counts, rows) of device tensors; nothing is waited for."""
     import torch
     B, N, M, D, _, dtype = _check_points(x, y)
     dev = x.device
@@ -414,16 +552,24 @@ def _candidates_launch(x, y, k, d_shp, d_lim, lim_ld):
         stream = torch.cuda.current_stream(dev)
         out = dict(cols=_empty((B, N, k), np.int32, dev), vals=_empty((B, N, k), np.float64, dev),
                    counts=_empty((B, N), np.int32, dev), rows=_empty(B, np.int32, dev))
-    _lib.check(lib.misslap_points_batch_candidates(
-        B, N, M, D, _ptr(x), *_strides(x, N, D), _ptr(y), *_strides(y, M, D), k, _ptr(d_shp), _ptr(d_lim), lim_ld,
-        C.byref(opts), C.c_void_p(int(stream.cuda_stream)), *(_ptr(v) for v in out.values())))
+    tail = (k, _ptr(d_shp), _ptr(d_lim), lim_ld, C.byref(opts), C.c_void_p(int(stream.cuda_stream)),
+            *(_ptr(v) for v in out.values()))
+    if w is None:
+        _lib.check(lib.misslap_points_batch_candidates(
+            B, N, M, D, _ptr(x), *_strides(x, N, D), _ptr(y), *_strides(y, M, D), *tail))
+    else:
+        _lib.check(lib.misslap_points_batch_candidates_whitened(
+            B, N, M, D, _ptr(x), *_strides(x, N, D), _ptr(y), *_strides(y, M, D), _ptr(w), *_whiten_strides(w, N, D),
+            *tail))
     return out
 
 
-def _candidates_input(x, y, shapes):
-    """The whole-call checks of the two list calls on x, y and shapes.  Returns (B, N, M, on_device, shapes as the
-    launch takes them: the device tensor, a checked int32 host array or None)."""
-    B, N, M, _, on_device, _ = _check_points(x, y)
+def _candidates_input(x, y, shapes, whiten=None):
+    """The whole-call checks of the two list calls on x, y, shapes and whiten.  Returns (B, N, M, on_device, shapes as
+    the launch takes them: the device tensor, a checked int32 host array or None)."""
+    B, N, M, D, on_device, _ = _check_points(x, y)
+    if whiten is not None:
+        _check_whiten(whiten, x, B, N, D, on_device)
     if _is_device_tensor(shapes):
         if not on_device:
             raise TypeError("shapes on the device need x / y on the device")
@@ -433,13 +579,14 @@ def _candidates_input(x, y, shapes):
     return B, N, M, on_device, shp
 
 
-def _upload_points(x, y):
+def _upload_points(x, y, whiten=None):
+    """numpy x, y (and whiten) -> (x, y, whiten or None) on the device"""
     import torch
     dev = torch.device("cuda", int(os.environ.get(_ENV_DEVICE, 0)))
-    return tuple(torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (x, y))
+    return tuple(None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (x, y, whiten))
 
 
-def points_candidates(x, y, k, shapes=None, limit=None):
+def points_candidates(x, y, k, shapes=None, limit=None, whiten=None):
     """Per row the (at most) k nearest points of y under the row's limit, as padded candidate lists: a batched, gated
     nearest-neighbour search on the squared distances of auction_solve_points_batch, and the lists
     auction_solve_ell_batch reads in place.  The (B, N, M) stack is never stored (misslap_points_batch_candidates: one
@@ -453,32 +600,36 @@ def points_candidates(x, y, k, shapes=None, limit=None):
     points_to_ell(x, y, k, shapes, limit), whose docstring is the definition: candidates in ascending column order,
     holes (cols -1, vals 0.0) behind them, counts before truncation, rows[b] = 0 for a bad device shape, a cost that is
     not finite stored as +inf.  Device tensors give device tensors, ordered on torch.cuda.current_stream(x.device), and
-    nothing is waited for; numpy point sets are uploaded once and the result comes back as numpy arrays."""
+    nothing is waited for; numpy point sets are uploaded once and the result comes back as numpy arrays.
+    whiten: None, or W (B, N, D, D) as auction_solve_points_batch takes it (a numpy array or a device view, matching
+    x / y; D <= 4): the costs are those of points_to_dense(x, y, shapes, whiten=W), the limit is in their units, and the
+    result is bit for bit points_to_ell(x, y, k, shapes, limit, whiten=W) (misslap_points_batch_candidates_whitened)."""
     k = _check_k(k)
-    B, N, _, on_device, shp = _candidates_input(x, y, shapes)
+    B, N, _, on_device, shp = _candidates_input(x, y, shapes, whiten)
     lim, lim_ld = _check_limit(limit, B, N, x.device if on_device else None)
-    xd, yd = (x, y) if on_device else _upload_points(x, y)
-    out = _candidates_launch(xd, yd, k, _send(shp, xd.device), _send(lim, xd.device), lim_ld)
+    xd, yd, wd = (x, y, whiten) if on_device else _upload_points(x, y, whiten)
+    out = _candidates_launch(xd, yd, k, _send(shp, xd.device), _send(lim, xd.device), lim_ld, wd)
     return out if on_device else {key: _host(v) for key, v in out.items()}
 
 
-def _solve_from_candidates(x, y, candidates, problem, eps_start, max_iter, fast, shapes, prices, outside, errors, finish):
+def _solve_from_candidates(x, y, candidates, problem, eps_start, max_iter, fast, shapes, prices, outside, errors, finish,
+                           whiten=None):
     """auction_solve_points_batch(candidates=K): the builder with the outside values as its limit, then the ELL call on
     its lists, both on the current stream of the point sets' device; nothing is waited for with device input."""
     if problem != "min":
         raise ValueError(f"candidates needs problem='min', got {problem!r}: the lists hold the NEAREST columns")
     k = _check_k(candidates)
-    B, N, M, on_device, shp = _candidates_input(x, y, shapes)
+    B, N, M, on_device, shp = _candidates_input(x, y, shapes, whiten)
     _eps(eps_start)
     if not on_device and (_is_device_tensor(prices) or _is_device_tensor(outside)):
         raise TypeError(f"{'prices' if _is_device_tensor(prices) else 'outside'} on the device need x / y on the device")
     if outside is not None and not on_device:
         _check_outside(outside, B, N, None, "x / y", "x")  # (dtype, shape and a finite scalar, ahead of the upload)
-    xd, yd = (x, y) if on_device else _upload_points(x, y)
+    xd, yd, wd = (x, y, whiten) if on_device else _upload_points(x, y, whiten)
     dev = xd.device
     out_v, out_ld = (None, 0) if outside is None else _check_outside(outside, B, N, dev, "x / y", "x")
     d_out = _send(out_v, dev)
-    cand = _candidates_launch(xd, yd, k, _send(shp, dev), d_out, out_ld)
+    cand = _candidates_launch(xd, yd, k, _send(shp, dev), d_out, out_ld, wd)
     res = auction_solve_ell_batch(cand["cols"], cand["vals"], rows=cand["rows"], n_cols=M, problem="min",
                                   eps_start=eps_start, max_iter=max_iter, fast=fast, prices=prices, errors="status",
                                   outside=d_out, finish=finish)
@@ -508,6 +659,9 @@ def _status_error(res, b, code, n, m, card):
             row = int(np.flatnonzero(~(o >= 0))[0])
         value = float(o[row])
     also = " or an outside value is +inf" if "outside_prices" in res else ""
+    if res.get("whitened") and code == _lib.BATCH_STATUS_INFINITE_VALUE:
+        return ValueError(f"problem {b}: a cost |W_i (x_i - y_j)|^2 is not finite (a NaN or an infinite coordinate or "
+                          f"element of the whitening matrix's lower triangle, or an overflow in the chain){also}")
     text = _STATUS_TEXT[code].format(n=n, m=m, N=N, M=M, card=card, row=row, value=value, also=also)
     return ValueError(f"problem {b}: {text}")
 
