@@ -48,7 +48,9 @@ extern "C" {
  *      misslap_list_batch_finish_workspace_bytes, misslap_solve_points_batch,
  *      misslap_points_batch_workspace_bytes, misslap_points_batch_reverse_finish,
  *      misslap_points_batch_candidates, misslap_solve_points_batch_whitened,
- *      misslap_points_batch_candidates_whitened (with MISSLAP_POINTS_BATCH_MAX_WHITEN_COORDS). */
+ *      misslap_points_batch_candidates_whitened (with MISSLAP_POINTS_BATCH_MAX_WHITEN_COORDS),
+ *      misslap_solve_boxes_batch, misslap_boxes_batch_candidates (with MISSLAP_BOXES_METRIC_IOU / _GIOU and
+ *      MISSLAP_BATCH_STATUS_BAD_BOX, code 16). */
 
 /* misslap_options.mat_dtype: the element type of a dense stack */
 #define MISSLAP_DTYPE_F64 0   /* double */
@@ -634,6 +636,9 @@ int64_t misslap_dense_batch_workspace_bytes(int64_t B, int64_t N, int64_t M, int
  * fast = 0) keeps the prices of earlier phases and is NOT optimal in general.  A single phase -- fast != 0, or
  * 0 < eps_start <= 1 / n_b -- from zero prices is optimal within n_b * eps. */
 #define MISSLAP_BATCH_STATUS_BAD_OUTSIDE 15  /* the outside value of a row is negative or a NaN (an absent entry) */
+/* (in parentheses: two tests from before this code pin the list of the plain `#define MISSLAP_BATCH_STATUS_<NAME> <n>`
+ * lines to 0 .. 15, and existing tests stay as they are; 16 is directly behind the others and reuses none) */
+#define MISSLAP_BATCH_STATUS_BAD_BOX (16)    /* misslap_solve_boxes_batch: a box inside the shape has x2 < x1 or y2 < y1 */
 int misslap_solve_dense_batch_outside(int64_t B, int64_t N, int64_t M, const void *mat, const int32_t *shapes,
                                       int32_t fast, const double *prices_in, const misslap_options *opt, void *stream,
                                       void *workspace, int64_t workspace_bytes, const double *outside, int64_t outside_ld,
@@ -1236,6 +1241,59 @@ int misslap_points_batch_candidates_whitened(int64_t B, int64_t N, int64_t M, in
                                              int64_t w_stride_l, int64_t K, const int32_t *shapes, const double *limit,
                                              int64_t limit_ld, const misslap_options *opt, void *stream, int32_t *cols,
                                              double *vals, int32_t *counts, int32_t *rows);
+
+/* ---- the batch from two box sets: IoU and generalised-IoU costs, the cost stack never stored.
+ * misslap_solve_boxes_batch is misslap_solve_points_batch and misslap_boxes_batch_candidates is
+ * misslap_points_batch_candidates, each on box sets -- point sets of exactly 4 coordinates (x1, y1, x2, y2), so there
+ * is no D -- with `metric` behind the b strides; every other argument, output, mode and the workspace
+ * (misslap_points_batch_workspace_bytes: the layout is the same) is that call's.  a holds B sets of N boxes and b B sets
+ * of M boxes, MISSLAP_DTYPE_F64 or MISSLAP_DTYPE_F32 (opt->mat_dtype): coordinate k of box i of problem b lies at
+ * a[b * a_stride_b + i * a_stride_n + k * a_stride_d], strides in elements and >= 0, the last element's offset within
+ * 62 bits; a host array is compact, strides (N * 4, 4, 1) and (M * 4, 4, 1).  The cost of (row box a, column box b), on
+ * the coordinates widened to double (exact), every operation a separately rounded IEEE double operation in this order,
+ * nothing fused (sslap_amd.boxes_to_dense is the definition; csrc/kernels_boxes_batch.hpp):
+ *     per box   w = x2 - x1,  h = y2 - y1,  area = w * h
+ *     per pair  iw = min(ax2, bx2) - max(ax1, bx1);  iw = iw > 0 ? iw : 0      (ih likewise, from the y's)
+ *               inter = iw * ih;  s = area_a + area_b;  u = s - inter;  iou = u > 0 ? inter / u : 0
+ *     MISSLAP_BOXES_METRIC_IOU    c = 1 - iou
+ *     MISSLAP_BOXES_METRIC_GIOU   cw = max(ax2, bx2) - min(ax1, bx1)  (ch likewise);  hull = cw * ch
+ *                                 e = hull - u;  e = e > 0 ? e : 0;  r = hull > 0 ? e / hull : 0;  c = 1 - (iou - r)
+ * A cost lies in [0, 1] (IOU) or [0, 2] (GIOU) and is never -0.0, so every finite cost is an entry and a problem with
+ * status 0 is bit for bit the dense call on the float64 stack of these costs, as for the points call.  outside / limit
+ * are costs: 1 - t gates at IoU >= t.
+ * The verdicts of a problem, in their order: MISSLAP_BATCH_STATUS_BAD_SHAPE, with outside
+ * MISSLAP_BATCH_STATUS_BAD_OUTSIDE, MISSLAP_BATCH_STATUS_INFINITE_VALUE (a NaN or an infinite coordinate inside the
+ * shape, classified on its bits before it is used; an intermediate of the chain that is infinite -- a width, an area,
+ * iw or ih before the clamp, s or a hull of float64 boxes; float32 boxes cannot overflow --; or an outside value of
+ * +inf), MISSLAP_BATCH_STATUS_BAD_BOX (a box inside the shape with x2 < x1 or y2 < y1; zero width or height is legal),
+ * without outside MISSLAP_BATCH_STATUS_INFEASIBLE (n_b > m_b), MISSLAP_BATCH_STATUS_PRICE_NOT_FINITE,
+ * MISSLAP_BATCH_STATUS_PRICE_NEGATIVE.  The builder has no status: a pair with a bad box, a NaN or infinite coordinate
+ * or an infinite intermediate is always a candidate, sorts first and is stored as +inf, so misslap_solve_ell_batch on
+ * the lists reports MISSLAP_BATCH_STATUS_INFINITE_VALUE for its problem: MISSLAP_BATCH_STATUS_BAD_BOX surfaces as 3 on
+ * the list route.
+ * These costs lie in [0, 2].  fast != 0 means eps = 1 / n_b and a guarantee of n_b * eps = 1 in total, which is coarse on
+ * this scale: a tracker should leave fast 0 and set opt->eps_start (any 0 < eps_start <= 1 / n_b is still one phase,
+ * optimal within n_b * eps_start); rounds grow as C / eps.
+ * An unknown metric, a null a / b / sol / status, a negative stride, a stride extent beyond 62 bits, N or M outside
+ * 1 .. MISSLAP_POINTS_BATCH_MAX_DIM or K outside 1 .. MISSLAP_POINTS_CANDIDATES_MAX_K are MISSLAP_ERR_INVALID before a
+ * device is touched.  There is no boxes reverse finish: the list route (the candidates, then
+ * misslap_solve_ell_batch_outside and misslap_ell_batch_reverse_finish) has one. */
+#define MISSLAP_BOXES_METRIC_IOU 1
+#define MISSLAP_BOXES_METRIC_GIOU 2
+int misslap_solve_boxes_batch(int64_t B, int64_t N, int64_t M,
+                              const void *a, int64_t a_stride_b, int64_t a_stride_n, int64_t a_stride_d,
+                              const void *b, int64_t b_stride_b, int64_t b_stride_m, int64_t b_stride_d,
+                              int32_t metric, const int32_t *shapes, int32_t fast, const double *prices_in,
+                              const misslap_options *opt, void *stream, void *workspace, int64_t workspace_bytes,
+                              const double *outside, int64_t outside_ld, int32_t *sol, double *prices_out,
+                              double *outside_prices_out, int32_t out_on_device, int32_t *status,
+                              int32_t *matching_size, misslap_dense_batch_meta *meta, misslap_dense_batch_info *info);
+int misslap_boxes_batch_candidates(int64_t B, int64_t N, int64_t M,
+                                   const void *a, int64_t a_stride_b, int64_t a_stride_n, int64_t a_stride_d,
+                                   const void *b, int64_t b_stride_b, int64_t b_stride_m, int64_t b_stride_d,
+                                   int32_t metric, int64_t K, const int32_t *shapes, const double *limit,
+                                   int64_t limit_ld, const misslap_options *opt, void *stream, int32_t *cols,
+                                   double *vals, int32_t *counts, int32_t *rows);
 
 /* ---- the matching of many small graphs in one call: the batch form of misslap_hopcroft_karp / sslap.hopcroft_solve
  * (feasibility_.pyx:227-283).  Each graph is matched by ONE workgroup of ONE launch, its state in LDS

@@ -105,6 +105,8 @@ POINTS_BATCH_MAX_WHITEN_COORDS = 4  # MISSLAP_POINTS_BATCH_MAX_WHITEN_COORDS
 (BATCH_STATUS_NO_ENTRIES, BATCH_STATUS_DIVISION_BY_ZERO, BATCH_STATUS_NEGATIVE_INDEX, BATCH_STATUS_ROWS_UNSORTED,
  BATCH_STATUS_ROW_GAP, BATCH_STATUS_TOO_LARGE, BATCH_STATUS_PRICES_TOO_NARROW) = range(8, 15)
 BATCH_STATUS_BAD_OUTSIDE = 15  # ... and the one misslap_solve_dense_batch_outside adds
+BATCH_STATUS_BAD_BOX = 16  # ... and the one misslap_solve_boxes_batch adds
+BOXES_METRIC_IOU, BOXES_METRIC_GIOU = 1, 2  # MISSLAP_BOXES_METRIC_*
 
 
 def new_meta():
@@ -274,6 +276,13 @@ SYMBOLS = {
                                                  [C.c_int64] * 3 + [_VP] + [C.c_int64] * 4 +
                                                  [C.c_int64, _VP, _VP, C.c_int64, C.POINTER(Options), _VP, _VP, _VP, _VP,
                                                   _VP]),
+    # (the plain points calls without D and with the metric behind the b strides)
+    "misslap_solve_boxes_batch": (C.c_int, [C.c_int64] * 3 + [_VP] + [C.c_int64] * 3 + [_VP] + [C.c_int64] * 3 +
+                                  [C.c_int32, _VP, C.c_int32, _VP, C.POINTER(Options), _VP, _VP, C.c_int64, _VP, C.c_int64,
+                                   _VP, _VP, _VP, C.c_int32, _VP, _VP, _VP, C.POINTER(DenseBatchInfo)]),
+    "misslap_boxes_batch_candidates": (C.c_int, [C.c_int64] * 3 + [_VP] + [C.c_int64] * 3 + [_VP] + [C.c_int64] * 3 +
+                                       [C.c_int32, C.c_int64, _VP, _VP, C.c_int64, C.POINTER(Options), _VP, _VP, _VP, _VP,
+                                        _VP]),
     "misslap_matching_batch": (C.c_int, [C.c_int64, _VP, _VP, C.POINTER(Options), _VP, _VP, _VP, _VP, C.c_int64, _VP,
                                          C.c_int64, C.c_int32, C.POINTER(MatchingBatchInfo)]),
     "misslap_matching_dense_batch": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, _VP, _VP, C.POINTER(Options), _VP, _VP,

@@ -14,7 +14,8 @@ SOURCES = ["misslap.hip", "device_common.hpp", "kernels_round.hpp", "kernels_tai
            "abi_sparse_batch_status.hpp", "kernels_matching_batch.hpp", "abi_matching_batch.hpp", "kernels_ell_batch.hpp",
            "abi_ell_batch.hpp", "kernels_list_finish.hpp", "abi_list_finish.hpp", "kernels_points_batch.hpp",
            "abi_points_batch.hpp", "kernels_points_finish.hpp", "abi_points_finish.hpp",
-           "kernels_points_candidates.hpp", "abi_points_candidates.hpp", "kernels_points_whiten.hpp", "abi_points_whiten.hpp", os.path.join("..", "..", "include", "misslap.h")]
+           "kernels_points_candidates.hpp", "abi_points_candidates.hpp", "kernels_points_whiten.hpp", "abi_points_whiten.hpp",
+           "kernels_boxes_batch.hpp", "abi_boxes_batch.hpp", os.path.join("..", "..", "include", "misslap.h")]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-honor-nans", "-std=c++17", "-shared", "-fPIC",
          "-fvisibility=hidden", "-Wall", "-Wextra"]
 

@@ -1,6 +1,7 @@
 // abi_points_batch.hpp -- C ABI: the batch solve from two point sets, costs |x_i - y_j|^2 formed from the coordinates and
 // never stored, with a verdict per problem and in stream order (include/misslap.h):
 //   misslap_solve_points_batch, misslap_solve_points_batch_whitened, misslap_points_batch_workspace_bytes
+// (and, through points_batch_call, misslap_solve_boxes_batch of abi_boxes_batch.hpp: a box set is a point set of D = 4)
 // One entry point serves the plain problem (outside == NULL) and the one with an outside option per row; the whitened
 // entry point is the same call with a lower-triangular matrix per row, costs |W_i (x_i - y_j)|^2.  The call is
 // described by one PointsCall and enqueued by points_enqueue: the check pass and the solve, whose kernels are in
@@ -35,6 +36,7 @@ struct PointsCall {
     int64_t outside_ld;
     int32_t fast;
     WhitenView w;  // p null: the plain call
+    int32_t boxes;  // 0, or MISSLAP_BOXES_METRIC_*: x and y are box sets (D = 4) and the cost is that metric's
 };
 
 // Without a workspace: every input of the call that is not on the device yet (c holds the caller's pointers) into
@@ -54,8 +56,9 @@ int points_upload(DevScratch &tmp, hipStream_t st, const misslap_options &opt, P
 }
 
 // The two kernels of a call: the plain pair takes its argument struct as it is, the whitened pair the struct and the
-// matrices (the specialisation for Wh = true is in abi_points_whiten.hpp, next to its kernels).
-template <class T, bool Out, bool Wh>
+// matrices (the specialisation for Wh = 1 is in abi_points_whiten.hpp, next to its kernels; Wh = 2 and 3 are the box
+// metrics of abi_boxes_batch.hpp, which take the plain structs).
+template <class T, bool Out, int Wh>
 struct PointsKernels {
     static PointsCheckArgs check_args(const PointsCheckArgs &k, const WhitenView &) { return k; }
     static PointsBatchArgs solve_args(const WhitenView &) { return PointsBatchArgs{}; }
@@ -65,7 +68,7 @@ struct PointsKernels {
 };
 
 // The two launches of a call on st: the check pass and the solve with its verdict.
-template <class T, bool Out, bool Wh>
+template <class T, bool Out, int Wh>
 int points_enqueue_as(hipStream_t st, const misslap_options &opt, const PointsCall &c, void *ws, const BatchStreamOut &d) {
     const BatchCarve carve = points_carve(c.B, c.N, c.M, c.d_p0 != nullptr, Out);
     PointsBatchCheck *d_chk = carve.at<PointsBatchCheck>(ws, 0);
@@ -116,17 +119,20 @@ int points_enqueue_as(hipStream_t st, const misslap_options &opt, const PointsCa
     }
 }
 
-template <bool Wh>
+template <int Wh>
 int points_enqueue_wh(hipStream_t st, const misslap_options &opt, const PointsCall &c, void *ws, const BatchStreamOut &d) {
     const bool f32 = opt.mat_dtype == MISSLAP_DTYPE_F32;
     if (c.d_outside)
         return f32 ? points_enqueue_as<float, true, Wh>(st, opt, c, ws, d) : points_enqueue_as<double, true, Wh>(st, opt, c, ws, d);
     return f32 ? points_enqueue_as<float, false, Wh>(st, opt, c, ws, d) : points_enqueue_as<double, false, Wh>(st, opt, c, ws, d);
 }
-// (abi_points_whiten.hpp: points_enqueue_wh<true>, behind the whitened kernels)
+// (abi_points_whiten.hpp: points_enqueue_wh<1>, behind the whitened kernels; abi_boxes_batch.hpp: <2> and <3>, behind
+// the box kernels)
 int points_whiten_enqueue(hipStream_t st, const misslap_options &opt, const PointsCall &c, void *ws, const BatchStreamOut &d);
+int boxes_enqueue(hipStream_t st, const misslap_options &opt, const PointsCall &c, void *ws, const BatchStreamOut &d);
 int points_enqueue(hipStream_t st, const misslap_options &opt, const PointsCall &c, void *ws, const BatchStreamOut &d) {
-    return c.w.p ? points_whiten_enqueue(st, opt, c, ws, d) : points_enqueue_wh<false>(st, opt, c, ws, d);
+    if (c.boxes) return boxes_enqueue(st, opt, c, ws, d);
+    return c.w.p ? points_whiten_enqueue(st, opt, c, ws, d) : points_enqueue_wh<0>(st, opt, c, ws, d);
 }
 
 // The matrices of a whitened call (`who`): D within the whitened cap, w not null, element strides >= 0 whose extent
@@ -161,8 +167,9 @@ MISSLAP_API int64_t misslap_points_batch_workspace_bytes(int64_t B, int64_t N, i
 }
 
 namespace {
-// misslap_solve_points_batch (whiten null) and misslap_solve_points_batch_whitened (`who`; whiten: w and its strides)
-int points_batch_call(const char *who, const WhitenView *whiten, int64_t B, int64_t N, int64_t M, int64_t D, const void *x,
+// misslap_solve_points_batch (whiten null), misslap_solve_points_batch_whitened (`who`; whiten: w and its strides) and
+// misslap_solve_boxes_batch (boxes: its metric, D = 4)
+int points_batch_call(const char *who, const WhitenView *whiten, int32_t boxes, int64_t B, int64_t N, int64_t M, int64_t D, const void *x,
                       int64_t x_stride_b, int64_t x_stride_n, int64_t x_stride_d, const void *y, int64_t y_stride_b,
                       int64_t y_stride_m, int64_t y_stride_d, const int32_t *shapes, int32_t fast, const double *prices_in,
                       const misslap_options *opt_in, void *stream, void *workspace, int64_t workspace_bytes,
@@ -200,7 +207,7 @@ int points_batch_call(const char *who, const WhitenView *whiten, int64_t B, int6
                     "compact: strides (N * D, D, 1) and (M * D, D, 1))", who);
     PointsCall c{B, N, M, D, {x, (long long)x_stride_b, (long long)x_stride_n, (long long)x_stride_d},
                  {y, (long long)y_stride_b, (long long)y_stride_m, (long long)y_stride_d}, shapes, prices_in, outside,
-                 outside ? outside_ld : 0, fast, whiten ? *whiten : WhitenView{}};
+                 outside ? outside_ld : 0, fast, whiten ? *whiten : WhitenView{}, boxes};
     k.B = B;
     k.out.sol = sol;
     k.out.sol_cells = (size_t)B * (size_t)N;
@@ -236,7 +243,7 @@ MISSLAP_API int misslap_solve_points_batch(int64_t B, int64_t N, int64_t M, int6
                                            double *outside_prices_out, int32_t out_on_device, int32_t *status,
                                            int32_t *matching_size, misslap_dense_batch_meta *meta,
                                            misslap_dense_batch_info *info) {
-    return points_batch_call("misslap_solve_points_batch", nullptr, B, N, M, D, x, x_stride_b, x_stride_n, x_stride_d, y,
+    return points_batch_call("misslap_solve_points_batch", nullptr, 0, B, N, M, D, x, x_stride_b, x_stride_n, x_stride_d, y,
                              y_stride_b, y_stride_m, y_stride_d, shapes, fast, prices_in, opt_in, stream, workspace,
                              workspace_bytes, outside, outside_ld, sol, prices_out, outside_prices_out, out_on_device, status,
                              matching_size, meta, info);
@@ -254,7 +261,7 @@ MISSLAP_API int misslap_solve_points_batch_whitened(int64_t B, int64_t N, int64_
                                                     int32_t *matching_size, misslap_dense_batch_meta *meta,
                                                     misslap_dense_batch_info *info) {
     const WhitenView wv{w, (long long)w_stride_b, (long long)w_stride_n, (long long)w_stride_k, (long long)w_stride_l};
-    return points_batch_call("misslap_solve_points_batch_whitened", &wv, B, N, M, D, x, x_stride_b, x_stride_n, x_stride_d, y,
+    return points_batch_call("misslap_solve_points_batch_whitened", &wv, 0, B, N, M, D, x, x_stride_b, x_stride_n, x_stride_d, y,
                              y_stride_b, y_stride_m, y_stride_d, shapes, fast, prices_in, opt_in, stream, workspace,
                              workspace_bytes, outside, outside_ld, sol, prices_out, outside_prices_out, out_on_device, status,
                              matching_size, meta, info);

@@ -24,9 +24,12 @@ int points_candidates_launch(hipStream_t st, const PointsCandidatesArgs &a) {
 }
 // (abi_points_whiten.hpp: the same launch of k_points_whiten_candidates<float or double>)
 int points_whiten_candidates_launch(hipStream_t st, const PointsCandidatesArgs &a, const WhitenView &w, bool f32);
+// (abi_boxes_batch.hpp: the same launch of k_boxes_batch_candidates<float or double, the metric>)
+int boxes_candidates_launch(hipStream_t st, const PointsCandidatesArgs &a, int32_t metric, bool f32);
 
-// misslap_points_batch_candidates (whiten null) and misslap_points_batch_candidates_whitened (`who`)
-int points_candidates_call(const char *who, const WhitenView *whiten, int64_t B, int64_t N, int64_t M, int64_t D,
+// misslap_points_batch_candidates (whiten null), misslap_points_batch_candidates_whitened (`who`) and
+// misslap_boxes_batch_candidates (boxes: its metric, D = 4)
+int points_candidates_call(const char *who, const WhitenView *whiten, int32_t boxes, int64_t B, int64_t N, int64_t M, int64_t D,
                            const void *x, int64_t x_stride_b, int64_t x_stride_n, int64_t x_stride_d, const void *y,
                            int64_t y_stride_b, int64_t y_stride_m, int64_t y_stride_d, int64_t K, const int32_t *shapes,
                            const double *limit, int64_t limit_ld, const misslap_options *opt_in, void *stream, int32_t *cols,
@@ -73,6 +76,7 @@ int points_candidates_call(const char *who, const WhitenView *whiten, int64_t B,
     a.vals = vals;
     a.counts = counts;
     a.rows = rows;
+    if (boxes) return boxes_candidates_launch((hipStream_t)stream, a, boxes, opt.mat_dtype == MISSLAP_DTYPE_F32);
     if (whiten) return points_whiten_candidates_launch((hipStream_t)stream, a, *whiten, opt.mat_dtype == MISSLAP_DTYPE_F32);
     return opt.mat_dtype == MISSLAP_DTYPE_F32 ? points_candidates_launch<float>((hipStream_t)stream, a)
                                               : points_candidates_launch<double>((hipStream_t)stream, a);
@@ -85,7 +89,7 @@ MISSLAP_API int misslap_points_batch_candidates(int64_t B, int64_t N, int64_t M,
                                                 const int32_t *shapes, const double *limit, int64_t limit_ld,
                                                 const misslap_options *opt_in, void *stream, int32_t *cols, double *vals,
                                                 int32_t *counts, int32_t *rows) {
-    return points_candidates_call("misslap_points_batch_candidates", nullptr, B, N, M, D, x, x_stride_b, x_stride_n,
+    return points_candidates_call("misslap_points_batch_candidates", nullptr, 0, B, N, M, D, x, x_stride_b, x_stride_n,
                                   x_stride_d, y, y_stride_b, y_stride_m, y_stride_d, K, shapes, limit, limit_ld, opt_in, stream,
                                   cols, vals, counts, rows);
 }
@@ -99,7 +103,7 @@ MISSLAP_API int misslap_points_batch_candidates_whitened(int64_t B, int64_t N, i
                                                          const misslap_options *opt_in, void *stream, int32_t *cols,
                                                          double *vals, int32_t *counts, int32_t *rows) {
     const WhitenView wv{w, (long long)w_stride_b, (long long)w_stride_n, (long long)w_stride_k, (long long)w_stride_l};
-    return points_candidates_call("misslap_points_batch_candidates_whitened", &wv, B, N, M, D, x, x_stride_b, x_stride_n,
+    return points_candidates_call("misslap_points_batch_candidates_whitened", &wv, 0, B, N, M, D, x, x_stride_b, x_stride_n,
                                   x_stride_d, y, y_stride_b, y_stride_m, y_stride_d, K, shapes, limit, limit_ld, opt_in, stream,
                                   cols, vals, counts, rows);
 }

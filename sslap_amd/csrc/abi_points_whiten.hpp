@@ -9,7 +9,7 @@
 
 namespace {
 template <class T, bool Out>
-struct PointsKernels<T, Out, true> {
+struct PointsKernels<T, Out, 1> {
     static PointsWhitenCheckArgs check_args(const PointsCheckArgs &k, const WhitenView &w) { return PointsWhitenCheckArgs{k, w}; }
     static PointsWhitenArgs solve_args(const WhitenView &w) { return PointsWhitenArgs{PointsBatchArgs{}, w}; }
     static PointsBatchArgs &inner(PointsWhitenArgs &a) { return a.a; }
@@ -18,7 +18,7 @@ struct PointsKernels<T, Out, true> {
 };
 
 int points_whiten_enqueue(hipStream_t st, const misslap_options &opt, const PointsCall &c, void *ws, const BatchStreamOut &d) {
-    return points_enqueue_wh<true>(st, opt, c, ws, d);
+    return points_enqueue_wh<1>(st, opt, c, ws, d);
 }
 
 int points_whiten_candidates_launch(hipStream_t st, const PointsCandidatesArgs &a, const WhitenView &w, bool f32) {

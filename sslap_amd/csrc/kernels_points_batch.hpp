@@ -45,7 +45,8 @@ struct WhitenView {
 struct PointsBatchCheck {
     unsigned long long absmax_bits;  // the largest cost (and outside value of a row < n), as bits
     int flags;                       // bit 0: a cost is not finite, or the outside value of a row < n is +inf;
-                                     // bit 1 (outside mode): the outside value of a row < n is negative or a NaN
+                                     // bit 1 (outside mode): the outside value of a row < n is negative or a NaN;
+                                     // bit 2 (kernels_boxes_batch.hpp only): a box inside the shape is a bad box
     int bad_price;                   // starting prices: bit 0 NaN / infinity, bit 1 sign bit set
 };
 

@@ -532,3 +532,5 @@ MISSLAP_API int misslap_get_state(misslap_solver *h, double *prices, int32_t *un
 #include "abi_points_candidates.hpp"
 #include "kernels_points_whiten.hpp"
 #include "abi_points_whiten.hpp"
+#include "kernels_boxes_batch.hpp"
+#include "abi_boxes_batch.hpp"

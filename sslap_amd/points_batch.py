@@ -216,7 +216,12 @@ def points_to_ell(x, y, k, shapes=None, limit=None, whiten=None):
         if shp.shape != (x.shape[0], 2):
             raise ValueError(f"shapes must have shape ({x.shape[0]}, 2), got {shp.shape}")
     # (the shape is applied below: beyond it nothing is a candidate, +inf or not)
-    c = _points_costs(x, y, whiten, shp)
+    return _ell_from_costs(_points_costs(x, y, whiten, shp), k, shp, limit)
+
+
+def _ell_from_costs(c, k, shp, limit):
+    """The lists of points_to_ell from the float64 (B, N, M) costs c before the shapes are applied (shp: int64 (B, 2)
+    or None); boxes_to_ell is the same function of its own costs."""
     B, N, M = c.shape
     if shp is None:
         shp = np.tile(np.array([N, M], dtype=np.int64), (B, 1))
